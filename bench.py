@@ -13,8 +13,12 @@ job time (= the slowest rank), so the spread between draws is visible.
 
 Prints ONE JSON line (rank 0).  `roofline` prices the solve kernel against the packed-fp32 vector peak (the roof that
 binds: the path is neither HBM- nor MFMA-shaped) with the ALGORITHMIC flop count of SURVEY.md section
-8(d); `cpu_baseline` times the fp64 CPU oracle on a bounded sample of the same workload on the host cores, on one core and
-on all of them (a reported baseline, not the target; the reference's own CasADi + OSQP path cannot run offline).
+8(d), from this run's own timed steps and the committed counter summaries under profiles/.
+
+A plain run sets up, warms up, times `--steps` steps and prints the line; `--dump-outputs DIR` writes what the last timed step
+returned (see dump_outputs).  `--full` adds what takes runs of its own: `cpu_baseline` times the fp64 CPU oracle on a bounded
+sample of the same workload on the host cores, on one core and on all of them (a reported baseline, not the target; the
+reference's own CasADi + OSQP path cannot run offline), and `breakdown` the secondary figures of gait_breakdown.
 """
 import argparse
 import json
@@ -35,6 +39,7 @@ TRAFFIC_FILE = "r03f_hbm_traffic.json"     # PMC passes of the current kernel (p
 SQ_FILE = "r03f_pmc.txt"                     # SQ counter passes of the same kernel and workload (tools/pmc_run.sh)
 FLOPS_FILE = "r03f_flops.json"               # floating-point instruction mix of the same kernel and workload (tools/pmc_flops.sh)
 PEAK_VALU_ISSUE = 1024 * 2.4e9 / 4          # wave-instructions/s: 1024 SIMDs, one wave64 vector instruction per 4 cycles (an fp64 FMA: 8)
+DUMP_LIMIT = 64 << 20                        # bytes written by --dump-outputs, all arrays together
 
 
 def algorithmic_flops(N, K):
@@ -57,6 +62,23 @@ def _host_cores():
     except (OSError, ValueError):
         pass
     return min(cores, 64)
+
+
+def dump_outputs(out, path, limit=DUMP_LIMIT):
+    """What one solve_batch returned (`out`), as .npy files under `path`: the forces `u` [B, N, 12] and residuals `res` [B, 2] in
+    float32, `status` and `iters` (ADMM iterations + 1000 x polish steps) in float64.  When all of it is larger than `limit`
+    bytes, the same fixed, seeded sample of QPs is kept from every array and its sorted batch indices go to `rows.npy`."""
+    arrays = {k: out[k].cpu().numpy().astype(dt) for k, dt in (("u", np.float32), ("res", np.float32), ("status", np.float64),
+                                                                   ("iters", np.float64))}
+    B = len(arrays["u"])
+    row_bytes = sum(a[0].nbytes for a in arrays.values()) + 8
+    if B * row_bytes > limit:
+        rows = np.sort(np.random.default_rng(0).choice(B, limit // row_bytes, replace=False))
+        arrays = {k: a[rows] for k, a in arrays.items()}
+        arrays["rows"] = rows.astype(np.float64)
+    os.makedirs(path, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), np.ascontiguousarray(a))
 
 
 def cpu_baseline(batch, cfg_kw, sample):
@@ -248,10 +270,14 @@ def main():
     ap.add_argument("--same-shards", action="store_true", help="N > 1, weak mode: every rank solves the configured batch (seed 20250809) instead of its own draw")
     ap.add_argument("--global-batch", type=int, default=0, help="strong scaling: this many QPs in total (config-4 distribution), sharded contiguously over the ranks")
     ap.add_argument("--first-block", type=int, default=0, help="MpcQpConfig.first_block (0: the engine's default; tools/first_block_sweep.sh)")
+    ap.add_argument("--full", action="store_true", help="also the CPU baseline and the secondary figures (breakdown), which take runs of their own")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step returned to DIR/<name>.npy (rank 0's shard)")
     ap.add_argument("--cpu-sample", type=int, default=1024)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-breakdown", action="store_true", help="skip the secondary per-gait / all-stance figures")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-breakdown", action="store_true", help="with --full: skip the secondary per-gait / all-stance figures")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -345,6 +371,8 @@ def main():
         rank_ms = [float(v) for v in allr[:, 1]]
         total_qps = int(allr[:, 2].sum())
         solved_all = float(allr[:, 3].sum()) / total_qps
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(out, args.dump_outputs)
 
     status = out["status"].cpu().numpy()
     iters = out["iters"].cpu().numpy()
@@ -424,7 +452,7 @@ def main():
                                  "algorithmic_bytes_per_qp": algorithmic_bytes(N), "note": "non-binding roof (SURVEY 8d)"},
                          "valu_issue": issue},
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             cb = cpu_baseline(batch, dict(N=N, delta=delta, rho=solver.cfg.rho, sigma=solver.cfg.sigma, relax=solver.cfg.relax,
                                           max_iter=int(solver.cfg.max_iter), check_every=int(solver.cfg.check_every),
                                           eps_abs=solver.cfg.eps_abs, eps_rel=solver.cfg.eps_rel,
@@ -432,7 +460,7 @@ def main():
                               min(args.cpu_sample, B))
             if cb:
                 line["cpu_baseline"] = cb
-        if world == 1 and not args.no_breakdown:
+        if args.full and world == 1 and not args.no_breakdown:
             line["breakdown"] = gait_breakdown(solver, N, delta, B, precision=args.precision)
         print(json.dumps(line), flush=True)
     if dist:

@@ -1,6 +1,7 @@
 import os
 import subprocess
 import sys
+import tempfile
 
 import numpy as np
 import pytest
@@ -15,6 +16,7 @@ for p in (REPO, os.path.join(REPO, "oracle")):
 
 _BENCH2 = {"proc": None, "result": None}
 _BENCH1N = {"proc": None, "result": None}
+_BENCH1P = {"proc": None, "result": None, "dir": None}
 
 
 def pytest_configure(config):
@@ -43,36 +45,40 @@ def pytest_configure(config):
                 [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
                  "--master-port", "29518", os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--allgather",
                  "--no-cpu-baseline", "--no-breakdown"], cwd=REPO, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, env=env1)
+            # ... and a plain one-GPU run, the command line the benchmark is measured with, writing its last step's results
+            _BENCH1P["dir"] = tempfile.mkdtemp(prefix="mpcqp_bench_dump_")
+            _BENCH1P["proc"] = subprocess.Popen(
+                [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--dump-outputs", _BENCH1P["dir"]],
+                cwd=REPO, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
+
+
+def _child_result(slot, what):
+    if slot["result"] is None:
+        p = slot["proc"]
+        if p is None:
+            pytest.skip(f"{what} was not started (no GPU at configure time)")
+        try:
+            out, err = p.communicate(timeout=600)
+        except subprocess.TimeoutExpired:
+            p.kill()
+            out, err = p.communicate()
+        slot["result"] = (p.returncode, out, err)
+    return slot["result"]
+
+
+def bench_plain_result():
+    """(returncode, stdout, stderr, dump directory) of the plain one-GPU bench child started in pytest_configure."""
+    return _child_result(_BENCH1P, "plain bench child") + (_BENCH1P["dir"],)
 
 
 def bench2_result():
     """(returncode, stdout, stderr) of the two-rank bench child started in pytest_configure."""
-    if _BENCH2["result"] is None:
-        p = _BENCH2["proc"]
-        if p is None:
-            pytest.skip("two-rank bench child was not started (no GPU at configure time)")
-        try:
-            out, err = p.communicate(timeout=600)
-        except subprocess.TimeoutExpired:
-            p.kill()
-            out, err = p.communicate()
-        _BENCH2["result"] = (p.returncode, out, err)
-    return _BENCH2["result"]
+    return _child_result(_BENCH2, "two-rank bench child")
 
 
 def bench1_nccl_result():
     """(returncode, stdout, stderr) of the one-rank RCCL bench child started in pytest_configure."""
-    if _BENCH1N["result"] is None:
-        p = _BENCH1N["proc"]
-        if p is None:
-            pytest.skip("one-rank RCCL bench child was not started (no GPU at configure time)")
-        try:
-            out, err = p.communicate(timeout=600)
-        except subprocess.TimeoutExpired:
-            p.kill()
-            out, err = p.communicate()
-        _BENCH1N["result"] = (p.returncode, out, err)
-    return _BENCH1N["result"]
+    return _child_result(_BENCH1N, "one-rank RCCL bench child")
 
 
 def _have_gpu():

@@ -8,8 +8,11 @@ run), plus the multi-rank bench rehearsal.
   on the GRFs, as everywhere); the ADMM-only mode (OSQP termination test, no polish) in fp32-tile and fp64 arithmetic.
 * `bench.py --gpus 2` as a fresh torch.distributed.run child with the gloo backend (started by conftest.py before this
   process touches the GPU): one JSON line, n_gpus = 2, whole-job value = 2 ranks x per-rank batches.
+* the plain `bench.py --gpus 1` run with `--dump-outputs` (also a child started by conftest.py): its line and its last step's results.
 """
 import json
+import os
+import shutil
 
 import numpy as np
 import pytest
@@ -17,7 +20,7 @@ import torch
 
 import mpcqp
 import qp_spec as S
-from conftest import rel_err, bench2_result
+from conftest import rel_err, bench2_result, bench_plain_result
 from test_gpu_parity import gpu_solve, solved
 
 pytestmark = pytest.mark.gpu
@@ -162,6 +165,37 @@ def test_two_rank_bench_rehearsal():
     assert k["n_gpus"] == 2 and k["scaling"] == "strong" and k["config"]["global_batch"] == 6001 and k["config"]["batch_per_gpu"] == 3001
     assert abs(k["value"] - 6001 * 3 / (k["ms_per_step"] * 3e-3)) <= 1e-6 * k["value"]
     assert k["config"]["solved_fraction"] >= 0.999 and len(k["rank_kernel_ms"]["per_rank"]) == 2
+
+
+def test_plain_bench_line_and_dumped_outputs():
+    """The plain run the benchmark is measured with (`bench.py --gpus 1 --steps 3 --warmup 1 --dump-outputs DIR`): one JSON line with
+    the headline fields and none of the `--full` figures, and the results of its last timed step, as dumped, equal to a solve of the
+    same seeded batch with the same settings in this process."""
+    rc, stdout, stderr, d = bench_plain_result()
+    try:
+        assert rc == 0, stderr[-2000:]
+        lines = [ln for ln in stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, stdout[-2000:]
+        j = json.loads(lines[0])
+        assert j["n_gpus"] == 1 and j["steps"] == 3 and j["warmup"] == 1 and j["unit"] == "QP solves/s" and j["higher_is_better"] is True
+        assert j["dtype"] == "f32 tiles + f64 residuals" and j["ms_per_step"] > 0
+        assert abs(j["value"] - 4096 * 3 / (j["ms_per_step"] * 3e-3)) <= 1e-6 * j["value"]
+        assert "roofline" in j and "cpu_baseline" not in j and "breakdown" not in j
+        got = {k: np.load(os.path.join(d, k + ".npy")) for k in ("u", "res", "status", "iters")}
+        assert sorted(os.listdir(d)) == ["iters.npy", "res.npy", "status.npy", "u.npy"]
+        assert got["u"].dtype == np.float32 and got["u"].shape == (4096, 10, 12)
+        assert got["res"].dtype == np.float32 and got["res"].shape == (4096, 2)
+        assert got["status"].dtype == np.float64 and got["iters"].dtype == np.float64 and got["status"].shape == (4096,)
+        b = mpcqp.synth.make_batch(4096, 10, 0.03, 20250809, ("trot", "pronk", "amble", "gallop"), (0.3, 0.5, 0.7, 1.0))
+        sol = mpcqp.MPCBatch(N=10, delta=0.03, io_dtype="f32", precision="mixed", flags=mpcqp.FLAG_POLISH | mpcqp.FLAG_NO_TIMING, first_block=0)
+        dev = sol.upload(b)
+        want = sol.solve_batch(dev["x0"], dev["r"], dev["contact"], dev["xdes"], dev["mu"])
+        torch.cuda.synchronize()
+        assert solved(got["status"]).mean() >= 0.999
+        for k in ("u", "res", "status", "iters"):
+            assert np.array_equal(got[k], want[k].cpu().numpy()), k
+    finally:
+        shutil.rmtree(d, ignore_errors=True)
 
 
 def test_one_rank_rccl_bench_rehearsal():

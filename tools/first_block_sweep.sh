@@ -6,6 +6,6 @@ R=$GRAFT_REPO_ROOT
 OUT=$R/gpurun_out/$TAG
 mkdir -p $OUT
 for V in 50 60 70 80 100; do
-  python3 $R/bench.py --first-block $V --no-cpu-baseline --steps 30 > $OUT/first_block_$V.json 2> $OUT/first_block_$V.log || exit 1
+  python3 $R/bench.py --full --first-block $V --no-cpu-baseline --steps 30 > $OUT/first_block_$V.json 2> $OUT/first_block_$V.log || exit 1
   echo "first_block $V done"
 done
