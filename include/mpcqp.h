@@ -27,7 +27,8 @@
 extern "C" {
 #endif
 
-#define MPCQP_VERSION 0x00010300 /* 1.3.0: MpcQpConfig grew by accel / accel_restart (Anderson-accelerated ADMM blocks); 1.2.0: round-1 kernels retired
+#define MPCQP_VERSION 0x00010301 /* 1.3.1: iters[] unambiguous at 1000 ADMM iterations and more (MPCQP_ITERS), max_iter < 1e6;
+                                      1.3.0: MpcQpConfig grew by accel / accel_restart (Anderson-accelerated ADMM blocks); 1.2.0: round-1 kernels retired
                                       (two engines: wrench-space, stage-wise); 1.1.0: horizons up to 64, tuning fields */
 
 /* return codes */
@@ -108,7 +109,7 @@ typedef struct MpcQpConfig {
   double rho;           /* ADMM penalty on the constraint rows */
   double sigma;         /* ADMM proximal weight on u */
   double relax;         /* over-relaxation in (0,2) */
-  int32_t max_iter;     /* ADMM iteration cap K */
+  int32_t max_iter;     /* ADMM iteration cap K, 1 <= K < MPCQP_ITERS_WIDE (mpcqp_create rejects larger caps) */
   int32_t check_every;  /* ADMM block length between polish attempts (iterations); default 100, tuned for N = 10 --
                            scale both with N / 10 for other horizons (200 / 800 at N = 20), as the Python host layer does.
                            With MPCQP_FLAG_POLISH a cold solve's first block is 0.6 check_every long (0.7 without `accel`; most QPs have
@@ -145,6 +146,20 @@ typedef struct MpcQpConfig {
   int32_t reserved0;
 } MpcQpConfig;
 
+/*
+ * iters[b] packs the ADMM iterations `admm` and the polish refinement steps `polish` of one QP:
+ *   admm + 1000 * polish                                  when admm < 1000 and polish < 1000 (the usual case: values < 1e6)
+ *   MPCQP_ITERS_WIDE * (min(polish, 2145) + 1) + admm      otherwise (values >= 1e6; the clamp keeps the result in int32)
+ * Decoding: v < 1e6 -> (v % 1000, v / 1000); else (v % 1e6, v / 1e6 - 1).  admm <= max_iter < MPCQP_ITERS_WIDE, so the two
+ * ranges cannot overlap.  (Python: mpcqp.split_iters.)
+ */
+#define MPCQP_ITERS_WIDE 1000000
+#define MPCQP_ITERS_POLISH_MAX 2145
+#define MPCQP_ITERS(admm, polish)                                                                                          \
+  (((admm) < 1000 && (polish) < 1000)                                                                                      \
+       ? (admm) + 1000 * (polish)                                                                                          \
+       : MPCQP_ITERS_WIDE * (((polish) < MPCQP_ITERS_POLISH_MAX ? (polish) : MPCQP_ITERS_POLISH_MAX) + 1) + (admm))
+
 typedef struct mpcqp_engine* mpcqp_handle;
 
 uint32_t mpcqp_version(void);
@@ -180,7 +195,7 @@ int mpcqp_reserve(mpcqp_handle h, int64_t B);
  *   u_out   T  [B,N,12]      sol.value(U) (src/mpc.py:267-268), stage-major, legs FL,FR,HL,HR x (fx,fy,fz)
  *   X_out   T  [B,N+1,13]    sol.value(X) (src/mpc.py:265-266); may be NULL
  *   status  i32[B]           MPCQP_STATUS_*
- *   iters   i32[B]           ADMM iterations used (+ 1000 * polish refinement steps)
+ *   iters   i32[B]           ADMM iterations and polish refinement steps used, packed by MPCQP_ITERS below
  *   res     f32[B,2]         final primal / dual residual (inf-norm); may be NULL
  * `stream` is a hipStream_t (product) or ignored (oracle).  Asynchronous on the stream; the caller owns all
  * buffers; no allocation happens after mpcqp_reserve(h, B) / the first call at a given B.

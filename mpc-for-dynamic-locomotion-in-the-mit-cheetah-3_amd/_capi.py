@@ -23,6 +23,23 @@ DTYPE_F32, DTYPE_F64 = 0, 1
 PREC_F32, PREC_MIXED, PREC_F64 = 0, 1, 2
 FLAG_POLISH, FLAG_WARM_START, FLAG_GENERAL_KERNEL, FLAG_NATURAL_ORDER, FLAG_WARM_SHIFT, FLAG_TILE_KERNEL, FLAG_NO_TIMING = 1, 2, 4, 8, 16, 32, 64
 FLAG_STAGE_KERNEL = 128
+ITERS_WIDE, ITERS_POLISH_MAX = 1000000, 2145
+
+
+def split_iters(iters):
+    """Decode the ``iters`` output (include/mpcqp.h, MPCQP_ITERS) into ``(admm, polish)``: ADMM iterations and polish
+    refinement steps.  Values below 1e6 are ``admm + 1000 * polish``; larger ones ``1e6 * (polish + 1) + admm`` (polish
+    clamped at 2145).  Takes an int or an integer array / tensor (any shape); returns ints or numpy arrays."""
+    if hasattr(iters, "cpu"):   # torch tensor (any device)
+        iters = iters.cpu().numpy()
+    if isinstance(iters, (int, np.integer)):
+        v = int(iters)
+        return (v % 1000, v // 1000) if v < ITERS_WIDE else (v % ITERS_WIDE, v // ITERS_WIDE - 1)
+    v = np.asarray(iters).astype(np.int64)
+    wide = v >= ITERS_WIDE
+    admm = np.where(wide, v % ITERS_WIDE, v % 1000)
+    polish = np.where(wide, v // ITERS_WIDE - 1, v // 1000)
+    return admm, polish
 
 EXPORTED_SYMBOLS = (
     "mpcqp_version", "mpcqp_default_config", "mpcqp_create", "mpcqp_destroy", "mpcqp_solve_batch",

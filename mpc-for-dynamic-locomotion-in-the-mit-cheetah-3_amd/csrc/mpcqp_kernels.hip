@@ -543,7 +543,7 @@ int mpcqp_create(const MpcQpConfig* cfg, mpcqp_handle* out) {
   if (cfg->dtype != MPCQP_DTYPE_F32 && cfg->dtype != MPCQP_DTYPE_F64) return reject(MPCQP_EINVAL);
   if (cfg->disc != MPCQP_DISC_EULER && cfg->disc != MPCQP_DISC_ZOH) return reject(MPCQP_EINVAL);
   if (!(cfg->delta > 0) || !(cfg->m > 0) || !(cfg->rho > 0) || !(cfg->sigma >= 0) || !(cfg->relax > 0 && cfg->relax < 2) ||
-      cfg->max_iter < 1 || cfg->check_every < 1 || cfg->polish_max < 0 || !(cfg->alpha >= 0) || !(cfg->f_max >= cfg->f_min))
+      cfg->max_iter < 1 || cfg->max_iter >= MPCQP_ITERS_WIDE || cfg->check_every < 1 || cfg->polish_max < 0 || !(cfg->alpha >= 0) || !(cfg->f_max >= cfg->f_min))
     return reject(MPCQP_EINVAL);
   for (int i = 0; i < 13; ++i)
     if (!(cfg->w[i] >= 0)) return reject(MPCQP_EINVAL);

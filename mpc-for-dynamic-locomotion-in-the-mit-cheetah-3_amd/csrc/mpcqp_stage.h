@@ -1134,7 +1134,8 @@ mpcqp_stage_solve(const DevCfg* __restrict__ cfgp, const FastIn<TIO> in, TIO* ug
     }
     __syncthreads();
     {   // src/mpc.py:71-78, 98-107; compute_skew column a = r x e_a (src/utils.py:43-56)
-      const double c = s.cy, sn = s.sy, Ib0 = cfg.Ib[0], Ib1 = cfg.Ib[1], Ib2 = cfg.Ib[2], m = Lg.stance ? 1.0 : 0.0;
+      const double c = s.cy, sn = s.sy, Ib0 = cfg.Ib[0], Ib1 = cfg.Ib[1], Ib2 = cfg.Ib[2];
+      const bool st = Lg.stance;   // a swing leg's column is selected to zero, never multiplied by it (its lever arm is a don't-care input)
 #pragma unroll
       for (int a = 0; a < 3; ++a) {
         double cx, cyv, cz;
@@ -1143,9 +1144,9 @@ mpcqp_stage_solve(const DevCfg* __restrict__ cfgp, const FastIn<TIO> in, TIO* ug
         else { cx = rr[1]; cyv = -rr[0]; cz = 0; }
         const double bx = (c * cx + sn * cyv) * Ib0, by = (-sn * cx + c * cyv) * Ib1, bz = cz * Ib2;
         const double tx = c * bx - sn * by, ty = sn * bx + c * by;
-        Lg.B[a] = m * (c * tx - sn * ty);
-        Lg.B[3 + a] = m * (sn * tx + c * ty);
-        Lg.B[6 + a] = m * bz;
+        Lg.B[a] = st ? c * tx - sn * ty : 0.0;
+        Lg.B[3 + a] = st ? sn * tx + c * ty : 0.0;
+        Lg.B[6 + a] = st ? bz : 0.0;
       }
       Lg.cm = Lg.stance ? s.inv_m : 0.0;
     }
@@ -1295,7 +1296,7 @@ mpcqp_stage_solve(const DevCfg* __restrict__ cfgp, const FastIn<TIO> in, TIO* ug
     }
     if (tid == 0) {
       statusg[b] = ok == 1 ? MPCQP_STATUS_SOLVED_POLISHED : (ok == 2 ? MPCQP_STATUS_SOLVED_ADMM : MPCQP_STATUS_MAX_ITER);
-      itersg[b] = s.iters + 1000 * s.psteps;
+      itersg[b] = MPCQP_ITERS(s.iters, s.psteps);
       if (resg) { resg[2 * b] = s.kkt[1]; resg[2 * b + 1] = fmaxf(s.kkt[2], s.kkt[0]); }
     }
     __syncthreads();

@@ -692,10 +692,11 @@ __device__ __forceinline__ int w_setup(SmemW<TV, N>& s, const DevCfg& cfg, const
       else { cx = ry; cyv = -rx; cz = 0; }
       const TV bx = (c * cx + sn * cyv) * Ib0, by = (-sn * cx + c * cyv) * Ib1, bz = cz * Ib2;   // diag(Ib) Rz' col
       const TV tx = c * bx - sn * by, ty = sn * bx + c * by;                                   // Ihat^-1 col
-      const TV m = st ? (TV)1 : (TV)0;
-      s.Bl[9 * L + 0 + a] = m * (c * tx - sn * ty);                                            // Rz Ihat^-1 col
-      s.Bl[9 * L + 3 + a] = m * (sn * tx + c * ty);
-      s.Bl[9 * L + 6 + a] = m * bz;
+      // a swing leg's column is SELECTED to zero, never multiplied by it: its lever arm is a don't-care input, and a finite one
+      // near the top of the range overflows above (0 x inf = NaN in B)
+      s.Bl[9 * L + 0 + a] = st ? c * tx - sn * ty : (TV)0;                                     // Rz Ihat^-1 col
+      s.Bl[9 * L + 3 + a] = st ? sn * tx + c * ty : (TV)0;
+      s.Bl[9 * L + 6 + a] = st ? bz : (TV)0;
     }
     s.cm[L] = st ? s.inv_m : (TV)0;
   }
@@ -1681,7 +1682,7 @@ __device__ __forceinline__ void w_output(SmemW<TV, N>& s, const WrTabs& tabs, TI
   }
   if (tid == 0) {
     statusg[b] = ok == 1 ? MPCQP_STATUS_SOLVED_POLISHED : (ok == 2 ? MPCQP_STATUS_SOLVED_ADMM : MPCQP_STATUS_MAX_ITER);
-    itersg[b] = s.iters + 1000 * s.psteps;
+    itersg[b] = MPCQP_ITERS(s.iters, s.psteps);
     if (resg) { resg[2 * b] = s.kkt[1]; resg[2 * b + 1] = fmaxf(s.kkt[2], s.kkt[0]); }
   }
   STAMP(8);

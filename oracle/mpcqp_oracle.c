@@ -65,6 +65,7 @@ int mpcqp_default_config(MpcQpConfig* c) {
 int mpcqp_create(const MpcQpConfig* cfg, mpcqp_handle* out) {
   if (!cfg || !out || cfg->size != sizeof(MpcQpConfig)) return MPCQP_EINVAL;
   if (cfg->N < 1 || cfg->N > 256 || cfg->dtype != MPCQP_DTYPE_F64) return MPCQP_EINVAL;
+  if (cfg->max_iter < 1 || cfg->max_iter >= MPCQP_ITERS_WIDE || cfg->check_every < 1) return MPCQP_EINVAL;
   struct mpcqp_engine* e = (struct mpcqp_engine*)calloc(1, sizeof(*e));
   if (!e) return MPCQP_ENOMEM;
   e->cfg = *cfg;
@@ -598,7 +599,7 @@ done:
   if (st == MPCQP_STATUS_NONFINITE) memset(w->u, 0, sizeof(double) * n);
   memcpy(u_out, w->u, sizeof(double) * n);
   if (X_out) rollout(w, x0, w->u, X_out);
-  *status = st; *iters = it + 1000 * psteps;
+  *status = st; *iters = MPCQP_ITERS(it, psteps);
   if (res) { res[0] = (float)rp; res[1] = (float)rd; }
   free(mu_leg);
 }

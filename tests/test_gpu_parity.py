@@ -12,6 +12,7 @@ import torch
 
 import mpcqp
 import qp_spec as S
+from batch_checks import check_batch
 from conftest import rel_err
 
 pytestmark = pytest.mark.gpu
@@ -25,6 +26,7 @@ def gpu_solve(batch, N=10, delta=0.03, io="f64", precision="mixed", want_X=True,
     torch.cuda.synchronize()
     res = {k: (v.cpu().numpy() if v is not None else None) for k, v in out.items()}
     res["ms"] = sol.last_kernel_ms()
+    res["max_iter"] = sol.cfg.max_iter
     return res
 
 
@@ -37,11 +39,7 @@ def test_config2_trot_parity(oracle_solve, precision, io):
     b = mpcqp.synth.config2(1024)                                  # BASELINE configs[1] at its stated size
     ref = oracle_solve(b)
     out = gpu_solve(b, io=io, precision=precision)
-    ok = solved(out["status"])
-    assert ok.mean() >= 0.999, ok.mean()                           # (measured: every QP solved; the floor is the measured behaviour)
-    e = rel_err(out["u"], ref["u"])
-    assert e[ok].max() <= TOL[precision], (precision, io, e[ok].max())
-    assert np.abs(out["X"][ok] - ref["X"][ok]).max() <= 1e-4
+    check_batch(out, b, ref, max_iter=out["max_iter"], allowed=0, tol=TOL[precision], what=f"config2 {precision}/{io}")
 
 
 @pytest.mark.parametrize("precision", ["mixed", "f64"])
@@ -49,10 +47,8 @@ def test_config3_mixed_gaits_parity(oracle_solve, precision):
     b = mpcqp.synth.config3(512)
     ref = oracle_solve(b)
     out = gpu_solve(b, io="f32", precision=precision)
-    ok = solved(out["status"])
-    assert ok.mean() >= 0.998, ok.mean()                           # at most one of 512 at the iteration cap (measured: none)
+    ok = check_batch(out, b, ref, max_iter=out["max_iter"], allowed=0, tol=TOL[precision], what=f"config3 {precision}")
     e = rel_err(out["u"], ref["u"])
-    assert e[ok].max() <= TOL[precision]
     # swing legs carry exactly zero force (src/mpc.py:139-144), on every QP, solved or not
     swing = np.repeat(b["contact"] == 0, 3, axis=2).reshape(len(e), 10, 12)
     assert np.all(out["u"][swing] == 0)
@@ -62,17 +58,14 @@ def test_config5_horizon20_parity(oracle_solve):
     b = mpcqp.synth.config5(128)
     ref = oracle_solve(b, N=20)
     out = gpu_solve(b, N=20, io="f32", precision="mixed")
-    ok = solved(out["status"])
-    assert ok.mean() >= 0.999, ok.mean()
-    assert rel_err(out["u"], ref["u"])[ok].max() <= 1e-4
+    check_batch(out, b, ref, max_iter=out["max_iter"], allowed=0, what="config5")
 
 
 def test_zoh_discretisation_parity(oracle_solve):
     b = mpcqp.synth.config3(128)
     ref = oracle_solve(b, disc=mpcqp.DISC_ZOH)
     out = gpu_solve(b, disc=mpcqp.DISC_ZOH)
-    ok = solved(out["status"])
-    assert ok.mean() >= 0.99 and rel_err(out["u"], ref["u"])[ok].max() <= 1e-4
+    check_batch(out, b, ref, max_iter=out["max_iter"], allowed=0, what="zoh")
     # and it is a different problem from Euler: the check above is not vacuous
     ref_e = oracle_solve(b)
     assert rel_err(ref["u"], ref_e["u"]).max() > 1e-3
@@ -121,6 +114,9 @@ def test_alpha0_reference_cost_unique_quantities(golden, mode):
             assert np.abs(Wn - opt["N10_a0_wrench"][i]).max() <= 1e-4 * max(1.0, np.abs(opt["N10_a0_wrench"][i]).max())
 
 
+ALPHA0_ALLOWED = 1   # measured on an MI355X: one of the 96 QPs ends its continuation early (MAX_ITER)
+
+
 def test_alpha0_continuation_on_config3(oracle_solve):
     """alpha = 0 on the bench distribution: >= 99 % reach the end of the continuation; states and per-stage net wrench within
     1e-4 of the alpha = 0 optimum (the oracle's ADMM run to 1e-10 on the singular problem)."""
@@ -129,7 +125,7 @@ def test_alpha0_continuation_on_config3(oracle_solve):
     ref = oracle_solve(b, alpha=0.0, rho=0.3, max_iter=200000)
     out = gpu_solve(b, precision="mixed", alpha=0.0, max_iter=800)
     ok = solved(out["status"]) & (ref["status"] != 3)
-    assert solved(out["status"]).mean() >= 0.98
+    check_batch(out, b, None, max_iter=out["max_iter"], allowed=ALPHA0_ALLOWED, cap_exact=False, what="alpha0")   # (forces are not unique at alpha = 0: compared below by wrench)
     cfg = S.QPConfig(N=10, delta=0.03, alpha=0.0)
     assert np.abs(out["X"][ok] - ref["X"][ok]).max() <= 1e-4
     for i in np.where(ok)[0]:
@@ -140,7 +136,7 @@ def test_alpha0_continuation_on_config3(oracle_solve):
 
 
 @pytest.mark.parametrize("engine", ["wrench", "stage"])
-def test_admm_only_converges_to_oracle(oracle_solve, engine):
+def test_admm_only_reaches_the_oracle(oracle_solve, engine):
     """No polish -- the mode the reference runs (OSQP, src/mpc.py:51-55): plain ADMM in f64 run long enough reaches the oracle on
     EVERY QP (the polish is an accelerator, not a crutch).  Tolerances below 1e-6 switch on one refinement step per linear solve
     (round-2 advisor: without it the explicit inverse left one dual residual in 32 stalled a decade above eps = 1e-9)."""
@@ -150,7 +146,7 @@ def test_admm_only_converges_to_oracle(oracle_solve, engine):
     out = gpu_solve(b, precision="f64", flags=flags, max_iter=20000, check_every=100, eps_abs=1e-9, eps_rel=1e-9)
     assert np.all(out["status"] == 2), (out["status"].tolist(), out["iters"].tolist())
     assert rel_err(out["u"], ref["u"]).max() <= 1e-4
-    assert out["iters"].max() <= 10000                            # (the emulation in exact arithmetic needs at most 1100)
+    assert mpcqp.split_iters(out["iters"])[0].max() <= 10000       # ADMM iterations, decoded: 1100 of them are packed as 1001100 (the emulation in exact arithmetic needs at most 1100)
 
 
 def test_full_size_properties():
@@ -160,8 +156,7 @@ def test_full_size_properties():
     out = gpu_solve(b, io="f32", precision="mixed")
     out2 = gpu_solve(b, io="f32", precision="mixed")
     assert np.array_equal(out["u"], out2["u"]) and np.array_equal(out["status"], out2["status"])   # bitwise repeatable
-    ok = solved(out["status"])
-    assert ok.mean() >= 0.9995, ok.mean()                          # (the bench workload: every QP solved; at most two at the cap)
+    ok = check_batch(out, b, None, max_iter=out["max_iter"], allowed=0, what="config3 4096")   # (the bench workload)
     u = out["u"].astype(np.float64).reshape(4096, 10, 4, 3)
     c = b["contact"].astype(bool)
     mu = b["mu"][:, None, None]
@@ -215,7 +210,7 @@ def test_inverse_updates_give_the_rebuilds_answers():
         upd = gpu_solve(b, N=N, io="f64", precision="mixed", polish_cheap_steps=-1)
         reb = gpu_solve(b, N=N, io="f64", precision="mixed", polish_cheap_steps=-1, incr_legs=-1)
         assert np.array_equal(upd["status"], reb["status"]) and np.array_equal(upd["iters"], reb["iters"])
-        assert (upd["iters"] // 1000).max() >= 3                          # (some QPs do take several steps in a round)
+        assert mpcqp.split_iters(upd["iters"])[1].max() >= 3                          # (some QPs do take several steps in a round)
         assert rel_err(upd["u"], reb["u"]).max() <= 1e-8, rel_err(upd["u"], reb["u"]).max()
 
 
@@ -229,12 +224,10 @@ def test_anderson_acceleration_changes_the_path_not_the_optimum(oracle_solve):
     on = gpu_solve(b, io="f64", precision="mixed")                      # default: accel = 5
     off = gpu_solve(b, io="f64", precision="mixed", accel=-1)
     for o in (on, off):
-        ok = solved(o["status"])
-        assert ok.mean() >= 0.999
-        assert rel_err(o["u"], ref["u"])[ok].max() <= 1e-4
+        check_batch(o, b, ref, max_iter=o["max_iter"], allowed=0, what="accel on/off")
     both = solved(on["status"]) & solved(off["status"])
     assert rel_err(on["u"], off["u"])[both].max() <= 1e-6, rel_err(on["u"], off["u"])[both].max()
-    it_on, it_off = on["iters"] % 1000, off["iters"] % 1000
+    it_on, it_off = mpcqp.split_iters(on["iters"])[0], mpcqp.split_iters(off["iters"])[0]
     assert not np.array_equal(it_on, it_off)                            # (the switch does something)
     hard = it_off >= 200                                                # what the plain iteration needs three blocks and more for
     assert hard.sum() >= 5 and it_on[hard].mean() < 0.8 * it_off[hard].mean(), (hard.sum(), it_on[hard].mean(), it_off[hard].mean())
@@ -243,10 +236,9 @@ def test_anderson_acceleration_changes_the_path_not_the_optimum(oracle_solve):
     bs = {k: (v[:128] if isinstance(v, np.ndarray) and len(v) == 1024 else v) for k, v in b.items()}
     s_on = gpu_solve(bs, io="f64", precision="mixed", flags=mpcqp.FLAG_POLISH | mpcqp.FLAG_STAGE_KERNEL)
     s_off = gpu_solve(bs, io="f64", precision="mixed", flags=mpcqp.FLAG_POLISH | mpcqp.FLAG_STAGE_KERNEL, accel=-1)
+    ref128 = {k: v[:128] for k, v in ref.items() if v is not None}
     for o in (s_on, s_off):
-        ok = solved(o["status"])
-        assert ok.mean() >= 0.99
-        assert rel_err(o["u"], ref["u"][:128])[ok].max() <= 1e-4
+        check_batch(o, bs, ref128, max_iter=o["max_iter"], allowed=0, what="stage accel")
     assert not np.array_equal(s_on["iters"], s_off["iters"])
 
 
@@ -258,9 +250,7 @@ def test_early_rho_check_and_history_restarts_are_switches_not_results(oracle_so
     base = gpu_solve(b, io="f64", precision="mixed")
     for kw in ({"adapt_thr": 6.0}, {"accel_restart": 25}):
         o = gpu_solve(b, io="f64", precision="mixed", **kw)
-        ok = solved(o["status"])
-        assert ok.mean() >= 0.998
-        assert rel_err(o["u"], ref["u"])[ok].max() <= 1e-4
+        check_batch(o, b, ref, max_iter=o["max_iter"], allowed=0, what=str(kw))
         assert not np.array_equal(o["iters"], base["iters"]), kw
 
 
@@ -309,22 +299,20 @@ def test_gait_entry_point_device_side_generation(oracle_solve):
     dg = sol.upload_gait(g)
     o = sol.solve_batch_gait(dg["x0"], dg["ref"], dg["feet0"], dg["footholds"], dg["gait"], dg["feet_id"], dg["mu"], want_X=True)
     torch.cuda.synchronize()
-    ug, Xg, stg = o["u"].cpu().numpy().copy(), o["X"].cpu().numpy().copy(), o["status"].cpu().numpy().copy()
+    ug, Xg, stg, itg = (o[k].cpu().numpy().copy() for k in ("u", "X", "status", "iters"))
     dt = sol.upload(t)
     o2 = sol.solve_batch(dt["x0"], dt["r"], dt["contact"], dt["xdes"], dt["mu"], want_X=True)
     torch.cuda.synchronize()
     ut, stt = o2["u"].cpu().numpy(), o2["status"].cpu().numpy()
-    ok = solved(stg)
-    assert ok.mean() >= 0.97 and np.array_equal(stg, stt)
-    assert rel_err(ug, ref["u"])[ok].max() <= 1e-4 and np.abs(Xg[ok] - ref["X"][ok]).max() <= 1e-4
+    ok = check_batch({"u": ug, "X": Xg, "status": stg, "iters": itg}, t, ref, max_iter=sol.cfg.max_iter, allowed=0, what="gait N=10")
+    assert np.array_equal(stg, stt)
     assert rel_err(ug, ut)[ok].max() <= 5e-5          # same problem through both entry points (each is ~1e-5 from the optimum)
     # f32 buffers through the gait entry
     sol32 = mpcqp.MPCBatch(io_dtype="f32", precision="mixed")
     d32 = sol32.upload_gait(g)
     o3 = sol32.solve_batch_gait(d32["x0"], d32["ref"], d32["feet0"], d32["footholds"], d32["gait"], d32["feet_id"], d32["mu"])
     torch.cuda.synchronize()
-    ok3 = solved(o3["status"].cpu().numpy())
-    assert ok3.mean() >= 0.97 and rel_err(o3["u"].cpu().numpy(), ref["u"])[ok3].max() <= 1e-4
+    check_batch(o3, t, {"u": ref["u"]}, max_iter=sol32.cfg.max_iter, allowed=0, what="gait N=10 f32")
 
 
 def test_gait_entry_point_any_horizon(oracle_solve):
@@ -348,9 +336,10 @@ def test_gait_entry_point_any_horizon(oracle_solve):
     both = solved(stg) & solved(st2)
     assert rel_err(ug, u2)[both].max() <= 5e-5     # the same problem through both entry points (the device expansion contracts its
                                                    # multiply-adds, the tuple differs from numpy's in the last bit; each is ~1e-5 from the optimum)
-    ok = solved(stg)
-    assert ok.mean() >= 0.99
-    assert rel_err(ug[:128], ref["u"])[ok[:128]].max() <= 1e-4 and np.abs(Xg[:128][ok[:128]] - ref["X"][ok[:128]]).max() <= 1e-4
+    og = {"u": ug, "X": Xg, "status": stg, "iters": itg}
+    check_batch(og, t, None, max_iter=sol.cfg.max_iter, allowed=0, what="gait N=20")
+    check_batch({k: v[:128] for k, v in og.items()}, {k: v[:128] for k, v in t.items()}, ref, max_iter=sol.cfg.max_iter, allowed=0,
+                what="gait N=20 vs checker")
     # two described steps at N = 20: the third step's stages fall back to the second step, all feet down
     g2 = mpcqp.synth.make_gait_batch(64, N=N, steps=2, seed=20250811)
     t2 = mpcqp.synth.expand_gait_batch(g2, N=N)
@@ -362,8 +351,9 @@ def test_gait_entry_point_any_horizon(oracle_solve):
     ob = sol.solve_batch(dt2["x0"], dt2["r"], dt2["contact"], dt2["xdes"], dt2["mu"])
     torch.cuda.synchronize()
     ub_, sb_ = ob["u"].cpu().numpy(), ob["status"].cpu().numpy()
-    both = solved(oa["status"].cpu().numpy()) & solved(sb_)
-    assert both.mean() >= 0.95 and rel_err(ua, ub_)[both].max() <= 5e-5
+    both = check_batch(oa, t2, None, max_iter=sol.cfg.max_iter, allowed=0, what="gait two steps") & check_batch(
+        ob, t2, None, max_iter=sol.cfg.max_iter, allowed=0, what="tuple two steps")
+    assert rel_err(ua, ub_)[both].max() <= 5e-5
     # the reference's own horizon through the descriptors (N = 60: five 15-tick steps), against the tuple entry
     g60 = mpcqp.synth.make_gait_batch(16, N=60, delta=0.01, steps=5, seed=3, gait_names=("trot", "gallop"), mus=(0.7, 1.0))
     t60 = mpcqp.synth.expand_gait_batch(g60, N=60, delta=0.01)
@@ -375,8 +365,9 @@ def test_gait_entry_point_any_horizon(oracle_solve):
     dt60 = s60.upload(t60)
     od = s60.solve_batch(dt60["x0"], dt60["r"], dt60["contact"], dt60["xdes"], dt60["mu"])
     torch.cuda.synchronize()
-    both = solved(sc) & solved(od["status"].cpu().numpy())
-    assert both.mean() >= 0.9 and rel_err(uc, od["u"].cpu().numpy())[both].max() <= 5e-5
+    both = check_batch({"u": uc, "status": sc, "iters": oc["iters"].cpu().numpy().copy()}, t60, None, max_iter=s60.cfg.max_iter, allowed=0,
+                       what="gait N=60") & check_batch(od, t60, None, max_iter=s60.cfg.max_iter, allowed=0, what="tuple N=60")
+    assert rel_err(uc, od["u"].cpu().numpy())[both].max() <= 5e-5
 
 
 @pytest.mark.parametrize("isotropic", [False, True])
@@ -390,10 +381,7 @@ def test_non_default_model_constants(oracle_solve, isotropic):
         kw["w"][7] = kw["w"][6]
     ref = oracle_solve(b, delta=0.02, **kw)
     out = gpu_solve(b, delta=0.02, io="f64", precision="mixed", flags=1, **kw)
-    ok = solved(out["status"])
-    assert ok.mean() >= 0.95
-    assert rel_err(out["u"], ref["u"])[ok].max() <= 1e-4
-    assert np.abs(out["X"][ok] - ref["X"][ok]).max() <= 1e-4
+    check_batch(out, b, ref, max_iter=out["max_iter"], allowed=0, what=f"model constants isotropic={isotropic}")
     # and the changed constants do change the answer (the check above is not vacuous)
     ref0 = oracle_solve(b, delta=0.02)
     assert rel_err(ref["u"], ref0["u"]).max() > 1e-2
@@ -413,17 +401,20 @@ def test_torque_map_epilogue():
         assert np.abs(tau.cpu().numpy() - want).max() <= tol * 30
 
 
+REGULARISER_ALLOWED = {(1.0, "mixed"): 0, (1e-3, "mixed"): 1, (1e-4, "mixed"): 1, (1e-4, "f64"): 1}   # QPs not solved, measured on an MI355X
+
+
 @pytest.mark.parametrize("alpha,precision,min_solved", [(1.0, "mixed", 0.99), (1e-3, "mixed", 0.99), (1e-4, "mixed", 0.99), (1e-4, "f64", 0.99)])
 def test_regulariser_sweep(oracle_solve, alpha, precision, min_solved):
     """`solved` must imply the 1e-4 band for any force regulariser alpha (conditioning ~ 1 / alpha): the polish acceptance
     scales with the curvature 2 alpha.  Below 1e-2 the engine finds the active set at 1e-2 and walks alpha down by continuation
-    (fp64 polish systems), which keeps the solved fraction at >= 99 % in MIXED as well."""
+    (fp64 polish systems), which keeps the QPs left at the cap to the measured count in MIXED as well."""
     b = mpcqp.synth.config3(256)
     ref = oracle_solve(b, alpha=alpha, max_iter=200000)
     out = gpu_solve(b, io="f64", precision=precision, alpha=alpha, max_iter=1000 if precision == "f64" else 400)
-    ok = solved(out["status"])
+    ok = check_batch(out, b, ref, max_iter=out["max_iter"], allowed=REGULARISER_ALLOWED[(alpha, precision)], cap_exact=alpha >= 1e-2,
+                     what=f"alpha={alpha} {precision}")
     assert ok.mean() >= min_solved, ok.mean()
-    assert rel_err(out["u"], ref["u"])[ok].max() <= 1e-4
 
 
 def test_queued_form_matches_plain_form_bitwise():
@@ -439,7 +430,8 @@ def test_queued_form_matches_plain_form_bitwise():
     queued = gpu_solve(b, io="f32", precision="mixed")
     for k in ("u", "X", "status", "iters", "res"):
         assert np.array_equal(plain[k], queued[k], equal_nan=True), k
-    assert np.all(queued["status"][[5, 700, 1099]] == -1) and solved(np.delete(queued["status"], [5, 700, 1099])).mean() >= 0.97
+    assert np.all(queued["status"][[5, 700, 1099]] == -1)
+    check_batch(queued, b, None, max_iter=queued["max_iter"], allowed=0, what="queued")
     g = mpcqp.synth.make_gait_batch(B)
     outs = []
     for flags in (mpcqp.FLAG_POLISH | mpcqp.FLAG_NATURAL_ORDER, mpcqp.FLAG_POLISH):

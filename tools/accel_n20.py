@@ -34,6 +34,6 @@ for combo in combos:
         else:
             ref[name] = (u, st == 1)
         m = float(np.median(ms))
-        line += f" | {name}: {m:.2f} ms = {4096 / m / 1e3:.3f} M QP/s uns {int((st != 1).sum())} it {(it % 1000).mean():.0f}/{(it % 1000).max()} ps {(it // 1000).mean():.2f}/{(it // 1000).max()} d {d:.0e}"
+        line += f" | {name}: {m:.2f} ms = {4096 / m / 1e3:.3f} M QP/s uns {int((st != 1).sum())} it {mpcqp.split_iters(it)[0].mean():.0f}/{mpcqp.split_iters(it)[0].max()} ps {mpcqp.split_iters(it)[1].mean():.2f}/{mpcqp.split_iters(it)[1].max()} d {d:.0e}"
         del sol
     print(line, flush=True)

@@ -44,7 +44,7 @@ for combo in combos:
         else:
             ref_u[sd] = (u, st == 1)
         m = float(np.median(ms)); rates.append(4096 / m / 1e3)
-        line += f" | {sd % 100000}: {m * 1e3:.0f}us uns {int((st != 1).sum())} it {(it % 1000).mean():.0f}/{(it % 1000).max()} ps {(it // 1000).mean():.2f}/{(it // 1000).max()} d {dmax:.0e}"
+        line += f" | {str(sd)[-5:]}: {m * 1e3:.0f}us uns {int((st != 1).sum())} it {mpcqp.split_iters(it)[0].mean():.0f}/{mpcqp.split_iters(it)[0].max()} ps {mpcqp.split_iters(it)[1].mean():.2f}/{mpcqp.split_iters(it)[1].max()} d {dmax:.0e}"
     dev = sol.upload(big)
     for _ in range(2):
         out = sol.solve_batch(dev["x0"], dev["r"], dev["contact"], dev["xdes"], dev["mu"])
@@ -55,5 +55,5 @@ for combo in combos:
         ev[0].record(); out = sol.solve_batch(dev["x0"], dev["r"], dev["contact"], dev["xdes"], dev["mu"]); ev[1].record()
         torch.cuda.synchronize(); ms.append(ev[0].elapsed_time(ev[1]))
     st = out["status"].cpu().numpy(); it = out["iters"].cpu().numpy()
-    print(line + f" || mean of other seeds {np.mean(rates[1:]):.2f} M, bench seed {rates[0]:.2f} M | B=65536: {65536 / np.median(ms) / 1e3:.2f} M uns {int((st != 1).sum())} it {(it % 1000).mean():.0f}", flush=True)
+    print(line + f" || mean of other seeds {np.mean(rates[1:]):.2f} M, bench seed {rates[0]:.2f} M | B=65536: {65536 / np.median(ms) / 1e3:.2f} M uns {int((st != 1).sum())} it {mpcqp.split_iters(it)[0].mean():.0f}", flush=True)
     del sol

@@ -27,4 +27,4 @@ for name, batch in cases:
         for _ in range(9):
             o = sol.solve_batch(dev["x0"], dev["r"], dev["contact"], dev["xdes"], dev["mu"]); torch.cuda.synchronize(); ms.append(sol.last_kernel_ms())
         st = o["status"].cpu().numpy(); it = o["iters"].cpu().numpy()
-        print(f"{name:7s} N={N} {prec:5s} thr={thr:<5g} {B / np.median(ms) / 1e3:7.3f} M QP/s  ms {np.median(ms):.3f} unsolved {int(np.sum(st != 1))} iters {np.mean(it % 1000):.1f} max {np.max(it % 1000)} psteps {np.mean(it // 1000):.2f} max {np.max(it // 1000)}", flush=True)
+        print(f"{name:7s} N={N} {prec:5s} thr={thr:<5g} {B / np.median(ms) / 1e3:7.3f} M QP/s  ms {np.median(ms):.3f} unsolved {int(np.sum(st != 1))} iters {np.mean(mpcqp.split_iters(it)[0]):.1f} max {np.max(mpcqp.split_iters(it)[0])} psteps {np.mean(mpcqp.split_iters(it)[1]):.2f} max {np.max(mpcqp.split_iters(it)[1])}", flush=True)

@@ -20,5 +20,5 @@ for N, mk in ((10, mpcqp.synth.config3), (20, mpcqp.synth.config5)):
             o = sol.solve_batch(dev["x0"], dev["r"], dev["contact"], dev["xdes"], dev["mu"]); torch.cuda.synchronize()
             e = relerr(o["u"].cpu().numpy(), ref["u"])
             it = o["iters"].cpu().numpy()
-            line += f"  {prec}: err max {e.max():.2e} med {np.median(e):.2e} iters {np.unique(it % 1000).tolist()} (oracle {np.unique(ref['iters'] % 1000).tolist()})"
+            line += f"  {prec}: err max {e.max():.2e} med {np.median(e):.2e} iters {np.unique(mpcqp.split_iters(it)[0]).tolist()} (oracle {np.unique(mpcqp.split_iters(ref['iters'])[0]).tolist()})"
         print(line, flush=True)

@@ -23,4 +23,4 @@ for name, mk, N in (("config2 B=1024 trot mu=1", lambda: mpcqp.synth.config2(102
         torch.cuda.synchronize()
         ms.append(sol.last_kernel_ms())
     st = out["status"].cpu().numpy(); it = out["iters"].cpu().numpy()
-    print(f"{name:26s}: {np.median(ms):8.3f} ms  {len(st) / np.median(ms) * 1e3:12,.0f} QP/s  solved {np.mean((st == 1) | (st == 2)):.4f}  admm {np.mean(it % 1000):.0f}  polish {np.mean(it // 1000):.2f}")
+    print(f"{name:26s}: {np.median(ms):8.3f} ms  {len(st) / np.median(ms) * 1e3:12,.0f} QP/s  solved {np.mean((st == 1) | (st == 2)):.4f}  admm {np.mean(mpcqp.split_iters(it)[0]):.0f}  polish {np.mean(mpcqp.split_iters(it)[1]):.2f}")

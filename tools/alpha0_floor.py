@@ -28,4 +28,4 @@ for floor in ("1e-5", "3e-6", "1e-6"):
     ok = (st == 1) & (r0["status"] != 3)
     dW = np.array([np.abs(S.net_wrench(u[i], batch["r"][i], batch["contact"][i], cfg0) - W0[i]).max() / max(1, np.abs(W0[i]).max()) for i in range(B)])
     dX = np.abs(X - r0["X"]).reshape(B, -1).max(axis=1)
-    print(f"floor {floor} config3: solved {(st == 1).mean():.3f} dX max {dX[ok].max():.1e} dW max {dW[ok].max():.1e} polish {np.mean(it // 1000):.1f} {sol.last_kernel_ms():.2f} ms", flush=True)
+    print(f"floor {floor} config3: solved {(st == 1).mean():.3f} dX max {dX[ok].max():.1e} dW max {dW[ok].max():.1e} polish {np.mean(mpcqp.split_iters(it)[1]):.1f} {sol.last_kernel_ms():.2f} ms", flush=True)

@@ -37,7 +37,7 @@ def run(label, precision, **kw):
     rec = dict(label, precision=precision, qp_per_s=B / (min(ms) * 1e-3), ms=min(ms), solved_fraction=float(ok.mean()),
                err_max_all=float(e.max()), err_median_all=float(np.median(e)),
                err_max_solved=float(e[okr].max()) if okr.any() else None, err_median_solved=float(np.median(e[okr])) if okr.any() else None,
-               admm_iters_mean=float((it % 1000).mean()), polish_steps_mean=float((it // 1000).mean()))
+               admm_iters_mean=float(mpcqp.split_iters(it)[0].mean()), polish_steps_mean=float(mpcqp.split_iters(it)[1].mean()))
     cells.append(rec)
     print(json.dumps(rec), flush=True)
 

@@ -13,7 +13,7 @@ sol = mpcqp.MPCBatch(N=10, precision="mixed")
 dev = sol.upload(batch)
 o = sol.solve_batch(dev["x0"], dev["r"], dev["contact"], dev["xdes"], dev["mu"]); torch.cuda.synchronize()
 it = o["iters"].cpu().numpy()
-cost = (it % 1000) + 60 * (it // 1000)
+cost = mpcqp.split_iters(it)[0] + 60 * mpcqp.split_iters(it)[1]
 order = np.argsort(-cost)[:6]
 print("hardest:", [(int(b), int(it[b])) for b in order], "contact stance legs/stage:", [batch["contact"][b].sum(axis=1).tolist() for b in order[:2]], "mu", [float(batch["mu"][b]) for b in order])
 names = ["setup", "admm-E", "admm-tile-init", "admm-sweep", "admm-iters", "rho-check", "polish-solve+kkt", "polish-publish", "output",
@@ -39,6 +39,6 @@ for which, L in (("product", None), ("stamps", lib)):
             dbg = (ctypes.c_double * 2048)()
             if L.lib.mpcqp_debug_read_wdbg(dbg) == 0:
                 d = np.array(list(dbg))[1300:1300 + 8 * 80].reshape(80, 8)
-                nst = int(o1["iters"][0]) // 1000
+                nst = mpcqp.split_iters(int(o1["iters"][0]))[1]
                 for r in d[:nst]:
                     print(f"      kind/round {int(r[0]):3d} step {int(r[1])} stat {r[2]:.2e} prim {r[3]:.2e} dual {r[4]:.2e} rho {r[5]:.3g} iters {int(r[6])} ok {int(r[7])}")

@@ -9,4 +9,4 @@ for K, mi in ((100, 400), (150, 600), (200, 800), (300, 900), (400, 1200)):
         out = sol.solve_batch(dev["x0"], dev["r"], dev["contact"], dev["xdes"], dev["mu"])
     torch.cuda.synchronize()
     st = out["status"].cpu().numpy(); it = out["iters"].cpu().numpy()
-    print(f"K={K}: {sol.last_kernel_ms():.2f} ms  {1024 / sol.last_kernel_ms() * 1e3:,.0f} QP/s solved {np.mean((st==1)|(st==2)):.4f} admm {np.mean(it % 1000):.0f} polish {np.mean(it // 1000):.2f}")
+    print(f"K={K}: {sol.last_kernel_ms():.2f} ms  {1024 / sol.last_kernel_ms() * 1e3:,.0f} QP/s solved {np.mean((st==1)|(st==2)):.4f} admm {np.mean(mpcqp.split_iters(it)[0]):.0f} polish {np.mean(mpcqp.split_iters(it)[1]):.2f}")

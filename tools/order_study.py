@@ -34,7 +34,7 @@ for name, batch in (("bench", mpcqp.synth.config3(B)), ("seed3", mpcqp.synth.mak
             o = sol.solve_batch(dev["x0"], dev["r"], dev["contact"], dev["xdes"], dev["mu"]); torch.cuda.synchronize(); ms.append(sol.last_kernel_ms())
         return np.median(ms), o["iters"].cpu().numpy()
     t_q, it = run(batch, 1)
-    cost = (it % 1000) + 55 * (it // 1000)
+    cost = mpcqp.split_iters(it)[0] + 55 * mpcqp.split_iters(it)[1]
     cl = classes(batch)
     perm = {"measured cost, dearest first": np.argsort(-cost, kind="stable"), "pre-pass class, dearest first": np.argsort(-cl, kind="stable"), "batch order": np.arange(B)}
     print(f"{name}:", flush=True)

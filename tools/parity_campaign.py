@@ -26,7 +26,7 @@ for N, delta, B, seed, prec in cases:
     err = np.abs(u - ur).max(axis=1) / np.maximum(np.abs(ur).max(axis=1), 1.0)
     worst = max(worst, float(err[ok].max()))
     print(f"N={N:2d} delta={delta} B={B:5d} seed {seed:3d} {prec:5s}: engine solved {np.mean((st == 1) | (st == 2)):.4f} (checker {np.mean((rs == 1) | (rs == 2)):.4f}), "
-          f"max rel force error of the solved {err[ok].max():.2e}, iterations mean {(it % 1000).mean():.0f} max {(it % 1000).max()}, polish steps mean {(it // 1000).mean():.2f}; checker {time.time() - t0:.1f} s", flush=True)
+          f"max rel force error of the solved {err[ok].max():.2e}, iterations mean {mpcqp.split_iters(it)[0].mean():.0f} max {mpcqp.split_iters(it)[0].max()}, polish steps mean {mpcqp.split_iters(it)[1].mean():.2f}; checker {time.time() - t0:.1f} s", flush=True)
     del sol
 print(f"worst relative force error over the campaign: {worst:.2e} (tolerance 1e-4)")
 assert worst <= 1e-4

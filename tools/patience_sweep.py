@@ -28,7 +28,7 @@ for lp, mi in combos:
             torch.cuda.synchronize(); ms.append(ev[0].elapsed_time(ev[1]))
         it = out["iters"].cpu().numpy(); st = out["status"].cpu().numpy()
         m = float(np.median(ms)); rates.append(4096 / m / 1e3)
-        line += f" | {sd % 100000}: {m * 1e3:.0f}us uns {int((st != 1).sum())} it {(it % 1000).mean():.0f} ps {(it // 1000).mean():.2f}"
+        line += f" | {str(sd)[-5:]}: {m * 1e3:.0f}us uns {int((st != 1).sum())} it {mpcqp.split_iters(it)[0].mean():.0f} ps {mpcqp.split_iters(it)[1].mean():.2f}"
     dev = sol.upload(big)
     for _ in range(2):
         out = sol.solve_batch(dev["x0"], dev["r"], dev["contact"], dev["xdes"], dev["mu"])

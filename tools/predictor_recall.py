@@ -27,7 +27,7 @@ for seed in (20250809, 1, 2, 3, 4):
     sol = mpcqp.MPCBatch(N=10, precision="mixed")
     dev = sol.upload(b)
     o = sol.solve_batch(dev["x0"], dev["r"], dev["contact"], dev["xdes"], dev["mu"]); torch.cuda.synchronize()
-    it = o["iters"].cpu().numpy(); admm = it % 1000; ps = it // 1000
+    it = o["iters"].cpu().numpy(); admm = mpcqp.split_iters(it)[0]; ps = mpcqp.split_iters(it)[1]
     cost = admm * 0.4 + ps * 12.0
     hard = admm > 200
     order = np.argsort(-cls, kind="stable")            # dearest class first (position inside a class: arrival order on the device)

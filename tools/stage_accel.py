@@ -23,7 +23,7 @@ for combo in combos:
     for prec in ("mixed", "f64"):
         for name, b in (("logged", logged), ("synthetic", synth)):
             o = gpu_solve(b, 60, 0.01, prec, alpha=1e-2, check_every=ce, max_iter=2400, polish_max=8, accel=ac, first_block=fb, **extra)
-            it = o["iters"] % 1000; ps = o["iters"] // 1000
+            it = mpcqp.split_iters(o["iters"])[0]; ps = mpcqp.split_iters(o["iters"])[1]
             u = o["u"].reshape(len(it), -1)
             key = (prec, name)
             d = 0.0

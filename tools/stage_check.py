@@ -34,8 +34,8 @@ if "n10" in which:
             ok = o["status"] == 1
             e = rel_err(o["u"], ref["u"]); eX = np.abs(o["X"] - ref["X"]).reshape(len(e), -1).max(axis=1)
             print(f"N={N} stage {prec}: solved {ok.sum()}/{len(ok)} statuses {np.bincount(o['status'] + 1).tolist()} max rel err u (solved) {e[ok].max() if ok.any() else float('nan'):.2e} "
-                  f"X {eX[ok].max() if ok.any() else float('nan'):.2e}; worst overall {e.max():.2e}; iters mean {np.mean(o['iters'] % 1000):.0f} polish {np.mean(o['iters'] // 1000):.2f} "
-                  f"(dense engine: {np.mean(dense['iters'] % 1000):.0f} / {np.mean(dense['iters'] // 1000):.2f}); kernel {o['ms']:.2f} ms (dense {dense['ms']:.3f})", flush=True)
+                  f"X {eX[ok].max() if ok.any() else float('nan'):.2e}; worst overall {e.max():.2e}; iters mean {np.mean(mpcqp.split_iters(o['iters'])[0]):.0f} polish {np.mean(mpcqp.split_iters(o['iters'])[1]):.2f} "
+                  f"(dense engine: {np.mean(mpcqp.split_iters(dense['iters'])[0]):.0f} / {np.mean(mpcqp.split_iters(dense['iters'])[1]):.2f}); kernel {o['ms']:.2f} ms (dense {dense['ms']:.3f})", flush=True)
 if "n60" in which:
     q = np.load(os.path.join(REPO, "tests", "golden", "qp_inputs.npz")); opt = np.load(os.path.join(REPO, "tests", "golden", "qp_optima.npz"))
     N = 60
@@ -51,7 +51,7 @@ if "rate" in which:
         b = mpcqp.synth.make_batch(B, 60, 0.01, 11, ("trot", "pronk", "amble", "gallop"), (0.3, 0.5, 0.7, 1.0))
         for prec in ("mixed", "f64"):
             o = gpu(b, 60, 0.01, prec, mpcqp.FLAG_POLISH)
-            it = o["iters"] % 1000 + 0; ps = o["iters"] // 1000
+            it = mpcqp.split_iters(o["iters"])[0] + 0; ps = mpcqp.split_iters(o["iters"])[1]
             print(f"N=60 B={B} {prec}: {o['ms']:.1f} ms = {B / o['ms']:.1f} k QP/s, solved {np.mean(o['status'] == 1):.3f}, iters mean {np.mean(it):.0f} max {it.max()} hist(/100) {np.bincount(it // 100).tolist()} "
                   f"polish mean {np.mean(ps):.1f} max {ps.max()}; unsolved: {[(int(i), int(o['iters'][i]), float(b['mu'][i]), int(b['gait_ids'][i])) for i in np.where(o['status'] != 1)[0][:6]]}", flush=True)
 if "prof" in which:

@@ -15,4 +15,4 @@ for N, flags in ((60, mpcqp.FLAG_POLISH), (10, mpcqp.FLAG_POLISH | mpcqp.FLAG_ST
         eJ = [abs(S.objective(o["X"][i], o["u"][i], bb["xdes"][i], cfg) / opt[f"N{N}_a0_J"][i] - 1) for i in range(10)]
         eX = np.abs(o["X"] - opt[f"N{N}_a0_X"]).reshape(10, -1).max(axis=1)
         print(f"N={N} floor {floor:.0e}: solved {int(ok.sum())}/10, objective rel err max (solved) {max([e for e, k in zip(eJ, ok) if k] or [float('nan')]):.1e}, "
-              f"states max (solved) {eX[ok].max() if ok.any() else float('nan'):.1e}; polish steps {(o['iters'] // 1000).tolist()}", flush=True)
+              f"states max (solved) {eX[ok].max() if ok.any() else float('nan'):.1e}; polish steps {mpcqp.split_iters(o['iters'])[1].tolist()}", flush=True)

@@ -30,7 +30,7 @@ for rep in range(2):
 v = np.array(list(buf), dtype=np.float64)
 it = out["iters"].cpu().numpy()
 tot = v[0] + v[8] + v[9]
-print(f"N={N} B={B} {prec}: kernel {sol.last_kernel_ms():.2f} ms; iterations mean {(it % 1000).mean():.0f}, polish steps mean {(it // 1000).mean():.2f}; "
+print(f"N={N} B={B} {prec}: kernel {sol.last_kernel_ms():.2f} ms; iterations mean {mpcqp.split_iters(it)[0].mean():.0f}, polish steps mean {mpcqp.split_iters(it)[1].mean():.2f}; "
       f"cycles/QP {tot / B:.0f} (100 MHz? no: shader clock)")
 for i, nme in enumerate(names):
     print(f"  {nme:28s} share {v[i] / tot:6.1%}  cycles/QP {v[i] / B:10.0f}  events/QP {v[16 + i] / B:7.2f}  cycles/event {v[i] / max(v[16 + i], 1):9.0f}")

@@ -12,6 +12,6 @@ for ce, mi, pm in ((200, 2400, 8), (150, 2400, 8), (120, 2400, 8), (100, 2400, 8
     line = f"check_every {ce} max_iter {mi} polish_max {pm}:"
     for name, b in (("logged", logged), ("synthetic", synth)):
         o = gpu_solve(b, 60, 0.01, "mixed", alpha=1e-2, check_every=ce, max_iter=mi, polish_max=pm)
-        it = o["iters"] % 1000; ps = o["iters"] // 1000
+        it = mpcqp.split_iters(o["iters"])[0]; ps = mpcqp.split_iters(o["iters"])[1]
         line += f" | {name}: {o['ms']:.1f} ms = {len(it) / o['ms']:.1f} k QP/s, solved {np.mean(o['status'] == 1):.4f}, iters mean {it.mean():.0f} max {it.max()}, polish mean {ps.mean():.2f} max {ps.max()}"
     print(line, flush=True)

@@ -23,5 +23,5 @@ for warm in (False, True):
             torch.cuda.synchronize(); t0 = time.perf_counter()
             o = ws.solve_batch(d["x0"], d["r"], d["contact"], d["xdes"], d["mu"]); torch.cuda.synchronize()
             ms.append((time.perf_counter() - t0) * 1e3)
-            it = int(o["iters"][0]); its.append(it % 1000); ps.append(it // 1000); bad += int(o["status"][0]) != 1
+            it = int(o["iters"][0]); its.append(mpcqp.split_iters(it)[0]); ps.append(mpcqp.split_iters(it)[1]); bad += int(o["status"][0]) != 1
     print(f"{'warm (shifted previous tick)' if warm else 'cold':30s}: iterations mean {np.mean(its[1:]):.1f} max {max(its[1:])}, polish steps mean {np.mean(ps[1:]):.2f}, {np.mean(ms[1:]):.3f} ms per tick = {1e3 / np.mean(ms[1:]):.0f} solves/s, unsolved {bad}", flush=True)

@@ -28,7 +28,7 @@ for seed in [int(x) for x in os.environ.get('TL_SEEDS', '20250809,1,2,3,4').spli
     t0 = t[:, 0].astype(np.float64); t1 = t[:, 1].astype(np.float64)
     xcc = (t[:, 2] >> np.uint64(32)).astype(np.int64) & 0xf
     it = out["iters"].cpu().numpy(); st = out["status"].cpu().numpy()
-    admm = it % 1000; ps = it // 1000
+    admm = mpcqp.split_iters(it)[0]; ps = mpcqp.split_iters(it)[1]
     dur = (t1 - t0)
     # the tick unit: calibrate on the launch itself (longest span on any XCD ~ kernel time)
     tick_per_us = TICK                                   # s_memrealtime: one clock for the whole device
