@@ -34,6 +34,30 @@ GAITS = {
     "gallop": (0, 0, 1, 1),          # the committed default, "pseudo-galloping" (src/main.py:39)
 }
 
+# Crawl patterns, kept apart from GAITS (whose entries the planner goldens pin): one foot swings during a step's ss phase, three
+# feet the next (the complement), so a crawl alternates three-foot and one-foot support -- stage patterns no two-beat gait has.
+CRAWLS = {
+    "crawl_fl": (0, 1, 1, 1),
+    "crawl_fr": (1, 0, 1, 1),
+    "crawl_hl": (1, 1, 0, 1),
+    "crawl_hr": (1, 1, 1, 0),
+}
+
+
+def gait_patterns(gaits):
+    """uint8 [G,4] first_swing patterns from names (GAITS, CRAWLS) or 4-tuples, in the given order."""
+    out = []
+    for g in gaits:
+        if isinstance(g, str):
+            g = GAITS[g] if g in GAITS else CRAWLS[g]
+        out.append(tuple(int(v) for v in g))
+    return np.asarray(out, dtype=np.uint8).reshape(-1, 4)
+
+
+def log_uniform_mu(rng, B, lo=0.05, hi=3.0):
+    """Friction coefficients drawn log-uniformly from [lo, hi]."""
+    return np.exp(rng.uniform(np.log(lo), np.log(hi), B))
+
 
 def contact_schedule(gait_ids, t0, N, gaits=None):
     """contact[B,N,4]: phase semantics of src/footstep_planner.py:239-246 for an endless two-beat gait.
@@ -54,8 +78,9 @@ def contact_schedule(gait_ids, t0, N, gaits=None):
     return contact
 
 
-def make_batch(B, N=10, delta=0.03, seed=20250808, gait_names=("trot",), mus=(1.0,), dtype=np.float64):
-    """State distribution of SURVEY.md section 8(d) config 2 (and 3-5 via gait_names / mus / N / seed)."""
+def make_batch(B, N=10, delta=0.03, seed=20250808, gait_names=("trot",), mus=(1.0,), dtype=np.float64, mu_range=None):
+    """State distribution of SURVEY.md section 8(d) config 2 (and 3-5 via gait_names / mus / N / seed).  `gait_names` are names or
+    4-tuples (gait_patterns); `mu_range=(lo, hi)` draws mu log-uniformly instead of from `mus` (after every other draw)."""
     rng = np.random.default_rng(seed)
     roll = rng.uniform(-0.1, 0.1, B)
     pitch = rng.uniform(-0.1, 0.1, B)
@@ -87,7 +112,9 @@ def make_batch(B, N=10, delta=0.03, seed=20250808, gait_names=("trot",), mus=(1.
     # lever arms, src/mpc.py:218-239: stage 0 from the measured com, stage k>=1 from the reference com
     r = feet[:, None, :, :] - xdes[:, :N, None, 3:6]
     r[:, 0] = feet - com[:, None, :]
-    contact = contact_schedule(gait_ids, t0, N, gaits=[GAITS[g] for g in gait_names])
+    contact = contact_schedule(gait_ids, t0, N, gaits=gait_patterns(gait_names))
+    if mu_range is not None:
+        mu = log_uniform_mu(rng, B, *mu_range)
     return {
         "x0": np.ascontiguousarray(x0, dtype=dtype),
         "r": np.ascontiguousarray(r, dtype=dtype),
@@ -119,15 +146,49 @@ def config5(B=4096, dtype=np.float64):
 
 
 # ----------------------------------------------------------------------------------------------------------------------
+# Per-leg timing: every leg keeps its own clock (early / late touchdown), so any of the 16 support patterns can occur
+# ----------------------------------------------------------------------------------------------------------------------
+def perleg_contact(timing, t0, N):
+    """contact[B,N,4] of per-leg timing (make_perleg_batch): leg l of robot b is in stance at tick t when
+    (t + offset[b,l]) mod period[b] < stance[b,l].  Advance one control tick with t0 + 1."""
+    P = np.asarray(timing["period"])[:, None, None]
+    t = np.asarray(t0)[:, None, None] + np.arange(N)[None, :, None] + np.asarray(timing["offset"])[:, None, :]
+    return ((t % P) < np.asarray(timing["stance"])[:, None, :]).astype(np.uint8)
+
+
+def make_perleg_batch(B, N=10, delta=0.03, seed=20250820, mu_range=(0.05, 3.0), period=(8, 30), duty=(0.25, 0.85), dtype=np.float64):
+    """The state and lever-arm distribution of `make_batch`, with a per-leg contact schedule: each robot gets a period (ticks), each
+    leg its own duty factor and phase offset.  mu is log-uniform on `mu_range`.  The timing parameters are returned (`timing`, `t0`)
+    so that a caller can advance the clock (perleg_contact)."""
+    b = make_batch(B, N, delta, seed, ("trot",), (1.0,), dtype)
+    rng = np.random.default_rng(seed + 1)
+    P = rng.integers(period[0], period[1] + 1, B)
+    stance = np.clip(np.rint(rng.uniform(duty[0], duty[1], (B, 4)) * P[:, None]), 1, P[:, None] - 1).astype(np.int64)
+    offset = rng.integers(0, 1 << 20, (B, 4)) % P[:, None]
+    t0 = rng.integers(0, 1 << 20, B) % P
+    timing = {"period": P, "stance": stance, "offset": offset}
+    b["contact"] = np.ascontiguousarray(perleg_contact(timing, t0, N))
+    b["mu"] = np.ascontiguousarray(log_uniform_mu(rng, B, *mu_range), dtype=dtype)
+    b["timing"], b["t0"] = timing, t0
+    del b["gait_ids"]
+    return b
+
+
+def make_crawl_batch(B, N=10, delta=0.03, seed=20250821, mu_range=(0.05, 3.0), dtype=np.float64):
+    """`make_batch` with the four crawl patterns (CRAWLS) and log-uniform mu: three-foot, one-foot and four-foot stages."""
+    return make_batch(B, N, delta, seed, tuple(CRAWLS), (1.0,), dtype, mu_range=mu_range)
+
+
+# ----------------------------------------------------------------------------------------------------------------------
 # Compact gait descriptors (include/mpcqp.h, mpcqp_solve_batch_gait) and their host expansion
 # ----------------------------------------------------------------------------------------------------------------------
 def make_gait_batch(B, N=10, delta=0.03, seed=20250812, gait_names=("trot", "pronk", "amble", "gallop"), mus=(0.3, 0.5, 0.7, 1.0),
-                    stride=0.06, steps=2):
+                    stride=0.06, steps=2, mu_range=None):
     """Same state distribution as `make_batch`, but described the way the controller knows it: measured feet, the
     planned footholds of the current and the following `steps - 1` steps (swing feet land `stride` ahead along the heading, the
     gait alternates feet_id with its complement step by step, src/footstep_planner.py:159-177), the gait clock."""
     rng = np.random.default_rng(seed)
-    base = make_batch(B, N, delta, seed, gait_names, mus)
+    base = make_batch(B, N, delta, seed, gait_names, mus, mu_range=mu_range)
     x0 = base["x0"]
     yaw = x0[:, 2]
     c, s = np.cos(yaw), np.sin(yaw)
@@ -135,7 +196,7 @@ def make_gait_batch(B, N=10, delta=0.03, seed=20250812, gait_names=("trot", "pro
     com_start = np.concatenate([x0[:, 3:5], np.full((B, 1), H_COM)], axis=1)
     ref = np.concatenate([np.zeros((B, 2)), yaw[:, None], com_start, v_ref, np.zeros((B, 1))], axis=1)
     feet0 = base["r"][:, 0] + x0[:, None, 3:6]                       # measured feet (stage-0 lever arm + com)
-    gaits = np.asarray([GAITS[g] for g in gait_names], dtype=np.uint8)
+    gaits = gait_patterns(gait_names)
     fid0 = gaits[base["gait_ids"]]
     t0 = base["t0"]
     step_par = (t0 // (SS_TICKS + DS_TICKS)) % 2
@@ -187,6 +248,7 @@ def make_rollout_batch(B, N=10, delta=0.03, seed=20250813, gait_names=("trot", "
     robot: the reference integrates v_com_ref in world axes (src/mpc.py:202-214) while its planner walks along the heading."""
     from .footstep_planner import LEGS, FootstepPlanner
     rng = np.random.default_rng(seed)
+    patterns = gait_patterns(gait_names)
     x = np.zeros((B, 13)); ref = np.zeros((B, 10))
     pos = np.zeros((B, total_steps, 4, 3)); fid = np.ones((B, total_steps, 4), np.uint8); meta = np.zeros((B, 4), np.int32)
     gid = rng.integers(0, len(gait_names), B)
@@ -195,7 +257,7 @@ def make_rollout_batch(B, N=10, delta=0.03, seed=20250813, gait_names=("trot", "
         com = np.array([0.0, 0.0, H_COM]) + rng.normal(0.0, 0.005, 3) * np.array([1.0, 1.0, 0.5])
         feet = NOMINAL_FEET + np.array([com[0], com[1], H_COM]) + np.concatenate([rng.normal(0.0, 0.003, (4, 2)), np.zeros((4, 1))], axis=1)
         params = {"g": G_ACC, "h": H_COM, "step_height": 0.08, "ss_duration": ss, "ds_duration": ds, "world_time_step": delta,
-                  "total_steps": total_steps, "first_swing": np.array(GAITS[gait_names[gid[b]]]), "µ": float(mu[b]), "N": N, "dof": 18,
+                  "total_steps": total_steps, "first_swing": patterns[gid[b]].astype(int), "µ": float(mu[b]), "N": N, "dof": 18,
                   "v_com_ref": np.asarray(v_ref, float), "theta_dot": 0.0, "log_samples": 0}
         initial = {l: feet[k].copy() for k, l in enumerate(LEGS)}
         initial.update(roll=0.0, pitch=0.0, yaw=0.0, com_position=com.copy())

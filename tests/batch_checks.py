@@ -73,3 +73,26 @@ def check_batch(out, batch, ref=None, *, max_iter, allowed=0, tol=1e-4, x_tol=1e
     n = int((fin & ~ok).sum())
     assert n <= allowed, f"{what}: {n} QPs with finite inputs not solved (allowed {allowed}): {np.nonzero(fin & ~ok)[0].tolist()[:20]}"
     return ok
+
+
+def kkt_certificate(H, g, G, lo, hi, u, act_tol=1e-7):
+    """Optimality certificate of `u` for the convex QP min 1/2 u'Hu + g'u s.t. lo <= Gu <= hi (oracle/qp_spec.py layout).
+
+    Multipliers come from a SIGN-CONSTRAINED least-squares fit on the active rows (y >= 0 on rows at their upper bound, y <= 0 at
+    their lower bound, free on equality rows), then qp_spec.kkt_report gives stationarity, primal feasibility, dual sign and
+    complementarity: stationarity with multipliers of the right sign IS optimality of the convex QP -- an unconstrained fit would
+    certify stationary points of the wrong active set too.  A row is active within `act_tol` relative to its bound."""
+    from scipy.optimize import lsq_linear
+    import qp_spec as S
+    Gu = G @ u
+    lo0, hi0 = np.where(np.isfinite(lo), lo, 0.0), np.where(np.isfinite(hi), hi, 0.0)
+    at_lo = np.isfinite(lo) & (np.abs(Gu - lo0) <= act_tol * np.maximum(1, np.abs(lo0)))
+    at_hi = np.isfinite(hi) & (np.abs(Gu - hi0) <= act_tol * np.maximum(1, np.abs(hi0)))
+    act = at_lo | at_hi
+    y = np.zeros(len(lo))
+    if act.any():
+        lb = np.where(at_lo[act], -np.inf, 0.0)
+        ub = np.where(at_hi[act], np.inf, 0.0)
+        fit = lsq_linear(G[act].T, -(H @ u + g), bounds=(lb, ub), method="bvls", tol=1e-14, max_iter=2000)
+        y[act] = fit.x
+    return S.kkt_report(H, g, G, lo, hi, u, y)

@@ -16,18 +16,21 @@ def solved(st):
     return (st == 1) | (st == 2)
 
 
-def next_tick(b, X, delta=0.03):
+def next_tick(b, X, delta=0.03, gaits=("trot", "pronk", "amble", "gallop")):
     """The QP one control tick later: the robot sits at the first predicted state, the references move on by one
-    step (src/mpc.py:261-262) and the gait clock advances (mpcqp.synth.contact_schedule)."""
-    nb = {k: np.array(v, copy=True) for k, v in b.items()}
+    step (src/mpc.py:261-262) and the gait clock advances (mpcqp.synth.contact_schedule over `gaits`, names or patterns, which
+    b["gait_ids"] index; per-leg clocks, mpcqp.synth.perleg_contact, where the batch carries its `timing`)."""
+    nb = {k: (v if isinstance(v, dict) else np.array(v, copy=True)) for k, v in b.items()}
     nb["x0"] = X[:, 1, :].copy()
     nb["x0"][:, 12] = b["x0"][:, 12]
     step = b["xdes"][:, 1, :] - b["xdes"][:, 0, :]
     nb["xdes"] = b["xdes"] + step[:, None, :]
     nb["xdes"][:, :, 12] = b["xdes"][:, :, 12]
     nb["t0"] = b["t0"] + 1
-    gaits = [mpcqp.synth.GAITS[g] for g in ("trot", "pronk", "amble", "gallop")]
-    nb["contact"] = mpcqp.synth.contact_schedule(b["gait_ids"], nb["t0"], b["contact"].shape[1], gaits=gaits)
+    if "timing" in b:
+        nb["contact"] = mpcqp.synth.perleg_contact(b["timing"], nb["t0"], b["contact"].shape[1])
+    else:
+        nb["contact"] = mpcqp.synth.contact_schedule(b["gait_ids"], nb["t0"], b["contact"].shape[1], gaits=mpcqp.synth.gait_patterns(gaits))
     feet = b["r"][:, 1] + b["xdes"][:, 1, None, 3:6]                      # fixed world footholds of the synthetic batch
     nb["r"] = feet[:, None, :, :] - nb["xdes"][:, :-1, None, 3:6]
     nb["r"][:, 0] = feet - nb["x0"][:, None, 3:6]

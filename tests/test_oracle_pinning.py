@@ -14,6 +14,7 @@ import pytest
 
 import mpcqp
 import qp_spec as S
+from batch_checks import kkt_certificate
 from conftest import rel_err
 
 
@@ -58,21 +59,7 @@ def test_c_oracle_matches_numpy_restatement_and_kkt(oracle_solve, disc):
         x0, r, c, xd, mu = b["x0"][i], b["r"][i], b["contact"][i], b["xdes"][i], b["mu"][i]
         H, g, c0, G, lo, hi, *_ = S.condensed_qp(x0, r, c, xd, mu, cfg)
         u = ref["u"][i].reshape(-1)
-        # multipliers by a SIGN-CONSTRAINED least-squares fit on the active rows (y >= 0 on rows at their upper bound, y <= 0 at
-        # their lower bound, free on equality rows), then the full KKT certificate: stationarity with multipliers of the right
-        # sign IS optimality of the convex QP -- an unconstrained fit would certify stationary points of the wrong active set too
-        from scipy.optimize import lsq_linear
-        Gu = G @ u
-        at_lo = np.isfinite(lo) & (np.abs(Gu - np.where(np.isfinite(lo), lo, 0.0)) <= 1e-7 * np.maximum(1, np.abs(np.where(np.isfinite(lo), lo, 0.0))))
-        at_hi = np.isfinite(hi) & (np.abs(Gu - np.where(np.isfinite(hi), hi, 0.0)) <= 1e-7 * np.maximum(1, np.abs(np.where(np.isfinite(hi), hi, 0.0))))
-        act = at_lo | at_hi
-        y = np.zeros(len(lo))
-        if act.any():
-            lb = np.where(at_lo[act], -np.inf, 0.0)
-            ub = np.where(at_hi[act], np.inf, 0.0)
-            fit = lsq_linear(G[act].T, -(H @ u + g), bounds=(lb, ub), method="bvls", tol=1e-14, max_iter=2000)
-            y[act] = fit.x
-        k = S.kkt_report(H, g, G, lo, hi, u, y)
+        k = kkt_certificate(H, g, G, lo, hi, u)                    # sign-constrained multiplier fit on the active rows, then KKT
         scale = max(1.0, np.abs(g).max())
         assert k["stationarity"] <= 1e-7 * scale, k
         assert k["primal"] <= 1e-7 * max(1.0, np.abs(u).max()), k
