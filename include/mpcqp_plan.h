@@ -1,0 +1,74 @@
+/*
+ * mpcqp_plan.h -- extension of include/mpcqp.h: footstep plans and swing-foot trajectories on the device.
+ *
+ * These are the two pieces of the reference's per-tick glue that sit around the QP: the footstep planner
+ * (FootstepPlanner.__init__, src/footstep_planner.py:29-177) and the swing-foot trajectory generator
+ * (FootTrajectoryGenerator.generate_feet_trajectories_at_time, src/foot_trajectory_generator.py:27-96), batched over B robots.
+ * mpcqp_plan_footsteps writes the plan tables that mpcqp_rollout reads, so a batch of roll-outs is set up without a host loop.
+ *
+ * The symbols declared here are exported by the product library libmpcqp.so ONLY; the CPU checker library under oracle/ does
+ * not have them (its host-side counterparts are footstep_planner.plan_tables / foot_trajectory_generator.swing_tables in the
+ * Python package).  Pointers are device memory on the handle's GPU, T is the handle's I/O dtype (MpcQpConfig.dtype), work is
+ * enqueued on `stream` and nothing is synchronised.  Both calls carry their arithmetic in fp64 whatever T is: fp32 outputs are
+ * the fp64 results rounded once.  A handle serves one stream at a time (include/mpcqp.h): mpcqp_plan_footsteps uses an
+ * engine-owned workspace of B * S * 40 bytes, allocated by the first call at a given size and reused afterwards.
+ * Return codes and mpcqp_last_error() as in mpcqp.h: sizes and null pointers are checked on the host (MPCQP_EINVAL).
+ */
+#ifndef MPCQP_PLAN_H_
+#define MPCQP_PLAN_H_
+
+#include "mpcqp.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+/*
+ * Footstep plan of src/footstep_planner.py:29-177 for B robots, in the table form mpcqp_rollout reads.
+ *   feet0        T  [B,4,3]   initial foot positions FL, FR, HL, HR (initial_configuration[leg])
+ *   cmd          T  [B,5]     yaw0, v_com_ref x, v_com_ref y, theta_dot, h
+ *   gait         i32[B,4]     total_steps, ss_duration, ds_duration, first_swing as a bit mask (bit k = leg k stays down in step 1)
+ *   plan_pos     T  [B,S,4,3] out: plan[step]['pos'] of the four feet
+ *   plan_feet_id u8 [B,S,4]   out: plan[step]['feet_id'] (1 = stance)
+ *   plan_meta    i32[B,4]     out: min(steps, S), ss, ds, 0 (steps = total_steps, or the 100 standing steps when total_steps <= 0)
+ *   plan_ang     T  [B,S]     out, may be NULL: yaw of each step
+ *   plan_hip     T  [B,S,3]   out, may be NULL: the planner's 'hip' row (x/y NaN for a standing plan, as the host)
+ * The tick length is MpcQpConfig.delta (the reference's world_time_step).  The planner's rules: step 0 is all stance; the
+ * unicycle (theta += theta_dot dt, centre += R(theta) v dt, ss + ds ticks per step) moves from the second step on; the feet that
+ * stay down keep their previous row, the others land on the fresh placement around the centre; first_swing alternates with its
+ * complement from step to step.  Rows s >= min(steps, S) repeat the last planned row.  The gait row lives in device memory and
+ * is clamped, never trusted: total_steps < 0 means the standing plan, ss and ds are clamped into [0, 65535].
+ */
+int mpcqp_plan_footsteps(mpcqp_handle h, int64_t B, int32_t S, const void* feet0, const void* cmd, const int32_t* gait,
+                         void* plan_pos, uint8_t* plan_feet_id, int32_t* plan_meta, void* plan_ang, void* plan_hip, void* stream);
+
+/*
+ * FootTrajectoryGenerator.generate_feet_trajectories_at_time for every leg at ticks tick[b] + j, j = 0..K-1.
+ *   plan_pos / plan_feet_id / plan_meta / plan_ang   as written by mpcqp_plan_footsteps ([B,S,...]; plan_ang is required)
+ *   tick        i32[B]          first tick of each robot (clamped at >= 0)
+ *   step_height T  [B]
+ *   traj        T  [B,K,4,3,6]  out: pos / vel / acc 6-vectors (angle xyz, position xyz) of each leg
+ *   feet_des    T  [B,K,4,3]    out, may be NULL: the desired foot position of the reference's closed-loop log
+ *                               (FEET POS des, src/main.py:152-167)
+ * Step of tick tau: s = min(tau / (ss + ds), S_b - 1), t = tau - s (ss + ds); the target past the last row is the start; step 0
+ * stands; the swing lands at 0.8 ss (cubic in x / y / angle, quartic bump of step_height in z); velocity and acceleration are
+ * divided by delta and delta^2.  plan_meta is clamped as in mpcqp_rollout (1 <= S_b <= S, ss, ds >= 0, ss + ds >= 1).
+ *
+ * The host generator marks a step all-stance (plan[step]['feet_id'] = 1) when it is queried in double support
+ * (src/foot_trajectory_generator.py:53-54).  These functions never write the plan; feet_des is the pure rule that reproduces
+ * what that side effect does to the log of a closed loop that has queried every tick from 0:
+ *   stance leg (plan_feet_id[s] == 1)                   plan_pos[s]
+ *   swing leg, single support (t < ss)                  trajectory position, z clamped at >= 0
+ *   swing leg, first double-support tick (t == ss)      the target plan_pos[s + 1] (past the plan: plan_pos[s]), z clamped at >= 0
+ *   swing leg, later double-support ticks (t > ss)      plan_pos[s]
+ * (Step 0 returns before the side effect in the host generator: a swing leg there, which only a hand-made table can have, keeps
+ * the trajectory position, i.e. the start, at every tick.)  Stance is any nonzero plan_feet_id.
+ */
+int mpcqp_swing_trajectories(mpcqp_handle h, int64_t B, int32_t K, int32_t S, const void* plan_pos, const uint8_t* plan_feet_id,
+                             const int32_t* plan_meta, const void* plan_ang, const int32_t* tick, const void* step_height,
+                             void* traj, void* feet_des, void* stream);
+
+#ifdef __cplusplus
+}
+#endif
+#endif /* MPCQP_PLAN_H_ */

@@ -1,4 +1,4 @@
-"""ctypes binding of the C-ABI declared in include/mpcqp.h.
+"""ctypes binding of the C-ABI declared in include/mpcqp.h and its product-only extension include/mpcqp_plan.h.
 
 The product path loads ``csrc/libmpcqp.so`` (hand-written HIP for gfx950) and nothing else: if that library is
 missing or cannot be loaded, importing the engine raises -- there is no CPU fallback.  The binding itself is
@@ -45,6 +45,9 @@ EXPORTED_SYMBOLS = (
     "mpcqp_version", "mpcqp_default_config", "mpcqp_create", "mpcqp_destroy", "mpcqp_solve_batch",
     "mpcqp_solve_batch_gait", "mpcqp_solve_batch_gait_steps", "mpcqp_torque_map", "mpcqp_default_leg_geometry", "mpcqp_leg_jacobians", "mpcqp_last_kernel_ms", "mpcqp_last_error", "mpcqp_reserve", "mpcqp_rollout",
 )
+
+# include/mpcqp_plan.h: exported by the product library only (the CPU checker under oracle/ does not have them)
+PLAN_SYMBOLS = ("mpcqp_plan_footsteps", "mpcqp_swing_trajectories")
 
 
 class MpcQpLegGeometry(ctypes.Structure):
@@ -114,6 +117,12 @@ class Library:
         L.mpcqp_last_kernel_ms.restype = c_int32
         L.mpcqp_last_error.argtypes = [c_void_p]
         L.mpcqp_last_error.restype = c_char_p
+        self.has_plan = all(hasattr(L, sym) for sym in PLAN_SYMBOLS)
+        if self.has_plan:
+            L.mpcqp_plan_footsteps.argtypes = [c_void_p, c_int64, c_int32] + [c_void_p] * 9
+            L.mpcqp_plan_footsteps.restype = c_int32
+            L.mpcqp_swing_trajectories.argtypes = [c_void_p, c_int64, c_int32, c_int32] + [c_void_p] * 9
+            L.mpcqp_swing_trajectories.restype = c_int32
 
     def version(self) -> int:
         return int(self.lib.mpcqp_version())
@@ -222,6 +231,27 @@ class Engine:
         self.rollout_ptr(B, T, S, x.ctypes.data, ref.ctypes.data, pos.ctypes.data, fid.ctypes.data, meta.ctypes.data, tick.ctypes.data,
                          mu.ctypes.data, actual.ctypes.data, desired.ctypes.data, forces.ctypes.data, solved.ctypes.data)
         return {"x": x, "ref": ref, "tick": tick, "actual": actual, "desired": desired, "forces": forces, "solved": solved}
+
+    def _plan_call(self, name):
+        if not self.library.has_plan:
+            raise MpcQpError(f"{name}: {self.library.path} does not export include/mpcqp_plan.h (product library only)")
+        return getattr(self.library.lib, name)
+
+    def plan_footsteps_ptr(self, B, S, feet0, cmd, gait, plan_pos, plan_feet_id, plan_meta, plan_ang=0, plan_hip=0, stream=0):
+        """Raw call of the device footstep planner (include/mpcqp_plan.h); every argument is an integer address."""
+        rc = self._plan_call("mpcqp_plan_footsteps")(self._h, int(B), int(S), feet0 or None, cmd or None, gait or None, plan_pos or None,
+                                                      plan_feet_id or None, plan_meta or None, plan_ang or None, plan_hip or None,
+                                                      stream or None)
+        if rc != 0:
+            raise MpcQpError(f"mpcqp_plan_footsteps failed with code {rc}: {self.last_error()}")
+
+    def swing_trajectories_ptr(self, B, K, S, plan_pos, plan_feet_id, plan_meta, plan_ang, tick, step_height, traj, feet_des=0, stream=0):
+        """Raw call of the device swing-foot trajectory generator (include/mpcqp_plan.h); every argument is an integer address."""
+        rc = self._plan_call("mpcqp_swing_trajectories")(self._h, int(B), int(K), int(S), plan_pos or None, plan_feet_id or None,
+                                                          plan_meta or None, plan_ang or None, tick or None, step_height or None,
+                                                          traj or None, feet_des or None, stream or None)
+        if rc != 0:
+            raise MpcQpError(f"mpcqp_swing_trajectories failed with code {rc}: {self.last_error()}")
 
     def torque_map_ptr(self, B, u, jac, tau, stream=0):
         rc = self.library.lib.mpcqp_torque_map(self._h, int(B), u, jac, tau, stream or None)

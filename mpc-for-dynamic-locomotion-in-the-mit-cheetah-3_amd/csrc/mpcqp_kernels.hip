@@ -8,11 +8,13 @@
 //                    (horizon 10) or per four waves (horizon 20), fp32 or fp64 ADMM, fp64 active-set polish, ADMM-only mode
 //   mpcqp_stage.h    stage-wise (Riccati) form of the same engine for any other horizon up to 64 -- the reference's own N = 60
 //   mpcqp_common.h   what they share: operator-tuple descriptor, policy constants, the dispatch-order pre-pass;  mpcqp_device.h: DPP helpers
-// plus the element-wise kernels around the solve: gait-descriptor expansion, closed-loop roll-out (expand / advance), torque map.
+// plus the element-wise kernels around the solve: gait-descriptor expansion, closed-loop roll-out (expand / advance), torque map,
+// and (mpcqp_plan.h, C-ABI include/mpcqp_plan.h) footstep plans and swing-foot trajectories.
 // DESIGN.md has the derivations.
 
 #include "mpcqp_wrench.h"
 #include "mpcqp_stage.h"
+#include "mpcqp_plan.h"
 
 #include <cstdio>
 #include <cstdlib>
@@ -271,6 +273,8 @@ struct mpcqp_engine {
   int64_t roll_cap = 0;
   void* gait_mem = nullptr;   // gait entry point: the expanded operator tuple [r | xdes | contact] of the current batch
   int64_t gait_cap = 0;
+  double* plan_ws = nullptr;  // footstep planner: theta, centre x / y, cos / sin theta per (robot, step) [plan_cap][5]
+  int64_t plan_cap = 0;
   bool wrench_ok = false;     // the configuration admits the wrench-space form (isotropic omega weight, positive velocity weights)
   bool form_ok = false;       // ... the same condition without the horizon-specific tables (stage-wise engine)
   double* stage_ws = nullptr; // stage-wise engine: factor workspace of the resident workgroups
@@ -492,6 +496,7 @@ static void free_engine(mpcqp_engine* h) {
   if (h->dual_mem) (void)hipFree(h->dual_mem);
   if (h->gait_mem) (void)hipFree(h->gait_mem);
   if (h->roll_mem) (void)hipFree(h->roll_mem);
+  if (h->plan_ws) (void)hipFree(h->plan_ws);
   if (h->wr_K) (void)hipFree(h->wr_K);
   if (h->wr_kinv32) (void)hipFree(h->wr_kinv32);
   if (h->wr_kinv64) (void)hipFree(h->wr_kinv64);
@@ -833,6 +838,67 @@ int mpcqp_rollout(mpcqp_handle h, int64_t B, int32_t T, int32_t S, void* x, void
     if (hipEventRecord(h->ev1, st) != hipSuccess) return fail(h, MPCQP_EHIP, "hipEventRecord");
     h->timed = true;
   }
+  return MPCQP_OK;
+}
+
+int mpcqp_plan_footsteps(mpcqp_handle h, int64_t B, int32_t S, const void* feet0, const void* cmd, const int32_t* gait, void* plan_pos,
+                         uint8_t* plan_feet_id, int32_t* plan_meta, void* plan_ang, void* plan_hip, void* stream) {
+  if (!h) return MPCQP_EINVAL;
+  if (B < 0 || B > 0x7fffffff || S < 1 || B * (int64_t)S > 0x7fffffff) return fail(h, MPCQP_EINVAL, "mpcqp_plan_footsteps: size out of range");
+  if (B > 0 && (!feet0 || !cmd || !gait || !plan_pos || !plan_feet_id || !plan_meta))
+    return fail(h, MPCQP_EINVAL, "mpcqp_plan_footsteps: null buffer");
+  if (B == 0) return MPCQP_OK;
+  DeviceGuard guard(h->cfg.device);
+  if (guard.err != hipSuccess) return fail(h, MPCQP_EHIP, "hipSetDevice", guard.err);
+  const int64_t rows = B * S;
+  if (h->plan_cap < rows) {   // once per size; later calls at this size or smaller allocate nothing
+    void* mem = nullptr;
+    if (hipMalloc(&mem, (size_t)rows * PLAN_WS * sizeof(double)) != hipSuccess) {
+      (void)hipGetLastError();
+      return fail(h, MPCQP_ENOMEM, "mpcqp_plan_footsteps: workspace allocation failed");
+    }
+    if (h->plan_ws) { (void)hipDeviceSynchronize(); (void)hipFree(h->plan_ws); }
+    h->plan_ws = (double*)mem; h->plan_cap = rows;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  const dim3 g1((unsigned)((B + 63) / 64)), g2((unsigned)((rows + PLAN_BLOCK - 1) / PLAN_BLOCK));
+  if (h->cfg.dtype == MPCQP_DTYPE_F64) {
+    hipLaunchKernelGGL((mpcqp_plan_unicycle_kernel<double>), g1, dim3(64), 0, st, (const double*)feet0, (const double*)cmd, gait,
+                       h->cfg.delta, (int)S, B, h->plan_ws);
+    hipLaunchKernelGGL((mpcqp_plan_tables_kernel<double>), g2, dim3(PLAN_BLOCK), 0, st, (const double*)feet0, (const double*)cmd, gait,
+                       (const double*)h->plan_ws, (int)S, B, (double*)plan_pos, plan_feet_id, plan_meta, (double*)plan_ang, (double*)plan_hip);
+  } else {
+    hipLaunchKernelGGL((mpcqp_plan_unicycle_kernel<float>), g1, dim3(64), 0, st, (const float*)feet0, (const float*)cmd, gait,
+                       h->cfg.delta, (int)S, B, h->plan_ws);
+    hipLaunchKernelGGL((mpcqp_plan_tables_kernel<float>), g2, dim3(PLAN_BLOCK), 0, st, (const float*)feet0, (const float*)cmd, gait,
+                       (const double*)h->plan_ws, (int)S, B, (float*)plan_pos, plan_feet_id, plan_meta, (float*)plan_ang, (float*)plan_hip);
+  }
+  const hipError_t he = hipGetLastError();
+  if (he != hipSuccess) return fail(h, MPCQP_EHIP, "footstep planner kernel launch", he);
+  return MPCQP_OK;
+}
+
+int mpcqp_swing_trajectories(mpcqp_handle h, int64_t B, int32_t K, int32_t S, const void* plan_pos, const uint8_t* plan_feet_id,
+                             const int32_t* plan_meta, const void* plan_ang, const int32_t* tick, const void* step_height, void* traj,
+                             void* feet_des, void* stream) {
+  if (!h) return MPCQP_EINVAL;
+  if (B < 0 || B > 0x7fffffff || K < 0 || S < 1 || B * (int64_t)K > 0x7fffffff)
+    return fail(h, MPCQP_EINVAL, "mpcqp_swing_trajectories: size out of range");
+  if (B > 0 && K > 0 && (!plan_pos || !plan_feet_id || !plan_meta || !plan_ang || !tick || !step_height || !traj))
+    return fail(h, MPCQP_EINVAL, "mpcqp_swing_trajectories: null buffer");
+  if (B == 0 || K == 0) return MPCQP_OK;
+  DeviceGuard guard(h->cfg.device);
+  if (guard.err != hipSuccess) return fail(h, MPCQP_EHIP, "hipSetDevice", guard.err);
+  const dim3 grid((unsigned)((B * K * 4 + PLAN_BLOCK - 1) / PLAN_BLOCK));
+  hipStream_t st = (hipStream_t)stream;
+  if (h->cfg.dtype == MPCQP_DTYPE_F64)
+    hipLaunchKernelGGL((mpcqp_swing_kernel<double>), grid, dim3(PLAN_BLOCK), 0, st, (const double*)plan_pos, plan_feet_id, plan_meta,
+                       (const double*)plan_ang, tick, (const double*)step_height, h->cfg.delta, (int)K, (int)S, B, (double*)traj, (double*)feet_des);
+  else
+    hipLaunchKernelGGL((mpcqp_swing_kernel<float>), grid, dim3(PLAN_BLOCK), 0, st, (const float*)plan_pos, plan_feet_id, plan_meta,
+                       (const float*)plan_ang, tick, (const float*)step_height, h->cfg.delta, (int)K, (int)S, B, (float*)traj, (float*)feet_des);
+  const hipError_t he = hipGetLastError();
+  if (he != hipSuccess) return fail(h, MPCQP_EHIP, "swing trajectory kernel launch", he);
   return MPCQP_OK;
 }
 

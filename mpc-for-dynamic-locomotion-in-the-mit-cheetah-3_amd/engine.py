@@ -149,6 +149,55 @@ class MPCBatch:
                                 tick.data_ptr(), mu.data_ptr(), p(actual), p(desired), p(forces), solved.data_ptr(), st.cuda_stream)
         return {"actual": actual, "desired": desired, "forces": forces, "solved": solved}
 
+    def plan_footsteps(self, feet0, cmd, gait, S, want_ang=True, want_hip=False, stream=None):
+        """Footstep plans of B robots on the device (include/mpcqp_plan.h, mpcqp_plan_footsteps; the host FootstepPlanner per robot):
+        feet0 [B,4,3] initial feet FL, FR, HL, HR and cmd [B,5] (yaw0, v_com_ref x, v_com_ref y, theta_dot, h) of the engine's dtype,
+        gait int32 [B,4] (total_steps, ss, ds, first_swing bit mask; bit k = leg k stays down in step 1).  Returns device tensors
+        plan_pos [B,S,4,3], plan_feet_id uint8 [B,S,4] and plan_meta int32 [B,4] -- the plan arguments of `rollout` -- plus plan_ang
+        [B,S] and plan_hip [B,S,3] when asked for (None otherwise).  The tick length is the engine's delta; asynchronous on `stream`."""
+        torch = _torch()
+        B, S = int(feet0.shape[0]), int(S)
+        for t, shape, dt in ((feet0, (B, 4, 3), self.tdtype), (cmd, (B, 5), self.tdtype), (gait, (B, 4), torch.int32)):
+            if tuple(t.shape) != shape or t.dtype != dt or not t.is_contiguous() or t.device != self.device:
+                raise ValueError(f"operand mismatch: expected {shape} {dt} contiguous on {self.device}, got {tuple(t.shape)} {t.dtype} on {t.device}")
+        if S < 1:
+            raise ValueError(f"S must be >= 1, got {S}")
+        st = stream if stream is not None else torch.cuda.current_stream(self.device)
+        with torch.cuda.stream(st):
+            e = lambda *shape: torch.empty(shape, dtype=self.tdtype, device=self.device)
+            out = {"plan_pos": e(B, S, 4, 3), "plan_feet_id": torch.empty((B, S, 4), dtype=torch.uint8, device=self.device),
+                   "plan_meta": torch.empty((B, 4), dtype=torch.int32, device=self.device),
+                   "plan_ang": e(B, S) if want_ang else None, "plan_hip": e(B, S, 3) if want_hip else None}
+        p = lambda t: t.data_ptr() if t is not None else 0
+        self.engine.plan_footsteps_ptr(B, S, feet0.data_ptr(), cmd.data_ptr(), gait.data_ptr(), out["plan_pos"].data_ptr(),
+                                       out["plan_feet_id"].data_ptr(), out["plan_meta"].data_ptr(), p(out["plan_ang"]), p(out["plan_hip"]),
+                                       st.cuda_stream)
+        return out
+
+    def swing_trajectories(self, plan, tick, K, step_height, want_des=True, stream=None):
+        """Swing-foot trajectories of every leg at ticks tick[b] + j, j < K (include/mpcqp_plan.h, mpcqp_swing_trajectories; the host
+        FootTrajectoryGenerator per robot, leg and tick): `plan` as returned by `plan_footsteps` (plan_ang required), tick int32 [B],
+        step_height [B] of the engine's dtype.  Returns {"traj": [B,K,4,3,6] pos / vel / acc 6-vectors (angle xyz, position xyz),
+        "feet_des": [B,K,4,3] the closed-loop log's desired foot positions, or None}.  Asynchronous on `stream`."""
+        torch = _torch()
+        pos, fid, meta, ang = plan["plan_pos"], plan["plan_feet_id"], plan["plan_meta"], plan.get("plan_ang")
+        if ang is None:
+            raise ValueError("swing_trajectories needs plan['plan_ang'] (plan_footsteps(..., want_ang=True))")
+        B, S, K = int(pos.shape[0]), int(pos.shape[1]) if pos.dim() == 4 else -1, int(K)
+        for t, shape, dt in ((pos, (B, S, 4, 3), self.tdtype), (fid, (B, S, 4), torch.uint8), (meta, (B, 4), torch.int32),
+                             (ang, (B, S), self.tdtype), (tick, (B,), torch.int32), (step_height, (B,), self.tdtype)):
+            if S < 1 or tuple(t.shape) != shape or t.dtype != dt or not t.is_contiguous() or t.device != self.device:
+                raise ValueError(f"operand mismatch: expected {shape} {dt} contiguous on {self.device}, got {tuple(t.shape)} {t.dtype} on {t.device}")
+        if K < 0:
+            raise ValueError(f"K must be >= 0, got {K}")
+        st = stream if stream is not None else torch.cuda.current_stream(self.device)
+        with torch.cuda.stream(st):
+            traj = torch.empty((B, K, 4, 3, 6), dtype=self.tdtype, device=self.device)
+            des = torch.empty((B, K, 4, 3), dtype=self.tdtype, device=self.device) if want_des else None
+        self.engine.swing_trajectories_ptr(B, K, S, pos.data_ptr(), fid.data_ptr(), meta.data_ptr(), ang.data_ptr(), tick.data_ptr(),
+                                           step_height.data_ptr(), traj.data_ptr(), des.data_ptr() if des is not None else 0, st.cuda_stream)
+        return {"traj": traj, "feet_des": des}
+
     def torque_map(self, u, jac, stream=None):
         """tau[B,4,3] = J^T (-f) of the stage-0 forces (src/main.py:212-214); jac[B,4,3,3] world-frame leg Jacobians."""
         torch = _torch()

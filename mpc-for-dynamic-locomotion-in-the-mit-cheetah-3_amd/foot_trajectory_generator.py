@@ -2,13 +2,14 @@
 
 Call surface of the reference's ``FootTrajectoryGenerator`` (src/foot_trajectory_generator.py:4-157):
 ``generate_feet_trajectories_at_time(time, foot) -> {'pos','vel','acc'}`` (6-vectors: angle, position).
-Cubic blend in x/y/angle and a quartic bump in z over the first 80 % of the single-support phase.
+Cubic blend in x/y/angle and a quartic bump in z over the first 80 % of the single-support phase.  ``swing_tables`` runs it over
+plan tables of B robots in the layout of the device generator (include/mpcqp_plan.h) and is its host checker.
 """
 from __future__ import annotations
 
 import numpy as np
 
-from .footstep_planner import LEGS, _LEG_INDEX
+from .footstep_planner import LEGS, _LEG_INDEX, FootstepPlanner
 
 
 class FootTrajectoryGenerator:
@@ -66,3 +67,34 @@ class FootTrajectoryGenerator:
             a.plot(ts, [x[key][3 + ax] for x in d]); a.set_ylabel(key); a.grid()
         plt.suptitle(f"{foot_to_sample} along {string_axs}")
         plt.show()
+
+
+def swing_tables(plan, tick, K, step_height, dt):
+    """Host reference of mpcqp_swing_trajectories (include/mpcqp_plan.h).  `plan`: numpy tables as written by
+    mpcqp_plan_footsteps / footstep_planner.plan_tables (plan_pos, plan_feet_id, plan_meta, plan_ang); tick [B]; step_height [B].
+    Returns traj [B,K,4,3,6] (pos / vel / acc 6-vectors of generate_feet_trajectories_at_time at ticks tick[b] + j) and feet_des
+    [B,K,4,3]: the desired feet of the closed loop of src/main.py:152-167, run from tick 0 so that the generator's side effect on
+    the plan (ftg.py:53-54) has happened exactly as in that loop.  Needs ss + ds >= 1."""
+    pos, fid = np.asarray(plan["plan_pos"], float), np.asarray(plan["plan_feet_id"])
+    meta, ang = np.asarray(plan["plan_meta"]), np.asarray(plan["plan_ang"], float)
+    B, S = pos.shape[:2]
+    traj, des = np.zeros((B, K, 4, 3, 6)), np.zeros((B, K, 4, 3))
+    for b in range(B):
+        Sb = min(max(int(meta[b, 0]), 1), S)
+        pl = FootstepPlanner.from_tables(pos[b, :Sb], fid[b, :Sb], ang[b, :Sb], max(int(meta[b, 1]), 0), max(int(meta[b, 2]), 0))
+        tg = FootTrajectoryGenerator(pl, {"world_time_step": dt, "step_height": float(step_height[b])})
+        t0 = max(int(tick[b]), 0)
+        for t in range(t0 + K):
+            si = pl.get_step_index_at_time(t)
+            gait = pl.plan[si]["feet_id"]
+            for k, leg in enumerate(LEGS):
+                d = tg.generate_feet_trajectories_at_time(t, leg)
+                if t < t0:
+                    continue
+                traj[b, t - t0, k] = d["pos"], d["vel"], d["acc"]
+                if gait[k] == 1:
+                    des[b, t - t0, k] = pl.pos[si, k]
+                else:
+                    des[b, t - t0, k] = d["pos"][3:]
+                    des[b, t - t0, k, 2] = max(d["pos"][5], 0.0)
+    return traj, des

@@ -3,7 +3,9 @@
 Call surface kept from the reference's ``FootstepPlanner`` (src/footstep_planner.py:5-256): constructor
 ``(initial_configuration, params, show=...)``, attribute ``plan`` (list of dicts with ``pos``, ``ang``,
 ``ss_duration``, ``ds_duration``, ``feet_id``), ``get_step_index_at_time``, ``get_start_time``,
-``get_phase_at_time``, ``is_swing``.  Internals are array based (the reference walks the list linearly for every
+``get_phase_at_time``, ``is_swing``.  ``plan_tables`` lays plans of B robots out in the table form of the device planner
+(include/mpcqp_plan.h) and is its host checker; ``FootstepPlanner.from_tables`` wraps one robot's device-made rows back into a
+planner object for reference-style callers.  Internals are array based (the reference walks the list linearly for every
 query, src/footstep_planner.py:226-237): step boundaries are a cumulative table, so queries are O(log S) and the
 horizon-wide contact mask / stance positions the engine needs are produced in one vectorised call.
 """
@@ -75,6 +77,22 @@ class FootstepPlanner:
         if show:
             self.show()
 
+    @classmethod
+    def from_tables(cls, pos, feet_id, ang, ss, ds, hip=None):
+        """A planner over given plan rows -- one robot's plan_pos [S,4,3], plan_feet_id [S,4] and plan_ang [S] as written by
+        mpcqp_plan_footsteps (cut at plan_meta[0]) -- with every query and the dict-shaped `plan` view of a constructed one."""
+        self = cls.__new__(cls)
+        self.pos = np.array(pos, dtype=float)
+        self.ang = np.array(ang, dtype=float)
+        self.feet_id = np.array(feet_id, dtype=int)
+        S = len(self.pos)
+        self.hip = np.full((S, 3), np.nan) if hip is None else np.array(hip, dtype=float)
+        self.ss = np.full(S, int(ss), dtype=int)
+        self.ds = np.full(S, int(ds), dtype=int)
+        self.step_end = np.cumsum(self.ss + self.ds)
+        self.plan = _PlanView(self)
+        return self
+
     # ------------------------------------------------------------------ reference queries (:226-256)
     def get_step_index_at_time(self, time):
         i = int(np.searchsorted(self.step_end, time, side="right"))
@@ -113,6 +131,37 @@ class FootstepPlanner:
         plt.plot(self.hip[:, 0], self.hip[:, 1], "k.", label="hip")
         plt.xlabel("x (m)"); plt.ylabel("y (m)"); plt.legend(); plt.grid(True); plt.title("Footstep plan")
         plt.show()
+
+
+STANDING_STEPS = 100      # total_steps == 0: the standing plan's length (src/footstep_planner.py:53-71)
+MAX_STEP_TICKS = 65535    # the device planner clamps ss / ds into [0, MAX_STEP_TICKS] (include/mpcqp_plan.h)
+
+
+def plan_tables(feet0, cmd, gait, S, dt):
+    """Host reference of mpcqp_plan_footsteps (include/mpcqp_plan.h): one FootstepPlanner per robot, laid out in table form.
+    feet0 [B,4,3]; cmd [B,5] = yaw0, v_com_ref x, v_com_ref y, theta_dot, h; gait [B,4] = total_steps, ss, ds, first_swing bit mask
+    (bit k = leg k stays down in step 1).  Returns float64 plan_pos [B,S,4,3], plan_ang [B,S], plan_hip [B,S,3], uint8 plan_feet_id
+    [B,S,4] and int32 plan_meta [B,4] = (min(steps, S), ss, ds, 0); rows past the plan repeat its last row.  Clamps as the device:
+    total_steps < 0 is the standing plan, ss / ds are clamped into [0, MAX_STEP_TICKS]."""
+    feet0, cmd, gait = np.asarray(feet0, float), np.asarray(cmd, float), np.asarray(gait, np.int64)
+    B, S = len(feet0), int(S)
+    out = {"plan_pos": np.zeros((B, S, 4, 3)), "plan_feet_id": np.zeros((B, S, 4), np.uint8), "plan_meta": np.zeros((B, 4), np.int32),
+           "plan_ang": np.zeros((B, S)), "plan_hip": np.zeros((B, S, 3))}
+    for b in range(B):
+        total = max(int(gait[b, 0]), 0)
+        ss, ds = (min(max(int(v), 0), MAX_STEP_TICKS) for v in gait[b, 1:3])
+        rows = min(total if total > 0 else STANDING_STEPS, S)
+        params = {"ss_duration": ss, "ds_duration": ds, "world_time_step": dt, "h": float(cmd[b, 4]),
+                  "v_com_ref": np.array([cmd[b, 1], cmd[b, 2], 0.0]), "theta_dot": float(cmd[b, 3]),
+                  # the recurrence is causal: planning the first `rows` steps gives the same rows as planning all of them
+                  "total_steps": min(total, rows), "first_swing": np.array([(int(gait[b, 3]) >> k) & 1 for k in range(4)])}
+        initial = {l: feet0[b, k] for k, l in enumerate(LEGS)}
+        initial["yaw"] = float(cmd[b, 0])
+        pl = FootstepPlanner(initial, params, show=False)
+        idx = np.minimum(np.arange(S), rows - 1)
+        out["plan_pos"][b], out["plan_feet_id"][b], out["plan_ang"][b], out["plan_hip"][b] = pl.pos[idx], pl.feet_id[idx], pl.ang[idx], pl.hip[idx]
+        out["plan_meta"][b] = (rows, ss, ds, 0)
+    return out
 
 
 class _StepView(dict):

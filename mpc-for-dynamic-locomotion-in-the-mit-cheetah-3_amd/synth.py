@@ -267,3 +267,21 @@ def make_rollout_batch(B, N=10, delta=0.03, seed=20250813, gait_names=("trot", "
         ref[b] = [0.0, 0.0, 0.0, com[0], com[1], H_COM, v_ref[0], v_ref[1], v_ref[2], 0.0]
     return {"x": x, "ref": ref, "plan_pos": pos, "plan_feet_id": fid, "plan_meta": meta, "tick": np.zeros(B, np.int32), "mu": mu,
             "gait_ids": gid}
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# Footstep-planner inputs (include/mpcqp_plan.h, mpcqp_plan_footsteps): heterogeneous commands and gaits
+# ----------------------------------------------------------------------------------------------------------------------
+def make_plan_inputs(B, seed=20250901, total_steps=(0, 1, 2, 3, 7, 20, 50), ss=(4, 10, 3), ds=(2, 5, 0), theta_dot=(0.0, 0.3, -0.3, 1.0),
+                     step_height=(0.05, 0.08)):
+    """B robots' planner inputs: feet0 [B,4,3] around a random torso position, cmd [B,5] (random yaw0, forward and lateral velocity,
+    theta_dot drawn from `theta_dot`, h), gait int32 [B,4] (total_steps, ss, ds drawn from the given sets; first_swing cycles
+    through all 16 masks) and step_height [B]."""
+    rng = np.random.default_rng(seed)
+    com = np.concatenate([rng.uniform(-1.0, 1.0, (B, 2)), np.full((B, 1), H_COM)], axis=1)
+    feet0 = NOMINAL_FEET[None] + com[:, None, :] + np.concatenate([rng.normal(0.0, 0.003, (B, 4, 2)), np.zeros((B, 4, 1))], axis=2)
+    pick = lambda vals: np.asarray(vals)[rng.integers(0, len(vals), B)]
+    cmd = np.stack([rng.uniform(-np.pi, np.pi, B), rng.uniform(-0.1, 0.3, B), rng.uniform(-0.1, 0.1, B), pick(theta_dot),
+                    np.full(B, H_COM)], axis=1)
+    gait = np.stack([pick(total_steps), pick(ss), pick(ds), np.arange(B) % 16], axis=1).astype(np.int32)
+    return {"feet0": feet0, "cmd": cmd, "gait": gait, "step_height": pick(step_height).astype(float)}
