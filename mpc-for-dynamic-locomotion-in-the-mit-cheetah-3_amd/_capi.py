@@ -1,4 +1,4 @@
-"""ctypes binding of the C-ABI declared in include/mpcqp.h and its product-only extension include/mpcqp_plan.h.
+"""ctypes binding of the C-ABI declared in include/mpcqp.h and its product-only extensions include/mpcqp_plan.h and include/mpcqp_sim.h.
 
 The product path loads ``csrc/libmpcqp.so`` (hand-written HIP for gfx950) and nothing else: if that library is
 missing or cannot be loaded, importing the engine raises -- there is no CPU fallback.  The binding itself is
@@ -48,6 +48,8 @@ EXPORTED_SYMBOLS = (
 
 # include/mpcqp_plan.h: exported by the product library only (the CPU checker under oracle/ does not have them)
 PLAN_SYMBOLS = ("mpcqp_plan_footsteps", "mpcqp_swing_trajectories")
+# include/mpcqp_sim.h: the rigid-body plant, likewise product-only
+SIM_SYMBOLS = ("mpcqp_plant_step", "mpcqp_rollout_plant")
 
 
 class MpcQpLegGeometry(ctypes.Structure):
@@ -123,6 +125,12 @@ class Library:
             L.mpcqp_plan_footsteps.restype = c_int32
             L.mpcqp_swing_trajectories.argtypes = [c_void_p, c_int64, c_int32, c_int32] + [c_void_p] * 9
             L.mpcqp_swing_trajectories.restype = c_int32
+        self.has_sim = all(hasattr(L, sym) for sym in SIM_SYMBOLS)
+        if self.has_sim:
+            L.mpcqp_plant_step.argtypes = [c_void_p, c_int64] + [c_void_p] * 6 + [c_int32, c_void_p, c_void_p]
+            L.mpcqp_plant_step.restype = c_int32
+            L.mpcqp_rollout_plant.argtypes = [c_void_p, c_int64, c_int32, c_int32] + [c_void_p] * 10 + [c_int32] + [c_void_p] * 5
+            L.mpcqp_rollout_plant.restype = c_int32
 
     def version(self) -> int:
         return int(self.lib.mpcqp_version())
@@ -252,6 +260,28 @@ class Engine:
                                                           traj or None, feet_des or None, stream or None)
         if rc != 0:
             raise MpcQpError(f"mpcqp_swing_trajectories failed with code {rc}: {self.last_error()}")
+
+    def _sim_call(self, name):
+        if not self.library.has_sim:
+            raise MpcQpError(f"{name}: {self.library.path} does not export include/mpcqp_sim.h (product library only)")
+        return getattr(self.library.lib, name)
+
+    def plant_step_ptr(self, B, x, f, feet, contact, body, wrench, substeps, x_out, stream=0):
+        """Raw call of the rigid-body plant (include/mpcqp_sim.h, mpcqp_plant_step); every argument is an integer address."""
+        rc = self._sim_call("mpcqp_plant_step")(self._h, int(B), x or None, f or None, feet or None, contact or None, body or None,
+                                                 wrench or None, int(substeps), x_out or None, stream or None)
+        if rc != 0:
+            raise MpcQpError(f"mpcqp_plant_step failed with code {rc}: {self.last_error()}")
+
+    def rollout_plant_ptr(self, B, T, S, x, ref, plan_pos, plan_feet_id, plan_meta, tick, mu, body, push, push_ticks, substeps,
+                          actual, desired, forces, solved, stream=0):
+        """Raw call of the roll-out on the rigid-body plant (include/mpcqp_sim.h, mpcqp_rollout_plant); integer addresses."""
+        rc = self._sim_call("mpcqp_rollout_plant")(self._h, int(B), int(T), int(S), x or None, ref or None, plan_pos or None,
+                                                    plan_feet_id or None, plan_meta or None, tick or None, mu or None, body or None,
+                                                    push or None, push_ticks or None, int(substeps), actual or None, desired or None,
+                                                    forces or None, solved or None, stream or None)
+        if rc != 0:
+            raise MpcQpError(f"mpcqp_rollout_plant failed with code {rc}: {self.last_error()}")
 
     def torque_map_ptr(self, B, u, jac, tau, stream=0):
         rc = self.library.lib.mpcqp_torque_map(self._h, int(B), u, jac, tau, stream or None)

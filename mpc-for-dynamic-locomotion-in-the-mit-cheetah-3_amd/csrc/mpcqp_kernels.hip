@@ -9,7 +9,8 @@
 //   mpcqp_stage.h    stage-wise (Riccati) form of the same engine for any other horizon up to 64 -- the reference's own N = 60
 //   mpcqp_common.h   what they share: operator-tuple descriptor, policy constants, the dispatch-order pre-pass;  mpcqp_device.h: DPP helpers
 // plus the element-wise kernels around the solve: gait-descriptor expansion, closed-loop roll-out (expand / advance), torque map,
-// and (mpcqp_plan.h, C-ABI include/mpcqp_plan.h) footstep plans and swing-foot trajectories.
+// (mpcqp_plan.h, C-ABI include/mpcqp_plan.h) footstep plans and swing-foot trajectories, and (mpcqp_plant.h, C-ABI
+// include/mpcqp_sim.h) the rigid-body plant that can replace the roll-out's world step.
 // DESIGN.md has the derivations.
 
 #include "mpcqp_wrench.h"
@@ -252,6 +253,8 @@ mpcqp_rollout_advance_kernel(TIO* __restrict__ x, TIO* __restrict__ ref, const R
 }
 
 }  // namespace
+
+#include "mpcqp_plant.h"   // the rigid-body plant (C-ABI include/mpcqp_sim.h): its roll-out advance reads RolloutPlan
 
 // ======================================================================================================
 // C-ABI (include/mpcqp.h)
@@ -781,15 +784,24 @@ int mpcqp_solve_batch_gait(mpcqp_handle h, int64_t B, const void* x0, const void
   return mpcqp_solve_batch_gait_steps(h, B, 2, x0, ref, feet0, footholds, gait, feet_id, mu, u_out, X_out, status, iters, res, stream);
 }
 
-int mpcqp_rollout(mpcqp_handle h, int64_t B, int32_t T, int32_t S, void* x, void* ref, const void* plan_pos, const uint8_t* plan_feet_id,
-                  const int32_t* plan_meta, int32_t* tick, const void* mu, void* actual, void* desired, void* forces, int32_t* solved,
-                  void* stream) {
-  if (!h) return MPCQP_EINVAL;
-  if (B < 0 || B > 0x7fffffff || T < 0 || S < 1) return fail(h, MPCQP_EINVAL, "mpcqp_rollout: size out of range");
-  if (B > 0 && (!x || !ref || !plan_pos || !plan_feet_id || !plan_meta || !tick || !mu)) return fail(h, MPCQP_EINVAL, "mpcqp_rollout: null buffer");
-  if (B == 0 || T == 0) return MPCQP_OK;
-  DeviceGuard guard(h->cfg.device);
-  if (guard.err != hipSuccess) return fail(h, MPCQP_EHIP, "hipSetDevice", guard.err);
+extern "C++" {   // (inside the C-ABI block: the roll-out driver and its plant arguments are C++)
+namespace {
+
+// Roll-out arguments of the plant (mpcqp_rollout_plant); null for mpcqp_rollout, whose world step is x <- X[:,1].
+struct RolloutPlantArgs { const void* body; const void* push; const int32_t* push_ticks; int n; };
+
+PlantModel plant_model(const mpcqp_engine* h) {
+  return {h->cfg.m, 1.0 / h->cfg.Ibody_inv[0], 1.0 / h->cfg.Ibody_inv[1], 1.0 / h->cfg.Ibody_inv[2]};
+}
+
+template <typename TIO>
+PlantIn<TIO> plant_in(const mpcqp_engine* h, const RolloutPlantArgs& a) {
+  return {(const TIO*)a.body, (const TIO*)a.push, a.push_ticks, plant_model(h), a.n, h->cfg.delta / a.n};
+}
+
+int rollout_run(mpcqp_handle h, int64_t B, int32_t T, int32_t S, void* x, void* ref, const void* plan_pos, const uint8_t* plan_feet_id,
+                const int32_t* plan_meta, int32_t* tick, const void* mu, void* actual, void* desired, void* forces, int32_t* solved,
+                void* stream, const RolloutPlantArgs* plant) {
   const size_t el = h->cfg.dtype == MPCQP_DTYPE_F64 ? 8 : 4, N = (size_t)h->cfg.N;
   if (reserve_gait(h, B) != MPCQP_OK) return fail(h, MPCQP_ENOMEM, "mpcqp_rollout: workspace allocation failed");
   if (h->roll_cap < B) {
@@ -825,7 +837,15 @@ int mpcqp_rollout(mpcqp_handle h, int64_t B, int32_t T, int32_t S, void* x, void
                          (int)N, (int)S, B, (float*)r, contact, (float*)xdes);
     const int rc = mpcqp_solve_batch(h, B, x, r, contact, xdes, mu, u, X, status, iters, nullptr, stream);
     if (rc != MPCQP_OK) return rc;
-    if (el == 8)
+    if (plant && el == 8)
+      hipLaunchKernelGGL((mpcqp_rollout_plant_advance_kernel<double>), ga, dim3(256), 0, st, (double*)x, (double*)ref, plan, tick, (const double*)u,
+                         status, plant_in<double>(h, *plant), h->cfg.delta, (int)N, B, (int)T, it, (int)S, (double*)actual, (double*)desired,
+                         (double*)forces, solved);
+    else if (plant)
+      hipLaunchKernelGGL((mpcqp_rollout_plant_advance_kernel<float>), ga, dim3(256), 0, st, (float*)x, (float*)ref, plan, tick, (const float*)u,
+                         status, plant_in<float>(h, *plant), h->cfg.delta, (int)N, B, (int)T, it, (int)S, (float*)actual, (float*)desired,
+                         (float*)forces, solved);
+    else if (el == 8)
       hipLaunchKernelGGL((mpcqp_rollout_advance_kernel<double>), ga, dim3(256), 0, st, (double*)x, (double*)ref, plan, tick, (const double*)X,
                          (const double*)u, status, h->cfg.delta, (int)N, B, (int)T, it, (int)S, (double*)actual, (double*)desired, (double*)forces, solved);
     else
@@ -838,6 +858,69 @@ int mpcqp_rollout(mpcqp_handle h, int64_t B, int32_t T, int32_t S, void* x, void
     if (hipEventRecord(h->ev1, st) != hipSuccess) return fail(h, MPCQP_EHIP, "hipEventRecord");
     h->timed = true;
   }
+  return MPCQP_OK;
+}
+
+// substeps of include/mpcqp_sim.h: 0 means the default, [1, 1000] as given; -1 for out of range
+int plant_substeps(int32_t substeps) {
+  if (substeps < 0 || substeps > PLANT_MAX_SUBSTEPS) return -1;
+  return substeps == 0 ? PLANT_DEFAULT_SUBSTEPS : substeps;
+}
+
+}  // namespace
+}  // extern "C++"
+
+int mpcqp_rollout(mpcqp_handle h, int64_t B, int32_t T, int32_t S, void* x, void* ref, const void* plan_pos, const uint8_t* plan_feet_id,
+                  const int32_t* plan_meta, int32_t* tick, const void* mu, void* actual, void* desired, void* forces, int32_t* solved,
+                  void* stream) {
+  if (!h) return MPCQP_EINVAL;
+  if (B < 0 || B > 0x7fffffff || T < 0 || S < 1) return fail(h, MPCQP_EINVAL, "mpcqp_rollout: size out of range");
+  if (B > 0 && (!x || !ref || !plan_pos || !plan_feet_id || !plan_meta || !tick || !mu)) return fail(h, MPCQP_EINVAL, "mpcqp_rollout: null buffer");
+  if (B == 0 || T == 0) return MPCQP_OK;
+  DeviceGuard guard(h->cfg.device);
+  if (guard.err != hipSuccess) return fail(h, MPCQP_EHIP, "hipSetDevice", guard.err);
+  return rollout_run(h, B, T, S, x, ref, plan_pos, plan_feet_id, plan_meta, tick, mu, actual, desired, forces, solved, stream, nullptr);
+}
+
+int mpcqp_rollout_plant(mpcqp_handle h, int64_t B, int32_t T, int32_t S, void* x, void* ref, const void* plan_pos,
+                        const uint8_t* plan_feet_id, const int32_t* plan_meta, int32_t* tick, const void* mu, const void* body,
+                        const void* push, const int32_t* push_ticks, int32_t substeps, void* actual, void* desired, void* forces,
+                        int32_t* solved, void* stream) {
+  if (!h) return MPCQP_EINVAL;
+  if (B < 0 || B > 0x7fffffff || T < 0 || S < 1) return fail(h, MPCQP_EINVAL, "mpcqp_rollout_plant: size out of range");
+  const int n = plant_substeps(substeps);
+  if (n < 0) return fail(h, MPCQP_EINVAL, "mpcqp_rollout_plant: substeps out of range [0, 1000]");
+  if (push && !push_ticks) return fail(h, MPCQP_EINVAL, "mpcqp_rollout_plant: push without push_ticks");
+  if (B > 0 && (!x || !ref || !plan_pos || !plan_feet_id || !plan_meta || !tick || !mu))
+    return fail(h, MPCQP_EINVAL, "mpcqp_rollout_plant: null buffer");
+  if (B == 0 || T == 0) return MPCQP_OK;
+  DeviceGuard guard(h->cfg.device);
+  if (guard.err != hipSuccess) return fail(h, MPCQP_EHIP, "hipSetDevice", guard.err);
+  const RolloutPlantArgs plant = {body, push, push ? push_ticks : nullptr, n};
+  return rollout_run(h, B, T, S, x, ref, plan_pos, plan_feet_id, plan_meta, tick, mu, actual, desired, forces, solved, stream, &plant);
+}
+
+int mpcqp_plant_step(mpcqp_handle h, int64_t B, const void* x, const void* f, const void* feet, const uint8_t* contact,
+                     const void* body, const void* wrench, int32_t substeps, void* x_out, void* stream) {
+  if (!h) return MPCQP_EINVAL;
+  if (B < 0 || B > 0x7fffffff) return fail(h, MPCQP_EINVAL, "mpcqp_plant_step: batch size out of range");
+  const int n = plant_substeps(substeps);
+  if (n < 0) return fail(h, MPCQP_EINVAL, "mpcqp_plant_step: substeps out of range [0, 1000]");
+  if (B > 0 && (!x || !f || !feet || !contact || !x_out)) return fail(h, MPCQP_EINVAL, "mpcqp_plant_step: null buffer");
+  if (B == 0) return MPCQP_OK;
+  DeviceGuard guard(h->cfg.device);
+  if (guard.err != hipSuccess) return fail(h, MPCQP_EHIP, "hipSetDevice", guard.err);
+  const dim3 grid((unsigned)((B + 255) / 256));
+  const double hstep = h->cfg.delta / n;
+  hipStream_t st = (hipStream_t)stream;
+  if (h->cfg.dtype == MPCQP_DTYPE_F64)
+    hipLaunchKernelGGL((mpcqp_plant_step_kernel<double>), grid, dim3(256), 0, st, (const double*)x, (const double*)f, (const double*)feet,
+                       contact, (const double*)body, (const double*)wrench, plant_model(h), n, hstep, B, (double*)x_out);
+  else
+    hipLaunchKernelGGL((mpcqp_plant_step_kernel<float>), grid, dim3(256), 0, st, (const float*)x, (const float*)f, (const float*)feet,
+                       contact, (const float*)body, (const float*)wrench, plant_model(h), n, hstep, B, (float*)x_out);
+  const hipError_t he = hipGetLastError();
+  if (he != hipSuccess) return fail(h, MPCQP_EHIP, "plant kernel launch", he);
   return MPCQP_OK;
 }
 

@@ -149,6 +149,56 @@ class MPCBatch:
                                 tick.data_ptr(), mu.data_ptr(), p(actual), p(desired), p(forces), solved.data_ptr(), st.cuda_stream)
         return {"actual": actual, "desired": desired, "forces": forces, "solved": solved}
 
+    def _check_plant_rows(self, B, body, extra):
+        torch = _torch()
+        rows = [(body, (B, 7), self.tdtype)] + extra
+        for t, shape, dt in rows:
+            if t is not None and (tuple(t.shape) != shape or t.dtype != dt or not t.is_contiguous() or t.device != self.device):
+                raise ValueError(f"operand mismatch: expected {shape} {dt} contiguous on {self.device}, got {tuple(t.shape)} {t.dtype} on {t.device}")
+
+    def plant_step(self, x, f, feet, contact, body=None, wrench=None, substeps=10, stream=None):
+        """One control period of the rigid-body plant for B robots (include/mpcqp_sim.h, mpcqp_plant_step): x [B,13], f [B,12] foot
+        forces held over the tick, feet [B,4,3] world foot positions, contact uint8 [B,4] (nonzero = stance), body [B,7] (m, Ixx, Iyy,
+        Izz, Ixy, Ixz, Iyz; None = the engine's model), wrench [B,6] (force, torque about the CoM; None = no push).  Returns a new
+        [B,13] tensor; asynchronous on `stream`.  The host checker is plant.srb_step."""
+        torch = _torch()
+        B = int(x.shape[0])
+        for t, shape, dt in ((x, (B, 13), self.tdtype), (f, (B, 12), self.tdtype), (feet, (B, 4, 3), self.tdtype), (contact, (B, 4), torch.uint8)):
+            if tuple(t.shape) != shape or t.dtype != dt or not t.is_contiguous() or t.device != self.device:
+                raise ValueError(f"operand mismatch: expected {shape} {dt} contiguous on {self.device}, got {tuple(t.shape)} {t.dtype} on {t.device}")
+        self._check_plant_rows(B, body, [(wrench, (B, 6), self.tdtype)])
+        st = stream if stream is not None else torch.cuda.current_stream(self.device)
+        with torch.cuda.stream(st):
+            out = torch.empty((B, 13), dtype=self.tdtype, device=self.device)
+        p = lambda t: t.data_ptr() if t is not None else 0
+        self.engine.plant_step_ptr(B, x.data_ptr(), f.data_ptr(), feet.data_ptr(), contact.data_ptr(), p(body), p(wrench), substeps,
+                                   out.data_ptr(), st.cuda_stream)
+        return out
+
+    def rollout_plant(self, x, ref, plan_pos, plan_feet_id, plan_meta, tick, mu, T, body=None, push=None, push_ticks=None, substeps=10,
+                      log=True, stream=None):
+        """`rollout` with the world step x <- X[:,1] replaced by the rigid-body plant (include/mpcqp_sim.h, mpcqp_rollout_plant):
+        body [B,7] per-robot mass and torso-frame inertia (None = the engine's model), push [B,6] a world-frame wrench acting on the
+        robot's own ticks push_ticks[b][0] <= tick < push_ticks[b][1] (int32 [B,2], required with push).  Same in-place advance of
+        `x`, `ref` and `tick`, same logs and `solved` count as `rollout`."""
+        torch = _torch()
+        B, S = int(plan_pos.shape[0]), int(plan_pos.shape[1])
+        for t, shape, dt in ((x, (B, 13), self.tdtype), (ref, (B, 10), self.tdtype), (plan_pos, (B, S, 4, 3), self.tdtype),
+                             (plan_feet_id, (B, S, 4), torch.uint8), (plan_meta, (B, 4), torch.int32), (tick, (B,), torch.int32),
+                             (mu, (B,), self.tdtype)):
+            if tuple(t.shape) != shape or t.dtype != dt or not t.is_contiguous() or t.device != self.device:
+                raise ValueError(f"operand mismatch: expected {shape} {dt} contiguous on {self.device}, got {tuple(t.shape)} {t.dtype} on {t.device}")
+        self._check_plant_rows(B, body, [(push, (B, 6), self.tdtype), (push_ticks, (B, 2), torch.int32)])
+        mk = lambda: torch.empty((B, T, 12), dtype=self.tdtype, device=self.device) if log else None
+        actual, desired, forces = mk(), mk(), mk()
+        st = stream if stream is not None else torch.cuda.current_stream(self.device)
+        solved = (torch.empty if T > 0 else torch.zeros)(B, dtype=torch.int32, device=self.device)
+        p = lambda t: t.data_ptr() if t is not None else None
+        self.engine.rollout_plant_ptr(B, T, S, x.data_ptr(), ref.data_ptr(), plan_pos.data_ptr(), plan_feet_id.data_ptr(),
+                                      plan_meta.data_ptr(), tick.data_ptr(), mu.data_ptr(), p(body), p(push), p(push_ticks), substeps,
+                                      p(actual), p(desired), p(forces), solved.data_ptr(), st.cuda_stream)
+        return {"actual": actual, "desired": desired, "forces": forces, "solved": solved}
+
     def plan_footsteps(self, feet0, cmd, gait, S, want_ang=True, want_hip=False, stream=None):
         """Footstep plans of B robots on the device (include/mpcqp_plan.h, mpcqp_plan_footsteps; the host FootstepPlanner per robot):
         feet0 [B,4,3] initial feet FL, FR, HL, HR and cmd [B,5] (yaw0, v_com_ref x, v_com_ref y, theta_dot, h) of the engine's dtype,

@@ -285,3 +285,31 @@ def make_plan_inputs(B, seed=20250901, total_steps=(0, 1, 2, 3, 7, 20, 50), ss=(
                     np.full(B, H_COM)], axis=1)
     gait = np.stack([pick(total_steps), pick(ss), pick(ds), np.arange(B) % 16], axis=1).astype(np.int32)
     return {"feet0": feet0, "cmd": cmd, "gait": gait, "step_height": pick(step_height).astype(float)}
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# Plant rows (include/mpcqp_sim.h, mpcqp_rollout_plant): heterogeneous bodies and push schedules
+# ----------------------------------------------------------------------------------------------------------------------
+def make_plant_rows(B, seed=20251016, m=8.885, ibody=(0.24, 1.0, 1.0), mass_scale=(0.8, 1.25), inertia_scale=(0.7, 1.5), offdiag=0.05,
+                    push_frac=0.5, push_force=(10.0, 40.0), push_torque=(0.0, 2.0), push_start=(5, 25), push_len=(1, 5)):
+    """B robots' plant rows around the model (m, diag(ibody)): body [B,7] = (m, Ixx, Iyy, Izz, Ixy, Ixz, Iyz) with the mass scaled
+    uniformly in `mass_scale`, the principal moments each in `inertia_scale`, and off-diagonal terms of up to `offdiag` of the
+    smaller moment of their pair, so every row is positive definite and none is the model's; push [B,6] world-frame wrenches
+    (a horizontal force of |F| in `push_force` N in a random direction, a torque of |tau| in `push_torque` N m) on a `push_frac`
+    share of the robots, zero elsewhere; push_ticks int32 [B,2] = [start, start + length) (an empty window where there is no push)."""
+    rng = np.random.default_rng(seed)
+    I0 = np.asarray(ibody, float)
+    d = I0[None] * rng.uniform(*inertia_scale, (B, 3))
+    pairs = ((0, 1), (0, 2), (1, 2))
+    off = np.stack([rng.uniform(-offdiag, offdiag, B) * np.minimum(d[:, i], d[:, j]) for i, j in pairs], axis=1)
+    body = np.concatenate([(m * rng.uniform(*mass_scale, B))[:, None], d, off], axis=1)
+    pushed = rng.uniform(0.0, 1.0, B) < push_frac
+    ang = rng.uniform(-np.pi, np.pi, B)
+    F = rng.uniform(*push_force, B)
+    tau = rng.normal(0.0, 1.0, (B, 3))
+    tau *= (rng.uniform(*push_torque, B) / np.maximum(np.linalg.norm(tau, axis=1), 1e-12))[:, None]
+    push = np.concatenate([np.stack([F * np.cos(ang), F * np.sin(ang), np.zeros(B)], axis=1), tau], axis=1) * pushed[:, None]
+    start = rng.integers(push_start[0], push_start[1] + 1, B)
+    length = rng.integers(push_len[0], push_len[1] + 1, B)
+    push_ticks = np.stack([start, np.where(pushed, start + length, start)], axis=1).astype(np.int32)
+    return {"body": body, "push": push, "push_ticks": push_ticks, "pushed": pushed}
