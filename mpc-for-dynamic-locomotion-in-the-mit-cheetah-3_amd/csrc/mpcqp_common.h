@@ -12,7 +12,7 @@ __device__ __forceinline__ f2 mk2(float a, float b) { f2 t = {a, b}; return t; }
 __device__ __forceinline__ f2 splat2(float v) { return mk2(v, v); }
 
 // Inputs of one solve: the operator tuple (x0, r, contact, xdes, mu).  The descriptor fields belong to the gait entry point,
-// whose expansion kernel (mpcqp_kernels.hip) turns them into a tuple in the engine's workspace before the solve.
+// whose expansion kernel (mpcqp_elementwise.h) turns them into a tuple in the engine's workspace before the solve.
 template <typename TIO>
 struct FastIn {
   const TIO* x0; const TIO* r; const uint8_t* contact; const TIO* xdes; const TIO* mu;             // tuple form

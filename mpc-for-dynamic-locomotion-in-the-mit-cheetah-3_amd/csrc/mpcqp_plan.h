@@ -1,6 +1,7 @@
 // mpcqp_plan.h -- footstep plans and swing-foot trajectories on the device (the C-ABI is include/mpcqp_plan.h; its entry points
-// live in mpcqp_kernels.hip next to the other element-wise kernels).  Everything here is fp64 arithmetic with T-typed I/O, in the
-// host ports' operation order and without contraction into fused multiply-adds (footstep_planner.py, foot_trajectory_generator.py).
+// live in mpcqp_kernels.hip), and the plan clock that every reader of a plan table decodes its meta row with (the swing kernel here,
+// the expand / advance kernels of mpcqp_elementwise.h).  The kernels here are fp64 arithmetic with T-typed I/O, in the host ports'
+// operation order and without contraction into fused multiply-adds (footstep_planner.py, foot_trajectory_generator.py).
 //
 //   planner   two launches.  (1) one lane per robot runs the sequential unicycle recurrence (theta += w dt, centre += R(theta) v dt,
 //             ss + ds ticks per step) and leaves theta, centre x / y, cos / sin theta of every step in an engine-owned [B,S,5] fp64
@@ -29,6 +30,37 @@ __device__ __forceinline__ PlanGait plan_gait(const int32_t* g, const int S) {
   p.ss = min(max(g[1], 0), PLAN_MAX_TICKS);
   p.ds = min(max(g[2], 0), PLAN_MAX_TICKS);
   return p;
+}
+
+// The plan clock: where tick tau falls in a plan whose meta row is [S, ss, ds, reserved].  The plan table lives in device memory the
+// host cannot inspect: malformed rows are clamped, never indexed with -- 1 <= S_b <= Smax, ss >= 0, ss + ds >= 1; callers clamp
+// tick >= 0 (include/mpcqp.h).  Past the plan: the last step with its time running on.  I is the caller's tick arithmetic: int
+// where tau stays within the horizon of a tick, int64_t in the swing kernel, whose tau = tick + K - 1 may pass 2^31.
+template <typename I>
+struct PlanClock {
+  int S;         // steps of the robot's plan
+  I ss, period;  // single-support ticks of a step, and all its ticks
+  int step;      // the step tau falls in
+  I tin;         // ... and the ticks into it
+  bool swing;    // ... which are single support: the step's own stance pattern holds (else every foot is down)
+  double gate;   // 0 on the last plan step, where the references are zeroed (src/mpc.py:181-183), else 1
+};
+
+template <typename I>
+__device__ __forceinline__ PlanClock<I> plan_clock(const int S, const int ss, const int ds, const int Smax, const I tau) {
+  PlanClock<I> c;
+  c.S = min(max(S, 1), Smax);
+  c.ss = max(ss, 0);
+  c.period = max(c.ss + max(ds, 0), (I)1);
+  c.step = (int)min(tau / c.period, (I)(c.S - 1));
+  c.tin = tau - c.step * c.period;
+  c.swing = c.tin < c.ss;
+  c.gate = c.step == c.S - 1 ? 0.0 : 1.0;
+  return c;
+}
+template <typename I>
+__device__ __forceinline__ PlanClock<I> plan_clock(const int32_t* meta, const int Smax, const I tau) {
+  return plan_clock(meta[0], meta[1], meta[2], Smax, tau);
 }
 
 template <typename TIO>
@@ -148,7 +180,7 @@ mpcqp_plan_tables_kernel(const TIO* __restrict__ feet0, const TIO* __restrict__ 
 }
 
 // One output group = (robot b, tick tick[b] + j, leg l): the pos / vel / acc 6-vectors of the trajectory and the logged desired
-// foot position.  Step index and time in step are closed form: s = min(tau / (ss + ds), S_b - 1).
+// foot position.  Step index and time in step are closed form (plan_clock).
 template <typename TIO>
 __global__ void __launch_bounds__(PLAN_BLOCK)
 mpcqp_swing_kernel(const TIO* __restrict__ pos, const uint8_t* __restrict__ fid, const int32_t* __restrict__ meta, const TIO* __restrict__ ang,
@@ -163,12 +195,9 @@ mpcqp_swing_kernel(const TIO* __restrict__ pos, const uint8_t* __restrict__ fid,
     const int l = (int)(gi & 3);
     const int64_t bj = gi >> 2, b = bj / K;
     const int j = (int)(bj - b * K);
-    const int32_t* m = meta + b * 4;
-    const int Sb = min(max(m[0], 1), Smax);
-    const int64_t ss = max(m[1], 0), period = max(ss + max(m[2], 0), (int64_t)1);
-    const int64_t tau = (int64_t)max(tick[b], 0) + j;
-    const int s = (int)min(tau / period, (int64_t)(Sb - 1)), nx = min(s + 1, Sb - 1);   // past the plan: target = start
-    const int64_t t = tau - s * period;
+    const PlanClock<int64_t> c = plan_clock(meta + b * 4, Smax, (int64_t)max(tick[b], 0) + j);
+    const int s = c.step, nx = min(s + 1, c.S - 1);        // past the plan: target = start
+    const int64_t ss = c.ss, t = c.tin;
     const TIO* p0 = pos + ((b * Smax + s) * 4 + l) * 3;
     const TIO* p1 = pos + ((b * Smax + nx) * 4 + l) * 3;
     const double a0 = (double)ang[b * Smax + s], a1 = (double)ang[b * Smax + nx];

@@ -1,5 +1,5 @@
 // mpcqp_plant.h -- the rigid-body plant of the device roll-out (the C-ABI is include/mpcqp_sim.h; its entry points live in
-// mpcqp_kernels.hip next to the other element-wise kernels, which include this file after the roll-out's own kernels).
+// mpcqp_kernels.hip; the roll-out's advance kernel, which takes a plant tick as its world step, in mpcqp_elementwise.h).
 //
 // Single rigid body, massless legs, forces held over the tick; integrated in a unit quaternion with classical RK4 over `substeps`
 // substeps, renormalised after each.  One thread per robot, fp64 arithmetic with T-typed I/O, in the host checker's operation order
@@ -205,56 +205,9 @@ mpcqp_plant_step_kernel(const TIO* x, const TIO* __restrict__ f, const TIO* __re
   for (int i = 0; i < 13; ++i) xo[b * 13 + i] = (TIO)out[i];
 }
 
+// The plant as the roll-out's world step (mpcqp_rollout_plant): per-robot body rows and pushes (either may be null), the push
+// window [push_ticks[2 b], push_ticks[2 b + 1]) in ticks, n substeps of h each.
 template <typename TIO>
 struct PlantIn { const TIO* body; const TIO* push; const int32_t* push_ticks; PlantModel model; int n; double h; };
-
-// mpcqp_rollout_plant's third launch per tick: mpcqp_rollout_advance_kernel's log rows, `solved`, reference roll-forward and tick
-// advance, with x <- X[:,1] replaced by one plant tick under the stage-0 forces of the solve.  Stance feet and contact are the expand
-// kernel's stage-0 rule.
-template <typename TIO>
-__global__ void __launch_bounds__(256)
-mpcqp_rollout_plant_advance_kernel(TIO* __restrict__ x, TIO* __restrict__ ref, const RolloutPlan plan, int32_t* __restrict__ tick,
-                                   const TIO* __restrict__ u, const int32_t* __restrict__ status, const PlantIn<TIO> pin, const double d,
-                                   const int N, const int64_t B, const int T, const int it, const int Smax, TIO* __restrict__ actual,
-                                   TIO* __restrict__ desired, TIO* __restrict__ forces, int32_t* __restrict__ solved) {
-  const int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (b >= B) return;
-  TIO* rf = ref + b * 10;
-  const int S = min(max(plan.meta[b * 4 + 0], 1), Smax), ss = max(plan.meta[b * 4 + 1], 0), period = max(ss + max(plan.meta[b * 4 + 2], 0), 1);
-  const int tk = tick[b], t0 = max(tk, 0);
-  const int step0 = min(t0 / period, S - 1), tin = t0 - step0 * period;
-  const double gate = step0 == S - 1 ? 0.0 : 1.0;
-  const size_t row = ((size_t)b * T + it) * 12;
-  if (actual) for (int c = 0; c < 12; ++c) actual[row + c] = x[b * 13 + c];
-  if (desired) {
-    const TIO des[12] = {rf[0], rf[1], rf[2], rf[3], rf[4], rf[5], (TIO)0, (TIO)0, (TIO)(gate * (double)rf[9]),
-                         (TIO)(gate * (double)rf[6]), (TIO)(gate * (double)rf[7]), (TIO)(gate * (double)rf[8])};
-    for (int c = 0; c < 12; ++c) desired[row + c] = des[c];
-  }
-  if (forces) for (int c = 0; c < 12; ++c) forces[row + c] = u[(size_t)b * N * 12 + c];
-  const int stt = status[b];
-  if (solved) solved[b] = (it == 0 ? 0 : solved[b]) + ((stt == MPCQP_STATUS_SOLVED_POLISHED || stt == MPCQP_STATUS_SOLVED_ADMM) ? 1 : 0);
-  // the world step: one plant tick
-  double xs[13], fs[12], ft[12], bd[7], wr[6], out[13];
-  bool st[4];
-  const TIO* pos = (const TIO*)plan.pos + (b * Smax + step0) * 12;
-  const uint8_t* fid = plan.feet_id + (b * Smax + step0) * 4;
-#pragma unroll
-  for (int i = 0; i < 13; ++i) xs[i] = (double)x[b * 13 + i];
-#pragma unroll
-  for (int i = 0; i < 12; ++i) { fs[i] = (double)u[(size_t)b * N * 12 + i]; ft[i] = (double)pos[i]; }
-#pragma unroll
-  for (int l = 0; l < 4; ++l) st[l] = tin < ss ? fid[l] != 0 : true;
-  plant_body_row(pin.body, pin.model, b, bd);
-  const bool pushed = pin.push && pin.push_ticks[2 * b] <= tk && tk < pin.push_ticks[2 * b + 1];
-#pragma unroll
-  for (int i = 0; i < 6; ++i) wr[i] = pushed ? (double)pin.push[b * 6 + i] : 0.0;
-  plant_tick(xs, fs, ft, st, bd, wr, pin.n, pin.h, out);
-#pragma unroll
-  for (int c = 0; c < 13; ++c) x[b * 13 + c] = (TIO)out[c];
-  for (int a = 0; a < 3; ++a) rf[3 + a] = (TIO)((double)rf[3 + a] + gate * (double)rf[6 + a] * d);   // src/mpc.py:261
-  rf[2] = (TIO)((double)rf[2] + gate * (double)rf[9] * d);                                      // src/mpc.py:262
-  tick[b] = tk + 1;
-}
 
 }  // namespace

@@ -1,0 +1,124 @@
+"""Developer aid for changes that must not change a result: seeded outputs of every entry point with whichever csrc/libmpcqp.so
+is in place, as raw arrays in one .npz, and their comparison byte for byte (integer views: NaN payloads and signed zeros count).
+Solves (tuple, gait S = 2, gait steps S = 4; f32 / f64 I/O; N = 10 / 20 / 60; MIXED / F64; warm start + shift over three calls),
+roll-outs on the model and on the plant (T = 50, B = 1024, cold and warm, with the malformed plan rows of tests/test_rollout.py),
+planner + swing trajectories, plant step, leg Jacobians and torque map.  One process per library build: copy the wanted build over
+csrc/libmpcqp.so before starting each.
+usage: dump_outputs.py OUT.npz            (needs a GPU)
+       dump_outputs.py --compare A.npz B.npz"""
+
+import os, sys
+import numpy as np
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, REPO); sys.path.insert(0, os.path.join(REPO, "tests"))
+
+
+def compare(pa, pb):
+    a, b = np.load(pa), np.load(pb)
+    bad = 0
+    for k in sorted(set(a.files) | set(b.files)):
+        if k not in a.files or k not in b.files:
+            print("ONLY ONE SIDE", k); bad += 1; continue
+        x, y = np.ascontiguousarray(a[k]), np.ascontiguousarray(b[k])
+        if x.shape != y.shape or x.dtype != y.dtype or x.tobytes() != y.tobytes():
+            bad += 1
+            n = int((x.view(np.uint8) != y.view(np.uint8)).sum()) if x.shape == y.shape and x.dtype == y.dtype else -1
+            print(f"DIFF {k}: {n} bytes of {x.nbytes} differ")
+    print(f"{pa} vs {pb}: {len(a.files)} arrays, {bad} differ")
+    return 1 if bad else 0
+
+
+if sys.argv[1] == "--compare":
+    sys.exit(compare(sys.argv[2], sys.argv[3]))
+import torch
+import mpcqp
+OUT = {}
+def put(name, t):
+    if t is None: return
+    a = t.detach().cpu().numpy() if hasattr(t, "detach") else np.asarray(t)
+    OUT[name] = a.copy()
+def dev(a, dt): return torch.as_tensor(np.ascontiguousarray(a), dtype=dt).cuda().contiguous()
+
+# ---- solves: tuple, gait (S = 2), gait steps (S = 4)
+for io in ("f32", "f64"):
+    tdt = torch.float32 if io == "f32" else torch.float64
+    for N in (10, 20, 60):
+        B = 512 if N == 60 else 4096
+        for prec in ("mixed", "f64"):
+            tag = f"{io}_N{N}_{prec}"
+            sol = mpcqp.MPCBatch(N=N, delta=0.03, io_dtype=io, precision=prec)
+            d = sol.upload(mpcqp.synth.make_batch(B, N=N, seed=101, gait_names=("trot", "amble", "gallop"), mus=(0.3, 0.7, 1.0)))
+            o = sol.solve_batch(d["x0"], d["r"], d["contact"], d["xdes"], d["mu"], want_X=True)
+            torch.cuda.synchronize()
+            for k in ("u", "X", "status", "iters", "res"): put(f"solve_{tag}_{k}", o[k])
+            for S in (2, 4):
+                g = sol.upload_gait(mpcqp.synth.make_gait_batch(B, N=N, seed=202 + S, steps=S))
+                o = sol.solve_batch_gait(g["x0"], g["ref"], g["feet0"], g["footholds"], g["gait"], g["feet_id"], g["mu"], want_X=True)
+                torch.cuda.synchronize()
+                for k in ("u", "X", "status", "iters", "res"): put(f"gait{S}_{tag}_{k}", o[k])
+            del sol
+    # warm start + shift over three consecutive calls
+    sol = mpcqp.MPCBatch(N=10, delta=0.03, io_dtype=io, precision="mixed", warm_start=True, warm_shift=True)
+    d = sol.upload(mpcqp.synth.make_batch(4096, N=10, seed=303, gait_names=("trot", "amble"), mus=(0.5, 1.0)))
+    for call in range(3):
+        o = sol.solve_batch(d["x0"], d["r"], d["contact"], d["xdes"], d["mu"], want_X=True)
+        torch.cuda.synchronize()
+        for k in ("u", "X", "status", "iters", "res"): put(f"warm{call}_{io}_{k}", o[k])
+    del sol
+    print("solves", io, "done", flush=True)
+
+# ---- roll-outs, T = 50, B = 1024, with the malformed plan rows of tests/test_rollout.py
+from test_rollout import _malformed
+T, B = 50, 1024
+rb = mpcqp.synth.make_rollout_batch(B, seed=11)
+meta, tick = _malformed(rb)
+rows = mpcqp.synth.make_plant_rows(B, seed=12, push_start=(3, 20))
+for io in ("f32", "f64"):
+    tdt = torch.float32 if io == "f32" else torch.float64
+    for warm in (False, True):
+        for kind in ("model", "plant", "plant_nopush"):
+            sol = mpcqp.MPCBatch(N=10, delta=0.03, io_dtype=io, precision="mixed", warm_start=warm, warm_shift=warm)
+            x, rf, tk = dev(rb["x"], tdt), dev(rb["ref"], tdt), dev(tick, torch.int32)
+            args = (x, rf, dev(rb["plan_pos"], tdt), dev(rb["plan_feet_id"], torch.uint8), dev(meta, torch.int32), tk, dev(rb["mu"], tdt), T)
+            if kind == "model": o = sol.rollout(*args)
+            elif kind == "plant": o = sol.rollout_plant(*args, body=dev(rows["body"], tdt), push=dev(rows["push"], tdt), push_ticks=dev(rows["push_ticks"], torch.int32))
+            else: o = sol.rollout_plant(*args, body=dev(rows["body"], tdt))
+            torch.cuda.synchronize()
+            tag = f"roll_{kind}_{io}_{'warm' if warm else 'cold'}"
+            put(tag + "_x", x); put(tag + "_ref", rf); put(tag + "_tick", tk)
+            for k in ("actual", "desired", "forces", "solved"): put(f"{tag}_{k}", o[k])
+            del sol
+    print("roll-outs", io, "done", flush=True)
+
+# ---- planner + swing, plant step, leg Jacobians + torque map: the inputs of their GPU tests
+from test_gpu_plant import _plant_inputs
+from test_leg_jacobians import _angles
+for io in ("f32", "f64"):
+    tdt = torch.float32 if io == "f32" else torch.float64
+    sol = mpcqp.MPCBatch(N=10, delta=0.03, io_dtype=io, precision="mixed")
+    pi = mpcqp.synth.make_plan_inputs(2048)
+    plan = sol.plan_footsteps(dev(pi["feet0"], tdt), dev(pi["cmd"], tdt), dev(pi["gait"], torch.int32), 24, want_ang=True, want_hip=True)
+    for k, v in plan.items(): put(f"plan_{io}_{k}", v)
+    rng = np.random.default_rng(5)
+    tk = rng.integers(-3, 200, 2048).astype(np.int32)
+    sw = sol.swing_trajectories(plan, dev(tk, torch.int32), 16, dev(pi["step_height"], tdt))
+    put(f"swing_{io}_traj", sw["traj"]); put(f"swing_{io}_des", sw["feet_des"])
+    bad = plan["plan_meta"].clone(); bad[0] = torch.tensor([0, 4, 2, 0]); bad[1] = torch.tensor([5, 0, 0, 0]); bad[2] = torch.tensor([99, 4, 2, 0]); bad[3] = torch.tensor([5, -3, -1, 0])
+    plan2 = dict(plan); plan2["plan_meta"] = bad
+    sw = sol.swing_trajectories(plan2, dev(tk, torch.int32), 16, dev(pi["step_height"], tdt))
+    put(f"swingbad_{io}_traj", sw["traj"]); put(f"swingbad_{io}_des", sw["feet_des"])
+    p = _plant_inputs(4096, 3)
+    dp = {k: dev(v, torch.uint8 if k == "contact" else tdt) for k, v in p.items()}
+    for sub in (1, 10):
+        put(f"plantstep_{io}_{sub}", sol.plant_step(dp["x"], dp["f"], dp["feet"], dp["contact"], dp["body"], dp["wrench"], sub))
+        put(f"plantstep_none_{io}_{sub}", sol.plant_step(dp["x"], dp["f"], dp["feet"], dp["contact"], None, None, sub))
+    q, R = _angles(3000, 11)
+    tq, tR = dev(q, tdt), dev(R, tdt)
+    J, P = sol.leg_jacobians(tq, tR); put(f"jac_{io}_J", J); put(f"jac_{io}_P", P)
+    J0, P0 = sol.leg_jacobians(tq, None); put(f"jac0_{io}_J", J0); put(f"jac0_{io}_P", P0)
+    u = dev(np.random.default_rng(2).normal(0, 30, (3000, 10, 12)), tdt)
+    put(f"tau_{io}", sol.torque_map(u, J))
+    torch.cuda.synchronize()
+    del sol
+np.savez(sys.argv[1], **OUT)
+print("dumped", len(OUT), "arrays", flush=True)

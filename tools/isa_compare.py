@@ -1,0 +1,31 @@
+"""Developer aid: per-kernel comparison of two gfx950 assembly listings of the library, to show that a host-side or file-layout change
+left the device code of a kernel alone.  Produce each listing with the Makefile's flags plus `-S --cuda-device-only`
+(hipcc -O3 -std=c++17 --offload-arch=gfx950 -fPIC -Wall -Wno-unused-variable -S --cuda-device-only -o a.s mpcqp_kernels.hip).
+A kernel is its text from the symbol's label to its .Lfunc_end, without comments, .loc / .file / .cfi / .p2align lines and the
+function index in local labels (.LBB<n>_<m> -> .LBB_<m>): position in the module does not leak into a kernel's code.
+usage: python tools/isa_compare.py a.s b.s      prints same / DIFF / ONLY per kernel symbol; exit status 1 when any differs"""
+import re, sys
+
+
+def kernels(path):
+    out = {}
+    for m in re.finditer(r"^(_Z\w+):\s*; @\1\n(.*?)^\.Lfunc_end\d+:", open(path).read(), re.S | re.M):
+        lines = []
+        for l in m.group(2).split("\n"):
+            s = l.split(";")[0].rstrip()
+            if s.strip() and not s.strip().startswith((".loc", ".file", ".cfi", ".p2align")):
+                lines.append(re.sub(r"\.LBB\d+_(\d+)", r".LBB_\1", s))
+        out[m.group(1)] = lines
+    return out
+
+
+a, b = kernels(sys.argv[1]), kernels(sys.argv[2])
+print(f"{len(a)} / {len(b)} kernels")
+bad = 0
+for k in sorted(set(a) | set(b)):
+    if k not in a or k not in b:
+        print("ONLY", "a" if k in a else "b", k)
+    else:
+        print("same" if a[k] == b[k] else "DIFF", len(a[k]), len(b[k]), k)
+    bad += k not in a or k not in b or a[k] != b[k]
+sys.exit(1 if bad else 0)

@@ -2,7 +2,7 @@
 roll-out (mpcqp_rollout), B = 4096 and 65 536 robots x T = 100 ticks, f32 buffers, warm-started (engine-side shift) and cold.
 Times each call with a host clock around a device synchronise (best of 3 after a warm-up) and prints robot-ticks/s, plus the plant
 kernel alone (mpcqp_plant_step, 10 substeps) timed with HIP events.  The plant's share of a tick comes from a separate
-`rocprofv3 --kernel-trace --stats -- python tools/plant_rate.py --plant-only` run (stable kernel names: mpcqp_rollout_plant_advance_kernel).
+`rocprofv3 --kernel-trace --stats -- python tools/plant_rate.py --plant-only` run (stable kernel names: mpcqp_rollout_advance_kernel<T, PlantIn<T>>).
 usage: plant_rate.py [--quick] [--plant-only]"""
 import json, os, sys, time
 import numpy as np, torch
