@@ -41,9 +41,11 @@ struct mpcqp_engine {
   int order_cap = 0;
   int slots = 0;              // workgroups the device holds at once (2 per CU)
   int listed_max = 4;         // device-fills up to which an ordered launch is one workgroup per QP (MpcQpConfig.listed_max)
-  double* wr_K = nullptr;     // wrench-space engine (mpcqp_wrench.h): K_q [6][N][N], K^-1 in tile layout (fp32 / fp64)
+  double* wr_K = nullptr;     // wrench-space engine (mpcqp_wrench.h): K_q [6][N][N], K_q^-1 [6][N][N] (fp32 / fp64)
   float* wr_kinv32 = nullptr;
   double* wr_kinv64 = nullptr;
+  float* wr_klane32 = nullptr;   // ... and K^-1 in lane order [NT][16]: the entries of each lane's 8 x 8 tile (w_tile_init)
+  double* wr_klane64 = nullptr;
   void* roll_mem = nullptr;   // roll-out: u [B,N,12], X [B,N+1,13], status / iters [B] of the current tick
   int64_t roll_cap = 0;
   void* gait_mem = nullptr;   // gait entry point: the expanded operator tuple [r | xdes | contact] of the current batch
@@ -120,7 +122,7 @@ hipError_t launch_wrench(mpcqp_engine* e, int64_t B, const FastIn<TIO>& in, void
       else grid = dim3((unsigned)slots);
     }
   }
-  const WrTabs tabs = {e->wr_K, e->wr_kinv32, e->wr_kinv64};
+  const WrTabs tabs = {e->wr_K, e->wr_kinv32, e->wr_kinv64, e->wr_klane32, e->wr_klane64};
   if (e->cfg.precision == MPCQP_PREC_MIXED)
     hipLaunchKernelGGL((mpcqp_wrench_solve<double, float, double, TIO, N>), grid, dim3(WG<N>::NT), MPCQP_DIAG_LDSPAD, s, e->dcfg, tabs, in, (TIO*)u,
                        (TIO*)X, st, it, res, ob, (int)B);
@@ -395,6 +397,29 @@ static bool invert_small(int n, const double* A, double* Ai) {
 // component, the latter in fp64 and rounded to fp32, from the coefficient tables
 //   c0[j][j'] = delta^2 (N - max(j,j')),   c1[j][j'] = delta^4 sum_{k > max(j,j')}^{N} (k-1-j+theta)(k-1-j'+theta)
 // MPCQP_OK, or why the tables are not there (out of memory; MPCQP_EINVAL for weights that leave a K_q singular in fp64).
+//
+// The lane-order table: lane t = G gr + gc of the tile grid holds rows R = 8 gr + r, columns C = 8 gc + c of
+//   S0 = [ K^-1 in stage-major order (index 6 j + q: S0[R][C] = Ki[q][R / 6][C / 6] iff R = C (mod 6), else 0)   0 ]
+//        [ 0                                                                                                      I ]   (8 G x 8 G)
+// Row r of the tile has its first K^-1 entry at tile column c0 = (r + 2 k) mod 6 with k = (gr - gc) mod 3, and a second one at
+// c0 + 6 when c0 < 2: slot [t][r] = S0[R][8 gc + c0], slot [t][8 + r] = S0[R][8 gc + c0 + 6] (0 when c0 >= 2).
+template <int N>
+static void lane_order_kinv(const double* Ki, double* lane) {
+  constexpr int G = WG<N>::G, NQ = WG<N>::NQ;
+  auto S0 = [&](int R, int C) -> double {
+    if (R >= NQ || C >= NQ) return R == C ? 1.0 : 0.0;
+    return R % 6 == C % 6 ? Ki[((R % 6) * N + R / 6) * N + C / 6] : 0.0;
+  };
+  for (int t = 0; t < G * G; ++t) {
+    const int gr = t / G, gc = t % G, k = ((gr - gc) % 3 + 3) % 3;
+    for (int r = 0; r < 8; ++r) {
+      const int c0 = (r + 2 * k) % 6;
+      lane[16 * t + r] = S0(8 * gr + r, 8 * gc + c0);
+      lane[16 * t + 8 + r] = c0 < 2 ? S0(8 * gr + r, 8 * gc + c0 + 6) : 0.0;
+    }
+  }
+}
+
 template <int N>
 static int build_wrench_tables(mpcqp_engine* e) {
   const MpcQpConfig& c = e->cfg;
@@ -402,7 +427,10 @@ static int build_wrench_tables(mpcqp_engine* e) {
   double* K = new (std::nothrow) double[6 * N * N];
   double* Ki = new (std::nothrow) double[6 * N * N];
   float* Ki32 = new (std::nothrow) float[6 * N * N];
-  int rc = tab && K && Ki && Ki32 ? MPCQP_OK : MPCQP_ENOMEM;
+  constexpr int NLANE = 16 * WG<N>::NT;
+  double* Kl = new (std::nothrow) double[NLANE];
+  float* Kl32 = new (std::nothrow) float[NLANE];
+  int rc = tab && K && Ki && Ki32 && Kl && Kl32 ? MPCQP_OK : MPCQP_ENOMEM;
   if (rc == MPCQP_OK) {
     const double dl = c.delta, th = e->dev.theta;
     for (int a = 0; a < N; ++a)
@@ -420,15 +448,21 @@ static int build_wrench_tables(mpcqp_engine* e) {
   }
   if (rc == MPCQP_OK) {
     for (int i = 0; i < 6 * N * N; ++i) Ki32[i] = (float)Ki[i];
+    lane_order_kinv<N>(Ki, Kl);
+    for (int i = 0; i < NLANE; ++i) Kl32[i] = (float)Kl[i];   // (the same rounding of the same fp64 entries as Ki32)
     hipError_t he = hipMalloc((void**)&e->wr_K, sizeof(double) * 6 * N * N);
     if (he == hipSuccess) he = hipMemcpy(e->wr_K, K, sizeof(double) * 6 * N * N, hipMemcpyHostToDevice);
     if (he == hipSuccess) he = hipMalloc((void**)&e->wr_kinv32, sizeof(float) * 6 * N * N);
     if (he == hipSuccess) he = hipMemcpy(e->wr_kinv32, Ki32, sizeof(float) * 6 * N * N, hipMemcpyHostToDevice);
     if (he == hipSuccess) he = hipMalloc((void**)&e->wr_kinv64, sizeof(double) * 6 * N * N);
     if (he == hipSuccess) he = hipMemcpy(e->wr_kinv64, Ki, sizeof(double) * 6 * N * N, hipMemcpyHostToDevice);
+    if (he == hipSuccess) he = hipMalloc((void**)&e->wr_klane32, sizeof(float) * NLANE);
+    if (he == hipSuccess) he = hipMemcpy(e->wr_klane32, Kl32, sizeof(float) * NLANE, hipMemcpyHostToDevice);
+    if (he == hipSuccess) he = hipMalloc((void**)&e->wr_klane64, sizeof(double) * NLANE);
+    if (he == hipSuccess) he = hipMemcpy(e->wr_klane64, Kl, sizeof(double) * NLANE, hipMemcpyHostToDevice);
     if (he != hipSuccess) { (void)hipGetLastError(); rc = MPCQP_ENOMEM; }
   }
-  delete[] tab; delete[] K; delete[] Ki; delete[] Ki32;
+  delete[] tab; delete[] K; delete[] Ki; delete[] Ki32; delete[] Kl; delete[] Kl32;
   return rc;
 }
 
@@ -442,6 +476,8 @@ static void free_engine(mpcqp_engine* h) {
   if (h->wr_K) (void)hipFree(h->wr_K);
   if (h->wr_kinv32) (void)hipFree(h->wr_kinv32);
   if (h->wr_kinv64) (void)hipFree(h->wr_kinv64);
+  if (h->wr_klane32) (void)hipFree(h->wr_klane32);
+  if (h->wr_klane64) (void)hipFree(h->wr_klane64);
   if (h->stage_ws) (void)hipFree(h->stage_ws);
   if (h->ev0) (void)hipEventDestroy(h->ev0);
   if (h->ev1) (void)hipEventDestroy(h->ev1);

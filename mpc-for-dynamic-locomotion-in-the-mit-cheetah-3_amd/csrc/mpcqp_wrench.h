@@ -36,8 +36,10 @@ struct WG {
 // Constant tables of a configuration (device memory, built by mpcqp_create).
 struct WrTabs {
   const double* K;        // [6][N][N]   K_q
-  const float* kinv32;    // [6][N][N]   K_q^-1 (w_tile_init gathers the tile entries from it)
+  const float* kinv32;    // [6][N][N]   K_q^-1
   const double* kinv64;   // [6][N][N]
+  const float* klane32;   // [NT][16]    K^-1 in lane order: what w_tile_init places in lane t's tile (v0[8] | v1[8])
+  const double* klane64;  // [NT][16]
 };
 
 template <typename TV, int N>
@@ -256,53 +258,85 @@ __device__ __forceinline__ void tilemv(const WTile<double>& t, const double (&x)
 
 // tile <- K^-1 (constant of the configuration) + E (block diagonal, 6 x 6 per stage, in LDS).
 // K^-1 = (+)_q K_q^-1 couples only equal wrench components: entry (R, C) of the stage-major ordering (index 6 j + q) is
-// kq[q][j][j'] when R = C (mod 6) and zero otherwise, so a lane's 8 x 8 tile holds one such entry per row, or two when the
-// first falls in tile column 0 or 1 (the second is six columns on).  Pass 1 gathers these <= 16 values from the compact
-// table kq (6 N^2 entries: 2.4 / 4.8 KB at horizon 10, resident in the CU's vector L1) and places them by column selects --
-// a full tile-layout table (16 / 32 KB per load, every lane 16 x 16 B) misses L1 for every wave of the CU and its loads
-// queued for ~30 k cycles at full occupancy (the miss queue of the L1, not bandwidth: phase stamps).
-// Pass 2 adds E: entry (R, C) of stage j = R / 6 sits at E[6 R + C - 6 j] and exists iff 0 <= C - 6 j < 6, i.e. for tile
-// column c iff (c - lo) <u 6 with lo = 6 j - 8 gc per tile row; outside a row's run the index is clamped to 0 and the value masked.
-template <typename TM, int N>
-__device__ __forceinline__ void w_tile_init(WTile<TM>& t, const TM* __restrict__ kq, const TM* __restrict__ E, int gr, int gc, int tid) {
-  constexpr int NT = WG<N>::NT, NQ = WG<N>::NQ;
-  asm volatile("" : "+v"(gr), "+v"(gc), "+v"(tid));   // (opaque: keeps the per-lane index arithmetic out of the enclosing loops' preheaders)
-  TM v0[8], v1[8];
-  int c0[8];
+// kq[q][j][j'] when R = C (mod 6) and zero otherwise, so a lane's 8 x 8 tile holds one such entry per row, at tile column
+// c0 = (R - 8 gc) mod 6, or two when c0 is 0 or 1 (the second is six columns on).  With R = 8 gr + r that is
+// c0 = (r + 2 k) mod 6 for the lane class k = (gr - gc) mod 3: WHERE a row's entries go depends on the class alone, and an
+// entry (r, c) with c - r odd is zero for every lane.  WHAT goes there -- v0[r] at c0, v1[r] at c0 + 6, with every mask already
+// applied (zeros beyond the 6 N wrench rows / columns, the ones of the identity padding) -- is a constant of the lane:
+// build_wrench_tables files the sixteen values per lane in lane order (WrTabs::klane32/64, [NT][16]) and a wave reads them as
+// one contiguous block, four / eight b128 loads per lane, issued by w_kq_load ahead of the phase that builds E.
+// (the gather of these values from the compact table, with the index arithmetic per build: ~770 VALU and sixteen scattered
+//  loads per lane into the same 20 / 40 cache lines for all waves at once; profiles/r06_tile_build_before.txt)
+// E: entry (R, C) of stage j = R / 6 sits at E[6 R + C - 6 j] and exists iff 0 <= C - 6 j < 6, i.e. for tile column c iff
+// (c - lo) <u 6 with lo = 6 j - 8 gc per tile row.  lo is even, so the run starts and ends on a PAIR of tile columns: a row is
+// read as two quads (tile columns 0..3 and 4..7, two aligned pairs each, from E[6 R - lo + 4 hq]), a pair slot p is inside the
+// run iff (p - lo / 2) <u 3, and a quad without any such pair reads E[0..3] instead -- no address outside E is formed, and what
+// a masked slot read never reaches the tile (a select, not a product).
+template <typename TM> struct WKq { TM v0[8], v1[8]; };
+
+template <typename TM> __device__ __forceinline__ const TM* w_klane(const WrTabs& tabs) {
+  if constexpr (sizeof(TM) == 4) return tabs.klane32; else return tabs.klane64;
+}
+
+// The lane's sixteen K^-1 values.  Nothing here waits for them: the caller puts other work between this and w_tile_init.
+template <typename TM>
+__device__ __forceinline__ void w_kq_load(WKq<TM>& k, const TM* __restrict__ klane, int tid) {
+  ld8<TM>(klane + 16 * tid, k.v0);
+  ld8<TM>(klane + 16 * tid + 8, k.v1);
+}
+
+__device__ __forceinline__ void ld4(const float* p, float (&o)[4]) {
+  const f2 a = reinterpret_cast<const f2*>(p)[0], b = reinterpret_cast<const f2*>(p)[1];
+  o[0] = a.x; o[1] = a.y; o[2] = b.x; o[3] = b.y;
+}
+__device__ __forceinline__ void ld4(const double* p, double (&o)[4]) {
+  const double2 a = reinterpret_cast<const double2*>(p)[0], b = reinterpret_cast<const double2*>(p)[1];
+  o[0] = a.x; o[1] = a.y; o[2] = b.x; o[3] = b.y;
+}
+
+// x where m is ~0, +0 where m is 0
+__device__ __forceinline__ float wmasked(float x, int m) { return __builtin_bit_cast(float, __builtin_bit_cast(int, x) & m); }
+__device__ __forceinline__ double wmasked(double x, int m) { return __builtin_bit_cast(double, __builtin_bit_cast(long long, x) & (long long)m); }
+
+// VM: the run masks as vector registers (bit field -> 0 / ~0 -> AND: a select all the same) instead of wave-wide compare results in
+// scalar register pairs.  Chosen per kernel by what the register allocator makes of it (profiles/r06_tile_build_after.txt): the
+// MIXED kernels lose their spills with it, the all-fp64 kernels spill less without.
+template <typename TM, int N, bool VM>
+__device__ __forceinline__ void w_tile_init(WTile<TM>& t, const WKq<TM>& kq, const TM* __restrict__ E, int gr, int gc) {
+  constexpr int NQ = WG<N>::NQ, G = WG<N>::G;
+  asm volatile("" : "+v"(gr), "+v"(gc));   // (opaque: keeps the per-lane index arithmetic out of the enclosing loops' preheaders)
+  const unsigned cls = (unsigned)(gr - gc + 3 * G) % 3u;
+  const bool kc[3] = {cls == 0u, cls == 1u, cls == 2u};
 #pragma unroll
   for (int r = 0; r < 8; ++r) {
-    const int R = 8 * gr + r, jR = (R * 43) >> 8, qR = R - 6 * jR;   // R / 6 for R < 128
-    const int d = R - 8 * gc;                                          // tile column of the diagonal (any sign)
-    const int dm = d + 126, m = dm - 6 * ((dm * 171) >> 10);           // d mod 6 in [0, 6): x / 6 = (171 x) >> 10 for x < 500
-    const int C0 = 8 * gc + m, j0 = (C0 * 43) >> 8;
-    const bool rowok = R < NQ, ok0 = rowok && C0 < NQ, ok1 = rowok && m < 2 && C0 + 6 < NQ;
-    const TM* row = kq + (qR * N + min(jR, N - 1)) * N;
-    v0[r] = row[ok0 ? j0 : 0];
-    v1[r] = row[ok1 ? j0 + 1 : 0];
-    if (!ok0) v0[r] = (TM)0;
-    if (!ok1) v1[r] = (TM)0;
-    c0[r] = m;
-    if (!rowok) { v0[r] = (TM)1; c0[r] = (d >= 0 && d < 8) ? d : 8; }   // identity on the padding: the sweep pivots on all 8 G rows
-  }
-#pragma unroll
-  for (int r = 0; r < 8; ++r) {
+    TM kv[8];   // the row of K^-1: one select per entry that any class fills, constants elsewhere
 #pragma unroll
     for (int c = 0; c < 8; ++c) {
-      TM v = c == c0[r] ? v0[r] : (TM)0;
-      if (c >= 6) v = c == c0[r] + 6 ? v1[r] : v;
-      tset(t, r, c, v);
+      TM v = (TM)0;
+#pragma unroll
+      for (int k = 0; k < 3; ++k) {
+        const int c0 = (r + 2 * k) % 6;
+        if (c == c0) v = kc[k] ? kq.v0[r] : v;
+        else if (c == c0 + 6) v = kc[k] ? kq.v1[r] : v;
+      }
+      kv[c] = v;
     }
-  }
-#pragma unroll
-  for (int r = 0; r < 8; ++r) {
     const int R = 8 * gr + r, jR = (R * 43) >> 8;            // R / 6 for R < 128
-    const int lo = 6 * jR - 8 * gc;
-    const int base = R < NQ ? 6 * R - lo : 0;
+    const int h = R < NQ ? 3 * jR - 4 * gc : 64;             // lo / 2; no pair slot is within three of 64
+    const int base = 6 * R - 2 * h;                           // E index of tile column 0
+    const unsigned bits = ((7u << min((unsigned)(h + 2), 31u)) >> 2) & 15u;   // bit p: pair slot p lies in the run, h <= p <= h + 2
 #pragma unroll
-    for (int c = 0; c < 8; ++c) {
-      const bool in = (unsigned)(c - lo) < 6u && R < NQ;
-      const TM e = E[in ? base + c : 0];                       // (index clamped, value masked: no address outside E is ever formed)
-      tset(t, r, c, tget(t, r, c) + (in ? e : (TM)0));
+    for (int hq = 0; hq < 2; ++hq) {
+      const bool in0 = (unsigned)(2 * hq - h) < 3u, in1 = (unsigned)(2 * hq + 1 - h) < 3u;
+      TM e[4];
+      if constexpr (VM) ld4(E + ((bits & (3u << (2 * hq))) ? base + 4 * hq : 0), e);
+      else ld4(E + ((in0 || in1) ? base + 4 * hq : 0), e);
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int c = 4 * hq + i;
+        if constexpr (VM) tset(t, r, c, kv[c] + wmasked(e[i], __builtin_amdgcn_sbfe((int)bits, 2 * hq + (i >> 1), 1)));
+        else tset(t, r, c, kv[c] + ((i < 2 ? in0 : in1) ? e[i] : (TM)0));
+      }
     }
   }
 }
@@ -1050,7 +1084,7 @@ __device__ __forceinline__ void w_admm_sys(const SmemW<TV, N>& s, const DevCfg& 
 // s.hard / s.ratio and leaves the new iterate in s.ua/za/ya and s.pu/py.
 // Register phases that share nothing but LDS (see w_polish): E | tile + sweep | iterations.
 template <typename TV, typename TM, int N, bool REFINE = false>
-__device__ __forceinline__ void w_admm(SmemW<TV, N>& s, const DevCfg& cfg, const WrTabs& tabs, const TM* __restrict__ kinvT, const int adapt,
+__device__ __forceinline__ void w_admm(SmemW<TV, N>& s, const DevCfg& cfg, const WrTabs& tabs, const int adapt,
                                        const int kfirst, const int tid0) {
   constexpr int NL = WG<N>::NL, NW = WG<N>::NW, G = WG<N>::G;
   // Element type of the sweep that inverts S.  Horizon 20: fp64 even when the iterations run on an fp32 tile -- the fp32 sweep of
@@ -1074,8 +1108,10 @@ __device__ __forceinline__ void w_admm(SmemW<TV, N>& s, const DevCfg& cfg, const
   float ratio = 0.f;
   STAMP_INIT
   for (;;) {
-    {   // ---- phase A: E = sum_legs A diag(dinv) A'
+    WKq<TS> kq;
+    {   // ---- phase A: E = sum_legs A diag(dinv) A' (behind the loads of the lane's K^-1 entries)
       const int tid = fresh_tid<NW>(tid0), L = min(tid, NL - 1);
+      w_kq_load<TS>(kq, w_klane<TS>(tabs), tid);
       LegSys<TS> Ls;
       w_admm_sys<TV, TS, N>(s, cfg, L, rho, Ls);
       w_build_E<TS, N>(Ls, reinterpret_cast<TS*>(s.E), tid);
@@ -1085,12 +1121,12 @@ __device__ __forceinline__ void w_admm(SmemW<TV, N>& s, const DevCfg& cfg, const
     {   // ---- phase B: S = K^-1 + E, swept in place
       const int tid = fresh_tid<NW>(tid0), gr = tid / G, gc = tid % G;
       if constexpr (sizeof(TS) == sizeof(TM)) {
-        w_tile_init<TM, N>(tile, kinvT, E, gr, gc, tid);
+        w_tile_init<TM, N, sizeof(TM) == 4>(tile, kq, E, gr, gc);
         STAMP(2);
         w_sweep<TM, N>(tile, piv, gr, gc);
       } else {   // swept in fp64, rounded to the fp32 tile the iterations use
         WTile<TS> t64;
-        w_tile_init<TS, N>(t64, tabs.kinv64, reinterpret_cast<const TS*>(s.E), gr, gc, tid);
+        w_tile_init<TS, N, sizeof(TM) == 4>(t64, kq, reinterpret_cast<const TS*>(s.E), gr, gc);
         STAMP(2);
         w_sweep<TS, N>(t64, reinterpret_cast<TS*>(s.piv), gr, gc);
 #pragma unroll
@@ -1252,7 +1288,10 @@ __device__ __forceinline__ void w_admm(SmemW<TV, N>& s, const DevCfg& cfg, const
     K = max(K, min((cfg.hard_x10 * K) / 10, cfg.max_iter - __builtin_amdgcn_readfirstlane(s.iters)));
     seg_end = min(K, it + seg_len);
   }
-  if (fresh_tid<NW>(tid0) == 0) { s.rho = rho; s.iters += K; s.hard |= hard; }
+  {   // (through an opaque offset: the address of these words, formed for the read of s.iters above, is otherwise kept across every phase -- a spill)
+    SmemW<TV, N>& so = *reinterpret_cast<SmemW<TV, N>*>(reinterpret_cast<char*>(&s) + opaque(0));
+    if (fresh_tid<NW>(tid0) == 0) { so.rho = rho; so.iters += K; so.hard |= hard; }
+  }
   wsync<NW>();
 }
 
@@ -1350,7 +1389,7 @@ __device__ __forceinline__ unsigned w_aset_hash(SmemW<TV, N>& s, const int tid) 
 // at most three rank-one terms removed and three added -- Sherman-Morrison, one mat-vec and one rank-one tile update per term
 // (about two pivots' work) against the 6 N pivots of a rebuild.  At most MPCQP_W_INCR_LEGS changed leg-stages
 // and MPCQP_W_INCR_STEPS updates in a row; a candidate from a drifted inverse would simply fail the KKT test.
-template <typename TV, typename TP, int N>
+template <typename TV, typename TP, int N, bool VM>
 __device__ __forceinline__ int w_polish_round(SmemW<TV, N>& s, const WrTabs& tabs, const TP* __restrict__ kinvT, const int tid0,
                                               const int budget, const bool last, const int trace_tag, const int incr_legs,
                                               const int patience, const int cheap_steps, const int cheap_legs, const int last_patience) {
@@ -1374,8 +1413,10 @@ __device__ __forceinline__ int w_polish_round(SmemW<TV, N>& s, const WrTabs& tab
   float vprev = INFINITY, vprev2 = INFINITY;
   bool done = false;
   while (!done) {
-    {   // ---- E = T D^-1 T' for the active set in s.aset
+    WKq<TP> kq;
+    {   // ---- E = T D^-1 T' for the active set in s.aset (behind the loads of the lane's K^-1 entries)
       const int tid = fresh_tid<NW>(tid0), L = min(tid, NL - 1);
+      w_kq_load<TP>(kq, w_klane<TP>(tabs), tid);
       LegSys<TP> Ls;
       w_polish_sys<TV, TP, N>(s, L, ActSet(s.aset[L], s.ct[L] != 0), Ls);
       w_build_E<TP, N>(Ls, E, tid);
@@ -1391,7 +1432,7 @@ __device__ __forceinline__ int w_polish_round(SmemW<TV, N>& s, const WrTabs& tab
       } else
 #endif
       {
-        w_tile_init<TP, N>(tile, kinvT, E, gr, gc, tid);
+        w_tile_init<TP, N, VM>(tile, kq, E, gr, gc);
         STAMP(10);
         w_sweep<TP, N>(tile, piv, gr, gc);
       }
@@ -1701,8 +1742,7 @@ mpcqp_wrench_solve(const DevCfg* __restrict__ cfgp, const WrTabs tabs, const Fas
   __shared__ SmemW<TV, N> s;
   __shared__ int s_next;
   const DevCfg& cfg = *cfgp;
-  const TM* kinvM; const TP* kinvP;
-  if constexpr (sizeof(TM) == 4) kinvM = tabs.kinv32; else kinvM = tabs.kinv64;
+  const TP* kinvP;   // (the compact table: only the MPCQP_SYM_SWEEP experiment of the polish still reads it)
   if constexpr (sizeof(TP) == 4) kinvP = tabs.kinv32; else kinvP = tabs.kinv64;
   for (int guard = 0; guard <= Btot; ++guard) {
     // The lane index is made opaque once per QP: everything derived from it (addresses into the constant tables, role
@@ -1788,7 +1828,7 @@ mpcqp_wrench_solve(const DevCfg* __restrict__ cfgp, const WrTabs tabs, const Fas
       int budget = kind == R_WARM ? min(warm_tries, polish_max) : 2 * polish_max;
       const bool admm_only = !(cfg.flags & MPCQP_FLAG_POLISH);
       if (kind == R_ADMM) {
-        w_admm<TV, TM, N, REFINE>(s, cfg, tabs, kinvM, round == 0 ? 1 : 0, round == 0 ? (warm >= 2 ? (cfg.first_block > 0 ? min(WARM_K, (WARM_FRAC10 * cfg.first_block) / 10) : WARM_K) : cfg.first_block) : 0, tid0);
+        w_admm<TV, TM, N, REFINE>(s, cfg, tabs, round == 0 ? 1 : 0, round == 0 ? (warm >= 2 ? (cfg.first_block > 0 ? min(WARM_K, (WARM_FRAC10 * cfg.first_block) / 10) : WARM_K) : cfg.first_block) : 0, tid0);
         budget = admm_only ? 0 : (__builtin_amdgcn_readfirstlane(s.hard) ? HARD_POLISH_FACTOR : 1) * polish_max;
       }
       // Active-set steps while they make progress: a step that does not at least halve the KKT violation of the previous one
@@ -1800,7 +1840,7 @@ mpcqp_wrench_solve(const DevCfg* __restrict__ cfgp, const WrTabs tabs, const Fas
 #else
       const int trace_tag = -1;
 #endif
-      if (budget > 0) ok = __builtin_amdgcn_readfirstlane(w_polish_round<TV, TP, N>(s, tabs, kinvP, tid0, budget, last, trace_tag, cfg.incr_legs, cfg.patience, cfg.cheap_steps, cfg.cheap_legs, (kind == R_ADMM) ? cfg.last_patience : 0));
+      if (budget > 0) ok = __builtin_amdgcn_readfirstlane(w_polish_round<TV, TP, N, sizeof(TM) == 4>(s, tabs, kinvP, tid0, budget, last, trace_tag, cfg.incr_legs, cfg.patience, cfg.cheap_steps, cfg.cheap_legs, (kind == R_ADMM) ? cfg.last_patience : 0));
       if (ok == 1 && s.alpha > s.alpha_target) {   // next continuation level, from this optimum and its multipliers
         const int tid = fresh_tid<NW>(tid0);
         for (int i = tid; i < n; i += NT) s.ua[i] = s.uv[i];            // the last accepted answer and its multipliers (the ADMM
