@@ -24,17 +24,12 @@ struct FastIn {
 
 
 
-#ifndef MPCQP_ADAPT_AT
-#define MPCQP_ADAPT_AT 25
-#endif
-#ifndef MPCQP_ADAPT_THR
-#define MPCQP_ADAPT_THR 10.f
-#endif
 #ifndef MPCQP_HARD_ITER_FACTOR
 #define MPCQP_HARD_ITER_FACTOR 2
 #endif
-constexpr int ADAPT_AT = MPCQP_ADAPT_AT;             // iteration of the single early rho check
-constexpr float ADAPT_THR = MPCQP_ADAPT_THR, ADAPT_RHO_MAX = 30.f;
+constexpr int ADAPT_AT = 25;             // iteration of the single early rho check of a cold solve's first ADMM block (both engines)
+constexpr float ADAPT_RHO_MAX = 30.f;    // cap of the penalty a QP that triggers it goes on with
+constexpr double ALPHA_EASY = 1e-2;      // regulariser at which the active-set search is done (continuation start)
 constexpr int HARD_ITER_FACTOR = MPCQP_HARD_ITER_FACTOR;      // ADMM block length of the QPs that trigger it (x check_every)
 constexpr int HARD_POLISH_FACTOR = 2;    // ... and their polish-step budget (x polish_max)
 #ifndef MPCQP_WARM_POLISH

@@ -1,0 +1,281 @@
+// mpcqp_leg.h -- what the two solve engines (mpcqp_wrench.h, mpcqp_stage.h) share: lane-level helpers, the data of one leg-stage as
+// both engines hold it in registers (LegSys, LegAdmm, ActSet, LegAA), the Anderson step, and the parts of OSQP's iteration on the five
+// rows  fz | fx - mu fz | fx + mu fz | fy - mu fz | fy + mu fz  (src/mpc.py:138-173) that both engines call as functions from register
+// values to register values: residuals and rho ratio, right-hand side, projection.  No LDS, no sync, no engine type in here.
+// What is NOT here: the leg's ADMM / polish systems, the active-set rule, the warm start and the relaxation step exist once per engine
+// (w_* / sg_*): through a common function every wrench kernel loses its assembly (profiles/r07_leg_share_check.txt).
+#pragma once
+#include "mpcqp_common.h"
+
+namespace {
+
+__device__ __forceinline__ int opaque(int v) { asm volatile("" : "+v"(v)); return v; }
+// A zero the optimiser cannot see through.  A 64-bit constant needs a register pair, LLVM hoists such pairs out of the persistent QP loop,
+// and with the register file full it then SPILLS the constant at kernel entry and reloads it per QP (scratch stores are written through:
+// 10 bytes per lane and wave of HBM writes for three zeros and a one, profiles/r03f_hbm_traffic.json).  Materialised where it is used instead.
+__device__ __forceinline__ double opaque_zero_f64() {
+  unsigned lo, hi;
+  asm volatile("v_mov_b32 %0, 0\n\tv_mov_b32 %1, 0" : "=v"(lo), "=v"(hi));
+  return __builtin_bit_cast(double, ((unsigned long long)hi << 32) | lo);
+}
+template <typename T> __device__ __forceinline__ T opaque_zero() {
+  if constexpr (sizeof(T) == 8) return (T)opaque_zero_f64();
+  else { float z; asm volatile("v_mov_b32 %0, 0" : "=v"(z)); return (T)z; }
+}
+// A wave-uniform float, moved to a scalar register (loop-carried uniform values otherwise occupy a vector register each).
+__device__ __forceinline__ float ufloat(float v) { return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v))); }
+
+template <int NW>
+__device__ __forceinline__ void wsync() {
+  if constexpr (NW == 1) {   // one wave: its LDS operations execute in order; only the compiler has to be told
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  } else {
+    __syncthreads();
+  }
+}
+
+template <int Q, int NW>
+__device__ __forceinline__ void wmax(float (&v)[Q], float* red, int tid) {
+  if constexpr (NW == 1) {
+#pragma unroll
+    for (int q = 0; q < Q; ++q) v[q] = wave_max(v[q]);
+  } else {
+    block_max<Q, NW>(v, red, tid);
+  }
+}
+
+template <int Q, int NW>
+__device__ __forceinline__ void wsum(float (&v)[Q], float* red, int tid) {
+  if constexpr (NW == 1) {
+#pragma unroll
+    for (int q = 0; q < Q; ++q) v[q] = wave_sum(v[q]);
+  } else {
+    block_sum<Q, NW>(v, red, tid);
+  }
+}
+
+template <typename T> __device__ __forceinline__ T quad_sum(T v) { v += dpp_mov<0xB1>(v); v += dpp_mov<0x4E>(v); return v; }
+
+// Reduce-scatter of 8 values over the 8 lanes of a group: lane gc ends with the group total of element gc.
+template <typename T>
+__device__ __forceinline__ T rs8(const T (&v)[8], int gc) {
+  const bool hi = (gc & 4) != 0, b1 = (gc & 2) != 0, b0 = (gc & 1) != 0;
+  T t[4];
+#pragma unroll
+  for (int m = 0; m < 4; ++m) { const T keep = hi ? v[4 + m] : v[m], send = hi ? v[m] : v[4 + m]; t[m] = keep + dpp_mov<0x141>(send); }
+  T s2[2];
+#pragma unroll
+  for (int m = 0; m < 2; ++m) { const T keep = b1 ? t[2 + m] : t[m], send = b1 ? t[m] : t[2 + m]; s2[m] = keep + dpp_mov<0x4E>(send); }
+  const T keep = b0 ? s2[1] : s2[0], send = b0 ? s2[0] : s2[1];
+  return keep + dpp_mov<0xB1>(send);
+}
+
+__device__ __forceinline__ float w_rcp(float x) { return __builtin_amdgcn_rcpf(x); }
+__device__ __forceinline__ double w_rcp(double x) {
+  double r = __builtin_amdgcn_rcp(x);
+  r = fma(fma(-x, r, 1.0), r, r);
+  r = fma(fma(-x, r, 1.0), r, r);
+  return r;
+}
+
+template <typename TM> __device__ __forceinline__ void ld8(const TM* p, TM (&o)[8]);
+template <> __device__ __forceinline__ void ld8<float>(const float* p, float (&o)[8]) {
+  const float4 a = reinterpret_cast<const float4*>(p)[0], b = reinterpret_cast<const float4*>(p)[1];
+  o[0] = a.x; o[1] = a.y; o[2] = a.z; o[3] = a.w; o[4] = b.x; o[5] = b.y; o[6] = b.z; o[7] = b.w;
+}
+template <> __device__ __forceinline__ void ld8<double>(const double* p, double (&o)[8]) {
+#pragma unroll
+  for (int h = 0; h < 4; ++h) { const double2 a = reinterpret_cast<const double2*>(p)[h]; o[2 * h] = a.x; o[2 * h + 1] = a.y; }
+}
+template <typename TM> __device__ __forceinline__ void st8(TM* p, const TM (&o)[8]);
+template <> __device__ __forceinline__ void st8<float>(float* p, const float (&o)[8]) {
+  reinterpret_cast<float4*>(p)[0] = make_float4(o[0], o[1], o[2], o[3]);
+  reinterpret_cast<float4*>(p)[1] = make_float4(o[4], o[5], o[6], o[7]);
+}
+template <> __device__ __forceinline__ void st8<double>(double* p, const double (&o)[8]) {
+#pragma unroll
+  for (int h = 0; h < 4; ++h) reinterpret_cast<double2*>(p)[h] = make_double2(o[2 * h], o[2 * h + 1]);
+}
+
+// Per-leg data of a linear solve with M = D + A-stack' K A-stack: columns of the 6 x 3 wrench map and the inverse diagonal.
+template <typename TM>
+struct LegSys {
+  TM A[3][6];    // A[c][q]: wrench component q of reduced variable c
+  TM dinv[3];
+};
+
+// OSQP algorithm 1 on the rows  fz | fx - mu fz | fx + mu fz | fy - mu fz | fy + mu fz  of a leg-stage
+// (src/mpc.py:138-173), one lane per leg-stage, scaled duals yh = y / rho.
+template <typename TM>
+struct LegAdmm {
+  TM u[3], z[5], yh[5], g[3];
+  TM lo0, hi0, loA, hiB;     // fz box; friction rows: A rows in [loA, 0], B rows in [0, hiB]
+  TM mu;
+};
+
+// The active set of a leg-stage as the polish uses it: zs / xs / ys in {-1, 0, +1} (fz at fmin / free / at fmax; fx, fy tied
+// to -mu fz / free / tied to +mu fz), packed as (zs + 1) | (xs + 1) << 2 | (ys + 1) << 4.
+struct ActSet {
+  int zs, xs, ys;
+  bool ez, ex, ey;
+  __device__ __forceinline__ ActSet(int code, bool stance) {
+    zs = (code & 3) - 1; xs = ((code >> 2) & 3) - 1; ys = ((code >> 4) & 3) - 1;
+    ez = stance && zs == 0; ex = stance && xs == 0; ey = stance && ys == 0;
+  }
+};
+
+// ----------------------------------------------------------------------------------------------------- Anderson acceleration
+// The ADMM block exists to find the active set, and on the QPs that end a launch (two-legged support at low friction) plain
+// ADMM needs 300 - 400 iterations for it: the iteration is a contraction with a factor close to 1 along a few directions.
+// Anderson acceleration (type II, memory AA_M) of the map  v -> f^p(v),  v = z + y / rho  the pre-projection variable of
+// OSQP's iteration (z = clip(v), y / rho = v - z: the five rows of a leg-stage, five numbers per lane):  every p-th iterate is
+// replaced by the combination of the last AA_M + 1 of them that minimises the fixed-point residual in the least-squares sense,
+//     gam = argmin | r - dF gam |,   v+ = f(v) - dX gam,     dF / dX: differences of consecutive residuals / images
+// -- nine inner products over the wave (seven DPP steps each), a regularised 3 x 3 solve in uniform registers, fifteen FMAs per
+// lane, once per p iterations.  numpy study on the condensed QP (tools/accel_study.py): the hardest QPs of five batches reach a
+// polishable iterate in half the iterations (worst case of a batch 375 -> 250 us of solve), the easy ones are unchanged.
+// Only with the polish (MPCQP_FLAG_POLISH): an ADMM-only run is OSQP's algorithm 1 unchanged.  History in fp32 (it steers an
+// extrapolation, it is not part of the answer); base point and images in the iteration's element type.
+#ifndef MPCQP_AA_M
+#define MPCQP_AA_M 3
+#endif
+constexpr int AA_M = MPCQP_AA_M;
+struct LegAA {
+  float rp[5];                       // previous residual f(v) - v
+  float dX[AA_M][5], dF[AA_M][5];    // column AA_M - 1 is the newest
+};
+
+__device__ __forceinline__ void w_aa_reset(LegAA& h) {
+#pragma unroll
+  for (int k = 0; k < 5; ++k) {
+    h.rp[k] = 0.f;
+#pragma unroll
+    for (int j = 0; j < AA_M; ++j) { h.dX[j][k] = 0.f; h.dF[j][k] = 0.f; }
+  }
+}
+
+// One extrapolation: fx = f^p(xb) has just been computed.  Files (fx, fx - xb) in the history and returns the next base point in
+// xb (the extrapolated iterate, or fx itself while the history is empty / when the least-squares problem is degenerate -- then the
+// history restarts).  `have_prev`: an earlier image exists (uniform).  Uniform control flow; ends with the caller's state untouched
+// except xb / fp / h.
+template <typename TM, int NW>
+__device__ __forceinline__ void w_aa_step(LegAA& h, TM (&xb)[5], TM (&fp)[5], const TM (&fx)[5], bool& have_prev, const bool leg,
+                                          float* __restrict__ red, const int tid) {
+  static_assert(AA_M == 3 || AA_M == 2, "the solve below is written for two or three columns");
+  constexpr int M = AA_M, NQ_ = M * (M + 1) / 2 + M;
+  float r[5];
+  if (!have_prev) {   // (uniform) the first image of a history: nothing to combine yet -- file it and go on from it
+#pragma unroll
+    for (int k = 0; k < 5; ++k) { h.rp[k] = leg ? (float)(fx[k] - xb[k]) : 0.f; fp[k] = fx[k]; xb[k] = fx[k]; }
+    have_prev = true;
+    return;
+  }
+#pragma unroll
+  for (int k = 0; k < 5; ++k) {
+    r[k] = leg ? (float)(fx[k] - xb[k]) : 0.f;
+    const float dx = have_prev ? (float)(fx[k] - fp[k]) : 0.f, df = have_prev ? r[k] - h.rp[k] : 0.f;
+#pragma unroll
+    for (int j = 0; j + 1 < M; ++j) { h.dX[j][k] = h.dX[j + 1][k]; h.dF[j][k] = h.dF[j + 1][k]; }
+    h.dX[M - 1][k] = dx; h.dF[M - 1][k] = df;
+    fp[k] = fx[k]; h.rp[k] = r[k];
+  }
+  have_prev = true;
+  float q[NQ_];   // M = 3: 00 01 02 11 12 22 | 0r 1r 2r;  M = 2: 00 01 11 | 0r 1r
+#pragma unroll
+  for (int i = 0; i < NQ_; ++i) q[i] = 0.f;
+#pragma unroll
+  for (int k = 0; k < 5; ++k) {
+    int at = 0;
+#pragma unroll
+    for (int i = 0; i < M; ++i) {
+#pragma unroll
+      for (int j = i; j < M; ++j) { q[at] = fmaf(h.dF[i][k], h.dF[j][k], q[at]); ++at; }
+    }
+#pragma unroll
+    for (int i = 0; i < M; ++i) { q[at] = fmaf(h.dF[i][k], r[k], q[at]); ++at; }
+  }
+  wsum<NQ_, NW>(q, red, tid);
+  float g[M];
+  bool ok;
+  if constexpr (M == 3) {
+    const float tr = q[0] + q[3] + q[5];
+    const bool have = tr > 0.f;
+    const float reg = 1e-6f * tr + 1e-30f;
+    // regularised normal equations by L D L' (uniform values)
+    const float a00 = q[0] + reg, a11 = q[3] + reg, a22 = q[5] + reg, a01 = q[1], a02 = q[2], a12 = q[4];
+    const float i0 = w_rcp(a00), l10 = a01 * i0, l20 = a02 * i0;
+    const float d1 = fmaf(-l10, a01, a11), i1 = w_rcp(d1), t21 = fmaf(-l20, a01, a12), l21 = t21 * i1;
+    const float d2 = fmaf(-l21, t21, fmaf(-l20, a02, a22)), i2 = w_rcp(d2);
+    const float y0 = q[6], y1 = fmaf(-l10, y0, q[7]), y2 = fmaf(-l21, y1, fmaf(-l20, y0, q[8]));
+    g[2] = y2 * i2; g[1] = fmaf(-l21, g[2], y1 * i1); g[0] = fmaf(-l20, g[2], fmaf(-l10, g[1], y0 * i0));
+    ok = have && d1 > 0.f && d2 > 0.f && fabsf(g[0]) + fabsf(g[1]) + fabsf(g[2]) <= 1e4f;   // (a NaN fails the comparison)
+    if (!have) have_prev = true; else if (!ok) { w_aa_reset(h); have_prev = false; }   // degenerate history: start again from this iterate
+  } else {
+    const float tr = q[0] + q[2];
+    const bool have = tr > 0.f;
+    const float reg = 1e-6f * tr + 1e-30f;
+    const float a00 = q[0] + reg, a11 = q[2] + reg, a01 = q[1];
+    const float i0 = w_rcp(a00), l10 = a01 * i0, d1 = fmaf(-l10, a01, a11), i1 = w_rcp(d1);
+    const float y0 = q[3], y1 = fmaf(-l10, y0, q[4]);
+    g[1] = y1 * i1; g[0] = fmaf(-l10, g[1], y0 * i0);
+    ok = have && d1 > 0.f && fabsf(g[0]) + fabsf(g[1]) <= 1e4f;
+    if (have && !ok) { w_aa_reset(h); have_prev = false; }
+  }
+#pragma unroll
+  for (int k = 0; k < 5; ++k) {
+    float c = 0.f;
+#pragma unroll
+    for (int j = 0; j < M; ++j) c = fmaf(g[j], h.dX[j][k], c);
+    xb[k] = ok ? fx[k] - (TM)c : fx[k];
+  }
+}
+
+// ----------------------------------------------------------------------------------------------------- residuals of an ADMM iterate
+// The leg-stage's share of OSQP's residuals of an ADMM iterate (u, z, y), hv = H u + g:  q = |r_prim|, |r_dual|, norm_prim, norm_dual
+// (running maxima; differences in TV: the ADMM-only termination test of an fp64 run looks below fp32 resolution).
+template <typename TV>
+__device__ __forceinline__ void leg_residuals(const TV (&u)[3], const TV (&z)[5], const TV (&y)[5], const TV (&g)[3], const TV (&hv)[3], const TV mu,
+                                              float (&q)[4]) {
+  const TV m = mu * u[2];
+  const TV gu[5] = {u[2], u[0] - m, u[0] + m, u[1] - m, u[1] + m};
+#pragma unroll
+  for (int i = 0; i < 5; ++i) {
+    q[0] = fmaxf(q[0], fabsf((float)(gu[i] - z[i])));
+    q[2] = fmaxf(q[2], fmaxf(fabsf((float)gu[i]), fabsf((float)z[i])));
+  }
+  const TV Gy[3] = {y[1] + y[2], y[3] + y[4], y[0] + mu * (-y[1] + y[2] - y[3] + y[4])};
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    q[1] = fmaxf(q[1], fabsf((float)(hv[a] + Gy[a])));
+    q[3] = fmaxf(q[3], fmaxf(fabsf((float)(hv[a] - g[a])), fabsf((float)Gy[a])));
+  }
+}
+// OSQP's rho-adaptation ratio sqrt((|r_prim| / norm_prim) / (|r_dual| / norm_dual)) from the reduced q, with sd = max(q[3], |g|_inf).
+__device__ __forceinline__ float admm_ratio(const float (&q)[4], const float sd) {
+  return sqrtf((q[0] / fmaxf(q[2], 1e-12f)) / fmaxf(q[1] / fmaxf(sd, 1e-12f), 1e-30f));
+}
+
+// ----------------------------------------------------------------------------------------------------- ADMM iteration
+// rhs = sigma u - g + rho G'(z - yh)
+template <typename TM>
+__device__ __forceinline__ void leg_admm_rhs(const LegAdmm<TM>& A, const TM sigma, const TM r, TM (&rhs)[3]) {
+  TM v[5];
+#pragma unroll
+  for (int k = 0; k < 5; ++k) v[k] = A.z[k] - A.yh[k];
+  const TM w0 = v[1] + v[2], w1 = v[3] + v[4], w2 = fma(A.mu, (v[2] - v[1]) + (v[4] - v[3]), v[0]);
+  rhs[0] = fma(r, w0, fma(sigma, A.u[0], -A.g[0]));
+  rhs[1] = fma(r, w1, fma(sigma, A.u[1], -A.g[1]));
+  rhs[2] = fma(r, w2, fma(sigma, A.u[2], -A.g[2]));
+}
+// Row k from its pre-projection value t = z + yh:  z = clip(t),  yh = t - z.
+template <typename TM>
+__device__ __forceinline__ void leg_admm_project(LegAdmm<TM>& A, const int k, const TM t) {
+  const TM lo = k == 0 ? A.lo0 : ((k & 1) ? A.loA : (TM)0), hi = k == 0 ? A.hi0 : ((k & 1) ? (TM)0 : A.hiB);
+  const TM zn = fmin(fmax(t, lo), hi);
+  A.yh[k] = t - zn;
+  A.z[k] = zn;
+}
+
+}  // namespace

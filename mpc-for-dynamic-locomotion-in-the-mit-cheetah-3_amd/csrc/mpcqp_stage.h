@@ -26,7 +26,7 @@
 // The factorisation itself always runs in fp64 (wave 0, 6 x 6 inverses in LDS); the ADMM chains use its fp32 rounding in the
 // MIXED precision and fp64 in F64; the polish is all fp64.
 #pragma once
-#include "mpcqp_wrench.h"
+#include "mpcqp_leg.h"
 
 namespace {
 
@@ -767,26 +767,12 @@ __device__ __forceinline__ float sg_ratio(SmemS& s, const SLeg& Lg, const double
   double hv[3];
   sg_grad(s, Lg, u, hv, N, tid);
   float q[4] = {0.f, 0.f, 0.f, 0.f};
-  if (Lg.leg) {
-    const double mu = s.mu, m = mu * u[2];
-    const double gu[5] = {u[2], u[0] - m, u[0] + m, u[1] - m, u[1] + m};
-#pragma unroll
-    for (int i = 0; i < 5; ++i) {
-      q[0] = fmaxf(q[0], fabsf((float)(gu[i] - z[i])));
-      q[2] = fmaxf(q[2], fmaxf(fabsf((float)gu[i]), fabsf((float)z[i])));
-    }
-    const double Gy[3] = {y[1] + y[2], y[3] + y[4], y[0] + mu * (-y[1] + y[2] - y[3] + y[4])};
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-      q[1] = fmaxf(q[1], fabsf((float)(hv[a] + Gy[a])));
-      q[3] = fmaxf(q[3], fmaxf(fabsf((float)(hv[a] - Lg.g[a])), fabsf((float)Gy[a])));
-    }
-  }
+  if (Lg.leg) leg_residuals<double>(u, z, y, Lg.g, hv, s.mu, q);
   block_max<4, SG_NW>(q, s.red, tid);
-  const float sp = q[2], sd = fmaxf(q[3], s.gmax);
-  if (tid == 0) { s.resid[0] = q[0]; s.resid[1] = q[1]; s.resid[2] = sp; s.resid[3] = sd; }
+  const float sd = fmaxf(q[3], s.gmax);
+  if (tid == 0) { s.resid[0] = q[0]; s.resid[1] = q[1]; s.resid[2] = q[2]; s.resid[3] = sd; }
   __syncthreads();
-  return sqrtf((q[0] / fmaxf(sp, 1e-12f)) / fmaxf(q[1] / fmaxf(sd, 1e-12f), 1e-30f));
+  return admm_ratio(q, sd);
 }
 
 // Warm start (MPCQP_FLAG_WARM_START [+ WARM_SHIFT]; the reference seeds every solve with its previous solution, src/mpc.py:270-271):
@@ -850,7 +836,7 @@ __device__ __forceinline__ void sg_admm(SmemS& s, const DevCfg& cfg, SLeg& Lg, d
   const int seg_len = (aa_on && cfg.accel_p > 0 && cfg.accel_restart > 0) ? cfg.accel_restart : (1 << 30);   // (segments: see w_admm)
   const bool check = adapt && cfg.early_check;
   // (a cold solve's first block is split at ADAPT_AT with or without the check: the history's one fresh start there is worth 2-3 %)
-  int it = 0, seg_end = min(K, (adapt && MPCQP_W_ADAPT_AT < K) ? MPCQP_W_ADAPT_AT : seg_len);
+  int it = 0, seg_end = min(K, (adapt && ADAPT_AT < K) ? ADAPT_AT : seg_len);
   int hard = 0;
   float ratio = 0.f;
   STAMP_INIT
@@ -861,15 +847,16 @@ __device__ __forceinline__ void sg_admm(SmemS& s, const DevCfg& cfg, SLeg& Lg, d
     sg_build_E(s, Ls, Lg.leg, tid);
     sg_factor<TM>(s, ws, N, tid, true);
     STAMP(1);
-    const double sigma = cfg.sigma, relax = cfg.relax, om = 1.0 - relax, BIG = 1e30, r = (double)rho, mu = s.mu;
-    double u[3], z[5], yh[5];
+    const double sigma = cfg.sigma, relax = cfg.relax, om = 1.0 - relax, BIG = 1e30, r = (double)rho;
+    LegAdmm<double> A;
+    A.mu = s.mu;
 #pragma unroll
-    for (int a = 0; a < 3; ++a) u[a] = Lg.ua[a];
+    for (int a = 0; a < 3; ++a) { A.u[a] = Lg.ua[a]; A.g[a] = Lg.g[a]; }
 #pragma unroll
-    for (int i = 0; i < 5; ++i) { z[i] = Lg.za[i]; yh[i] = Lg.ya[i] / r; }
-    const double lo0 = Lg.stance ? s.fmin : 0.0, hi0 = Lg.stance ? s.fmax : 0.0, loA = Lg.stance ? -BIG : 0.0, hiB = Lg.stance ? BIG : 0.0;
+    for (int i = 0; i < 5; ++i) { A.z[i] = Lg.za[i]; A.yh[i] = Lg.ya[i] / r; }
+    A.lo0 = Lg.stance ? s.fmin : 0.0; A.hi0 = Lg.stance ? s.fmax : 0.0; A.loA = Lg.stance ? -BIG : 0.0; A.hiB = Lg.stance ? BIG : 0.0;
     bool rebuild = false;
-    // Anderson acceleration of the block (mpcqp_wrench.h: w_aa_step; with the polish only): an iteration costs two recursions of N
+    // Anderson acceleration of the block (mpcqp_leg.h: w_aa_step; with the polish only): an iteration costs two recursions of N
     // steps here, an extrapolation nine workgroup-wide sums -- a few per cent of the block for the iterations it saves.  In a cold
     // solve's FIRST block only: at N = 60 the later rounds of the few QPs that need them ended in polish rounds of up to 98 steps with
     // it (a refactorisation each; profiles/r03_stage_accel.txt), while the first block is where the logged ticks of the reference's
@@ -884,21 +871,17 @@ __device__ __forceinline__ void sg_admm(SmemS& s, const DevCfg& cfg, SLeg& Lg, d
       if (aa_p > 0) {
         w_aa_reset(aa);
 #pragma unroll
-        for (int k = 0; k < 5; ++k) { aa_xb[k] = z[k] + yh[k]; aa_fp[k] = aa_xb[k]; }
+        for (int k = 0; k < 5; ++k) { aa_xb[k] = A.z[k] + A.yh[k]; aa_fp[k] = aa_xb[k]; }
       }
       for (; it < seg_end; ++it) {
-        double v[5];
-#pragma unroll
-        for (int k = 0; k < 5; ++k) v[k] = z[k] - yh[k];
-        const double w0 = v[1] + v[2], w1 = v[3] + v[4], w2 = fma(mu, (v[2] - v[1]) + (v[4] - v[3]), v[0]);
-        const double rhs[3] = {fma(r, w0, fma(sigma, u[0], -Lg.g[0])), fma(r, w1, fma(sigma, u[1], -Lg.g[1])), fma(r, w2, fma(sigma, u[2], -Lg.g[2]))};
-        double ut[3];
+        double rhs[3], ut[3];
+        leg_admm_rhs<double>(A, sigma, r, rhs);
         sg_leg_solve<TM>(s, ws, Ls, rhs, ut, Lg.leg, N, tid, true);
         if constexpr (sizeof(TM) == 8) {
           if (cfg.refine_admm) {   // tight-tolerance ADMM-only runs: one refinement step on M u~ = rhs (mpcqp_wrench.h)
             double hv[3], rr[3], du[3];
             sg_grad(s, Lg, ut, hv, N, tid);   // H u~ + g
-            const double dg[3] = {2.0, 2.0, 1.0 + 4.0 * mu * mu};
+            const double dg[3] = {2.0, 2.0, 1.0 + 4.0 * A.mu * A.mu};
 #pragma unroll
             for (int a = 0; a < 3; ++a) rr[a] = rhs[a] - ((hv[a] - Lg.g[a]) + (sigma + r * dg[a]) * ut[a]);
             sg_leg_solve<TM>(s, ws, Ls, rr, du, Lg.leg, N, tid, true);
@@ -906,51 +889,40 @@ __device__ __forceinline__ void sg_admm(SmemS& s, const DevCfg& cfg, SLeg& Lg, d
             for (int a = 0; a < 3; ++a) ut[a] += du[a];
           }
         }
-        const double mz = mu * ut[2];
+        const double mz = A.mu * ut[2];
         const double gt[5] = {ut[2], ut[0] - mz, ut[0] + mz, ut[1] - mz, ut[1] + mz};
 #pragma unroll
-        for (int a = 0; a < 3; ++a) u[a] = fma(relax, ut[a], om * u[a]);
+        for (int a = 0; a < 3; ++a) A.u[a] = fma(relax, ut[a], om * A.u[a]);
 #pragma unroll
-        for (int k = 0; k < 5; ++k) {
-          const double lo = k == 0 ? lo0 : ((k & 1) ? loA : 0.0), hi = k == 0 ? hi0 : ((k & 1) ? 0.0 : hiB);
-          const double t = fma(relax, gt[k], om * z[k]) + yh[k];
-          const double zn = fmin(fmax(t, lo), hi);
-          yh[k] = t - zn;
-          z[k] = zn;
-        }
+        for (int k = 0; k < 5; ++k) leg_admm_project<double>(A, k, fma(relax, gt[k], om * A.z[k]) + A.yh[k]);
         if (aa_p > 0 && --aa_left == 0) {   // uniform
           aa_left = aa_p;
           if (it + 1 + aa_p <= seg_end) {   // (the segment ends with at least a period of genuine ADMM iterations, see w_admm)
             double fx[5];
 #pragma unroll
-            for (int k = 0; k < 5; ++k) fx[k] = z[k] + yh[k];
+            for (int k = 0; k < 5; ++k) fx[k] = A.z[k] + A.yh[k];
             w_aa_step<double, SG_NW>(aa, aa_xb, aa_fp, fx, aa_have, Lg.leg, s.aared, tid);
 #pragma unroll
-            for (int k = 0; k < 5; ++k) {
-              const double lo = k == 0 ? lo0 : ((k & 1) ? loA : 0.0), hi = k == 0 ? hi0 : ((k & 1) ? 0.0 : hiB);
-              const double zn = fmin(fmax(aa_xb[k], lo), hi);
-              yh[k] = aa_xb[k] - zn;
-              z[k] = zn;
-            }
+            for (int k = 0; k < 5; ++k) leg_admm_project<double>(A, k, aa_xb[k]);
           }
         }
       }
       STAMP(2);
       if (it >= K) break;
-      if (check && !hard && it == MPCQP_W_ADAPT_AT) {
+      if (check && !hard && it == ADAPT_AT) {
         double y5[5];
 #pragma unroll
-        for (int k = 0; k < 5; ++k) y5[k] = r * yh[k];
-        ratio = sg_ratio(s, Lg, u, z, y5, N, tid);
+        for (int k = 0; k < 5; ++k) y5[k] = r * A.yh[k];
+        ratio = sg_ratio(s, Lg, A.u, A.z, y5, N, tid);
         STAMP(3);
         if (ratio > cfg.adapt_thr) { rebuild = true; break; }   // uniform
       }
       seg_end = min(K, it + seg_len);
     }
 #pragma unroll
-    for (int a = 0; a < 3; ++a) { Lg.ua[a] = u[a]; Lg.pu[a] = u[a]; }
+    for (int a = 0; a < 3; ++a) { Lg.ua[a] = A.u[a]; Lg.pu[a] = A.u[a]; }
 #pragma unroll
-    for (int k = 0; k < 5; ++k) { const double y = r * yh[k]; Lg.za[k] = z[k]; Lg.ya[k] = y; Lg.py[k] = y; }
+    for (int k = 0; k < 5; ++k) { const double y = r * A.yh[k]; Lg.za[k] = A.z[k]; Lg.ya[k] = y; Lg.py[k] = y; }
     if (!rebuild) break;
     rho = fminf(rho * ratio, ADAPT_RHO_MAX);
     hard = 1;

@@ -19,7 +19,7 @@
 // The polish therefore builds and sweeps its S in fp64 (v_fma_f64 issues at the unpacked fp32 rate on gfx950): the
 // solve is then exact to ~1e-9 and no iterative refinement is needed (one solve + two gradients per step).
 #pragma once
-#include "mpcqp_common.h"   // FastIn, OrderBuf, the dispatch-order pre-pass, policy constants
+#include "mpcqp_leg.h"   // lane helpers, leg-stage structs, Anderson step, residuals / right-hand side / projection; through it mpcqp_common.h (FastIn, OrderBuf, the dispatch-order pre-pass, policy constants)
 
 namespace {
 
@@ -36,8 +36,8 @@ struct WG {
 // Constant tables of a configuration (device memory, built by mpcqp_create).
 struct WrTabs {
   const double* K;        // [6][N][N]   K_q
-  const float* kinv32;    // [6][N][N]   K_q^-1
-  const double* kinv64;   // [6][N][N]
+  const float* kinv32;    // [6][N][N]   K_q^-1: no kernel reads these two any more (the symmetric-sweep experiment did); they stay
+  const double* kinv64;   // [6][N][N]   because dropping them moves the kernel arguments, i.e. changes every wrench kernel's code
   const float* klane32;   // [NT][16]    K^-1 in lane order: what w_tile_init places in lane t's tile (v0[8] | v1[8])
   const double* klane64;  // [NT][16]
 };
@@ -83,21 +83,6 @@ struct SmemW {
   uint8_t aset[Geo::NL];         // active set of the current polish step (ActSet code)
 };
 
-__device__ __forceinline__ int opaque(int v) { asm volatile("" : "+v"(v)); return v; }
-// A zero the optimiser cannot see through.  A 64-bit constant needs a register pair, LLVM hoists such pairs out of the persistent QP loop,
-// and with the register file full it then SPILLS the constant at kernel entry and reloads it per QP (scratch stores are written through:
-// 10 bytes per lane and wave of HBM writes for three zeros and a one, profiles/r03f_hbm_traffic.json).  Materialised where it is used instead.
-__device__ __forceinline__ double opaque_zero_f64() {
-  unsigned lo, hi;
-  asm volatile("v_mov_b32 %0, 0\n\tv_mov_b32 %1, 0" : "=v"(lo), "=v"(hi));
-  return __builtin_bit_cast(double, ((unsigned long long)hi << 32) | lo);
-}
-template <typename T> __device__ __forceinline__ T opaque_zero() {
-  if constexpr (sizeof(T) == 8) return (T)opaque_zero_f64();
-  else { float z; asm volatile("v_mov_b32 %0, 0" : "=v"(z)); return (T)z; }
-}
-// A wave-uniform float, moved to a scalar register (loop-carried uniform values otherwise occupy a vector register each).
-__device__ __forceinline__ float ufloat(float v) { return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v))); }
 // The thread index of a register phase.  One wave per QP: recomputed from the lane counter where it is needed (two VALU
 // instructions, not hoistable, nothing kept alive between phases -- a copy of threadIdx.x held across the fp64 sweep is spilled,
 // and so is every LDS address LLVM derives from it ahead of the round loop).  Four waves: an opaque copy of threadIdx.x.
@@ -112,64 +97,6 @@ __device__ __forceinline__ int fresh_tid(int tid0) {
   }
 }
 
-template <int NW>
-__device__ __forceinline__ void wsync() {
-  if constexpr (NW == 1) {   // one wave: its LDS operations execute in order; only the compiler has to be told
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-#ifdef MPCQP_W_WAIT
-    __builtin_amdgcn_s_waitcnt(0xC07F);   // lgkmcnt(0)
-#endif
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-  } else {
-    __syncthreads();
-  }
-}
-
-template <int Q, int NW>
-__device__ __forceinline__ void wmax(float (&v)[Q], float* red, int tid) {
-  if constexpr (NW == 1) {
-#pragma unroll
-    for (int q = 0; q < Q; ++q) v[q] = wave_max(v[q]);
-  } else {
-    block_max<Q, NW>(v, red, tid);
-  }
-}
-
-template <int Q, int NW>
-__device__ __forceinline__ void wsum(float (&v)[Q], float* red, int tid) {
-  if constexpr (NW == 1) {
-#pragma unroll
-    for (int q = 0; q < Q; ++q) v[q] = wave_sum(v[q]);
-  } else {
-    block_sum<Q, NW>(v, red, tid);
-  }
-}
-
-template <typename T> __device__ __forceinline__ T quad_sum(T v) { v += dpp_mov<0xB1>(v); v += dpp_mov<0x4E>(v); return v; }
-
-// Reduce-scatter of 8 values over the 8 lanes of a group: lane gc ends with the group total of element gc.
-template <typename T>
-__device__ __forceinline__ T rs8(const T (&v)[8], int gc) {
-  const bool hi = (gc & 4) != 0, b1 = (gc & 2) != 0, b0 = (gc & 1) != 0;
-  T t[4];
-#pragma unroll
-  for (int m = 0; m < 4; ++m) { const T keep = hi ? v[4 + m] : v[m], send = hi ? v[m] : v[4 + m]; t[m] = keep + dpp_mov<0x141>(send); }
-  T s2[2];
-#pragma unroll
-  for (int m = 0; m < 2; ++m) { const T keep = b1 ? t[2 + m] : t[m], send = b1 ? t[m] : t[2 + m]; s2[m] = keep + dpp_mov<0x4E>(send); }
-  const T keep = b0 ? s2[1] : s2[0], send = b0 ? s2[0] : s2[1];
-  return keep + dpp_mov<0xB1>(send);
-}
-
-__device__ __forceinline__ float w_rcp(float x) { return __builtin_amdgcn_rcpf(x); }
-__device__ __forceinline__ double w_rcp(double x) {
-  double r = __builtin_amdgcn_rcp(x);
-  r = fma(fma(-x, r, 1.0), r, r);
-  r = fma(fma(-x, r, 1.0), r, r);
-  return r;
-}
-
 // ----------------------------------------------------------------------------------------------------- register tile
 template <typename TM> struct WTile;
 template <> struct WTile<float> { f2 v[8][4]; };
@@ -179,25 +106,6 @@ __device__ __forceinline__ float tget(const WTile<float>& t, int i, int j) { ret
 __device__ __forceinline__ double tget(const WTile<double>& t, int i, int j) { return t.v[i][j]; }
 __device__ __forceinline__ void tset(WTile<float>& t, int i, int j, float x) { if (j & 1) t.v[i][j >> 1].y = x; else t.v[i][j >> 1].x = x; }
 __device__ __forceinline__ void tset(WTile<double>& t, int i, int j, double x) { t.v[i][j] = x; }
-
-template <typename TM> __device__ __forceinline__ void ld8(const TM* p, TM (&o)[8]);
-template <> __device__ __forceinline__ void ld8<float>(const float* p, float (&o)[8]) {
-  const float4 a = reinterpret_cast<const float4*>(p)[0], b = reinterpret_cast<const float4*>(p)[1];
-  o[0] = a.x; o[1] = a.y; o[2] = a.z; o[3] = a.w; o[4] = b.x; o[5] = b.y; o[6] = b.z; o[7] = b.w;
-}
-template <> __device__ __forceinline__ void ld8<double>(const double* p, double (&o)[8]) {
-#pragma unroll
-  for (int h = 0; h < 4; ++h) { const double2 a = reinterpret_cast<const double2*>(p)[h]; o[2 * h] = a.x; o[2 * h + 1] = a.y; }
-}
-template <typename TM> __device__ __forceinline__ void st8(TM* p, const TM (&o)[8]);
-template <> __device__ __forceinline__ void st8<float>(float* p, const float (&o)[8]) {
-  reinterpret_cast<float4*>(p)[0] = make_float4(o[0], o[1], o[2], o[3]);
-  reinterpret_cast<float4*>(p)[1] = make_float4(o[4], o[5], o[6], o[7]);
-}
-template <> __device__ __forceinline__ void st8<double>(double* p, const double (&o)[8]) {
-#pragma unroll
-  for (int h = 0; h < 4; ++h) reinterpret_cast<double2*>(p)[h] = make_double2(o[2 * h], o[2 * h + 1]);
-}
 
 // Opaque redefinition of the whole tile (no instructions): arithmetic on the tile cannot move across this point.
 __device__ __forceinline__ void tpin(WTile<float>& t) {
@@ -387,129 +295,6 @@ __device__ __forceinline__ void w_sweep(WTile<TM>& t, TM* __restrict__ piv, int 
   }
 }
 
-#ifdef MPCQP_SYM_SWEEP
-// ----------------------------------------------------------------------------------------------------- symmetric sweep (polish, horizon 10)
-// EXPERIMENT, compiled only with -DMPCQP_SYM_SWEEP (round 3: correct -- all GPU tests green -- and no faster: profiles/r03f_symmetric_sweep.txt).
-// S = K^-1 + E is symmetric, and so is every intermediate of the symmetric sweep: sweep only the lower block triangle.  In the
-// stage-major ordering the 60 x 60 matrix is a 10 x 10 grid of 6 x 6 stage blocks; lane l = bi (bi + 1) / 2 + bj holds block (bi, bj),
-// bi >= bj -- 55 lanes, 36 values each instead of 64: 36 instead of 64 fp64 FMAs per pivot and lane.  K^-1 = (+)_q K_q^-1 puts ONE entry
-// on each diagonal position of a block and E_j is the diagonal block (j, j) itself, so the initialisation is six table loads per lane.
-// A pivot row k = 6 p + r is published by the lanes of block row p (their local row r) and, for the columns right of the diagonal, by
-// the lanes of block column p (their local COLUMN r: S[k][c] = S[c][k]).  Afterwards the inverse is handed to the 8 x 8 lane grid of
-// 8 x 8 tiles that the solves and the rank-one updates work on, block row by block row through the 360 doubles of s.E -- and that
-// hand-over (~4 k cycles) takes back what the sweep saves (95 instructions per pivot with 38 fp64 FMAs against 101 with 64).  What
-// would make it pay: solves and updates on the symmetric layout too.
-struct WSym { double v[6][6]; };
-
-__device__ __forceinline__ void sympin(WSym& t) {
-#pragma unroll
-  for (int a = 0; a < 6; ++a) asm volatile("" : "+v"(t.v[a][0]), "+v"(t.v[a][1]), "+v"(t.v[a][2]), "+v"(t.v[a][3]), "+v"(t.v[a][4]), "+v"(t.v[a][5]));
-}
-__device__ __forceinline__ void ld6(const double* p, double (&o)[6]) {
-#pragma unroll
-  for (int h = 0; h < 3; ++h) { const double2 a = reinterpret_cast<const double2*>(p)[h]; o[2 * h] = a.x; o[2 * h + 1] = a.y; }
-}
-__device__ __forceinline__ void st6(double* p, const double (&o)[6]) {
-#pragma unroll
-  for (int h = 0; h < 3; ++h) reinterpret_cast<double2*>(p)[h] = make_double2(o[2 * h], o[2 * h + 1]);
-}
-
-// tile <- -(K^-1 + E)^-1 in the 8 x 8 grid layout, by way of the symmetric half.  kq: [6][10][10] K_q^-1; E: the ten 6 x 6 blocks of
-// T D^-1 T' (consumed by the initialisation, then reused as the hand-over buffer); piv: pivot-row broadcast.
-__device__ __forceinline__ void w_sym_build(WTile<double>& tile, const double* __restrict__ kq, double* __restrict__ E, double* __restrict__ piv,
-                                            int tid) {
-  constexpr int N = 10;
-  asm volatile("" : "+v"(tid));
-  const int l = min(tid, 54);
-  const int bi = (l >= 1) + (l >= 3) + (l >= 6) + (l >= 10) + (l >= 15) + (l >= 21) + (l >= 28) + (l >= 36) + (l >= 45);
-  const int bj = l - ((bi * (bi + 1)) >> 1);
-  const bool on = tid < 55;
-  WSym t;
-  {   // initialisation
-    double kd[6];
-#pragma unroll
-    for (int a = 0; a < 6; ++a) kd[a] = kq[(a * N + bi) * N + bj];
-    const bool dg = bi == bj;
-    const double* Eb = E + 36 * bi;
-#pragma unroll
-    for (int a = 0; a < 6; ++a) {
-#pragma unroll
-      for (int b = 0; b < 6; ++b) {
-        const double e = Eb[6 * a + b];
-        t.v[a][b] = (a == b ? kd[a] : 0.0) + (dg ? e : 0.0);
-      }
-    }
-  }
-  wsync<1>();   // (E has been read: its bytes serve the hand-over below; nothing else writes them during the sweep)
-  for (int p = 0; p < N; ++p) {
-    const bool prow = bi == p, pcol = bj == p;
-#pragma unroll
-    for (int r = 0; r < 6; ++r) {
-      {   // publish pivot row k = 6 p + r
-        double o[6];
-#pragma unroll
-        for (int c = 0; c < 6; ++c) o[c] = prow ? t.v[r][c] : t.v[c][r];   // block row p: local row r;  block column p below the diagonal: local column r
-        if (on && (prow || pcol)) st6(piv + 6 * (prow ? bj : bi), o);
-      }
-      wsync<1>();
-      const double pinv = w_rcp(piv[6 * p + r]);
-      double vr[6], vc[6], m[6];
-      ld6(piv + 6 * bi, vr);
-      ld6(piv + 6 * bj, vc);
-#pragma unroll
-      for (int a = 0; a < 6; ++a) { vr[a] *= pinv; m[a] = vr[a]; }
-      m[r] = prow ? 1.0 - pinv : vr[r];     // (the owner's pivot row comes out of the same FMAs: its tile row IS the published row)
-#pragma unroll
-      for (int a = 0; a < 6; ++a) {
-        const double ma = -m[a];
-#pragma unroll
-        for (int b = 0; b < 6; ++b) t.v[a][b] = fma(ma, vc[b], t.v[a][b]);
-      }
-#pragma unroll
-      for (int a = 0; a < 6; ++a) {         // pivot column (selects, as in w_sweep)
-        const double v = (a == r && prow) ? -pinv : vr[a];
-        t.v[a][r] = pcol ? v : t.v[a][r];
-      }
-      wsync<1>();
-      sympin(t);
-    }
-  }
-  // hand-over to the 8 x 8 grid: block row p of the full matrix (6 rows x 60 columns) through E
-  const int gr = tid >> 3, gc = tid & 7;
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) tile.v[i][j] = (8 * gr + i >= 60 && i == j && gr == gc) ? 1.0 : 0.0;   // identity on the padding
-  }
-  for (int p = 0; p < N; ++p) {
-    if (on && bi == p) {                    // rows 6 p .. 6 p + 5, columns of block bj
-#pragma unroll
-      for (int a = 0; a < 6; ++a) st6(E + 60 * a + 6 * bj, t.v[a]);
-    } else if (on && bj == p) {             // the same rows, columns of block bi > p: the transposed block
-#pragma unroll
-      for (int b = 0; b < 6; ++b) {
-        double o[6];
-#pragma unroll
-        for (int a = 0; a < 6; ++a) o[a] = t.v[a][b];
-        st6(E + 60 * b + 6 * bi, o);
-      }
-    }
-    wsync<1>();
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      const int a = 8 * gr + i - 6 * p;     // local row of this block row, if any
-      if ((unsigned)a < 6u) {
-        double o[8];
-        ld8<double>(E + 60 * a + 8 * gc, o);     // (gc = 7 reads four doubles into the next row / the bytes after E: masked below)
-#pragma unroll
-        for (int j = 0; j < 8; ++j) tile.v[i][j] = (8 * gc + j < 60) ? o[j] : 0.0;
-      }
-    }
-    wsync<1>();
-  }
-}
-#endif
-
 // y = S^-1 x for x in LDS (bv, padded layout): returns element 8 gr + gc (valid on lanes gc < 8) and writes it to cv.
 template <typename TM, int N>
 __device__ __forceinline__ void w_matvec(const WTile<TM>& t, const TM* __restrict__ bv, TM* __restrict__ cv, int gr, int gc) {
@@ -524,13 +309,6 @@ __device__ __forceinline__ void w_matvec(const WTile<TM>& t, const TM* __restric
   const TM tot = -rs8<TM>(acc, gc & 7);   // tile = -S^-1
   if (gc < 8) cv[8 * gr + gc] = tot;
 }
-
-// Per-leg data of a linear solve with M = D + A-stack' K A-stack: columns of the 6 x 3 wrench map and the inverse diagonal.
-template <typename TM>
-struct LegSys {
-  TM A[3][6];    // A[c][q]: wrench component q of reduced variable c
-  TM dinv[3];
-};
 
 // E_j = sum_legs A diag(dinv) A' -> LDS (full 6 x 6 per stage).  Leg lanes; ends with a sync.
 template <typename TM, int N>
@@ -882,15 +660,6 @@ __device__ __forceinline__ void w_warm_start(SmemW<TV, N>& s, const WrTabs& tabs
 }
 
 // ----------------------------------------------------------------------------------------------------- ADMM block
-// OSQP algorithm 1 on the rows  fz | fx - mu fz | fx + mu fz | fy - mu fz | fy + mu fz  of a leg-stage
-// (src/mpc.py:138-173), one lane per leg-stage, scaled duals yh = y / rho.
-template <typename TM>
-struct LegAdmm {
-  TM u[3], z[5], yh[5], g[3];
-  TM lo0, hi0, loA, hiB;     // fz box; friction rows: A rows in [loA, 0], B rows in [0, hiB]
-  TM mu;
-};
-
 // OSQP's rho-adaptation ratio sqrt((|r_prim| / norm_prim) / (|r_dual| / norm_dual)) of the ADMM iterate (u, z, y): one
 // structured gradient for H u + g, the rest per leg.  Uniform result.
 template <typename TV, int N>
@@ -905,25 +674,11 @@ __device__ __forceinline__ float w_ratio(SmemW<TV, N>& s, const WrTabs& tabs, co
   TV hv[3];
   w_grad<TV, N>(s, tabs.K, tid, hv);
   float q[4] = {0.f, 0.f, 0.f, 0.f};
-  if (leg) {   // (differences in TV: the ADMM-only termination test of an fp64 run looks below fp32 resolution)
-    const TV m = mu * u[2];
-    const TV gu[5] = {u[2], u[0] - m, u[0] + m, u[1] - m, u[1] + m};
-#pragma unroll
-    for (int i = 0; i < 5; ++i) {
-      q[0] = fmaxf(q[0], fabsf((float)(gu[i] - z[i])));
-      q[2] = fmaxf(q[2], fmaxf(fabsf((float)gu[i]), fabsf((float)z[i])));
-    }
-    const TV Gy[3] = {y[1] + y[2], y[3] + y[4], y[0] + mu * (-y[1] + y[2] - y[3] + y[4])};
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-      q[1] = fmaxf(q[1], fabsf((float)(hv[a] + Gy[a])));
-      q[3] = fmaxf(q[3], fmaxf(fabsf((float)(hv[a] - g[a])), fabsf((float)Gy[a])));
-    }
-  }
+  if (leg) leg_residuals<TV>(u, z, y, g, hv, mu, q);
   wmax<4, NW>(q, s.red, tid);
-  const float sp = q[2], sd = fmaxf(q[3], s.gmax);
-  if (tid == 0) { s.resid[0] = q[0]; s.resid[1] = q[1]; s.resid[2] = sp; s.resid[3] = sd; }   // |r_prim|, |r_dual| and their norms (ADMM-only termination)
-  return sqrtf((q[0] / fmaxf(sp, 1e-12f)) / fmaxf(q[1] / fmaxf(sd, 1e-12f), 1e-30f));
+  const float sd = fmaxf(q[3], s.gmax);
+  if (tid == 0) { s.resid[0] = q[0]; s.resid[1] = q[1]; s.resid[2] = q[2]; s.resid[3] = sd; }   // |r_prim|, |r_dual| and their norms (ADMM-only termination)
+  return admm_ratio(q, sd);
 }
 
 // The same for the iterate the last ADMM block left in LDS (only needed when its polish steps failed).
@@ -939,129 +694,18 @@ __device__ __forceinline__ float w_ratio_lds(SmemW<TV, N>& s, const WrTabs& tabs
   return w_ratio<TV, N>(s, tabs, u, z, y, g, s.mu, tid < NL, tid);
 }
 
-constexpr double ALPHA_EASY = 1e-2;     // regulariser at which the active-set search is done (continuation start)
 constexpr double ALPHA_FLOOR = 3e-6;    // where a request for alpha = 0 ends (tools/alpha0_floor.py: 1e-5 leaves the net wrench 2e-4 off, 1e-6 stalls)
-#ifndef MPCQP_W_POLISH_PATIENCE
-#define MPCQP_W_POLISH_PATIENCE 1
-#endif
 constexpr int POLISH_CHEAP_LEGS = 3;    // ... on at most this many changed leg-stages (a changed leg-stage costs up to six rank-one updates, ~3.7 us)
 constexpr int POLISH_CHEAP_STEPS = 3;   // further steps of a round beyond the patience rule while they only update the inverse on few leg-stages
                                         // (seven batches of other seeds than the bench's, tools/patience_sweep.py, profiles/r03_cheap_sweep.txt:
                                         //  3 steps on <= 3 leg-stages: +7.9 % on their mean at B = 4096; <= 5 leg-stages: -3 %; without the
                                         //  leg limit -- any step that updates, up to 8 leg-stages -- no gain: a changed leg-stage costs up to six
                                         //  rank-one updates, and a futile step on five of them costs as much as the rebuild it avoids)
-constexpr int POLISH_PATIENCE = MPCQP_W_POLISH_PATIENCE;   // polish steps that may fail to halve the KKT violation before the round gives up
-#ifndef MPCQP_W_ADAPT_AT
-#define MPCQP_W_ADAPT_AT 25
-#endif
-
-// ----------------------------------------------------------------------------------------------------- Anderson acceleration
-// The ADMM block exists to find the active set, and on the QPs that end a launch (two-legged support at low friction) plain
-// ADMM needs 300 - 400 iterations for it: the iteration is a contraction with a factor close to 1 along a few directions.
-// Anderson acceleration (type II, memory AA_M) of the map  v -> f^p(v),  v = z + y / rho  the pre-projection variable of
-// OSQP's iteration (z = clip(v), y / rho = v - z: the five rows of a leg-stage, five numbers per lane):  every p-th iterate is
-// replaced by the combination of the last AA_M + 1 of them that minimises the fixed-point residual in the least-squares sense,
-//     gam = argmin | r - dF gam |,   v+ = f(v) - dX gam,     dF / dX: differences of consecutive residuals / images
-// -- nine inner products over the wave (seven DPP steps each), a regularised 3 x 3 solve in uniform registers, fifteen FMAs per
-// lane, once per p iterations.  numpy study on the condensed QP (tools/accel_study.py): the hardest QPs of five batches reach a
-// polishable iterate in half the iterations (worst case of a batch 375 -> 250 us of solve), the easy ones are unchanged.
-// Only with the polish (MPCQP_FLAG_POLISH): an ADMM-only run is OSQP's algorithm 1 unchanged.  History in fp32 (it steers an
-// extrapolation, it is not part of the answer); base point and images in the iteration's element type.
-#ifndef MPCQP_AA_M
-#define MPCQP_AA_M 3
-#endif
-constexpr int AA_M = MPCQP_AA_M;
-struct LegAA {
-  float rp[5];                       // previous residual f(v) - v
-  float dX[AA_M][5], dF[AA_M][5];    // column AA_M - 1 is the newest
-};
-
-__device__ __forceinline__ void w_aa_reset(LegAA& h) {
-#pragma unroll
-  for (int k = 0; k < 5; ++k) {
-    h.rp[k] = 0.f;
-#pragma unroll
-    for (int j = 0; j < AA_M; ++j) { h.dX[j][k] = 0.f; h.dF[j][k] = 0.f; }
-  }
-}
-
-// One extrapolation: fx = f^p(xb) has just been computed.  Files (fx, fx - xb) in the history and returns the next base point in
-// xb (the extrapolated iterate, or fx itself while the history is empty / when the least-squares problem is degenerate -- then the
-// history restarts).  `have_prev`: an earlier image exists (uniform).  Uniform control flow; ends with the caller's state untouched
-// except xb / fp / h.
-template <typename TM, int NW>
-__device__ __forceinline__ void w_aa_step(LegAA& h, TM (&xb)[5], TM (&fp)[5], const TM (&fx)[5], bool& have_prev, const bool leg,
-                                          float* __restrict__ red, const int tid) {
-  static_assert(AA_M == 3 || AA_M == 2, "the solve below is written for two or three columns");
-  constexpr int M = AA_M, NQ_ = M * (M + 1) / 2 + M;
-  float r[5];
-  if (!have_prev) {   // (uniform) the first image of a history: nothing to combine yet -- file it and go on from it
-#pragma unroll
-    for (int k = 0; k < 5; ++k) { h.rp[k] = leg ? (float)(fx[k] - xb[k]) : 0.f; fp[k] = fx[k]; xb[k] = fx[k]; }
-    have_prev = true;
-    return;
-  }
-#pragma unroll
-  for (int k = 0; k < 5; ++k) {
-    r[k] = leg ? (float)(fx[k] - xb[k]) : 0.f;
-    const float dx = have_prev ? (float)(fx[k] - fp[k]) : 0.f, df = have_prev ? r[k] - h.rp[k] : 0.f;
-#pragma unroll
-    for (int j = 0; j + 1 < M; ++j) { h.dX[j][k] = h.dX[j + 1][k]; h.dF[j][k] = h.dF[j + 1][k]; }
-    h.dX[M - 1][k] = dx; h.dF[M - 1][k] = df;
-    fp[k] = fx[k]; h.rp[k] = r[k];
-  }
-  have_prev = true;
-  float q[NQ_];   // M = 3: 00 01 02 11 12 22 | 0r 1r 2r;  M = 2: 00 01 11 | 0r 1r
-#pragma unroll
-  for (int i = 0; i < NQ_; ++i) q[i] = 0.f;
-#pragma unroll
-  for (int k = 0; k < 5; ++k) {
-    int at = 0;
-#pragma unroll
-    for (int i = 0; i < M; ++i) {
-#pragma unroll
-      for (int j = i; j < M; ++j) { q[at] = fmaf(h.dF[i][k], h.dF[j][k], q[at]); ++at; }
-    }
-#pragma unroll
-    for (int i = 0; i < M; ++i) { q[at] = fmaf(h.dF[i][k], r[k], q[at]); ++at; }
-  }
-  wsum<NQ_, NW>(q, red, tid);
-  float g[M];
-  bool ok;
-  if constexpr (M == 3) {
-    const float tr = q[0] + q[3] + q[5];
-    const bool have = tr > 0.f;
-    const float reg = 1e-6f * tr + 1e-30f;
-    // regularised normal equations by L D L' (uniform values)
-    const float a00 = q[0] + reg, a11 = q[3] + reg, a22 = q[5] + reg, a01 = q[1], a02 = q[2], a12 = q[4];
-    const float i0 = w_rcp(a00), l10 = a01 * i0, l20 = a02 * i0;
-    const float d1 = fmaf(-l10, a01, a11), i1 = w_rcp(d1), t21 = fmaf(-l20, a01, a12), l21 = t21 * i1;
-    const float d2 = fmaf(-l21, t21, fmaf(-l20, a02, a22)), i2 = w_rcp(d2);
-    const float y0 = q[6], y1 = fmaf(-l10, y0, q[7]), y2 = fmaf(-l21, y1, fmaf(-l20, y0, q[8]));
-    g[2] = y2 * i2; g[1] = fmaf(-l21, g[2], y1 * i1); g[0] = fmaf(-l20, g[2], fmaf(-l10, g[1], y0 * i0));
-    ok = have && d1 > 0.f && d2 > 0.f && fabsf(g[0]) + fabsf(g[1]) + fabsf(g[2]) <= 1e4f;   // (a NaN fails the comparison)
-    if (!have) have_prev = true; else if (!ok) { w_aa_reset(h); have_prev = false; }   // degenerate history: start again from this iterate
-  } else {
-    const float tr = q[0] + q[2];
-    const bool have = tr > 0.f;
-    const float reg = 1e-6f * tr + 1e-30f;
-    const float a00 = q[0] + reg, a11 = q[2] + reg, a01 = q[1];
-    const float i0 = w_rcp(a00), l10 = a01 * i0, d1 = fmaf(-l10, a01, a11), i1 = w_rcp(d1);
-    const float y0 = q[3], y1 = fmaf(-l10, y0, q[4]);
-    g[1] = y1 * i1; g[0] = fmaf(-l10, g[1], y0 * i0);
-    ok = have && d1 > 0.f && fabsf(g[0]) + fabsf(g[1]) <= 1e4f;
-    if (have && !ok) { w_aa_reset(h); have_prev = false; }
-  }
-#pragma unroll
-  for (int k = 0; k < 5; ++k) {
-    float c = 0.f;
-#pragma unroll
-    for (int j = 0; j < M; ++j) c = fmaf(g[j], h.dX[j][k], c);
-    xb[k] = ok ? fx[k] - (TM)c : fx[k];
-  }
-}
+constexpr int POLISH_PATIENCE = 1;   // polish steps that may fail to halve the KKT violation before the round gives up
 
 // The leg's 6 x 3 wrench map [B_l ; contact / m I] and the inverse diagonal of D = 2 alpha + sigma + rho G'G.
+// (kept equal by hand with sg_admm_sys / sg_polish_sys / sg_polish_rule of mpcqp_stage.h, as are the warm start's per-leg part and the
+//  relaxation step: profiles/r07_leg_share_check.txt)
 template <typename TV, typename TM, int N>
 __device__ __forceinline__ void w_admm_sys(const SmemW<TV, N>& s, const DevCfg& cfg, int L, float rho, LegSys<TM>& Ls) {
   const bool stance = s.ct[L] != 0;
@@ -1103,7 +747,7 @@ __device__ __forceinline__ void w_admm(SmemW<TV, N>& s, const DevCfg& cfg, const
   const int seg_len = (!REFINE && sizeof(TM) == 4 && cfg.accel_p > 0 && cfg.accel_restart > 0) ? cfg.accel_restart : (1 << 30);
   const bool check = adapt && cfg.early_check;
   // (a cold solve's first block is split at ADAPT_AT with or without the check: the history's one fresh start there is worth 2-3 %)
-  int it = 0, seg_end = min(K, (adapt && MPCQP_W_ADAPT_AT < K) ? MPCQP_W_ADAPT_AT : seg_len);
+  int it = 0, seg_end = min(K, (adapt && ADAPT_AT < K) ? ADAPT_AT : seg_len);
   int hard = 0;
   float ratio = 0.f;
   STAMP_INIT
@@ -1196,14 +840,8 @@ __device__ __forceinline__ void w_admm(SmemW<TV, N>& s, const DevCfg& cfg, const
           aa_park();
         }
         for (int i = 0; i < n_it; ++i) {
-          // rhs = sigma u - g + rho G'(z - yh)
-          TM v[5];
-#pragma unroll
-          for (int k = 0; k < 5; ++k) v[k] = A.z[k] - A.yh[k];
-          const TM w0 = v[1] + v[2], w1 = v[3] + v[4], w2 = fma(A.mu, (v[2] - v[1]) + (v[4] - v[3]), v[0]);
-          const TM rhs[3] = {fma(r, w0, fma(sigma, A.u[0], -A.g[0])), fma(r, w1, fma(sigma, A.u[1], -A.g[1])),
-                             fma(r, w2, fma(sigma, A.u[2], -A.g[2]))};
-          TM ut[3];
+          TM rhs[3], ut[3];
+          leg_admm_rhs<TM>(A, sigma, r, rhs);
           w_solve<TM, N>(tile, Ls, rhs, ut, bv, cv, tid, gr, gc);
           if constexpr (REFINE) {
             // (own instantiation of the kernel, REFINE = true: the extra live values cost the all-fp64 kernel 85 more spilled registers)
@@ -1251,19 +889,14 @@ __device__ __forceinline__ void w_admm(SmemW<TV, N>& s, const DevCfg& cfg, const
               w_aa_step<TM, NW>(aa, aa_xb, aa_fp, fx, aa_have, leg, s.aared, tid);
               aa_park();
 #pragma unroll
-              for (int k = 0; k < 5; ++k) {
-                const TM lo = k == 0 ? A.lo0 : ((k & 1) ? A.loA : (TM)0), hi = k == 0 ? A.hi0 : ((k & 1) ? (TM)0 : A.hiB);
-                const TM zn = fmin(fmax(aa_xb[k], lo), hi);
-                A.yh[k] = aa_xb[k] - zn;
-                A.z[k] = zn;
-              }
+              for (int k = 0; k < 5; ++k) leg_admm_project<TM>(A, k, aa_xb[k]);
             }
           }
         }
         it = seg_end;
         STAMP(4);
         if (it >= K) break;
-        if (check && !hard && it == MPCQP_W_ADAPT_AT) {   // the single early rho check: OSQP's residual ratio after the first ADAPT_AT iterations
+        if (check && !hard && it == ADAPT_AT) {   // the single early rho check: OSQP's residual ratio after the first ADAPT_AT iterations
           const TV u3[3] = {(TV)A.u[0], (TV)A.u[1], (TV)A.u[2]}, g3[3] = {(TV)A.g[0], (TV)A.g[1], (TV)A.g[2]};
           TV z5[5], y5[5];
 #pragma unroll
@@ -1296,21 +929,6 @@ __device__ __forceinline__ void w_admm(SmemW<TV, N>& s, const DevCfg& cfg, const
 }
 
 // ----------------------------------------------------------------------------------------------------- polish step
-// One primal-dual active-set step from (s.pu, s.py) (OSQP's `polish`, specialised to the 5 rows of a leg-stage): fz at a
-// bound and/or fx, fy tied to +-mu fz per leg; the equality-constrained QP is solved in the free variables through the
-// wrench-space system in TP precision; duals from stationarity; accepted only on a KKT check.  Returns 1 when accepted
-// (answer in s.uv), else 0 with (s.pu, s.py) replaced by the candidate.
-// The active set of a leg-stage as the polish uses it: zs / xs / ys in {-1, 0, +1} (fz at fmin / free / at fmax; fx, fy tied
-// to -mu fz / free / tied to +mu fz), packed as (zs + 1) | (xs + 1) << 2 | (ys + 1) << 4.
-struct ActSet {
-  int zs, xs, ys;
-  bool ez, ex, ey;
-  __device__ __forceinline__ ActSet(int code, bool stance) {
-    zs = (code & 3) - 1; xs = ((code >> 2) & 3) - 1; ys = ((code >> 4) & 3) - 1;
-    ez = stance && zs == 0; ex = stance && xs == 0; ey = stance && ys == 0;
-  }
-};
-
 // The leg's 6 x 3 reduced wrench map (tied tangential components ride on fz) and inverse diagonal 1 / (2 alpha Z'Z).
 template <typename TV, typename TP, int N>
 __device__ __forceinline__ void w_polish_sys(const SmemW<TV, N>& s, int L, const ActSet& a, LegSys<TP>& Ls) {
@@ -1390,7 +1008,7 @@ __device__ __forceinline__ unsigned w_aset_hash(SmemW<TV, N>& s, const int tid) 
 // (about two pivots' work) against the 6 N pivots of a rebuild.  At most MPCQP_W_INCR_LEGS changed leg-stages
 // and MPCQP_W_INCR_STEPS updates in a row; a candidate from a drifted inverse would simply fail the KKT test.
 template <typename TV, typename TP, int N, bool VM>
-__device__ __forceinline__ int w_polish_round(SmemW<TV, N>& s, const WrTabs& tabs, const TP* __restrict__ kinvT, const int tid0,
+__device__ __forceinline__ int w_polish_round(SmemW<TV, N>& s, const WrTabs& tabs, const int tid0,
                                               const int budget, const bool last, const int trace_tag, const int incr_legs,
                                               const int patience, const int cheap_steps, const int cheap_legs, const int last_patience) {
   constexpr int NL = WG<N>::NL, NW = WG<N>::NW, G = WG<N>::G;
@@ -1425,17 +1043,9 @@ __device__ __forceinline__ int w_polish_round(SmemW<TV, N>& s, const WrTabs& tab
     WTile<TP> tile;
     {   // ---- S = K^-1 + E, swept in place
       const int tid = fresh_tid<NW>(tid0), gr = tid / G, gc = tid % G;
-#ifdef MPCQP_SYM_SWEEP   // (experiment: the lower block triangle only, see w_sym_build)
-      if constexpr (N == 10 && NW == 1 && sizeof(TP) == 8) {
-        w_sym_build(tile, kinvT, E, piv, tid);
-        STAMP(10);
-      } else
-#endif
-      {
-        w_tile_init<TP, N, VM>(tile, kq, E, gr, gc);
-        STAMP(10);
-        w_sweep<TP, N>(tile, piv, gr, gc);
-      }
+      w_tile_init<TP, N, VM>(tile, kq, E, gr, gc);
+      STAMP(10);
+      w_sweep<TP, N>(tile, piv, gr, gc);
     }
     STAMP(11);
     int in_row = 0;
@@ -1742,8 +1352,6 @@ mpcqp_wrench_solve(const DevCfg* __restrict__ cfgp, const WrTabs tabs, const Fas
   __shared__ SmemW<TV, N> s;
   __shared__ int s_next;
   const DevCfg& cfg = *cfgp;
-  const TP* kinvP;   // (the compact table: only the MPCQP_SYM_SWEEP experiment of the polish still reads it)
-  if constexpr (sizeof(TP) == 4) kinvP = tabs.kinv32; else kinvP = tabs.kinv64;
   for (int guard = 0; guard <= Btot; ++guard) {
     // The lane index is made opaque once per QP: everything derived from it (addresses into the constant tables, role
     // masks, loop coefficients) is invariant across the QPs of a resident wave, and LLVM would hoist all of it out of
@@ -1840,7 +1448,7 @@ mpcqp_wrench_solve(const DevCfg* __restrict__ cfgp, const WrTabs tabs, const Fas
 #else
       const int trace_tag = -1;
 #endif
-      if (budget > 0) ok = __builtin_amdgcn_readfirstlane(w_polish_round<TV, TP, N, sizeof(TM) == 4>(s, tabs, kinvP, tid0, budget, last, trace_tag, cfg.incr_legs, cfg.patience, cfg.cheap_steps, cfg.cheap_legs, (kind == R_ADMM) ? cfg.last_patience : 0));
+      if (budget > 0) ok = __builtin_amdgcn_readfirstlane(w_polish_round<TV, TP, N, sizeof(TM) == 4>(s, tabs, tid0, budget, last, trace_tag, cfg.incr_legs, cfg.patience, cfg.cheap_steps, cfg.cheap_legs, (kind == R_ADMM) ? cfg.last_patience : 0));
       if (ok == 1 && s.alpha > s.alpha_target) {   // next continuation level, from this optimum and its multipliers
         const int tid = fresh_tid<NW>(tid0);
         for (int i = tid; i < n; i += NT) s.ua[i] = s.uv[i];            // the last accepted answer and its multipliers (the ADMM

@@ -1,4 +1,4 @@
-"""Diagnostic: early-rho-check threshold (env MPCQP_ADAPT_THR, read at mpcqp_create) over seeds that are NOT the bench seed,
+"""Diagnostic: early-rho-check threshold (the engine override adapt_thr; values from env SW_THR) over seeds that are NOT the bench seed,
 plus the bench batch and a 65536 batch."""
 import os, sys
 import numpy as np, torch

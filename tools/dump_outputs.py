@@ -1,6 +1,7 @@
 """Developer aid for changes that must not change a result: seeded outputs of every entry point with whichever csrc/libmpcqp.so
 is in place, as raw arrays in one .npz, and their comparison byte for byte (integer views: NaN payloads and signed zeros count).
 Solves (tuple, gait S = 2, gait steps S = 4; f32 / f64 I/O; N = 10 / 20 / 60; MIXED / F64; warm start + shift over three calls),
+the stage-wise engine at N = 60 and, by MPCQP_FLAG_STAGE_KERNEL, at N = 10 (MIXED / F64, cold and warm-started with shift),
 roll-outs on the model and on the plant (T = 50, B = 1024, cold and warm, with the malformed plan rows of tests/test_rollout.py),
 planner + swing trajectories, plant step, leg Jacobians and torque map.  One process per library build: copy the wanted build over
 csrc/libmpcqp.so before starting each.
@@ -66,6 +67,22 @@ for io in ("f32", "f64"):
         for k in ("u", "X", "status", "iters", "res"): put(f"warm{call}_{io}_{k}", o[k])
     del sol
     print("solves", io, "done", flush=True)
+
+# ---- the stage-wise engine by itself: the reference's horizon, and horizon 10 by MPCQP_FLAG_STAGE_KERNEL; MIXED / F64; cold, and
+#      warm-started with shift over three consecutive calls
+for N, flags in ((60, mpcqp.FLAG_POLISH), (10, mpcqp.FLAG_POLISH | mpcqp.FLAG_STAGE_KERNEL)):
+    B = 256 if N == 60 else 1024
+    d0 = mpcqp.synth.make_batch(B, N=N, seed=404, gait_names=("trot", "amble", "gallop"), mus=(0.3, 0.7, 1.0))
+    for prec in ("mixed", "f64"):
+        for warm in (False, True):
+            sol = mpcqp.MPCBatch(N=N, delta=0.03, io_dtype="f64", precision=prec, warm_start=warm, warm_shift=warm, flags=flags)
+            d = sol.upload(d0)
+            for call in range(3 if warm else 1):
+                o = sol.solve_batch(d["x0"], d["r"], d["contact"], d["xdes"], d["mu"], want_X=True)
+                torch.cuda.synchronize()
+                for k in ("u", "X", "status", "iters", "res"): put(f"stage_N{N}_{prec}_{'warm%d' % call if warm else 'cold'}_{k}", o[k])
+            del sol
+print("stage engine done", flush=True)
 
 # ---- roll-outs, T = 50, B = 1024, with the malformed plan rows of tests/test_rollout.py
 from test_rollout import _malformed
