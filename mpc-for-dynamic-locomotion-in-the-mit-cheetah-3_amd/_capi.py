@@ -1,4 +1,4 @@
-"""ctypes binding of the C-ABI declared in include/mpcqp.h and its product-only extensions include/mpcqp_plan.h and include/mpcqp_sim.h.
+"""ctypes binding of the C-ABI declared in include/mpcqp.h and its product-only extensions include/mpcqp_plan.h, mpcqp_sim.h and mpcqp_model.h.
 
 The product path loads ``csrc/libmpcqp.so`` (hand-written HIP for gfx950) and nothing else: if that library is
 missing or cannot be loaded, importing the engine raises -- there is no CPU fallback.  The binding itself is
@@ -50,6 +50,8 @@ EXPORTED_SYMBOLS = (
 PLAN_SYMBOLS = ("mpcqp_plan_footsteps", "mpcqp_swing_trajectories")
 # include/mpcqp_sim.h: the rigid-body plant, likewise product-only
 SIM_SYMBOLS = ("mpcqp_plant_step", "mpcqp_rollout_plant")
+# include/mpcqp_model.h: per-robot model rows, likewise product-only
+MODEL_SYMBOLS = ("mpcqp_set_models", "mpcqp_clear_models")
 
 
 class MpcQpLegGeometry(ctypes.Structure):
@@ -131,6 +133,12 @@ class Library:
             L.mpcqp_plant_step.restype = c_int32
             L.mpcqp_rollout_plant.argtypes = [c_void_p, c_int64, c_int32, c_int32] + [c_void_p] * 10 + [c_int32] + [c_void_p] * 5
             L.mpcqp_rollout_plant.restype = c_int32
+        self.has_model = all(hasattr(L, sym) for sym in MODEL_SYMBOLS)
+        if self.has_model:
+            L.mpcqp_set_models.argtypes = [c_void_p, c_int64, c_void_p, c_void_p]
+            L.mpcqp_set_models.restype = c_int32
+            L.mpcqp_clear_models.argtypes = [c_void_p]
+            L.mpcqp_clear_models.restype = c_int32
 
     def version(self) -> int:
         return int(self.lib.mpcqp_version())
@@ -282,6 +290,23 @@ class Engine:
                                                     forces or None, solved or None, stream or None)
         if rc != 0:
             raise MpcQpError(f"mpcqp_rollout_plant failed with code {rc}: {self.last_error()}")
+
+    def _model_call(self, name):
+        if not self.library.has_model:
+            raise MpcQpError(f"{name}: {self.library.path} does not export include/mpcqp_model.h (product library only)")
+        return getattr(self.library.lib, name)
+
+    def set_models_ptr(self, B, model, stream=0):
+        """Raw call of mpcqp_set_models (include/mpcqp_model.h): `model` is the address of an fp64 [B,6] device table."""
+        rc = self._model_call("mpcqp_set_models")(self._h, int(B), model or None, stream or None)
+        if rc != 0:
+            raise MpcQpError(f"mpcqp_set_models failed with code {rc}: {self.last_error()}")
+
+    def clear_models(self):
+        """mpcqp_clear_models (include/mpcqp_model.h): back to the configuration's m, Ibody_inv, f_min, f_max."""
+        rc = self._model_call("mpcqp_clear_models")(self._h)
+        if rc != 0:
+            raise MpcQpError(f"mpcqp_clear_models failed with code {rc}: {self.last_error()}")
 
     def torque_map_ptr(self, B, u, jac, tau, stream=0):
         rc = self.library.lib.mpcqp_torque_map(self._h, int(B), u, jac, tau, stream or None)

@@ -22,6 +22,9 @@ struct FastIn {
   int shift;           // MPCQP_FLAG_WARM_SHIFT: the guess and the record are one control tick old: use stage k + 1 for stage k
 };
 
+// A model row as the engine keeps it (DevCfg::model, mpcqp_model.h): 1 / m, 1 / Ixx, 1 / Iyy, 1 / Izz, f_min, f_max.  An invalid
+// row is six NaNs.
+constexpr int MODEL_ROW = 6;
 
 
 #ifndef MPCQP_HARD_ITER_FACTOR

@@ -58,6 +58,10 @@ struct DevCfg {
   int accel_p;          // Anderson acceleration of the ADMM blocks: an extrapolation every accel_p iterations (0: off)
   int early_check;      // the single early rho check of a cold solve's first block (off by default where the acceleration runs)
   int accel_restart;    // iterations after which the acceleration's history starts afresh (0: only with a new matrix)
+  // Per-robot model rows (include/mpcqp_model.h): the engine's table [B][MODEL_ROW], null = this configuration's row for every QP.
+  // In the device copy only, written on the device by mpcqp_set_models / mpcqp_clear_models and read by the MODEL instantiations of
+  // the solve kernels in their setup phase (a pointer among the kernel arguments stays in registers across a resident workgroup's QPs).
+  const double* model;
 };
 
 // Sum over the 8 lanes of a leg group with DPP lane moves (no LDS crossbar): quad butterfly, then half-row mirror.

@@ -3,7 +3,7 @@
 // Replaces, for a batch of B independent robots, the solve the reference performs once per control tick:
 // CasADi Opti('conic') -> OSQP on the QP of src/mpc.py:58-173, filled at src/mpc.py:242-255, solved at :258.
 //
-// This translation unit is the C-ABI of include/mpcqp.h, mpcqp_plan.h and mpcqp_sim.h: the handle, its host helpers (I/O-type
+// This translation unit is the C-ABI of include/mpcqp.h, mpcqp_plan.h, mpcqp_sim.h and mpcqp_model.h: the handle, its host helpers (I/O-type
 // dispatch, workspaces, the policy behind the configuration's defaults) and the extern "C" entry points.  The device code is in
 //   mpcqp_wrench.h       the engine: wrench-space (Woodbury) form, H = 2 alpha I + T'KT with a 6N x 6N system, one QP per wave
 //                        (horizon 10) or per four waves (horizon 20), fp32 or fp64 ADMM, fp64 active-set polish, ADMM-only mode
@@ -14,16 +14,19 @@
 //                        torque map, leg kinematics
 //   mpcqp_plan.h         footstep plans, swing-foot trajectories and the plan clock
 //   mpcqp_plant.h        the rigid-body plant that can replace the roll-out's world step
+//   mpcqp_model.h        per-robot model rows: the conversion of the caller's table into the engine's
 // DESIGN.md has the derivations.
 
 #include "mpcqp_wrench.h"
 #include "mpcqp_stage.h"
 #include "mpcqp_elementwise.h"
+#include "mpcqp_model.h"
 
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <new>
+#include <type_traits>
 
 #ifndef MPCQP_DIAG_LDSPAD   // (diagnostic builds only: dynamic LDS that limits the resident workgroups per CU, profiles/r03f_occupancy_study.txt)
 #define MPCQP_DIAG_LDSPAD 0
@@ -57,6 +60,9 @@ struct mpcqp_engine {
   int stage_slots = 0;        // ... and how many of them the device holds
   float* dual_mem = nullptr;  // warm-started engines: multipliers of the previous solve per batch slot [dual_cap][4 N][5]
   int64_t dual_cap = 0;
+  double* model_mem = nullptr;   // per-robot model rows (include/mpcqp_model.h): the converted table [model_cap][MODEL_ROW]
+  int64_t model_B = 0;        // rows of the table that is set; 0 = none, every QP has the configuration's
+  int64_t model_cap = 0;
   bool timed = false;
   char err[512];
 };
@@ -124,15 +130,20 @@ hipError_t launch_wrench(mpcqp_engine* e, int64_t B, const FastIn<TIO>& in, void
     }
   }
   const WrTabs tabs = {e->wr_K, e->wr_kinv32, e->wr_kinv64, e->wr_klane32, e->wr_klane64};
-  if (e->cfg.precision == MPCQP_PREC_MIXED)
-    hipLaunchKernelGGL((mpcqp_wrench_solve<double, float, double, TIO, N>), grid, dim3(WG<N>::NT), MPCQP_DIAG_LDSPAD, s, e->dcfg, tabs, in, (TIO*)u,
-                       (TIO*)X, st, it, res, ob, (int)B);
-  else if (e->dev.refine_admm)   // tight-tolerance ADMM-only runs: the instantiation with a refinement step per linear solve
-    hipLaunchKernelGGL((mpcqp_wrench_solve<double, double, double, TIO, N, true>), grid, dim3(WG<N>::NT), 0, s, e->dcfg, tabs, in, (TIO*)u,
-                       (TIO*)X, st, it, res, ob, (int)B);
-  else
-    hipLaunchKernelGGL((mpcqp_wrench_solve<double, double, double, TIO, N>), grid, dim3(WG<N>::NT), 0, s, e->dcfg, tabs, in, (TIO*)u,
-                       (TIO*)X, st, it, res, ob, (int)B);
+  // (MODEL: a handle with a model table runs the instantiations that read it; without one, the kernels are what they were)
+  auto launch = [&](auto model) {
+    constexpr bool MODEL = decltype(model)::value;
+    if (e->cfg.precision == MPCQP_PREC_MIXED)
+      hipLaunchKernelGGL((mpcqp_wrench_solve<double, float, double, TIO, N, false, MODEL>), grid, dim3(WG<N>::NT), MPCQP_DIAG_LDSPAD, s, e->dcfg, tabs, in,
+                         (TIO*)u, (TIO*)X, st, it, res, ob, (int)B);
+    else if (e->dev.refine_admm)   // tight-tolerance ADMM-only runs: the instantiation with a refinement step per linear solve
+      hipLaunchKernelGGL((mpcqp_wrench_solve<double, double, double, TIO, N, true, MODEL>), grid, dim3(WG<N>::NT), 0, s, e->dcfg, tabs, in, (TIO*)u,
+                         (TIO*)X, st, it, res, ob, (int)B);
+    else
+      hipLaunchKernelGGL((mpcqp_wrench_solve<double, double, double, TIO, N, false, MODEL>), grid, dim3(WG<N>::NT), 0, s, e->dcfg, tabs, in, (TIO*)u,
+                         (TIO*)X, st, it, res, ob, (int)B);
+  };
+  if (e->model_B > 0) launch(std::true_type{}); else launch(std::false_type{});
   return hipGetLastError();
 }
 
@@ -141,10 +152,14 @@ template <typename TIO>
 hipError_t launch_stage(mpcqp_engine* e, int64_t B, const FastIn<TIO>& in, void* u, void* X, int32_t* st, int32_t* it, float* res, hipStream_t s) {
   const int64_t slots = e->stage_slots > 0 ? e->stage_slots : 256;
   const dim3 grid((unsigned)(B < slots ? B : slots));
-  if (e->cfg.precision == MPCQP_PREC_F64)
-    hipLaunchKernelGGL((mpcqp_stage_solve<double, TIO>), grid, dim3(SG_NT), 0, s, e->dcfg, in, (TIO*)u, (TIO*)X, st, it, res, e->stage_ws, e->cfg.N, (int)B);
-  else
-    hipLaunchKernelGGL((mpcqp_stage_solve<float, TIO>), grid, dim3(SG_NT), 0, s, e->dcfg, in, (TIO*)u, (TIO*)X, st, it, res, e->stage_ws, e->cfg.N, (int)B);
+  auto launch = [&](auto model) {
+    constexpr bool MODEL = decltype(model)::value;
+    if (e->cfg.precision == MPCQP_PREC_F64)
+      hipLaunchKernelGGL((mpcqp_stage_solve<double, TIO, MODEL>), grid, dim3(SG_NT), 0, s, e->dcfg, in, (TIO*)u, (TIO*)X, st, it, res, e->stage_ws, e->cfg.N, (int)B);
+    else
+      hipLaunchKernelGGL((mpcqp_stage_solve<float, TIO, MODEL>), grid, dim3(SG_NT), 0, s, e->dcfg, in, (TIO*)u, (TIO*)X, st, it, res, e->stage_ws, e->cfg.N, (int)B);
+  };
+  if (e->model_B > 0) launch(std::true_type{}); else launch(std::false_type{});
   return hipGetLastError();
 }
 
@@ -180,6 +195,13 @@ hipError_t enqueue_solve(mpcqp_engine* h, int64_t B, const FastIn<T>& in, T* u, 
   if (!wrench_serves(h->cfg)) return launch_stage<T>(h, B, in, u, X, status, iters, res, st);
   if (h->cfg.N == 10) return launch_wrench<T, 10>(h, B, in, u, X, status, iters, res, st);
   return launch_wrench<T, 20>(h, B, in, u, X, status, iters, res, st);
+}
+
+// A solving entry point's batch against the model table, when one is set (include/mpcqp_model.h): row b belongs to batch slot b.
+int models_match(mpcqp_engine* h, int64_t B, const char* who) {
+  if (h->model_B == 0 || h->model_B == B) return MPCQP_OK;
+  snprintf(h->err, sizeof(h->err), "%s: batch size %lld, but the model table has %lld rows", who, (long long)B, (long long)h->model_B);
+  return MPCQP_EINVAL;
 }
 
 // The event pair behind mpcqp_last_kernel_ms: an entry point records ev0 in front of its first launch and ev1 behind its last.
@@ -364,6 +386,7 @@ void resolve_policy(const MpcQpConfig& cfg, DevCfg& d, int& listed_max) {
   // The round that nothing follows (iteration cap reached) used to run its whole polish budget; it now gives up after four steps that
   // fail to halve the KKT violation (horizon 10: 9.04 -> 9.35 M on the held-out mean, the same QPs solved, profiles/r03_last_patience_sweep.txt)
   d.last_patience = cfg.polish_last_patience > 0 ? cfg.polish_last_patience : (cfg.polish_last_patience < 0 || N > 10 ? 0 : 4);
+  d.model = nullptr;   // (the device copy's is set by mpcqp_set_models)
   d.refine_admm = (!polish && cfg.precision == MPCQP_PREC_F64 && cfg.eps_abs < 1e-6) ? 1 : 0;
 }
 
@@ -471,6 +494,7 @@ static void free_engine(mpcqp_engine* h) {
   if (h->dcfg) (void)hipFree(h->dcfg);
   if (h->order_mem) (void)hipFree(h->order_mem);
   if (h->dual_mem) (void)hipFree(h->dual_mem);
+  if (h->model_mem) (void)hipFree(h->model_mem);
   if (h->gait_mem) (void)hipFree(h->gait_mem);
   if (h->roll_mem) (void)hipFree(h->roll_mem);
   if (h->plan_ws) (void)hipFree(h->plan_ws);
@@ -583,6 +607,7 @@ int mpcqp_solve_batch(mpcqp_handle h, int64_t B, const void* x0, const void* r, 
   if (B < 0 || B > 0x7fffffff) return fail(h, MPCQP_EINVAL, "mpcqp_solve_batch: batch size out of range");
   if (B > 0 && (!x0 || !r || !contact || !xdes || !mu || !u_out || !status || !iters))
     return fail(h, MPCQP_EINVAL, "mpcqp_solve_batch: null buffer");
+  if (B > 0) if (const int rc = models_match(h, B, "mpcqp_solve_batch")) return rc;
   DeviceGuard guard(h->cfg.device);
   if (guard.err != hipSuccess) return fail(h, MPCQP_EHIP, "hipSetDevice", guard.err);
   if (reserve_workspace(h, B) != MPCQP_OK) return fail(h, MPCQP_ENOMEM, "mpcqp_solve_batch: workspace allocation failed");
@@ -607,6 +632,7 @@ int mpcqp_solve_batch_gait_steps(mpcqp_handle h, int64_t B, int32_t S, const voi
   if (B > 0 && (!x0 || !ref || !feet0 || !footholds || !gait || !feet_id || !mu || !u_out || !status || !iters))
     return fail(h, MPCQP_EINVAL, "mpcqp_solve_batch_gait_steps: null buffer");
   if (B == 0) return mpcqp_solve_batch(h, 0, x0, nullptr, nullptr, nullptr, mu, u_out, X_out, status, iters, res, stream);
+  if (const int rc = models_match(h, B, "mpcqp_solve_batch_gait_steps")) return rc;
   DeviceGuard guard(h->cfg.device);
   if (guard.err != hipSuccess) return fail(h, MPCQP_EHIP, "hipSetDevice", guard.err);
   if (reserve_workspace(h, B) != MPCQP_OK || reserve_gait(h, B) != MPCQP_OK)
@@ -703,6 +729,7 @@ int mpcqp_rollout(mpcqp_handle h, int64_t B, int32_t T, int32_t S, void* x, void
   if (B < 0 || B > 0x7fffffff || T < 0 || S < 1) return fail(h, MPCQP_EINVAL, "mpcqp_rollout: size out of range");
   if (B > 0 && (!x || !ref || !plan_pos || !plan_feet_id || !plan_meta || !tick || !mu)) return fail(h, MPCQP_EINVAL, "mpcqp_rollout: null buffer");
   if (B == 0 || T == 0) return MPCQP_OK;
+  if (const int rc = models_match(h, B, "mpcqp_rollout")) return rc;
   DeviceGuard guard(h->cfg.device);
   if (guard.err != hipSuccess) return fail(h, MPCQP_EHIP, "hipSetDevice", guard.err);
   return rollout_run(h, B, T, S, x, ref, plan_pos, plan_feet_id, plan_meta, tick, mu, actual, desired, forces, solved, stream, nullptr);
@@ -720,10 +747,43 @@ int mpcqp_rollout_plant(mpcqp_handle h, int64_t B, int32_t T, int32_t S, void* x
   if (B > 0 && (!x || !ref || !plan_pos || !plan_feet_id || !plan_meta || !tick || !mu))
     return fail(h, MPCQP_EINVAL, "mpcqp_rollout_plant: null buffer");
   if (B == 0 || T == 0) return MPCQP_OK;
+  if (const int rc = models_match(h, B, "mpcqp_rollout_plant")) return rc;
   DeviceGuard guard(h->cfg.device);
   if (guard.err != hipSuccess) return fail(h, MPCQP_EHIP, "hipSetDevice", guard.err);
   const RolloutPlantArgs plant = {body, push, push ? push_ticks : nullptr, n};
   return rollout_run(h, B, T, S, x, ref, plan_pos, plan_feet_id, plan_meta, tick, mu, actual, desired, forces, solved, stream, &plant);
+}
+
+int mpcqp_set_models(mpcqp_handle h, int64_t B, const double* model, void* stream) {
+  if (!h) return MPCQP_EINVAL;
+  if (B <= 0 || B > 0x7fffffff) return fail(h, MPCQP_EINVAL, "mpcqp_set_models: batch size out of range");
+  if (!model) return fail(h, MPCQP_EINVAL, "mpcqp_set_models: null model table");
+  DeviceGuard guard(h->cfg.device);
+  if (guard.err != hipSuccess) return fail(h, MPCQP_EHIP, "hipSetDevice", guard.err);
+  if (h->model_cap < B) {   // once per size, like the mpcqp_reserve workspace (grow waits for the device before it frees the old
+                            // buffer; when the allocation fails the old table stays set)
+    if (!grow(h->model_mem, (size_t)B * MODEL_ROW * sizeof(double))) return fail(h, MPCQP_ENOMEM, "mpcqp_set_models: table allocation failed");
+    h->model_cap = B;
+    h->model_B = 0;   // (the device's pointer is the freed buffer until the kernel below has run: if its launch fails, no solve may read it)
+  }
+  hipLaunchKernelGGL(mpcqp_model_rows_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, (hipStream_t)stream, model, h->model_mem, B, h->dcfg);
+  const int rc = launched(h, "model table kernel launch");
+  h->model_B = rc == MPCQP_OK ? B : 0;
+  return rc;
+}
+
+int mpcqp_clear_models(mpcqp_handle h) {
+  if (!h) return MPCQP_EINVAL;
+  if (h->model_B == 0) return MPCQP_OK;
+  DeviceGuard guard(h->cfg.device);
+  if (guard.err != hipSuccess) return fail(h, MPCQP_EHIP, "hipSetDevice", guard.err);
+  // No stream argument: the solves enqueued so far (on whatever stream) finish with the table, every later one starts without it.
+  hipError_t he = hipDeviceSynchronize();
+  if (he == hipSuccess) { hipLaunchKernelGGL(mpcqp_model_clear_kernel, dim3(1), dim3(1), 0, nullptr, h->dcfg); he = hipGetLastError(); }
+  if (he == hipSuccess) he = hipDeviceSynchronize();
+  if (he != hipSuccess) return fail(h, MPCQP_EHIP, "mpcqp_clear_models", he);
+  h->model_B = 0;
+  return MPCQP_OK;
 }
 
 int mpcqp_plant_step(mpcqp_handle h, int64_t B, const void* x, const void* f, const void* feet, const uint8_t* contact,

@@ -1050,7 +1050,8 @@ __device__ __forceinline__ int sg_polish_round(SmemS& s, const DevCfg& cfg, SLeg
 
 // ----------------------------------------------------------------------------------------------------- the kernel
 // Persistent workgroups: workgroup w solves QPs w, w + gridDim.x, ...; its factor workspace is ws_all + w * SG_WS_DOUBLES.
-template <typename TM, typename TIO>
+// MODEL: the launch has a model table (mpcqp_model.h, DevCfg::model), as in mpcqp_wrench.h.
+template <typename TM, typename TIO, bool MODEL = false>
 __global__ void __launch_bounds__(SG_NT)
 mpcqp_stage_solve(const DevCfg* __restrict__ cfgp, const FastIn<TIO> in, TIO* ug, TIO* __restrict__ Xg, int* __restrict__ statusg,
                   int* __restrict__ itersg, float* __restrict__ resg, double* __restrict__ ws_all, const int N, const int Btot) {
@@ -1078,6 +1079,15 @@ mpcqp_stage_solve(const DevCfg* __restrict__ cfgp, const FastIn<TIO> in, TIO* ug
     for (int i = tid; i < NX; i += SG_NT) { const double v = (double)in.xdes[(size_t)b * NX + i]; xd[i] = v; bad |= !isfinite(v); }
     if (tid < 13) { const double v = (double)in.x0[(size_t)b * 13 + tid]; s.x0[tid] = v; bad |= !isfinite(v); }
     if (tid == 0) { const double v = (double)in.mu[b]; s.mu = v; bad |= !isfinite(v); }
+    if constexpr (MODEL) {
+      if (tid == 0) {   // 1 / m and the box of row b over the configuration's (an invalid row is all NaN; so is a table that is not there)
+        const double* const mrow = cfg.model ? cfg.model + (size_t)b * MODEL_ROW : nullptr;
+        const double nan = __builtin_nan("");
+        const double im = mrow ? mrow[0] : nan, lo = mrow ? mrow[4] : nan, hi = mrow ? mrow[5] : nan;
+        s.inv_m = im; s.fmin = lo; s.fmax = hi;
+        bad |= !isfinite(im) || !isfinite(lo) || !isfinite(hi);
+      }
+    }
     double rr[3] = {0, 0, 0};
     Lg.stance = false;
     if (Lg.leg) {
@@ -1106,7 +1116,9 @@ mpcqp_stage_solve(const DevCfg* __restrict__ cfgp, const FastIn<TIO> in, TIO* ug
     }
     __syncthreads();
     {   // src/mpc.py:71-78, 98-107; compute_skew column a = r x e_a (src/utils.py:43-56)
-      const double c = s.cy, sn = s.sy, Ib0 = cfg.Ib[0], Ib1 = cfg.Ib[1], Ib2 = cfg.Ib[2];
+      const double c = s.cy, sn = s.sy;
+      double Ib0 = cfg.Ib[0], Ib1 = cfg.Ib[1], Ib2 = cfg.Ib[2];
+      if constexpr (MODEL) { const double* const mrow = cfg.model + (size_t)b * MODEL_ROW; Ib0 = mrow[1]; Ib1 = mrow[2]; Ib2 = mrow[3]; }   // (not null: checked above)
       const bool st = Lg.stance;   // a swing leg's column is selected to zero, never multiplied by it (its lever arm is a don't-care input)
 #pragma unroll
       for (int a = 0; a < 3; ++a) {

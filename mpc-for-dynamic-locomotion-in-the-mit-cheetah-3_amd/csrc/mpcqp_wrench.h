@@ -462,7 +462,10 @@ __device__ __forceinline__ void w_grad(SmemW<TV, N>& s, const double* __restrict
 }
 
 // Per-QP setup: constants (once per workgroup), inputs, B_l, free response, gam, g, |g|_inf, cold ADMM state.
-template <typename TV, typename TIO, int N>
+// MODEL: the launch has a model table (mpcqp_model.h, DevCfg::model): the QP's own row replaces the configuration's 1 / m, inertia
+// diagonal and f_z box, for EVERY QP -- a resident workgroup's next QP is another robot.  A kernel argument of its own, so the
+// kernels of a handle without a table are the code they were.  An invalid row is all NaN; so is a table that is not there.
+template <typename TV, typename TIO, int N, bool MODEL>
 __device__ __forceinline__ int w_setup(SmemW<TV, N>& s, const DevCfg& cfg, const WrTabs& tabs, const FastIn<TIO>& in, size_t b, int tid,
                                        bool first) {
   constexpr int NT = WG<N>::NT, NL = WG<N>::NL, NQ = WG<N>::NQ, n = WG<N>::n, NW = WG<N>::NW, DP = WG<N>::DP;
@@ -475,6 +478,15 @@ __device__ __forceinline__ int w_setup(SmemW<TV, N>& s, const DevCfg& cfg, const
     { const double z = opaque_zero_f64(); for (int i = tid; i < DP; i += NT) { s.bv[i] = z; s.cv[i] = z; s.piv[i] = z; s.piv[DP + i] = z; } }   // pad slots stay finite
   }
   int bad = w_load<TV, TIO, N>(s, in, b, tid);
+  if constexpr (MODEL) {
+    if (tid == 0) {   // 1 / m and the box of row b over the configuration's
+      const double* const mrow = cfg.model ? cfg.model + b * MODEL_ROW : nullptr;
+      const double nan = __builtin_nan("");
+      const double im = mrow ? mrow[0] : nan, lo = mrow ? mrow[4] : nan, hi = mrow ? mrow[5] : nan;
+      s.inv_m = (TV)im; s.fmin = (TV)lo; s.fmax = (TV)hi;
+      bad |= !isfinite(im) || !isfinite(lo) || !isfinite(hi);
+    }
+  }
   if constexpr (NW == 1) {
     bad = __any(bad) ? 1 : 0;
   } else {
@@ -495,7 +507,8 @@ __device__ __forceinline__ int w_setup(SmemW<TV, N>& s, const DevCfg& cfg, const
     const bool st = s.ct[L] != 0;
     const TV rx = s.rr[3 * L], ry = s.rr[3 * L + 1], rz = s.rr[3 * L + 2];
     const TV c = s.cy, sn = s.sy;
-    const TV Ib0 = (TV)cfg.Ib[0], Ib1 = (TV)cfg.Ib[1], Ib2 = (TV)cfg.Ib[2];
+    TV Ib0 = (TV)cfg.Ib[0], Ib1 = (TV)cfg.Ib[1], Ib2 = (TV)cfg.Ib[2];
+    if constexpr (MODEL) { const double* const mrow = cfg.model + b * MODEL_ROW; Ib0 = (TV)mrow[1]; Ib1 = (TV)mrow[2]; Ib2 = (TV)mrow[3]; }   // (not null: checked above)
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
       TV cx, cyv, cz;
@@ -1344,7 +1357,7 @@ __device__ __forceinline__ void w_output(SmemW<TV, N>& s, const WrTabs& tabs, TI
 // of the dearest-expected-first order that the pre-pass (mpcqp_common.h) files; the hardware's dispatcher places the workgroups.
 // Queued form (ob.head != null): only as many workgroups as the device holds, each pulling QPs from the head of that order until
 // it is empty (no workgroup turnover: the form for batches many times the device).
-template <typename TV, typename TM, typename TP, typename TIO, int N, bool REFINE = false>
+template <typename TV, typename TM, typename TP, typename TIO, int N, bool REFINE = false, bool MODEL = false>
 __global__ void __launch_bounds__(WG<N>::NT, 2)
 mpcqp_wrench_solve(const DevCfg* __restrict__ cfgp, const WrTabs tabs, const FastIn<TIO> in, TIO* ug, TIO* __restrict__ Xg,
                    int* __restrict__ statusg, int* __restrict__ itersg, float* __restrict__ resg, const OrderBuf ob, const int Btot) {
@@ -1409,7 +1422,7 @@ mpcqp_wrench_solve(const DevCfg* __restrict__ cfgp, const WrTabs tabs, const Fas
       s.alpha_target = (TV)cfg.alpha_target;   // (both decided on the host: a double constant compared here lives in a hoisted, spilled register pair)
       s.alpha = (TV)cfg.alpha_start;
     }
-    if (w_setup<TV, TIO, N>(s, cfg, tabs, in, b, tid, first_qp)) {   // non-finite input -> zero outputs, status -1
+    if (w_setup<TV, TIO, N, MODEL>(s, cfg, tabs, in, b, tid, first_qp)) {   // non-finite input -> zero outputs, status -1
       for (int i = tid; i < n; i += NT) ug[b * n + i] = (TIO)0;
       if (Xg) for (int i = tid; i < (N + 1) * 13; i += NT) Xg[b * (size_t)(N + 1) * 13 + i] = (TIO)0;
       if (tid == 0) {

@@ -98,6 +98,25 @@ class MPCBatch:
                                     out["iters"].data_ptr(), out["res"].data_ptr(), st.cuda_stream)
         return out
 
+    def set_models(self, models, stream=None):
+        """Per-robot model rows (include/mpcqp_model.h, mpcqp_set_models): `models` [B,6] = (m, Ixx, Iyy, Izz, f_min, f_max) per batch
+        slot, a float64 tensor on the engine's device or a numpy array (uploaded).  Every later solve, gait solve and roll-out of
+        this engine builds QP b from row b and must have B robots; rows are fp64 whatever the I/O dtype (mpcqp.models has the row
+        helpers and the host checker).  Asynchronous on `stream`."""
+        torch = _torch()
+        if not hasattr(models, "data_ptr"):
+            models = torch.as_tensor(np.ascontiguousarray(models, dtype=np.float64)).to(self.device)
+        if models.dim() != 2 or models.shape[1] != 6 or models.shape[0] < 1 or models.dtype != torch.float64 or not models.is_contiguous() \
+                or models.device != self.device:
+            raise ValueError(f"models must be a contiguous [B,6] float64 tensor on {self.device}, got {tuple(models.shape)} {models.dtype} on {models.device}")
+        st = stream if stream is not None else torch.cuda.current_stream(self.device)
+        models.record_stream(st)   # (the conversion kernel reads it on `st`; the engine keeps its own table)
+        self.engine.set_models_ptr(int(models.shape[0]), models.data_ptr(), st.cuda_stream)
+
+    def clear_models(self):
+        """Back to the configuration's model for every QP (mpcqp_clear_models; waits for the device)."""
+        self.engine.clear_models()
+
     def upload_gait(self, g):
         """Host numpy gait descriptors (mpcqp.synth.make_gait_batch layout) -> resident device tensors."""
         torch = _torch()

@@ -313,3 +313,23 @@ def make_plant_rows(B, seed=20251016, m=8.885, ibody=(0.24, 1.0, 1.0), mass_scal
     length = rng.integers(push_len[0], push_len[1] + 1, B)
     push_ticks = np.stack([start, np.where(pushed, start + length, start)], axis=1).astype(np.int32)
     return {"body": body, "push": push, "push_ticks": push_ticks, "pushed": pushed}
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# Model rows (include/mpcqp_model.h, mpcqp_set_models): a few distinct controllers' models, assigned to the slots cyclically
+# ----------------------------------------------------------------------------------------------------------------------
+def make_model_rows(B, classes=4, seed=20251017, m=8.885, ibody=(0.24, 1.0, 1.0), mass_scale=(0.8, 1.5), inertia_scale=(0.7, 1.5),
+                    f_min=(1.0, 5.0), f_max=(40.0, 150.0)):
+    """Model rows [B,6] = (m, Ixx, Iyy, Izz, f_min, f_max) around the model (m, diag(ibody)): `classes` distinct rows -- mass, each
+    principal inertia and the f_z box drawn uniformly from the given ranges -- with slot b getting row b mod classes (few distinct
+    rows: the host checker needs one handle per row).  The LAST class carries less than its weight on two legs: its f_max is
+    0.45 m |g| whatever `f_max` says, so 2 f_max < m |g| and the upper bound of f_z is active in two-legged support, which the
+    default configuration's 100 N almost never is."""
+    rng = np.random.default_rng(seed)
+    rows = np.empty((classes, 6))
+    rows[:, 0] = m * rng.uniform(*mass_scale, classes)
+    rows[:, 1:4] = np.asarray(ibody, float)[None] * rng.uniform(*inertia_scale, (classes, 3))
+    rows[:, 4] = rng.uniform(*f_min, classes)
+    rows[:, 5] = rng.uniform(*f_max, classes)
+    rows[-1, 5] = 0.45 * rows[-1, 0] * abs(G_ACC)
+    return np.ascontiguousarray(rows[np.arange(B) % classes])
