@@ -1,4 +1,5 @@
-"""ctypes binding of the C-ABI declared in include/mpcqp.h and its product-only extensions include/mpcqp_plan.h, mpcqp_sim.h and mpcqp_model.h.
+"""ctypes binding of the C-ABI declared in include/mpcqp.h and its product-only extensions include/mpcqp_plan.h, mpcqp_sim.h, mpcqp_model.h
+and mpcqp_joints.h.
 
 The product path loads ``csrc/libmpcqp.so`` (hand-written HIP for gfx950) and nothing else: if that library is
 missing or cannot be loaded, importing the engine raises -- there is no CPU fallback.  The binding itself is
@@ -52,6 +53,8 @@ PLAN_SYMBOLS = ("mpcqp_plan_footsteps", "mpcqp_swing_trajectories")
 SIM_SYMBOLS = ("mpcqp_plant_step", "mpcqp_rollout_plant")
 # include/mpcqp_model.h: per-robot model rows, likewise product-only
 MODEL_SYMBOLS = ("mpcqp_set_models", "mpcqp_clear_models")
+# include/mpcqp_joints.h: closed-form leg inverse kinematics and the joint-space log, likewise product-only
+JOINTS_SYMBOLS = ("mpcqp_leg_ik", "mpcqp_joint_log")
 
 
 class MpcQpLegGeometry(ctypes.Structure):
@@ -139,6 +142,13 @@ class Library:
             L.mpcqp_set_models.restype = c_int32
             L.mpcqp_clear_models.argtypes = [c_void_p]
             L.mpcqp_clear_models.restype = c_int32
+        self.has_joints = all(hasattr(L, sym) for sym in JOINTS_SYMBOLS)
+        if self.has_joints:
+            L.mpcqp_leg_ik.argtypes = [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, ctypes.POINTER(MpcQpLegGeometry), c_void_p, c_void_p, c_void_p]
+            L.mpcqp_leg_ik.restype = c_int32
+            L.mpcqp_joint_log.argtypes = [c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_void_p, ctypes.POINTER(MpcQpLegGeometry),
+                                          c_void_p, c_void_p, c_void_p, c_void_p]
+            L.mpcqp_joint_log.restype = c_int32
 
     def version(self) -> int:
         return int(self.lib.mpcqp_version())
@@ -307,6 +317,27 @@ class Engine:
         rc = self._model_call("mpcqp_clear_models")(self._h)
         if rc != 0:
             raise MpcQpError(f"mpcqp_clear_models failed with code {rc}: {self.last_error()}")
+
+    def _joints_call(self, name):
+        if not self.library.has_joints:
+            raise MpcQpError(f"{name}: {self.library.path} does not export include/mpcqp_joints.h (product library only)")
+        return getattr(self.library.lib, name)
+
+    def leg_ik_ptr(self, B, foot, rot, origin, q, reach=0, geometry=None, stream=0):
+        """Raw call of the closed-form leg inverse kinematics (include/mpcqp_joints.h, mpcqp_leg_ik); integer addresses."""
+        rc = self._joints_call("mpcqp_leg_ik")(self._h, int(B), foot or None, rot or None, origin or None,
+                                               ctypes.byref(geometry) if geometry is not None else None, q or None, reach or None,
+                                               stream or None)
+        if rc != 0:
+            raise MpcQpError(f"mpcqp_leg_ik failed with code {rc}: {self.last_error()}")
+
+    def joint_log_ptr(self, B, T, actual, forces, feet, q, tau, reach, geometry=None, stream=0):
+        """Raw call of the joint-space log of a roll-out (include/mpcqp_joints.h, mpcqp_joint_log); integer addresses."""
+        rc = self._joints_call("mpcqp_joint_log")(self._h, int(B), int(T), actual or None, forces or None, feet or None,
+                                                  ctypes.byref(geometry) if geometry is not None else None, q or None, tau or None,
+                                                  reach or None, stream or None)
+        if rc != 0:
+            raise MpcQpError(f"mpcqp_joint_log failed with code {rc}: {self.last_error()}")
 
     def torque_map_ptr(self, B, u, jac, tau, stream=0):
         rc = self.library.lib.mpcqp_torque_map(self._h, int(B), u, jac, tau, stream or None)

@@ -52,21 +52,16 @@ __device__ __forceinline__ void cross3(const double (&a)[3], const double (&b)[3
   o[0] = a[1] * b[2] - a[2] * b[1]; o[1] = a[2] * b[0] - a[0] * b[2]; o[2] = a[0] * b[1] - a[1] * b[0];
 }
 
-template <typename TIO>
-__global__ void __launch_bounds__(256)
-mpcqp_leg_jacobian_kernel(const TIO* __restrict__ q, const TIO* __restrict__ rot, const LegGeoDev geo, TIO* __restrict__ jac,
-                          TIO* __restrict__ foot, const int64_t B) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;   // i = 4 b + leg
-  if (i >= 4 * B) return;
-  const int64_t b = i / 4;
-  const int l = (int)(i % 4);
+// The forward map of leg l in the torso frame: foot position pf relative to the torso origin and J = d pf / d q, row-major
+// (row = axis, column = joint).  Shared by mpcqp_leg_jacobian_kernel and the joint-space log (mpcqp_joints.h).
+__device__ __forceinline__ void leg_fk_jac(const LegGeoDev& geo, const int l, const double (&q)[3], double (&pf)[3], double (&J)[9]) {
   double R1[9], Ry[9], R2[9], R3[9];
-  rodrigues(geo.ax, (double)q[3 * i], R1);
-  rodrigues(geo.ay, (double)q[3 * i + 1], Ry);
+  rodrigues(geo.ax, q[0], R1);
+  rodrigues(geo.ay, q[1], Ry);
   mat3_mul(R1, Ry, R2);
-  rodrigues(geo.ay, (double)q[3 * i + 2], Ry);
+  rodrigues(geo.ay, q[2], Ry);
   mat3_mul(R2, Ry, R3);
-  double hx[3], hy[3], p2[3], p3[3], pf[3], t[3];
+  double hx[3], hy[3], p2[3], p3[3], t[3];
 #pragma unroll
   for (int a = 0; a < 3; ++a) { hx[a] = geo.hx[l][a]; hy[a] = geo.hy[l][a]; }   // (leg-indexed: a scalar-indexed copy per lane)
   mat3_vec(R1, hy, t);
@@ -78,7 +73,7 @@ mpcqp_leg_jacobian_kernel(const TIO* __restrict__ q, const TIO* __restrict__ rot
   mat3_vec(R3, geo.ft, t);
 #pragma unroll
   for (int a = 0; a < 3; ++a) pf[a] = p3[a] + t[a];
-  double J[9], w[3], dlt[3], col[3];   // column j = (joint axis in the torso frame) x (foot - joint origin)
+  double w[3], dlt[3], col[3];   // column j = (joint axis in the torso frame) x (foot - joint origin)
   mat3_vec(R1, geo.ax, w);
 #pragma unroll
   for (int a = 0; a < 3; ++a) dlt[a] = pf[a] - hx[a];
@@ -97,6 +92,19 @@ mpcqp_leg_jacobian_kernel(const TIO* __restrict__ q, const TIO* __restrict__ rot
   cross3(w, dlt, col);
 #pragma unroll
   for (int a = 0; a < 3; ++a) J[3 * a + 2] = col[a];
+}
+
+template <typename TIO>
+__global__ void __launch_bounds__(256)
+mpcqp_leg_jacobian_kernel(const TIO* __restrict__ q, const TIO* __restrict__ rot, const LegGeoDev geo, TIO* __restrict__ jac,
+                          TIO* __restrict__ foot, const int64_t B) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;   // i = 4 b + leg
+  if (i >= 4 * B) return;
+  const int64_t b = i / 4;
+  const int l = (int)(i % 4);
+  const double ql[3] = {(double)q[3 * i], (double)q[3 * i + 1], (double)q[3 * i + 2]};
+  double pf[3], J[9];
+  leg_fk_jac(geo, l, ql, pf, J);
   if (rot) {   // world <- torso
     double Rb[9], Jw[9], pw[3];
 #pragma unroll

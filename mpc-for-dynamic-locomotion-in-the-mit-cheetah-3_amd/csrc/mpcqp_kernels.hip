@@ -3,7 +3,7 @@
 // Replaces, for a batch of B independent robots, the solve the reference performs once per control tick:
 // CasADi Opti('conic') -> OSQP on the QP of src/mpc.py:58-173, filled at src/mpc.py:242-255, solved at :258.
 //
-// This translation unit is the C-ABI of include/mpcqp.h, mpcqp_plan.h, mpcqp_sim.h and mpcqp_model.h: the handle, its host helpers (I/O-type
+// This translation unit is the C-ABI of include/mpcqp.h, mpcqp_plan.h, mpcqp_sim.h, mpcqp_model.h and mpcqp_joints.h: the handle, its host helpers (I/O-type
 // dispatch, workspaces, the policy behind the configuration's defaults) and the extern "C" entry points.  The device code is in
 //   mpcqp_wrench.h       the engine: wrench-space (Woodbury) form, H = 2 alpha I + T'KT with a 6N x 6N system, one QP per wave
 //                        (horizon 10) or per four waves (horizon 20), fp32 or fp64 ADMM, fp64 active-set polish, ADMM-only mode
@@ -15,12 +15,14 @@
 //   mpcqp_plan.h         footstep plans, swing-foot trajectories and the plan clock
 //   mpcqp_plant.h        the rigid-body plant that can replace the roll-out's world step
 //   mpcqp_model.h        per-robot model rows: the conversion of the caller's table into the engine's
+//   mpcqp_joints.h       closed-form leg inverse kinematics and the joint-space log of a roll-out
 // DESIGN.md has the derivations.
 
 #include "mpcqp_wrench.h"
 #include "mpcqp_stage.h"
 #include "mpcqp_elementwise.h"
 #include "mpcqp_model.h"
+#include "mpcqp_joints.h"
 
 #include <cstdio>
 #include <cstdlib>
@@ -911,6 +913,85 @@ int mpcqp_leg_jacobians(mpcqp_handle h, int64_t B, const void* q, const void* ro
                        (T*)foot, B);
   });
   return launched(h, "leg Jacobian kernel launch");
+}
+
+extern "C++" {
+namespace {
+
+// The geometry of include/mpcqp_joints.h: the closed form needs a HipX joint about +-e_x followed by a planar chain about +-e_y.
+// Fills g (unit axes) or names the field that does not fit.
+int leg_ik_geometry(mpcqp_handle h, const char* who, const MpcQpLegGeometry* geo, LegGeoDev& g) {
+  MpcQpLegGeometry lite3;
+  if (!geo) { (void)mpcqp_default_leg_geometry(&lite3); geo = &lite3; }
+  char msg[160];
+  const char* bad = nullptr;
+  if (geo->size != sizeof(MpcQpLegGeometry)) {
+    snprintf(msg, sizeof(msg), "%s: geometry struct size mismatch", who);
+    return fail(h, MPCQP_EINVAL, msg);
+  }
+  const auto fin3 = [](const double* a) { return std::isfinite(a[0]) && std::isfinite(a[1]) && std::isfinite(a[2]); };
+  if (!fin3(geo->axis_x) || geo->axis_x[0] == 0.0 || geo->axis_x[1] != 0.0 || geo->axis_x[2] != 0.0) bad = "axis_x is not +-e_x";
+  else if (!fin3(geo->axis_y) || geo->axis_y[1] == 0.0 || geo->axis_y[0] != 0.0 || geo->axis_y[2] != 0.0) bad = "axis_y is not +-e_y";
+  else if (!fin3(geo->knee) || geo->knee[0] != 0.0 || geo->knee[1] != 0.0 || !(geo->knee[2] < 0.0)) bad = "knee is not (0, 0, -l1), l1 > 0";
+  else if (!fin3(geo->foot) || geo->foot[0] != 0.0 || geo->foot[1] != 0.0 || !(geo->foot[2] < 0.0)) bad = "foot is not (0, 0, -l2), l2 > 0";
+  for (int l = 0; l < 4 && !bad; ++l) {
+    if (!fin3(geo->hip_y[l]) || geo->hip_y[l][0] != 0.0 || geo->hip_y[l][2] != 0.0) bad = "hip_y is not (0, d, 0)";
+    else if (!fin3(geo->hip_x[l])) bad = "hip_x is not finite";
+  }
+  if (bad) {
+    snprintf(msg, sizeof(msg), "%s: the closed form needs the Lite3's leg structure: %s", who, bad);
+    return fail(h, MPCQP_EINVAL, msg);
+  }
+  memcpy(g.hx, geo->hip_x, sizeof(g.hx)); memcpy(g.hy, geo->hip_y, sizeof(g.hy));
+  memcpy(g.kn, geo->knee, sizeof(g.kn)); memcpy(g.ft, geo->foot, sizeof(g.ft));
+  for (int c = 0; c < 3; ++c) { g.ax[c] = 0.0; g.ay[c] = 0.0; }
+  g.ax[0] = geo->axis_x[0] > 0.0 ? 1.0 : -1.0;
+  g.ay[1] = geo->axis_y[1] > 0.0 ? 1.0 : -1.0;
+  return MPCQP_OK;
+}
+
+}  // namespace
+}  // extern "C++"
+
+int mpcqp_leg_ik(mpcqp_handle h, int64_t B, const void* foot, const void* rot, const void* origin, const MpcQpLegGeometry* geo, void* q,
+                 uint8_t* reach, void* stream) {
+  if (!h) return MPCQP_EINVAL;
+  if (B < 0 || B > 0x1fffffff) return fail(h, MPCQP_EINVAL, "mpcqp_leg_ik: batch size out of range");
+  if (B > 0 && !foot) return fail(h, MPCQP_EINVAL, "mpcqp_leg_ik: null foot buffer");
+  if (B > 0 && !q) return fail(h, MPCQP_EINVAL, "mpcqp_leg_ik: null q buffer");
+  LegGeoDev g;
+  if (const int rc = leg_ik_geometry(h, "mpcqp_leg_ik", geo, g)) return rc;
+  if (B == 0) return MPCQP_OK;
+  DeviceGuard guard(h->cfg.device);
+  if (guard.err != hipSuccess) return fail(h, MPCQP_EHIP, "hipSetDevice", guard.err);
+  const dim3 grid((unsigned)((4 * B + 255) / 256));
+  with_io(h, [&](auto tag) {
+    using T = decltype(tag);
+    hipLaunchKernelGGL((mpcqp_leg_ik_kernel<T>), grid, dim3(256), 0, (hipStream_t)stream, (const T*)foot, (const T*)rot, (const T*)origin, g,
+                       (T*)q, reach, B);
+  });
+  return launched(h, "leg inverse kinematics kernel launch");
+}
+
+int mpcqp_joint_log(mpcqp_handle h, int64_t B, int32_t T, const void* actual, const void* forces, const void* feet,
+                    const MpcQpLegGeometry* geo, void* q, void* tau, uint8_t* reach, void* stream) {
+  if (!h) return MPCQP_EINVAL;
+  if (B < 0 || B > 0x7fffffff || T < 0 || B * (int64_t)T > 0x1fffffff) return fail(h, MPCQP_EINVAL, "mpcqp_joint_log: size out of range");
+  if (!q && !tau && !reach) return fail(h, MPCQP_EINVAL, "mpcqp_joint_log: no output buffer (q, tau and reach are all null)");
+  if (B > 0 && T > 0 && (!actual || !forces || !feet)) return fail(h, MPCQP_EINVAL, "mpcqp_joint_log: null buffer");
+  LegGeoDev g;
+  if (const int rc = leg_ik_geometry(h, "mpcqp_joint_log", geo, g)) return rc;
+  if (B == 0 || T == 0) return MPCQP_OK;
+  DeviceGuard guard(h->cfg.device);
+  if (guard.err != hipSuccess) return fail(h, MPCQP_EHIP, "hipSetDevice", guard.err);
+  const int64_t rows = B * T;
+  const dim3 grid((unsigned)((4 * rows + 255) / 256));
+  with_io(h, [&](auto tag) {
+    using TIO = decltype(tag);
+    hipLaunchKernelGGL((mpcqp_joint_log_kernel<TIO>), grid, dim3(256), 0, (hipStream_t)stream, (const TIO*)actual, (const TIO*)forces,
+                       (const TIO*)feet, g, (TIO*)q, (TIO*)tau, reach, rows);
+  });
+  return launched(h, "joint log kernel launch");
 }
 
 int mpcqp_last_kernel_ms(mpcqp_handle h, float* ms) {

@@ -295,5 +295,44 @@ class MPCBatch:
                                       foot.data_ptr() if foot is not None else 0, geometry, st.cuda_stream)
         return jac, foot
 
+    def _check_rows(self, rows):
+        for name, t, shape in rows:
+            if t is not None and (tuple(t.shape) != shape or t.dtype != self.tdtype or not t.is_contiguous() or t.device != self.device):
+                raise ValueError(f"{name} must be a contiguous {shape} {self.tdtype} tensor on {self.device}, got {tuple(t.shape)} {t.dtype} on {t.device}")
+
+    def leg_ik(self, foot, rot=None, origin=None, geometry=None, want_reach=True, stream=None):
+        """Closed-form inverse kinematics of the four legs on the device (include/mpcqp_joints.h, mpcqp_leg_ik; the host counterpart is
+        lite3_model.leg_ik_closed): foot [B,4,3] foot positions in world orientation, rot [B,3,3] torso orientation (world <- torso) or
+        None, origin [B,3] torso origin or None -> (q [B,4,3] HipX, HipY, Knee, reach uint8 [B,4] or None).  With rot and origin None
+        this inverts the `foot` output of `leg_jacobians`.  Out of reach: q of the nearest boundary and reach = 0; a non-finite leg:
+        NaN and 0.  Asynchronous on `stream`."""
+        torch = _torch()
+        B = int(foot.shape[0])
+        self._check_rows([("foot", foot, (B, 4, 3)), ("rot", rot, (B, 3, 3)), ("origin", origin, (B, 3))])
+        st = stream if stream is not None else torch.cuda.current_stream(self.device)
+        with torch.cuda.stream(st):
+            q = torch.empty((B, 4, 3), dtype=self.tdtype, device=self.device)
+            reach = torch.empty((B, 4), dtype=torch.uint8, device=self.device) if want_reach else None
+        p = lambda t: t.data_ptr() if t is not None else 0
+        self.engine.leg_ik_ptr(B, foot.data_ptr(), p(rot), p(origin), q.data_ptr(), p(reach), geometry, st.cuda_stream)
+        return q, reach
+
+    def joint_log(self, actual, forces, feet, geometry=None, stream=None):
+        """Joint-space log of a roll-out on the device (include/mpcqp_joints.h, mpcqp_joint_log; the host counterpart is
+        lite3_model.joint_log_host): actual, forces [B,T,12] as `rollout` / `rollout_plant` return them, feet [B,T,4,3] world foot
+        positions -- `swing_trajectories(plan, first_tick, K=T, ...)["feet_des"]` -> {"q": [B,T,4,3] joint angles, "tau": [B,T,4,3]
+        joint torques (R J)^T (-f), "reach": uint8 [B,T,4]}.  Asynchronous on `stream`."""
+        torch = _torch()
+        B, T = int(actual.shape[0]), int(actual.shape[1]) if actual.dim() == 3 else -1
+        self._check_rows([("actual", actual, (B, T, 12)), ("forces", forces, (B, T, 12)), ("feet", feet, (B, T, 4, 3))])
+        st = stream if stream is not None else torch.cuda.current_stream(self.device)
+        with torch.cuda.stream(st):
+            q = torch.empty((B, T, 4, 3), dtype=self.tdtype, device=self.device)
+            tau = torch.empty((B, T, 4, 3), dtype=self.tdtype, device=self.device)
+            reach = torch.empty((B, T, 4), dtype=torch.uint8, device=self.device)
+        self.engine.joint_log_ptr(B, T, actual.data_ptr(), forces.data_ptr(), feet.data_ptr(), q.data_ptr(), tau.data_ptr(), reach.data_ptr(),
+                                  geometry, st.cuda_stream)
+        return {"q": q, "tau": tau, "reach": reach}
+
     def last_kernel_ms(self):
         return self.engine.last_kernel_ms()

@@ -44,6 +44,69 @@ def leg_ik(leg: int, p_body, q0=(0.0, -1.0, 1.6), iters=30):
     return q
 
 
+def leg_ik_closed(p_body, leg=None):
+    """Closed-form inverse of `leg_fk_jac` (the host counterpart of mpcqp_leg_ik, include/mpcqp_joints.h): foot positions in the
+    torso frame, [...,4,3] for the four legs or [...,3] with a leg index, -> (q [...,3] HipX, HipY, Knee, reach uint8 [...]).
+
+    The leg is a HipX joint followed by a planar 2R chain: with p = p_body - hip_x and d the lateral HipY offset, the foot in the
+    HipX link frame is (p_x, d, z_s), z_s = -sqrt(p_y^2 + p_z^2 - d^2); HipX turns (d, z_s) onto (p_y, p_z), HipY and Knee follow from
+    the cosine law in (p_x, z_s).  Branch: foot below the HipX axis (z_s <= 0), knee angle in [0, pi].  Out of reach (reach = 0) the
+    square-root argument is clamped at 0 and the cosine at +-1: q is the joint vector of the nearest boundary.  A non-finite row
+    gives NaN and reach = 0.  No iteration, no seed."""
+    p = np.asarray(p_body, dtype=float)
+    if leg is None:
+        if p.shape[-2:] != (4, 3):
+            raise ValueError(f"p_body must be [...,4,3] (or [...,3] with a leg index), got {p.shape}")
+        hx, d = _HIPX, _HIPY[:, 1]
+    else:
+        if p.shape[-1] != 3:
+            raise ValueError(f"p_body must be [...,3], got {p.shape}")
+        hx, d = _HIPX[leg], _HIPY[leg, 1]
+    sx, sy, l1, l2 = _AX_X[0], _AX_Y[1], -_KNEE[2], -_FOOT[2]
+    with np.errstate(invalid="ignore", over="ignore"):
+        px, py, pz = p[..., 0] - hx[..., 0], p[..., 1] - hx[..., 1], p[..., 2] - hx[..., 2]
+        finite = np.isfinite(px) & np.isfinite(py) & np.isfinite(pz)
+        w = py * py + pz * pz - d * d
+        ok = w >= 0.0
+        zs = -np.sqrt(np.where(ok, w, 0.0))
+        a0 = np.arctan2(d * pz - zs * py, d * py + zs * pz)
+        r2 = px * px + zs * zs
+        r = np.sqrt(r2)
+        ok &= (r >= abs(l1 - l2)) & (r <= l1 + l2)
+        c = (r2 - l1 * l1 - l2 * l2) / (2.0 * l1 * l2)
+        c = np.where(c > 1.0, 1.0, np.where(c < -1.0, -1.0, c))
+        k = np.arccos(c)
+        s = np.sqrt((1.0 - c) * (1.0 + c))
+        u, v = l1 + l2 * c, sy * (l2 * s)                  # the foot seen from the HipY joint, along and across the thigh
+        a1 = np.arctan2(zs * v - px * u, -(zs * u + px * v))
+        q = np.stack([sx * a0, sy * a1, k], axis=-1)       # (a0, a1: angles about +e_x, +e_y; the knee's is sy * k)
+        q = np.where(finite[..., None], q, np.nan)
+    return q, (ok & finite).astype(np.uint8)
+
+
+def joint_log_host(actual, forces, feet):
+    """Joint-space log of a roll-out (the host counterpart of mpcqp_joint_log, include/mpcqp_joints.h): actual, forces [B,T,12] as
+    the roll-out logs them (actual = rotation vector, CoM, omega, v), feet [B,T,4,3] world foot positions -> (q [B,T,4,3],
+    tau [B,T,4,3], reach uint8 [B,T,4]).  Per leg: p = R^T (foot - CoM) with R from the rotation vector, q by `leg_ik_closed`,
+    tau = (R J(q))^T (-f) (src/main.py:212-214); the torque is computed from the clamped q where reach = 0."""
+    from scipy.spatial.transform import Rotation
+    actual, forces, feet = (np.asarray(a, dtype=float) for a in (actual, forces, feet))
+    B, T = actual.shape[:2]
+    R = Rotation.from_rotvec(actual[..., :3].reshape(-1, 3)).as_matrix().reshape(B, T, 3, 3)
+    p = np.einsum("btji,btlj->btli", R, feet - actual[:, :, None, 3:6])
+    q, reach = leg_ik_closed(p)
+    f = forces.reshape(B, T, 4, 3)
+    tau = np.empty((B, T, 4, 3))
+    for b in range(B):
+        for t in range(T):
+            for l in range(4):
+                if np.isfinite(q[b, t, l]).all():
+                    tau[b, t, l] = (R[b, t] @ leg_fk_jac(l, q[b, t, l])[1]).T @ -f[b, t, l]
+                else:
+                    tau[b, t, l] = np.nan
+    return q, tau, reach
+
+
 def world_jacobians(R_body, q_all):
     """{leg: 3x3 world-frame linear Jacobian block} for joint angles q_all[4,3] (src/main.py:205-210)."""
     return {LEGS[k]: R_body @ leg_fk_jac(k, q_all[k])[1] for k in range(4)}
