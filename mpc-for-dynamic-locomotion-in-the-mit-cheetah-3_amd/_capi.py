@@ -10,7 +10,7 @@ from __future__ import annotations
 
 import ctypes
 import os
-from ctypes import c_char_p, c_double, c_float, c_int32, c_int64, c_uint32, c_void_p
+from ctypes import c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_uint32, c_void_p
 
 import numpy as np
 
@@ -41,21 +41,6 @@ def split_iters(iters):
     admm = np.where(wide, v % ITERS_WIDE, v % 1000)
     polish = np.where(wide, v // ITERS_WIDE - 1, v // 1000)
     return admm, polish
-
-EXPORTED_SYMBOLS = (
-    "mpcqp_version", "mpcqp_default_config", "mpcqp_create", "mpcqp_destroy", "mpcqp_solve_batch",
-    "mpcqp_solve_batch_gait", "mpcqp_solve_batch_gait_steps", "mpcqp_torque_map", "mpcqp_default_leg_geometry", "mpcqp_leg_jacobians", "mpcqp_last_kernel_ms", "mpcqp_last_error", "mpcqp_reserve", "mpcqp_rollout",
-)
-
-# include/mpcqp_plan.h: exported by the product library only (the CPU checker under oracle/ does not have them)
-PLAN_SYMBOLS = ("mpcqp_plan_footsteps", "mpcqp_swing_trajectories")
-# include/mpcqp_sim.h: the rigid-body plant, likewise product-only
-SIM_SYMBOLS = ("mpcqp_plant_step", "mpcqp_rollout_plant")
-# include/mpcqp_model.h: per-robot model rows, likewise product-only
-MODEL_SYMBOLS = ("mpcqp_set_models", "mpcqp_clear_models")
-# include/mpcqp_joints.h: closed-form leg inverse kinematics and the joint-space log, likewise product-only
-JOINTS_SYMBOLS = ("mpcqp_leg_ik", "mpcqp_joint_log")
-
 
 class MpcQpLegGeometry(ctypes.Structure):
     """Mirror of struct MpcQpLegGeometry (include/mpcqp.h)."""
@@ -88,67 +73,69 @@ class MpcQpError(RuntimeError):
     pass
 
 
+# The C-ABI, one row per function: (name, return type, parameter types), by the header that declares it.  include/mpcqp.h is required;
+# the other four are exported by the product library only (the CPU checker under oracle/ does not have them).  tests/test_capi.py
+# compares every row with the prototype in the header.
+_P, _I32, _I64 = c_void_p, c_int32, c_int64   # any address (handle, buffer, stream), int32_t, int64_t
+_CFG, _GEO = ctypes.POINTER(MpcQpConfig), ctypes.POINTER(MpcQpLegGeometry)
+CORE_HEADER = "mpcqp.h"
+ABI = {
+    "mpcqp.h": (
+        ("mpcqp_version", c_uint32, ()),
+        ("mpcqp_default_config", c_int, (_CFG,)),
+        ("mpcqp_create", c_int, (_CFG, ctypes.POINTER(c_void_p))),
+        ("mpcqp_destroy", c_int, (_P,)),
+        ("mpcqp_reserve", c_int, (_P, _I64)),
+        ("mpcqp_solve_batch", c_int, (_P, _I64) + (_P,) * 11),
+        ("mpcqp_solve_batch_gait", c_int, (_P, _I64) + (_P,) * 13),
+        ("mpcqp_solve_batch_gait_steps", c_int, (_P, _I64, _I32) + (_P,) * 13),
+        ("mpcqp_rollout", c_int, (_P, _I64, _I32, _I32) + (_P,) * 12),
+        ("mpcqp_torque_map", c_int, (_P, _I64, _P, _P, _P, _P)),
+        ("mpcqp_default_leg_geometry", c_int, (_GEO,)),
+        ("mpcqp_leg_jacobians", c_int, (_P, _I64, _P, _P, _GEO, _P, _P, _P)),
+        ("mpcqp_last_kernel_ms", c_int, (_P, ctypes.POINTER(c_float))),
+        ("mpcqp_last_error", c_char_p, (_P,)),
+    ),
+    "mpcqp_plan.h": (   # footstep plans and swing-foot trajectories
+        ("mpcqp_plan_footsteps", c_int, (_P, _I64, _I32) + (_P,) * 9),
+        ("mpcqp_swing_trajectories", c_int, (_P, _I64, _I32, _I32) + (_P,) * 9),
+    ),
+    "mpcqp_sim.h": (    # the rigid-body plant
+        ("mpcqp_plant_step", c_int, (_P, _I64) + (_P,) * 6 + (_I32, _P, _P)),
+        ("mpcqp_rollout_plant", c_int, (_P, _I64, _I32, _I32) + (_P,) * 10 + (_I32,) + (_P,) * 5),
+    ),
+    "mpcqp_model.h": (  # per-robot model rows
+        ("mpcqp_set_models", c_int, (_P, _I64, _P, _P)),
+        ("mpcqp_clear_models", c_int, (_P,)),
+    ),
+    "mpcqp_joints.h": (  # closed-form leg inverse kinematics and the joint-space log
+        ("mpcqp_leg_ik", c_int, (_P, _I64, _P, _P, _P, _GEO, _P, _P, _P)),
+        ("mpcqp_joint_log", c_int, (_P, _I64, _I32, _P, _P, _P, _GEO, _P, _P, _P, _P)),
+    ),
+}
+EXPORTED_SYMBOLS, PLAN_SYMBOLS, SIM_SYMBOLS, MODEL_SYMBOLS, JOINTS_SYMBOLS = (tuple(row[0] for row in rows) for rows in ABI.values())
+
+
 class Library:
-    """A loaded shared object exporting the mpcqp C-ABI."""
+    """A loaded shared object exporting the mpcqp C-ABI.  `has_plan`, `has_sim`, `has_model` and `has_joints` say whether it exports
+    include/mpcqp_plan.h, mpcqp_sim.h, mpcqp_model.h and mpcqp_joints.h."""
 
     def __init__(self, path: str):
         if not os.path.exists(path):
             raise MpcQpError(f"mpcqp library not found: {path} (run `python -c 'import __graft_entry__ as g; g.build()'`)")
         self.path = path
         self.lib = ctypes.CDLL(path)
-        L = self.lib
-        L.mpcqp_version.restype = c_uint32
-        L.mpcqp_default_config.argtypes = [ctypes.POINTER(MpcQpConfig)]
-        L.mpcqp_default_config.restype = c_int32
-        L.mpcqp_create.argtypes = [ctypes.POINTER(MpcQpConfig), ctypes.POINTER(c_void_p)]
-        L.mpcqp_create.restype = c_int32
-        L.mpcqp_destroy.argtypes = [c_void_p]
-        L.mpcqp_reserve.argtypes = [c_void_p, c_int64]
-        L.mpcqp_rollout.argtypes = [c_void_p, c_int64, c_int32, c_int32] + [c_void_p] * 12
-        L.mpcqp_rollout.restype = ctypes.c_int
-        L.mpcqp_reserve.restype = ctypes.c_int
-        L.mpcqp_destroy.restype = c_int32
-        L.mpcqp_solve_batch.argtypes = [c_void_p, c_int64] + [c_void_p] * 11
-        L.mpcqp_solve_batch.restype = c_int32
-        L.mpcqp_solve_batch_gait.argtypes = [c_void_p, c_int64] + [c_void_p] * 13
-        L.mpcqp_solve_batch_gait.restype = c_int32
-        L.mpcqp_solve_batch_gait_steps.argtypes = [c_void_p, c_int64, c_int32] + [c_void_p] * 13
-        L.mpcqp_solve_batch_gait_steps.restype = c_int32
-        L.mpcqp_torque_map.argtypes = [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]
-        L.mpcqp_torque_map.restype = c_int32
-        L.mpcqp_default_leg_geometry.argtypes = [ctypes.POINTER(MpcQpLegGeometry)]
-        L.mpcqp_default_leg_geometry.restype = c_int32
-        L.mpcqp_leg_jacobians.argtypes = [c_void_p, c_int64, c_void_p, c_void_p, ctypes.POINTER(MpcQpLegGeometry), c_void_p, c_void_p, c_void_p]
-        L.mpcqp_leg_jacobians.restype = c_int32
-        L.mpcqp_last_kernel_ms.argtypes = [c_void_p, ctypes.POINTER(c_float)]
-        L.mpcqp_last_kernel_ms.restype = c_int32
-        L.mpcqp_last_error.argtypes = [c_void_p]
-        L.mpcqp_last_error.restype = c_char_p
-        self.has_plan = all(hasattr(L, sym) for sym in PLAN_SYMBOLS)
-        if self.has_plan:
-            L.mpcqp_plan_footsteps.argtypes = [c_void_p, c_int64, c_int32] + [c_void_p] * 9
-            L.mpcqp_plan_footsteps.restype = c_int32
-            L.mpcqp_swing_trajectories.argtypes = [c_void_p, c_int64, c_int32, c_int32] + [c_void_p] * 9
-            L.mpcqp_swing_trajectories.restype = c_int32
-        self.has_sim = all(hasattr(L, sym) for sym in SIM_SYMBOLS)
-        if self.has_sim:
-            L.mpcqp_plant_step.argtypes = [c_void_p, c_int64] + [c_void_p] * 6 + [c_int32, c_void_p, c_void_p]
-            L.mpcqp_plant_step.restype = c_int32
-            L.mpcqp_rollout_plant.argtypes = [c_void_p, c_int64, c_int32, c_int32] + [c_void_p] * 10 + [c_int32] + [c_void_p] * 5
-            L.mpcqp_rollout_plant.restype = c_int32
-        self.has_model = all(hasattr(L, sym) for sym in MODEL_SYMBOLS)
-        if self.has_model:
-            L.mpcqp_set_models.argtypes = [c_void_p, c_int64, c_void_p, c_void_p]
-            L.mpcqp_set_models.restype = c_int32
-            L.mpcqp_clear_models.argtypes = [c_void_p]
-            L.mpcqp_clear_models.restype = c_int32
-        self.has_joints = all(hasattr(L, sym) for sym in JOINTS_SYMBOLS)
-        if self.has_joints:
-            L.mpcqp_leg_ik.argtypes = [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, ctypes.POINTER(MpcQpLegGeometry), c_void_p, c_void_p, c_void_p]
-            L.mpcqp_leg_ik.restype = c_int32
-            L.mpcqp_joint_log.argtypes = [c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_void_p, ctypes.POINTER(MpcQpLegGeometry),
-                                          c_void_p, c_void_p, c_void_p, c_void_p]
-            L.mpcqp_joint_log.restype = c_int32
+        self.calls = {}   # name -> (function or None, its header, which parameters after the handle are addresses): Engine._call
+        for header, rows in ABI.items():
+            have = header == CORE_HEADER or all(hasattr(self.lib, row[0]) for row in rows)
+            if header != CORE_HEADER:
+                setattr(self, "has_" + header[len("mpcqp_"):-len(".h")], have)
+            for name, restype, argtypes in rows:
+                fn = None
+                if have:   # (a symbol of the core header that is missing raises here)
+                    fn = getattr(self.lib, name)
+                    fn.restype, fn.argtypes = restype, argtypes
+                self.calls[name] = (fn, header, tuple(t not in (_I32, _I64) for t in argtypes[1:]))
 
     def version(self) -> int:
         return int(self.lib.mpcqp_version())
@@ -212,40 +199,84 @@ class Engine:
     def last_error(self) -> str:
         return (self.library.lib.mpcqp_last_error(self._h) or b"").decode()
 
+    def _call(self, name, *args):
+        """The one call path into the library: `args` are the C parameters after the handle, in the C order.  An address of 0 or
+        None is passed as NULL; a nonzero return code raises with the library's own message."""
+        fn, header, is_address = self.library.calls[name]
+        if fn is None:
+            raise MpcQpError(f"{name}: {self.library.path} does not export include/{header} (product library only)")
+        if len(args) != len(is_address):
+            raise TypeError(f"{name} takes {len(is_address)} arguments after the handle, got {len(args)}")
+        rc = fn(self._h, *[(a or None) if p else int(a) for a, p in zip(args, is_address)])
+        if rc != 0:
+            raise MpcQpError(f"{name} failed with code {rc}: {self.last_error()}")
+
     def reserve(self, B):
         """Pre-size the batch-dependent workspace so that no later solve of at most B QPs allocates or synchronises."""
-        rc = self.library.lib.mpcqp_reserve(self._h, int(B))
-        if rc != 0:
-            raise MpcQpError(f"mpcqp_reserve failed with code {rc}: {self.last_error()}")
+        self._call("mpcqp_reserve", B)
 
+    # Raw calls: every buffer and `stream` is an integer address (device memory for the product library, host memory for the checker).
     def solve_batch_ptr(self, B, x0, r, contact, xdes, mu, u_out, X_out, status, iters, res, stream=0):
-        """Raw call: every argument is an integer address (device memory for the product library)."""
-        rc = self.library.lib.mpcqp_solve_batch(self._h, int(B), x0, r, contact, xdes, mu, u_out, X_out or None,
-                                                status, iters, res or None, stream or None)
-        if rc != 0:
-            raise MpcQpError(f"mpcqp_solve_batch failed with code {rc}: {self.last_error()}")
+        self._call("mpcqp_solve_batch", B, x0, r, contact, xdes, mu, u_out, X_out, status, iters, res, stream)
 
     def solve_batch_gait_ptr(self, B, x0, ref, feet0, footholds, gait, feet_id, mu, u_out, X_out, status, iters, res, stream=0):
-        """Raw call of the gait entry point (addresses; device memory for the product library)."""
-        rc = self.library.lib.mpcqp_solve_batch_gait(self._h, int(B), x0, ref, feet0, footholds, gait, feet_id, mu, u_out,
-                                                     X_out or None, status, iters, res or None, stream or None)
-        if rc != 0:
-            raise MpcQpError(f"mpcqp_solve_batch_gait failed with code {rc}: {self.last_error()}")
+        self._call("mpcqp_solve_batch_gait", B, x0, ref, feet0, footholds, gait, feet_id, mu, u_out, X_out, status, iters, res, stream)
 
     def solve_batch_gait_steps_ptr(self, B, S, x0, ref, feet0, footholds, gait, feet_id, mu, u_out, X_out, status, iters, res, stream=0):
-        """Raw call of the gait entry point with S plan steps per robot (footholds [B,S,4,3], feet_id [B,S,4])."""
-        rc = self.library.lib.mpcqp_solve_batch_gait_steps(self._h, int(B), int(S), x0, ref, feet0, footholds, gait, feet_id, mu, u_out,
-                                                           X_out or None, status, iters, res or None, stream or None)
-        if rc != 0:
-            raise MpcQpError(f"mpcqp_solve_batch_gait_steps failed with code {rc}: {self.last_error()}")
+        """The gait entry point with S plan steps per robot (footholds [B,S,4,3], feet_id [B,S,4])."""
+        self._call("mpcqp_solve_batch_gait_steps", B, S, x0, ref, feet0, footholds, gait, feet_id, mu, u_out, X_out, status, iters, res, stream)
 
     def rollout_ptr(self, B, T, S, x, ref, plan_pos, plan_feet_id, plan_meta, tick, mu, actual, desired, forces, solved, stream=0):
-        """Raw call of the closed-loop roll-out (include/mpcqp.h, mpcqp_rollout); every argument is an integer address."""
-        rc = self.library.lib.mpcqp_rollout(self._h, int(B), int(T), int(S), x, ref, plan_pos, plan_feet_id, plan_meta, tick, mu,
-                                            actual or None, desired or None, forces or None, solved or None, stream or None)
-        if rc != 0:
-            raise MpcQpError(f"mpcqp_rollout failed with code {rc}: {self.last_error()}")
+        """The closed-loop roll-out (include/mpcqp.h, mpcqp_rollout)."""
+        self._call("mpcqp_rollout", B, T, S, x, ref, plan_pos, plan_feet_id, plan_meta, tick, mu, actual, desired, forces, solved, stream)
 
+    def plan_footsteps_ptr(self, B, S, feet0, cmd, gait, plan_pos, plan_feet_id, plan_meta, plan_ang=0, plan_hip=0, stream=0):
+        """The device footstep planner (include/mpcqp_plan.h)."""
+        self._call("mpcqp_plan_footsteps", B, S, feet0, cmd, gait, plan_pos, plan_feet_id, plan_meta, plan_ang, plan_hip, stream)
+
+    def swing_trajectories_ptr(self, B, K, S, plan_pos, plan_feet_id, plan_meta, plan_ang, tick, step_height, traj, feet_des=0, stream=0):
+        """The device swing-foot trajectory generator (include/mpcqp_plan.h)."""
+        self._call("mpcqp_swing_trajectories", B, K, S, plan_pos, plan_feet_id, plan_meta, plan_ang, tick, step_height, traj, feet_des, stream)
+
+    def plant_step_ptr(self, B, x, f, feet, contact, body, wrench, substeps, x_out, stream=0):
+        """The rigid-body plant (include/mpcqp_sim.h, mpcqp_plant_step)."""
+        self._call("mpcqp_plant_step", B, x, f, feet, contact, body, wrench, substeps, x_out, stream)
+
+    def rollout_plant_ptr(self, B, T, S, x, ref, plan_pos, plan_feet_id, plan_meta, tick, mu, body, push, push_ticks, substeps,
+                          actual, desired, forces, solved, stream=0):
+        """The roll-out on the rigid-body plant (include/mpcqp_sim.h, mpcqp_rollout_plant)."""
+        self._call("mpcqp_rollout_plant", B, T, S, x, ref, plan_pos, plan_feet_id, plan_meta, tick, mu, body, push, push_ticks, substeps,
+                   actual, desired, forces, solved, stream)
+
+    def set_models_ptr(self, B, model, stream=0):
+        """mpcqp_set_models (include/mpcqp_model.h): `model` is the address of an fp64 [B,6] device table."""
+        self._call("mpcqp_set_models", B, model, stream)
+
+    def clear_models(self):
+        """mpcqp_clear_models (include/mpcqp_model.h): back to the configuration's m, Ibody_inv, f_min, f_max."""
+        self._call("mpcqp_clear_models")
+
+    # (`geometry` is an MpcQpLegGeometry or None = the Lite3; ctypes passes the structure by reference)
+    def leg_ik_ptr(self, B, foot, rot, origin, q, reach=0, geometry=None, stream=0):
+        """The closed-form leg inverse kinematics (include/mpcqp_joints.h, mpcqp_leg_ik)."""
+        self._call("mpcqp_leg_ik", B, foot, rot, origin, geometry, q, reach, stream)
+
+    def joint_log_ptr(self, B, T, actual, forces, feet, q, tau, reach, geometry=None, stream=0):
+        """The joint-space log of a roll-out (include/mpcqp_joints.h, mpcqp_joint_log)."""
+        self._call("mpcqp_joint_log", B, T, actual, forces, feet, geometry, q, tau, reach, stream)
+
+    def torque_map_ptr(self, B, u, jac, tau, stream=0):
+        self._call("mpcqp_torque_map", B, u, jac, tau, stream)
+
+    def leg_jacobians_ptr(self, B, q, rot, jac, foot=0, geometry=None, stream=0):
+        self._call("mpcqp_leg_jacobians", B, q, rot, geometry, jac, foot, stream)
+
+    def last_kernel_ms(self) -> float:
+        ms = c_float()
+        self._call("mpcqp_last_kernel_ms", ctypes.byref(ms))
+        return float(ms.value)
+
+    # host-pointer convenience (numpy); valid for libraries that take host memory
     def rollout_host(self, x, ref, plan_pos, plan_feet_id, plan_meta, tick, mu, T):
         """Oracle convenience (host memory, float64): returns the advanced (x, ref, tick) and the per-tick logs."""
         f = lambda a: np.ascontiguousarray(a, dtype=np.float64).copy()
@@ -258,98 +289,6 @@ class Engine:
                          mu.ctypes.data, actual.ctypes.data, desired.ctypes.data, forces.ctypes.data, solved.ctypes.data)
         return {"x": x, "ref": ref, "tick": tick, "actual": actual, "desired": desired, "forces": forces, "solved": solved}
 
-    def _plan_call(self, name):
-        if not self.library.has_plan:
-            raise MpcQpError(f"{name}: {self.library.path} does not export include/mpcqp_plan.h (product library only)")
-        return getattr(self.library.lib, name)
-
-    def plan_footsteps_ptr(self, B, S, feet0, cmd, gait, plan_pos, plan_feet_id, plan_meta, plan_ang=0, plan_hip=0, stream=0):
-        """Raw call of the device footstep planner (include/mpcqp_plan.h); every argument is an integer address."""
-        rc = self._plan_call("mpcqp_plan_footsteps")(self._h, int(B), int(S), feet0 or None, cmd or None, gait or None, plan_pos or None,
-                                                      plan_feet_id or None, plan_meta or None, plan_ang or None, plan_hip or None,
-                                                      stream or None)
-        if rc != 0:
-            raise MpcQpError(f"mpcqp_plan_footsteps failed with code {rc}: {self.last_error()}")
-
-    def swing_trajectories_ptr(self, B, K, S, plan_pos, plan_feet_id, plan_meta, plan_ang, tick, step_height, traj, feet_des=0, stream=0):
-        """Raw call of the device swing-foot trajectory generator (include/mpcqp_plan.h); every argument is an integer address."""
-        rc = self._plan_call("mpcqp_swing_trajectories")(self._h, int(B), int(K), int(S), plan_pos or None, plan_feet_id or None,
-                                                          plan_meta or None, plan_ang or None, tick or None, step_height or None,
-                                                          traj or None, feet_des or None, stream or None)
-        if rc != 0:
-            raise MpcQpError(f"mpcqp_swing_trajectories failed with code {rc}: {self.last_error()}")
-
-    def _sim_call(self, name):
-        if not self.library.has_sim:
-            raise MpcQpError(f"{name}: {self.library.path} does not export include/mpcqp_sim.h (product library only)")
-        return getattr(self.library.lib, name)
-
-    def plant_step_ptr(self, B, x, f, feet, contact, body, wrench, substeps, x_out, stream=0):
-        """Raw call of the rigid-body plant (include/mpcqp_sim.h, mpcqp_plant_step); every argument is an integer address."""
-        rc = self._sim_call("mpcqp_plant_step")(self._h, int(B), x or None, f or None, feet or None, contact or None, body or None,
-                                                 wrench or None, int(substeps), x_out or None, stream or None)
-        if rc != 0:
-            raise MpcQpError(f"mpcqp_plant_step failed with code {rc}: {self.last_error()}")
-
-    def rollout_plant_ptr(self, B, T, S, x, ref, plan_pos, plan_feet_id, plan_meta, tick, mu, body, push, push_ticks, substeps,
-                          actual, desired, forces, solved, stream=0):
-        """Raw call of the roll-out on the rigid-body plant (include/mpcqp_sim.h, mpcqp_rollout_plant); integer addresses."""
-        rc = self._sim_call("mpcqp_rollout_plant")(self._h, int(B), int(T), int(S), x or None, ref or None, plan_pos or None,
-                                                    plan_feet_id or None, plan_meta or None, tick or None, mu or None, body or None,
-                                                    push or None, push_ticks or None, int(substeps), actual or None, desired or None,
-                                                    forces or None, solved or None, stream or None)
-        if rc != 0:
-            raise MpcQpError(f"mpcqp_rollout_plant failed with code {rc}: {self.last_error()}")
-
-    def _model_call(self, name):
-        if not self.library.has_model:
-            raise MpcQpError(f"{name}: {self.library.path} does not export include/mpcqp_model.h (product library only)")
-        return getattr(self.library.lib, name)
-
-    def set_models_ptr(self, B, model, stream=0):
-        """Raw call of mpcqp_set_models (include/mpcqp_model.h): `model` is the address of an fp64 [B,6] device table."""
-        rc = self._model_call("mpcqp_set_models")(self._h, int(B), model or None, stream or None)
-        if rc != 0:
-            raise MpcQpError(f"mpcqp_set_models failed with code {rc}: {self.last_error()}")
-
-    def clear_models(self):
-        """mpcqp_clear_models (include/mpcqp_model.h): back to the configuration's m, Ibody_inv, f_min, f_max."""
-        rc = self._model_call("mpcqp_clear_models")(self._h)
-        if rc != 0:
-            raise MpcQpError(f"mpcqp_clear_models failed with code {rc}: {self.last_error()}")
-
-    def _joints_call(self, name):
-        if not self.library.has_joints:
-            raise MpcQpError(f"{name}: {self.library.path} does not export include/mpcqp_joints.h (product library only)")
-        return getattr(self.library.lib, name)
-
-    def leg_ik_ptr(self, B, foot, rot, origin, q, reach=0, geometry=None, stream=0):
-        """Raw call of the closed-form leg inverse kinematics (include/mpcqp_joints.h, mpcqp_leg_ik); integer addresses."""
-        rc = self._joints_call("mpcqp_leg_ik")(self._h, int(B), foot or None, rot or None, origin or None,
-                                               ctypes.byref(geometry) if geometry is not None else None, q or None, reach or None,
-                                               stream or None)
-        if rc != 0:
-            raise MpcQpError(f"mpcqp_leg_ik failed with code {rc}: {self.last_error()}")
-
-    def joint_log_ptr(self, B, T, actual, forces, feet, q, tau, reach, geometry=None, stream=0):
-        """Raw call of the joint-space log of a roll-out (include/mpcqp_joints.h, mpcqp_joint_log); integer addresses."""
-        rc = self._joints_call("mpcqp_joint_log")(self._h, int(B), int(T), actual or None, forces or None, feet or None,
-                                                  ctypes.byref(geometry) if geometry is not None else None, q or None, tau or None,
-                                                  reach or None, stream or None)
-        if rc != 0:
-            raise MpcQpError(f"mpcqp_joint_log failed with code {rc}: {self.last_error()}")
-
-    def torque_map_ptr(self, B, u, jac, tau, stream=0):
-        rc = self.library.lib.mpcqp_torque_map(self._h, int(B), u, jac, tau, stream or None)
-        if rc != 0:
-            raise MpcQpError(f"mpcqp_torque_map failed with code {rc}: {self.last_error()}")
-
-    def leg_jacobians_ptr(self, B, q, rot, jac, foot=0, geometry=None, stream=0):
-        rc = self.library.lib.mpcqp_leg_jacobians(self._h, int(B), q, rot or None, ctypes.byref(geometry) if geometry is not None else None,
-                                                  jac, foot or None, stream or None)
-        if rc != 0:
-            raise MpcQpError(f"mpcqp_leg_jacobians failed with code {rc}: {self.last_error()}")
-
     def leg_jacobians_host(self, q, rot=None, geometry=None):
         """Host-memory call (the CPU checker): q [B,4,3], rot [B,3,3] or None -> (jac [B,4,3,3], foot [B,4,3]), float64."""
         q = np.ascontiguousarray(q, dtype=np.float64); B = q.shape[0]
@@ -358,45 +297,38 @@ class Engine:
         self.leg_jacobians_ptr(B, q.ctypes.data, 0 if rot is None else rot.ctypes.data, jac.ctypes.data, foot.ctypes.data, geometry)
         return jac, foot
 
-    def last_kernel_ms(self) -> float:
-        ms = c_float()
-        rc = self.library.lib.mpcqp_last_kernel_ms(self._h, ctypes.byref(ms))
-        if rc != 0:
-            raise MpcQpError(f"mpcqp_last_kernel_ms failed with code {rc}: {self.last_error()}")
-        return float(ms.value)
+    def _host_dtype(self):
+        return np.float64 if self.cfg.dtype == DTYPE_F64 else np.float32
 
-    # host-pointer convenience (numpy); valid for libraries that take host memory
+    def _host_results(self, B, want_X):
+        """The result dict of the two *_host solves and the addresses of its arrays, in the C order of the outputs."""
+        N, ft = self.cfg.N, self._host_dtype()
+        out = {"u": np.zeros((B, N, 12), ft), "X": np.zeros((B, N + 1, 13), ft) if want_X else None,
+               "status": np.zeros(B, np.int32), "iters": np.zeros(B, np.int32), "res": np.zeros((B, 2), np.float32)}
+        return out, [a.ctypes.data if a is not None else None for a in out.values()]
+
     def solve_batch_host(self, x0, r, contact, xdes, mu, want_X=True):
-        N = self.cfg.N
-        ft = np.float64 if self.cfg.dtype == DTYPE_F64 else np.float32
+        N, ft = self.cfg.N, self._host_dtype()
         x0 = np.ascontiguousarray(x0, dtype=ft); r = np.ascontiguousarray(r, dtype=ft)
         xdes = np.ascontiguousarray(xdes, dtype=ft); mu = np.ascontiguousarray(mu, dtype=ft)
         contact = np.ascontiguousarray(contact, dtype=np.uint8)
         B = x0.shape[0]
         assert x0.shape == (B, 13) and r.shape == (B, N, 4, 3) and contact.shape == (B, N, 4)
         assert xdes.shape == (B, N + 1, 13) and mu.shape == (B,)
-        u = np.zeros((B, N, 12), ft)
-        X = np.zeros((B, N + 1, 13), ft) if want_X else None
-        status = np.zeros(B, np.int32); iters = np.zeros(B, np.int32); res = np.zeros((B, 2), np.float32)
-        self.solve_batch_ptr(B, x0.ctypes.data, r.ctypes.data, contact.ctypes.data, xdes.ctypes.data, mu.ctypes.data,
-                             u.ctypes.data, X.ctypes.data if want_X else None, status.ctypes.data, iters.ctypes.data,
-                             res.ctypes.data)
-        return {"u": u, "X": X, "status": status, "iters": iters, "res": res}
-
+        out, out_ptrs = self._host_results(B, want_X)
+        self.solve_batch_ptr(B, x0.ctypes.data, r.ctypes.data, contact.ctypes.data, xdes.ctypes.data, mu.ctypes.data, *out_ptrs)
+        return out
 
     def solve_batch_gait_host(self, g, want_X=True):
         """Host-pointer convenience for the gait entry point; `g` is a dict as produced by synth.make_gait_batch (footholds [B,S,4,3])."""
-        N = self.cfg.N
-        ft = np.float64 if self.cfg.dtype == DTYPE_F64 else np.float32
+        ft = self._host_dtype()
         a = {k: np.ascontiguousarray(g[k], dtype=ft) for k in ("x0", "ref", "feet0", "footholds", "mu")}
         gait = np.ascontiguousarray(g["gait"], dtype=np.int32); fid = np.ascontiguousarray(g["feet_id"], dtype=np.uint8)
         B, S = a["x0"].shape[0], a["footholds"].shape[1]
-        u = np.zeros((B, N, 12), ft); X = np.zeros((B, N + 1, 13), ft) if want_X else None
-        status = np.zeros(B, np.int32); iters = np.zeros(B, np.int32); res = np.zeros((B, 2), np.float32)
+        out, out_ptrs = self._host_results(B, want_X)
         self.solve_batch_gait_steps_ptr(B, S, a["x0"].ctypes.data, a["ref"].ctypes.data, a["feet0"].ctypes.data, a["footholds"].ctypes.data,
-                                        gait.ctypes.data, fid.ctypes.data, a["mu"].ctypes.data, u.ctypes.data,
-                                        X.ctypes.data if want_X else None, status.ctypes.data, iters.ctypes.data, res.ctypes.data)
-        return {"u": u, "X": X, "status": status, "iters": iters, "res": res}
+                                        gait.ctypes.data, fid.ctypes.data, a["mu"].ctypes.data, *out_ptrs)
+        return out
 
 
 _product = None
