@@ -134,7 +134,11 @@ struct ActSet {
 // replaced by the combination of the last AA_M + 1 of them that minimises the fixed-point residual in the least-squares sense,
 //     gam = argmin | r - dF gam |,   v+ = f(v) - dX gam,     dF / dX: differences of consecutive residuals / images
 // -- nine inner products over the wave (seven DPP steps each), a regularised 3 x 3 solve in uniform registers, fifteen FMAs per
-// lane, once per p iterations.  numpy study on the condensed QP (tools/accel_study.py): the hardest QPs of five batches reach a
+// lane, once per p iterations.  (Of the nine numbers the solve takes, the three Gram entries among the two older columns are the
+// previous call's entries among its two newer ones -- the same lane products, summed in the same order.  CARRY = true, the MIXED
+// horizon-10 kernels, keeps them in three words of LDS and sums six: bit-identical, tests/test_gpu_accel_identity.py on the device
+// and tools/aa_carry_check.cpp on the host; 192 -> 153 VALU per call, kernel -1.5 %, profiles/r07_accel_carry.txt.  A restart of
+// the history clears them with the columns.)  numpy study on the condensed QP (tools/accel_study.py): the hardest QPs of five batches reach a
 // polishable iterate in half the iterations (worst case of a batch 375 -> 250 us of solve), the easy ones are unchanged.
 // Only with the polish (MPCQP_FLAG_POLISH): an ADMM-only run is OSQP's algorithm 1 unchanged.  History in fp32 (it steers an
 // extrapolation, it is not part of the answer); base point and images in the iteration's element type.
@@ -142,29 +146,42 @@ struct ActSet {
 #define MPCQP_AA_M 3
 #endif
 constexpr int AA_M = MPCQP_AA_M;
+constexpr int AA_NS = 2 * AA_M;                  // inner products summed per call: the newest column against every column, the right-hand sides
+constexpr int AA_NC = AA_M * (AA_M - 1) / 2;   // Gram entries among the AA_M - 1 columns that survive a call: carried, not summed again
+// The carried entries are uniform over the workgroup and live in LDS between calls, in the words of `red` (12 per wave) that follow
+// the AA_NS partial sums of wave 0: held in scalar registers from call to call they cost the headline kernel four spilled vector
+// registers (hipcc's resource report; in LDS: none).  Every thread stores the same values.
+static_assert(AA_NS + AA_NC <= 12, "the carried Gram entries share wave 0's row of the partial sums");
+// Position of dF_i . dF_j (i <= j) in the upper triangle of the Gram matrix, row by row (M = 3: 00 01 02 11 12 22).
+constexpr int aa_gram_at(int i, int j) { return i * AA_M - i * (i - 1) / 2 + (j - i); }
 struct LegAA {
   float rp[5];                       // previous residual f(v) - v
   float dX[AA_M][5], dF[AA_M][5];    // column AA_M - 1 is the newest
 };
 
-__device__ __forceinline__ void w_aa_reset(LegAA& h) {
+// Empty history; `red`: the partial-sum words w_aa_step is called with (the carried Gram entries of empty columns are zeros).
+template <bool CARRY>
+__device__ __forceinline__ void w_aa_reset(LegAA& h, float* __restrict__ red) {
 #pragma unroll
   for (int k = 0; k < 5; ++k) {
     h.rp[k] = 0.f;
 #pragma unroll
     for (int j = 0; j < AA_M; ++j) { h.dX[j][k] = 0.f; h.dF[j][k] = 0.f; }
   }
+#pragma unroll
+  for (int c = 0; c < (CARRY ? AA_NC : 0); ++c) red[AA_NS + c] = 0.f;
 }
 
 // One extrapolation: fx = f^p(xb) has just been computed.  Files (fx, fx - xb) in the history and returns the next base point in
 // xb (the extrapolated iterate, or fx itself while the history is empty / when the least-squares problem is degenerate -- then the
 // history restarts).  `have_prev`: an earlier image exists (uniform).  Uniform control flow; ends with the caller's state untouched
-// except xb / fp / h.
-template <typename TM, int NW>
+// except xb / fp / h.  CARRY = false sums all the Gram entries in every call (horizon 20 and the stage-wise engine: there the
+// carried form costs three to nine more spilled registers per kernel, hipcc's resource report).
+template <typename TM, int NW, bool CARRY>
 __device__ __forceinline__ void w_aa_step(LegAA& h, TM (&xb)[5], TM (&fp)[5], const TM (&fx)[5], bool& have_prev, const bool leg,
                                           float* __restrict__ red, const int tid) {
   static_assert(AA_M == 3 || AA_M == 2, "the solve below is written for two or three columns");
-  constexpr int M = AA_M, NQ_ = M * (M + 1) / 2 + M;
+  constexpr int M = AA_M, NG = M * (M + 1) / 2, NQ_ = NG + M, NS = AA_NS, NC = CARRY ? AA_NC : 0;
   float r[5];
   if (!have_prev) {   // (uniform) the first image of a history: nothing to combine yet -- file it and go on from it
 #pragma unroll
@@ -172,6 +189,9 @@ __device__ __forceinline__ void w_aa_step(LegAA& h, TM (&xb)[5], TM (&fp)[5], co
     have_prev = true;
     return;
   }
+  float gc[AA_NC];   // Gram entries of columns 0 .. M - 2 (upper triangle, row by row) as the last call left them
+#pragma unroll
+  for (int c = 0; c < NC; ++c) gc[c] = red[NS + c];
 #pragma unroll
   for (int k = 0; k < 5; ++k) {
     r[k] = leg ? (float)(fx[k] - xb[k]) : 0.f;
@@ -183,20 +203,52 @@ __device__ __forceinline__ void w_aa_step(LegAA& h, TM (&xb)[5], TM (&fp)[5], co
   }
   have_prev = true;
   float q[NQ_];   // M = 3: 00 01 02 11 12 22 | 0r 1r 2r;  M = 2: 00 01 11 | 0r 1r
+  if constexpr (CARRY) {
+    // (uniform: read ahead of the filing above, moved to scalar registers here -- no vector register next to the products and the sums)
 #pragma unroll
-  for (int i = 0; i < NQ_; ++i) q[i] = 0.f;
+    for (int c = 0; c < NC; ++c) gc[c] = ufloat(gc[c]);
+    // Summed in this call: the newest column against every column and the right-hand sides (M = 3: 02 12 22 | 0r 1r 2r).  The other
+    // Gram entries are the previous call's, one column on (00 01 11 <- 11 12 22): the same lane products summed in the same order.
+    float p[NS];
 #pragma unroll
-  for (int k = 0; k < 5; ++k) {
-    int at = 0;
+    for (int i = 0; i < NS; ++i) p[i] = 0.f;
+#pragma unroll
+    for (int k = 0; k < 5; ++k) {
+#pragma unroll
+      for (int i = 0; i < M; ++i) p[i] = fmaf(h.dF[i][k], h.dF[M - 1][k], p[i]);
+#pragma unroll
+      for (int i = 0; i < M; ++i) p[M + i] = fmaf(h.dF[i][k], r[k], p[M + i]);
+    }
+    wsum<NS, NW>(p, red, tid);
+    int ac = 0;
 #pragma unroll
     for (int i = 0; i < M; ++i) {
 #pragma unroll
-      for (int j = i; j < M; ++j) { q[at] = fmaf(h.dF[i][k], h.dF[j][k], q[at]); ++at; }
+      for (int j = i; j < M; ++j) q[aa_gram_at(i, j)] = j == M - 1 ? p[i] : gc[ac++];
+      q[NG + i] = p[M + i];
     }
+    ac = 0;
 #pragma unroll
-    for (int i = 0; i < M; ++i) { q[at] = fmaf(h.dF[i][k], r[k], q[at]); ++at; }
+    for (int i = 0; i + 1 < M; ++i) {
+#pragma unroll
+      for (int j = i; j + 1 < M; ++j) red[NS + ac++] = q[aa_gram_at(i + 1, j + 1)];   // (cleared again below if the history restarts)
+    }
+  } else {
+#pragma unroll
+    for (int i = 0; i < NQ_; ++i) q[i] = 0.f;
+#pragma unroll
+    for (int k = 0; k < 5; ++k) {
+      int at = 0;
+#pragma unroll
+      for (int i = 0; i < M; ++i) {
+#pragma unroll
+        for (int j = i; j < M; ++j) { q[at] = fmaf(h.dF[i][k], h.dF[j][k], q[at]); ++at; }
+      }
+#pragma unroll
+      for (int i = 0; i < M; ++i) { q[at] = fmaf(h.dF[i][k], r[k], q[at]); ++at; }
+    }
+    wsum<NQ_, NW>(q, red, tid);
   }
-  wsum<NQ_, NW>(q, red, tid);
   float g[M];
   bool ok;
   if constexpr (M == 3) {
@@ -211,7 +263,7 @@ __device__ __forceinline__ void w_aa_step(LegAA& h, TM (&xb)[5], TM (&fp)[5], co
     const float y0 = q[6], y1 = fmaf(-l10, y0, q[7]), y2 = fmaf(-l21, y1, fmaf(-l20, y0, q[8]));
     g[2] = y2 * i2; g[1] = fmaf(-l21, g[2], y1 * i1); g[0] = fmaf(-l20, g[2], fmaf(-l10, g[1], y0 * i0));
     ok = have && d1 > 0.f && d2 > 0.f && fabsf(g[0]) + fabsf(g[1]) + fabsf(g[2]) <= 1e4f;   // (a NaN fails the comparison)
-    if (!have) have_prev = true; else if (!ok) { w_aa_reset(h); have_prev = false; }   // degenerate history: start again from this iterate
+    if (!have) have_prev = true; else if (!ok) { w_aa_reset<CARRY>(h, red); have_prev = false; }   // degenerate history: start again from this iterate
   } else {
     const float tr = q[0] + q[2];
     const bool have = tr > 0.f;
@@ -221,7 +273,7 @@ __device__ __forceinline__ void w_aa_step(LegAA& h, TM (&xb)[5], TM (&fp)[5], co
     const float y0 = q[3], y1 = fmaf(-l10, y0, q[4]);
     g[1] = y1 * i1; g[0] = fmaf(-l10, g[1], y0 * i0);
     ok = have && d1 > 0.f && fabsf(g[0]) + fabsf(g[1]) <= 1e4f;
-    if (have && !ok) { w_aa_reset(h); have_prev = false; }
+    if (have && !ok) { w_aa_reset<CARRY>(h, red); have_prev = false; }
   }
 #pragma unroll
   for (int k = 0; k < 5; ++k) {

@@ -869,7 +869,7 @@ __device__ __forceinline__ void sg_admm(SmemS& s, const DevCfg& cfg, SLeg& Lg, d
       bool aa_have = false;
       int aa_left = aa_p;
       if (aa_p > 0) {
-        w_aa_reset(aa);
+        w_aa_reset<false>(aa, s.aared);
 #pragma unroll
         for (int k = 0; k < 5; ++k) { aa_xb[k] = A.z[k] + A.yh[k]; aa_fp[k] = aa_xb[k]; }
       }
@@ -901,7 +901,7 @@ __device__ __forceinline__ void sg_admm(SmemS& s, const DevCfg& cfg, SLeg& Lg, d
             double fx[5];
 #pragma unroll
             for (int k = 0; k < 5; ++k) fx[k] = A.z[k] + A.yh[k];
-            w_aa_step<double, SG_NW>(aa, aa_xb, aa_fp, fx, aa_have, Lg.leg, s.aared, tid);
+            w_aa_step<double, SG_NW, false>(aa, aa_xb, aa_fp, fx, aa_have, Lg.leg, s.aared, tid);
 #pragma unroll
             for (int k = 0; k < 5; ++k) leg_admm_project<double>(A, k, aa_xb[k]);
           }

@@ -744,6 +744,10 @@ template <typename TV, typename TM, int N, bool REFINE = false>
 __device__ __forceinline__ void w_admm(SmemW<TV, N>& s, const DevCfg& cfg, const WrTabs& tabs, const int adapt,
                                        const int kfirst, const int tid0) {
   constexpr int NL = WG<N>::NL, NW = WG<N>::NW, G = WG<N>::G;
+  // The extrapolation carries the Gram entries of its older columns (w_aa_step) where a QP is one wave and the iterations are
+  // accelerated: the MIXED horizon-10 kernels.  Four waves (horizon 20): the carried form costs the MIXED kernels registers (hipcc's
+  // resource report: 9 more spilled with fp64 buffers, 8 bytes of scratch with fp32).  Every other instantiation is compiled as before.
+  constexpr bool AA_CARRY = NW == 1 && !REFINE && sizeof(TM) == 4;
   // Element type of the sweep that inverts S.  Horizon 20: fp64 even when the iterations run on an fp32 tile -- the fp32 sweep of
   // the 120 x 120 system leaves the ADMM iterate ~5e-4 off (10 x the horizon-10 figure) and the active set of 0.2 - 0.8 % of the
   // low-friction QPs never settles; rounding the fp64 inverse to fp32 costs 13 % and leaves 1 - 3 of 4096 (tools/adapt_sweep.py).
@@ -847,7 +851,7 @@ __device__ __forceinline__ void w_admm(SmemW<TV, N>& s, const DevCfg& cfg, const
         bool aa_have = false;
         int aa_left = aa_p;
         if (aa_p > 0) {
-          w_aa_reset(aa);
+          w_aa_reset<AA_CARRY>(aa, s.aared);
 #pragma unroll
           for (int k = 0; k < 5; ++k) { aa_xb[k] = A.z[k] + A.yh[k]; aa_fp[k] = aa_xb[k]; }
           aa_park();
@@ -899,7 +903,7 @@ __device__ __forceinline__ void w_admm(SmemW<TV, N>& s, const DevCfg& cfg, const
 #pragma unroll
               for (int k = 0; k < 5; ++k) fx[k] = A.z[k] + A.yh[k];
               aa_fetch();
-              w_aa_step<TM, NW>(aa, aa_xb, aa_fp, fx, aa_have, leg, s.aared, tid);
+              w_aa_step<TM, NW, AA_CARRY>(aa, aa_xb, aa_fp, fx, aa_have, leg, s.aared, tid);
               aa_park();
 #pragma unroll
               for (int k = 0; k < 5; ++k) leg_admm_project<TM>(A, k, aa_xb[k]);
@@ -921,10 +925,13 @@ __device__ __forceinline__ void w_admm(SmemW<TV, N>& s, const DevCfg& cfg, const
         seg_end = min(K, it + seg_len);
       }
       if (leg) {
+        // (with the carry the leg-stage index is formed afresh: addresses made from the one above are kept across the iteration loop and
+        //  spilled at its head, two registers and 12 bytes of scratch in the MIXED horizon-10 kernels)
+        const int Le = AA_CARRY ? min(fresh_tid<NW>(tid0), NL - 1) : L;
 #pragma unroll
-        for (int a = 0; a < 3; ++a) { s.ua[3 * L + a] = (TV)A.u[a]; s.pu[3 * L + a] = (TV)A.u[a]; }
+        for (int a = 0; a < 3; ++a) { s.ua[3 * Le + a] = (TV)A.u[a]; s.pu[3 * Le + a] = (TV)A.u[a]; }
 #pragma unroll
-        for (int k = 0; k < 5; ++k) { const TV y = (TV)rho * (TV)A.yh[k]; s.za[5 * L + k] = (TV)A.z[k]; s.ya[5 * L + k] = y; s.py[5 * L + k] = y; }
+        for (int k = 0; k < 5; ++k) { const TV y = (TV)rho * (TV)A.yh[k]; s.za[5 * Le + k] = (TV)A.z[k]; s.ya[5 * Le + k] = y; s.py[5 * Le + k] = y; }
       }
       wsync<NW>();
       if (!rebuild) break;
