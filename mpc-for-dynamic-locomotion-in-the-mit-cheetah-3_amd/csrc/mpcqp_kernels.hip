@@ -9,6 +9,7 @@
 //                        (horizon 10) or per four waves (horizon 20), fp32 or fp64 ADMM, fp64 active-set polish, ADMM-only mode
 //   mpcqp_stage.h        stage-wise (Riccati) form of the same engine for any other horizon up to 64 -- the reference's own N = 60
 //   mpcqp_leg.h          what both engines call on one leg-stage: its structs, the Anderson step, residuals / right-hand side / projection, lane helpers
+//   mpcqp_legmap.h       the leg-stage's 6 x 3 wrench map in its two structured forms (ADMM, polish) and the dense one; plain C++, also compiled on the host
 //   mpcqp_common.h       what they share besides: operator-tuple descriptor, policy constants, the dispatch-order pre-pass;  mpcqp_device.h: DPP helpers
 //   mpcqp_elementwise.h  the element-wise kernels around the solve: gait-descriptor expansion, closed-loop roll-out (expand / advance),
 //                        torque map, leg kinematics

@@ -1,11 +1,12 @@
 // mpcqp_leg.h -- what the two solve engines (mpcqp_wrench.h, mpcqp_stage.h) share: lane-level helpers, the data of one leg-stage as
-// both engines hold it in registers (LegSys, LegAdmm, ActSet, LegAA), the Anderson step, and the parts of OSQP's iteration on the five
+// both engines hold it in registers (LegMapAdmm / LegMapPolish of mpcqp_legmap.h, LegAdmm, ActSet, LegAA), the Anderson step, and the parts of OSQP's iteration on the five
 // rows  fz | fx - mu fz | fx + mu fz | fy - mu fz | fy + mu fz  (src/mpc.py:138-173) that both engines call as functions from register
 // values to register values: residuals and rho ratio, right-hand side, projection.  No LDS, no sync, no engine type in here.
-// What is NOT here: the leg's ADMM / polish systems, the active-set rule, the warm start and the relaxation step exist once per engine
+// What is NOT here: the functions that fill the leg's ADMM / polish systems (they fill the same types), the active-set rule, the warm start and the relaxation step exist once per engine
 // (w_* / sg_*): through a common function every wrench kernel loses its assembly (profiles/r07_leg_share_check.txt).
 #pragma once
 #include "mpcqp_common.h"
+#include "mpcqp_legmap.h"
 
 namespace {
 
@@ -99,12 +100,8 @@ template <> __device__ __forceinline__ void st8<double>(double* p, const double 
   for (int h = 0; h < 4; ++h) reinterpret_cast<double2*>(p)[h] = make_double2(o[2 * h], o[2 * h + 1]);
 }
 
-// Per-leg data of a linear solve with M = D + A-stack' K A-stack: columns of the 6 x 3 wrench map and the inverse diagonal.
-template <typename TM>
-struct LegSys {
-  TM A[3][6];    // A[c][q]: wrench component q of reduced variable c
-  TM dinv[3];
-};
+// Per-leg data of a linear solve with M = D + A-stack' K A-stack -- the 6 x 3 wrench map and the inverse diagonal -- is a LegMapAdmm
+// or a LegMapPolish (mpcqp_legmap.h): both engines' *_sys functions build the same structured types.
 
 // OSQP algorithm 1 on the rows  fz | fx - mu fz | fx + mu fz | fy - mu fz | fy + mu fz  of a leg-stage
 // (src/mpc.py:138-173), one lane per leg-stage, scaled duals yh = y / rho.

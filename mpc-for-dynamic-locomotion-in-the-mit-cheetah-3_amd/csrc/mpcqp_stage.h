@@ -270,20 +270,32 @@ __device__ __forceinline__ void sg_factor(SmemS& s, double* __restrict__ ws, con
   }
 }
 
-// E_k = sum_legs A diag(dinv) A' (fp64) -> LDS.  Leg lanes (a quad = a stage).  Ends with a barrier.
-__device__ __forceinline__ void sg_build_E(SmemS& s, const LegSys<double>& L, const bool leg, const int tid) {
+// The stage-wise kernels keep the dense form of the leg maps (LegMapDense, mpcqp_legmap.h, and the expressions on it written out below: the assembly of these kernels is what it was): with the structured form every one
+// of them gains registers (hipcc's resource report: 4 more AGPRs with fp32 chains, 5 -> 13 / 7 -> 13 spilled VGPRs and 24 - 28 bytes
+// more scratch with fp64 chains).
+constexpr bool SG_LEGMAP = false;
+
+// E_k = sum_legs A diag(dinv) A' (fp64) -> LDS.  Leg lanes (a quad = a stage).  Ends with a barrier.  LS: LegMapAdmm / LegMapPolish
+// (mpcqp_legmap.h; structurally zero entries are +0 without a quad sum).
+template <typename LS>
+__device__ __forceinline__ void sg_build_E(SmemS& s, const LS& L, const bool leg, const int tid) {
   double e[21];
-  int k = 0;
+  if constexpr (LS::dense) {
+    int k = 0;
 #pragma unroll
-  for (int q = 0; q < 6; ++q) {
+    for (int q = 0; q < 6; ++q) {
 #pragma unroll
-    for (int p = q; p < 6; ++p) {
-      double a = L.dinv[0] * L.A[0][q] * L.A[0][p];
-      a = fma(L.dinv[1] * L.A[1][q], L.A[1][p], a);
-      a = fma(L.dinv[2] * L.A[2][q], L.A[2][p], a);
-      e[k++] = quad_sum(a);
+      for (int p = q; p < 6; ++p) {
+        double a = L.dinv[0] * L.A[0][q] * L.A[0][p];
+        a = fma(L.dinv[1] * L.A[1][q], L.A[1][p], a);
+        a = fma(L.dinv[2] * L.A[2][q], L.A[2][p], a);
+        e[k++] = quad_sum(a);
+      }
     }
+  } else {
+    L.gram(e, [](double a) { return quad_sum(a); });
   }
+  int k = 0;
   if (leg && (tid & 3) == 0) {
     double* Ej = s.Es + 36 * (tid >> 2);
     k = 0;
@@ -338,8 +350,8 @@ __device__ __forceinline__ void sg_ld_cols(const double* __restrict__ M, const i
 //   chain       forward recursion: z_{k+1} -> zst
 //   leg lanes   y_k = PG_k' z_{k+1} + Gam' pi_{k+1} (two components per lane, shared over the quad by DPP),  x = a - dinv A' y_k
 // Four barriers.  The chain lanes read their pair of the NEXT step and its factor rows one step ahead; nothing in a step waits for LDS.
-template <typename TM>
-__device__ __forceinline__ void sg_leg_solve(SmemS& s, const double* __restrict__ ws, const LegSys<double>& L, const double (&rhs)[3], double (&x)[3],
+template <typename TM, typename LS>
+__device__ __forceinline__ void sg_leg_solve(SmemS& s, const double* __restrict__ ws, const LS& L, const double (&rhs)[3], double (&x)[3],
                                              const bool leg, const int N, const int tid, const bool chunks = false) {
   using T2 = std::conditional_t<sizeof(TM) == 4, float2, double2>;
   const bool two_level = chunks && N >= SG_TL_MIN;   // (uniform; the factorisation was asked for the chunks' transition matrices)
@@ -355,8 +367,12 @@ __device__ __forceinline__ void sg_leg_solve(SmemS& s, const double* __restrict_
   for (int c = 0; c < 3; ++c) a[c] = L.dinv[c] * rhs[c];
   {
     double b[6];
+    if constexpr (LS::dense) {
 #pragma unroll
-    for (int q = 0; q < 6; ++q) b[q] = quad_sum(fma(L.A[2][q], a[2], fma(L.A[1][q], a[1], L.A[0][q] * a[0])));
+      for (int q = 0; q < 6; ++q) b[q] = quad_sum(fma(L.A[2][q], a[2], fma(L.A[1][q], a[1], L.A[0][q] * a[0])));
+    } else {
+      L.wrench(a, b, [](double v) { return quad_sum(v); });
+    }
     if (leg) {
       if (lq == 0) {
 #pragma unroll
@@ -639,12 +655,16 @@ __device__ __forceinline__ void sg_leg_solve(SmemS& s, const double* __restrict_
       y1 = fma(s.PGs[72 * kq + 6 * i + c0 + 1], zv, y1);
     }
     const double yj[6] = {dpp_mov<0x00>(y0), dpp_mov<0x00>(y1), dpp_mov<0x55>(y0), dpp_mov<0x55>(y1), dpp_mov<0xAA>(y0), dpp_mov<0xAA>(y1)};
+    if constexpr (LS::dense) {
 #pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      double sum = L.A[c][0] * yj[0];
+      for (int c = 0; c < 3; ++c) {
+        double sum = L.A[c][0] * yj[0];
 #pragma unroll
-      for (int q = 1; q < 6; ++q) sum = fma(L.A[c][q], yj[q], sum);
-      x[c] = a[c] - L.dinv[c] * sum;
+        for (int q = 1; q < 6; ++q) sum = fma(L.A[c][q], yj[q], sum);
+        x[c] = a[c] - L.dinv[c] * sum;
+      }
+    } else {
+      L.back(yj, [&](const int c, const double sc) { x[c] = a[c] - L.dinv[c] * sc; });
     }
   }
 }
@@ -714,30 +734,53 @@ __device__ __forceinline__ void sg_grad(SmemS& s, const SLeg& Lg, const double (
 }
 
 // The leg's 6 x 3 wrench map and inverse diagonal: ADMM (D = 2 alpha + sigma + rho G'G) / polish (reduced variables, D = 2 alpha Z'Z).
-__device__ __forceinline__ void sg_admm_sys(const SmemS& s, const DevCfg& cfg, const SLeg& Lg, const double rho, LegSys<double>& Ls) {
+template <typename LS>   // LegMapAdmm<double> or LegMapDense<double>
+__device__ __forceinline__ void sg_admm_sys(const SmemS& s, const DevCfg& cfg, const SLeg& Lg, const double rho, LS& Ls) {
+  if constexpr (LS::dense) {
 #pragma unroll
-  for (int c = 0; c < 3; ++c) {
+    for (int c = 0; c < 3; ++c) {
 #pragma unroll
-    for (int i = 0; i < 3; ++i) Ls.A[c][i] = Lg.B[3 * i + c];
+      for (int i = 0; i < 3; ++i) Ls.A[c][i] = Lg.B[3 * i + c];
 #pragma unroll
-    for (int a = 0; a < 3; ++a) Ls.A[c][3 + a] = a == c ? Lg.cm : 0.0;
+      for (int a = 0; a < 3; ++a) Ls.A[c][3 + a] = a == c ? Lg.cm : 0.0;
+    }
+  } else {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+#pragma unroll
+      for (int i = 0; i < 3; ++i) Ls.B[c][i] = Lg.B[3 * i + c];
+    }
+    Ls.cm = Lg.cm;
   }
   const double a2 = 2.0 * s.alpha, m = s.mu;
   Ls.dinv[0] = Ls.dinv[1] = Lg.stance ? 1.0 / (a2 + cfg.sigma + 2.0 * rho) : 0.0;
   Ls.dinv[2] = Lg.stance ? 1.0 / (a2 + cfg.sigma + rho * (1.0 + 4.0 * m * m)) : 0.0;
 }
 
-__device__ __forceinline__ void sg_polish_sys(const SmemS& s, const SLeg& Lg, const ActSet& a, LegSys<double>& Ls) {
+template <typename LS>   // LegMapPolish<double> or LegMapDense<double>
+__device__ __forceinline__ void sg_polish_sys(const SmemS& s, const SLeg& Lg, const ActSet& a, LS& Ls) {
   const double muv = s.mu, txs = (double)a.xs * muv, tys = (double)a.ys * muv, cm = Lg.cm;
+  if constexpr (LS::dense) {
 #pragma unroll
-  for (int i = 0; i < 3; ++i) {
-    Ls.A[0][i] = a.ex ? Lg.B[3 * i] : 0.0;
-    Ls.A[1][i] = a.ey ? Lg.B[3 * i + 1] : 0.0;
-    Ls.A[2][i] = a.ez ? Lg.B[3 * i + 2] + txs * Lg.B[3 * i] + tys * Lg.B[3 * i + 1] : 0.0;
+    for (int i = 0; i < 3; ++i) {
+      Ls.A[0][i] = a.ex ? Lg.B[3 * i] : 0.0;
+      Ls.A[1][i] = a.ey ? Lg.B[3 * i + 1] : 0.0;
+      Ls.A[2][i] = a.ez ? Lg.B[3 * i + 2] + txs * Lg.B[3 * i] + tys * Lg.B[3 * i + 1] : 0.0;
+    }
+    Ls.A[0][3] = a.ex ? cm : 0.0; Ls.A[0][4] = 0; Ls.A[0][5] = 0;
+    Ls.A[1][3] = 0; Ls.A[1][4] = a.ey ? cm : 0.0; Ls.A[1][5] = 0;
+    Ls.A[2][3] = a.ez ? txs * cm : 0.0; Ls.A[2][4] = a.ez ? tys * cm : 0.0; Ls.A[2][5] = a.ez ? cm : 0.0;
+  } else {
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+      Ls.B[0][i] = a.ex ? Lg.B[3 * i] : 0.0;
+      Ls.B[1][i] = a.ey ? Lg.B[3 * i + 1] : 0.0;
+      Ls.B[2][i] = a.ez ? Lg.B[3 * i + 2] + txs * Lg.B[3 * i] + tys * Lg.B[3 * i + 1] : 0.0;
+    }
+    Ls.d0 = a.ex ? cm : 0.0;
+    Ls.d1 = a.ey ? cm : 0.0;
+    Ls.t[0] = a.ez ? txs * cm : 0.0; Ls.t[1] = a.ez ? tys * cm : 0.0; Ls.t[2] = a.ez ? cm : 0.0;
   }
-  Ls.A[0][3] = a.ex ? cm : 0.0; Ls.A[0][4] = 0; Ls.A[0][5] = 0;
-  Ls.A[1][3] = 0; Ls.A[1][4] = a.ey ? cm : 0.0; Ls.A[1][5] = 0;
-  Ls.A[2][3] = a.ez ? txs * cm : 0.0; Ls.A[2][4] = a.ez ? tys * cm : 0.0; Ls.A[2][5] = a.ez ? cm : 0.0;
   const double a2 = 2.0 * s.alpha;
   Ls.dinv[0] = a.ex ? 1.0 / a2 : 0.0;
   Ls.dinv[1] = a.ey ? 1.0 / a2 : 0.0;
@@ -842,7 +885,7 @@ __device__ __forceinline__ void sg_admm(SmemS& s, const DevCfg& cfg, SLeg& Lg, d
   STAMP_INIT
   __syncthreads();   // (everyone has read s.rho / s.iters)
   for (;;) {
-    LegSys<double> Ls;
+    LegMapPick<SG_LEGMAP, LegMapAdmm<double>, double>::type Ls;
     sg_admm_sys(s, cfg, Lg, (double)rho, Ls);
     sg_build_E(s, Ls, Lg.leg, tid);
     sg_factor<TM>(s, ws, N, tid, true);
@@ -957,7 +1000,7 @@ __device__ __forceinline__ int sg_polish_round(SmemS& s, const DevCfg& cfg, SLeg
       if (seen && !last) break;   // uniform (a round that nothing follows goes on: mpcqp_wrench.h)
     }
     const ActSet as(code, Lg.stance);
-    LegSys<double> Ls;
+    LegMapPick<SG_LEGMAP, LegMapPolish<double>, double>::type Ls;
     sg_polish_sys(s, Lg, as, Ls);
     STAMP(7);
     sg_build_E(s, Ls, Lg.leg, tid);

@@ -310,21 +310,34 @@ __device__ __forceinline__ void w_matvec(const WTile<TM>& t, const TM* __restric
   if (gc < 8) cv[8 * gr + gc] = tot;
 }
 
-// E_j = sum_legs A diag(dinv) A' -> LDS (full 6 x 6 per stage).  Leg lanes; ends with a sync.
-template <typename TM, int N>
-__device__ __forceinline__ void w_build_E(const LegSys<TM>& L, TM* __restrict__ E, int tid) {
+// Which kernel instantiations compute with the structured leg maps (mpcqp_legmap.h); the others fill the dense form (LegMapDense) and
+// multiply its zeros as before -- their assembly is what it was (tools/isa_compare.py).  MIXED (iterations on an fp32 tile) at horizon 10, both buffer types, with and without model rows:
+// same registers, no spill, no scratch with either form.  Every other instantiation LOSES registers to the structured form (hipcc's
+// resource report, all-fp64 horizon 10: 44 -> 48 spilled registers, with the refinement step 125 -> 133; horizon 20: 8 - 16 bytes more
+// scratch in every kernel), although it has fewer values to hold: the allocation of these kernels sits on the 256-register limit and
+// any change of the instruction stream moves it.  They keep the dense form, as the AA_CARRY switch of w_admm does for the same reason.
+template <int N, bool MIXED> constexpr bool W_LEGMAP = N == 10 && MIXED;
+
+// E_j = sum_legs A diag(dinv) A' -> LDS (full 6 x 6 per stage).  Leg lanes; ends with a sync.  LS: LegMapAdmm / LegMapPolish
+// (mpcqp_legmap.h): an entry that is zero by the map's structure is written as +0 without a quad sum.
+template <typename TM, int N, typename LS>
+__device__ __forceinline__ void w_build_E(const LS& L, TM* __restrict__ E, int tid) {
   constexpr int NL = WG<N>::NL, NW = WG<N>::NW;
   TM e[21];
   int k = 0;
+  if constexpr (LS::dense) {
 #pragma unroll
-  for (int q = 0; q < 6; ++q) {
+    for (int q = 0; q < 6; ++q) {
 #pragma unroll
-    for (int p = q; p < 6; ++p) {
-      TM a = L.dinv[0] * L.A[0][q] * L.A[0][p];
-      a = fma(L.dinv[1] * L.A[1][q], L.A[1][p], a);
-      a = fma(L.dinv[2] * L.A[2][q], L.A[2][p], a);
-      e[k++] = quad_sum(a);
+      for (int p = q; p < 6; ++p) {
+        TM a = L.dinv[0] * L.A[0][q] * L.A[0][p];
+        a = fma(L.dinv[1] * L.A[1][q], L.A[1][p], a);
+        a = fma(L.dinv[2] * L.A[2][q], L.A[2][p], a);
+        e[k++] = quad_sum(a);
+      }
     }
+  } else {
+    L.gram(e, [](TM a) { return quad_sum(a); });
   }
   if (tid < NL && (tid & 3) == 0) {
     TM* Ej = E + 36 * (tid >> 2);
@@ -339,19 +352,39 @@ __device__ __forceinline__ void w_build_E(const LegSys<TM>& L, TM* __restrict__ 
 }
 
 // x = M^-1 rhs through the swept tile: x = dinv (rhs - A' S^-1 A-stack dinv rhs).  All lanes call; leg lanes hold data.
-template <typename TM, int N>
-__device__ __forceinline__ void w_solve(const WTile<TM>& t, const LegSys<TM>& L, const TM (&rhs)[3], TM (&x)[3], TM* __restrict__ bv,
+template <typename TM, int N, bool QUAD_PIN = false, typename LS>   // QUAD_PIN: the fp32 iteration of a one-wave kernel on the structured maps
+__device__ __forceinline__ void w_solve(const WTile<TM>& t, const LS& L, const TM (&rhs)[3], TM (&x)[3], TM* __restrict__ bv,
                                         TM* __restrict__ cv, int tid, int gr, int gc) {
   constexpr int NL = WG<N>::NL, NW = WG<N>::NW;
   TM a[3];
 #pragma unroll
   for (int c = 0; c < 3; ++c) a[c] = L.dinv[c] * rhs[c];
   TM b[6];
+  static_assert(!QUAD_PIN || (sizeof(TM) == 4 && !LS::dense), "the pinned form is written for fp32 on the structured maps");
+  if constexpr (LS::dense) {
 #pragma unroll
-  for (int q = 0; q < 6; ++q) b[q] = quad_sum(fma(L.A[2][q], a[2], fma(L.A[1][q], a[1], L.A[0][q] * a[0])));
+    for (int q = 0; q < 6; ++q) b[q] = quad_sum(fma(L.A[2][q], a[2], fma(L.A[1][q], a[1], L.A[0][q] * a[0])));
+  } else if constexpr (!QUAD_PIN) {
+    L.wrench(a, b, [](TM v) { return quad_sum(v); });
+  } else {
+    L.wrench(a, b, [](TM v) { return v; });
+    // The vectoriser works back from the paired store below: left to itself it pairs the ADDS of the quad sums -- a packed add takes
+    // no DPP operand, so every pair costs two lane moves and an add per step, 18 instructions for the six sums -- and, once the adds
+    // are cut off from the store, leaves the products scalar.  So both are said here: the two pairs of products that have the same
+    // shape go through a two-element vector (packed multiplies), and every sum and the stored pair are pinned as scalars (twelve adds
+    // that take their lane exchange as an operand).  The same IEEE operations on the same operands either way.
+    typedef float v2f __attribute__((ext_vector_type(2)));
+    v2f p01 = {b[0], b[1]}, p34 = {b[3], b[4]};
+    asm volatile("" : "+v"(p01), "+v"(p34));
+    b[0] = p01.x; b[1] = p01.y; b[3] = p34.x; b[4] = p34.y;
+    asm volatile("" : "+v"(b[2]), "+v"(b[5]));
+#pragma unroll
+    for (int q = 0; q < 6; ++q) b[q] = quad_sum(b[q]);
+  }
   {   // lanes 0..2 of the quad write two components each (lane 3 repeats lane 2)
     const int l = min(tid & 3, 2);
-    const TM v0 = l == 0 ? b[0] : (l == 1 ? b[2] : b[4]), v1 = l == 0 ? b[1] : (l == 1 ? b[3] : b[5]);
+    TM v0 = l == 0 ? b[0] : (l == 1 ? b[2] : b[4]), v1 = l == 0 ? b[1] : (l == 1 ? b[3] : b[5]);
+    if constexpr (QUAD_PIN) { asm volatile("" : "+v"(v0)); asm volatile("" : "+v"(v1)); }
     if (tid < NL) { TM* d = bv + 6 * (tid >> 2) + 2 * l; d[0] = v0; d[1] = v1; }
   }
   wsync<NW>();
@@ -361,12 +394,16 @@ __device__ __forceinline__ void w_solve(const WTile<TM>& t, const LegSys<TM>& L,
   TM c6[6];
 #pragma unroll
   for (int q = 0; q < 6; ++q) c6[q] = cj[q];
+  if constexpr (LS::dense) {
 #pragma unroll
-  for (int c = 0; c < 3; ++c) {
-    TM s = L.A[c][0] * c6[0];
+    for (int c = 0; c < 3; ++c) {
+      TM s = L.A[c][0] * c6[0];
 #pragma unroll
-    for (int q = 1; q < 6; ++q) s = fma(L.A[c][q], c6[q], s);
-    x[c] = a[c] - L.dinv[c] * s;
+      for (int q = 1; q < 6; ++q) s = fma(L.A[c][q], c6[q], s);
+      x[c] = a[c] - L.dinv[c] * s;
+    }
+  } else {
+    L.back(c6, [&](const int c, const TM sc) { x[c] = a[c] - L.dinv[c] * sc; });
   }
 }
 
@@ -717,23 +754,45 @@ constexpr int POLISH_CHEAP_STEPS = 3;   // further steps of a round beyond the p
 constexpr int POLISH_PATIENCE = 1;   // polish steps that may fail to halve the KKT violation before the round gives up
 
 // The leg's 6 x 3 wrench map [B_l ; contact / m I] and the inverse diagonal of D = 2 alpha + sigma + rho G'G.
-// (kept equal by hand with sg_admm_sys / sg_polish_sys / sg_polish_rule of mpcqp_stage.h, as are the warm start's per-leg part and the
-//  relaxation step: profiles/r07_leg_share_check.txt)
-template <typename TV, typename TM, int N>
-__device__ __forceinline__ void w_admm_sys(const SmemW<TV, N>& s, const DevCfg& cfg, int L, float rho, LegSys<TM>& Ls) {
+// (w_admm_sys / w_polish_sys and sg_admm_sys / sg_polish_sys of mpcqp_stage.h build the same structured types, LegMapAdmm / LegMapPolish of
+//  mpcqp_legmap.h; the active-set rule, the warm start's per-leg part and the relaxation step are kept equal by hand between the engines:
+//  profiles/r07_leg_share_check.txt)
+template <typename TV, typename TM, int N, typename LS>   // LS: LegMapAdmm<TM>, or LegMapDense<TM> filled as it always was
+__device__ __forceinline__ void w_admm_sys(const SmemW<TV, N>& s, const DevCfg& cfg, int L, float rho, LS& Ls) {
   const bool stance = s.ct[L] != 0;
+  if constexpr (LS::dense) {
 #pragma unroll
-  for (int c = 0; c < 3; ++c) {
+    for (int c = 0; c < 3; ++c) {
 #pragma unroll
-    for (int i = 0; i < 3; ++i) Ls.A[c][i] = (TM)s.Bl[9 * L + 3 * i + c];
+      for (int i = 0; i < 3; ++i) Ls.A[c][i] = (TM)s.Bl[9 * L + 3 * i + c];
 #pragma unroll
-    for (int a = 0; a < 3; ++a) Ls.A[c][3 + a] = a == c ? (TM)s.cm[L] : (TM)0;
+      for (int a = 0; a < 3; ++a) Ls.A[c][3 + a] = a == c ? (TM)s.cm[L] : (TM)0;
+    }
+  } else {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+#pragma unroll
+      for (int i = 0; i < 3; ++i) Ls.B[c][i] = (TM)s.Bl[9 * L + 3 * i + c];
+    }
+    Ls.cm = (TM)s.cm[L];
   }
   TM sigma = (TM)cfg.sigma;
   if constexpr (sizeof(TM) == 4) sigma = ufloat(sigma);   // (a converted configuration constant is hoisted out of the QP loop: keep it scalar)
   const TM r = (TM)rho, m = (TM)s.mu, a2 = (TM)((TV)2 * s.alpha);
-  Ls.dinv[0] = Ls.dinv[1] = stance ? (TM)1 / (a2 + sigma + (TM)2 * r) : (TM)0;
-  Ls.dinv[2] = stance ? (TM)1 / (a2 + sigma + r * fma((TM)4 * m, m, (TM)1)) : (TM)0;   // (an fma: the 1 is an inline operand, not half of a hoisted register pair)
+  if constexpr (!LS::dense) {
+    // The same two numbers as below, with the operations spelled out.  Below, the compiler contracts  r * (1 + 4 mu^2) + (a2 + sigma)
+    // into one fma and leaves  (a2 + sigma) + 2 r  an add (2 r is exact).  Behind the structured maps the vectoriser pairs the two
+    // sums first: as written below it keeps the pair's constant (2, .) in a register pair hoisted out of the QP loop, which the
+    // headline kernel spills (four registers, 12 bytes of scratch; opaque_zero_f64 in mpcqp_leg.h is the same mechanism), and with
+    // 2 r as r + r it pairs the ADDS and the product of the second one is rounded by itself -- another dinv[2], found by
+    // tests/test_gpu_accel_identity.py on the QPs whose rho is adapted.  An explicit fma cannot be paired with an add.
+    const TM base = a2 + sigma;
+    Ls.dinv[0] = Ls.dinv[1] = stance ? (TM)1 / (base + (r + r)) : (TM)0;
+    Ls.dinv[2] = stance ? (TM)1 / fma(r, fma((TM)4 * m, m, (TM)1), base) : (TM)0;
+  } else {
+    Ls.dinv[0] = Ls.dinv[1] = stance ? (TM)1 / (a2 + sigma + (TM)2 * r) : (TM)0;
+    Ls.dinv[2] = stance ? (TM)1 / (a2 + sigma + r * fma((TM)4 * m, m, (TM)1)) : (TM)0;   // (an fma: the 1 is an inline operand, not half of a hoisted register pair)
+  }
 }
 
 // One ADMM block from the state in s.ua / s.za / s.ya with penalty s.rho.  `adapt`: run the single early rho check (round 0
@@ -748,6 +807,8 @@ __device__ __forceinline__ void w_admm(SmemW<TV, N>& s, const DevCfg& cfg, const
   // accelerated: the MIXED horizon-10 kernels.  Four waves (horizon 20): the carried form costs the MIXED kernels registers (hipcc's
   // resource report: 9 more spilled with fp64 buffers, 8 bytes of scratch with fp32).  Every other instantiation is compiled as before.
   constexpr bool AA_CARRY = NW == 1 && !REFINE && sizeof(TM) == 4;
+  constexpr bool LM = W_LEGMAP<N, sizeof(TM) == 4>;   // structured leg maps, or the dense form
+  static_assert(!LM || (NW == 1 && sizeof(TM) == 4), "w_solve's pinned quad sums are written for one wave and fp32");
   // Element type of the sweep that inverts S.  Horizon 20: fp64 even when the iterations run on an fp32 tile -- the fp32 sweep of
   // the 120 x 120 system leaves the ADMM iterate ~5e-4 off (10 x the horizon-10 figure) and the active set of 0.2 - 0.8 % of the
   // low-friction QPs never settles; rounding the fp64 inverse to fp32 costs 13 % and leaves 1 - 3 of 4096 (tools/adapt_sweep.py).
@@ -773,7 +834,7 @@ __device__ __forceinline__ void w_admm(SmemW<TV, N>& s, const DevCfg& cfg, const
     {   // ---- phase A: E = sum_legs A diag(dinv) A' (behind the loads of the lane's K^-1 entries)
       const int tid = fresh_tid<NW>(tid0), L = min(tid, NL - 1);
       w_kq_load<TS>(kq, w_klane<TS>(tabs), tid);
-      LegSys<TS> Ls;
+      typename LegMapPick<LM, LegMapAdmm<TS>, TS>::type Ls;
       w_admm_sys<TV, TS, N>(s, cfg, L, rho, Ls);
       w_build_E<TS, N>(Ls, reinterpret_cast<TS*>(s.E), tid);
     }
@@ -803,7 +864,7 @@ __device__ __forceinline__ void w_admm(SmemW<TV, N>& s, const DevCfg& cfg, const
       const bool leg = tid < NL, stance = s.ct[L] != 0;
       const TM sigma = (TM)cfg.sigma, relax = (TM)cfg.relax, om = (TM)1 - relax, BIG = (TM)1e30, r = (TM)rho;
       if (tid >= WG<N>::NQ && tid < WG<N>::DP) bv[tid] = (TM)0;   // pad slots of the mat-vec input, in THIS phase's element type
-      LegSys<TM> Ls;                                               // (the fp64 polish overlays the same bytes)
+      typename LegMapPick<LM, LegMapAdmm<TM>, TM>::type Ls;        // (the fp64 polish overlays the same bytes)
       w_admm_sys<TV, TM, N>(s, cfg, L, rho, Ls);
       LegAdmm<TM> A;
       A.mu = (TM)s.mu;
@@ -859,7 +920,7 @@ __device__ __forceinline__ void w_admm(SmemW<TV, N>& s, const DevCfg& cfg, const
         for (int i = 0; i < n_it; ++i) {
           TM rhs[3], ut[3];
           leg_admm_rhs<TM>(A, sigma, r, rhs);
-          w_solve<TM, N>(tile, Ls, rhs, ut, bv, cv, tid, gr, gc);
+          w_solve<TM, N, LM>(tile, Ls, rhs, ut, bv, cv, tid, gr, gc);   // (LM: one wave, fp32 -- the pinned quad sums)
           if constexpr (REFINE) {
             // (own instantiation of the kernel, REFINE = true: the extra live values cost the all-fp64 kernel 85 more spilled registers)
             // ADMM that has to converge by itself to tight tolerances (polish off, eps below ~1e-6): one step of iterative refinement
@@ -950,22 +1011,34 @@ __device__ __forceinline__ void w_admm(SmemW<TV, N>& s, const DevCfg& cfg, const
 
 // ----------------------------------------------------------------------------------------------------- polish step
 // The leg's 6 x 3 reduced wrench map (tied tangential components ride on fz) and inverse diagonal 1 / (2 alpha Z'Z).
-template <typename TV, typename TP, int N>
-__device__ __forceinline__ void w_polish_sys(const SmemW<TV, N>& s, int L, const ActSet& a, LegSys<TP>& Ls) {
+template <typename TV, typename TP, int N, typename LS>   // LS: LegMapPolish<TP>, or LegMapDense<TP> filled as it always was
+__device__ __forceinline__ void w_polish_sys(const SmemW<TV, N>& s, int L, const ActSet& a, LS& Ls) {
   const TV muv = s.mu, txs = (TV)a.xs * muv, tys = (TV)a.ys * muv;
   TV B[9];
 #pragma unroll
   for (int i = 0; i < 9; ++i) B[i] = s.Bl[9 * L + i];
   const TV cm = s.cm[L];
+  if constexpr (LS::dense) {
 #pragma unroll
-  for (int i = 0; i < 3; ++i) {
-    Ls.A[0][i] = a.ex ? (TP)B[3 * i] : (TP)0;
-    Ls.A[1][i] = a.ey ? (TP)B[3 * i + 1] : (TP)0;
-    Ls.A[2][i] = a.ez ? (TP)(B[3 * i + 2] + txs * B[3 * i] + tys * B[3 * i + 1]) : (TP)0;
+    for (int i = 0; i < 3; ++i) {
+      Ls.A[0][i] = a.ex ? (TP)B[3 * i] : (TP)0;
+      Ls.A[1][i] = a.ey ? (TP)B[3 * i + 1] : (TP)0;
+      Ls.A[2][i] = a.ez ? (TP)(B[3 * i + 2] + txs * B[3 * i] + tys * B[3 * i + 1]) : (TP)0;
+    }
+    Ls.A[0][3] = a.ex ? (TP)cm : (TP)0; Ls.A[0][4] = 0; Ls.A[0][5] = 0;
+    Ls.A[1][3] = 0; Ls.A[1][4] = a.ey ? (TP)cm : (TP)0; Ls.A[1][5] = 0;
+    Ls.A[2][3] = a.ez ? (TP)(txs * cm) : (TP)0; Ls.A[2][4] = a.ez ? (TP)(tys * cm) : (TP)0; Ls.A[2][5] = a.ez ? (TP)cm : (TP)0;
+  } else {
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+      Ls.B[0][i] = a.ex ? (TP)B[3 * i] : (TP)0;
+      Ls.B[1][i] = a.ey ? (TP)B[3 * i + 1] : (TP)0;
+      Ls.B[2][i] = a.ez ? (TP)(B[3 * i + 2] + txs * B[3 * i] + tys * B[3 * i + 1]) : (TP)0;
+    }
+    Ls.d0 = a.ex ? (TP)cm : (TP)0;
+    Ls.d1 = a.ey ? (TP)cm : (TP)0;
+    Ls.t[0] = a.ez ? (TP)(txs * cm) : (TP)0; Ls.t[1] = a.ez ? (TP)(tys * cm) : (TP)0; Ls.t[2] = a.ez ? (TP)cm : (TP)0;
   }
-  Ls.A[0][3] = a.ex ? (TP)cm : (TP)0; Ls.A[0][4] = 0; Ls.A[0][5] = 0;
-  Ls.A[1][3] = 0; Ls.A[1][4] = a.ey ? (TP)cm : (TP)0; Ls.A[1][5] = 0;
-  Ls.A[2][3] = a.ez ? (TP)(txs * cm) : (TP)0; Ls.A[2][4] = a.ez ? (TP)(tys * cm) : (TP)0; Ls.A[2][5] = a.ez ? (TP)cm : (TP)0;
   const TV a2 = (TV)2 * s.alpha;
   Ls.dinv[0] = a.ex ? (TP)((TV)1 / a2) : (TP)0;
   Ls.dinv[1] = a.ey ? (TP)((TV)1 / a2) : (TP)0;
@@ -1027,11 +1100,12 @@ __device__ __forceinline__ unsigned w_aset_hash(SmemW<TV, N>& s, const int tid) 
 // at most three rank-one terms removed and three added -- Sherman-Morrison, one mat-vec and one rank-one tile update per term
 // (about two pivots' work) against the 6 N pivots of a rebuild.  At most MPCQP_W_INCR_LEGS changed leg-stages
 // and MPCQP_W_INCR_STEPS updates in a row; a candidate from a drifted inverse would simply fail the KKT test.
-template <typename TV, typename TP, int N, bool VM>
+template <typename TV, typename TP, int N, bool VM, bool LM>   // VM: w_tile_init's run masks; LM: structured leg maps (W_LEGMAP of the kernel)
 __device__ __forceinline__ int w_polish_round(SmemW<TV, N>& s, const WrTabs& tabs, const int tid0,
                                               const int budget, const bool last, const int trace_tag, const int incr_legs,
                                               const int patience, const int cheap_steps, const int cheap_legs, const int last_patience) {
   constexpr int NL = WG<N>::NL, NW = WG<N>::NW, G = WG<N>::G;
+  using PMap = typename LegMapPick<LM, LegMapPolish<TP>, TP>::type;
   constexpr int STG = 2 * 21 + 1;   // staging record of a changed leg-stage in s.E: removed | added {A[3][6], weight[3]}, stage index
   static_assert(STG * MPCQP_W_INCR_LEGS <= N * 36, "the staging records share the bytes of E");
   TP* const E = reinterpret_cast<TP*>(s.E);
@@ -1055,7 +1129,7 @@ __device__ __forceinline__ int w_polish_round(SmemW<TV, N>& s, const WrTabs& tab
     {   // ---- E = T D^-1 T' for the active set in s.aset (behind the loads of the lane's K^-1 entries)
       const int tid = fresh_tid<NW>(tid0), L = min(tid, NL - 1);
       w_kq_load<TP>(kq, w_klane<TP>(tabs), tid);
-      LegSys<TP> Ls;
+      PMap Ls;
       w_polish_sys<TV, TP, N>(s, L, ActSet(s.aset[L], s.ct[L] != 0), Ls);
       w_build_E<TP, N>(Ls, E, tid);
     }
@@ -1119,7 +1193,7 @@ __device__ __forceinline__ int w_polish_round(SmemW<TV, N>& s, const WrTabs& tab
         const TP rhs[3] = {(TP)(-rg[0]), (TP)(-rg[1]), (TP)(-rg[2])};
         TP dx[3];
         {
-          LegSys<TP> Ls;
+          PMap Ls;
           w_polish_sys<TV, TP, N>(s, L, as, Ls);
           w_solve<TP, N>(tile, Ls, rhs, dx, bv, cv, tid, gr, gc);
         }
@@ -1225,19 +1299,23 @@ __device__ __forceinline__ int w_polish_round(SmemW<TV, N>& s, const WrTabs& tab
           incr = in_row < MPCQP_W_INCR_STEPS && nupd <= incr_legs;
           if (incr && chg) {
             TP* rec = E + STG * slot;
-            LegSys<TP> Lo;
+            PMap Lo;
             w_polish_sys<TV, TP, N>(s, L, ActSet(s.aset[L], stance), Lo);
 #pragma unroll
             for (int c = 0; c < 3; ++c) {
+              TP ro[6];
+              Lo.row(c, ro);   // (dense form: its row; structured: the row with its zeros)
 #pragma unroll
-              for (int q = 0; q < 6; ++q) rec[6 * c + q] = Lo.A[c][q];
+              for (int q = 0; q < 6; ++q) rec[6 * c + q] = ro[q];
               rec[18 + c] = -Lo.dinv[c];
             }
             w_polish_sys<TV, TP, N>(s, L, ActSet(code, stance), Lo);
 #pragma unroll
             for (int c = 0; c < 3; ++c) {
+              TP ro[6];
+              Lo.row(c, ro);
 #pragma unroll
-              for (int q = 0; q < 6; ++q) rec[21 + 6 * c + q] = Lo.A[c][q];
+              for (int q = 0; q < 6; ++q) rec[21 + 6 * c + q] = ro[q];
               rec[21 + 18 + c] = Lo.dinv[c];
             }
             rec[42] = (TP)(L >> 2);
@@ -1468,7 +1546,7 @@ mpcqp_wrench_solve(const DevCfg* __restrict__ cfgp, const WrTabs tabs, const Fas
 #else
       const int trace_tag = -1;
 #endif
-      if (budget > 0) ok = __builtin_amdgcn_readfirstlane(w_polish_round<TV, TP, N, sizeof(TM) == 4>(s, tabs, tid0, budget, last, trace_tag, cfg.incr_legs, cfg.patience, cfg.cheap_steps, cfg.cheap_legs, (kind == R_ADMM) ? cfg.last_patience : 0));
+      if (budget > 0) ok = __builtin_amdgcn_readfirstlane(w_polish_round<TV, TP, N, sizeof(TM) == 4, W_LEGMAP<N, sizeof(TM) == 4>>(s, tabs, tid0, budget, last, trace_tag, cfg.incr_legs, cfg.patience, cfg.cheap_steps, cfg.cheap_legs, (kind == R_ADMM) ? cfg.last_patience : 0));
       if (ok == 1 && s.alpha > s.alpha_target) {   // next continuation level, from this optimum and its multipliers
         const int tid = fresh_tid<NW>(tid0);
         for (int i = tid; i < n; i += NT) s.ua[i] = s.uv[i];            // the last accepted answer and its multipliers (the ADMM
