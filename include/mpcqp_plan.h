@@ -1,7 +1,7 @@
 /*
  * mpcqp_plan.h -- extension of include/mpcqp.h: footstep plans and swing-foot trajectories on the device.
  *
- * These are the two pieces of the reference's per-tick glue that sit around the QP: the footstep planner
+ * These are the pieces of the per-tick glue that sit around the QP.  Two are the reference's: the footstep planner
  * (FootstepPlanner.__init__, src/footstep_planner.py:29-177) and the swing-foot trajectory generator
  * (FootTrajectoryGenerator.generate_feet_trajectories_at_time, src/foot_trajectory_generator.py:27-96), batched over B robots.
  * mpcqp_plan_footsteps writes the plan tables that mpcqp_rollout reads, so a batch of roll-outs is set up without a host loop.
@@ -67,6 +67,45 @@ int mpcqp_plan_footsteps(mpcqp_handle h, int64_t B, int32_t S, const void* feet0
 int mpcqp_swing_trajectories(mpcqp_handle h, int64_t B, int32_t K, int32_t S, const void* plan_pos, const uint8_t* plan_feet_id,
                              const int32_t* plan_meta, const void* plan_ang, const int32_t* tick, const void* step_height,
                              void* traj, void* feet_des, void* stream);
+
+/*
+ * Per-leg periodic gaits with reactive footholds: a phase clock per leg in place of a plan table.
+ *
+ * Gait row   gait i32[B,9] = (P, offset[4], stance[4]) in ticks, legs FL, FR, HL, HR.  Leg l is in stance at tick t >= 0 when
+ *            phi_l(t) = (t + offset_l) mod P < stance_l, and touches down at t exactly when 0 < stance_l < P and phi_l(t) = 0.
+ *            stance = P is a leg that never lifts, stance = 0 one that never lands; neither has a touchdown.  The row lives in device
+ *            memory and is clamped, never trusted: P into [1, 65535], offset reduced into [0, P) (a negative one to its non-negative
+ *            residue), stance into [0, P], a negative tick to 0; t + offset is formed in unsigned 32 bits, which it cannot overflow.
+ * Foothold   of a touchdown of leg l, from a CoM c, a yaw psi, a velocity v, the reference velocity v_ref = ref[6..8] and the stance
+ *            time Ts = stance_l delta:
+ *              p_xy = c_xy + Rz(psi) stand_xy[l] + (Ts / 2) v_ref_xy + gain (v_xy - v_ref_xy),    p_z = stand_z[l]
+ *   stand    T  [B,4,3]  nominal foot of each leg relative to the CoM in the yaw frame (x, y); the third entry is the WORLD z of the
+ *                        ground under that foot
+ *   gain     T  [B]      velocity feedback in seconds, or NULL for 0
+ * All arithmetic is fp64 whatever T is; fp32 outputs are the fp64 results rounded once.
+ *
+ * mpcqp_phase_expand turns (x0, ref, feet, gait, tick, stand, gain) into a caller-owned operator tuple:
+ *   x0       T  [B,13]     measured state                     ref   T  [B,10]  roll, pitch, yaw, com (3), v_ref (3), theta_dot
+ *   feet     T  [B,4,3]    the feet the robot holds (world)   tick  i32[B]     tick of stage 0
+ *   r        T  [B,N,4,3]  out                                contact u8[B,N,4] out     xdes  T [B,N+1,13]  out
+ * xdes is that of mpcqp_solve_batch_gait (never gated); contact[k][l] is the clock at tick + k.  The foothold of (k, l) belongs to the
+ * leg's last touchdown, at stage j = k - phi_l(tick + k): if 0 < stance_l < P and j >= 1 it is the rule at the REFERENCE pose of
+ * stage j (c = ref com + j delta v_ref, psi = ref yaw + j delta theta_dot) with the measured velocity v = x0[9..11]; otherwise it is
+ * the held foot feet[b][l].  The lever arm is foothold - com with the measured com at stage 0 and the reference's from stage 1 on.
+ * A swing leg gets the same rule (its force is pinned to 0 by the solve).  A non-finite stand or gain row makes the stage-0
+ * lever arms of that robot non-finite whatever its clock, and a non-finite held foot its own lever arms, so the robot's solve reports
+ * MPCQP_STATUS_NONFINITE; no other robot changes.
+ */
+int mpcqp_phase_expand(mpcqp_handle h, int64_t B, const void* x0, const void* ref, const void* feet, const int32_t* gait,
+                       const int32_t* tick, const void* stand, const void* gain, void* r, uint8_t* contact, void* xdes, void* stream);
+
+/*
+ * mpcqp_phase_expand into the engine's tuple workspace, then the solve exactly as mpcqp_solve_batch does it on that tuple: outputs,
+ * warm-start flags, model rows and mpcqp_last_kernel_ms (expand + solve) as there.  Any horizon, both engines.
+ */
+int mpcqp_solve_batch_phase(mpcqp_handle h, int64_t B, const void* x0, const void* ref, const void* feet, const int32_t* gait,
+                            const int32_t* tick, const void* stand, const void* gain, const void* mu, void* u_out, void* X_out,
+                            int32_t* status, int32_t* iters, float* res, void* stream);
 
 #ifdef __cplusplus
 }

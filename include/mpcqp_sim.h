@@ -73,6 +73,34 @@ int mpcqp_rollout_plant(mpcqp_handle h, int64_t B, int32_t T, int32_t S, void* x
                         const void* push, const int32_t* push_ticks, int32_t substeps, void* actual, void* desired, void* forces,
                         int32_t* solved, void* stream);
 
+/*
+ * mpcqp_rollout_plant with the plan table replaced by a per-leg gait clock and each robot's feet carried as state (gait row, clock and
+ * foothold rule: include/mpcqp_plan.h, mpcqp_phase_expand).  Per tick: the phase expand, the unchanged solve and one advance launch;
+ * three launches, no host synchronisation and no allocation after mpcqp_reserve.  The advance, per robot and in this order:
+ *   1. logs actual / desired / forces / solved as mpcqp_rollout does (desired is never gated: a gait has no last step)
+ *   2. logs feet_log and contact_log: the feet and the stance mask the plant uses this tick
+ *   3. steps the plant under the stage-0 forces with the held feet and the clock's stance mask (no stance leg: a ballistic tick)
+ *   4. rolls `ref` forward (com += v_ref delta, yaw += theta_dot delta) and advances `tick`
+ *   5. for every leg that touches down at the NEW tick writes feet[b][l] from the foothold rule at the MEASURED post-step state as it
+ *      is stored in x: c the CoM, v the velocity, psi = atan2(R10, R00) of the rotation the plant's rotation-vector conversion gives.
+ *      Every other foot is left bit-for-bit alone.
+ *   feet         T  [B,4,3]   in / out: the feet each robot holds (world).  A swing leg's entry is its lift-off foot until it lands.
+ *   gait         i32[B,9]     stand  T [B,4,3]     gain  T [B] or NULL
+ *   feet_log     T  [B,T,4,3] out, may be NULL.  A swing leg's row is its lift-off foot: mpcqp_joint_log on feet_log is meaningful
+ *                             for stance legs only (contact_log tells which).
+ *   contact_log  u8 [B,T,4]   out, may be NULL
+ *   x, ref, tick, mu, body, push, push_ticks, substeps, actual, desired, forces, solved   as in mpcqp_rollout_plant
+ * What is reactive: where a foot lands (step 5 reads the measured state).  What is not: when it lands (the clock is open-loop), the
+ * footholds the horizon previews for later touchdowns (reference pose, measured velocity) and the height of the ground.
+ * A non-finite feet, stand or gain row: that robot's solves report MPCQP_STATUS_NONFINITE; no other robot changes.
+ * MPCQP_EINVAL: B or T negative, B * T > 2^31 - 1, substeps outside [0, 1000], push without push_ticks, a null required buffer.
+ * B = 0 or T = 0 is a no-op.
+ */
+int mpcqp_rollout_phase(mpcqp_handle h, int64_t B, int32_t T, void* x, void* ref, void* feet, const int32_t* gait, const void* stand,
+                        const void* gain, int32_t* tick, const void* mu, const void* body, const void* push, const int32_t* push_ticks,
+                        int32_t substeps, void* actual, void* desired, void* forces, void* feet_log, uint8_t* contact_log,
+                        int32_t* solved, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

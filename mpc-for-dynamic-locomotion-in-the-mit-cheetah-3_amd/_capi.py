@@ -96,13 +96,16 @@ ABI = {
         ("mpcqp_last_kernel_ms", c_int, (_P, ctypes.POINTER(c_float))),
         ("mpcqp_last_error", c_char_p, (_P,)),
     ),
-    "mpcqp_plan.h": (   # footstep plans and swing-foot trajectories
+    "mpcqp_plan.h": (   # footstep plans, swing-foot trajectories and per-leg periodic gaits
         ("mpcqp_plan_footsteps", c_int, (_P, _I64, _I32) + (_P,) * 9),
         ("mpcqp_swing_trajectories", c_int, (_P, _I64, _I32, _I32) + (_P,) * 9),
+        ("mpcqp_phase_expand", c_int, (_P, _I64) + (_P,) * 11),
+        ("mpcqp_solve_batch_phase", c_int, (_P, _I64) + (_P,) * 14),
     ),
     "mpcqp_sim.h": (    # the rigid-body plant
         ("mpcqp_plant_step", c_int, (_P, _I64) + (_P,) * 6 + (_I32, _P, _P)),
         ("mpcqp_rollout_plant", c_int, (_P, _I64, _I32, _I32) + (_P,) * 10 + (_I32,) + (_P,) * 5),
+        ("mpcqp_rollout_phase", c_int, (_P, _I64, _I32) + (_P,) * 11 + (_I32,) + (_P,) * 7),
     ),
     "mpcqp_model.h": (  # per-robot model rows
         ("mpcqp_set_models", c_int, (_P, _I64, _P, _P)),
@@ -118,9 +121,10 @@ EXPORTED_SYMBOLS, PLAN_SYMBOLS, SIM_SYMBOLS, MODEL_SYMBOLS, JOINTS_SYMBOLS = (tu
 
 class Library:
     """A loaded shared object exporting the mpcqp C-ABI.  `has_plan`, `has_sim`, `has_model` and `has_joints` say whether it exports
-    include/mpcqp_plan.h, mpcqp_sim.h, mpcqp_model.h and mpcqp_joints.h."""
+    all of include/mpcqp_plan.h, mpcqp_sim.h, mpcqp_model.h and mpcqp_joints.h.  An extension header's calls are bound only when the
+    library has them all; `partial=True` binds whichever it has (an older build of the product library, in a comparison tool)."""
 
-    def __init__(self, path: str):
+    def __init__(self, path: str, partial: bool = False):
         if not os.path.exists(path):
             raise MpcQpError(f"mpcqp library not found: {path} (run `python -c 'import __graft_entry__ as g; g.build()'`)")
         self.path = path
@@ -132,7 +136,7 @@ class Library:
                 setattr(self, "has_" + header[len("mpcqp_"):-len(".h")], have)
             for name, restype, argtypes in rows:
                 fn = None
-                if have:   # (a symbol of the core header that is missing raises here)
+                if have or (partial and hasattr(self.lib, name)):   # (a symbol of the core header that is missing raises here)
                     fn = getattr(self.lib, name)
                     fn.restype, fn.argtypes = restype, argtypes
                 self.calls[name] = (fn, header, tuple(t not in (_I32, _I64) for t in argtypes[1:]))
@@ -247,6 +251,20 @@ class Engine:
         """The roll-out on the rigid-body plant (include/mpcqp_sim.h, mpcqp_rollout_plant)."""
         self._call("mpcqp_rollout_plant", B, T, S, x, ref, plan_pos, plan_feet_id, plan_meta, tick, mu, body, push, push_ticks, substeps,
                    actual, desired, forces, solved, stream)
+
+    def phase_expand_ptr(self, B, x0, ref, feet, gait, tick, stand, gain, r, contact, xdes, stream=0):
+        """The per-leg gait clock and foothold rule expanded into an operator tuple (include/mpcqp_plan.h, mpcqp_phase_expand)."""
+        self._call("mpcqp_phase_expand", B, x0, ref, feet, gait, tick, stand, gain, r, contact, xdes, stream)
+
+    def solve_batch_phase_ptr(self, B, x0, ref, feet, gait, tick, stand, gain, mu, u_out, X_out, status, iters, res, stream=0):
+        """That expansion and the solve in one call (include/mpcqp_plan.h, mpcqp_solve_batch_phase)."""
+        self._call("mpcqp_solve_batch_phase", B, x0, ref, feet, gait, tick, stand, gain, mu, u_out, X_out, status, iters, res, stream)
+
+    def rollout_phase_ptr(self, B, T, x, ref, feet, gait, stand, gain, tick, mu, body, push, push_ticks, substeps, actual, desired, forces,
+                          feet_log, contact_log, solved, stream=0):
+        """The roll-out on the plant with a gait clock and reactive footholds (include/mpcqp_sim.h, mpcqp_rollout_phase)."""
+        self._call("mpcqp_rollout_phase", B, T, x, ref, feet, gait, stand, gain, tick, mu, body, push, push_ticks, substeps, actual, desired,
+                   forces, feet_log, contact_log, solved, stream)
 
     def set_models_ptr(self, B, model, stream=0):
         """mpcqp_set_models (include/mpcqp_model.h): `model` is the address of an fp64 [B,6] device table."""

@@ -1,5 +1,5 @@
 // mpcqp_common.h -- what the engines share besides mpcqp_device.h: the operator-tuple descriptor, packed-fp32 helpers, the solver
-// policy constants, and the dispatch-order pre-pass (dearest-expected-first order of a batch that oversubscribes the device).
+// policy constants, the element arithmetic of the tuple expansions, and the dispatch-order pre-pass (dearest-expected-first order of a batch that oversubscribes the device).
 #pragma once
 #include "mpcqp_device.h"
 
@@ -21,6 +21,29 @@ struct FastIn {
   float* y_state;      // ... and the engine's per-slot record of the previous solve's multipliers [cap][40][5] (read, then rewritten)
   int shift;           // MPCQP_FLAG_WARM_SHIFT: the guess and the record are one control tick old: use stage k + 1 for stage k
 };
+
+// Element arithmetic of an expansion into the operator tuple, shared by the expand kernels of mpcqp_elementwise.h and mpcqp_gaits.h.
+// Element c of x_des[k].  rf: the reference row [roll, pitch, yaw, com (3), v (3), w]; g: the state's gravity entry; gate: 0 where the
+// references are zeroed (roll-out, last plan step), else 1.
+template <typename TIO>
+__device__ __forceinline__ double xdes_elem(const TIO* rf, const TIO g, const int k, const int c, const double d, const double gate) {
+  if (c < 2) return (double)rf[c];
+  if (c == 2) return (double)rf[2] + (double)k * d * gate * (double)rf[9];
+  if (c < 6) return (double)rf[c] + (double)k * d * gate * (double)rf[6 + (c - 3)];
+  if (c < 8) return 0.0;
+  if (c == 8) return gate * (double)rf[9];
+  if (c < 12) return gate * (double)rf[6 + (c - 9)];
+  return (double)g;
+}
+
+// Component a of a lever arm r[k][l] = foot - com: the measured com at stage 0, the reference's from stage 1 on.  (TF: the foot as
+// stored, or in fp64 where a rule has just computed it)
+template <typename TF, typename TIO>
+__device__ __forceinline__ double lever_elem(const TF foot, const TIO* rf, const TIO* x, const int k, const int a, const double d,
+                                             const double gate) {
+  const double com = k == 0 ? (double)x[3 + a] : (double)rf[3 + a] + (double)k * d * gate * (double)rf[6 + a];
+  return (double)foot - com;
+}
 
 // A model row as the engine keeps it (DevCfg::model, mpcqp_model.h): 1 / m, 1 / Ixx, 1 / Iyy, 1 / Izz, f_min, f_max.  An invalid
 // row is six NaNs.

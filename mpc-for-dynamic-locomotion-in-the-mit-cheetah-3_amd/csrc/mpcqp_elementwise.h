@@ -5,6 +5,7 @@
 #include "mpcqp_common.h"
 #include "mpcqp_plan.h"
 #include "mpcqp_plant.h"
+#include "mpcqp_gaits.h"
 
 namespace {
 
@@ -132,28 +133,8 @@ mpcqp_leg_jacobian_kernel(const TIO* __restrict__ q, const TIO* __restrict__ rot
 //   r[0]       = measured foot - measured com;  r[k>=1] = planned foothold of step(k) - x_des com(k)   (src/mpc.py:218-239)
 // with step(k) from the plan clock (mpcqp_plan.h).  Both expand kernels are element-wise and HBM-bound (about 100 B in, 1.1 KB out
 // per QP at N = 10, which the solve kernel then reads from L2): one thread per output element, consecutive threads write
-// consecutive addresses.  They share the element arithmetic below and differ in where the rows and the clock come from.
-
-// Element c of x_des[k].  rf: the reference row [roll, pitch, yaw, com (3), v (3), w]; g: the state's gravity entry; gate: 0 where the
-// references are zeroed (roll-out, last plan step), else 1.
-template <typename TIO>
-__device__ __forceinline__ double xdes_elem(const TIO* rf, const TIO g, const int k, const int c, const double d, const double gate) {
-  if (c < 2) return (double)rf[c];
-  if (c == 2) return (double)rf[2] + (double)k * d * gate * (double)rf[9];
-  if (c < 6) return (double)rf[c] + (double)k * d * gate * (double)rf[6 + (c - 3)];
-  if (c < 8) return 0.0;
-  if (c == 8) return gate * (double)rf[9];
-  if (c < 12) return gate * (double)rf[6 + (c - 9)];
-  return (double)g;
-}
-
-// Component a of a lever arm r[k][l] = foot - com: the measured com at stage 0, the reference's from stage 1 on.
-template <typename TIO>
-__device__ __forceinline__ double lever_elem(const TIO foot, const TIO* rf, const TIO* x, const int k, const int a, const double d,
-                                             const double gate) {
-  const double com = k == 0 ? (double)x[3 + a] : (double)rf[3 + a] + (double)k * d * gate * (double)rf[6 + a];
-  return (double)foot - com;
-}
+// consecutive addresses.  They share the element arithmetic of mpcqp_common.h (xdes_elem, lever_elem) with the expansion of a per-leg
+// gait (mpcqp_gaits.h) and differ in where the rows and the clock come from.
 
 // Leg l of the step row `fid` carries force at a tick: the step's own pattern during single support, every foot after it.
 __device__ __forceinline__ bool in_stance(const PlanClock<int>& c, const uint8_t* fid, const int l) { return c.swing ? fid[l] != 0 : true; }
@@ -235,19 +216,16 @@ __device__ __forceinline__ void world_step(const ModelWorld<TIO>& w, TIO* x, con
   for (int i = 0; i < 12; ++i) x[i] = w.X[((size_t)b * (N + 1) + 1) * 13 + i];
 }
 
+// One plant tick of robot b at its tick tk: stage-0 forces u0, feet pos [4,3] and stance mask st of the tick, the robot's body row and
+// its push inside the window.
 template <typename TIO>
-__device__ __forceinline__ void world_step(const PlantIn<TIO>& pin, TIO* x, const TIO* u0, const RolloutPlan<TIO>& plan,
-                                           const PlanClock<int>& c, const int64_t b, const int N, const int Smax, const int tk) {
+__device__ __forceinline__ void plant_world_step(const PlantIn<TIO>& pin, TIO* x, const TIO* u0, const TIO* pos, const bool (&st)[4],
+                                                 const int64_t b, const int tk) {
   double xs[13], fs[12], ft[12], bd[7], wr[6], out[13];
-  bool st[4];
-  const TIO* pos = plan.pos + (b * Smax + c.step) * 12;
-  const uint8_t* fid = plan.feet_id + (b * Smax + c.step) * 4;
 #pragma unroll
   for (int i = 0; i < 13; ++i) xs[i] = (double)x[i];
 #pragma unroll
   for (int i = 0; i < 12; ++i) { fs[i] = (double)u0[i]; ft[i] = (double)pos[i]; }
-#pragma unroll
-  for (int l = 0; l < 4; ++l) st[l] = in_stance(c, fid, l);
   plant_body_row(pin.body, pin.model, b, bd);
   const bool pushed = pin.push && pin.push_ticks[2 * b] <= tk && tk < pin.push_ticks[2 * b + 1];
 #pragma unroll
@@ -255,6 +233,38 @@ __device__ __forceinline__ void world_step(const PlantIn<TIO>& pin, TIO* x, cons
   plant_tick(xs, fs, ft, st, bd, wr, pin.n, pin.h, out);
 #pragma unroll
   for (int i = 0; i < 13; ++i) x[i] = (TIO)out[i];
+}
+
+template <typename TIO>
+__device__ __forceinline__ void world_step(const PlantIn<TIO>& pin, TIO* x, const TIO* u0, const RolloutPlan<TIO>& plan,
+                                           const PlanClock<int>& c, const int64_t b, const int N, const int Smax, const int tk) {
+  bool st[4];
+  const uint8_t* fid = plan.feet_id + (b * Smax + c.step) * 4;
+#pragma unroll
+  for (int l = 0; l < 4; ++l) st[l] = in_stance(c, fid, l);
+  plant_world_step(pin, x, u0, plan.pos + (b * Smax + c.step) * 12, st, b, tk);
+}
+
+// What every advance kernel does around its world step.  advance_log: the tick's log rows and the `solved` count, before the state
+// moves; advance_ref: the reference roll-forward after it.
+template <typename TIO>
+__device__ __forceinline__ void advance_log(const TIO* xb, const TIO* rf, const TIO* u0, const int st, const double gate, const size_t row,
+                                            const int it, const int64_t b, TIO* __restrict__ actual, TIO* __restrict__ desired,
+                                            TIO* __restrict__ forces, int32_t* __restrict__ solved) {
+  if (actual) for (int i = 0; i < 12; ++i) actual[row + i] = xb[i];                               // logger.log_tracking_data (src/mpc.py:295)
+  if (desired) {
+    const TIO des[12] = {rf[0], rf[1], rf[2], rf[3], rf[4], rf[5], (TIO)0, (TIO)0, (TIO)(gate * (double)rf[9]),
+                         (TIO)(gate * (double)rf[6]), (TIO)(gate * (double)rf[7]), (TIO)(gate * (double)rf[8])};
+    for (int i = 0; i < 12; ++i) desired[row + i] = des[i];
+  }
+  if (forces) for (int i = 0; i < 12; ++i) forces[row + i] = u0[i];                               // src/main.py:216-218
+  if (solved) solved[b] = (it == 0 ? 0 : solved[b]) + ((st == MPCQP_STATUS_SOLVED_POLISHED || st == MPCQP_STATUS_SOLVED_ADMM) ? 1 : 0);
+}
+
+template <typename TIO>
+__device__ __forceinline__ void advance_ref(TIO* rf, const double gate, const double d) {
+  for (int a = 0; a < 3; ++a) rf[3 + a] = (TIO)((double)rf[3 + a] + gate * (double)rf[6 + a] * d);   // src/mpc.py:261
+  rf[2] = (TIO)((double)rf[2] + gate * (double)rf[9] * d);                                      // src/mpc.py:262
 }
 
 // The roll-out's third launch per tick, one thread per robot: log rows, `solved` count, world step, reference roll-forward, tick.
@@ -272,20 +282,61 @@ mpcqp_rollout_advance_kernel(TIO* __restrict__ x, TIO* __restrict__ ref, const R
   const int tk = tick[b];
   const PlanClock<int> c = plan_clock(plan.meta + b * 4, Smax, max(tk, 0));
   const double gate = c.gate;
-  const size_t row = ((size_t)b * T + it) * 12;
-  if (actual) for (int i = 0; i < 12; ++i) actual[row + i] = xb[i];                               // logger.log_tracking_data (src/mpc.py:295)
-  if (desired) {
-    const TIO des[12] = {rf[0], rf[1], rf[2], rf[3], rf[4], rf[5], (TIO)0, (TIO)0, (TIO)(gate * (double)rf[9]),
-                         (TIO)(gate * (double)rf[6]), (TIO)(gate * (double)rf[7]), (TIO)(gate * (double)rf[8])};
-    for (int i = 0; i < 12; ++i) desired[row + i] = des[i];
-  }
-  if (forces) for (int i = 0; i < 12; ++i) forces[row + i] = u0[i];                               // src/main.py:216-218
-  const int st = status[b];
-  if (solved) solved[b] = (it == 0 ? 0 : solved[b]) + ((st == MPCQP_STATUS_SOLVED_POLISHED || st == MPCQP_STATUS_SOLVED_ADMM) ? 1 : 0);
+  advance_log(xb, rf, u0, status[b], gate, ((size_t)b * T + it) * 12, it, b, actual, desired, forces, solved);
   world_step(world, xb, u0, plan, c, b, N, Smax, tk);
-  for (int a = 0; a < 3; ++a) rf[3 + a] = (TIO)((double)rf[3 + a] + gate * (double)rf[6 + a] * d);   // src/mpc.py:261
-  rf[2] = (TIO)((double)rf[2] + gate * (double)rf[9] * d);                                      // src/mpc.py:262
+  advance_ref(rf, gate, d);
   tick[b] = tk + 1;
+}
+
+// The advance of mpcqp_rollout_phase: the gait clock (mpcqp_gaits.h) in place of the plan table, the robot's feet as state.  After the
+// plant tick every leg that touches down at the new tick gets its foothold from the measured state -- the state as stored, so that the
+// log replays: CoM, velocity, yaw = atan2(R10, R00) of the plant's own rotation-vector conversion.  Every other foot is not written.
+template <typename TIO>
+__global__ void __launch_bounds__(256)
+mpcqp_phase_advance_kernel(TIO* __restrict__ x, TIO* __restrict__ ref, TIO* feet, const PhaseRows<TIO> ph, int32_t* __restrict__ tick,
+                           const PlantIn<TIO> pin, const TIO* __restrict__ u, const int32_t* __restrict__ status, const double d, const int N,
+                           const int64_t B, const int T, const int it, TIO* __restrict__ actual, TIO* __restrict__ desired,
+                           TIO* __restrict__ forces, TIO* __restrict__ feet_log, uint8_t* __restrict__ contact_log,
+                           int32_t* __restrict__ solved) {
+  const int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B) return;
+  TIO* rf = ref + b * 10;
+  TIO* xb = x + b * 13;
+  TIO* ft = feet + b * 12;
+  const TIO* u0 = u + (size_t)b * N * 12;
+  const int tk = tick[b];
+  const GaitLeg c[4] = {gait_leg(ph.gait + b * GAIT_ROW, 0), gait_leg(ph.gait + b * GAIT_ROW, 1), gait_leg(ph.gait + b * GAIT_ROW, 2),
+                        gait_leg(ph.gait + b * GAIT_ROW, 3)};
+  advance_log(xb, rf, u0, status[b], 1.0, ((size_t)b * T + it) * 12, it, b, actual, desired, forces, solved);
+  bool st[4];
+#pragma unroll
+  for (int l = 0; l < 4; ++l) st[l] = gait_phase(c[l], (uint32_t)max(tk, 0)) < c[l].st;
+  if (feet_log) for (int i = 0; i < 12; ++i) feet_log[((size_t)b * T + it) * 12 + i] = ft[i];
+  if (contact_log) for (int l = 0; l < 4; ++l) contact_log[((size_t)b * T + it) * 4 + l] = st[l] ? 1 : 0;
+  plant_world_step(pin, xb, u0, ft, st, b, tk);
+  advance_ref(rf, 1.0, d);
+  tick[b] = tk + 1;
+  const uint32_t tn = tk < 0 ? 0u : (uint32_t)tk + 1u;
+  bool td[4], any = false;
+#pragma unroll
+  for (int l = 0; l < 4; ++l) { td[l] = gait_steps(c[l]) && gait_phase(c[l], tn) == 0; any = any || td[l]; }
+  if (!any) return;
+  double q[4], sn, cs;
+  plant_rotvec_to_quat((double)xb[0], (double)xb[1], (double)xb[2], q);
+  {
+#pragma clang fp contract(off)
+    sincos(atan2(2.0 * (q[1] * q[2] + q[0] * q[3]), 1.0 - 2.0 * (q[2] * q[2] + q[3] * q[3])), &sn, &cs);
+  }
+  const double gain = ph.gain ? (double)ph.gain[b] : 0.0;
+#pragma unroll
+  for (int l = 0; l < 4; ++l) {
+    if (!td[l]) continue;
+    const TIO* s = ph.stand + b * 12 + l * 3;
+    for (int a = 0; a < 2; ++a)
+      ft[3 * l + a] = (TIO)gait_foothold_xy(a, (double)xb[3 + a], cs, sn, (double)s[0], (double)s[1], (double)xb[9 + a], (double)rf[6 + a],
+                                            gait_half_stance(c[l], d), gain);
+    ft[3 * l + 2] = s[2];
+  }
 }
 
 }  // namespace

@@ -10,11 +10,12 @@
 //   mpcqp_stage.h        stage-wise (Riccati) form of the same engine for any other horizon up to 64 -- the reference's own N = 60
 //   mpcqp_leg.h          what both engines call on one leg-stage: its structs, the Anderson step, residuals / right-hand side / projection, lane helpers
 //   mpcqp_legmap.h       the leg-stage's 6 x 3 wrench map in its two structured forms (ADMM, polish) and the dense one; plain C++, also compiled on the host
-//   mpcqp_common.h       what they share besides: operator-tuple descriptor, policy constants, the dispatch-order pre-pass;  mpcqp_device.h: DPP helpers
+//   mpcqp_common.h       what they share besides: operator-tuple descriptor and expansion elements, policy constants, the dispatch-order pre-pass;  mpcqp_device.h: DPP helpers
 //   mpcqp_elementwise.h  the element-wise kernels around the solve: gait-descriptor expansion, closed-loop roll-out (expand / advance),
 //                        torque map, leg kinematics
 //   mpcqp_plan.h         footstep plans, swing-foot trajectories and the plan clock
 //   mpcqp_plant.h        the rigid-body plant that can replace the roll-out's world step
+//   mpcqp_gaits.h        per-leg periodic gaits: the phase clock, the touchdown foothold rule and their expansion into an operator tuple
 //   mpcqp_model.h        per-robot model rows: the conversion of the caller's table into the engine's
 //   mpcqp_joints.h       closed-form leg inverse kinematics and the joint-space log of a roll-out
 // DESIGN.md has the derivations.
@@ -674,39 +675,32 @@ PlantModel plant_model(const mpcqp_engine* h) {
   return {h->cfg.m, 1.0 / h->cfg.Ibody_inv[0], 1.0 / h->cfg.Ibody_inv[1], 1.0 / h->cfg.Ibody_inv[2]};
 }
 
-// The roll-out behind mpcqp_rollout and mpcqp_rollout_plant: workspace reserved once, then 3 launches per tick on the caller's
-// stream, no host synchronisation and no copies in between.  (mpcqp_last_kernel_ms after a roll-out: all T ticks)
-int rollout_run(mpcqp_handle h, int64_t B, int32_t T, int32_t S, void* x, void* ref, const void* plan_pos, const uint8_t* plan_feet_id,
-                const int32_t* plan_meta, int32_t* tick, const void* mu, void* actual, void* desired, void* forces, int32_t* solved,
-                void* stream, const RolloutPlantArgs* plant) {
-  if (reserve_workspace(h, B) != MPCQP_OK || reserve_gait(h, B) != MPCQP_OK || reserve_roll(h, B) != MPCQP_OK)
-    return fail(h, MPCQP_ENOMEM, "mpcqp_rollout: workspace allocation failed");
+// The roll-out loop behind mpcqp_rollout, mpcqp_rollout_plant and mpcqp_rollout_phase: workspace reserved once, then 3 launches per
+// tick on the caller's stream, no host synchronisation and no copies in between.  expand(tag, x, ref, w) launches the tick's expand
+// kernel into the tuple workspace w, advance(tag, x, ref, o, it) the advance kernel on the results o; tag carries the I/O type.
+// (mpcqp_last_kernel_ms after a roll-out: all T ticks)
+template <typename Expand, typename Advance>
+int rollout_loop(mpcqp_handle h, const char* who, int64_t B, int32_t T, void* x, void* ref, const void* mu, void* stream, Expand&& expand,
+                 Advance&& advance) {
+  if (reserve_workspace(h, B) != MPCQP_OK || reserve_gait(h, B) != MPCQP_OK || reserve_roll(h, B) != MPCQP_OK) {
+    snprintf(h->err, sizeof(h->err), "%s: workspace allocation failed", who);
+    return MPCQP_ENOMEM;
+  }
   const int N = h->cfg.N;
-  const double d = h->cfg.delta;
-  const dim3 ge((unsigned)((B * (int64_t)tuple_elems(N) + 255) / 256)), ga((unsigned)((B + 255) / 256)), nt(256);
   hipStream_t st = (hipStream_t)stream;
   if (const int rc = record(h, h->ev0, st)) return rc;
   const hipError_t he = with_io(h, [&](auto tag) {
     using TIO = decltype(tag);
     const TupleWs<TIO> w = tuple_ws<TIO>(h->gait_mem, B, N);
     const ResultWs<TIO> o = result_ws<TIO>(h->roll_mem, B, N);
-    const RolloutPlan<TIO> plan = {(const TIO*)plan_pos, plan_feet_id, plan_meta};
     const FastIn<TIO> in = tuple_in<TIO>(h, x, w.r, w.contact, w.xdes, mu, o.u);
     TIO* xs = (TIO*)x;
     TIO* rf = (TIO*)ref;
     for (int it = 0; it < T; ++it) {
-      hipLaunchKernelGGL((mpcqp_rollout_expand_kernel<TIO>), ge, nt, 0, st, xs, rf, plan, tick, d, N, (int)S, B, w.r, w.contact, w.xdes);
+      expand(tag, xs, rf, w);
       hipError_t e = enqueue_solve<TIO>(h, B, in, o.u, o.X, o.status, o.iters, nullptr, st);
       if (e != hipSuccess) return e;
-      if (plant) {
-        const PlantIn<TIO> world = {(const TIO*)plant->body, (const TIO*)plant->push, plant->push_ticks, plant_model(h), plant->n, d / plant->n};
-        hipLaunchKernelGGL((mpcqp_rollout_advance_kernel<TIO, PlantIn<TIO>>), ga, nt, 0, st, xs, rf, plan, tick, world, o.u, o.status, d, N, B,
-                           (int)T, it, (int)S, (TIO*)actual, (TIO*)desired, (TIO*)forces, solved);
-      } else {
-        const ModelWorld<TIO> world = {o.X};
-        hipLaunchKernelGGL((mpcqp_rollout_advance_kernel<TIO, ModelWorld<TIO>>), ga, nt, 0, st, xs, rf, plan, tick, world, o.u, o.status, d, N, B,
-                           (int)T, it, (int)S, (TIO*)actual, (TIO*)desired, (TIO*)forces, solved);
-      }
+      advance(tag, xs, rf, o, it);
       e = hipGetLastError();
       if (e != hipSuccess) return e;
     }
@@ -714,6 +708,43 @@ int rollout_run(mpcqp_handle h, int64_t B, int32_t T, int32_t S, void* x, void* 
   });
   if (he != hipSuccess) return fail(h, MPCQP_EHIP, "roll-out kernel launch", he);
   return record(h, h->ev1, st);
+}
+
+// Launch grids of the roll-out's element-wise kernels: one thread per tuple element (expand), one per robot (advance).
+dim3 expand_grid(int64_t B, int N) { return dim3((unsigned)((B * (int64_t)tuple_elems(N) + 255) / 256)); }
+dim3 advance_grid(int64_t B) { return dim3((unsigned)((B + 255) / 256)); }
+
+template <typename TIO>
+PlantIn<TIO> plant_in(const mpcqp_engine* h, const RolloutPlantArgs& p) {
+  return {(const TIO*)p.body, (const TIO*)p.push, p.push_ticks, plant_model(h), p.n, h->cfg.delta / p.n};
+}
+
+// The roll-out on a plan table: mpcqp_rollout (plant = null) and mpcqp_rollout_plant.
+int rollout_run(mpcqp_handle h, int64_t B, int32_t T, int32_t S, void* x, void* ref, const void* plan_pos, const uint8_t* plan_feet_id,
+                const int32_t* plan_meta, int32_t* tick, const void* mu, void* actual, void* desired, void* forces, int32_t* solved,
+                void* stream, const RolloutPlantArgs* plant) {
+  const int N = h->cfg.N;
+  const double d = h->cfg.delta;
+  const dim3 ge = expand_grid(B, N), ga = advance_grid(B), nt(256);
+  hipStream_t st = (hipStream_t)stream;
+  return rollout_loop(h, "mpcqp_rollout", B, T, x, ref, mu, stream,
+    [&](auto tag, auto* xs, auto* rf, const auto& w) {
+      using TIO = decltype(tag);
+      const RolloutPlan<TIO> plan = {(const TIO*)plan_pos, plan_feet_id, plan_meta};
+      hipLaunchKernelGGL((mpcqp_rollout_expand_kernel<TIO>), ge, nt, 0, st, xs, rf, plan, tick, d, N, (int)S, B, w.r, w.contact, w.xdes);
+    },
+    [&](auto tag, auto* xs, auto* rf, const auto& o, int it) {
+      using TIO = decltype(tag);
+      const RolloutPlan<TIO> plan = {(const TIO*)plan_pos, plan_feet_id, plan_meta};
+      if (plant) {
+        hipLaunchKernelGGL((mpcqp_rollout_advance_kernel<TIO, PlantIn<TIO>>), ga, nt, 0, st, xs, rf, plan, tick, plant_in<TIO>(h, *plant), o.u,
+                           o.status, d, N, B, (int)T, it, (int)S, (TIO*)actual, (TIO*)desired, (TIO*)forces, solved);
+      } else {
+        const ModelWorld<TIO> world = {o.X};
+        hipLaunchKernelGGL((mpcqp_rollout_advance_kernel<TIO, ModelWorld<TIO>>), ga, nt, 0, st, xs, rf, plan, tick, world, o.u, o.status, d, N, B,
+                           (int)T, it, (int)S, (TIO*)actual, (TIO*)desired, (TIO*)forces, solved);
+      }
+    });
 }
 
 // substeps of include/mpcqp_sim.h: 0 means the default, [1, 1000] as given; -1 for out of range
@@ -755,6 +786,87 @@ int mpcqp_rollout_plant(mpcqp_handle h, int64_t B, int32_t T, int32_t S, void* x
   if (guard.err != hipSuccess) return fail(h, MPCQP_EHIP, "hipSetDevice", guard.err);
   const RolloutPlantArgs plant = {body, push, push ? push_ticks : nullptr, n};
   return rollout_run(h, B, T, S, x, ref, plan_pos, plan_feet_id, plan_meta, tick, mu, actual, desired, forces, solved, stream, &plant);
+}
+
+int mpcqp_phase_expand(mpcqp_handle h, int64_t B, const void* x0, const void* ref, const void* feet, const int32_t* gait, const int32_t* tick,
+                       const void* stand, const void* gain, void* r, uint8_t* contact, void* xdes, void* stream) {
+  if (!h) return MPCQP_EINVAL;
+  if (B < 0 || B > 0x7fffffff) return fail(h, MPCQP_EINVAL, "mpcqp_phase_expand: batch size out of range");
+  if (B > 0 && (!x0 || !ref || !feet || !gait || !tick || !stand || !r || !contact || !xdes))
+    return fail(h, MPCQP_EINVAL, "mpcqp_phase_expand: null buffer");
+  if (B == 0) return MPCQP_OK;
+  DeviceGuard guard(h->cfg.device);
+  if (guard.err != hipSuccess) return fail(h, MPCQP_EHIP, "hipSetDevice", guard.err);
+  const int N = h->cfg.N;
+  with_io(h, [&](auto tag) {
+    using T = decltype(tag);
+    const PhaseRows<T> ph = {(const T*)feet, gait, (const T*)stand, (const T*)gain};
+    hipLaunchKernelGGL((mpcqp_phase_expand_kernel<T>), expand_grid(B, N), dim3(256), 0, (hipStream_t)stream, (const T*)x0, (const T*)ref, ph,
+                       tick, h->cfg.delta, N, B, (T*)r, contact, (T*)xdes);
+  });
+  return launched(h, "phase expansion kernel launch");
+}
+
+int mpcqp_solve_batch_phase(mpcqp_handle h, int64_t B, const void* x0, const void* ref, const void* feet, const int32_t* gait,
+                            const int32_t* tick, const void* stand, const void* gain, const void* mu, void* u_out, void* X_out,
+                            int32_t* status, int32_t* iters, float* res, void* stream) {
+  if (!h) return MPCQP_EINVAL;
+  if (B < 0 || B > 0x7fffffff) return fail(h, MPCQP_EINVAL, "mpcqp_solve_batch_phase: batch size out of range");
+  if (B > 0 && (!x0 || !ref || !feet || !gait || !tick || !stand || !mu || !u_out || !status || !iters))
+    return fail(h, MPCQP_EINVAL, "mpcqp_solve_batch_phase: null buffer");
+  if (B == 0) return mpcqp_solve_batch(h, 0, x0, nullptr, nullptr, nullptr, mu, u_out, X_out, status, iters, res, stream);
+  if (const int rc = models_match(h, B, "mpcqp_solve_batch_phase")) return rc;
+  DeviceGuard guard(h->cfg.device);
+  if (guard.err != hipSuccess) return fail(h, MPCQP_EHIP, "hipSetDevice", guard.err);
+  if (reserve_workspace(h, B) != MPCQP_OK || reserve_gait(h, B) != MPCQP_OK)
+    return fail(h, MPCQP_ENOMEM, "mpcqp_solve_batch_phase: workspace allocation failed");
+  // as the gait entry point: the expansion into the engine's tuple workspace, then the normal solve on that tuple; the timing covers both
+  const int N = h->cfg.N;
+  hipStream_t st = (hipStream_t)stream;
+  if (const int rc = record(h, h->ev0, st)) return rc;
+  const hipError_t he = with_io(h, [&](auto tag) {
+    using T = decltype(tag);
+    const TupleWs<T> w = tuple_ws<T>(h->gait_mem, B, N);
+    const PhaseRows<T> ph = {(const T*)feet, gait, (const T*)stand, (const T*)gain};
+    hipLaunchKernelGGL((mpcqp_phase_expand_kernel<T>), expand_grid(B, N), dim3(256), 0, st, (const T*)x0, (const T*)ref, ph, tick, h->cfg.delta,
+                       N, B, w.r, w.contact, w.xdes);
+    return enqueue_solve<T>(h, B, tuple_in<T>(h, x0, w.r, w.contact, w.xdes, mu, u_out), (T*)u_out, (T*)X_out, status, iters, res, st);
+  });
+  if (he != hipSuccess) return fail(h, MPCQP_EHIP, "phase expansion / solve kernel launch", he);
+  return record(h, h->ev1, st);
+}
+
+int mpcqp_rollout_phase(mpcqp_handle h, int64_t B, int32_t T, void* x, void* ref, void* feet, const int32_t* gait, const void* stand,
+                        const void* gain, int32_t* tick, const void* mu, const void* body, const void* push, const int32_t* push_ticks,
+                        int32_t substeps, void* actual, void* desired, void* forces, void* feet_log, uint8_t* contact_log, int32_t* solved,
+                        void* stream) {
+  if (!h) return MPCQP_EINVAL;
+  if (B < 0 || B > 0x7fffffff || T < 0 || B * (int64_t)T > 0x7fffffff) return fail(h, MPCQP_EINVAL, "mpcqp_rollout_phase: size out of range");
+  const int n = plant_substeps(substeps);
+  if (n < 0) return fail(h, MPCQP_EINVAL, "mpcqp_rollout_phase: substeps out of range [0, 1000]");
+  if (push && !push_ticks) return fail(h, MPCQP_EINVAL, "mpcqp_rollout_phase: push without push_ticks");
+  if (B > 0 && (!x || !ref || !feet || !gait || !stand || !tick || !mu)) return fail(h, MPCQP_EINVAL, "mpcqp_rollout_phase: null buffer");
+  if (B == 0 || T == 0) return MPCQP_OK;
+  if (const int rc = models_match(h, B, "mpcqp_rollout_phase")) return rc;
+  DeviceGuard guard(h->cfg.device);
+  if (guard.err != hipSuccess) return fail(h, MPCQP_EHIP, "hipSetDevice", guard.err);
+  const RolloutPlantArgs plant = {body, push, push ? push_ticks : nullptr, n};
+  const int N = h->cfg.N;
+  const double d = h->cfg.delta;
+  const dim3 ge = expand_grid(B, N), ga = advance_grid(B), nt(256);
+  hipStream_t st = (hipStream_t)stream;
+  return rollout_loop(h, "mpcqp_rollout_phase", B, T, x, ref, mu, stream,
+    [&](auto tag, auto* xs, auto* rf, const auto& w) {
+      using TIO = decltype(tag);
+      const PhaseRows<TIO> ph = {(const TIO*)feet, gait, (const TIO*)stand, (const TIO*)gain};
+      hipLaunchKernelGGL((mpcqp_phase_expand_kernel<TIO>), ge, nt, 0, st, xs, rf, ph, tick, d, N, B, w.r, w.contact, w.xdes);
+    },
+    [&](auto tag, auto* xs, auto* rf, const auto& o, int it) {
+      using TIO = decltype(tag);
+      const PhaseRows<TIO> ph = {(const TIO*)feet, gait, (const TIO*)stand, (const TIO*)gain};
+      hipLaunchKernelGGL((mpcqp_phase_advance_kernel<TIO>), ga, nt, 0, st, xs, rf, (TIO*)feet, ph, tick, plant_in<TIO>(h, plant), o.u, o.status, d, N, B,
+                         (int)T, it, (TIO*)actual, (TIO*)desired, (TIO*)forces, (TIO*)feet_log, contact_log, solved);
+    });
 }
 
 int mpcqp_set_models(mpcqp_handle h, int64_t B, const double* model, void* stream) {

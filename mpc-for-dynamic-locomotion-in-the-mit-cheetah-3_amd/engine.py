@@ -36,15 +36,16 @@ def _ptr(t):
 class MPCBatch:
     """One engine handle on one GPU.  All tensors live on ``cuda:<device>``; nothing is copied to the host."""
 
-    def __init__(self, N=10, delta=0.03, device=0, io_dtype="f32", precision="mixed", warm_start=False, warm_shift=False,
+    def __init__(self, N=10, delta=0.03, device=0, io_dtype="f32", precision="mixed", warm_start=False, warm_shift=False, library=None,
                  **overrides):
         """``warm_start=True`` sets MPCQP_FLAG_WARM_START: every solve is seeded with the forces already in the output
         buffer -- the previous solve's solution unless ``u_init`` is passed -- like ``opt.set_initial(U, sol.value(U))``
-        in the reference (src/mpc.py:270-271)."""
+        in the reference (src/mpc.py:270-271).  `library`: another build of the product library (a `_capi.Library`) instead of the
+        in-tree one, for tools that compare builds."""
         torch = _torch()
         if not torch.cuda.is_available():
             raise _capi.MpcQpError("MPCBatch needs a GPU: the mpcqp engine has no CPU path")
-        lib = _capi.product_library()
+        lib = library or _capi.product_library()
         if warm_start:
             overrides["flags"] = int(overrides.get("flags", _capi.FLAG_POLISH)) | _capi.FLAG_WARM_START
             if warm_shift:   # the buffer holds the previous control tick's solution: the engine shifts it (and its duals)
@@ -212,6 +213,60 @@ class MPCBatch:
         robot's own ticks push_ticks[b][0] <= tick < push_ticks[b][1] (int32 [B,2], required with push).  Same in-place advance of
         `x`, `ref` and `tick`, same logs and `solved` count as `rollout`."""
         return self._rollout(x, ref, plan_pos, plan_feet_id, plan_meta, tick, mu, T, log, stream, (body, push, push_ticks, substeps))
+
+    def _phase_rows(self, B, x, ref, feet, gait, tick, stand, gain, x_name="x0"):
+        """Operand rows the three phase calls share."""
+        torch = _torch()
+        return ((x_name, x, (B, 13), self.tdtype), ("ref", ref, (B, 10), self.tdtype), ("feet", feet, (B, 4, 3), self.tdtype),
+                ("gait", gait, (B, 9), torch.int32), ("tick", tick, (B,), torch.int32), ("stand", stand, (B, 4, 3), self.tdtype),
+                ("gain", gain, (B,), self.tdtype))
+
+    def phase_expand(self, x0, ref, feet, gait, tick, stand, gain=None, stream=None):
+        """The operator tuple of a per-leg periodic gait, generated on the device (include/mpcqp_plan.h, mpcqp_phase_expand; the host
+        counterpart is gaits.phase_expand_host): x0 [B,13], ref [B,10], feet [B,4,3] the held feet, gait int32 [B,9] = (P, offset[4],
+        stance[4]) in ticks (gaits.gait_rows), tick int32 [B], stand [B,4,3] (nominal foot x / y in the yaw frame, world ground z),
+        gain [B] or None (0) -> {"r": [B,N,4,3], "contact": uint8 [B,N,4], "xdes": [B,N+1,13]}.  Asynchronous on `stream`."""
+        torch = _torch()
+        B, N = int(x0.shape[0]), self.N
+        check_operands(self.device, self._phase_rows(B, x0, ref, feet, gait, tick, stand, gain), optional=("gain",))
+        st = self._stream(stream)
+        r, contact, xdes = self._alloc(stream, ((B, N, 4, 3), self.tdtype), ((B, N, 4), torch.uint8), ((B, N + 1, 13), self.tdtype))
+        self.engine.phase_expand_ptr(B, x0.data_ptr(), ref.data_ptr(), feet.data_ptr(), gait.data_ptr(), tick.data_ptr(), stand.data_ptr(),
+                                     _ptr(gain), r.data_ptr(), contact.data_ptr(), xdes.data_ptr(), st.cuda_stream)
+        return {"r": r, "contact": contact, "xdes": xdes}
+
+    def solve_batch_phase(self, x0, ref, feet, gait, tick, stand, gain, mu, want_X=False, stream=None, u_init=None):
+        """`phase_expand` into the engine's own workspace and `solve_batch` on that tuple, in one call (include/mpcqp_plan.h,
+        mpcqp_solve_batch_phase).  `gain` may be None."""
+        B = int(x0.shape[0])
+        check_operands(self.device, self._phase_rows(B, x0, ref, feet, gait, tick, stand, gain) + (("mu", mu, (B,), self.tdtype),),
+                       optional=("gain",))
+        call = lambda B, x0, ref, feet, gait, tick, stand, mu, *out: self.engine.solve_batch_phase_ptr(
+            B, x0, ref, feet, gait, tick, stand, _ptr(gain), mu, *out)
+        return self._solve(call, (B,), (x0, ref, feet, gait, tick, stand, mu), want_X, stream, u_init)
+
+    def rollout_phase(self, x, ref, feet, gait, stand, gain, tick, mu, T, body=None, push=None, push_ticks=None, substeps=10, log=True,
+                      stream=None):
+        """`rollout_plant` on a per-leg gait clock with reactive footholds (include/mpcqp_sim.h, mpcqp_rollout_phase; the host
+        counterpart is gaits.rollout_phase_host): `feet` [B,4,3] is state next to `x`, `ref` and `tick`, all advanced IN PLACE -- a leg
+        that touches down gets its foothold from the measured state, every other foot is untouched.  gait, stand, gain as in
+        `phase_expand`; body, push, push_ticks, substeps as in `rollout_plant`.  Returns the logs of `rollout` plus "feet_log"
+        [B,T,4,3] and "contact_log" uint8 [B,T,4], the feet and stance mask the plant used each tick (a swing leg's row is its lift-off
+        foot: `joint_log` on feet_log is meaningful for stance legs only)."""
+        torch = _torch()
+        B, T = int(x.shape[0]), int(T)
+        check_operands(self.device, self._phase_rows(B, x, ref, feet, gait, tick, stand, gain, "x") + (
+            ("mu", mu, (B,), self.tdtype), ("body", body, (B, 7), self.tdtype), ("push", push, (B, 6), self.tdtype),
+            ("push_ticks", push_ticks, (B, 2), torch.int32)), optional=("gain", "body", "push", "push_ticks"))
+        st = self._stream(stream)
+        rows = ((B, T, 12), self.tdtype) if log else None
+        actual, desired, forces, feet_log, contact_log, solved = self._alloc(
+            stream, rows, rows, rows, ((B, T, 4, 3), self.tdtype) if log else None, ((B, T, 4), torch.uint8) if log else None,
+            ((B,), torch.int32, not T > 0))
+        self.engine.rollout_phase_ptr(B, T, x.data_ptr(), ref.data_ptr(), feet.data_ptr(), gait.data_ptr(), stand.data_ptr(), _ptr(gain),
+                                      tick.data_ptr(), mu.data_ptr(), _ptr(body), _ptr(push), _ptr(push_ticks), substeps, _ptr(actual),
+                                      _ptr(desired), _ptr(forces), _ptr(feet_log), _ptr(contact_log), solved.data_ptr(), st.cuda_stream)
+        return {"actual": actual, "desired": desired, "forces": forces, "feet_log": feet_log, "contact_log": contact_log, "solved": solved}
 
     def plan_footsteps(self, feet0, cmd, gait, S, want_ang=True, want_hip=False, stream=None):
         """Footstep plans of B robots on the device (include/mpcqp_plan.h, mpcqp_plan_footsteps; the host FootstepPlanner per robot):

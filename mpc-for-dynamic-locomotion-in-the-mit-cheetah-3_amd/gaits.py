@@ -1,0 +1,227 @@
+"""Host counterpart of the per-leg periodic gaits (include/mpcqp_plan.h: mpcqp_phase_expand, mpcqp_solve_batch_phase;
+include/mpcqp_sim.h: mpcqp_rollout_phase): numpy fp64, vectorised over robots, in the device's operation order
+(csrc/mpcqp_gaits.h) so that the two agree to rounding.
+
+The clock.  A gait row is ``(P, offset[4], stance[4])`` in ticks, legs FL, FR, HL, HR.  Leg l is in stance at tick t >= 0 when
+``phi_l(t) = (t + offset_l) mod P < stance_l`` (the convention of ``synth.perleg_contact``) and touches down at t exactly when
+``0 < stance_l < P`` and ``phi_l(t) = 0``.  Rows are clamped as the device clamps them: P into [1, 65535], offset reduced into
+[0, P), stance into [0, P], negative ticks to 0.
+
+The rule.  ``p_xy = c_xy + Rz(psi) stand_xy + (Ts / 2) v_ref_xy + gain (v_xy - v_ref_xy)``, ``p_z = stand_z`` with
+``Ts = stance_l * delta``: the nominal foot under the hip, half a stance of travel ahead, moved by the velocity error.
+
+Named rows (``gait_rows``).  Each is (touchdown time of FL, FR, HL, HR as a fraction of the period, duty factor); leg l lands at
+ticks t = round(touchdown_l P) (mod P) and stays down for round(duty P) ticks, at least 1 and at most P - 1.  The fractions are
+this project's choice of a plain representative of each gait, not a measurement of an animal or of the Cheetah 3:
+
+    trot         diagonal pairs (FL+HR, FR+HL) half a period apart, duty 0.6: the pairs overlap, there is always support
+    flying_trot  the same pairs, duty 0.4: a flight phase of a tenth of the period between the pairs
+    pace         lateral pairs (FL+HL, FR+HR), duty 0.6
+    bound        front pair and hind pair half a period apart, duty 0.5
+    pronk        all four together, duty 0.5: half of the period is flight
+    gallop       transverse: FL 0, FR 0.1, HL 0.5, HR 0.6, duty 0.3: a flight phase of a tenth of the period after each pair
+    walk         four beats a quarter apart in lateral sequence (FL 0, HR 0.25, FR 0.5, HL 0.75), duty 0.75: one leg swings at a time
+    stand        stance = P: no leg ever lifts
+"""
+from __future__ import annotations
+
+import numpy as np
+
+from .plant import DEFAULT_SUBSTEPS, model_body, push_wrench, rotvec_to_quat, srb_step
+
+MAX_PERIOD = 65535
+
+# name: ((touchdown fraction of FL, FR, HL, HR), duty factor); duty None = never lifts
+GAITS = {
+    "trot": ((0.0, 0.5, 0.5, 0.0), 0.6),
+    "flying_trot": ((0.0, 0.5, 0.5, 0.0), 0.4),
+    "pace": ((0.0, 0.5, 0.0, 0.5), 0.6),
+    "bound": ((0.0, 0.0, 0.5, 0.5), 0.5),
+    "pronk": ((0.0, 0.0, 0.0, 0.0), 0.5),
+    "gallop": ((0.0, 0.1, 0.5, 0.6), 0.3),
+    "walk": ((0.0, 0.5, 0.75, 0.25), 0.75),
+    "stand": ((0.0, 0.0, 0.0, 0.0), None),
+}
+
+
+def _f64(a):
+    return np.asarray(a, dtype=np.float64)
+
+
+def gait_rows(names, period):
+    """int32 [B,9] gait rows of the named gaits (GAITS) at `period` ticks (a scalar or one per name)."""
+    names = [names] if isinstance(names, str) else list(names)
+    P = np.broadcast_to(np.asarray(period, dtype=np.int64), (len(names),))
+    rows = np.zeros((len(names), 9), np.int32)
+    for i, name in enumerate(names):
+        land, duty = GAITS[name]
+        p = int(P[i])
+        if not 1 <= p <= MAX_PERIOD:
+            raise ValueError(f"period must be in [1, {MAX_PERIOD}], got {p}")
+        rows[i, 0] = p
+        for l in range(4):   # landing at tick t0 means phi(t0) = 0: offset = -t0 mod P
+            rows[i, 1 + l] = (-int(np.floor(land[l] * p + 0.5))) % p
+            rows[i, 5 + l] = p if duty is None else min(max(int(np.floor(duty * p + 0.5)), 1), max(p - 1, 1))
+    return rows
+
+
+def clamp_gait(gait):
+    """The clamped row of the device (csrc/mpcqp_gaits.h, gait_leg): (P [B], offset [B,4], stance [B,4]) as int64."""
+    g = np.asarray(gait).astype(np.int64).reshape(-1, 9)
+    P = np.clip(g[:, 0], 1, MAX_PERIOD)
+    off = np.mod(g[:, 1:5], P[:, None])            # numpy's mod has the divisor's sign: a non-negative residue
+    st = np.clip(g[:, 5:9], 0, P[:, None])
+    return P, off, st
+
+
+def phase(gait, tick):
+    """phi [B,...,4] of every leg at the ticks `tick` [B,...] (clamped at >= 0)."""
+    P, off, _ = clamp_gait(gait)
+    t = np.maximum(np.asarray(tick).astype(np.int64), 0)
+    ex = (slice(None),) + (None,) * (t.ndim - 1)
+    return np.mod(t[..., None] + off[ex], P[ex + (None,)])
+
+
+def phase_contact(gait, tick, N):
+    """contact uint8 [B,N,4]: the clock at tick + k, k < N."""
+    _, _, st = clamp_gait(gait)
+    t = np.maximum(np.asarray(tick).astype(np.int64), 0)[:, None] + np.arange(N)[None, :]
+    return (phase(gait, t) < st[:, None, :]).astype(np.uint8)
+
+
+def touchdown_mask(gait, tick):
+    """bool [B,4]: leg l touches down at `tick` [B]."""
+    P, _, st = clamp_gait(gait)
+    steps = (st > 0) & (st < P[:, None])
+    return steps & (phase(gait, tick) == 0)
+
+
+def touchdown_foothold(com, psi, v, v_ref, stand, gain, gait, delta):
+    """The foothold rule for all four legs: com [B,>=2], psi [B], v and v_ref [B,>=2], stand [B,4,3], gain [B] or None, the gait
+    rows (for the stance time) -> p [B,4,3]."""
+    com, v, vr, stand = _f64(com), _f64(v), _f64(v_ref), _f64(stand)
+    B = stand.shape[0]
+    psi = _f64(psi).reshape(B)
+    gain = np.zeros(B) if gain is None else _f64(gain).reshape(B)
+    _, _, st = clamp_gait(gait)
+    half_ts = 0.5 * (st.astype(np.float64) * float(delta))                                   # [B,4]
+    cs, sn = np.cos(psi)[:, None], np.sin(psi)[:, None]
+    sx, sy = stand[:, :, 0], stand[:, :, 1]
+    rot = [cs * sx - sn * sy, sn * sx + cs * sy]
+    p = np.empty((B, 4, 3))
+    with np.errstate(invalid="ignore", over="ignore"):
+        for a in range(2):
+            p[:, :, a] = ((com[:, None, a] + rot[a]) + half_ts * vr[:, None, a]) + gain[:, None] * (v[:, None, a] - vr[:, None, a])
+    p[:, :, 2] = stand[:, :, 2]
+    return p
+
+
+def measured_yaw(theta):
+    """Yaw of a rotation vector [B,3] the way the roll-out's advance reads it: atan2(R10, R00) of the plant's quaternion."""
+    q = rotvec_to_quat(theta)
+    w, x, y, z = q[..., 0], q[..., 1], q[..., 2], q[..., 3]
+    return np.arctan2(2.0 * (x * y + w * z), 1.0 - 2.0 * (y * y + z * z))
+
+
+def _xdes(x0, ref, N, delta):
+    B = len(x0)
+    k = np.arange(N + 1)[None, :, None]
+    xdes = np.zeros((B, N + 1, 13))
+    xdes[:, :, 0], xdes[:, :, 1] = ref[:, None, 0], ref[:, None, 1]
+    xdes[:, :, 2] = ref[:, None, 2] + k[:, :, 0] * delta * ref[:, None, 9]
+    xdes[:, :, 3:6] = ref[:, None, 3:6] + k * delta * ref[:, None, 6:9]
+    xdes[:, :, 8] = ref[:, None, 9]
+    xdes[:, :, 9:12] = ref[:, None, 6:9]
+    xdes[:, :, 12] = x0[:, None, 12]
+    return xdes
+
+
+def phase_expand_host(x0, ref, feet, gait, tick, stand, gain, N=10, delta=0.03):
+    """mpcqp_phase_expand on the host: {"r" [B,N,4,3], "contact" uint8 [B,N,4], "xdes" [B,N+1,13]}."""
+    x0, ref, feet, stand = _f64(x0), _f64(ref), _f64(feet), _f64(stand)
+    B = len(x0)
+    gainv = np.zeros(B) if gain is None else _f64(gain).reshape(B)
+    P, _, st = clamp_gait(gait)
+    xdes = _xdes(x0, ref, N, delta)
+    t = np.maximum(np.asarray(tick).astype(np.int64), 0)[:, None] + np.arange(N)[None, :]
+    phi = phase(gait, t)                                                                      # [B,N,4]
+    contact = (phi < st[:, None, :]).astype(np.uint8)
+    j = np.arange(N)[None, :, None] - phi
+    ruled = ((st > 0) & (st < P[:, None]))[:, None, :] & (j >= 1)
+    foot = np.broadcast_to(feet[:, None], (B, N, 4, 3)).copy()
+    jd = np.maximum(j, 0) * float(delta)                                                      # [B,N,4]
+    with np.errstate(invalid="ignore", over="ignore"):
+        psi = ref[:, None, None, 2] + jd * ref[:, None, None, 9]
+        cs, sn = np.cos(psi), np.sin(psi)
+        sx, sy = stand[:, None, :, 0], stand[:, None, :, 1]
+        rot = [cs * sx - sn * sy, sn * sx + cs * sy]
+        half_ts = 0.5 * (st.astype(np.float64) * float(delta))[:, None, :]
+        for a in range(2):
+            c = ref[:, None, None, 3 + a] + jd * ref[:, None, None, 6 + a]
+            vr = ref[:, None, None, 6 + a]
+            p = ((c + rot[a]) + half_ts * vr) + gainv[:, None, None] * (x0[:, None, None, 9 + a] - vr)
+            foot[:, :, :, a] = np.where(ruled, p, foot[:, :, :, a])
+        foot[:, :, :, 2] = np.where(ruled, np.broadcast_to(stand[:, None, :, 2], (B, N, 4)), foot[:, :, :, 2])
+        r = foot - xdes[:, :N, None, 3:6]
+        r[:, 0] = foot[:, 0] - x0[:, None, 3:6]
+    bad = ~(np.isfinite(stand).all(axis=(1, 2)) & np.isfinite(gainv))
+    r[bad, 0] = np.nan            # the stage-0 lever arms, which never read the rule: the tuple is non-finite whatever the clock
+    return {"r": r, "contact": contact, "xdes": xdes}
+
+
+def rollout_phase_host(oracle_engine, x, ref, feet, gait, stand, gain, tick, mu, T, body=None, push=None, push_ticks=None,
+                       substeps=DEFAULT_SUBSTEPS):
+    """Closed loop of mpcqp_rollout_phase on the CPU checker (host memory, fp64).  Per tick: ``phase_expand_host``, the checker's
+    ``solve_batch_host`` on that tuple, the log rows, ``plant.srb_step`` under the stage-0 forces with the held feet and the clock's
+    stance mask, the reference roll-forward and the tick advance, then ``touchdown_foothold`` at the measured state for the legs that
+    land at the new tick.  Returns the advanced (x, ref, tick, feet) and the logs."""
+    if push is not None and push_ticks is None:
+        raise ValueError("push needs push_ticks")
+    cfg = oracle_engine.cfg
+    N, delta = cfg.N, cfg.delta
+    x = _f64(x).copy(); ref = _f64(ref).copy(); feet = _f64(feet).copy(); tick = np.asarray(tick, dtype=np.int32).copy()
+    B = x.shape[0]
+    body = model_body(cfg.m, list(cfg.Ibody_inv), B) if body is None else _f64(body)
+    actual = np.zeros((B, T, 12)); desired = np.zeros((B, T, 12)); forces = np.zeros((B, T, 12)); solved = np.zeros(B, np.int32)
+    feet_log = np.zeros((B, T, 4, 3)); contact_log = np.zeros((B, T, 4), np.uint8)
+    for t in range(T):
+        e = phase_expand_host(x, ref, feet, gait, tick, stand, gain, N, delta)
+        o = oracle_engine.solve_batch_host(x, e["r"], e["contact"], e["xdes"], mu, want_X=False)
+        actual[:, t] = x[:, :12]
+        desired[:, t, 0:6] = ref[:, 0:6]; desired[:, t, 8] = ref[:, 9]; desired[:, t, 9:12] = ref[:, 6:9]
+        forces[:, t] = o["u"][:, 0]
+        solved += ((o["status"] == 1) | (o["status"] == 2)).astype(np.int32)
+        feet_log[:, t], contact_log[:, t] = feet, e["contact"][:, 0]
+        wr = None if push is None else push_wrench(push, push_ticks, tick)
+        x = srb_step(x, forces[:, t], feet, e["contact"][:, 0], body, wr, delta, substeps)
+        ref[:, 3:6] = ref[:, 3:6] + ref[:, 6:9] * delta
+        ref[:, 2] = ref[:, 2] + ref[:, 9] * delta
+        tick = tick + 1
+        td = touchdown_mask(gait, tick)
+        if td.any():
+            p = touchdown_foothold(x[:, 3:6], measured_yaw(x[:, 0:3]), x[:, 9:12], ref[:, 6:9], stand, gain, gait, delta)
+            feet = np.where(td[:, :, None], p, feet)
+    return {"x": x, "ref": ref, "tick": tick, "feet": feet, "actual": actual, "desired": desired, "forces": forces, "solved": solved,
+            "feet_log": feet_log, "contact_log": contact_log}
+
+
+def make_phase_batch(B, names=("trot", "bound"), period=12, seed=20251018, mus=(0.5, 0.7, 1.0), v_ref=(0.18, 0.0, 0.0), theta_dot=0.0,
+                     gain=0.03):
+    """B robots at the start of a walk on a gait clock: state, reference descriptor, feet under the nominal stance, gait rows (robot
+    b gets names[b mod len(names)]), stand rows (synth.NOMINAL_FEET x / y, ground height synth.FOOT_Z) and gains (0 for the first
+    half of the robots)."""
+    from .synth import FOOT_Z, G_ACC, H_COM, NOMINAL_FEET
+    rng = np.random.default_rng(seed)
+    names = [names] if isinstance(names, str) else list(names)
+    x = np.zeros((B, 13)); ref = np.zeros((B, 10))
+    com = np.array([0.0, 0.0, H_COM])[None] + rng.normal(0.0, 0.005, (B, 3)) * np.array([1.0, 1.0, 0.5])
+    x[:, 3:6] = com; x[:, 6:9] = rng.normal(0.0, 0.02, (B, 3)); x[:, 9:12] = rng.normal(0.0, 0.02, (B, 3)); x[:, 12] = G_ACC
+    ref[:, 3:5] = com[:, :2]; ref[:, 5] = H_COM; ref[:, 6:9] = np.asarray(v_ref, float); ref[:, 9] = theta_dot
+    stand = np.tile(np.concatenate([NOMINAL_FEET[:, :2], np.full((4, 1), FOOT_Z)], axis=1), (B, 1, 1))
+    stand[:, :, :2] += rng.normal(0.0, 0.003, (B, 4, 2))
+    feet = stand.copy()
+    feet[:, :, :2] += com[:, None, :2]
+    gains = np.where(np.arange(B) < B // 2, 0.0, gain)
+    mu = np.asarray(mus, float)[rng.integers(0, len(mus), B)]
+    gait = gait_rows([names[b % len(names)] for b in range(B)], period)
+    return {"x": x, "ref": ref, "feet": feet, "gait": gait, "stand": stand, "gain": gains, "tick": np.zeros(B, np.int32), "mu": mu}
