@@ -318,11 +318,27 @@ __device__ __forceinline__ void leg_admm_rhs(const LegAdmm<TM>& A, const TM sigm
   rhs[1] = fma(r, w1, fma(sigma, A.u[1], -A.g[1]));
   rhs[2] = fma(r, w2, fma(sigma, A.u[2], -A.g[2]));
 }
+// clip(t) to [lo, hi].  MED3 = false: fmin(fmax(t, lo), hi) -- a max, a min and, in a loop, one more max per bound that is not a
+// constant: the instruction selector quiets every operand of a min / max that it cannot see to be canonical, and sees no further than
+// the basic block (v_max x, x on the loop-invariant lo0 / hi0 / loA / hiB in EVERY iteration: four of the fourteen instructions that
+// the five rows of the MIXED horizon-10 iteration spent on their clamps).  MED3 = true (fp32): the median of the three, one v_med3_f32,
+// no quieting.  For finite t and lo <= hi the median is the clamp; the result WORDS of the two forms were compared on the device
+// over every bound pair the kernels form and +-0, denormals, +-1e30, +-inf, NaN, the bounds and their neighbours: no difference,
+// tools/clamp_forms.hip (tests/test_clamp_forms.py), and every row kind takes the median.  (A QP with a non-finite input never gets here.)
+template <bool MED3, typename TM>
+__device__ __forceinline__ TM leg_clip(const TM t, const TM lo, const TM hi) {
+  if constexpr (MED3) {
+    static_assert(sizeof(TM) == 4, "v_med3_f32");
+    return __builtin_amdgcn_fmed3f(t, lo, hi);
+  } else {
+    return fmin(fmax(t, lo), hi);
+  }
+}
 // Row k from its pre-projection value t = z + yh:  z = clip(t),  yh = t - z.
-template <typename TM>
+template <typename TM, bool MED3 = false>
 __device__ __forceinline__ void leg_admm_project(LegAdmm<TM>& A, const int k, const TM t) {
   const TM lo = k == 0 ? A.lo0 : ((k & 1) ? A.loA : (TM)0), hi = k == 0 ? A.hi0 : ((k & 1) ? (TM)0 : A.hiB);
-  const TM zn = fmin(fmax(t, lo), hi);
+  const TM zn = leg_clip<MED3, TM>(t, lo, hi);
   A.yh[k] = t - zn;
   A.z[k] = zn;
 }

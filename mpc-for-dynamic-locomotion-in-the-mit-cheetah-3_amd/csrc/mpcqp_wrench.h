@@ -296,7 +296,9 @@ __device__ __forceinline__ void w_sweep(WTile<TM>& t, TM* __restrict__ piv, int 
 }
 
 // y = S^-1 x for x in LDS (bv, padded layout): returns element 8 gr + gc (valid on lanes gc < 8) and writes it to cv.
-template <typename TM, int N>
+// NEGATE = false: writes -y, the sum as the tile (-S^-1) gives it, and leaves the sign to the reader -- w_solve's pinned form, where the
+// six values are operands of multiplications and FMAs that take the sign as a source modifier (one v_xor per iteration less).
+template <typename TM, int N, bool NEGATE = true>
 __device__ __forceinline__ void w_matvec(const WTile<TM>& t, const TM* __restrict__ bv, TM* __restrict__ cv, int gr, int gc) {
   constexpr int G = WG<N>::G;
   TM x[8], acc[8];
@@ -306,7 +308,7 @@ __device__ __forceinline__ void w_matvec(const WTile<TM>& t, const TM* __restric
 #pragma unroll
     for (int i = 0; i < 8; ++i) acc[i] += dpp_mov<0x140>(acc[i]);   // row_mirror: both halves of the 16 now hold the pair sums
   }
-  const TM tot = -rs8<TM>(acc, gc & 7);   // tile = -S^-1
+  const TM sum = rs8<TM>(acc, gc & 7), tot = NEGATE ? -sum : sum;   // tile = -S^-1
   if (gc < 8) cv[8 * gr + gc] = tot;
 }
 
@@ -317,6 +319,10 @@ __device__ __forceinline__ void w_matvec(const WTile<TM>& t, const TM* __restric
 // scratch in every kernel), although it has fewer values to hold: the allocation of these kernels sits on the 256-register limit and
 // any change of the instruction stream moves it.  They keep the dense form, as the AA_CARRY switch of w_admm does for the same reason.
 template <int N, bool MIXED> constexpr bool W_LEGMAP = N == 10 && MIXED;
+// Which instantiations project the ADMM rows with one v_med3_f32 each (mpcqp_leg.h: leg_clip): the same four, whose iterations are fp32
+// and one wave's.  The others keep fmin(fmax()) -- fp64 has no such pair of forms to choose from, and the horizon-20 MIXED kernels' allocation
+// is not touched for a loop that is not where their time goes.
+template <int N, bool MIXED> constexpr bool W_MED3 = N == 10 && MIXED;
 
 // E_j = sum_legs A diag(dinv) A' -> LDS (full 6 x 6 per stage).  Leg lanes; ends with a sync.  LS: LegMapAdmm / LegMapPolish
 // (mpcqp_legmap.h): an entry that is zero by the map's structure is written as +0 without a quad sum.
@@ -388,12 +394,12 @@ __device__ __forceinline__ void w_solve(const WTile<TM>& t, const LS& L, const T
     if (tid < NL) { TM* d = bv + 6 * (tid >> 2) + 2 * l; d[0] = v0; d[1] = v1; }
   }
   wsync<NW>();
-  w_matvec<TM, N>(t, bv, cv, gr, gc);
+  w_matvec<TM, N, !QUAD_PIN>(t, bv, cv, gr, gc);
   wsync<NW>();
   const TM* cj = cv + 6 * (min(tid, NL - 1) >> 2);
   TM c6[6];
 #pragma unroll
-  for (int q = 0; q < 6; ++q) c6[q] = cj[q];
+  for (int q = 0; q < 6; ++q) c6[q] = QUAD_PIN ? -cj[q] : cj[q];   // (the negation is exact: the same operands reach `back` either way)
   if constexpr (LS::dense) {
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
@@ -809,6 +815,7 @@ __device__ __forceinline__ void w_admm(SmemW<TV, N>& s, const DevCfg& cfg, const
   constexpr bool AA_CARRY = NW == 1 && !REFINE && sizeof(TM) == 4;
   constexpr bool LM = W_LEGMAP<N, sizeof(TM) == 4>;   // structured leg maps, or the dense form
   static_assert(!LM || (NW == 1 && sizeof(TM) == 4), "w_solve's pinned quad sums are written for one wave and fp32");
+  constexpr bool MED3 = W_MED3<N, sizeof(TM) == 4>;   // the row projections as medians (leg_clip), or as fmin(fmax())
   // Element type of the sweep that inverts S.  Horizon 20: fp64 even when the iterations run on an fp32 tile -- the fp32 sweep of
   // the 120 x 120 system leaves the ADMM iterate ~5e-4 off (10 x the horizon-10 figure) and the active set of 0.2 - 0.8 % of the
   // low-friction QPs never settles; rounding the fp64 inverse to fp32 costs 13 % and leaves 1 - 3 of 4096 (tools/adapt_sweep.py).
@@ -951,7 +958,7 @@ __device__ __forceinline__ void w_admm(SmemW<TV, N>& s, const DevCfg& cfg, const
           for (int k = 0; k < 5; ++k) {
             const TM lo = k == 0 ? A.lo0 : ((k & 1) ? A.loA : (TM)0), hi = k == 0 ? A.hi0 : ((k & 1) ? (TM)0 : A.hiB);
             const TM t = fma(relax, gt[k], om * A.z[k]) + A.yh[k];
-            const TM zn = fmin(fmax(t, lo), hi);
+            const TM zn = leg_clip<MED3, TM>(t, lo, hi);
             A.yh[k] = t - zn;
             A.z[k] = zn;
           }
@@ -967,7 +974,7 @@ __device__ __forceinline__ void w_admm(SmemW<TV, N>& s, const DevCfg& cfg, const
               w_aa_step<TM, NW, AA_CARRY>(aa, aa_xb, aa_fp, fx, aa_have, leg, s.aared, tid);
               aa_park();
 #pragma unroll
-              for (int k = 0; k < 5; ++k) leg_admm_project<TM>(A, k, aa_xb[k]);
+              for (int k = 0; k < 5; ++k) leg_admm_project<TM, MED3>(A, k, aa_xb[k]);
             }
           }
         }
