@@ -78,6 +78,28 @@ int mpcqp_leg_ik(mpcqp_handle h, int64_t B, const void* foot, const void* rot, c
 int mpcqp_joint_log(mpcqp_handle h, int64_t B, int32_t T, const void* actual, const void* forces, const void* feet,
                     const MpcQpLegGeometry* geo, void* q, void* tau, uint8_t* reach, void* stream);
 
+/*
+ * mpcqp_joint_log plus joint rates and joint power.
+ *   actual, forces, feet, geo   as for mpcqp_joint_log; of actual also omega = [6..8] and v = [9..11] are read
+ *   foot_vel T  [B,T,4,3]  world velocity of each foot, or NULL = the feet are at rest in the world (stance feet; the `vel` of
+ *                          mpcqp_phase_swing for a swing leg)
+ *   q        T  [B,T,4,3]  out, may be NULL: as mpcqp_joint_log
+ *   qd       T  [B,T,4,3]  out, may be NULL: joint rates in rad / s
+ *   tau      T  [B,T,4,3]  out, may be NULL: as mpcqp_joint_log
+ *   power    T  [B,T,4]    out, may be NULL: sum_j tau_j qd_j per leg, the mechanical power of the leg's joints in W
+ *   reach    u8 [B,T,4]    out, may be NULL: as mpcqp_joint_log
+ * At least one output is required; sizes as for mpcqp_joint_log.  q, tau and reach are mpcqp_joint_log's, bit for bit.  The foot's
+ * world velocity is foot_vel = v + omega x (foot - CoM) + R J(q) qd, hence
+ *   qd = J(q)^-1 R^T (foot_vel - v - omega x (foot - CoM)),
+ * the 3x3 system solved by adjugate and determinant.  For a foot at rest power summed over the legs is the rate at which the ground
+ * forces work on the body, sum_l f_l . (v + omega x (foot_l - CoM)).  Where reach = 0 or det J = 0 (the straight and the folded
+ * knee, the foot on the HipX axis), qd and power are 0.  A non-finite leg as for mpcqp_joint_log; a non-finite omega, v or foot_vel
+ * makes qd and power of that leg NaN and leaves q, tau and reach alone.
+ */
+int mpcqp_joint_rates(mpcqp_handle h, int64_t B, int32_t T, const void* actual, const void* forces, const void* feet,
+                      const void* foot_vel, const MpcQpLegGeometry* geo, void* q, void* qd, void* tau, void* power, uint8_t* reach,
+                      void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -107,6 +107,40 @@ int mpcqp_solve_batch_phase(mpcqp_handle h, int64_t B, const void* x0, const voi
                             const int32_t* tick, const void* stand, const void* gain, const void* mu, void* u_out, void* X_out,
                             int32_t* status, int32_t* iters, float* res, void* stream);
 
+/*
+ * Swing-foot trajectories of a roll-out on a gait clock, from its logs: what mpcqp_swing_trajectories is to the plan table.
+ *   actual      T  [B,T,12]     as mpcqp_rollout_phase logs it: rotation vector, CoM, omega, v
+ *   desired     T  [B,T,12]     as it logs it; read: [8] the reference yaw rate, [9..11] v_ref
+ *   feet_log    T  [B,T,4,3]    as it logs it: the feet the plant used each tick; a swing leg's row is its lift-off foot
+ *   gait        i32[B,9]        the roll-out's gait rows, clamped as above
+ *   tick0       i32[B]          the value `tick` had BEFORE the roll-out.  The roll-out advances `tick` in place, so the caller keeps a
+ *                               copy.  Row t is tick max(tick0 + t, 0), as the roll-out's advance clamps it (a negative start tick holds
+ *                               the clock at 0); the sum saturates at 2^31 - 1.
+ *   stand, gain                 the roll-out's rows (gain may be NULL)
+ *   step_height T  [B]          apex of the swing above the straight line from lift-off to target
+ *   swing       T  [B,T,4,4,3]  out: per (robot, row, leg) the four 3-vectors pos, vel, acc, target
+ *   feet_des    T  [B,T,4,3]    out, may be NULL: pos -- the `feet` operand of mpcqp_joint_log / mpcqp_joint_rates
+ * A pure function of one log row per (robot, row, leg).  phi = phi_l(tick of the row).  The leg swings when 0 < stance_l < P and
+ * phi >= stance_l; then with n = P - stance_l, s = (phi - stance_l) / n in [0, 1), rem = P - phi ticks to touchdown, T_sw = n delta:
+ *   p0      = feet_log[b,t,l], the lift-off foot
+ *   p1      = the foothold rule at the touchdown predicted from the row: c_xy = com_xy + (rem delta) v_xy,
+ *             psi = measured yaw + (rem delta) desired[8], v the measured velocity, v_ref = desired[9..11], Ts = stance_l delta;
+ *             p1_z = stand_z.  The measured yaw is atan2(R10, R00) of the plant's rotation-vector conversion, as the roll-out reads it.
+ *             With rem = 0 this is, term for term, the foothold the roll-out writes at the landing.
+ *   pos     = p0 + b(s) (p1 - p0) + z_b(s) e_z,     b(s) = 3 s^2 - 2 s^3,   z_b(s) = 16 step_height s^2 (1 - s)^2
+ *   vel     = [b'(s) (p1 - p0) + z_b'(s) e_z] / T_sw,     acc = [b''(s) (p1 - p0) + z_b''(s) e_z] / T_sw^2
+ *   target  = p1
+ * The target moves from row to row with the measured state; vel and acc hold it frozen (they are the derivatives of the row's own
+ * curve, not differences between rows).  A stance leg, and a leg without touchdowns (stance = 0 or stance = P), has
+ * pos = target = its feet_log row bit for bit and vel = acc = 0.  A non-finite stand, gain or step_height row makes every output of
+ * that robot NaN, a non-finite actual row or desired[8..10] every output of that (robot, row), a non-finite foot its own leg's; no
+ * other robot, row or leg changes.  B = 0 or T = 0 is a no-op; B or T negative, B T > 0x7fffffff or a null required buffer is
+ * MPCQP_EINVAL.
+ */
+int mpcqp_phase_swing(mpcqp_handle h, int64_t B, int32_t T, const void* actual, const void* desired, const void* feet_log,
+                      const int32_t* gait, const int32_t* tick0, const void* stand, const void* gain, const void* step_height,
+                      void* swing, void* feet_des, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -86,8 +86,9 @@ int mpcqp_rollout_plant(mpcqp_handle h, int64_t B, int32_t T, int32_t S, void* x
  *      Every other foot is left bit-for-bit alone.
  *   feet         T  [B,4,3]   in / out: the feet each robot holds (world).  A swing leg's entry is its lift-off foot until it lands.
  *   gait         i32[B,9]     stand  T [B,4,3]     gain  T [B] or NULL
- *   feet_log     T  [B,T,4,3] out, may be NULL.  A swing leg's row is its lift-off foot: mpcqp_joint_log on feet_log is meaningful
- *                             for stance legs only (contact_log tells which).
+ *   feet_log     T  [B,T,4,3] out, may be NULL.  A swing leg's row is its lift-off foot (contact_log tells which legs swing):
+ *                             mpcqp_phase_swing (mpcqp_plan.h) turns these logs into swing trajectories, and its feet_des, not
+ *                             feet_log, is the operand mpcqp_joint_log and mpcqp_joint_rates want.
  *   contact_log  u8 [B,T,4]   out, may be NULL
  *   x, ref, tick, mu, body, push, push_ticks, substeps, actual, desired, forces, solved   as in mpcqp_rollout_plant
  * What is reactive: where a foot lands (step 5 reads the measured state).  What is not: when it lands (the clock is open-loop), the

@@ -101,6 +101,7 @@ ABI = {
         ("mpcqp_swing_trajectories", c_int, (_P, _I64, _I32, _I32) + (_P,) * 9),
         ("mpcqp_phase_expand", c_int, (_P, _I64) + (_P,) * 11),
         ("mpcqp_solve_batch_phase", c_int, (_P, _I64) + (_P,) * 14),
+        ("mpcqp_phase_swing", c_int, (_P, _I64, _I32) + (_P,) * 11),
     ),
     "mpcqp_sim.h": (    # the rigid-body plant
         ("mpcqp_plant_step", c_int, (_P, _I64) + (_P,) * 6 + (_I32, _P, _P)),
@@ -114,6 +115,7 @@ ABI = {
     "mpcqp_joints.h": (  # closed-form leg inverse kinematics and the joint-space log
         ("mpcqp_leg_ik", c_int, (_P, _I64, _P, _P, _P, _GEO, _P, _P, _P)),
         ("mpcqp_joint_log", c_int, (_P, _I64, _I32, _P, _P, _P, _GEO, _P, _P, _P, _P)),
+        ("mpcqp_joint_rates", c_int, (_P, _I64, _I32, _P, _P, _P, _P, _GEO) + (_P,) * 6),
     ),
 }
 EXPORTED_SYMBOLS, PLAN_SYMBOLS, SIM_SYMBOLS, MODEL_SYMBOLS, JOINTS_SYMBOLS = (tuple(row[0] for row in rows) for rows in ABI.values())
@@ -266,6 +268,10 @@ class Engine:
         self._call("mpcqp_rollout_phase", B, T, x, ref, feet, gait, stand, gain, tick, mu, body, push, push_ticks, substeps, actual, desired,
                    forces, feet_log, contact_log, solved, stream)
 
+    def phase_swing_ptr(self, B, T, actual, desired, feet_log, gait, tick0, stand, gain, step_height, swing, feet_des=0, stream=0):
+        """The swing-foot trajectories of a roll-out on a gait clock, from its logs (include/mpcqp_plan.h, mpcqp_phase_swing)."""
+        self._call("mpcqp_phase_swing", B, T, actual, desired, feet_log, gait, tick0, stand, gain, step_height, swing, feet_des, stream)
+
     def set_models_ptr(self, B, model, stream=0):
         """mpcqp_set_models (include/mpcqp_model.h): `model` is the address of an fp64 [B,6] device table."""
         self._call("mpcqp_set_models", B, model, stream)
@@ -282,6 +288,10 @@ class Engine:
     def joint_log_ptr(self, B, T, actual, forces, feet, q, tau, reach, geometry=None, stream=0):
         """The joint-space log of a roll-out (include/mpcqp_joints.h, mpcqp_joint_log)."""
         self._call("mpcqp_joint_log", B, T, actual, forces, feet, geometry, q, tau, reach, stream)
+
+    def joint_rates_ptr(self, B, T, actual, forces, feet, foot_vel, q, qd, tau, power, reach, geometry=None, stream=0):
+        """The joint-space log with joint rates and power (include/mpcqp_joints.h, mpcqp_joint_rates)."""
+        self._call("mpcqp_joint_rates", B, T, actual, forces, feet, foot_vel, geometry, q, qd, tau, power, reach, stream)
 
     def torque_map_ptr(self, B, u, jac, tau, stream=0):
         self._call("mpcqp_torque_map", B, u, jac, tau, stream)

@@ -114,4 +114,77 @@ mpcqp_phase_expand_kernel(const TIO* __restrict__ x, const TIO* __restrict__ ref
   }
 }
 
+// mpcqp_phase_swing: the swing-foot trajectory of the roll-out on a gait clock, from its logs alone.  One thread per (robot, log row,
+// leg), i = 4 (b T + t) + l; a pure function of that row.  A leg in swing (gait_steps and phase >= stance) moves from its lift-off
+// foot p0 = feet_log[b,t,l] to the target p1, the foothold rule at the touchdown predicted from the row's measured state (CoM and yaw
+// carried rem delta ahead at the measured velocity and the reference yaw rate), along
+//   pos = p0 + b(s) (p1 - p0) + z_b(s) e_z,   b(s) = 3 s^2 - 2 s^3,   z_b(s) = 16 H s^2 (1 - s)^2,   s = (phase - stance) / (P - stance)
+// with the target held frozen in vel = d pos / dt and acc = d^2 pos / dt^2 (t = s T_sw, T_sw = (P - stance) delta).  With rem = 0 the
+// target is, term for term, what mpcqp_phase_advance_kernel writes at the landing.  Every other leg: pos = target = p0, vel = acc = 0.
+// Out [row, leg, (pos, vel, acc, target), 3]; every lane runs the same instructions, the cases are selects on the outputs.
+template <typename TIO>
+__global__ void __launch_bounds__(256)
+mpcqp_phase_swing_kernel(const TIO* __restrict__ actual, const TIO* __restrict__ desired, const TIO* __restrict__ feet_log,
+                         const int32_t* __restrict__ gait, const int32_t* __restrict__ tick0, const TIO* __restrict__ stand,
+                         const TIO* __restrict__ gain, const TIO* __restrict__ step_height, const double d, const int T, const int64_t B,
+                         TIO* __restrict__ swing, TIO* __restrict__ feet_des) {
+#pragma clang fp contract(off)
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= 4 * B * T) return;
+  const int l = (int)(i & 3);
+  const int64_t row = i >> 2, b = row / T;
+  const int t = (int)(row - b * T);
+  const TIO* xa = actual + row * 12;
+  const TIO* xd = desired + row * 12;
+  const PhaseRows<TIO> ph = {feet_log, gait, stand, gain};
+  // the tick of the row: tick0 + t as the advance kernel's clock sees it (a negative one is 0; the sum saturates at 2^31 - 1)
+  const int64_t tk = min(max((int64_t)tick0[b] + t, (int64_t)0), (int64_t)0x7fffffff);
+  const GaitLeg c = gait_leg(gait + b * GAIT_ROW, l);
+  const int phi = gait_phase(c, (uint32_t)tk);
+  const bool up = gait_steps(c) && phi >= c.st;
+  const int n = up ? c.P - c.st : 1;   // (a leg that is down never divides by its own count)
+  const double s = (double)(up ? phi - c.st : 0) / (double)n;
+  const double ahead = (double)(c.P - phi) * d, tsw = (double)n * d;
+  const double hh = (double)step_height[b], g = gain ? (double)gain[b] : 0.0;
+  bool fin = phase_rows_finite(ph, b) && isfinite(hh) && isfinite((double)xd[8]) && isfinite((double)xd[9]) && isfinite((double)xd[10]);
+#pragma unroll
+  for (int a = 0; a < 12; ++a) fin = fin && isfinite((double)xa[a]);
+  double p0[3], p1[3];
+#pragma unroll
+  for (int a = 0; a < 3; ++a) { p0[a] = (double)feet_log[3 * i + a]; fin = fin && isfinite(p0[a]); }
+  // the yaw exactly as mpcqp_phase_advance_kernel reads it, then carried to the touchdown
+  double q[4], sn, cs;
+  plant_rotvec_to_quat((double)xa[0], (double)xa[1], (double)xa[2], q);
+  const double yaw = atan2(2.0 * (q[1] * q[2] + q[0] * q[3]), 1.0 - 2.0 * (q[2] * q[2] + q[3] * q[3]));
+  sincos(yaw + ahead * (double)xd[8], &sn, &cs);
+  const TIO* sl = stand + b * 12 + l * 3;
+#pragma unroll
+  for (int a = 0; a < 2; ++a)
+    p1[a] = gait_foothold_xy(a, (double)xa[3 + a] + ahead * (double)xa[9 + a], cs, sn, (double)sl[0], (double)sl[1], (double)xa[9 + a],
+                             (double)xd[9 + a], gait_half_stance(c, d), g);
+  p1[2] = (double)sl[2];
+  const double s2 = s * s, u = s * (1.0 - s);
+  const double b0 = s2 * (3.0 - 2.0 * s), b1 = 6.0 * u, b2 = 6.0 - 12.0 * s;
+  const double z0 = (16.0 * hh) * (u * u), z1 = (32.0 * hh) * (u * (1.0 - 2.0 * s)), z2 = (32.0 * hh) * ((1.0 - 6.0 * s) + 6.0 * s2);
+  const double nan = __builtin_nan("");
+  double o[12];
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    const double dp = p1[a] - p0[a];
+    const double pos = a == 2 ? (p0[a] + b0 * dp) + z0 : p0[a] + b0 * dp;
+    const double vel = (a == 2 ? b1 * dp + z1 : b1 * dp) / tsw;
+    const double acc = (a == 2 ? b2 * dp + z2 : b2 * dp) / (tsw * tsw);
+    o[a] = !fin ? nan : (up ? pos : p0[a]);
+    o[3 + a] = !fin ? nan : (up ? vel : 0.0);
+    o[6 + a] = !fin ? nan : (up ? acc : 0.0);
+    o[9 + a] = !fin ? nan : (up ? p1[a] : p0[a]);
+  }
+#pragma unroll
+  for (int e = 0; e < 12; ++e) swing[12 * i + e] = (TIO)o[e];
+  if (feet_des) {
+#pragma unroll
+    for (int a = 0; a < 3; ++a) feet_des[3 * i + a] = (TIO)o[a];
+  }
+}
+
 }  // namespace

@@ -968,6 +968,26 @@ int mpcqp_swing_trajectories(mpcqp_handle h, int64_t B, int32_t K, int32_t S, co
   return launched(h, "swing trajectory kernel launch");
 }
 
+int mpcqp_phase_swing(mpcqp_handle h, int64_t B, int32_t T, const void* actual, const void* desired, const void* feet_log, const int32_t* gait,
+                      const int32_t* tick0, const void* stand, const void* gain, const void* step_height, void* swing, void* feet_des,
+                      void* stream) {
+  if (!h) return MPCQP_EINVAL;
+  if (B < 0 || B > 0x7fffffff || T < 0 || B * (int64_t)T > 0x7fffffff) return fail(h, MPCQP_EINVAL, "mpcqp_phase_swing: size out of range");
+  if (B > 0 && T > 0 && (!actual || !desired || !feet_log || !gait || !tick0 || !stand || !step_height || !swing))
+    return fail(h, MPCQP_EINVAL, "mpcqp_phase_swing: null buffer");
+  if (B == 0 || T == 0) return MPCQP_OK;
+  DeviceGuard guard(h->cfg.device);
+  if (guard.err != hipSuccess) return fail(h, MPCQP_EHIP, "hipSetDevice", guard.err);
+  const dim3 grid((unsigned)((4 * B * T + 255) / 256));
+  with_io(h, [&](auto tag) {
+    using TIO = decltype(tag);
+    hipLaunchKernelGGL((mpcqp_phase_swing_kernel<TIO>), grid, dim3(256), 0, (hipStream_t)stream, (const TIO*)actual, (const TIO*)desired,
+                       (const TIO*)feet_log, gait, tick0, (const TIO*)stand, (const TIO*)gain, (const TIO*)step_height, h->cfg.delta, (int)T, B,
+                       (TIO*)swing, (TIO*)feet_des);
+  });
+  return launched(h, "phase swing kernel launch");
+}
+
 int mpcqp_torque_map(mpcqp_handle h, int64_t B, const void* u, const void* jac, void* tau, void* stream) {
   if (!h) return MPCQP_EINVAL;
   if (B < 0 || B > 0x1fffffff) return fail(h, MPCQP_EINVAL, "mpcqp_torque_map: batch size out of range");
@@ -1105,6 +1125,28 @@ int mpcqp_joint_log(mpcqp_handle h, int64_t B, int32_t T, const void* actual, co
                        (const TIO*)feet, g, (TIO*)q, (TIO*)tau, reach, rows);
   });
   return launched(h, "joint log kernel launch");
+}
+
+int mpcqp_joint_rates(mpcqp_handle h, int64_t B, int32_t T, const void* actual, const void* forces, const void* feet, const void* foot_vel,
+                      const MpcQpLegGeometry* geo, void* q, void* qd, void* tau, void* power, uint8_t* reach, void* stream) {
+  if (!h) return MPCQP_EINVAL;
+  if (B < 0 || B > 0x7fffffff || T < 0 || B * (int64_t)T > 0x1fffffff) return fail(h, MPCQP_EINVAL, "mpcqp_joint_rates: size out of range");
+  if (!q && !qd && !tau && !power && !reach)
+    return fail(h, MPCQP_EINVAL, "mpcqp_joint_rates: no output buffer (q, qd, tau, power and reach are all null)");
+  if (B > 0 && T > 0 && (!actual || !forces || !feet)) return fail(h, MPCQP_EINVAL, "mpcqp_joint_rates: null buffer");
+  LegGeoDev g;
+  if (const int rc = leg_ik_geometry(h, "mpcqp_joint_rates", geo, g)) return rc;
+  if (B == 0 || T == 0) return MPCQP_OK;
+  DeviceGuard guard(h->cfg.device);
+  if (guard.err != hipSuccess) return fail(h, MPCQP_EHIP, "hipSetDevice", guard.err);
+  const int64_t rows = B * T;
+  const dim3 grid((unsigned)((4 * rows + 255) / 256));
+  with_io(h, [&](auto tag) {
+    using TIO = decltype(tag);
+    hipLaunchKernelGGL((mpcqp_joint_rates_kernel<TIO>), grid, dim3(256), 0, (hipStream_t)stream, (const TIO*)actual, (const TIO*)forces,
+                       (const TIO*)feet, (const TIO*)foot_vel, g, (TIO*)q, (TIO*)qd, (TIO*)tau, (TIO*)power, reach, rows);
+  });
+  return launched(h, "joint rates kernel launch");
 }
 
 int mpcqp_last_kernel_ms(mpcqp_handle h, float* ms) {

@@ -252,7 +252,8 @@ class MPCBatch:
         that touches down gets its foothold from the measured state, every other foot is untouched.  gait, stand, gain as in
         `phase_expand`; body, push, push_ticks, substeps as in `rollout_plant`.  Returns the logs of `rollout` plus "feet_log"
         [B,T,4,3] and "contact_log" uint8 [B,T,4], the feet and stance mask the plant used each tick (a swing leg's row is its lift-off
-        foot: `joint_log` on feet_log is meaningful for stance legs only)."""
+        foot: `phase_swing` turns these logs into the swing trajectories, and its "feet_des" is the operand `joint_log` and
+        `joint_rates` want).  Keep a copy of `tick` for that call: the roll-out advances it."""
         torch = _torch()
         B, T = int(x.shape[0]), int(T)
         check_operands(self.device, self._phase_rows(B, x, ref, feet, gait, tick, stand, gain, "x") + (
@@ -267,6 +268,28 @@ class MPCBatch:
                                       tick.data_ptr(), mu.data_ptr(), _ptr(body), _ptr(push), _ptr(push_ticks), substeps, _ptr(actual),
                                       _ptr(desired), _ptr(forces), _ptr(feet_log), _ptr(contact_log), solved.data_ptr(), st.cuda_stream)
         return {"actual": actual, "desired": desired, "forces": forces, "feet_log": feet_log, "contact_log": contact_log, "solved": solved}
+
+    def phase_swing(self, logs, gait, tick0, stand, gain, step_height, want_des=True, stream=None):
+        """Swing-foot trajectories of a `rollout_phase` from its logs (include/mpcqp_plan.h, mpcqp_phase_swing; the host counterpart is
+        gaits.phase_swing_host): `logs` as `rollout_phase` returns them ("actual", "desired", "feet_log"), gait / stand / gain the
+        roll-out's rows (gain may be None), tick0 int32 [B] the value `tick` had BEFORE the roll-out (a copy: the roll-out advances
+        `tick` in place), step_height [B].  Returns {"swing": [B,T,4,4,3] pos / vel / acc / target of every (robot, tick, leg),
+        "feet_des": [B,T,4,3] = pos, or None}: a swing leg runs from its lift-off foot to the foothold rule at the touchdown predicted
+        from the tick's measured state; a stance leg keeps its feet_log row with vel = acc = 0.  Asynchronous on `stream`."""
+        torch = _torch()
+        actual, desired, feet_log = logs["actual"], logs["desired"], logs["feet_log"]
+        if actual is None or actual.dim() != 3:
+            raise ValueError("phase_swing needs the logs of rollout_phase(..., log=True)")
+        B, T = int(actual.shape[0]), int(actual.shape[1])
+        check_operands(self.device, (("actual", actual, (B, T, 12), self.tdtype), ("desired", desired, (B, T, 12), self.tdtype),
+                                     ("feet_log", feet_log, (B, T, 4, 3), self.tdtype), ("gait", gait, (B, 9), torch.int32),
+                                     ("tick0", tick0, (B,), torch.int32), ("stand", stand, (B, 4, 3), self.tdtype),
+                                     ("gain", gain, (B,), self.tdtype), ("step_height", step_height, (B,), self.tdtype)), optional=("gain",))
+        st = self._stream(stream)
+        swing, des = self._alloc(stream, ((B, T, 4, 4, 3), self.tdtype), ((B, T, 4, 3), self.tdtype) if want_des else None)
+        self.engine.phase_swing_ptr(B, T, actual.data_ptr(), desired.data_ptr(), feet_log.data_ptr(), gait.data_ptr(), tick0.data_ptr(),
+                                    stand.data_ptr(), _ptr(gain), step_height.data_ptr(), swing.data_ptr(), _ptr(des), st.cuda_stream)
+        return {"swing": swing, "feet_des": des}
 
     def plan_footsteps(self, feet0, cmd, gait, S, want_ang=True, want_hip=False, stream=None):
         """Footstep plans of B robots on the device (include/mpcqp_plan.h, mpcqp_plan_footsteps; the host FootstepPlanner per robot):
@@ -358,6 +381,22 @@ class MPCBatch:
         self.engine.joint_log_ptr(B, T, actual.data_ptr(), forces.data_ptr(), feet.data_ptr(), q.data_ptr(), tau.data_ptr(), reach.data_ptr(),
                                   geometry, st.cuda_stream)
         return {"q": q, "tau": tau, "reach": reach}
+
+    def joint_rates(self, actual, forces, feet, foot_vel=None, geometry=None, stream=None):
+        """`joint_log` plus joint rates and joint power (include/mpcqp_joints.h, mpcqp_joint_rates; the host counterpart is
+        lite3_model.joint_rates_host): foot_vel [B,T,4,3] the feet's world velocities -- `phase_swing(...)["swing"][:, :, :, 1]`, made
+        contiguous -- or None for feet at rest in the world -> {"q", "qd" [B,T,4,3] rad / s, "tau", "power" [B,T,4] = tau . qd per leg
+        in W, "reach"}; q, tau and reach are `joint_log`'s, bit for bit.  Out of reach: qd = power = 0.  Asynchronous on `stream`."""
+        B, T = int(actual.shape[0]), int(actual.shape[1]) if actual.dim() == 3 else -1
+        check_operands(self.device, (("actual", actual, (B, T, 12), self.tdtype), ("forces", forces, (B, T, 12), self.tdtype),
+                                     ("feet", feet, (B, T, 4, 3), self.tdtype), ("foot_vel", foot_vel, (B, T, 4, 3), self.tdtype)),
+                       optional=("foot_vel",))
+        st = self._stream(stream)
+        legs = ((B, T, 4, 3), self.tdtype)
+        q, qd, tau, power, reach = self._alloc(stream, legs, legs, legs, ((B, T, 4), self.tdtype), ((B, T, 4), _torch().uint8))
+        self.engine.joint_rates_ptr(B, T, actual.data_ptr(), forces.data_ptr(), feet.data_ptr(), _ptr(foot_vel), q.data_ptr(), qd.data_ptr(),
+                                    tau.data_ptr(), power.data_ptr(), reach.data_ptr(), geometry, st.cuda_stream)
+        return {"q": q, "qd": qd, "tau": tau, "power": power, "reach": reach}
 
     def last_kernel_ms(self):
         return self.engine.last_kernel_ms()

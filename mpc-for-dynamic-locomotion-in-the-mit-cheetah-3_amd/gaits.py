@@ -1,5 +1,5 @@
-"""Host counterpart of the per-leg periodic gaits (include/mpcqp_plan.h: mpcqp_phase_expand, mpcqp_solve_batch_phase;
-include/mpcqp_sim.h: mpcqp_rollout_phase): numpy fp64, vectorised over robots, in the device's operation order
+"""Host counterpart of the per-leg periodic gaits (include/mpcqp_plan.h: mpcqp_phase_expand, mpcqp_solve_batch_phase,
+mpcqp_phase_swing; include/mpcqp_sim.h: mpcqp_rollout_phase): numpy fp64, vectorised over robots, in the device's operation order
 (csrc/mpcqp_gaits.h) so that the two agree to rounding.
 
 The clock.  A gait row is ``(P, offset[4], stance[4])`` in ticks, legs FL, FR, HL, HR.  Leg l is in stance at tick t >= 0 when
@@ -203,6 +203,75 @@ def rollout_phase_host(oracle_engine, x, ref, feet, gait, stand, gain, tick, mu,
             feet = np.where(td[:, :, None], p, feet)
     return {"x": x, "ref": ref, "tick": tick, "feet": feet, "actual": actual, "desired": desired, "forces": forces, "solved": solved,
             "feet_log": feet_log, "contact_log": contact_log}
+
+
+def swing_target(actual, desired, gait, stand, gain, rem, delta):
+    """The target of a swing (mpcqp_phase_swing): the foothold rule at the touchdown predicted `rem` [...,4] ticks ahead of the log
+    rows actual, desired [...,12] of robots [B,...] -- CoM and yaw carried (rem delta) ahead at the measured velocity and the reference
+    yaw rate desired[8], v measured, v_ref = desired[9..11] -> p1 [...,4,3].  With rem = 0 it is `touchdown_foothold` at the row."""
+    actual, desired, stand = _f64(actual), _f64(desired), _f64(stand)
+    B = stand.shape[0]
+    lead = actual.shape[1:-1]
+    ex = (slice(None),) + (None,) * len(lead)
+    gainv = (np.zeros(B) if gain is None else _f64(gain).reshape(B))[ex + (None,)]
+    _, _, st = clamp_gait(gait)
+    half_ts = (0.5 * (st.astype(np.float64) * float(delta)))[ex]                              # [B,...,4]
+    ahead = _f64(rem) * float(delta)                                                          # [B,...,4]
+    sx, sy = stand[ex + (slice(None), 0)], stand[ex + (slice(None), 1)]
+    p = np.empty(actual.shape[:-1] + (4, 3))
+    with np.errstate(invalid="ignore", over="ignore"):
+        psi = measured_yaw(actual[..., 0:3])[..., None] + ahead * desired[..., None, 8]
+        cs, sn = np.cos(psi), np.sin(psi)
+        rot = [cs * sx - sn * sy, sn * sx + cs * sy]
+        for a in range(2):
+            c = actual[..., None, 3 + a] + ahead * actual[..., None, 9 + a]
+            v, vr = actual[..., None, 9 + a], desired[..., None, 9 + a]
+            p[..., a] = ((c + rot[a]) + half_ts * vr) + gainv * (v - vr)
+    p[..., 2] = np.broadcast_to(stand[ex + (slice(None), 2)], p.shape[:-1])
+    return p
+
+
+def swing_profile(s, p0, p1, step_height, t_swing):
+    """The swing curve of mpcqp_phase_swing at s [...] in [0, 1] between p0 and a frozen p1 [...,3], apex step_height [...], swing
+    time t_swing [...]: pos = p0 + b(s) (p1 - p0) + z_b(s) e_z with b = 3 s^2 - 2 s^3 and z_b = 16 H s^2 (1 - s)^2, and its first and
+    second time derivatives -> (pos, vel, acc) [...,3]."""
+    s, p0, p1, hh, tsw = _f64(s), _f64(p0), _f64(p1), _f64(step_height), _f64(t_swing)
+    with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+        s2, u = s * s, s * (1.0 - s)
+        b0, b1, b2 = s2 * (3.0 - 2.0 * s), 6.0 * u, 6.0 - 12.0 * s
+        z0, z1, z2 = (16.0 * hh) * (u * u), (32.0 * hh) * (u * (1.0 - 2.0 * s)), (32.0 * hh) * ((1.0 - 6.0 * s) + 6.0 * s2)
+        dp = p1 - p0
+        pos, vel, acc = p0 + b0[..., None] * dp, b1[..., None] * dp, b2[..., None] * dp
+        pos[..., 2] = pos[..., 2] + z0
+        vel[..., 2] = vel[..., 2] + z1
+        acc[..., 2] = acc[..., 2] + z2
+        return pos, vel / tsw[..., None], acc / (tsw * tsw)[..., None]
+
+
+def phase_swing_host(actual, desired, feet_log, gait, tick0, stand, gain, step_height, delta=0.03):
+    """mpcqp_phase_swing on the host, from the logs of a roll-out on a gait clock: actual, desired [B,T,12], feet_log [B,T,4,3], gait
+    [B,9], tick0 [B] the tick BEFORE the roll-out, stand [B,4,3], gain [B] or None, step_height [B] -> {"swing": [B,T,4,4,3] (pos,
+    vel, acc, target), "feet_des": [B,T,4,3] = pos}.  A swing leg runs from its lift-off foot feet_log[b,t,l] to `swing_target` at
+    rem = P - phi along `swing_profile` at s = (phi - stance) / (P - stance); every other leg keeps its feet_log row, vel = acc = 0."""
+    actual, desired, feet_log, stand, hh = _f64(actual), _f64(desired), _f64(feet_log), _f64(stand), _f64(step_height)
+    B, T = actual.shape[:2]
+    hh = hh.reshape(B)
+    gainv = np.zeros(B) if gain is None else _f64(gain).reshape(B)
+    P, _, st = clamp_gait(gait)
+    tick = np.minimum(np.maximum(np.asarray(tick0).astype(np.int64).reshape(B, 1) + np.arange(T)[None, :], 0), 2 ** 31 - 1)
+    phi = phase(gait, tick)                                                                   # [B,T,4]
+    up = ((st > 0) & (st < P[:, None]))[:, None, :] & (phi >= st[:, None, :])
+    n = np.where(up, P[:, None, None] - st[:, None, :], 1)
+    s = np.where(up, phi - st[:, None, :], 0).astype(np.float64) / n.astype(np.float64)
+    p1 = swing_target(actual, desired, gait, stand, gain, P[:, None, None] - phi, delta)
+    pos, vel, acc = swing_profile(s, feet_log, p1, hh[:, None, None], n.astype(np.float64) * float(delta))
+    m = up[..., None]
+    out = np.stack([np.where(m, pos, feet_log), np.where(m, vel, 0.0), np.where(m, acc, 0.0), np.where(m, p1, feet_log)], axis=3)
+    fin = (np.isfinite(stand).all(axis=(1, 2)) & np.isfinite(gainv) & np.isfinite(hh))[:, None, None]
+    fin = fin & (np.isfinite(actual).all(axis=2) & np.isfinite(desired[:, :, 8:11]).all(axis=2))[:, :, None]
+    fin = fin & np.isfinite(feet_log).all(axis=3)
+    out = np.where(fin[..., None, None], out, np.nan)
+    return {"swing": out, "feet_des": out[:, :, :, 0].copy()}
 
 
 def make_phase_batch(B, names=("trot", "bound"), period=12, seed=20251018, mus=(0.5, 0.7, 1.0), v_ref=(0.18, 0.0, 0.0), theta_dot=0.0,

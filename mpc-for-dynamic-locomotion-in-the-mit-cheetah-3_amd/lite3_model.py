@@ -107,6 +107,41 @@ def joint_log_host(actual, forces, feet):
     return q, tau, reach
 
 
+def joint_rates_host(actual, forces, feet, foot_vel=None):
+    """`joint_log_host` plus joint rates and power (the host counterpart of mpcqp_joint_rates, include/mpcqp_joints.h): foot_vel
+    [B,T,4,3] world foot velocities, None = feet at rest in the world -> (q, qd [B,T,4,3], tau, power [B,T,4], reach).  The foot
+    moves with foot_vel = v + omega x (foot - CoM) + R J(q) qd, so qd = J^-1 R^T (foot_vel - v - omega x (foot - CoM)), by adjugate and
+    determinant in the device's order; power = sum_j tau_j qd_j.  Out of reach or det J = 0: qd = power = 0; non-finite: NaN."""
+    from scipy.spatial.transform import Rotation
+    q, tau, reach = joint_log_host(actual, forces, feet)
+    actual, feet = np.asarray(actual, dtype=float), np.asarray(feet, dtype=float)
+    B, T = actual.shape[:2]
+    fv = np.zeros((B, T, 4, 3)) if foot_vel is None else np.asarray(foot_vel, dtype=float)
+    R = Rotation.from_rotvec(actual[..., :3].reshape(-1, 3)).as_matrix().reshape(B, T, 3, 3)
+    pw = feet - actual[:, :, None, 3:6]
+    with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+        vrel = (fv - actual[:, :, None, 9:12]) - np.cross(actual[:, :, None, 6:9], pw)
+        h = np.einsum("btji,btlj->btli", R, vrel)
+        J = np.full((B, T, 4, 3, 3), np.nan)
+        for b in range(B):
+            for t in range(T):
+                for l in range(4):
+                    if np.isfinite(q[b, t, l]).all():
+                        J[b, t, l] = leg_fk_jac(l, q[b, t, l])[1]
+        j = [J[..., a // 3, a % 3] for a in range(9)]
+        c = [[j[4] * j[8] - j[5] * j[7], j[5] * j[6] - j[3] * j[8], j[3] * j[7] - j[4] * j[6]],
+             [j[2] * j[7] - j[1] * j[8], j[0] * j[8] - j[2] * j[6], j[1] * j[6] - j[0] * j[7]],
+             [j[1] * j[5] - j[2] * j[4], j[2] * j[3] - j[0] * j[5], j[0] * j[4] - j[1] * j[3]]]
+        det = j[0] * c[0][0] + j[1] * c[0][1] + j[2] * c[0][2]
+        qd = np.stack([(c[0][k] * h[..., 0] + c[1][k] * h[..., 1] + c[2][k] * h[..., 2]) / det for k in range(3)], axis=-1)
+        move = (reach != 0) & (det != 0.0)
+        fin = np.isfinite(q).all(axis=-1) & np.isfinite(vrel).all(axis=-1)
+        qd = np.where(fin[..., None], np.where(move[..., None], qd, 0.0), np.nan)
+        power = (tau[..., 0] * qd[..., 0] + tau[..., 1] * qd[..., 1]) + tau[..., 2] * qd[..., 2]
+        power = np.where(fin, np.where(move, power, 0.0), np.nan)
+    return q, qd, tau, power, reach
+
+
 def world_jacobians(R_body, q_all):
     """{leg: 3x3 world-frame linear Jacobian block} for joint angles q_all[4,3] (src/main.py:205-210)."""
     return {LEGS[k]: R_body @ leg_fk_jac(k, q_all[k])[1] for k in range(4)}
