@@ -52,7 +52,8 @@ struct mpcqp_engine {
   double* wr_K = nullptr;     // wrench-space engine (mpcqp_wrench.h): K_q [6][N][N], K_q^-1 [6][N][N] (fp32 / fp64)
   float* wr_kinv32 = nullptr;
   double* wr_kinv64 = nullptr;
-  float* wr_klane32 = nullptr;   // ... and K^-1 in lane order [NT][16]: the entries of each lane's 8 x 8 tile (w_tile_init)
+  float* wr_klane32 = nullptr;   // ... and K^-1 in lane order [NT][16]: the entries of each lane's 8 x 8 tile (w_tile_init); horizon 10: each
+                                 // followed by the lane records [NT][16 values | 8 row words] of w_kq_rows_load (mpcqp_rowtab.h)
   double* wr_klane64 = nullptr;
   void* roll_mem = nullptr;   // roll-out: u [B,N,12], X [B,N+1,13], status / iters [B] of the current tick
   int64_t roll_cap = 0;
@@ -458,7 +459,14 @@ static int build_wrench_tables(mpcqp_engine* e) {
   constexpr int NLANE = 16 * WG<N>::NT;
   double* Kl = new (std::nothrow) double[NLANE];
   float* Kl32 = new (std::nothrow) float[NLANE];
-  int rc = tab && K && Ki && Ki32 && Kl && Kl32 ? MPCQP_OK : MPCQP_ENOMEM;
+  // The device images of the two lane tables: [NT][16] values and, at horizon 10 (whose MIXED kernels read them), one record per lane
+  // behind them -- the same sixteen values and the lane's eight row words of the tile build (mpcqp_rowtab.h)
+  constexpr int NREC = N == 10 ? WG<N>::NT : 0;
+  constexpr size_t L32 = sizeof(float) * NLANE + NREC * mpcqp_rowtab::record_bytes<float>();
+  constexpr size_t L64 = sizeof(double) * NLANE + NREC * mpcqp_rowtab::record_bytes<double>();
+  unsigned* rows = new (std::nothrow) unsigned[mpcqp_rowtab::ROW_WORDS * WG<N>::NT];
+  unsigned char* img = new (std::nothrow) unsigned char[L32 + L64];
+  int rc = tab && K && Ki && Ki32 && Kl && Kl32 && rows && img ? MPCQP_OK : MPCQP_ENOMEM;
   if (rc == MPCQP_OK) {
     const double dl = c.delta, th = e->dev.theta;
     for (int a = 0; a < N; ++a)
@@ -474,6 +482,7 @@ static int build_wrench_tables(mpcqp_engine* e) {
     for (int i = 0; i < N * N; ++i) K[q * N * N + i] = 2.0 * (c.w[q] * tab[N * N + i] + c.w[6 + q] * tab[i]);
     if (!invert_small(N, K + q * N * N, Ki + q * N * N)) rc = MPCQP_EINVAL;
   }
+  if (rc == MPCQP_OK && NREC > 0 && !mpcqp_rowtab::lane_order_rows(N, WG<N>::G, rows)) rc = MPCQP_EINVAL;   // (a rule of N alone: holds for N = 10)
   if (rc == MPCQP_OK) {
     for (int i = 0; i < 6 * N * N; ++i) Ki32[i] = (float)Ki[i];
     lane_order_kinv<N>(Ki, Kl);
@@ -484,13 +493,19 @@ static int build_wrench_tables(mpcqp_engine* e) {
     if (he == hipSuccess) he = hipMemcpy(e->wr_kinv32, Ki32, sizeof(float) * 6 * N * N, hipMemcpyHostToDevice);
     if (he == hipSuccess) he = hipMalloc((void**)&e->wr_kinv64, sizeof(double) * 6 * N * N);
     if (he == hipSuccess) he = hipMemcpy(e->wr_kinv64, Ki, sizeof(double) * 6 * N * N, hipMemcpyHostToDevice);
-    if (he == hipSuccess) he = hipMalloc((void**)&e->wr_klane32, sizeof(float) * NLANE);
-    if (he == hipSuccess) he = hipMemcpy(e->wr_klane32, Kl32, sizeof(float) * NLANE, hipMemcpyHostToDevice);
-    if (he == hipSuccess) he = hipMalloc((void**)&e->wr_klane64, sizeof(double) * NLANE);
-    if (he == hipSuccess) he = hipMemcpy(e->wr_klane64, Kl, sizeof(double) * NLANE, hipMemcpyHostToDevice);
+    memcpy(img, Kl32, sizeof(float) * NLANE);
+    memcpy(img + L32, Kl, sizeof(double) * NLANE);
+    if (NREC > 0) {
+      mpcqp_rowtab::pack_records<float>(NREC, Kl32, rows, img + sizeof(float) * NLANE);
+      mpcqp_rowtab::pack_records<double>(NREC, Kl, rows, img + L32 + sizeof(double) * NLANE);
+    }
+    if (he == hipSuccess) he = hipMalloc((void**)&e->wr_klane32, L32);
+    if (he == hipSuccess) he = hipMemcpy(e->wr_klane32, img, L32, hipMemcpyHostToDevice);
+    if (he == hipSuccess) he = hipMalloc((void**)&e->wr_klane64, L64);
+    if (he == hipSuccess) he = hipMemcpy(e->wr_klane64, img + L32, L64, hipMemcpyHostToDevice);
     if (he != hipSuccess) { (void)hipGetLastError(); rc = MPCQP_ENOMEM; }
   }
-  delete[] tab; delete[] K; delete[] Ki; delete[] Ki32; delete[] Kl; delete[] Kl32;
+  delete[] tab; delete[] K; delete[] Ki; delete[] Ki32; delete[] Kl; delete[] Kl32; delete[] rows; delete[] img;
   return rc;
 }
 

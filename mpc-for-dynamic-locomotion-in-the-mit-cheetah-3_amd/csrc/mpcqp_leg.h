@@ -73,6 +73,43 @@ __device__ __forceinline__ T rs8(const T (&v)[8], int gc) {
   return keep + dpp_mov<0xB1>(send);
 }
 
+// The same reduce-scatter with the first step's keep / send selects done by the write mask of the DPP add (fp32; the 8 lanes of a
+// group are the 8 consecutive lanes 8 gr + gc of a wave: one wave per QP at horizon 10).  In that step a lane with gc & 4 clear adds
+// its own v[m] to its partner's v[m] (the partner, lane 7 - gc of the group, has the bit set and sends v[m]); a lane with the bit
+// set does the same with v[4 + m].  The lanes with the bit clear are DPP banks 0 and 2 of every row of 16 (bank = 2 (gr & 1) +
+// (gc >> 2)), so two adds into one destination -- `v[m] + v[m]'` under bank_mask 0x5, `v[4 + m] + v[4 + m]'` under 0xa, lanes outside
+// the mask keep the destination -- give every lane the sum the select form gives it, with the operands swapped; an IEEE add commutes
+// bit for bit (two NaNs of different payloads aside: tools/rs8_forms.hip compares the words of the two forms, tests/test_rs8_forms.py).
+// Eight instructions for twelve, and the mask of bit 2 is never formed.  The later steps pair lanes inside a quad, where no bank mask
+// separates them: they are rs8's.  (A write mask cannot be said through __builtin_amdgcn_update_dpp and an add -- the DPP combine
+// folds full masks only -- hence the asm; its DPP sources may have been written by the instruction just before, which needs two
+// wait states that the compiler does not count for an asm: the s_nop.  The destinations are written in full by the two adds and
+// first read by a select, not by a DPP operand.)  fp64 keeps the selects: a masked 64-bit value is three moves per word.
+// Preconditions of the block, which the hazard recognizer cannot check inside an asm and the caller has to keep (w_matvec in w_solve:
+// "all lanes call", uniform control flow around it):  no VALU instruction writes EXEC within five wait states before it (a DPP
+// instruction after a VALU write of EXEC needs them);  all 64 lanes are active -- without bound_ctrl a source lane that is switched
+// off leaves its partner's destination unwritten, and the "=&v" destinations have no defined value to fall back to.
+__device__ __forceinline__ float rs8_banked(const float (&v)[8], int gc) {
+  const bool b1 = (gc & 2) != 0, b0 = (gc & 1) != 0;
+  float t[4];
+  asm("s_nop 1\n\t"
+      "v_add_f32_dpp %0, %4, %4 row_half_mirror row_mask:0xf bank_mask:0x5\n\t"
+      "v_add_f32_dpp %1, %5, %5 row_half_mirror row_mask:0xf bank_mask:0x5\n\t"
+      "v_add_f32_dpp %2, %6, %6 row_half_mirror row_mask:0xf bank_mask:0x5\n\t"
+      "v_add_f32_dpp %3, %7, %7 row_half_mirror row_mask:0xf bank_mask:0x5\n\t"
+      "v_add_f32_dpp %0, %8, %8 row_half_mirror row_mask:0xf bank_mask:0xa\n\t"
+      "v_add_f32_dpp %1, %9, %9 row_half_mirror row_mask:0xf bank_mask:0xa\n\t"
+      "v_add_f32_dpp %2, %10, %10 row_half_mirror row_mask:0xf bank_mask:0xa\n\t"
+      "v_add_f32_dpp %3, %11, %11 row_half_mirror row_mask:0xf bank_mask:0xa"
+      : "=&v"(t[0]), "=&v"(t[1]), "=&v"(t[2]), "=&v"(t[3])
+      : "v"(v[0]), "v"(v[1]), "v"(v[2]), "v"(v[3]), "v"(v[4]), "v"(v[5]), "v"(v[6]), "v"(v[7]));
+  float s2[2];
+#pragma unroll
+  for (int m = 0; m < 2; ++m) { const float keep = b1 ? t[2 + m] : t[m], send = b1 ? t[m] : t[2 + m]; s2[m] = keep + dpp_mov<0x4E>(send); }
+  const float keep = b0 ? s2[1] : s2[0], send = b0 ? s2[0] : s2[1];
+  return keep + dpp_mov<0xB1>(send);
+}
+
 __device__ __forceinline__ float w_rcp(float x) { return __builtin_amdgcn_rcpf(x); }
 __device__ __forceinline__ double w_rcp(double x) {
   double r = __builtin_amdgcn_rcp(x);

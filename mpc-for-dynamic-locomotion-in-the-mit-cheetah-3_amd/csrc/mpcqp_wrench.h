@@ -19,6 +19,7 @@
 // The polish therefore builds and sweeps its S in fp64 (v_fma_f64 issues at the unpacked fp32 rate on gfx950): the
 // solve is then exact to ~1e-9 and no iterative refinement is needed (one solve + two gradients per step).
 #pragma once
+#include "mpcqp_rowtab.h"   // the word layout of the tile build's row table
 #include "mpcqp_leg.h"   // lane helpers, leg-stage structs, Anderson step, residuals / right-hand side / projection; through it mpcqp_common.h (FastIn, OrderBuf, the dispatch-order pre-pass, policy constants)
 
 namespace {
@@ -39,7 +40,7 @@ struct WrTabs {
   const float* kinv32;    // [6][N][N]   K_q^-1: no kernel reads these two any more (the symmetric-sweep experiment did); they stay
   const double* kinv64;   // [6][N][N]   because dropping them moves the kernel arguments, i.e. changes every wrench kernel's code
   const float* klane32;   // [NT][16]    K^-1 in lane order: what w_tile_init places in lane t's tile (v0[8] | v1[8])
-  const double* klane64;  // [NT][16]
+  const double* klane64;  // [NT][16]    (horizon 10: each of the two is followed by the lane records of w_kq_rows_load, [NT][16 values | 8 row words])
 };
 
 template <typename TV, int N>
@@ -249,9 +250,72 @@ __device__ __forceinline__ void w_tile_init(WTile<TM>& t, const WKq<TM>& kq, con
   }
 }
 
+// The same tile from the lane's row words (mpcqp_rowtab.h; W_TRIM_ROWTAB): everything w_tile_init computes per row
+// from the lane and the row alone -- R, R / 6, h, base, the pair bits, the two quad addresses and their fallback to E[0] -- is one
+// word, of which a bit-field extract gives a quad's byte offset into E and a signed one-bit extract each pair's mask.  The K^-1
+// placement and the element operation are w_tile_init's: kinv + e, or kinv + 0 with the masked slot ANDed away, never multiplied.
+// (the run masks in their vector form, VM of w_tile_init: the kernels that read the table are those that build with VM)
+struct WRows { unsigned w[8]; };
+
+// The lane's sixteen K^-1 values and its eight row words from ONE record per lane (six / ten b128 loads off one address), issued
+// where w_kq_load issues its loads; nothing waits for them before the build.  The records follow the [NT][16] table of the element
+// type at hand in the same allocation (build_wrench_tables files them behind klane32 and behind klane64; the values are the same
+// words as the table's).  A table pointer of their own for the row words -- the slot of WrTabs that no kernel reads -- is one more
+// scalar register pair that lives through the whole kernel: the MIXED horizon-10 kernels then spill two more scalar registers
+// (75 -> 77, hipcc's report); the words as a block of their own behind the table, a second address: two spilled vector registers.
+template <typename TM, int N>
+__device__ __forceinline__ void w_kq_rows_load(WKq<TM>& k, WRows& rw, const TM* __restrict__ klane, int tid) {
+  using namespace mpcqp_rowtab;   // the record layout: record_bytes / record_words_at, the one pack_records writes on the host
+  static_assert(LANE_VALUES == 16 && ROW_WORDS == 8, "v0[8] | v1[8] and WRows::w[8]");
+  const char* rec = reinterpret_cast<const char*>(klane + LANE_VALUES * WG<N>::NT) + record_bytes<TM>() * tid;
+  ld8<TM>(reinterpret_cast<const TM*>(rec), k.v0);
+  ld8<TM>(reinterpret_cast<const TM*>(rec) + 8, k.v1);
+  const uint4 a = reinterpret_cast<const uint4*>(rec + record_words_at<TM>())[0], b = reinterpret_cast<const uint4*>(rec + record_words_at<TM>())[1];
+  rw.w[0] = a.x; rw.w[1] = a.y; rw.w[2] = a.z; rw.w[3] = a.w; rw.w[4] = b.x; rw.w[5] = b.y; rw.w[6] = b.z; rw.w[7] = b.w;
+}
+
+template <typename TM, int N>
+__device__ __forceinline__ void w_tile_init_rows(WTile<TM>& t, const WKq<TM>& kq, const WRows& rw, const TM* __restrict__ E, int gr, int gc) {
+  constexpr int G = WG<N>::G;
+  using namespace mpcqp_rowtab;
+  asm volatile("" : "+v"(gr), "+v"(gc));   // (opaque, as in w_tile_init)
+  const unsigned cls = (unsigned)(gr - gc + 3 * G) % 3u;
+  const bool kc[3] = {cls == 0u, cls == 1u, cls == 2u};
+#pragma unroll
+  for (int r = 0; r < 8; ++r) {
+    TM kv[8];   // the row of K^-1, placed by the lane's class as in w_tile_init
+#pragma unroll
+    for (int c = 0; c < 8; ++c) {
+      TM v = (TM)0;
+#pragma unroll
+      for (int k = 0; k < 3; ++k) {
+        const int c0 = (r + 2 * k) % 6;
+        if (c == c0) v = kc[k] ? kq.v0[r] : v;
+        else if (c == c0 + 6) v = kc[k] ? kq.v1[r] : v;
+      }
+      kv[c] = v;
+    }
+    const unsigned w = rw.w[r];
+#pragma unroll
+    for (int hq = 0; hq < 2; ++hq) {
+      // byte offset of the quad: the field holds 8 x the element offset -- as it is for fp64, without its lowest bit for fp32
+      const unsigned off = sizeof(TM) == 4 ? __builtin_amdgcn_ubfe(w, QUAD_STEP * hq + 1, PAIR_BIT - 1) : __builtin_amdgcn_ubfe(w, QUAD_STEP * hq, PAIR_BIT);
+      TM e[4];
+      ld4(reinterpret_cast<const TM*>(reinterpret_cast<const char*>(E) + off), e);
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int c = 4 * hq + i;
+        tset(t, r, c, kv[c] + wmasked(e[i], __builtin_amdgcn_sbfe((int)w, PAIR_BIT + 2 * hq + (i >> 1), 1)));
+      }
+    }
+  }
+}
+
 // In-register symmetric sweep of all NQ pivots: tile <- -S^-1.  Lanes of grid row og publish pivot row k = 8 og + rr; by
 // symmetry the same vector serves as the pivot column.  One LDS broadcast per pivot; no barrier when the QP is one wave.
-template <typename TM, int N>
+// PKMUL (fp32; W_TRIM_PKMUL): the scaled pivot row p * vr as four packed multiplies on the register pairs the b128 loads deliver --
+// the same two IEEE products per instruction as the eight scalar multiplies; rank1 and the column selects take the halves.
+template <typename TM, int N, bool PKMUL = false>
 __device__ __forceinline__ void w_sweep(WTile<TM>& t, TM* __restrict__ piv, int gr, int gc) {
   constexpr int NW = WG<N>::NW, DP = WG<N>::DP, G = WG<N>::G;
   int step = 0;
@@ -274,7 +338,15 @@ __device__ __forceinline__ void w_sweep(WTile<TM>& t, TM* __restrict__ piv, int 
       const bool prow = gr == og, pcol = gc == og;
       TM m[8];
 #pragma unroll
-      for (int i = 0; i < 8; ++i) { vr[i] *= p; m[i] = vr[i]; }
+      for (int i = 0; i < 8; ++i) {
+        if constexpr (PKMUL) {
+          static_assert(sizeof(TM) == 4, "packed multiplies are fp32");
+          if (i % 2 == 0) { const f2 s = mk2(vr[i], vr[i + 1]) * splat2(p); vr[i] = s.x; vr[i + 1] = s.y; }
+        } else {
+          vr[i] *= p;
+        }
+        m[i] = vr[i];
+      }
       // the owner's pivot row becomes p * row: its tile row IS the published row, so the multiplier 1 - p does it
       // (the same trick on the pivot column -- multiplier 1 / p - 1 on the published pivot element -- costs eps / p relative on
       //  the column entries, which the alpha = 1e-4 polish systems do not survive: measured, tests/test_gpu_parity.py)
@@ -298,7 +370,8 @@ __device__ __forceinline__ void w_sweep(WTile<TM>& t, TM* __restrict__ piv, int 
 // y = S^-1 x for x in LDS (bv, padded layout): returns element 8 gr + gc (valid on lanes gc < 8) and writes it to cv.
 // NEGATE = false: writes -y, the sum as the tile (-S^-1) gives it, and leaves the sign to the reader -- w_solve's pinned form, where the
 // six values are operands of multiplications and FMAs that take the sign as a source modifier (one v_xor per iteration less).
-template <typename TM, int N, bool NEGATE = true>
+// BANKED: the reduce-scatter with its first step on DPP write masks (mpcqp_leg.h: rs8_banked; W_TRIM below).
+template <typename TM, int N, bool NEGATE = true, bool BANKED = false>
 __device__ __forceinline__ void w_matvec(const WTile<TM>& t, const TM* __restrict__ bv, TM* __restrict__ cv, int gr, int gc) {
   constexpr int G = WG<N>::G;
   TM x[8], acc[8];
@@ -308,7 +381,14 @@ __device__ __forceinline__ void w_matvec(const WTile<TM>& t, const TM* __restric
 #pragma unroll
     for (int i = 0; i < 8; ++i) acc[i] += dpp_mov<0x140>(acc[i]);   // row_mirror: both halves of the 16 now hold the pair sums
   }
-  const TM sum = rs8<TM>(acc, gc & 7), tot = NEGATE ? -sum : sum;   // tile = -S^-1
+  TM sum;
+  if constexpr (BANKED) {
+    static_assert(G == 8 && sizeof(TM) == 4, "rs8_banked: lane = 8 gr + gc of one wave, fp32");
+    sum = rs8_banked(acc, gc & 7);
+  } else {
+    sum = rs8<TM>(acc, gc & 7);
+  }
+  const TM tot = NEGATE ? -sum : sum;   // tile = -S^-1
   if (gc < 8) cv[8 * gr + gc] = tot;
 }
 
@@ -323,6 +403,15 @@ template <int N, bool MIXED> constexpr bool W_LEGMAP = N == 10 && MIXED;
 // and one wave's.  The others keep fmin(fmax()) -- fp64 has no such pair of forms to choose from, and the horizon-20 MIXED kernels' allocation
 // is not touched for a loop that is not where their time goes.
 template <int N, bool MIXED> constexpr bool W_MED3 = N == 10 && MIXED;
+// Which instantiations reach their arithmetic with fewer non-arithmetic instructions -- the same four again; no operand and no order
+// of a sum differs (tests/test_gpu_trim_identity.py), every other kernel is compiled as before (tools/isa_compare.py):
+//   W_TRIM_RS8     the mat-vec's reduce-scatter with its first step on DPP write masks (mpcqp_leg.h: rs8_banked), in w_solve's pinned form
+//   W_TRIM_PKMUL   the fp32 sweep scales the pivot row with four packed multiplies, not eight scalar ones (w_sweep)
+//   W_TRIM_ROWTAB  the tile builds (the fp32 iteration tile and the fp64 polish tile of these kernels) take each row's quad offsets
+//                  into E and its pair-in-run bits from a lane-order table, not from index arithmetic (w_tile_init, mpcqp_rowtab.h)
+template <int N, bool MIXED> constexpr bool W_TRIM_RS8 = N == 10 && MIXED;
+template <int N, bool MIXED> constexpr bool W_TRIM_PKMUL = N == 10 && MIXED;
+template <int N, bool MIXED> constexpr bool W_TRIM_ROWTAB = N == 10 && MIXED;
 
 // E_j = sum_legs A diag(dinv) A' -> LDS (full 6 x 6 per stage).  Leg lanes; ends with a sync.  LS: LegMapAdmm / LegMapPolish
 // (mpcqp_legmap.h): an entry that is zero by the map's structure is written as +0 without a quad sum.
@@ -394,7 +483,7 @@ __device__ __forceinline__ void w_solve(const WTile<TM>& t, const LS& L, const T
     if (tid < NL) { TM* d = bv + 6 * (tid >> 2) + 2 * l; d[0] = v0; d[1] = v1; }
   }
   wsync<NW>();
-  w_matvec<TM, N, !QUAD_PIN>(t, bv, cv, gr, gc);
+  w_matvec<TM, N, !QUAD_PIN, QUAD_PIN && W_TRIM_RS8<N, sizeof(TM) == 4>>(t, bv, cv, gr, gc);
   wsync<NW>();
   const TM* cj = cv + 6 * (min(tid, NL - 1) >> 2);
   TM c6[6];
@@ -816,6 +905,7 @@ __device__ __forceinline__ void w_admm(SmemW<TV, N>& s, const DevCfg& cfg, const
   constexpr bool LM = W_LEGMAP<N, sizeof(TM) == 4>;   // structured leg maps, or the dense form
   static_assert(!LM || (NW == 1 && sizeof(TM) == 4), "w_solve's pinned quad sums are written for one wave and fp32");
   constexpr bool MED3 = W_MED3<N, sizeof(TM) == 4>;   // the row projections as medians (leg_clip), or as fmin(fmax())
+  constexpr bool ROWTAB = W_TRIM_ROWTAB<N, sizeof(TM) == 4>;   // the tile build from the lane's row words, or from index arithmetic
   // Element type of the sweep that inverts S.  Horizon 20: fp64 even when the iterations run on an fp32 tile -- the fp32 sweep of
   // the 120 x 120 system leaves the ADMM iterate ~5e-4 off (10 x the horizon-10 figure) and the active set of 0.2 - 0.8 % of the
   // low-friction QPs never settles; rounding the fp64 inverse to fp32 costs 13 % and leaves 1 - 3 of 4096 (tools/adapt_sweep.py).
@@ -838,9 +928,11 @@ __device__ __forceinline__ void w_admm(SmemW<TV, N>& s, const DevCfg& cfg, const
   STAMP_INIT
   for (;;) {
     WKq<TS> kq;
+    WRows rw;   // (ROWTAB only)
     {   // ---- phase A: E = sum_legs A diag(dinv) A' (behind the loads of the lane's K^-1 entries)
       const int tid = fresh_tid<NW>(tid0), L = min(tid, NL - 1);
-      w_kq_load<TS>(kq, w_klane<TS>(tabs), tid);
+      if constexpr (ROWTAB) w_kq_rows_load<TS, N>(kq, rw, w_klane<TS>(tabs), tid);
+      else w_kq_load<TS>(kq, w_klane<TS>(tabs), tid);
       typename LegMapPick<LM, LegMapAdmm<TS>, TS>::type Ls;
       w_admm_sys<TV, TS, N>(s, cfg, L, rho, Ls);
       w_build_E<TS, N>(Ls, reinterpret_cast<TS*>(s.E), tid);
@@ -849,10 +941,15 @@ __device__ __forceinline__ void w_admm(SmemW<TV, N>& s, const DevCfg& cfg, const
     WTile<TM> tile;
     {   // ---- phase B: S = K^-1 + E, swept in place
       const int tid = fresh_tid<NW>(tid0), gr = tid / G, gc = tid % G;
-      if constexpr (sizeof(TS) == sizeof(TM)) {
+      if constexpr (ROWTAB) {
+        static_assert(!ROWTAB || sizeof(TS) == sizeof(TM), "kq and rw were loaded in the sweep's element type: the row table serves a tile that is built and swept in TM");
+        w_tile_init_rows<TM, N>(tile, kq, rw, E, gr, gc);
+        STAMP(2);
+        w_sweep<TM, N, W_TRIM_PKMUL<N, sizeof(TM) == 4>>(tile, piv, gr, gc);
+      } else if constexpr (sizeof(TS) == sizeof(TM)) {
         w_tile_init<TM, N, sizeof(TM) == 4>(tile, kq, E, gr, gc);
         STAMP(2);
-        w_sweep<TM, N>(tile, piv, gr, gc);
+        w_sweep<TM, N, W_TRIM_PKMUL<N, sizeof(TM) == 4>>(tile, piv, gr, gc);   // (false here while the W_TRIM switches are equal: said so that W_TRIM_ROWTAB can be switched off alone)
       } else {   // swept in fp64, rounded to the fp32 tile the iterations use
         WTile<TS> t64;
         w_tile_init<TS, N, sizeof(TM) == 4>(t64, kq, reinterpret_cast<const TS*>(s.E), gr, gc);
@@ -1131,11 +1228,14 @@ __device__ __forceinline__ int w_polish_round(SmemW<TV, N>& s, const WrTabs& tab
   int ok = 0, ps = 0, nstall = 0, cheap_used = 0;
   float vprev = INFINITY, vprev2 = INFINITY;
   bool done = false;
+  constexpr bool ROWTAB = W_TRIM_ROWTAB<N, VM>;   // (VM: the kernel iterates on an fp32 tile)
   while (!done) {
     WKq<TP> kq;
+    WRows rw;   // (ROWTAB only)
     {   // ---- E = T D^-1 T' for the active set in s.aset (behind the loads of the lane's K^-1 entries)
       const int tid = fresh_tid<NW>(tid0), L = min(tid, NL - 1);
-      w_kq_load<TP>(kq, w_klane<TP>(tabs), tid);
+      if constexpr (ROWTAB) w_kq_rows_load<TP, N>(kq, rw, w_klane<TP>(tabs), tid);
+      else w_kq_load<TP>(kq, w_klane<TP>(tabs), tid);
       PMap Ls;
       w_polish_sys<TV, TP, N>(s, L, ActSet(s.aset[L], s.ct[L] != 0), Ls);
       w_build_E<TP, N>(Ls, E, tid);
@@ -1144,7 +1244,8 @@ __device__ __forceinline__ int w_polish_round(SmemW<TV, N>& s, const WrTabs& tab
     WTile<TP> tile;
     {   // ---- S = K^-1 + E, swept in place
       const int tid = fresh_tid<NW>(tid0), gr = tid / G, gc = tid % G;
-      w_tile_init<TP, N, VM>(tile, kq, E, gr, gc);
+      if constexpr (ROWTAB) w_tile_init_rows<TP, N>(tile, kq, rw, E, gr, gc);
+      else w_tile_init<TP, N, VM>(tile, kq, E, gr, gc);
       STAMP(10);
       w_sweep<TP, N>(tile, piv, gr, gc);
     }
