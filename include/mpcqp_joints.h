@@ -100,6 +100,105 @@ int mpcqp_joint_rates(mpcqp_handle h, int64_t B, int32_t T, const void* actual, 
                       const void* foot_vel, const MpcQpLegGeometry* geo, void* q, void* qd, void* tau, void* power, uint8_t* reach,
                       void* stream);
 
+/*
+ * ---- Leg dynamics: the rigid-body dynamics of the three-link leg on a moving torso ----------------------------------------------
+ *
+ * The joint log above prices a leg's motion at zero: tau = (R J)^T (-f) is the torque of the ground force alone, and a swing leg's is
+ * a zero.  The calls below add what moving the 1.16 kg of leg costs -- the reference's controller adds the same terms, an operational-
+ * space feed-forward plus the leg's Coriolis and gravity forces, to J^T (-f) for a swing leg (src/main.py:225-282).
+ *
+ * The inertial row.  Per leg the HIP, THIGH and SHANK link: mass, centre of mass in the link's own frame (origin at its joint, axes
+ * of the joint's child frame at q = 0, i.e. the torso's axes) and the inertia tensor about the centre of mass in the link's axes
+ * (Ixy etc. are the tensor's elements).  A link that hangs on a fixed joint (the Lite3's FOOT) has to be folded into the row of the
+ * link it hangs from.  mpcqp_default_leg_inertia fills in the Lite3: the <inertial> blocks and joint <limit> rows of
+ * lite3_urdf/urdf/Lite3.urdf, gravity -9.81, and the FOOT link (0.01 kg, inertia 1e-2 kg m^2 about its own centre, at the foot
+ * point (0, 0, -0.21) of the shank frame) folded into the SHANK row by the parallel-axis theorem.  That foot inertia is fifteen
+ * times the shank's own; it is the description's model and is kept (DESIGN.md has the shank row with and without it).
+ * The row is checked on the host: a non-finite entry, a negative mass, q_min > q_max, a negative qd_max / tau_max, or a gravity that
+ * is not negative and finite is MPCQP_EINVAL with the field named in mpcqp_last_error().  All-zero masses and inertias are valid
+ * (massless legs: the dynamic torque is then an exact zero).
+ *
+ * The recursion (Newton-Euler over HipX, HipY, Knee, in the torso's axes; link k turns about the axis z_k through its joint origin
+ * p_k, its centre of mass is c_k, its mass m_k and inertia I_k):
+ *   outwards  w_k  = w_{k-1} + z_k qd_k,   al_k = al_{k-1} + z_k qdd_k + (w_{k-1} x z_k) qd_k,
+ *             a(p_{k+1}) = a(p_k) + al_k x (p_{k+1} - p_k) + w_k x (w_k x (p_{k+1} - p_k)),  likewise a(c_k);  p_4 = the foot point
+ *             F_k = m_k (a(c_k) - g),   N_k = I_k al_k + w_k x (I_k w_k)
+ *   inwards   f_k = F_k + f_{k+1},   n_k = N_k + (c_k - p_k) x F_k + n_{k+1} + (p_{k+1} - p_k) x f_{k+1},   tau_k = z_k . n_k
+ * starting from the torso's w_0, al_0 and a(p_1) = a_0 + al_0 x p_1 + w_0 x (w_0 x p_1).  No foot force enters: the ground's share
+ * is the (R J)^T (-f) of the joint log.
+ *
+ * Not built (each would need state the plant does not carry): the PD terms of the reference's swing-leg controller -- the plant has
+ * no leg state, so there is no tracking error to feed back; the reaction of the legs on the torso -- the plant's legs stay massless;
+ * and the reference's op_space_mi = J*M*J.T, an element-wise product on a block of the mass matrix that is not the leg's:
+ * what is computed here is the rigid-body answer, not a copy of that expression.
+ */
+typedef struct MpcQpLegInertia {
+  uint32_t size, reserved;
+  double mass[4][3];        /* HIP, THIGH, SHANK link of FL, FR, HL, HR, kg; >= 0 */
+  double com[4][3][3];      /* centre of mass in the link's own frame (origin at its joint) */
+  double inertia[4][3][6];  /* Ixx, Iyy, Izz, Ixy, Ixz, Iyz about the centre of mass, link axes */
+  double q_min[3], q_max[3], qd_max[3], tau_max[3];   /* HipX, HipY, Knee */
+  double gravity;           /* negative, m/s^2 */
+} MpcQpLegInertia;
+
+/* The Lite3's row (sets size); MPCQP_EINVAL for a null pointer. */
+int mpcqp_default_leg_inertia(MpcQpLegInertia* inr);
+
+/*
+ * The leg's equations of motion for B rows: tau = M(q) qdd + bias(q, qd, torso motion, gravity).
+ *   q       T  [B,4,3]    joint angles HipX, HipY, Knee
+ *   qd      T  [B,4,3]    joint rates, NULL = 0
+ *   qdd     T  [B,4,3]    joint accelerations, NULL = 0
+ *   rot     T  [B,3,3]    torso orientation (world <- torso), NULL = identity
+ *   base    T  [B,9]      world-frame angular velocity, angular acceleration and linear acceleration of the torso origin; NULL = the
+ *                         torso at rest.  Gravity is inr->gravity along world -z.
+ *   geo                   host pointer, NULL = the Lite3.  Any geometry mpcqp_leg_jacobians takes (no closed-form structure needed)
+ *   inr                   host pointer, NULL = the Lite3 (mpcqp_default_leg_inertia)
+ *   tau     T  [B,4,3]    out, may be NULL: the joint torques that produce qdd (no foot force)
+ *   mass    T  [B,4,3,3]  out, may be NULL: the joint-space inertia M(q), row-major; column j is the recursion at a unit qdd_j without
+ *                         velocity, torso and gravity terms
+ *   bias    T  [B,4,3]    out, may be NULL: tau at qdd = 0
+ * At least one output is required.  B = 0 is a no-op; B < 0 or B > 0x1fffffff is MPCQP_EINVAL.  A non-finite operand makes the
+ * outputs that depend on it NaN in its own leg (q: its leg; rot, base: the four legs of its row; mass depends on q alone).
+ */
+int mpcqp_leg_dynamics(mpcqp_handle h, int64_t B, const void* q, const void* qd, const void* qdd, const void* rot, const void* base,
+                       const MpcQpLegGeometry* geo, const MpcQpLegInertia* inr, void* tau, void* mass, void* bias, void* stream);
+
+/*
+ * The full joint torques of a roll-out's log, and whether the actuators could deliver them.
+ *   actual, forces, feet, foot_vel, geo   exactly the operands of mpcqp_joint_rates (the closed form's geometry)
+ *   foot_acc T  [B,T,4,3]  world acceleration of each foot, or NULL = 0 (the `acc` of mpcqp_phase_swing / mpcqp_swing_trajectories)
+ *   base_acc T  [B,T,6]    world-frame angular acceleration of the torso and linear acceleration of the CoM, or NULL = the unpushed
+ *                          plant's right-hand side at the row: a = sum_l f_l / m + g e_z, alpha = I_w^-1 (sum_l r_l x f_l - omega x I_w
+ *                          omega), I_w = R I_b R^T, r_l = foot_l - CoM, g = inr->gravity.  No contact mask is needed: a swing leg's
+ *                          force is an exact zero.  A caller that pushes its robots passes its own.
+ *   body     T  [B,7]      as for mpcqp_plant_step (m, Ixx, Iyy, Izz, Ixy, Ixz, Iyz), NULL = the handle's model; read only when
+ *                          base_acc is NULL.  An invalid row (the plant's check) makes every output of that robot NaN, limit 0xff.
+ *   inr                    host pointer, NULL = the Lite3
+ *   qdd      T  [B,T,4,3]  out, may be NULL: joint accelerations in rad / s^2
+ *   tau_dyn  T  [B,T,4,3]  out, may be NULL: mpcqp_leg_dynamics' tau at (q, qd, qdd)
+ *   tau      T  [B,T,4,3]  out, may be NULL: tau_f + tau_dyn, tau_f = (R J)^T (-f) the tau of mpcqp_joint_rates
+ *   power    T  [B,T,4]    out, may be NULL: sum_j tau_j qd_j, formed as mpcqp_joint_rates' power (tau_f . qd) plus tau_dyn . qd
+ *   limit    u8 [B,T,4]    out, may be NULL: OR over the leg's three joints of  1: q outside [q_min, q_max],  2: |qd| > qd_max,
+ *                          4: |tau| > tau_max;  8: the leg is out of reach (reach = 0)
+ * At least one output is required; sizes as for mpcqp_joint_log.  Per (robot, tick, leg): q, qd, tau_f and reach are those of
+ * mpcqp_joint_rates (the same device function).  With the CoM standing in for the torso origin, as in the joint log, the foot's
+ * world acceleration is
+ *   a_foot = a + alpha x r + omega x (omega x r) + 2 omega x u + R (Jdot qd) + R J qdd,     r = foot - CoM,  u = R J qd;
+ * everything but the last term is the foot point's acceleration in the forward pass of the recursion at qdd = 0 (with r = R p_foot(q),
+ * which is foot - CoM for a leg in reach), and qdd = J^-1 R^T (a_foot - that) by adjugate and determinant as for the rates, of the J
+ * the recursion's own chain gives (the shared device function of the joint log is left as it is).  With base_acc NULL the row's
+ * sum_l f_l and sum_l r_l x f_l are formed across the four legs as (FL + FR) + (HL + HR).  tau_dyn
+ * is the recursion at (q, qd, qdd) with rot = R and base = (omega, alpha, a).  Where reach = 0 or det J = 0: qd = qdd = 0, and tau_dyn
+ * is the torque that holds the clamped q on the moving torso.  A non-finite value among the leg's inputs (its row of actual, its
+ * force, foot, foot_vel, foot_acc, its row of base_acc -- or, with base_acc NULL, any force or foot of its row and its robot's body)
+ * or results makes all five outputs of that leg NaN / 0xff; no other leg changes.
+ */
+int mpcqp_leg_effort(mpcqp_handle h, int64_t B, int32_t T, const void* actual, const void* forces, const void* feet,
+                     const void* foot_vel, const void* foot_acc, const void* base_acc, const void* body,
+                     const MpcQpLegGeometry* geo, const MpcQpLegInertia* inr,
+                     void* qdd, void* tau_dyn, void* tau, void* power, uint8_t* limit, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

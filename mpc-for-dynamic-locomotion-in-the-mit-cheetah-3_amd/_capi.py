@@ -48,6 +48,33 @@ class MpcQpLegGeometry(ctypes.Structure):
                 ("knee", c_double * 3), ("foot", c_double * 3), ("axis_x", c_double * 3), ("axis_y", c_double * 3)]
 
 
+class MpcQpLegInertia(ctypes.Structure):
+    """Mirror of struct MpcQpLegInertia (include/mpcqp_joints.h)."""
+    _fields_ = [("size", c_uint32), ("reserved", c_uint32), ("mass", c_double * 3 * 4), ("com", c_double * 3 * 3 * 4),
+                ("inertia", c_double * 6 * 3 * 4), ("q_min", c_double * 3), ("q_max", c_double * 3), ("qd_max", c_double * 3),
+                ("tau_max", c_double * 3), ("gravity", c_double)]
+    ARRAYS = ("mass", "com", "inertia", "q_min", "q_max", "qd_max", "tau_max")
+
+    @classmethod
+    def from_dict(cls, d):
+        """The struct of a dict of arrays as lite3_model.leg_inertia() returns it (no check: the library checks the row)."""
+        r = cls()
+        r.size = ctypes.sizeof(cls)
+        for k in cls.ARRAYS:
+            a = np.ascontiguousarray(d[k], dtype=np.float64)
+            field = getattr(r, k)
+            if a.nbytes != ctypes.sizeof(field):
+                raise ValueError(f"leg inertia field {k}: expected {ctypes.sizeof(field) // 8} values, got {a.size}")
+            ctypes.memmove(field, a.ctypes.data, a.nbytes)
+        r.gravity = float(d["gravity"])
+        return r
+
+    def as_dict(self):
+        out = {k: np.ctypeslib.as_array(getattr(self, k)).copy() for k in self.ARRAYS}
+        out["gravity"] = float(self.gravity)
+        return out
+
+
 class MpcQpConfig(ctypes.Structure):
     """Mirror of ``struct MpcQpConfig`` (include/mpcqp.h)."""
     _fields_ = [
@@ -77,7 +104,7 @@ class MpcQpError(RuntimeError):
 # the other four are exported by the product library only (the CPU checker under oracle/ does not have them).  tests/test_capi.py
 # compares every row with the prototype in the header.
 _P, _I32, _I64 = c_void_p, c_int32, c_int64   # any address (handle, buffer, stream), int32_t, int64_t
-_CFG, _GEO = ctypes.POINTER(MpcQpConfig), ctypes.POINTER(MpcQpLegGeometry)
+_CFG, _GEO, _INR = ctypes.POINTER(MpcQpConfig), ctypes.POINTER(MpcQpLegGeometry), ctypes.POINTER(MpcQpLegInertia)
 CORE_HEADER = "mpcqp.h"
 ABI = {
     "mpcqp.h": (
@@ -112,10 +139,13 @@ ABI = {
         ("mpcqp_set_models", c_int, (_P, _I64, _P, _P)),
         ("mpcqp_clear_models", c_int, (_P,)),
     ),
-    "mpcqp_joints.h": (  # closed-form leg inverse kinematics and the joint-space log
+    "mpcqp_joints.h": (  # closed-form leg inverse kinematics, the joint-space log and the leg dynamics
         ("mpcqp_leg_ik", c_int, (_P, _I64, _P, _P, _P, _GEO, _P, _P, _P)),
         ("mpcqp_joint_log", c_int, (_P, _I64, _I32, _P, _P, _P, _GEO, _P, _P, _P, _P)),
         ("mpcqp_joint_rates", c_int, (_P, _I64, _I32, _P, _P, _P, _P, _GEO) + (_P,) * 6),
+        ("mpcqp_default_leg_inertia", c_int, (_INR,)),
+        ("mpcqp_leg_dynamics", c_int, (_P, _I64) + (_P,) * 5 + (_GEO, _INR) + (_P,) * 4),
+        ("mpcqp_leg_effort", c_int, (_P, _I64, _I32) + (_P,) * 7 + (_GEO, _INR) + (_P,) * 6),
     ),
 }
 EXPORTED_SYMBOLS, PLAN_SYMBOLS, SIM_SYMBOLS, MODEL_SYMBOLS, JOINTS_SYMBOLS = (tuple(row[0] for row in rows) for rows in ABI.values())
@@ -145,6 +175,17 @@ class Library:
 
     def version(self) -> int:
         return int(self.lib.mpcqp_version())
+
+    def default_leg_inertia(self) -> "MpcQpLegInertia":
+        """The Lite3's inertial row and actuator limits (include/mpcqp_joints.h, mpcqp_default_leg_inertia; product library only)."""
+        fn, header, _ = self.calls["mpcqp_default_leg_inertia"]
+        if fn is None:
+            raise MpcQpError(f"mpcqp_default_leg_inertia: {self.path} does not export include/{header} (product library only)")
+        row = MpcQpLegInertia()
+        rc = fn(ctypes.byref(row))
+        if rc != 0:
+            raise MpcQpError(f"mpcqp_default_leg_inertia failed: {rc}")
+        return row
 
     def default_config(self, **overrides) -> MpcQpConfig:
         cfg = MpcQpConfig()
@@ -292,6 +333,17 @@ class Engine:
     def joint_rates_ptr(self, B, T, actual, forces, feet, foot_vel, q, qd, tau, power, reach, geometry=None, stream=0):
         """The joint-space log with joint rates and power (include/mpcqp_joints.h, mpcqp_joint_rates)."""
         self._call("mpcqp_joint_rates", B, T, actual, forces, feet, foot_vel, geometry, q, qd, tau, power, reach, stream)
+
+    # (`inertia` is an MpcQpLegInertia or None = the Lite3)
+    def leg_dynamics_ptr(self, B, q, qd, qdd, rot, base, tau, mass, bias, geometry=None, inertia=None, stream=0):
+        """The leg's equations of motion (include/mpcqp_joints.h, mpcqp_leg_dynamics)."""
+        self._call("mpcqp_leg_dynamics", B, q, qd, qdd, rot, base, geometry, inertia, tau, mass, bias, stream)
+
+    def leg_effort_ptr(self, B, T, actual, forces, feet, foot_vel, foot_acc, base_acc, body, qdd, tau_dyn, tau, power, limit, geometry=None,
+                       inertia=None, stream=0):
+        """The full joint torques of a roll-out's log and the actuator-limit flags (include/mpcqp_joints.h, mpcqp_leg_effort)."""
+        self._call("mpcqp_leg_effort", B, T, actual, forces, feet, foot_vel, foot_acc, base_acc, body, geometry, inertia, qdd, tau_dyn, tau,
+                   power, limit, stream)
 
     def torque_map_ptr(self, B, u, jac, tau, stream=0):
         self._call("mpcqp_torque_map", B, u, jac, tau, stream)

@@ -25,6 +25,7 @@
 #include "mpcqp_elementwise.h"
 #include "mpcqp_model.h"
 #include "mpcqp_joints.h"
+#include "mpcqp_legdyn.h"
 
 #include <cstdio>
 #include <cstdlib>
@@ -1162,6 +1163,168 @@ int mpcqp_joint_rates(mpcqp_handle h, int64_t B, int32_t T, const void* actual, 
                        (const TIO*)feet, (const TIO*)foot_vel, g, (TIO*)q, (TIO*)qd, (TIO*)tau, (TIO*)power, reach, rows);
   });
   return launched(h, "joint rates kernel launch");
+}
+
+int mpcqp_default_leg_inertia(MpcQpLegInertia* r) {   // lite3_urdf/urdf/Lite3.urdf: <inertial> of the HIP / THIGH / SHANK / FOOT links, joint <limit> rows (data)
+  if (!r) return MPCQP_EINVAL;
+  memset(r, 0, sizeof(*r));
+  r->size = (uint32_t)sizeof(*r);
+  // HIP: mirrored left / right in y and front / hind in x, to the description's own digits (its rows differ in the last ones)
+  static const double hip_com[4][3] = {{-0.0047, -0.0091, -0.0018}, {-0.0047, 0.0091, -0.0018}, {0.0047, -0.0091, -0.0018}, {0.0047, 0.0091, -0.0018}};
+  static const double hip_prod[4][3] = {{8.1579e-07, -1.264e-05, 1.3443e-06}, {-8.1551e-07, -1.2639e-05, -1.3441e-06},
+                                        {-8.1585e-07, 1.2639e-05, 1.3444e-06}, {8.1545e-07, 1.2639e-05, -1.344e-06}};
+  const double foot_m = 0.01, foot_i = 1e-2, foot_c[3] = {0.0, 0.0, -0.21};   // the FOOT link, on the fixed Ankle joint
+  for (int l = 0; l < 4; ++l) {
+    const double sy = (l % 2 == 0) ? 1.0 : -1.0;   // left : right
+    r->mass[l][0] = 0.428;
+    for (int a = 0; a < 3; ++a) { r->com[l][0][a] = hip_com[l][a]; r->inertia[l][0][3 + a] = hip_prod[l][a]; }
+    r->inertia[l][0][0] = 0.00014538; r->inertia[l][0][1] = 0.00024024; r->inertia[l][0][2] = 0.00013038;
+    // THIGH: mirrored left / right only (the hind thighs are the front ones)
+    r->mass[l][1] = 0.61;
+    r->com[l][1][0] = -0.00523; r->com[l][1][1] = -0.0216 * sy; r->com[l][1][2] = -0.0273;
+    r->inertia[l][1][0] = 0.001; r->inertia[l][1][1] = 0.00116; r->inertia[l][1][2] = 2.68e-04;
+    r->inertia[l][1][3] = -2.5e-06 * sy; r->inertia[l][1][4] = -1.12e-04; r->inertia[l][1][5] = 3.75e-07 * sy;
+    // SHANK (the same row on all four legs) with the FOOT folded in by the parallel-axis theorem
+    const double sm = 0.115, sc[3] = {0.00585, -8.732e-07, -0.12};
+    const double si[6] = {6.68e-04, 6.86e-04, 3.155e-05, -1.24e-08, 6.91e-06, 5.65e-09};
+    const double m = sm + foot_m;
+    double c[3], I[6];
+    for (int a = 0; a < 3; ++a) c[a] = (sm * sc[a] + foot_m * foot_c[a]) / m;
+    for (int a = 0; a < 6; ++a) I[a] = si[a] + (a < 3 ? foot_i : 0.0);
+    for (int k = 0; k < 2; ++k) {
+      const double mk = k ? foot_m : sm;
+      const double* ck = k ? foot_c : sc;
+      const double dx = ck[0] - c[0], dy = ck[1] - c[1], dz = ck[2] - c[2];
+      I[0] = I[0] + mk * (dy * dy + dz * dz); I[1] = I[1] + mk * (dx * dx + dz * dz); I[2] = I[2] + mk * (dx * dx + dy * dy);
+      I[3] = I[3] - mk * (dx * dy); I[4] = I[4] - mk * (dx * dz); I[5] = I[5] - mk * (dy * dz);
+    }
+    r->mass[l][2] = m;
+    for (int a = 0; a < 3; ++a) r->com[l][2][a] = c[a];
+    for (int a = 0; a < 6; ++a) r->inertia[l][2][a] = I[a];
+  }
+  const double lim[4][3] = {{-0.42, -2.67, 0.6}, {0.42, 0.314, 2.72}, {26.0, 26.0, 17.0}, {24.0, 24.0, 36.0}};
+  for (int j = 0; j < 3; ++j) { r->q_min[j] = lim[0][j]; r->q_max[j] = lim[1][j]; r->qd_max[j] = lim[2][j]; r->tau_max[j] = lim[3][j]; }
+  r->gravity = -9.81;
+  return MPCQP_OK;
+}
+
+extern "C++" {
+namespace {
+
+// The geometry as mpcqp_leg_jacobians takes it: any chain with non-zero joint axes (normalised here).
+int leg_fk_geometry(mpcqp_handle h, const char* who, const MpcQpLegGeometry* geo, LegGeoDev& g) {
+  MpcQpLegGeometry lite3;
+  if (!geo) { (void)mpcqp_default_leg_geometry(&lite3); geo = &lite3; }
+  char msg[160];
+  if (geo->size != sizeof(MpcQpLegGeometry)) {
+    snprintf(msg, sizeof(msg), "%s: geometry struct size mismatch", who);
+    return fail(h, MPCQP_EINVAL, msg);
+  }
+  memcpy(g.hx, geo->hip_x, sizeof(g.hx)); memcpy(g.hy, geo->hip_y, sizeof(g.hy));
+  memcpy(g.kn, geo->knee, sizeof(g.kn)); memcpy(g.ft, geo->foot, sizeof(g.ft));
+  for (int k = 0; k < 2; ++k) {   // unit axes (Rodrigues' formula assumes them)
+    const double* a = k ? geo->axis_y : geo->axis_x;
+    const double nrm = std::sqrt(a[0] * a[0] + a[1] * a[1] + a[2] * a[2]);
+    if (!(nrm > 0) || !std::isfinite(nrm)) {
+      snprintf(msg, sizeof(msg), "%s: zero joint axis", who);
+      return fail(h, MPCQP_EINVAL, msg);
+    }
+    for (int c = 0; c < 3; ++c) (k ? g.ay : g.ax)[c] = a[c] / nrm;
+  }
+  return MPCQP_OK;
+}
+
+// The inertial row of include/mpcqp_joints.h: fills r or names the field that is not valid.
+int leg_inertia_row(mpcqp_handle h, const char* who, const MpcQpLegInertia* inr, LegInrDev& r) {
+  MpcQpLegInertia lite3;
+  if (!inr) { (void)mpcqp_default_leg_inertia(&lite3); inr = &lite3; }
+  char msg[160];
+  const char* bad = nullptr;
+  if (inr->size != sizeof(MpcQpLegInertia)) {
+    snprintf(msg, sizeof(msg), "%s: inertia struct size mismatch", who);
+    return fail(h, MPCQP_EINVAL, msg);
+  }
+  const auto fin = [](const double* a, int n) { for (int i = 0; i < n; ++i) if (!std::isfinite(a[i])) return false; return true; };
+  if (!fin(&inr->mass[0][0], 12)) bad = "mass is not finite";
+  else if (!fin(&inr->com[0][0][0], 36)) bad = "com is not finite";
+  else if (!fin(&inr->inertia[0][0][0], 72)) bad = "inertia is not finite";
+  else if (!fin(inr->q_min, 3)) bad = "q_min is not finite";
+  else if (!fin(inr->q_max, 3)) bad = "q_max is not finite";
+  else if (!fin(inr->qd_max, 3)) bad = "qd_max is not finite";
+  else if (!fin(inr->tau_max, 3)) bad = "tau_max is not finite";
+  else if (!std::isfinite(inr->gravity) || !(inr->gravity < 0.0)) bad = "gravity is not negative and finite";
+  for (int i = 0; i < 12 && !bad; ++i) if ((&inr->mass[0][0])[i] < 0.0) bad = "mass is negative";
+  for (int j = 0; j < 3 && !bad; ++j) {
+    if (inr->q_min[j] > inr->q_max[j]) bad = "q_min > q_max";
+    else if (inr->qd_max[j] < 0.0) bad = "qd_max is negative";
+    else if (inr->tau_max[j] < 0.0) bad = "tau_max is negative";
+  }
+  if (bad) {
+    snprintf(msg, sizeof(msg), "%s: invalid leg inertia row: %s", who, bad);
+    return fail(h, MPCQP_EINVAL, msg);
+  }
+  LegLinkInr* link[3] = {&r.k0, &r.k1, &r.k2};
+  for (int l = 0; l < 4; ++l)
+    for (int k = 0; k < 3; ++k) {
+      link[k]->m[l] = inr->mass[l][k];
+      memcpy(link[k]->c[l], inr->com[l][k], sizeof(link[k]->c[l]));
+      memcpy(link[k]->I[l], inr->inertia[l][k], sizeof(link[k]->I[l]));
+    }
+  memcpy(r.lim.qmin, inr->q_min, sizeof(r.lim.qmin)); memcpy(r.lim.qmax, inr->q_max, sizeof(r.lim.qmax));
+  memcpy(r.lim.qdmax, inr->qd_max, sizeof(r.lim.qdmax)); memcpy(r.lim.taumax, inr->tau_max, sizeof(r.lim.taumax));
+  r.lim.g = inr->gravity;
+  return MPCQP_OK;
+}
+
+}  // namespace
+}  // extern "C++"
+
+int mpcqp_leg_dynamics(mpcqp_handle h, int64_t B, const void* q, const void* qd, const void* qdd, const void* rot, const void* base,
+                       const MpcQpLegGeometry* geo, const MpcQpLegInertia* inr, void* tau, void* mass, void* bias, void* stream) {
+  if (!h) return MPCQP_EINVAL;
+  if (B < 0 || B > 0x1fffffff) return fail(h, MPCQP_EINVAL, "mpcqp_leg_dynamics: batch size out of range");
+  if (!tau && !mass && !bias) return fail(h, MPCQP_EINVAL, "mpcqp_leg_dynamics: no output buffer (tau, mass and bias are all null)");
+  if (B > 0 && !q) return fail(h, MPCQP_EINVAL, "mpcqp_leg_dynamics: null q buffer");
+  LegGeoDev g;
+  if (const int rc = leg_fk_geometry(h, "mpcqp_leg_dynamics", geo, g)) return rc;
+  LegInrDev r;
+  if (const int rc = leg_inertia_row(h, "mpcqp_leg_dynamics", inr, r)) return rc;
+  if (B == 0) return MPCQP_OK;
+  DeviceGuard guard(h->cfg.device);
+  if (guard.err != hipSuccess) return fail(h, MPCQP_EHIP, "hipSetDevice", guard.err);
+  const dim3 grid((unsigned)((4 * B + 255) / 256));
+  with_io(h, [&](auto tag) {
+    using T = decltype(tag);
+    hipLaunchKernelGGL((mpcqp_leg_dynamics_kernel<T>), grid, dim3(256), 0, (hipStream_t)stream, (const T*)q, (const T*)qd, (const T*)qdd,
+                       (const T*)rot, (const T*)base, g, r.k0, r.k1, r.k2, r.lim, (T*)tau, (T*)mass, (T*)bias, B);
+  });
+  return launched(h, "leg dynamics kernel launch");
+}
+
+int mpcqp_leg_effort(mpcqp_handle h, int64_t B, int32_t T, const void* actual, const void* forces, const void* feet, const void* foot_vel,
+                     const void* foot_acc, const void* base_acc, const void* body, const MpcQpLegGeometry* geo, const MpcQpLegInertia* inr,
+                     void* qdd, void* tau_dyn, void* tau, void* power, uint8_t* limit, void* stream) {
+  if (!h) return MPCQP_EINVAL;
+  if (B < 0 || B > 0x7fffffff || T < 0 || B * (int64_t)T > 0x1fffffff) return fail(h, MPCQP_EINVAL, "mpcqp_leg_effort: size out of range");
+  if (!qdd && !tau_dyn && !tau && !power && !limit)
+    return fail(h, MPCQP_EINVAL, "mpcqp_leg_effort: no output buffer (qdd, tau_dyn, tau, power and limit are all null)");
+  if (B > 0 && T > 0 && (!actual || !forces || !feet)) return fail(h, MPCQP_EINVAL, "mpcqp_leg_effort: null buffer");
+  LegGeoDev g;
+  if (const int rc = leg_ik_geometry(h, "mpcqp_leg_effort", geo, g)) return rc;
+  LegInrDev r;
+  if (const int rc = leg_inertia_row(h, "mpcqp_leg_effort", inr, r)) return rc;
+  if (B == 0 || T == 0) return MPCQP_OK;
+  DeviceGuard guard(h->cfg.device);
+  if (guard.err != hipSuccess) return fail(h, MPCQP_EHIP, "hipSetDevice", guard.err);
+  const int64_t rows = B * T;
+  const dim3 grid((unsigned)((4 * rows + 255) / 256));
+  with_io(h, [&](auto tag) {
+    using TIO = decltype(tag);
+    hipLaunchKernelGGL((mpcqp_leg_effort_kernel<TIO>), grid, dim3(256), 0, (hipStream_t)stream, (const TIO*)actual, (const TIO*)forces,
+                       (const TIO*)feet, (const TIO*)foot_vel, (const TIO*)foot_acc, (const TIO*)base_acc, (const TIO*)body, plant_model(h),
+                       g, r.k0, r.k1, r.k2, r.lim, (TIO*)qdd, (TIO*)tau_dyn, (TIO*)tau, (TIO*)power, limit, rows, (int64_t)T);
+  });
+  return launched(h, "leg effort kernel launch");
 }
 
 int mpcqp_last_kernel_ms(mpcqp_handle h, float* ms) {

@@ -398,5 +398,50 @@ class MPCBatch:
                                     tau.data_ptr(), power.data_ptr(), reach.data_ptr(), geometry, st.cuda_stream)
         return {"q": q, "qd": qd, "tau": tau, "power": power, "reach": reach}
 
+    @staticmethod
+    def _inertia(inertia):
+        """None, an MpcQpLegInertia, or a dict of arrays as lite3_model.leg_inertia() returns it."""
+        return _capi.MpcQpLegInertia.from_dict(inertia) if isinstance(inertia, dict) else inertia
+
+    def leg_dynamics(self, q, qd=None, qdd=None, rot=None, base=None, inertia=None, geometry=None, want=("tau", "mass", "bias"), stream=None):
+        """The leg's equations of motion on the device (include/mpcqp_joints.h, mpcqp_leg_dynamics; the host counterpart is
+        lite3_model.leg_dynamics_host): q [B,4,3], qd / qdd [B,4,3] or None (0), rot [B,3,3] world <- torso or None, base [B,9] = the
+        torso's world-frame angular velocity, angular acceleration and the linear acceleration of its origin, or None (at rest);
+        inertia a dict as lite3_model.leg_inertia() or None (the Lite3) -> {"tau": [B,4,3] joint torques that produce qdd, "mass":
+        [B,4,3,3] M(q), "bias": [B,4,3] tau at qdd = 0}, so tau = M qdd + bias; an output not in `want` is None.  Asynchronous."""
+        B = int(q.shape[0])
+        legs = (B, 4, 3)
+        check_operands(self.device, (("q", q, legs, self.tdtype), ("qd", qd, legs, self.tdtype), ("qdd", qdd, legs, self.tdtype),
+                                     ("rot", rot, (B, 3, 3), self.tdtype), ("base", base, (B, 9), self.tdtype)),
+                       optional=("qd", "qdd", "rot", "base"))
+        st = self._stream(stream)
+        tau, mass, bias = self._alloc(stream, (legs, self.tdtype) if "tau" in want else None,
+                                      ((B, 4, 3, 3), self.tdtype) if "mass" in want else None, (legs, self.tdtype) if "bias" in want else None)
+        self.engine.leg_dynamics_ptr(B, q.data_ptr(), _ptr(qd), _ptr(qdd), _ptr(rot), _ptr(base), _ptr(tau), _ptr(mass), _ptr(bias), geometry,
+                                     self._inertia(inertia), st.cuda_stream)
+        return {"tau": tau, "mass": mass, "bias": bias}
+
+    def leg_effort(self, actual, forces, feet, foot_vel=None, foot_acc=None, base_acc=None, body=None, inertia=None, geometry=None,
+                   stream=None):
+        """The full joint torques of a roll-out's log and whether the actuators could deliver them (include/mpcqp_joints.h,
+        mpcqp_leg_effort; the host counterpart is lite3_model.leg_effort_host): actual, forces, feet, foot_vel as for `joint_rates`;
+        foot_acc [B,T,4,3] the feet's world accelerations -- `phase_swing(...)["swing"][:, :, :, 2]`, made contiguous -- or None (0);
+        base_acc [B,T,6] the torso's angular and the CoM's linear acceleration, or None for the unpushed plant's right-hand side at each
+        row, formed with body [B,7] (None = the engine's model) -> {"qdd", "tau_dyn", "tau" [B,T,4,3], "power" [B,T,4], "limit" uint8
+        [B,T,4]: 1 = a joint angle, 2 = a joint rate, 4 = a joint torque beyond the actuator's limit, 8 = out of reach; 0xff = a
+        non-finite leg}.  tau = `joint_rates`' tau + tau_dyn.  Asynchronous on `stream`."""
+        B, T = int(actual.shape[0]), int(actual.shape[1]) if actual.dim() == 3 else -1
+        legs = ((B, T, 4, 3), self.tdtype)
+        check_operands(self.device, (("actual", actual, (B, T, 12), self.tdtype), ("forces", forces, (B, T, 12), self.tdtype),
+                                     ("feet", feet, *legs), ("foot_vel", foot_vel, *legs), ("foot_acc", foot_acc, *legs),
+                                     ("base_acc", base_acc, (B, T, 6), self.tdtype), ("body", body, (B, 7), self.tdtype)),
+                       optional=("foot_vel", "foot_acc", "base_acc", "body"))
+        st = self._stream(stream)
+        qdd, tau_dyn, tau, power, limit = self._alloc(stream, legs, legs, legs, ((B, T, 4), self.tdtype), ((B, T, 4), _torch().uint8))
+        self.engine.leg_effort_ptr(B, T, actual.data_ptr(), forces.data_ptr(), feet.data_ptr(), _ptr(foot_vel), _ptr(foot_acc), _ptr(base_acc),
+                                   _ptr(body), qdd.data_ptr(), tau_dyn.data_ptr(), tau.data_ptr(), power.data_ptr(), limit.data_ptr(), geometry,
+                                   self._inertia(inertia), st.cuda_stream)
+        return {"qdd": qdd, "tau_dyn": tau_dyn, "tau": tau, "power": power, "limit": limit}
+
     def last_kernel_ms(self):
         return self.engine.last_kernel_ms()

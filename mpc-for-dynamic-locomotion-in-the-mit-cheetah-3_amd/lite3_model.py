@@ -142,6 +142,223 @@ def joint_rates_host(actual, forces, feet, foot_vel=None):
     return q, qd, tau, power, reach
 
 
+# ---- leg dynamics (the host counterparts of mpcqp_leg_dynamics / mpcqp_leg_effort, include/mpcqp_joints.h) ------------------------
+_BODY = np.array([8.885, 0.24, 1.0, 1.0, 0.0, 0.0, 0.0])   # body = None: MpcQpConfig.m and diag(1 / Ibody_inv) of the default handle
+
+
+def leg_inertia(fold_foot=True):
+    """The Lite3's inertial row and actuator limits as a dict of arrays, the numbers of mpcqp_default_leg_inertia (read off the
+    <inertial> blocks and joint <limit> rows of lite3_urdf/urdf/Lite3.urdf; data, no code): mass [4,3] kg, com [4,3,3] m, inertia
+    [4,3,6] (Ixx, Iyy, Izz, Ixy, Ixz, Iyz about the centre of mass) of the HIP, THIGH, SHANK link of FL, FR, HL, HR; q_min, q_max,
+    qd_max, tau_max [3] of HipX, HipY, Knee; gravity.  The FOOT link (0.01 kg, 1e-2 kg m^2, on a fixed joint at the foot point) is
+    folded into the SHANK row by the parallel-axis theorem; fold_foot=False gives the shank's own row."""
+    mass, com, inertia = np.zeros((4, 3)), np.zeros((4, 3, 3)), np.zeros((4, 3, 6))
+    hip_com = [[-0.0047, -0.0091, -0.0018], [-0.0047, 0.0091, -0.0018], [0.0047, -0.0091, -0.0018], [0.0047, 0.0091, -0.0018]]
+    hip_prod = [[8.1579e-07, -1.264e-05, 1.3443e-06], [-8.1551e-07, -1.2639e-05, -1.3441e-06],
+                [-8.1585e-07, 1.2639e-05, 1.3444e-06], [8.1545e-07, 1.2639e-05, -1.344e-06]]
+    foot_m, foot_i, foot_c = 0.01, 1e-2, [0.0, 0.0, -0.21]
+    sm, sc = 0.115, [0.00585, -8.732e-07, -0.12]
+    si = [6.68e-04, 6.86e-04, 3.155e-05, -1.24e-08, 6.91e-06, 5.65e-09]
+    for l in range(4):
+        sy = 1.0 if l % 2 == 0 else -1.0
+        mass[l, 0] = 0.428
+        com[l, 0] = hip_com[l]
+        inertia[l, 0] = [0.00014538, 0.00024024, 0.00013038, *hip_prod[l]]
+        mass[l, 1] = 0.61
+        com[l, 1] = [-0.00523, -0.0216 * sy, -0.0273]
+        inertia[l, 1] = [0.001, 0.00116, 2.68e-04, -2.5e-06 * sy, -1.12e-04, 3.75e-07 * sy]
+        if not fold_foot:
+            mass[l, 2], com[l, 2], inertia[l, 2] = sm, sc, si
+            continue
+        m = sm + foot_m
+        c = [(sm * sc[a] + foot_m * foot_c[a]) / m for a in range(3)]
+        I = [si[a] + (foot_i if a < 3 else 0.0) for a in range(6)]
+        for mk, ck in ((sm, sc), (foot_m, foot_c)):
+            dx, dy, dz = ck[0] - c[0], ck[1] - c[1], ck[2] - c[2]
+            I[0] = I[0] + mk * (dy * dy + dz * dz); I[1] = I[1] + mk * (dx * dx + dz * dz); I[2] = I[2] + mk * (dx * dx + dy * dy)
+            I[3] = I[3] - mk * (dx * dy); I[4] = I[4] - mk * (dx * dz); I[5] = I[5] - mk * (dy * dz)
+        mass[l, 2], com[l, 2], inertia[l, 2] = m, c, I
+    return {"mass": mass, "com": com, "inertia": inertia, "q_min": np.array([-0.42, -2.67, 0.6]), "q_max": np.array([0.42, 0.314, 2.72]),
+            "qd_max": np.array([26.0, 26.0, 17.0]), "tau_max": np.array([24.0, 24.0, 36.0]), "gravity": -9.81}
+
+
+def _rodrigues(a, ang):
+    s, c = np.sin(ang), np.cos(ang)
+    t = 1.0 - c
+    R = [c + t * a[0] * a[0], t * a[0] * a[1] - s * a[2], t * a[0] * a[2] + s * a[1],
+         t * a[1] * a[0] + s * a[2], c + t * a[1] * a[1], t * a[1] * a[2] - s * a[0],
+         t * a[2] * a[0] - s * a[1], t * a[2] * a[1] + s * a[0], c + t * a[2] * a[2]]
+    return np.stack(R, axis=-1).reshape(ang.shape + (3, 3))
+
+
+def _mv(R, v):
+    return np.einsum("...ij,...j->...i", R, v)
+
+
+def _mtv(R, v):
+    return np.einsum("...ji,...j->...i", R, v)
+
+
+def _leg_chain(q):
+    """q [...,4,3] -> link orientations Rl[k] [...,4,3,3] (torso <- HIP, THIGH, SHANK), joint axes z[k] [...,4,3], joint origins and
+    foot p[0..3] [...,4,3], all in the torso frame, as `leg_fk_jac` composes them."""
+    R1 = _rodrigues(_AX_X, q[..., 0])
+    R2 = R1 @ _rodrigues(_AX_Y, q[..., 1])
+    R3 = R2 @ _rodrigues(_AX_Y, q[..., 2])
+    p1 = np.broadcast_to(_HIPX, q.shape)
+    p2 = p1 + _mv(R1, _HIPY)
+    p3 = p2 + _mv(R2, _KNEE)
+    pf = p3 + _mv(R3, _FOOT)
+    return (R1, R2, R3), (_mv(R1, _AX_X), _mv(R2, _AX_Y), _mv(R3, _AX_Y)), (p1, p2, p3, pf)
+
+
+def _leg_rnea(inr, chain, w0, al0, a0, gb, qd, qdd, vel=True):
+    """The recursion of include/mpcqp_joints.h on a chain (csrc/mpcqp_legdyn.h, leg_rnea): torso motion w0, al0, a0 and gravity gb
+    in the torso's axes [...,1 or 4,3], qd, qdd [...,4,3] -> (tau [...,4,3], foot acceleration [...,4,3]).  vel=False: M(q) qdd."""
+    Rl, z, p = chain
+    x = np.cross
+    if vel:
+        w, al = w0 + 0.0 * p[0], al0 + 0.0 * p[0]
+        ap = (a0 + x(al0, p[0])) + x(w0, x(w0, p[0]))
+    else:
+        w = al = ap = np.zeros_like(p[0])
+    F, N, rc, d = [], [], [], []
+    for k in range(3):
+        if vel:
+            al = (al + z[k] * qdd[..., k:k + 1]) + x(w, z[k]) * qd[..., k:k + 1]
+            w = w + z[k] * qd[..., k:k + 1]
+        else:
+            al = al + z[k] * qdd[..., k:k + 1]
+        S = inr["inertia"][:, k]
+        S = np.stack([S[:, 0], S[:, 3], S[:, 4], S[:, 3], S[:, 1], S[:, 5], S[:, 4], S[:, 5], S[:, 2]], axis=-1).reshape(4, 3, 3)
+        Iv = lambda v: _mv(Rl[k], _mv(S, _mtv(Rl[k], v)))
+        mk = inr["mass"][:, k][:, None]
+        rc.append(_mv(Rl[k], inr["com"][:, k]))
+        d.append(p[k + 1] - p[k])
+        ac, an, Nk = ap + x(al, rc[k]), ap + x(al, d[k]), Iv(al)
+        if vel:
+            ac = ac + x(w, x(w, rc[k]))
+            an = an + x(w, x(w, d[k]))
+            Nk = Nk + x(w, Iv(w))
+            F.append(mk * (ac - gb))
+        else:
+            F.append(mk * ac)
+        N.append(Nk)
+        ap = an
+    f, n, tau = np.zeros_like(ap), np.zeros_like(ap), [None] * 3
+    for k in (2, 1, 0):
+        n = ((N[k] + x(rc[k], F[k])) + n) + x(d[k], f)
+        f = F[k] + f
+        tau[k] = (z[k][..., 0] * n[..., 0] + z[k][..., 1] * n[..., 1]) + z[k][..., 2] * n[..., 2]
+    return np.stack(tau, axis=-1), ap
+
+
+def _inertia_arrays(inertia):
+    inr = leg_inertia() if inertia is None else inertia
+    return {k: (np.asarray(v, dtype=float) if k != "gravity" else float(v)) for k, v in inr.items()}
+
+
+def leg_dynamics_host(q, qd=None, qdd=None, rot=None, base=None, inertia=None):
+    """The leg's equations of motion (the host counterpart of mpcqp_leg_dynamics, include/mpcqp_joints.h): q [B,4,3], qd / qdd
+    [B,4,3] or None (0), rot [B,3,3] world <- torso or None, base [B,9] the torso's world-frame angular velocity, angular
+    acceleration and linear acceleration of its origin or None (at rest), inertia a dict as `leg_inertia` -> (tau [B,4,3], mass
+    [B,4,3,3], bias [B,4,3]): tau = mass qdd + bias, the joint torques without a foot force."""
+    inr = _inertia_arrays(inertia)
+    q = np.asarray(q, dtype=float)
+    qd = np.zeros_like(q) if qd is None else np.asarray(qd, dtype=float)
+    qdd = np.zeros_like(q) if qdd is None else np.asarray(qdd, dtype=float)
+    B = q.shape[0]
+    R = np.broadcast_to(np.eye(3), (B, 3, 3)) if rot is None else np.asarray(rot, dtype=float)
+    bw = np.zeros((B, 9)) if base is None else np.asarray(base, dtype=float)
+    with np.errstate(invalid="ignore", over="ignore"):
+        w0, al0, a0 = (_mtv(R, bw[:, 3 * k:3 * k + 3])[:, None, :] for k in range(3))
+        gb = (R[:, 2, :] * inr["gravity"])[:, None, :]
+        chain = _leg_chain(q)
+        tau = _leg_rnea(inr, chain, w0, al0, a0, gb, qd, qdd)[0]
+        bias = _leg_rnea(inr, chain, w0, al0, a0, gb, qd, np.zeros_like(q))[0]
+        cols = [_leg_rnea(inr, chain, None, None, None, None, None, np.broadcast_to(np.eye(3)[j], q.shape), vel=False)[0] for j in range(3)]
+    return tau, np.stack(cols, axis=-1), bias
+
+
+def plant_base_acc_host(actual, forces, feet, body=None, gravity=-9.81):
+    """What base_acc = None means in `leg_effort_host` / mpcqp_leg_effort: the unpushed plant's right-hand side at every row of a log,
+    [B,T,6] = (alpha, a) in world axes; a = sum f / m + g e_z, alpha = R I_b^-1 (R^T sum (foot - CoM) x f - wb x I_b wb), wb = R^T
+    omega, in the plant's operation order.  body [B,7] or None (the default handle's model); an invalid row gives NaN."""
+    from . import plant
+    actual, forces, feet = (np.asarray(a, dtype=float) for a in (actual, forces, feet))
+    B, T = actual.shape[:2]
+    bd = np.broadcast_to(_BODY, (B, 7)) if body is None else np.asarray(body, dtype=float)
+    bd = [np.repeat(bd[:, i][:, None], T, axis=1) for i in range(7)]
+    with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+        Ii, ok = plant.inertia_inverse(bd[0], bd[1:])
+        R = plant.quat_to_matrix(plant.rotvec_to_quat(actual[..., 0:3])).reshape(B, T, 9)
+        R = [R[..., a] for a in range(9)]
+        f = forces.reshape(B, T, 4, 3)
+        fk = [[f[:, :, k, a] for a in range(3)] for k in range(4)]
+        cr = [plant._cross([feet[:, :, k, a] - actual[..., 3 + a] for a in range(3)], fk[k]) for k in range(4)]
+        Fs = [(fk[0][a] + fk[1][a]) + (fk[2][a] + fk[3][a]) for a in range(3)]      # the device's sum across the row's four lanes
+        Ms = [(cr[0][a] + cr[1][a]) + (cr[2][a] + cr[3][a]) for a in range(3)]
+        om = [actual[..., 6 + a] for a in range(3)]
+        wb = [(R[a] * om[0] + R[3 + a] * om[1]) + R[6 + a] * om[2] for a in range(3)]
+        tb = [(R[a] * Ms[0] + R[3 + a] * Ms[1]) + R[6 + a] * Ms[2] for a in range(3)]
+        aw = [Fs[a] / bd[0] for a in range(3)]
+        aw[2] = aw[2] + gravity
+        gy = plant._cross(wb, plant._symv(bd[1:], wb))
+        e = plant._symv(Ii, [tb[a] - gy[a] for a in range(3)])
+        alw = [(R[3 * a] * e[0] + R[3 * a + 1] * e[1]) + R[3 * a + 2] * e[2] for a in range(3)]
+        out = np.stack(alw + aw, axis=-1)
+    return np.where(ok[..., None], out, np.nan)
+
+
+def leg_effort_host(actual, forces, feet, foot_vel=None, foot_acc=None, base_acc=None, body=None, inertia=None):
+    """The full joint torques of a roll-out's log (the host counterpart of mpcqp_leg_effort, include/mpcqp_joints.h): the operands of
+    `joint_rates_host` plus foot_acc [B,T,4,3] (None = 0), base_acc [B,T,6] world (alpha, a) of the torso / CoM (None =
+    `plant_base_acc_host` with `body`) and inertia (a dict as `leg_inertia`) -> {"q", "qd", "tau_f", "reach"} of `joint_rates_host`
+    and {"qdd", "tau_dyn", "tau" [B,T,4,3], "power" [B,T,4], "limit" uint8 [B,T,4]}.  qdd = J^-1 (R^T foot_acc - the foot point's
+    acceleration in the recursion at qdd = 0) by the rates' adjugate and determinant; tau_dyn = the recursion at (q, qd, qdd);
+    tau = tau_f + tau_dyn; power = tau_f . qd + tau_dyn . qd; limit bits 1: q, 2: qd, 4: tau beyond the row's limits, 8: out of
+    reach; a non-finite leg: NaN and 0xff."""
+    from . import plant
+    inr = _inertia_arrays(inertia)
+    q, qd, tau_f, power_f, reach = joint_rates_host(actual, forces, feet, foot_vel)
+    actual, forces = np.asarray(actual, dtype=float), np.asarray(forces, dtype=float)
+    B, T = actual.shape[:2]
+    fa = np.zeros((B, T, 4, 3)) if foot_acc is None else np.asarray(foot_acc, dtype=float)
+    if base_acc is None:
+        base_acc = plant_base_acc_host(actual, forces, feet, body, inr["gravity"])
+    base_acc = np.asarray(base_acc, dtype=float)
+    with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+        R = plant.quat_to_matrix(plant.rotvec_to_quat(actual[..., 0:3]))
+        w0, al0, a0 = (_mtv(R, v)[:, :, None, :] for v in (actual[..., 6:9], base_acc[..., 0:3], base_acc[..., 3:6]))
+        gb = (R[..., 2, :] * inr["gravity"])[:, :, None, :]
+        chain = _leg_chain(q)
+        z, p = chain[1], chain[2]
+        J = np.stack([np.cross(z[k], p[3] - p[k]) for k in range(3)], axis=-1)
+        j = [J[..., a // 3, a % 3] for a in range(9)]
+        c = [[j[4] * j[8] - j[5] * j[7], j[5] * j[6] - j[3] * j[8], j[3] * j[7] - j[4] * j[6]],
+             [j[2] * j[7] - j[1] * j[8], j[0] * j[8] - j[2] * j[6], j[1] * j[6] - j[0] * j[7]],
+             [j[1] * j[5] - j[2] * j[4], j[2] * j[3] - j[0] * j[5], j[0] * j[4] - j[1] * j[3]]]
+        det = j[0] * c[0][0] + j[1] * c[0][1] + j[2] * c[0][2]
+        move = (reach != 0) & (det != 0.0)
+        af0 = _leg_rnea(inr, chain, w0, al0, a0, gb, qd, np.zeros_like(q))[1]
+        h = _mtv(R[:, :, None], fa) - af0
+        qdd = np.stack([(c[0][k] * h[..., 0] + c[1][k] * h[..., 1] + c[2][k] * h[..., 2]) / det for k in range(3)], axis=-1)
+        qdd = np.where(move[..., None], qdd, 0.0)
+        tau_dyn = _leg_rnea(inr, chain, w0, al0, a0, gb, qd, qdd)[0]
+        tau = tau_f + tau_dyn
+        power = power_f + ((tau_dyn[..., 0] * qd[..., 0] + tau_dyn[..., 1] * qd[..., 1]) + tau_dyn[..., 2] * qd[..., 2])
+        fin = np.isfinite(base_acc).all(axis=-1)[:, :, None] & np.isfinite(forces.reshape(B, T, 4, 3)).all(axis=-1)
+        for v in (fa, q, qd, qdd, tau_dyn, tau):
+            fin = fin & np.isfinite(v).all(axis=-1)
+        lim = np.where(reach != 0, 0, 8)
+        lim = lim | np.where(((q < inr["q_min"]) | (q > inr["q_max"])).any(axis=-1), 1, 0)
+        lim = lim | np.where((np.abs(qd) > inr["qd_max"]).any(axis=-1), 2, 0)
+        lim = lim | np.where((np.abs(tau) > inr["tau_max"]).any(axis=-1), 4, 0)
+    nan3 = lambda v: np.where(fin[..., None], v, np.nan)
+    return {"q": q, "qd": qd, "tau_f": tau_f, "reach": reach, "qdd": nan3(qdd), "tau_dyn": nan3(tau_dyn), "tau": nan3(tau),
+            "power": np.where(fin, power, np.nan), "limit": np.where(fin, lim, 0xff).astype(np.uint8)}
+
+
 def world_jacobians(R_body, q_all):
     """{leg: 3x3 world-frame linear Jacobian block} for joint angles q_all[4,3] (src/main.py:205-210)."""
     return {LEGS[k]: R_body @ leg_fk_jac(k, q_all[k])[1] for k in range(4)}
