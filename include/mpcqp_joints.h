@@ -127,8 +127,8 @@ int mpcqp_joint_rates(mpcqp_handle h, int64_t B, int32_t T, const void* actual, 
  * starting from the torso's w_0, al_0 and a(p_1) = a_0 + al_0 x p_1 + w_0 x (w_0 x p_1).  No foot force enters: the ground's share
  * is the (R J)^T (-f) of the joint log.
  *
- * Not built (each would need state the plant does not carry): the PD terms of the reference's swing-leg controller -- the plant has
- * no leg state, so there is no tracking error to feed back; the reaction of the legs on the torso -- the plant's legs stay massless;
+ * Not in these two calls: the PD terms of the reference's swing-leg controller -- they need a leg state to form a tracking error,
+ * which mpcqp_swing_track below carries; the reaction of the legs on the torso -- the plant's legs stay massless;
  * and the reference's op_space_mi = J*M*J.T, an element-wise product on a block of the mass matrix that is not the leg's:
  * what is computed here is the rigid-body answer, not a copy of that expression.
  */
@@ -198,6 +198,88 @@ int mpcqp_leg_effort(mpcqp_handle h, int64_t B, int32_t T, const void* actual, c
                      const void* foot_vel, const void* foot_acc, const void* base_acc, const void* body,
                      const MpcQpLegGeometry* geo, const MpcQpLegInertia* inr,
                      void* qdd, void* tau_dyn, void* tau, void* power, uint8_t* limit, void* stream);
+
+/*
+ * ---- The swing leg as a controlled plant --------------------------------------------------------------------------------------
+ *
+ * mpcqp_leg_effort assumes the leg exactly on its desired trajectory.  The two calls below give the leg a state of its own: its
+ * forward dynamics, and the swing legs of a roll-out's log integrated under the reference's swing-leg controller with its PD terms
+ * (src/main.py:225-282), so that the foot's actual position, the commanded torque with feedback, its saturation and the landing miss
+ * can be read off.  The coupling is one-way: the torso moves as the log says.
+ *
+ * The leg's forward dynamics for B rows: qdd = M(q)^-1 (tau - bias(q, qd, torso motion, gravity)).
+ *   q, qd, rot, base, geo, inr   as for mpcqp_leg_dynamics (qd, rot, base may be NULL)
+ *   tau     T  [B,4,3]    the applied joint torques (no foot force)
+ *   qdd     T  [B,4,3]    out: joint accelerations in rad / s^2
+ *   det     T  [B,4]      out, may be NULL: det M(q)
+ * M comes column by column from the recursion at unit accelerations without velocity, torso and gravity terms, bias from the recursion
+ * at qdd = 0; the 3x3 system is solved by cofactors and determinant, as the rates solve J.  Massless legs (det M = 0) give qdd = 0.  A
+ * non-finite operand makes qdd NaN in its own leg (q, qd, tau: its leg; rot, base: the four legs of its row); det depends on q alone.
+ * B = 0 is a no-op; B < 0 or B > 0x1fffffff is MPCQP_EINVAL, as are a null q, tau or qdd.
+ */
+int mpcqp_leg_accel(mpcqp_handle h, int64_t B, const void* q, const void* qd, const void* tau, const void* rot, const void* base,
+                    const MpcQpLegGeometry* geo, const MpcQpLegInertia* inr, void* qdd, void* det, void* stream);
+
+/*
+ * The swing legs of a roll-out as a controlled plant: one leg state per (robot, leg), carried through the T rows of the log.
+ *   actual, forces T [B,T,12], feet_log T [B,T,4,3], contact_log u8 [B,T,4]   as mpcqp_rollout_phase logs them
+ *   swing    T  [B,T,4,4,3]  as mpcqp_phase_swing writes it; pos, vel and acc are read.  A stance leg's pos is its held foot and its
+ *                            vel and acc are 0 (what mpcqp_phase_swing writes)
+ *   base_acc T  [B,T,6]      as for mpcqp_leg_effort, or NULL = the unpushed plant's right-hand side at the row, formed as there over
+ *                            the row's forces and the feet the plant held (feet_log), with
+ *   body     T  [B,7]        as for mpcqp_leg_effort (NULL = the handle's model; read only when base_acc is NULL)
+ *   gains    T  [B,2]        (Kp, Kd) of the Cartesian PD in N / m and N s / m, NULL = 250 and 15 (src/main.py:48-49).  The rows are
+ *                            device memory: a negative or non-finite row is not an error, it poisons its robot
+ *   state    T  [B,4,7]      in / out, may be NULL: per leg q (3), qd (3), live.  live != 0: q, qd are a swing state to be continued;
+ *                            0: the leg starts from its row.  NULL = all live = 0, nothing is written back.  On return it holds the
+ *                            state after row T - 1 (live = 1 where that row was a swing row), so a long log can be tracked in pieces
+ *   substeps                 control periods per tick, h = delta / substeps; 0 = ceil(delta / h0) (below); < 0 or > 1000: MPCQP_EINVAL
+ *   geo, inr                 host pointers, NULL = the Lite3 (the closed form's geometry, as for mpcqp_leg_effort)
+ *   q, qd, tau, foot T [B,T,4,3], err T [B,T,4], flag u8 [B,T,4]   out, each may be NULL, at least one required
+ * Sizes as for mpcqp_leg_effort; B = 0 or T = 0 is a no-op.
+ *
+ * Per row and leg.  The on-trajectory state of a row is mpcqp_joint_rates' q, qd at feet = pos, foot_vel = vel.
+ *   Stance row (contact != 0): if the incoming state is live this is a landing row: err = |c + R p_foot(q carried) - pos|, the miss
+ *     between where the simulated leg put the foot and the foothold the plant used, and flag bit 64.  In every case the state becomes
+ *     the on-trajectory state, live = 0; q, qd are that state, tau = (R J)^T (-f) (mpcqp_joint_rates' value, not necessarily its bits),
+ *     foot = c + R p_foot(q), and err = |pos - foot| where the row is no landing row.
+ *   Swing row, state not live (lift-off, or the first row in mid-swing without a given state): the state becomes the on-trajectory
+ *     state of the row, live = 1 (at a lift-off pos is the lift-off foot and vel = 0: the leg starts at rest on the ground); then
+ *   Swing row: q, qd = the state at the start of the row, foot = c + R p_foot(q), err = |pos - foot|, tau = the applied torque of the
+ *     first control period.  Then `substeps` control periods of h; in period k, s = k h:
+ *       torso     c(s) = c + s v + s^2 / 2 a,  v(s) = v + s a,  omega(s) = omega + s alpha  (alpha, a: base_acc); its orientation starts
+ *                 from the row's quaternion and takes one Euler step of the plant's quaternion rate at omega(s) per period, renormalised
+ *       desired   p_des = pos + s vel + s^2 / 2 acc,  v_des = vel + s acc,  a_des = acc
+ *       1  foot = c(s) + R p_foot(q),  foot_vel = v(s) + omega(s) x (R p_foot) + R J qd
+ *       2  F = Kp (p_des - foot) + Kd (v_des - foot_vel)
+ *       3  bias and the foot point's acceleration af0 from the recursion at (q, qd, qdd = 0) on the torso's (omega(s), alpha, a); M(q)
+ *       4  qdd_des = J^-1 (R^T a_des - af0), of the chain's own J; 0 where det J = 0 (flag bit 16)
+ *       5  tau_cmd = (R J)^T F + M qdd_des + bias      computed torque: the rigid-body form of the reference's feed-forward
+ *       6  tau_app = tau_cmd clamped per joint into [-tau_max, tau_max]  (flag bit 2 where it differs)
+ *       7  qdd = M^-1 (tau_app - bias)  (0 where det M = 0)
+ *       8  qd += h qdd;  q += h qd       semi-implicit Euler
+ *   flag: 1 swing (dynamic) row, 2 some period's torque was clamped, 4 q outside [q_min, q_max] (at the start of some period; on a
+ *   stance row: of the logged q), 8 |qd| > qd_max (likewise), 16 det J = 0 in some period or the leg was (re-)initialised out of reach,
+ *   64 landing row; 0xff non-finite.
+ * A non-finite input of the leg's row (its row of actual, its force, held foot, pos / vel / acc, its row of base_acc -- or, with
+ * base_acc NULL, any force or held foot of its row and its robot's body -- its robot's gains, a live state given non-finite) makes
+ * that leg's six outputs NaN / 0xff from that row until its next stance row re-initialises it -- the landing row that ends the swing
+ * included, whatever the input was: the miss of a poisoned swing is not known; the leg is clean from the row after -- and so does a
+ * state that stops being finite; no other leg changes.
+ *
+ * Not built: the legs' reaction on the torso, joint-limit stops (a joint beyond its limit is flagged, not stopped) and ground contact
+ * of a swing foot (a foot below the ground is not stopped; the landing row's err says where it was).
+ *
+ * The default control period.  The explicit step is stable only while h lambda < 2, lambda = max eig(M^-1 J^T Kd J).  Measured on the
+ * host (lite3_model.swing_gain_lambda) at Kd = 15 over the joint box of the IK and dynamics tests (HipX in [-0.5, 0.5], HipY in
+ * [-1.5, -0.2], Knee in [0.5, 2.3], 80 000 legs): lambda = 106.5 / s, so h < 18.8 ms.  h0 is the largest of 2, 1, 0.5, 0.25 ms that is
+ * <= 0.5 / lambda = 4.70 ms (the factor 4 is for the Kp term and the torso coupling, which the bound leaves out): h0 = 2 ms, and
+ * substeps = 0 means ceil(delta / h0) -- 15 periods at delta = 0.03.  Other gains need their own substeps: lambda scales with Kd.
+ */
+int mpcqp_swing_track(mpcqp_handle h, int64_t B, int32_t T, const void* actual, const void* forces, const void* feet_log,
+                      const uint8_t* contact_log, const void* swing, const void* base_acc, const void* body, const void* gains, void* state,
+                      int32_t substeps, const MpcQpLegGeometry* geo, const MpcQpLegInertia* inr, void* q, void* qd, void* tau, void* foot,
+                      void* err, uint8_t* flag, void* stream);
 
 #ifdef __cplusplus
 }

@@ -146,15 +146,21 @@ ABI = {
         ("mpcqp_default_leg_inertia", c_int, (_INR,)),
         ("mpcqp_leg_dynamics", c_int, (_P, _I64) + (_P,) * 5 + (_GEO, _INR) + (_P,) * 4),
         ("mpcqp_leg_effort", c_int, (_P, _I64, _I32) + (_P,) * 7 + (_GEO, _INR) + (_P,) * 6),
+        ("mpcqp_leg_accel", c_int, (_P, _I64) + (_P,) * 5 + (_GEO, _INR) + (_P,) * 3),
+        ("mpcqp_swing_track", c_int, (_P, _I64, _I32) + (_P,) * 9 + (_I32, _GEO, _INR) + (_P,) * 7),
     ),
 }
 EXPORTED_SYMBOLS, PLAN_SYMBOLS, SIM_SYMBOLS, MODEL_SYMBOLS, JOINTS_SYMBOLS = (tuple(row[0] for row in rows) for rows in ABI.values())
+# The swing-leg plant of include/mpcqp_joints.h came after the rest of that header: a product library built before it still has the
+# header's other calls (`has_joints`) and is told apart by `has_legsim`.
+LEGSIM_SYMBOLS = ("mpcqp_leg_accel", "mpcqp_swing_track")
 
 
 class Library:
     """A loaded shared object exporting the mpcqp C-ABI.  `has_plan`, `has_sim`, `has_model` and `has_joints` say whether it exports
-    all of include/mpcqp_plan.h, mpcqp_sim.h, mpcqp_model.h and mpcqp_joints.h.  An extension header's calls are bound only when the
-    library has them all; `partial=True` binds whichever it has (an older build of the product library, in a comparison tool)."""
+    all of include/mpcqp_plan.h, mpcqp_sim.h, mpcqp_model.h and mpcqp_joints.h (of the last: all but LEGSIM_SYMBOLS, which `has_legsim`
+    answers for).  An extension header's calls are bound only when the library has them all; `partial=True` binds whichever it has (an
+    older build of the product library, in a comparison tool)."""
 
     def __init__(self, path: str, partial: bool = False):
         if not os.path.exists(path):
@@ -162,13 +168,15 @@ class Library:
         self.path = path
         self.lib = ctypes.CDLL(path)
         self.calls = {}   # name -> (function or None, its header, which parameters after the handle are addresses): Engine._call
+        self.has_legsim = all(hasattr(self.lib, name) for name in LEGSIM_SYMBOLS)
         for header, rows in ABI.items():
-            have = header == CORE_HEADER or all(hasattr(self.lib, row[0]) for row in rows)
+            have = header == CORE_HEADER or all(hasattr(self.lib, row[0]) for row in rows if row[0] not in LEGSIM_SYMBOLS)
             if header != CORE_HEADER:
                 setattr(self, "has_" + header[len("mpcqp_"):-len(".h")], have)
             for name, restype, argtypes in rows:
                 fn = None
-                if have or (partial and hasattr(self.lib, name)):   # (a symbol of the core header that is missing raises here)
+                bind = have and (self.has_legsim or name not in LEGSIM_SYMBOLS)
+                if bind or (partial and hasattr(self.lib, name)):   # (a symbol of the core header that is missing raises here)
                     fn = getattr(self.lib, name)
                     fn.restype, fn.argtypes = restype, argtypes
                 self.calls[name] = (fn, header, tuple(t not in (_I32, _I64) for t in argtypes[1:]))
@@ -250,6 +258,8 @@ class Engine:
         """The one call path into the library: `args` are the C parameters after the handle, in the C order.  An address of 0 or
         None is passed as NULL; a nonzero return code raises with the library's own message."""
         fn, header, is_address = self.library.calls[name]
+        if fn is None and name in LEGSIM_SYMBOLS and self.library.has_joints:
+            raise MpcQpError(f"{name}: {self.library.path} exports include/{header} without {' / '.join(LEGSIM_SYMBOLS)} (built before them)")
         if fn is None:
             raise MpcQpError(f"{name}: {self.library.path} does not export include/{header} (product library only)")
         if len(args) != len(is_address):
@@ -344,6 +354,16 @@ class Engine:
         """The full joint torques of a roll-out's log and the actuator-limit flags (include/mpcqp_joints.h, mpcqp_leg_effort)."""
         self._call("mpcqp_leg_effort", B, T, actual, forces, feet, foot_vel, foot_acc, base_acc, body, geometry, inertia, qdd, tau_dyn, tau,
                    power, limit, stream)
+
+    def leg_accel_ptr(self, B, q, qd, tau, rot, base, qdd, det=0, geometry=None, inertia=None, stream=0):
+        """The leg's forward dynamics (include/mpcqp_joints.h, mpcqp_leg_accel)."""
+        self._call("mpcqp_leg_accel", B, q, qd, tau, rot, base, geometry, inertia, qdd, det, stream)
+
+    def swing_track_ptr(self, B, T, actual, forces, feet_log, contact_log, swing, base_acc, body, gains, state, substeps, q, qd, tau, foot,
+                        err, flag, geometry=None, inertia=None, stream=0):
+        """The swing legs of a roll-out as a controlled plant (include/mpcqp_joints.h, mpcqp_swing_track)."""
+        self._call("mpcqp_swing_track", B, T, actual, forces, feet_log, contact_log, swing, base_acc, body, gains, state, substeps, geometry,
+                   inertia, q, qd, tau, foot, err, flag, stream)
 
     def torque_map_ptr(self, B, u, jac, tau, stream=0):
         self._call("mpcqp_torque_map", B, u, jac, tau, stream)

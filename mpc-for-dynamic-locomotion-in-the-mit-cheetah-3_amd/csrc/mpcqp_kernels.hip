@@ -26,6 +26,7 @@
 #include "mpcqp_model.h"
 #include "mpcqp_joints.h"
 #include "mpcqp_legdyn.h"
+#include "mpcqp_legsim.h"
 
 #include <cstdio>
 #include <cstdlib>
@@ -1325,6 +1326,64 @@ int mpcqp_leg_effort(mpcqp_handle h, int64_t B, int32_t T, const void* actual, c
                        g, r.k0, r.k1, r.k2, r.lim, (TIO*)qdd, (TIO*)tau_dyn, (TIO*)tau, (TIO*)power, limit, rows, (int64_t)T);
   });
   return launched(h, "leg effort kernel launch");
+}
+
+int mpcqp_leg_accel(mpcqp_handle h, int64_t B, const void* q, const void* qd, const void* tau, const void* rot, const void* base,
+                    const MpcQpLegGeometry* geo, const MpcQpLegInertia* inr, void* qdd, void* det, void* stream) {
+  if (!h) return MPCQP_EINVAL;
+  if (B < 0 || B > 0x1fffffff) return fail(h, MPCQP_EINVAL, "mpcqp_leg_accel: batch size out of range");
+  if (B > 0 && !q) return fail(h, MPCQP_EINVAL, "mpcqp_leg_accel: null q buffer");
+  if (B > 0 && !tau) return fail(h, MPCQP_EINVAL, "mpcqp_leg_accel: null tau buffer");
+  if (B > 0 && !qdd) return fail(h, MPCQP_EINVAL, "mpcqp_leg_accel: null qdd buffer");
+  LegGeoDev g;
+  if (const int rc = leg_fk_geometry(h, "mpcqp_leg_accel", geo, g)) return rc;
+  LegInrDev r;
+  if (const int rc = leg_inertia_row(h, "mpcqp_leg_accel", inr, r)) return rc;
+  if (B == 0) return MPCQP_OK;
+  DeviceGuard guard(h->cfg.device);
+  if (guard.err != hipSuccess) return fail(h, MPCQP_EHIP, "hipSetDevice", guard.err);
+  const dim3 grid((unsigned)((4 * B + 255) / 256));
+  with_io(h, [&](auto tag) {
+    using T = decltype(tag);
+    hipLaunchKernelGGL((mpcqp_leg_accel_kernel<T>), grid, dim3(256), 0, (hipStream_t)stream, (const T*)q, (const T*)qd, (const T*)tau,
+                       (const T*)rot, (const T*)base, g, r.k0, r.k1, r.k2, r.lim, (T*)qdd, (T*)det, B);
+  });
+  return launched(h, "leg acceleration kernel launch");
+}
+
+int mpcqp_swing_track(mpcqp_handle h, int64_t B, int32_t T, const void* actual, const void* forces, const void* feet_log,
+                      const uint8_t* contact_log, const void* swing, const void* base_acc, const void* body, const void* gains, void* state,
+                      int32_t substeps, const MpcQpLegGeometry* geo, const MpcQpLegInertia* inr, void* q, void* qd, void* tau, void* foot,
+                      void* err, uint8_t* flag, void* stream) {
+  if (!h) return MPCQP_EINVAL;
+  if (B < 0 || B > 0x7fffffff || T < 0 || B * (int64_t)T > 0x1fffffff) return fail(h, MPCQP_EINVAL, "mpcqp_swing_track: size out of range");
+  if (substeps < 0 || substeps > SWING_MAX_SUBSTEPS) return fail(h, MPCQP_EINVAL, "mpcqp_swing_track: substeps out of range [0, 1000]");
+  if (!q && !qd && !tau && !foot && !err && !flag)
+    return fail(h, MPCQP_EINVAL, "mpcqp_swing_track: no output buffer (q, qd, tau, foot, err and flag are all null)");
+  if (B > 0 && T > 0 && (!actual || !forces || !feet_log || !contact_log || !swing)) return fail(h, MPCQP_EINVAL, "mpcqp_swing_track: null buffer");
+  LegGeoDev g;
+  if (const int rc = leg_ik_geometry(h, "mpcqp_swing_track", geo, g)) return rc;
+  LegInrDev r;
+  if (const int rc = leg_inertia_row(h, "mpcqp_swing_track", inr, r)) return rc;
+  if (B == 0 || T == 0) return MPCQP_OK;
+  int n = substeps;
+  if (n == 0) {   // the default control period: the fewest periods of at most SWING_H0
+    n = (int)std::ceil(h->cfg.delta / SWING_H0);
+    while (n > 1 && h->cfg.delta / (n - 1) <= SWING_H0) --n;   // (delta / h0 a whole number up to rounding)
+    n = n < 1 ? 1 : (n > SWING_MAX_SUBSTEPS ? SWING_MAX_SUBSTEPS : n);
+  }
+  DeviceGuard guard(h->cfg.device);
+  if (guard.err != hipSuccess) return fail(h, MPCQP_EHIP, "hipSetDevice", guard.err);
+  const dim3 grid((unsigned)((4 * B + 255) / 256));
+  with_io(h, [&](auto tag) {
+    using TIO = decltype(tag);
+    const SwingIn<TIO> in = {(const TIO*)actual, (const TIO*)forces, (const TIO*)feet_log, contact_log, (const TIO*)swing,
+                             (const TIO*)base_acc, (const TIO*)body, (const TIO*)gains};
+    const SwingOut<TIO> out = {(TIO*)q, (TIO*)qd, (TIO*)tau, (TIO*)foot, (TIO*)err, flag};
+    hipLaunchKernelGGL((mpcqp_swing_track_kernel<TIO>), grid, dim3(256), 0, (hipStream_t)stream, in, (TIO*)state, plant_model(h), g, r.k0,
+                       r.k1, r.k2, r.lim, out, B, (int)T, n, h->cfg.delta / n);
+  });
+  return launched(h, "swing track kernel launch");
 }
 
 int mpcqp_last_kernel_ms(mpcqp_handle h, float* ms) {

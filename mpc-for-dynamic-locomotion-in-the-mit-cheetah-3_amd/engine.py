@@ -443,5 +443,54 @@ class MPCBatch:
                                    self._inertia(inertia), st.cuda_stream)
         return {"qdd": qdd, "tau_dyn": tau_dyn, "tau": tau, "power": power, "limit": limit}
 
+    def leg_accel(self, q, tau, qd=None, rot=None, base=None, inertia=None, geometry=None, want_det=True, stream=None):
+        """The leg's forward dynamics on the device (include/mpcqp_joints.h, mpcqp_leg_accel; the host counterpart is
+        lite3_model.leg_accel_host): the operands of `leg_dynamics` with the applied joint torques tau [B,4,3] on the input side ->
+        {"qdd": [B,4,3] = M^-1 (tau - bias), "det": [B,4] = det M(q) or None}.  Massless legs: qdd = 0.  Asynchronous on `stream`."""
+        B = int(q.shape[0])
+        legs = (B, 4, 3)
+        check_operands(self.device, (("q", q, legs, self.tdtype), ("tau", tau, legs, self.tdtype), ("qd", qd, legs, self.tdtype),
+                                     ("rot", rot, (B, 3, 3), self.tdtype), ("base", base, (B, 9), self.tdtype)),
+                       optional=("qd", "rot", "base"))
+        st = self._stream(stream)
+        qdd, det = self._alloc(stream, (legs, self.tdtype), ((B, 4), self.tdtype) if want_det else None)
+        self.engine.leg_accel_ptr(B, q.data_ptr(), _ptr(qd), tau.data_ptr(), _ptr(rot), _ptr(base), qdd.data_ptr(), _ptr(det), geometry,
+                                  self._inertia(inertia), st.cuda_stream)
+        return {"qdd": qdd, "det": det}
+
+    from .lite3_model import SWING_OUT      # ("q", "qd", "tau", "foot", "err", "flag"): the host counterpart's names, in the C order
+
+    def swing_track(self, logs, swing, body=None, base_acc=None, gains=None, state=None, substeps=0, inertia=None, geometry=None,
+                    want=SWING_OUT, stream=None):
+        """The swing legs of a roll-out under their tracking controller, on the device (include/mpcqp_joints.h, mpcqp_swing_track; the
+        host counterpart is lite3_model.swing_track_host): `logs` as `rollout_phase` returns them ("actual", "forces", "feet_log",
+        "contact_log"), swing [B,T,4,4,3] the "swing" of `phase_swing`; base_acc [B,T,6] or None for the unpushed plant's right-hand
+        side formed with body [B,7] (None = the engine's model); gains [B,2] = (Kp, Kd) or None (250, 15); state [B,4,7] = per leg q,
+        qd, live, advanced IN PLACE, or None (every leg starts from its row); `substeps` control periods per tick (0: 2 ms periods) ->
+        {"q", "qd", "tau", "foot" [B,T,4,3], "err" [B,T,4] = |desired - actual foot| and on a landing row the landing miss, "flag" uint8
+        [B,T,4]: 1 swing row, 2 torque clamped, 4 joint angle, 8 joint rate beyond its limit, 16 singular, 64 landing row, 0xff
+        non-finite}; an output not in `want` is None.  Asynchronous on `stream`."""
+        torch = _torch()
+        actual, forces, feet_log, contact = logs["actual"], logs["forces"], logs["feet_log"], logs["contact_log"]
+        if actual is None or actual.dim() != 3:
+            raise ValueError("swing_track needs the logs of rollout_phase(..., log=True)")
+        B, T = int(actual.shape[0]), int(actual.shape[1])
+        legs = ((B, T, 4, 3), self.tdtype)
+        check_operands(self.device, (("actual", actual, (B, T, 12), self.tdtype), ("forces", forces, (B, T, 12), self.tdtype),
+                                     ("feet_log", feet_log, *legs), ("contact_log", contact, (B, T, 4), torch.uint8),
+                                     ("swing", swing, (B, T, 4, 4, 3), self.tdtype), ("base_acc", base_acc, (B, T, 6), self.tdtype),
+                                     ("body", body, (B, 7), self.tdtype), ("gains", gains, (B, 2), self.tdtype),
+                                     ("state", state, (B, 4, 7), self.tdtype)), optional=("base_acc", "body", "gains", "state"))
+        unknown = set(want) - set(self.SWING_OUT)
+        if unknown or not want:
+            raise ValueError(f"want must name at least one of {self.SWING_OUT}, got {tuple(want)}")
+        st = self._stream(stream)
+        spec = {"q": legs, "qd": legs, "tau": legs, "foot": legs, "err": ((B, T, 4), self.tdtype), "flag": ((B, T, 4), torch.uint8)}
+        out = dict(zip(self.SWING_OUT, self._alloc(stream, *[spec[k] if k in want else None for k in self.SWING_OUT])))
+        self.engine.swing_track_ptr(B, T, actual.data_ptr(), forces.data_ptr(), feet_log.data_ptr(), contact.data_ptr(), swing.data_ptr(),
+                                    _ptr(base_acc), _ptr(body), _ptr(gains), _ptr(state), int(substeps),
+                                    *[_ptr(out[k]) for k in self.SWING_OUT], geometry, self._inertia(inertia), st.cuda_stream)
+        return out
+
     def last_kernel_ms(self):
         return self.engine.last_kernel_ms()

@@ -359,6 +359,214 @@ def leg_effort_host(actual, forces, feet, foot_vel=None, foot_acc=None, base_acc
             "power": np.where(fin, power, np.nan), "limit": np.where(fin, lim, 0xff).astype(np.uint8)}
 
 
+# ---- the swing leg as a controlled plant (the host counterparts of mpcqp_leg_accel / mpcqp_swing_track, include/mpcqp_joints.h) ----
+SWING_KP, SWING_KD = 250.0, 15.0      # gains = None: N / m and N s / m (src/main.py:48-49)
+SWING_H0 = 2e-3                       # the default control period in s (include/mpcqp_joints.h has the bound it comes from)
+SWING_MAX_SUBSTEPS = 1000
+SWING_OUT = ("q", "qd", "tau", "foot", "err", "flag")
+
+
+def _adj_solve(A, h):
+    """x = A^-1 h of 3x3 systems [...,3,3], [...,3] by cofactors and determinant, in the order the rates solve J -> (x, det)."""
+    a = [A[..., k // 3, k % 3] for k in range(9)]
+    c = [[a[4] * a[8] - a[5] * a[7], a[5] * a[6] - a[3] * a[8], a[3] * a[7] - a[4] * a[6]],
+         [a[2] * a[7] - a[1] * a[8], a[0] * a[8] - a[2] * a[6], a[1] * a[6] - a[0] * a[7]],
+         [a[1] * a[5] - a[2] * a[4], a[2] * a[3] - a[0] * a[5], a[0] * a[4] - a[1] * a[3]]]
+    det = a[0] * c[0][0] + a[1] * c[0][1] + a[2] * c[0][2]
+    x = np.stack([(c[0][k] * h[..., 0] + c[1][k] * h[..., 1] + c[2][k] * h[..., 2]) / det for k in range(3)], axis=-1)
+    return x, det
+
+
+def _leg_mass(inr, chain, shape):
+    """M(q) [...,4,3,3] of a chain: column j is the recursion at a unit qdd_j without velocity, torso and gravity terms."""
+    cols = [_leg_rnea(inr, chain, None, None, None, None, None, np.broadcast_to(np.eye(3)[j], shape), vel=False)[0] for j in range(3)]
+    return np.stack(cols, axis=-1)
+
+
+def _dot3(a, b):
+    return (a[..., 0] * b[..., 0] + a[..., 1] * b[..., 1]) + a[..., 2] * b[..., 2]
+
+
+def leg_accel_host(q, tau, qd=None, rot=None, base=None, inertia=None):
+    """The leg's forward dynamics (the host counterpart of mpcqp_leg_accel, include/mpcqp_joints.h): the operands of
+    `leg_dynamics_host` with the applied joint torques tau [B,4,3] on the input side -> (qdd [B,4,3], det [B,4] = det M(q));
+    qdd = M^-1 (tau - bias) by cofactors and determinant, 0 where det M = 0 (massless legs), NaN in a leg with a non-finite operand."""
+    inr = _inertia_arrays(inertia)
+    q, tau = np.asarray(q, dtype=float), np.asarray(tau, dtype=float)
+    qd = np.zeros_like(q) if qd is None else np.asarray(qd, dtype=float)
+    B = q.shape[0]
+    R = np.broadcast_to(np.eye(3), (B, 3, 3)) if rot is None else np.asarray(rot, dtype=float)
+    bw = np.zeros((B, 9)) if base is None else np.asarray(base, dtype=float)
+    with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+        w0, al0, a0 = (_mtv(R, bw[:, 3 * k:3 * k + 3])[:, None, :] for k in range(3))
+        gb = (R[:, 2, :] * inr["gravity"])[:, None, :]
+        chain = _leg_chain(q)
+        bias = _leg_rnea(inr, chain, w0, al0, a0, gb, qd, np.zeros_like(q))[0]
+        x, det = _adj_solve(_leg_mass(inr, chain, q.shape), tau - bias)
+        x = np.where((det != 0.0)[..., None], x, 0.0)
+        fin = np.isfinite(q).all(axis=-1) & np.isfinite(qd).all(axis=-1) & np.isfinite(tau).all(axis=-1)
+        fin = fin & (np.isfinite(R).all(axis=(1, 2)) & np.isfinite(bw).all(axis=1))[:, None] & np.isfinite(x).all(axis=-1)
+    return np.where(fin[..., None], x, np.nan), det
+
+
+def swing_substeps(delta, substeps=0):
+    """The number of control periods per tick: `substeps`, or ceil(delta / SWING_H0) for 0 (mpcqp_swing_track's rule)."""
+    substeps = int(substeps)
+    if substeps < 0 or substeps > SWING_MAX_SUBSTEPS:
+        raise ValueError(f"substeps must be in [0, {SWING_MAX_SUBSTEPS}], got {substeps}")
+    if substeps:
+        return substeps
+    n = int(np.ceil(float(delta) / SWING_H0))
+    while n > 1 and float(delta) / (n - 1) <= SWING_H0:      # (delta / h0 a whole number up to rounding)
+        n -= 1
+    return min(max(n, 1), SWING_MAX_SUBSTEPS)
+
+
+def swing_gain_lambda(q, kd=SWING_KD, inertia=None):
+    """max eig(M(q)^-1 J(q)^T kd J(q)) per leg of q [n,4,3]: the stiffness of the damping term that the explicit step has to resolve
+    (h lambda < 2)."""
+    inr = _inertia_arrays(inertia)
+    q = np.asarray(q, dtype=float)
+    chain = _leg_chain(q)
+    z, p = chain[1], chain[2]
+    J = np.stack([np.cross(z[k], p[3] - p[k]) for k in range(3)], axis=-1)
+    M = _leg_mass(inr, chain, q.shape)
+    A = np.linalg.solve(M, kd * np.einsum("...ki,...kj->...ij", J, J))
+    return np.abs(np.linalg.eigvals(A)).max(axis=-1)
+
+
+def swing_track_host(actual, forces, feet_log, contact_log, swing, base_acc=None, body=None, gains=None, state=None, substeps=0,
+                     delta=0.03, inertia=None):
+    """The swing legs of a roll-out as a controlled plant (the host counterpart of mpcqp_swing_track, include/mpcqp_joints.h, in the
+    device's operation order): actual, forces [B,T,12], feet_log [B,T,4,3], contact_log [B,T,4] as `rollout_phase` logs them, swing
+    [B,T,4,4,3] as `phase_swing` writes it, base_acc [B,T,6] or None (`plant_base_acc_host` at feet_log with `body`), gains [B,2] =
+    (Kp, Kd) or None (250, 15), state [B,4,7] = (q, qd, live) per leg or None, `substeps` control periods per tick of `delta` s (0:
+    `swing_substeps`) -> {"q", "qd", "tau", "foot" [B,T,4,3], "err" [B,T,4], "flag" uint8 [B,T,4], "state" [B,4,7]}.  A stance row
+    logs `joint_rates_host`'s q, qd, tau and re-initialises the leg; a swing row logs the carried state, the applied torque of its
+    first control period, and integrates the leg under computed torque plus Cartesian PD, clamped at tau_max, over the tick.
+    "margin" [B,T,4] (host only) is the row's smallest distance |value - threshold| / max(1, |threshold|) to a joint, rate or torque
+    limit over its control periods, to det J = 0 and, where the leg is (re-)initialised, to the reach decision: where it is tiny a rounding difference may flip a flag bit."""
+    from . import plant
+    inr = _inertia_arrays(inertia)
+    actual, forces, feet_log, swing = (np.asarray(a, dtype=float) for a in (actual, forces, feet_log, swing))
+    contact = np.asarray(contact_log)
+    B, T = actual.shape[:2]
+    n = swing_substeps(delta, substeps)
+    h = float(delta) / n
+    pos, vel, acc = swing[:, :, :, 0], swing[:, :, :, 1], swing[:, :, :, 2]
+    f = forces.reshape(B, T, 4, 3)
+    g = inr["gravity"]
+    if base_acc is None:
+        base_acc = plant_base_acc_host(actual, forces, feet_log, body, g)
+    base_acc = np.asarray(base_acc, dtype=float)
+    gn = np.broadcast_to(np.array([SWING_KP, SWING_KD]), (B, 2)) if gains is None else np.asarray(gains, dtype=float)
+    with np.errstate(invalid="ignore"):
+        gain_ok = np.isfinite(gn).all(axis=1) & (gn >= 0.0).all(axis=1)
+    kp, kd = gn[:, 0][:, None, None], gn[:, 1][:, None, None]
+    if state is None:
+        sq, sqd, live = np.zeros((B, 4, 3)), np.zeros((B, 4, 3)), np.zeros((B, 4), bool)
+    else:
+        state = np.asarray(state, dtype=float)
+        sq, sqd = state[:, :, 0:3].copy(), state[:, :, 3:6].copy()
+        with np.errstate(invalid="ignore"):
+            live = ~(state[:, :, 6] == 0.0)
+    bad = live & ~(np.isfinite(sq).all(axis=-1) & np.isfinite(sqd).all(axis=-1))
+    if B and T:
+        q_on, qd_on, tau_f, _, reach = joint_rates_host(actual, forces, pos, vel)      # the on-trajectory state of every row
+    out = {k: np.zeros((B, T, 4, 3)) for k in ("q", "qd", "tau", "foot")}
+    out["err"], out["flag"] = np.zeros((B, T, 4)), np.zeros((B, T, 4), np.uint8)
+    tmax, zero = inr["tau_max"], np.zeros((B, 4, 3))
+    norm = lambda d: np.sqrt((d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1]) + d[..., 2] * d[..., 2])
+    limits = lambda q_, qd_: (np.where(((q_ < inr["q_min"]) | (q_ > inr["q_max"])).any(axis=-1), 4, 0)
+                              | np.where((np.abs(qd_) > inr["qd_max"]).any(axis=-1), 8, 0))
+    rel = lambda val, thr: (np.abs(val - thr) / np.maximum(1.0, np.abs(thr))).min(axis=-1)      # distance to a threshold, per leg
+    margins = lambda q_, qd_: np.minimum(np.minimum(rel(q_, inr["q_min"]), rel(q_, inr["q_max"])), rel(np.abs(qd_), inr["qd_max"]))
+    out["margin"] = np.full((B, T, 4), np.inf)
+    with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+        for t in range(T):
+            x = actual[:, t]
+            qt = plant.rotvec_to_quat(x[:, 0:3])
+            R = plant.quat_to_matrix(qt)
+            c, om, v = x[:, None, 3:6], x[:, None, 6:9], x[:, None, 9:12]
+            alw, aw = base_acc[:, t, None, 0:3], base_acc[:, t, None, 3:6]
+            fin = np.isfinite(x).all(axis=1)[:, None] & np.isfinite(base_acc[:, t]).all(axis=1)[:, None] & gain_ok[:, None]
+            for a in (pos[:, t], vel[:, t], acc[:, t], f[:, t], feet_log[:, t]):
+                fin = fin & np.isfinite(a).all(axis=-1)
+            stance = contact[:, t] != 0
+            landing = stance & live
+            miss = norm((c + _mv(R[:, None], _leg_chain(sq)[2][3])) - pos[:, t])
+            init = stance | ~live
+            carried_bad = landing & bad                                            # a poisoned swing ends NaN: its miss is not known
+            sq, sqd = np.where(init[..., None], q_on[:, t], sq), np.where(init[..., None], qd_on[:, t], sqd)
+            bad = np.where(init, ~fin, bad | ~fin)
+            live = ~stance
+            bits = np.where(stance, np.where(landing, 64, 0), 1) | np.where(init & (reach[:, t] == 0), 16, 0)
+            foot = c + _mv(R[:, None], _leg_chain(sq)[2][3])
+            out["q"][:, t], out["qd"][:, t], out["foot"][:, t] = sq, sqd, foot
+            out["err"][:, t] = np.where(landing, miss, norm(pos[:, t] - foot))
+            bits = bits | np.where(stance, limits(sq, sqd), 0)
+            marg = margins(sq, sqd)
+            # ... and of the reach decision where the leg was (re-)initialised: the closed form's three comparisons
+            pt = _mtv(R[:, None], pos[:, t] - c) - _HIPX
+            wr_ = (pt[..., 1] * pt[..., 1] + pt[..., 2] * pt[..., 2]) - _HIPY[:, 1] * _HIPY[:, 1]
+            rr_ = np.sqrt(pt[..., 0] * pt[..., 0] + np.maximum(wr_, 0.0))
+            l1_, l2_ = -_KNEE[2], -_FOOT[2]
+            marg = np.where(init, np.minimum(marg, np.minimum(np.abs(wr_), np.minimum(np.abs(rr_ - abs(l1_ - l2_)), np.abs(rr_ - (l1_ + l2_))))), marg)
+            tau_log = tau_f[:, t]
+            if live.any():
+                dq, dqd, dbits = sq, sqd, np.zeros((B, 4), np.int64)
+                Rk = R
+                for k in range(n):
+                    s = k * h
+                    cs, vs, oms = (c + s * v) + (0.5 * s * s) * aw, v + s * aw, om + s * alw
+                    pd, vd = (pos[:, t] + s * vel[:, t]) + (0.5 * s * s) * acc[:, t], vel[:, t] + s * acc[:, t]
+                    chain = _leg_chain(dq)
+                    z, p = chain[1], chain[2]
+                    J = np.stack([np.cross(z[j], p[3] - p[j]) for j in range(3)], axis=-1)
+                    Rl = Rk[:, None]
+                    rp = _mv(Rl, p[3])
+                    jq = (J[..., 0] * dqd[..., 0:1] + J[..., 1] * dqd[..., 1:2]) + J[..., 2] * dqd[..., 2:3]
+                    fv = (vs + np.cross(oms, rp)) + _mv(Rl, jq)
+                    F = kp * (pd - (cs + rp)) + kd * (vd - fv)
+                    w0, al0, a0 = _mtv(Rk, oms[:, 0])[:, None], _mtv(Rk, alw[:, 0])[:, None], _mtv(Rk, aw[:, 0])[:, None]
+                    gb = (Rk[:, 2, :] * g)[:, None, :]
+                    bias, af0 = _leg_rnea(inr, chain, w0, al0, a0, gb, dqd, zero)
+                    M = _leg_mass(inr, chain, dq.shape)
+                    qdes, detj = _adj_solve(J, _mtv(Rl, acc[:, t]) - af0)
+                    qdes = np.where((detj != 0.0)[..., None], qdes, 0.0)
+                    gF = _mtv(Rl, F)
+                    tff = (M[..., 0] * qdes[..., 0:1] + M[..., 1] * qdes[..., 1:2]) + M[..., 2] * qdes[..., 2:3]
+                    cmd = (np.stack([_dot3(J[..., j], gF) for j in range(3)], axis=-1) + tff) + bias
+                    app = np.minimum(np.maximum(cmd, -tmax), tmax)
+                    qdd, detm = _adj_solve(M, app - bias)
+                    qdd = np.where((detm != 0.0)[..., None], qdd, 0.0)
+                    dbits = dbits | limits(dq, dqd) | np.where((app != cmd).any(axis=-1), 2, 0) | np.where(detj == 0.0, 16, 0)
+                    marg = np.where(live, np.minimum(marg, np.minimum(np.minimum(margins(dq, dqd), rel(np.abs(cmd), tmax)), np.abs(detj))), marg)
+                    if k == 0:
+                        tau_log = np.where(stance[..., None], tau_log, app)
+                    dqd = dqd + h * qdd
+                    dq = dq + h * dqd
+                    w, qx, qy, qz = qt[:, 0], qt[:, 1], qt[:, 2], qt[:, 3]      # the plant's quaternion rate at omega(s), one Euler step
+                    o = oms[:, 0]
+                    d = [0.5 * (-((o[:, 0] * qx + o[:, 1] * qy) + o[:, 2] * qz)), 0.5 * (w * o[:, 0] + (o[:, 1] * qz - o[:, 2] * qy)),
+                         0.5 * (w * o[:, 1] + (o[:, 2] * qx - o[:, 0] * qz)), 0.5 * (w * o[:, 2] + (o[:, 0] * qy - o[:, 1] * qx))]
+                    qt = np.stack([qt[:, i] + h * d[i] for i in range(4)], axis=-1)
+                    qt = qt / np.sqrt(((qt[:, 0] * qt[:, 0] + qt[:, 1] * qt[:, 1]) + qt[:, 2] * qt[:, 2]) + qt[:, 3] * qt[:, 3])[:, None]
+                    Rk = plant.quat_to_matrix(qt)
+                sq, sqd = np.where(live[..., None], dq, sq), np.where(live[..., None], dqd, sqd)
+                bits = bits | np.where(live, dbits, 0)
+                bad = bad | (live & ~(np.isfinite(sq).all(axis=-1) & np.isfinite(sqd).all(axis=-1)))
+            out["tau"][:, t], out["margin"][:, t] = tau_log, marg
+            rowbad = bad | carried_bad | ~np.isfinite(tau_log).all(axis=-1) | ~np.isfinite(out["err"][:, t])
+            for k in ("q", "qd", "tau", "foot"):
+                out[k][:, t] = np.where(rowbad[..., None], np.nan, out[k][:, t])
+            out["err"][:, t] = np.where(rowbad, np.nan, out["err"][:, t])
+            out["flag"][:, t] = np.where(rowbad, 0xff, bits).astype(np.uint8)
+    nan3 = lambda a: np.where(bad[..., None], np.nan, a)
+    out["state"] = np.concatenate([nan3(sq), nan3(sqd), live[..., None].astype(float)], axis=-1)
+    return out
+
+
 def world_jacobians(R_body, q_all):
     """{leg: 3x3 world-frame linear Jacobian block} for joint angles q_all[4,3] (src/main.py:205-210)."""
     return {LEGS[k]: R_body @ leg_fk_jac(k, q_all[k])[1] for k in range(4)}
