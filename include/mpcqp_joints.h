@@ -268,7 +268,9 @@ int mpcqp_leg_accel(mpcqp_handle h, int64_t B, const void* q, const void* qd, co
  * state that stops being finite; no other leg changes.
  *
  * Not built: the legs' reaction on the torso, joint-limit stops (a joint beyond its limit is flagged, not stopped) and ground contact
- * of a swing foot (a foot below the ground is not stopped; the landing row's err says where it was).
+ * of a swing foot (a foot below the ground is not stopped; the landing row's err says where it was).  This call runs after the roll-out,
+ * on its logs; mpcqp_rollout_legs (include/mpcqp_sim.h) runs the same row inside the roll-out, tick by tick, and can land a foot where
+ * its leg put it.
  *
  * The default control period.  The explicit step is stable only while h lambda < 2, lambda = max eig(M^-1 J^T Kd J).  Measured on the
  * host (lite3_model.swing_gain_lambda) at Kd = 15 over the joint box of the IK and dynamics tests (HipX in [-0.5, 0.5], HipY in

@@ -37,6 +37,7 @@
 #define MPCQP_SIM_H_
 
 #include "mpcqp.h"
+#include "mpcqp_joints.h"   /* MpcQpLegInertia, for mpcqp_rollout_legs */
 
 #ifdef __cplusplus
 extern "C" {
@@ -101,6 +102,59 @@ int mpcqp_rollout_phase(mpcqp_handle h, int64_t B, int32_t T, void* x, void* ref
                         const void* gain, int32_t* tick, const void* mu, const void* body, const void* push, const int32_t* push_ticks,
                         int32_t substeps, void* actual, void* desired, void* forces, void* feet_log, uint8_t* contact_log,
                         int32_t* solved, void* stream);
+
+/*
+ * mpcqp_rollout_phase with the swing legs integrated inside the roll-out, tick by tick: a leg state per (robot, leg) is carried next to
+ * x, ref, feet and tick, and a foot that touches down may land where its leg put it instead of on the foothold rule.  Every argument of
+ * mpcqp_rollout_phase keeps its meaning.  (A product library built before this call has the header's other three; the Python binding
+ * tells the two apart.)
+ *   legs         double [B,4,7]  in / out, required: per leg q (3), qd (3) and live, in the layout and with the `live` semantics of
+ *                                mpcqp_swing_track's `state` (include/mpcqp_joints.h).  fp64 whatever the I/O dtype: a state that passes
+ *                                through memory every tick must not be rounded to float32 on the way (mpcqp_set_models' rows are doubles
+ *                                for the same reason).  All zeros: every leg starts from its row.
+ *   step_height  T [B]           as for mpcqp_phase_swing
+ *   gains        T [B,2] or NULL, leg_substeps, geo, inr   as `gains`, `substeps`, `geo`, `inr` of mpcqp_swing_track: leg_substeps = 0
+ *                                means control periods of 2 ms, a value below 0 or above 1000 is MPCQP_EINVAL
+ *   land         MPCQP_LAND_RULE or MPCQP_LAND_ACTUAL; anything else is MPCQP_EINVAL
+ *   logs, each may be NULL:
+ *   swing_log    T  [B,T,4,4,3]  pos / vel / acc / target, as mpcqp_phase_swing's `swing`
+ *   q_log, qd_log, tau_log, foot_log   T [B,T,4,3],  err_log T [B,T,4],  flag_log u8 [B,T,4]: mpcqp_swing_track's outputs, with its
+ *                                per-row meaning and flag bits
+ *   miss_log     T  [B,T,4]      the landing miss of a leg that touches down at the tick after row t; 0 for every other leg
+ * Per tick, in this order:
+ *   1. the phase expand and the solve, unchanged
+ *   2. the legs step, one lane per (robot, leg).  It forms the row mpcqp_swing_track would read at this tick from the live buffers:
+ *      actual = x[0..11], forces = the solve's stage-0 forces, the held foot = feet, the stance mask from the gait clock at
+ *      max(tick, 0), swing = mpcqp_phase_swing's rule at this row with desired[8] = ref[9] and desired[9..11] = ref[6..8], as the I/O
+ *      dtype holds it.  Then exactly what mpcqp_swing_track does with a row -- landing / lift-off re-initialisation, the per-row
+ *      outputs, the leg_substeps control periods on a swing row -- and the state goes back to `legs`.  The torso's acceleration over
+ *      the tick is the plant's right-hand side at the row WITH the robot's push where its window is open:
+ *        a = (sum f + F_push) / m + g e_z,   alpha = I_w^-1 (sum r x f + tau_push - omega x I_w omega)
+ *      (the roll-out knows the push; mpcqp_swing_track has to be told through base_acc), formed in fp64 and, like the swing row, held
+ *      as the I/O dtype would hold it in a base_acc row: with float32 I/O mpcqp_swing_track on the logs, given this right-hand side,
+ *      starts every row from the same operands.
+ *   3. the advance of mpcqp_rollout_phase, bit for bit: logs, plant step, ref, tick, rule footholds.  Then, for every leg that touches
+ *      down at the new tick: p_act = c + R p_foot(q) with q from `legs` and c, R from the post-step state as stored (what
+ *      mpcqp_swing_track's landing row calls the miss); miss_log[b,it,l] = |p_act - rule foothold| in 3-D; and with MPCQP_LAND_ACTUAL
+ *      feet[b][l] = (p_act.x, p_act.y, stand_z) instead of the rule's xy.
+ * Five launches per tick, no host synchronisation, copy or allocation inside the T ticks.
+ * Non-finite operands: a non-finite leg state at a landing with MPCQP_LAND_ACTUAL writes a NaN foot; that robot's solves then report
+ * MPCQP_STATUS_NONFINITE and no other robot changes.  A bad gains or step_height row poisons its robot's legs the same way (leg logs NaN,
+ * flag 0xff).  With MPCQP_LAND_RULE a poisoned leg never reaches x or feet: x, ref, feet, tick and the six logs of mpcqp_rollout_phase
+ * are then bit for bit what mpcqp_rollout_phase gives.
+ * MPCQP_EINVAL: as mpcqp_rollout_phase, and a null legs or step_height, leg_substeps or land out of range, an invalid geo / inr row.
+ * Not built: the legs' reaction on the torso (the body's mass already contains the legs: hip forces added naively would count their
+ * weight twice), joint stops, swing-foot ground contact and early / late touchdown (the clock stays open-loop), a variant on plan
+ * tables.
+ */
+#define MPCQP_LAND_RULE 0
+#define MPCQP_LAND_ACTUAL 1
+int mpcqp_rollout_legs(mpcqp_handle h, int64_t B, int32_t T, void* x, void* ref, void* feet, double* legs, const int32_t* gait,
+                       const void* stand, const void* gain, int32_t* tick, const void* mu, const void* body, const void* push,
+                       const int32_t* push_ticks, int32_t substeps, const void* step_height, const void* gains, int32_t leg_substeps,
+                       const MpcQpLegGeometry* geo, const MpcQpLegInertia* inr, int32_t land, void* actual, void* desired, void* forces,
+                       void* feet_log, uint8_t* contact_log, int32_t* solved, void* swing_log, void* q_log, void* qd_log, void* tau_log,
+                       void* foot_log, void* err_log, uint8_t* flag_log, void* miss_log, void* stream);
 
 #ifdef __cplusplus
 }

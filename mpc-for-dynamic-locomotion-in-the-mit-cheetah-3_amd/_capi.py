@@ -134,6 +134,7 @@ ABI = {
         ("mpcqp_plant_step", c_int, (_P, _I64) + (_P,) * 6 + (_I32, _P, _P)),
         ("mpcqp_rollout_plant", c_int, (_P, _I64, _I32, _I32) + (_P,) * 10 + (_I32,) + (_P,) * 5),
         ("mpcqp_rollout_phase", c_int, (_P, _I64, _I32) + (_P,) * 11 + (_I32,) + (_P,) * 7),
+        ("mpcqp_rollout_legs", c_int, (_P, _I64, _I32) + (_P,) * 12 + (_I32, _P, _P, _I32, _GEO, _INR, _I32) + (_P,) * 15),
     ),
     "mpcqp_model.h": (  # per-robot model rows
         ("mpcqp_set_models", c_int, (_P, _I64, _P, _P)),
@@ -154,13 +155,17 @@ EXPORTED_SYMBOLS, PLAN_SYMBOLS, SIM_SYMBOLS, MODEL_SYMBOLS, JOINTS_SYMBOLS = (tu
 # The swing-leg plant of include/mpcqp_joints.h came after the rest of that header: a product library built before it still has the
 # header's other calls (`has_joints`) and is told apart by `has_legsim`.
 LEGSIM_SYMBOLS = ("mpcqp_leg_accel", "mpcqp_swing_track")
+# Likewise the roll-out with the swing legs inside it, which came after the rest of include/mpcqp_sim.h (`has_sim`): `has_legroll`.
+LEGROLL_SYMBOLS = ("mpcqp_rollout_legs",)
+_GATED = {**{name: ("has_legsim", LEGSIM_SYMBOLS) for name in LEGSIM_SYMBOLS}, **{name: ("has_legroll", LEGROLL_SYMBOLS) for name in LEGROLL_SYMBOLS}}
+LAND_RULE, LAND_ACTUAL = 0, 1   # include/mpcqp_sim.h, MPCQP_LAND_*
 
 
 class Library:
     """A loaded shared object exporting the mpcqp C-ABI.  `has_plan`, `has_sim`, `has_model` and `has_joints` say whether it exports
     all of include/mpcqp_plan.h, mpcqp_sim.h, mpcqp_model.h and mpcqp_joints.h (of the last: all but LEGSIM_SYMBOLS, which `has_legsim`
-    answers for).  An extension header's calls are bound only when the library has them all; `partial=True` binds whichever it has (an
-    older build of the product library, in a comparison tool)."""
+    answers for; of mpcqp_sim.h: all but LEGROLL_SYMBOLS, `has_legroll`).  An extension header's calls are bound only when the library
+    has them all; `partial=True` binds whichever it has (an older build of the product library, in a comparison tool)."""
 
     def __init__(self, path: str, partial: bool = False):
         if not os.path.exists(path):
@@ -169,13 +174,14 @@ class Library:
         self.lib = ctypes.CDLL(path)
         self.calls = {}   # name -> (function or None, its header, which parameters after the handle are addresses): Engine._call
         self.has_legsim = all(hasattr(self.lib, name) for name in LEGSIM_SYMBOLS)
+        self.has_legroll = all(hasattr(self.lib, name) for name in LEGROLL_SYMBOLS)
         for header, rows in ABI.items():
-            have = header == CORE_HEADER or all(hasattr(self.lib, row[0]) for row in rows if row[0] not in LEGSIM_SYMBOLS)
+            have = header == CORE_HEADER or all(hasattr(self.lib, row[0]) for row in rows if row[0] not in _GATED)
             if header != CORE_HEADER:
                 setattr(self, "has_" + header[len("mpcqp_"):-len(".h")], have)
             for name, restype, argtypes in rows:
                 fn = None
-                bind = have and (self.has_legsim or name not in LEGSIM_SYMBOLS)
+                bind = have and (name not in _GATED or getattr(self, _GATED[name][0]))
                 if bind or (partial and hasattr(self.lib, name)):   # (a symbol of the core header that is missing raises here)
                     fn = getattr(self.lib, name)
                     fn.restype, fn.argtypes = restype, argtypes
@@ -258,8 +264,8 @@ class Engine:
         """The one call path into the library: `args` are the C parameters after the handle, in the C order.  An address of 0 or
         None is passed as NULL; a nonzero return code raises with the library's own message."""
         fn, header, is_address = self.library.calls[name]
-        if fn is None and name in LEGSIM_SYMBOLS and self.library.has_joints:
-            raise MpcQpError(f"{name}: {self.library.path} exports include/{header} without {' / '.join(LEGSIM_SYMBOLS)} (built before them)")
+        if fn is None and name in _GATED and getattr(self.library, "has_" + header[len("mpcqp_"):-len(".h")]):
+            raise MpcQpError(f"{name}: {self.library.path} exports include/{header} without {' / '.join(_GATED[name][1])} (built before them)")
         if fn is None:
             raise MpcQpError(f"{name}: {self.library.path} does not export include/{header} (product library only)")
         if len(args) != len(is_address):
@@ -318,6 +324,14 @@ class Engine:
         """The roll-out on the plant with a gait clock and reactive footholds (include/mpcqp_sim.h, mpcqp_rollout_phase)."""
         self._call("mpcqp_rollout_phase", B, T, x, ref, feet, gait, stand, gain, tick, mu, body, push, push_ticks, substeps, actual, desired,
                    forces, feet_log, contact_log, solved, stream)
+
+    def rollout_legs_ptr(self, B, T, x, ref, feet, legs, gait, stand, gain, tick, mu, body, push, push_ticks, substeps, step_height, gains,
+                         leg_substeps, land, actual, desired, forces, feet_log, contact_log, solved, swing_log, q_log, qd_log, tau_log,
+                         foot_log, err_log, flag_log, miss_log, geometry=None, inertia=None, stream=0):
+        """The roll-out on a gait clock with the swing legs integrated inside it (include/mpcqp_sim.h, mpcqp_rollout_legs)."""
+        self._call("mpcqp_rollout_legs", B, T, x, ref, feet, legs, gait, stand, gain, tick, mu, body, push, push_ticks, substeps, step_height,
+                   gains, leg_substeps, geometry, inertia, land, actual, desired, forces, feet_log, contact_log, solved, swing_log, q_log,
+                   qd_log, tau_log, foot_log, err_log, flag_log, miss_log, stream)
 
     def phase_swing_ptr(self, B, T, actual, desired, feet_log, gait, tick0, stand, gain, step_height, swing, feet_des=0, stream=0):
         """The swing-foot trajectories of a roll-out on a gait clock, from its logs (include/mpcqp_plan.h, mpcqp_phase_swing)."""

@@ -27,6 +27,7 @@
 #include "mpcqp_joints.h"
 #include "mpcqp_legdyn.h"
 #include "mpcqp_legsim.h"
+#include "mpcqp_legroll.h"
 
 #include <cstdio>
 #include <cstdlib>
@@ -1384,6 +1385,60 @@ int mpcqp_swing_track(mpcqp_handle h, int64_t B, int32_t T, const void* actual, 
                        r.k1, r.k2, r.lim, out, B, (int)T, n, h->cfg.delta / n);
   });
   return launched(h, "swing track kernel launch");
+}
+
+int mpcqp_rollout_legs(mpcqp_handle h, int64_t B, int32_t T, void* x, void* ref, void* feet, double* legs, const int32_t* gait,
+                       const void* stand, const void* gain, int32_t* tick, const void* mu, const void* body, const void* push,
+                       const int32_t* push_ticks, int32_t substeps, const void* step_height, const void* gains, int32_t leg_substeps,
+                       const MpcQpLegGeometry* geo, const MpcQpLegInertia* inr, int32_t land, void* actual, void* desired, void* forces,
+                       void* feet_log, uint8_t* contact_log, int32_t* solved, void* swing_log, void* q_log, void* qd_log, void* tau_log,
+                       void* foot_log, void* err_log, uint8_t* flag_log, void* miss_log, void* stream) {
+  if (!h) return MPCQP_EINVAL;
+  if (B < 0 || B > 0x7fffffff || T < 0 || B * (int64_t)T > 0x7fffffff) return fail(h, MPCQP_EINVAL, "mpcqp_rollout_legs: size out of range");
+  const int n = plant_substeps(substeps);
+  if (n < 0) return fail(h, MPCQP_EINVAL, "mpcqp_rollout_legs: substeps out of range [0, 1000]");
+  if (leg_substeps < 0 || leg_substeps > SWING_MAX_SUBSTEPS) return fail(h, MPCQP_EINVAL, "mpcqp_rollout_legs: leg_substeps out of range [0, 1000]");
+  if (land != MPCQP_LAND_RULE && land != MPCQP_LAND_ACTUAL) return fail(h, MPCQP_EINVAL, "mpcqp_rollout_legs: land is neither MPCQP_LAND_RULE nor MPCQP_LAND_ACTUAL");
+  if (push && !push_ticks) return fail(h, MPCQP_EINVAL, "mpcqp_rollout_legs: push without push_ticks");
+  if (B > 0 && (!x || !ref || !feet || !legs || !gait || !stand || !tick || !mu || !step_height))
+    return fail(h, MPCQP_EINVAL, "mpcqp_rollout_legs: null buffer");
+  LegGeoDev g;
+  if (const int rc = leg_ik_geometry(h, "mpcqp_rollout_legs", geo, g)) return rc;
+  LegInrDev r;
+  if (const int rc = leg_inertia_row(h, "mpcqp_rollout_legs", inr, r)) return rc;
+  if (B == 0 || T == 0) return MPCQP_OK;
+  if (const int rc = models_match(h, B, "mpcqp_rollout_legs")) return rc;
+  int nl = leg_substeps;
+  if (nl == 0) {   // the default control period, as mpcqp_swing_track: the fewest periods of at most SWING_H0
+    nl = (int)std::ceil(h->cfg.delta / SWING_H0);
+    while (nl > 1 && h->cfg.delta / (nl - 1) <= SWING_H0) --nl;
+    nl = nl < 1 ? 1 : (nl > SWING_MAX_SUBSTEPS ? SWING_MAX_SUBSTEPS : nl);
+  }
+  DeviceGuard guard(h->cfg.device);
+  if (guard.err != hipSuccess) return fail(h, MPCQP_EHIP, "hipSetDevice", guard.err);
+  const RolloutPlantArgs plant = {body, push, push ? push_ticks : nullptr, n};
+  const int N = h->cfg.N;
+  const double d = h->cfg.delta;
+  const dim3 ge = expand_grid(B, N), ga = advance_grid(B), gl((unsigned)((4 * B + 255) / 256)), nt(256);
+  hipStream_t st = (hipStream_t)stream;
+  // the roll-out loop of mpcqp_rollout_phase with the legs step in front of its advance and the landing behind it: 5 launches per tick
+  return rollout_loop(h, "mpcqp_rollout_legs", B, T, x, ref, mu, stream,
+    [&](auto tag, auto* xs, auto* rf, const auto& w) {
+      using TIO = decltype(tag);
+      const PhaseRows<TIO> ph = {(const TIO*)feet, gait, (const TIO*)stand, (const TIO*)gain};
+      hipLaunchKernelGGL((mpcqp_phase_expand_kernel<TIO>), ge, nt, 0, st, xs, rf, ph, tick, d, N, B, w.r, w.contact, w.xdes);
+    },
+    [&](auto tag, auto* xs, auto* rf, const auto& o, int it) {
+      using TIO = decltype(tag);
+      const PhaseRows<TIO> ph = {(const TIO*)feet, gait, (const TIO*)stand, (const TIO*)gain};
+      const LegRollOut<TIO> out = {(TIO*)swing_log, (TIO*)q_log, (TIO*)qd_log, (TIO*)tau_log, (TIO*)foot_log, (TIO*)err_log, flag_log};
+      hipLaunchKernelGGL((mpcqp_legs_step_kernel<TIO>), gl, nt, 0, st, xs, rf, ph, tick, o.u, (const TIO*)step_height, (const TIO*)gains, legs,
+                         plant_in<TIO>(h, plant), g, r.k0, r.k1, r.k2, r.lim, out, d, N, B, (int)T, it, nl, d / nl);
+      hipLaunchKernelGGL((mpcqp_phase_advance_kernel<TIO>), ga, nt, 0, st, xs, rf, (TIO*)feet, ph, tick, plant_in<TIO>(h, plant), o.u, o.status, d, N, B,
+                         (int)T, it, (TIO*)actual, (TIO*)desired, (TIO*)forces, (TIO*)feet_log, contact_log, solved);
+      hipLaunchKernelGGL((mpcqp_legs_land_kernel<TIO>), gl, nt, 0, st, xs, (TIO*)feet, gait, tick, legs, g, (int)land, B, (int)T, it,
+                         (TIO*)miss_log);
+    });
 }
 
 int mpcqp_last_kernel_ms(mpcqp_handle h, float* ms) {

@@ -492,5 +492,45 @@ class MPCBatch:
                                     *[_ptr(out[k]) for k in self.SWING_OUT], geometry, self._inertia(inertia), st.cuda_stream)
         return out
 
+    LEGS_LOGS = ("swing",) + SWING_OUT + ("miss",)      # the logs `rollout_legs` adds to `rollout_phase`'s, in the C order
+
+    def rollout_legs(self, x, ref, feet, legs, gait, stand, gain, tick, mu, T, step_height, land="rule", body=None, push=None,
+                     push_ticks=None, substeps=10, gains=None, leg_substeps=0, inertia=None, geometry=None, log=True, stream=None):
+        """`rollout_phase` with the swing legs integrated inside the roll-out (include/mpcqp_sim.h, mpcqp_rollout_legs; the host
+        counterpart is gaits.rollout_legs_host): legs float64 [B,4,7] = per leg q, qd, live (the `state` of `swing_track`; zeros: every
+        leg starts from its row) is state next to `x`, `ref`, `feet` and `tick`, all advanced IN PLACE.  Per tick the legs take one row
+        of `phase_swing` and of `swing_track` formed from the live buffers, under the plant's right-hand side with the robot's push;
+        step_height [B] as in `phase_swing`; gains [B,2], leg_substeps, inertia, geometry as `gains`, `substeps`, ... of `swing_track`.
+        land="rule": a foot that touches down lands on the foothold rule, and x, ref, feet, tick and `rollout_phase`'s logs are what
+        `rollout_phase` gives, bit for bit; land="actual": it lands where its leg put it (the rule's z).  Returns the logs of
+        `rollout_phase` plus "swing" [B,T,4,4,3] (`phase_swing`'s), "q", "qd", "tau", "foot" [B,T,4,3], "err" [B,T,4], "flag" uint8
+        [B,T,4] (`swing_track`'s) and "miss" [B,T,4]: the distance between the delivered foot and the rule's foothold of a leg that
+        touches down after tick t, 0 elsewhere.  Asynchronous on `stream`."""
+        torch = _torch()
+        B, T = int(x.shape[0]), int(T)
+        if land not in ("rule", "actual"):
+            raise ValueError(f"land must be 'rule' or 'actual', got {land!r}")
+        check_operands(self.device, self._phase_rows(B, x, ref, feet, gait, tick, stand, gain, "x") + (
+            ("legs", legs, (B, 4, 7), torch.float64), ("mu", mu, (B,), self.tdtype), ("body", body, (B, 7), self.tdtype),
+            ("push", push, (B, 6), self.tdtype), ("push_ticks", push_ticks, (B, 2), torch.int32),
+            ("step_height", step_height, (B,), self.tdtype), ("gains", gains, (B, 2), self.tdtype)),
+            optional=("gain", "body", "push", "push_ticks", "gains"))
+        st = self._stream(stream)
+        rows, leg3 = ((B, T, 12), self.tdtype), ((B, T, 4, 3), self.tdtype)
+        leg1, mask = ((B, T, 4), self.tdtype), ((B, T, 4), torch.uint8)
+        spec = (rows, rows, rows, leg3, mask) + (((B, T, 4, 4, 3), self.tdtype), leg3, leg3, leg3, leg3, leg1, mask, leg1)
+        names = ("actual", "desired", "forces", "feet_log", "contact_log") + self.LEGS_LOGS
+        out = dict(zip(names, self._alloc(stream, *[s if log else None for s in spec])))
+        solved, = self._alloc(stream, ((B,), torch.int32, not T > 0))
+        p = lambda k: _ptr(out[k])
+        self.engine.rollout_legs_ptr(B, T, x.data_ptr(), ref.data_ptr(), feet.data_ptr(), legs.data_ptr(), gait.data_ptr(), stand.data_ptr(),
+                                     _ptr(gain), tick.data_ptr(), mu.data_ptr(), _ptr(body), _ptr(push), _ptr(push_ticks), substeps,
+                                     step_height.data_ptr(), _ptr(gains), int(leg_substeps),
+                                     _capi.LAND_ACTUAL if land == "actual" else _capi.LAND_RULE,
+                                     *[p(k) for k in names[:5]], solved.data_ptr(), *[p(k) for k in self.LEGS_LOGS],
+                                     geometry, self._inertia(inertia), st.cuda_stream)
+        out["solved"] = solved
+        return out
+
     def last_kernel_ms(self):
         return self.engine.last_kernel_ms()

@@ -1,5 +1,5 @@
 """Host counterpart of the per-leg periodic gaits (include/mpcqp_plan.h: mpcqp_phase_expand, mpcqp_solve_batch_phase,
-mpcqp_phase_swing; include/mpcqp_sim.h: mpcqp_rollout_phase): numpy fp64, vectorised over robots, in the device's operation order
+mpcqp_phase_swing; include/mpcqp_sim.h: mpcqp_rollout_phase, mpcqp_rollout_legs): numpy fp64, vectorised over robots, in the device's operation order
 (csrc/mpcqp_gaits.h) so that the two agree to rounding.
 
 The clock.  A gait row is ``(P, offset[4], stance[4])`` in ticks, legs FL, FR, HL, HR.  Leg l is in stance at tick t >= 0 when
@@ -272,6 +272,88 @@ def phase_swing_host(actual, desired, feet_log, gait, tick0, stand, gain, step_h
     fin = fin & np.isfinite(feet_log).all(axis=3)
     out = np.where(fin[..., None, None], out, np.nan)
     return {"swing": out, "feet_des": out[:, :, :, 0].copy()}
+
+
+def log_wrench(push, push_ticks, tick0, T):
+    """The push acting at every row of a roll-out's log, [B,T,6]: `plant.push_wrench` at the ticks tick0 + t (zeros for push = None)."""
+    tick0 = np.asarray(tick0, dtype=np.int32)
+    B = tick0.shape[0]
+    if push is None:
+        return np.zeros((B, T, 6))
+    return np.stack([push_wrench(push, push_ticks, tick0 + t) for t in range(T)], axis=1)
+
+
+LEGS_LOGS = ("swing", "q", "qd", "tau", "foot", "err", "flag", "miss")
+
+
+def leg_feet_host(x, legs):
+    """Where the legs hold their feet: c + R p_foot(q) [B,4,3] of the states x [B,>=12] as stored and the leg states legs [B,4,7]."""
+    from . import lite3_model, plant
+    x, legs = _f64(x), _f64(legs)
+    R = plant.quat_to_matrix(rotvec_to_quat(x[:, 0:3]))
+    with np.errstate(invalid="ignore"):
+        return x[:, None, 3:6] + lite3_model._mv(R[:, None], lite3_model._leg_chain(legs[:, :, 0:3])[2][3])
+
+
+def rollout_legs_host(oracle_engine, x, ref, feet, legs, gait, stand, gain, tick, mu, T, step_height, land="rule", body=None, push=None,
+                      push_ticks=None, substeps=DEFAULT_SUBSTEPS, gains=None, leg_substeps=0, inertia=None):
+    """Closed loop of mpcqp_rollout_legs on the CPU checker (host memory, fp64): `rollout_phase_host`'s loop with, per tick, one row of
+    `phase_swing_host` and one row of `lite3_model.swing_track_host` (the state carried in `legs` [B,4,7]) formed from the live
+    buffers before the plant steps, under `lite3_model.plant_base_acc_host` with the robot's push; after the step the landing miss
+    |c + R p_foot(q) - rule foothold| of every leg that touches down at the new tick and, with land="actual", that foot's xy in place of
+    the rule's.  Returns what `rollout_phase_host` returns plus "legs" and the logs LEGS_LOGS."""
+    from . import lite3_model
+    if push is not None and push_ticks is None:
+        raise ValueError("push needs push_ticks")
+    if land not in ("rule", "actual"):
+        raise ValueError(f"land must be 'rule' or 'actual', got {land!r}")
+    cfg = oracle_engine.cfg
+    N, delta = cfg.N, cfg.delta
+    x = _f64(x).copy(); ref = _f64(ref).copy(); feet = _f64(feet).copy(); tick = np.asarray(tick, dtype=np.int32).copy()
+    legs = _f64(legs).copy()
+    B = x.shape[0]
+    bd = model_body(cfg.m, list(cfg.Ibody_inv), B) if body is None else _f64(body)
+    grav = lite3_model._inertia_arrays(inertia)["gravity"]
+    actual = np.zeros((B, T, 12)); desired = np.zeros((B, T, 12)); forces = np.zeros((B, T, 12)); solved = np.zeros(B, np.int32)
+    feet_log = np.zeros((B, T, 4, 3)); contact_log = np.zeros((B, T, 4), np.uint8)
+    out = {"swing": np.zeros((B, T, 4, 4, 3)), "err": np.zeros((B, T, 4)), "flag": np.zeros((B, T, 4), np.uint8), "miss": np.zeros((B, T, 4)),
+           "margin": np.full((B, T, 4), np.inf), **{k: np.zeros((B, T, 4, 3)) for k in ("q", "qd", "tau", "foot")}}
+    for t in range(T):
+        e = phase_expand_host(x, ref, feet, gait, tick, stand, gain, N, delta)
+        o = oracle_engine.solve_batch_host(x, e["r"], e["contact"], e["xdes"], mu, want_X=False)
+        actual[:, t] = x[:, :12]
+        desired[:, t, 0:6] = ref[:, 0:6]; desired[:, t, 8] = ref[:, 9]; desired[:, t, 9:12] = ref[:, 6:9]
+        forces[:, t] = o["u"][:, 0]
+        solved += ((o["status"] == 1) | (o["status"] == 2)).astype(np.int32)
+        feet_log[:, t], contact_log[:, t] = feet, e["contact"][:, 0]
+        wr = None if push is None else push_wrench(push, push_ticks, tick)
+        # the legs step: the row of the logs at this tick, through phase_swing and swing_track
+        row = lambda a: a[:, t:t + 1]
+        sw = phase_swing_host(row(actual), row(desired), row(feet_log), gait, tick, stand, gain, step_height, delta)["swing"]
+        acc = lite3_model.plant_base_acc_host(row(actual), row(forces), row(feet_log), bd, grav, None if wr is None else wr[:, None])
+        trk = lite3_model.swing_track_host(row(actual), row(forces), row(feet_log), row(contact_log), sw, acc, gains=gains, state=legs,
+                                           substeps=leg_substeps, delta=delta, inertia=inertia)
+        legs = trk["state"]
+        out["swing"][:, t] = sw[:, 0]
+        for k in ("q", "qd", "tau", "foot", "err", "flag", "margin"):
+            out[k][:, t] = trk[k][:, 0]
+        x = srb_step(x, forces[:, t], feet, e["contact"][:, 0], bd, wr, delta, substeps)
+        ref[:, 3:6] = ref[:, 3:6] + ref[:, 6:9] * delta
+        ref[:, 2] = ref[:, 2] + ref[:, 9] * delta
+        tick = tick + 1
+        td = touchdown_mask(gait, tick)
+        if td.any():
+            p = touchdown_foothold(x[:, 3:6], measured_yaw(x[:, 0:3]), x[:, 9:12], ref[:, 6:9], stand, gain, gait, delta)
+            pa = leg_feet_host(x, legs)
+            dlt = pa - p
+            with np.errstate(invalid="ignore"):
+                miss = np.sqrt((dlt[..., 0] * dlt[..., 0] + dlt[..., 1] * dlt[..., 1]) + dlt[..., 2] * dlt[..., 2])
+            out["miss"][:, t] = np.where(td, miss, 0.0)
+            if land == "actual":
+                p[:, :, 0:2] = pa[:, :, 0:2]
+            feet = np.where(td[:, :, None], p, feet)
+    return {"x": x, "ref": ref, "tick": tick, "feet": feet, "legs": legs, "actual": actual, "desired": desired, "forces": forces,
+            "solved": solved, "feet_log": feet_log, "contact_log": contact_log, **out}
 
 
 def make_phase_batch(B, names=("trot", "bound"), period=12, seed=20251018, mus=(0.5, 0.7, 1.0), v_ref=(0.18, 0.0, 0.0), theta_dot=0.0,

@@ -280,10 +280,11 @@ def leg_dynamics_host(q, qd=None, qdd=None, rot=None, base=None, inertia=None):
     return tau, np.stack(cols, axis=-1), bias
 
 
-def plant_base_acc_host(actual, forces, feet, body=None, gravity=-9.81):
+def plant_base_acc_host(actual, forces, feet, body=None, gravity=-9.81, wrench=None):
     """What base_acc = None means in `leg_effort_host` / mpcqp_leg_effort: the unpushed plant's right-hand side at every row of a log,
     [B,T,6] = (alpha, a) in world axes; a = sum f / m + g e_z, alpha = R I_b^-1 (R^T sum (foot - CoM) x f - wb x I_b wb), wb = R^T
-    omega, in the plant's operation order.  body [B,7] or None (the default handle's model); an invalid row gives NaN."""
+    omega, in the plant's operation order.  body [B,7] or None (the default handle's model); an invalid row gives NaN.  wrench
+    [B,T,6] = (F, tau) or None: the push acting at each row, added to the two sums -- the right-hand side mpcqp_rollout_legs forms."""
     from . import plant
     actual, forces, feet = (np.asarray(a, dtype=float) for a in (actual, forces, feet))
     B, T = actual.shape[:2]
@@ -298,6 +299,9 @@ def plant_base_acc_host(actual, forces, feet, body=None, gravity=-9.81):
         cr = [plant._cross([feet[:, :, k, a] - actual[..., 3 + a] for a in range(3)], fk[k]) for k in range(4)]
         Fs = [(fk[0][a] + fk[1][a]) + (fk[2][a] + fk[3][a]) for a in range(3)]      # the device's sum across the row's four lanes
         Ms = [(cr[0][a] + cr[1][a]) + (cr[2][a] + cr[3][a]) for a in range(3)]
+        if wrench is not None:
+            wrench = np.asarray(wrench, dtype=float)
+            Fs, Ms = [Fs[a] + wrench[..., a] for a in range(3)], [Ms[a] + wrench[..., 3 + a] for a in range(3)]
         om = [actual[..., 6 + a] for a in range(3)]
         wb = [(R[a] * om[0] + R[3 + a] * om[1]) + R[6 + a] * om[2] for a in range(3)]
         tb = [(R[a] * Ms[0] + R[3 + a] * Ms[1]) + R[6 + a] * Ms[2] for a in range(3)]
