@@ -156,6 +156,90 @@ int mpcqp_rollout_legs(mpcqp_handle h, int64_t B, int32_t T, void* x, void* ref,
                        void* feet_log, uint8_t* contact_log, int32_t* solved, void* swing_log, void* q_log, void* qd_log, void* tau_log,
                        void* foot_log, void* err_log, uint8_t* flag_log, void* miss_log, void* stream);
 
+/*
+ * The score row of a roll-out: one HIP reduction over the logs of mpcqp_rollout / _plant / _phase / _legs into MPCQP_SCORE_FIELDS doubles
+ * per robot -- did it fall, how well did it track, what did it cost, how often did its actuators saturate, how far did its feet miss.
+ * (A product library built before this call has the header's other four; the Python binding tells the two apart.)
+ *   actual, desired, forces   T  [B,T,12]   required, as the roll-outs write them
+ *   contact_log               u8 [B,T,4]    required; nonzero = stance (mpcqp_rollout and mpcqp_rollout_plant write none: the caller
+ *                                           supplies the mask the plan gave)
+ *   tau, qd                   T  [B,T,4,3], flag u8 [B,T,4]   the leg group, mpcqp_swing_track's rows: all three or none
+ *   miss                      T  [B,T,4]    or NULL; needs nothing else
+ *   rule                      host pointer, NULL = the defaults below
+ *   score                     double [B, MPCQP_SCORE_FIELDS], fp64 whatever the I/O dtype: it passes through memory between pieces (the
+ *                             reason `legs` is fp64).  accumulate = 0: written fresh, whatever it held.  accumulate != 0: the row in
+ *                             `score` is combined with this piece (sums and counts add, maxima take the larger, fall_row keeps the
+ *                             first), and this piece's first row has the global index rows + bad_rows of the incoming row: a long
+ *                             roll-out is scored piece by piece and its logs need the memory of one piece.
+ * A row t of robot b is FALLEN when p_z < z_frac * p_z_des or sqrt(theta_x^2 + theta_y^2) > tilt_max (actual[5], desired[5],
+ * actual[0..1]).  The defaults, z_frac = 0.5 and tilt_max = 0.7 rad, are a CONVENTION of this header -- half the commanded height, 40
+ * degrees off the vertical -- not a property of the robot or of the plant, which lets a torso sink through the ground; pass the rule a
+ * study means.  A fallen row is scored like any other.  A rule that is not finite and positive, or whose size is not the struct's, is
+ * MPCQP_EINVAL.
+ * A row with a non-finite entry among its 36 values of actual, desired and forces is a BAD row: it counts in bad_rows, it may be the
+ * fall_row, and nothing else of it is read -- not its leg rows or misses either -- so a score stays finite.
+ * Fields, in this order (all arithmetic fp64; float32 logs convert exactly; maxima and counts start at 0; sums are per row, the time
+ * step goes in on the host):
+ *   body    ROWS rows scored; BAD_ROWS; FALL_ROW the global index of the first fallen or bad row, -1 if none; Z_SQ sum (p_z - p_z_des)^2,
+ *           Z_MAX max |p_z - p_z_des|; VEL_SQ sum |v_xy - v_xy_des|^2, VEL_MAX max |v_xy - v_xy_des|; ANG_SQ sum |theta - theta_des|^2,
+ *           ANG_MAX max |theta - theta_des|; TILT_MAX max sqrt(theta_x^2 + theta_y^2); VX_SUM, VY_SUM sum v_x, sum v_y
+ *   forces  legs with contact != 0 only.  FZ_MAX max f_z; FRIC_MAX max of max(|f_x|, |f_y|) / f_z over stance legs with f_z > 0: the
+ *           pyramid's use, to be read against mu; F_SQ sum |f|^2; STANCE_ROWS + l the stance rows of leg l; FLIGHT_ROWS rows with no
+ *           stance leg
+ *   legs    0 without the group.  A leg-row whose flag is 0xff (or that holds a non-finite tau or qd, which the roll-outs write only
+ *           under that flag) counts in POISONED_ROWS only.  TAU_MAX max |tau_j|; TAU_SQ sum tau_j^2; WORK_POS sum over leg-rows of
+ *           max(tau . qd, 0); WORK_ABS sum |tau . qd|; SWING_ROWS, CLAMP_ROWS, QLIM_ROWS, RATE_ROWS, SINGULAR_ROWS leg-rows with flag bit
+ *           1, 2, 4, 8, 16
+ *   miss    0 without it.  LANDINGS entries with miss != 0; MISS_MAX max miss; MISS_SQ sum miss^2.  A non-finite miss is a landing and is
+ *           left out of MISS_MAX and MISS_SQ.
+ * One wave per robot, one fixed reduction order: a robot's row does not depend on B, on its slot in the batch or on anything but its
+ * own T rows, and the same call gives the same bits.  Nothing is synchronised or allocated.
+ * MPCQP_EINVAL: B or T negative, B * T > 2^31 - 1, a null required buffer (B > 0 and T > 0) or a null score (B > 0), a leg group given in
+ * part, a float buffer that is not 16-byte aligned or a u8 buffer that is not 4-byte aligned (the rows are read as vectors), a bad rule.
+ * B = 0 is a no-op; T = 0 writes the identity row (zeros, FALL_ROW -1) with accumulate = 0 and leaves `score` alone otherwise.
+ */
+typedef struct MpcQpScoreRule {
+  uint32_t size;    /* sizeof(MpcQpScoreRule) */
+  double z_frac;    /* fallen: p_z < z_frac * p_z_des; default 0.5 */
+  double tilt_max;  /* fallen: sqrt(theta_x^2 + theta_y^2) > tilt_max [rad]; default 0.7 */
+} MpcQpScoreRule;
+#define MPCQP_SCORE_RULE_Z_FRAC 0.5
+#define MPCQP_SCORE_RULE_TILT_MAX 0.7
+#define MPCQP_SCORE_ROWS 0
+#define MPCQP_SCORE_BAD_ROWS 1
+#define MPCQP_SCORE_FALL_ROW 2
+#define MPCQP_SCORE_Z_SQ 3
+#define MPCQP_SCORE_Z_MAX 4
+#define MPCQP_SCORE_VEL_SQ 5
+#define MPCQP_SCORE_VEL_MAX 6
+#define MPCQP_SCORE_ANG_SQ 7
+#define MPCQP_SCORE_ANG_MAX 8
+#define MPCQP_SCORE_TILT_MAX 9
+#define MPCQP_SCORE_VX_SUM 10
+#define MPCQP_SCORE_VY_SUM 11
+#define MPCQP_SCORE_FZ_MAX 12
+#define MPCQP_SCORE_FRIC_MAX 13
+#define MPCQP_SCORE_F_SQ 14
+#define MPCQP_SCORE_STANCE_ROWS 15   /* + leg: 15 .. 18 */
+#define MPCQP_SCORE_FLIGHT_ROWS 19
+#define MPCQP_SCORE_TAU_MAX 20
+#define MPCQP_SCORE_TAU_SQ 21
+#define MPCQP_SCORE_WORK_POS 22
+#define MPCQP_SCORE_WORK_ABS 23
+#define MPCQP_SCORE_SWING_ROWS 24
+#define MPCQP_SCORE_CLAMP_ROWS 25
+#define MPCQP_SCORE_QLIM_ROWS 26
+#define MPCQP_SCORE_RATE_ROWS 27
+#define MPCQP_SCORE_SINGULAR_ROWS 28
+#define MPCQP_SCORE_POISONED_ROWS 29
+#define MPCQP_SCORE_LANDINGS 30
+#define MPCQP_SCORE_MISS_MAX 31
+#define MPCQP_SCORE_MISS_SQ 32
+#define MPCQP_SCORE_FIELDS 33
+int mpcqp_rollout_score(mpcqp_handle h, int64_t B, int32_t T, const void* actual, const void* desired, const void* forces,
+                        const uint8_t* contact_log, const void* tau, const void* qd, const uint8_t* flag, const void* miss,
+                        const MpcQpScoreRule* rule, int32_t accumulate, double* score, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

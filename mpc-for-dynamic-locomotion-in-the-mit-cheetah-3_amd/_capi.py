@@ -75,6 +75,11 @@ class MpcQpLegInertia(ctypes.Structure):
         return out
 
 
+class MpcQpScoreRule(ctypes.Structure):
+    """Mirror of struct MpcQpScoreRule (include/mpcqp_sim.h): when a log row counts as fallen."""
+    _fields_ = [("size", c_uint32), ("z_frac", c_double), ("tilt_max", c_double)]
+
+
 class MpcQpConfig(ctypes.Structure):
     """Mirror of ``struct MpcQpConfig`` (include/mpcqp.h)."""
     _fields_ = [
@@ -105,6 +110,7 @@ class MpcQpError(RuntimeError):
 # compares every row with the prototype in the header.
 _P, _I32, _I64 = c_void_p, c_int32, c_int64   # any address (handle, buffer, stream), int32_t, int64_t
 _CFG, _GEO, _INR = ctypes.POINTER(MpcQpConfig), ctypes.POINTER(MpcQpLegGeometry), ctypes.POINTER(MpcQpLegInertia)
+_RULE = ctypes.POINTER(MpcQpScoreRule)
 CORE_HEADER = "mpcqp.h"
 ABI = {
     "mpcqp.h": (
@@ -135,6 +141,7 @@ ABI = {
         ("mpcqp_rollout_plant", c_int, (_P, _I64, _I32, _I32) + (_P,) * 10 + (_I32,) + (_P,) * 5),
         ("mpcqp_rollout_phase", c_int, (_P, _I64, _I32) + (_P,) * 11 + (_I32,) + (_P,) * 7),
         ("mpcqp_rollout_legs", c_int, (_P, _I64, _I32) + (_P,) * 12 + (_I32, _P, _P, _I32, _GEO, _INR, _I32) + (_P,) * 15),
+        ("mpcqp_rollout_score", c_int, (_P, _I64, _I32) + (_P,) * 8 + (_RULE, _I32, _P, _P)),
     ),
     "mpcqp_model.h": (  # per-robot model rows
         ("mpcqp_set_models", c_int, (_P, _I64, _P, _P)),
@@ -157,14 +164,17 @@ EXPORTED_SYMBOLS, PLAN_SYMBOLS, SIM_SYMBOLS, MODEL_SYMBOLS, JOINTS_SYMBOLS = (tu
 LEGSIM_SYMBOLS = ("mpcqp_leg_accel", "mpcqp_swing_track")
 # Likewise the roll-out with the swing legs inside it, which came after the rest of include/mpcqp_sim.h (`has_sim`): `has_legroll`.
 LEGROLL_SYMBOLS = ("mpcqp_rollout_legs",)
-_GATED = {**{name: ("has_legsim", LEGSIM_SYMBOLS) for name in LEGSIM_SYMBOLS}, **{name: ("has_legroll", LEGROLL_SYMBOLS) for name in LEGROLL_SYMBOLS}}
+# ... and the score row of a roll-out's logs, the header's newest call: `has_score`.
+SCORE_SYMBOLS = ("mpcqp_rollout_score",)
+_GATED = {name: (gate, names) for gate, names in (("has_legsim", LEGSIM_SYMBOLS), ("has_legroll", LEGROLL_SYMBOLS), ("has_score", SCORE_SYMBOLS))
+          for name in names}
 LAND_RULE, LAND_ACTUAL = 0, 1   # include/mpcqp_sim.h, MPCQP_LAND_*
 
 
 class Library:
     """A loaded shared object exporting the mpcqp C-ABI.  `has_plan`, `has_sim`, `has_model` and `has_joints` say whether it exports
     all of include/mpcqp_plan.h, mpcqp_sim.h, mpcqp_model.h and mpcqp_joints.h (of the last: all but LEGSIM_SYMBOLS, which `has_legsim`
-    answers for; of mpcqp_sim.h: all but LEGROLL_SYMBOLS, `has_legroll`).  An extension header's calls are bound only when the library
+    answers for; of mpcqp_sim.h: all but LEGROLL_SYMBOLS and SCORE_SYMBOLS, `has_legroll` and `has_score`).  An extension header's calls are bound only when the library
     has them all; `partial=True` binds whichever it has (an older build of the product library, in a comparison tool)."""
 
     def __init__(self, path: str, partial: bool = False):
@@ -175,6 +185,7 @@ class Library:
         self.calls = {}   # name -> (function or None, its header, which parameters after the handle are addresses): Engine._call
         self.has_legsim = all(hasattr(self.lib, name) for name in LEGSIM_SYMBOLS)
         self.has_legroll = all(hasattr(self.lib, name) for name in LEGROLL_SYMBOLS)
+        self.has_score = all(hasattr(self.lib, name) for name in SCORE_SYMBOLS)
         for header, rows in ABI.items():
             have = header == CORE_HEADER or all(hasattr(self.lib, row[0]) for row in rows if row[0] not in _GATED)
             if header != CORE_HEADER:
@@ -332,6 +343,10 @@ class Engine:
         self._call("mpcqp_rollout_legs", B, T, x, ref, feet, legs, gait, stand, gain, tick, mu, body, push, push_ticks, substeps, step_height,
                    gains, leg_substeps, geometry, inertia, land, actual, desired, forces, feet_log, contact_log, solved, swing_log, q_log,
                    qd_log, tau_log, foot_log, err_log, flag_log, miss_log, stream)
+
+    def rollout_score_ptr(self, B, T, actual, desired, forces, contact_log, tau, qd, flag, miss, accumulate, score, rule=None, stream=0):
+        """The score row of a roll-out's logs (include/mpcqp_sim.h, mpcqp_rollout_score); `rule` is an MpcQpScoreRule or None = the defaults."""
+        self._call("mpcqp_rollout_score", B, T, actual, desired, forces, contact_log, tau, qd, flag, miss, rule, accumulate, score, stream)
 
     def phase_swing_ptr(self, B, T, actual, desired, feet_log, gait, tick0, stand, gain, step_height, swing, feet_des=0, stream=0):
         """The swing-foot trajectories of a roll-out on a gait clock, from its logs (include/mpcqp_plan.h, mpcqp_phase_swing)."""

@@ -28,10 +28,12 @@
 #include "mpcqp_legdyn.h"
 #include "mpcqp_legsim.h"
 #include "mpcqp_legroll.h"
+#include "mpcqp_score.h"
 
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <new>
 #include <type_traits>
 
@@ -1439,6 +1441,38 @@ int mpcqp_rollout_legs(mpcqp_handle h, int64_t B, int32_t T, void* x, void* ref,
       hipLaunchKernelGGL((mpcqp_legs_land_kernel<TIO>), gl, nt, 0, st, xs, (TIO*)feet, gait, tick, legs, g, (int)land, B, (int)T, it,
                          (TIO*)miss_log);
     });
+}
+
+int mpcqp_rollout_score(mpcqp_handle h, int64_t B, int32_t T, const void* actual, const void* desired, const void* forces,
+                        const uint8_t* contact_log, const void* tau, const void* qd, const uint8_t* flag, const void* miss,
+                        const MpcQpScoreRule* rule, int32_t accumulate, double* score, void* stream) {
+  if (!h) return MPCQP_EINVAL;
+  if (B < 0 || B > 0x7fffffff || T < 0 || B * (int64_t)T > 0x7fffffff) return fail(h, MPCQP_EINVAL, "mpcqp_rollout_score: size out of range");
+  if ((tau || qd || flag) && !(tau && qd && flag))
+    return fail(h, MPCQP_EINVAL, "mpcqp_rollout_score: the leg group is tau, qd and flag: all three or none");
+  if (B > 0 && (!score || (T > 0 && (!actual || !desired || !forces || !contact_log)))) return fail(h, MPCQP_EINVAL, "mpcqp_rollout_score: null buffer");
+  const MpcQpScoreRule dflt = {(uint32_t)sizeof(MpcQpScoreRule), MPCQP_SCORE_RULE_Z_FRAC, MPCQP_SCORE_RULE_TILT_MAX};
+  if (!rule) rule = &dflt;
+  if (rule->size != sizeof(MpcQpScoreRule)) return fail(h, MPCQP_EINVAL, "mpcqp_rollout_score: rule struct size mismatch");
+  if (!std::isfinite(rule->z_frac) || !std::isfinite(rule->tilt_max) || !(rule->z_frac > 0) || !(rule->tilt_max > 0))
+    return fail(h, MPCQP_EINVAL, "mpcqp_rollout_score: z_frac and tilt_max must be finite and positive");
+  // the rows are read as 16-byte vectors and dwords
+  for (const void* p : {actual, desired, forces, tau, qd, miss})
+    if ((uintptr_t)p % 16) return fail(h, MPCQP_EINVAL, "mpcqp_rollout_score: a log buffer is not 16-byte aligned");
+  if ((uintptr_t)contact_log % 4 || (uintptr_t)flag % 4 || (uintptr_t)score % 8)
+    return fail(h, MPCQP_EINVAL, "mpcqp_rollout_score: contact_log / flag not 4-byte or score not 8-byte aligned");
+  if (B == 0 || (T == 0 && accumulate)) return MPCQP_OK;
+  DeviceGuard guard(h->cfg.device);
+  if (guard.err != hipSuccess) return fail(h, MPCQP_EHIP, "hipSetDevice", guard.err);
+  const dim3 grid((unsigned)((B + 3) / 4));   // one wave per robot
+  with_io(h, [&](auto tag) {
+    using TIO = decltype(tag);
+    const ScoreIn<TIO> in = {(const TIO*)actual, (const TIO*)desired, (const TIO*)forces, contact_log, (const TIO*)tau, (const TIO*)qd, flag,
+                             (const TIO*)miss};
+    hipLaunchKernelGGL((mpcqp_score_kernel<TIO>), grid, dim3(256), 0, (hipStream_t)stream, in, rule->z_frac, rule->tilt_max, (int)(accumulate != 0),
+                       score, (int)B, (int)T);
+  });
+  return launched(h, "score kernel launch");
 }
 
 int mpcqp_last_kernel_ms(mpcqp_handle h, float* ms) {

@@ -532,5 +532,38 @@ class MPCBatch:
         out["solved"] = solved
         return out
 
+    def score(self, logs, score=None, rule=None, stream=None):
+        """The score row of a roll-out's logs, reduced on the device (include/mpcqp_sim.h, mpcqp_rollout_score; the host counterpart is
+        score.score_host, the field names are score.FIELDS, score.summarize reads the figures off the rows): `logs` is the dict
+        `rollout`, `rollout_plant`, `rollout_phase` or `rollout_legs` returns ("actual", "desired", "forces" [B,T,12] and "contact_log"
+        uint8 [B,T,4], which the caller adds to the logs of the first two; the leg group when "tau", "qd" [B,T,4,3] and "flag" uint8
+        [B,T,4] are all there, "miss" [B,T,4] when it is).  score=None: a fresh float64 [B, len(score.FIELDS)] tensor; a given one is
+        combined with these rows IN PLACE and returned, its rows + bad_rows being the global index of this piece's first row (a long
+        roll-out scored piece by piece: score.scored_rollout).  `rule`: None = the header's defaults, or (z_frac, tilt_max) / a dict, as
+        score.rule_pair takes it.  Asynchronous on `stream`."""
+        from . import score as _score
+        torch = _torch()
+        actual = logs.get("actual")
+        if actual is None or actual.dim() != 3:
+            raise ValueError("score needs the logs of a roll-out run with log=True")
+        B, T = int(actual.shape[0]), int(actual.shape[1])
+        rows, leg3, leg1, mask = (B, T, 12), (B, T, 4, 3), (B, T, 4), (B, T, 4)
+        group = [logs.get(k) for k in ("tau", "qd", "flag")]
+        if any(t is not None for t in group) and any(t is None for t in group):
+            raise ValueError("the leg group is tau, qd and flag: all three or none")
+        check_operands(self.device, (("actual", actual, rows, self.tdtype), ("desired", logs.get("desired"), rows, self.tdtype),
+                                     ("forces", logs.get("forces"), rows, self.tdtype), ("contact_log", logs.get("contact_log"), mask, torch.uint8),
+                                     ("tau", group[0], leg3, self.tdtype), ("qd", group[1], leg3, self.tdtype), ("flag", group[2], mask, torch.uint8),
+                                     ("miss", logs.get("miss"), leg1, self.tdtype), ("score", score, (B, len(_score.FIELDS)), torch.float64)),
+                       optional=("tau", "qd", "flag", "miss", "score"))
+        st = self._stream(stream)
+        accumulate = score is not None
+        if score is None:
+            score, = self._alloc(stream, ((B, len(_score.FIELDS)), torch.float64))
+        self.engine.rollout_score_ptr(B, T, actual.data_ptr(), logs["desired"].data_ptr(), logs["forces"].data_ptr(), logs["contact_log"].data_ptr(),
+                                      *[_ptr(t) for t in group], _ptr(logs.get("miss")), int(accumulate), score.data_ptr(),
+                                      _score.rule_struct(rule), st.cuda_stream)
+        return score
+
     def last_kernel_ms(self):
         return self.engine.last_kernel_ms()
