@@ -240,6 +240,71 @@ int mpcqp_rollout_score(mpcqp_handle h, int64_t B, int32_t T, const void* actual
                         const uint8_t* contact_log, const void* tau, const void* qd, const uint8_t* flag, const void* miss,
                         const MpcQpScoreRule* rule, int32_t accumulate, double* score, void* stream);
 
+/*
+ * What a stance leg delivers.  The roll-outs above apply the solve's stage-0 forces as returned: the legs are ideal force sources and
+ * the ground transmits anything.  The rule here puts the actuators' torque limit and the ground between the commanded force and the
+ * plant; mpcqp_stance_drive is the rule for B robots (it is to the drive what mpcqp_plant_step is to the plant), mpcqp_rollout_drive the
+ * roll-out with the rule in its loop.  (A product library built before these two has the header's other five; the Python binding tells
+ * them apart.)
+ * The rule, for one stance leg (contact != 0) with commanded force f (world), held foot, state x as stored:
+ *   1. R from the rotation vector exactly as mpcqp_joint_log forms it; (q, reach) the closed-form IK with rot = R, origin = CoM;
+ *      A = (R J(q))^T; tau_cmd = A (-f) -- mpcqp_joint_log's stance torque, from the same device functions.
+ *   2. tau_app = tau_cmd clamped per joint into [-tau_max, tau_max] (the inertia row's); the leg is CLAMPED when any joint differs.
+ *   3. not clamped: f1 = f (a select: the bits of f are kept).  Clamped, reach = 1 and det J != 0: f1 = -A^-1 tau_app = -R (J^-T tau_app),
+ *      J^T solved by cofactors and determinant in the order the rates solve J.  Clamped but out of reach or singular: f1 = f, bit 16.
+ *   4. the ground.  f1_z <= 0: f2 = 0, the foot cannot pull.  Otherwise, with a friction row mu_g, if sqrt(f1_x^2 + f1_y^2) > mu_g f1_z the
+ *      tangential part is scaled by mu_g f1_z / sqrt(f1_x^2 + f1_y^2): onto the circular Coulomb cone, direction kept.  Otherwise f2 = f1.
+ *      Bit 32 is set exactly when f2 != f1.  THE FOOT DOES NOT MOVE: slip kinematics are not built.  f2 is the force a sliding foot
+ *      transmits, but the held foot stays where it is until the leg lifts off.
+ *   5. f_out = f2; tau = tau_app where bit 32 is clear, else (R J)^T (-f2); flag bits 2 clamped, 4 q outside [q_min, q_max], 16 the leg
+ *      cannot be resolved, 32 the ground limited the force.
+ *   6. a swing leg (contact == 0): f_out = f bit for bit, tau = 0, flag 0.
+ * A stance leg with a non-finite operand (its force or foot) writes NaN into its own f_out and tau and flag 0xff; so do all four legs of
+ * a robot whose x[0..11] or mu_g is not finite or whose mu_g < 0.  No other robot changes.
+ * Arithmetic is fp64 without contraction, float32 outputs are rounded once.  Neither limit is told to the MPC: a controller that should
+ * know lowers f_max through mpcqp_set_models (include/mpcqp_model.h) or mu.
+ *   x        T  [B,13]   f  T [B,12]   feet  T [B,4,3]   contact  u8 [B,4]   as in mpcqp_plant_step
+ *   ground   T  [B]      or NULL: no friction limit (the foot still cannot pull)
+ *   geo, inr             as in mpcqp_leg_effort: tau_max, q_min, q_max are read (one row per call)
+ *   f_out    T  [B,12]   out; may equal f
+ *   tau      T  [B,4,3]  out, may be NULL        flag  u8 [B,4]  out, may be NULL
+ * MPCQP_EINVAL: B negative or above 2^29 - 1, a null x, f, feet, contact or f_out (B > 0), an invalid geo / inr row.  B = 0 is a no-op.
+ */
+int mpcqp_stance_drive(mpcqp_handle h, int64_t B, const void* x, const void* f, const void* feet, const uint8_t* contact, const void* ground,
+                       const MpcQpLegGeometry* geo, const MpcQpLegInertia* inr, void* f_out, void* tau, uint8_t* flag, void* stream);
+
+/*
+ * mpcqp_rollout_legs with the stance drive in its loop.  Every argument of mpcqp_rollout_legs keeps its meaning.
+ *   drive     MPCQP_DRIVE_IDEAL: step 2 of the rule is skipped (no torque limit); MPCQP_DRIVE_LIMITED: the whole rule with inr's
+ *             tau_max -- the row the swing legs are clamped by.  Anything else is MPCQP_EINVAL.
+ *   ground    T [B] or NULL, as in mpcqp_stance_drive
+ *   cmd_log   T [B,T,12] out, may be NULL: the COMMANDED stage-0 forces of the solve
+ * Per tick, after the unchanged expand and solve, the rule runs on the live buffers: x, feet, the stance mask of the gait clock that the
+ * advance uses, the solve's stage-0 forces.  Then:
+ *   - the legs step's torso acceleration, the plant step and the `forces` log use the APPLIED forces
+ *   - on stance rows tau_log is the rule's tau and flag_log the row's bits OR the rule's 2 / 16 / 32 (0xff for a poisoned leg); a stance
+ *     row the legs step itself poisons (tau NaN, flag 0xff) stays so
+ *   - the solver's own buffers are not altered: the next solve warm-starts from what it returned, not from what was delivered
+ * MPCQP_DRIVE_IDEAL with ground = NULL leaves every force with f_z > 0 alone: x, ref, feet, legs, tick and every log are then
+ * mpcqp_rollout_legs' bit for bit, and cmd_log == forces.  (In that mode a stance row the rule leaves alone keeps the torque
+ * mpcqp_rollout_legs logs, which is the rule's tau_cmd up to the last place in fp64; in every other mode all stance rows hold the
+ * rule's tau, so that mpcqp_stance_drive on the logged rows -- x = actual, f = cmd_log, feet_log, contact_log -- reproduces forces,
+ * the stance rows of tau_log and the bits 2 / 16 / 32 of flag_log bit for bit.)
+ * Six launches per tick, seven with tau_log or flag_log; no host synchronisation, copy or allocation inside the T ticks (the side
+ * buffers are part of the roll-out's reserve).  A non-finite or negative ground row: that robot's applied forces are NaN, its solves
+ * report MPCQP_STATUS_NONFINITE from the next tick with a stance leg on, and no other robot changes.
+ * Not built: slip kinematics, a tau_max per robot, torque-speed curves, a variant on plan tables.
+ */
+#define MPCQP_DRIVE_IDEAL 0
+#define MPCQP_DRIVE_LIMITED 1
+int mpcqp_rollout_drive(mpcqp_handle h, int64_t B, int32_t T, void* x, void* ref, void* feet, double* legs, const int32_t* gait,
+                        const void* stand, const void* gain, int32_t* tick, const void* mu, const void* body, const void* push,
+                        const int32_t* push_ticks, int32_t substeps, const void* step_height, const void* gains, int32_t leg_substeps,
+                        const MpcQpLegGeometry* geo, const MpcQpLegInertia* inr, int32_t land, int32_t drive, const void* ground,
+                        void* actual, void* desired, void* forces, void* feet_log, uint8_t* contact_log, int32_t* solved, void* swing_log,
+                        void* q_log, void* qd_log, void* tau_log, void* foot_log, void* err_log, uint8_t* flag_log, void* miss_log,
+                        void* cmd_log, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

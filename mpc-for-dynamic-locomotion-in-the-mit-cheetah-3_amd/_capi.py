@@ -142,6 +142,8 @@ ABI = {
         ("mpcqp_rollout_phase", c_int, (_P, _I64, _I32) + (_P,) * 11 + (_I32,) + (_P,) * 7),
         ("mpcqp_rollout_legs", c_int, (_P, _I64, _I32) + (_P,) * 12 + (_I32, _P, _P, _I32, _GEO, _INR, _I32) + (_P,) * 15),
         ("mpcqp_rollout_score", c_int, (_P, _I64, _I32) + (_P,) * 8 + (_RULE, _I32, _P, _P)),
+        ("mpcqp_stance_drive", c_int, (_P, _I64) + (_P,) * 5 + (_GEO, _INR) + (_P,) * 4),
+        ("mpcqp_rollout_drive", c_int, (_P, _I64, _I32) + (_P,) * 12 + (_I32, _P, _P, _I32, _GEO, _INR, _I32, _I32, _P) + (_P,) * 16),
     ),
     "mpcqp_model.h": (  # per-robot model rows
         ("mpcqp_set_models", c_int, (_P, _I64, _P, _P)),
@@ -166,15 +168,22 @@ LEGSIM_SYMBOLS = ("mpcqp_leg_accel", "mpcqp_swing_track")
 LEGROLL_SYMBOLS = ("mpcqp_rollout_legs",)
 # ... and the score row of a roll-out's logs, the header's newest call: `has_score`.
 SCORE_SYMBOLS = ("mpcqp_rollout_score",)
-_GATED = {name: (gate, names) for gate, names in (("has_legsim", LEGSIM_SYMBOLS), ("has_legroll", LEGROLL_SYMBOLS), ("has_score", SCORE_SYMBOLS))
+# ... and the stance drive, the header's newest pair: `has_drive`.
+DRIVE_SYMBOLS = ("mpcqp_stance_drive", "mpcqp_rollout_drive")
+_GATED = {name: (gate, names) for gate, names in (("has_legsim", LEGSIM_SYMBOLS), ("has_legroll", LEGROLL_SYMBOLS), ("has_score", SCORE_SYMBOLS),
+                                                  ("has_drive", DRIVE_SYMBOLS))
           for name in names}
 LAND_RULE, LAND_ACTUAL = 0, 1   # include/mpcqp_sim.h, MPCQP_LAND_*
+DRIVE_IDEAL, DRIVE_LIMITED = 0, 1   # include/mpcqp_sim.h, MPCQP_DRIVE_*
+# The flag bits the stance drive writes (include/mpcqp_sim.h): clamped, q outside its limits, not resolvable, limited by the ground.
+DRIVE_CLAMPED, DRIVE_QLIM, DRIVE_UNRESOLVED, DRIVE_GROUND, DRIVE_POISONED = 2, 4, 16, 32, 0xff
 
 
 class Library:
     """A loaded shared object exporting the mpcqp C-ABI.  `has_plan`, `has_sim`, `has_model` and `has_joints` say whether it exports
     all of include/mpcqp_plan.h, mpcqp_sim.h, mpcqp_model.h and mpcqp_joints.h (of the last: all but LEGSIM_SYMBOLS, which `has_legsim`
-    answers for; of mpcqp_sim.h: all but LEGROLL_SYMBOLS and SCORE_SYMBOLS, `has_legroll` and `has_score`).  An extension header's calls are bound only when the library
+    answers for; of mpcqp_sim.h: all but LEGROLL_SYMBOLS, SCORE_SYMBOLS and DRIVE_SYMBOLS, `has_legroll`, `has_score` and `has_drive`).  An
+    extension header's calls are bound only when the library
     has them all; `partial=True` binds whichever it has (an older build of the product library, in a comparison tool)."""
 
     def __init__(self, path: str, partial: bool = False):
@@ -186,6 +195,7 @@ class Library:
         self.has_legsim = all(hasattr(self.lib, name) for name in LEGSIM_SYMBOLS)
         self.has_legroll = all(hasattr(self.lib, name) for name in LEGROLL_SYMBOLS)
         self.has_score = all(hasattr(self.lib, name) for name in SCORE_SYMBOLS)
+        self.has_drive = all(hasattr(self.lib, name) for name in DRIVE_SYMBOLS)
         for header, rows in ABI.items():
             have = header == CORE_HEADER or all(hasattr(self.lib, row[0]) for row in rows if row[0] not in _GATED)
             if header != CORE_HEADER:
@@ -347,6 +357,18 @@ class Engine:
     def rollout_score_ptr(self, B, T, actual, desired, forces, contact_log, tau, qd, flag, miss, accumulate, score, rule=None, stream=0):
         """The score row of a roll-out's logs (include/mpcqp_sim.h, mpcqp_rollout_score); `rule` is an MpcQpScoreRule or None = the defaults."""
         self._call("mpcqp_rollout_score", B, T, actual, desired, forces, contact_log, tau, qd, flag, miss, rule, accumulate, score, stream)
+
+    def stance_drive_ptr(self, B, x, f, feet, contact, ground, f_out, tau=0, flag=0, geometry=None, inertia=None, stream=0):
+        """What the stance legs deliver of a commanded force (include/mpcqp_sim.h, mpcqp_stance_drive)."""
+        self._call("mpcqp_stance_drive", B, x, f, feet, contact, ground, geometry, inertia, f_out, tau, flag, stream)
+
+    def rollout_drive_ptr(self, B, T, x, ref, feet, legs, gait, stand, gain, tick, mu, body, push, push_ticks, substeps, step_height, gains,
+                          leg_substeps, land, drive, ground, actual, desired, forces, feet_log, contact_log, solved, swing_log, q_log, qd_log,
+                          tau_log, foot_log, err_log, flag_log, miss_log, cmd_log, geometry=None, inertia=None, stream=0):
+        """`rollout_legs_ptr` with the stance drive in the loop (include/mpcqp_sim.h, mpcqp_rollout_drive)."""
+        self._call("mpcqp_rollout_drive", B, T, x, ref, feet, legs, gait, stand, gain, tick, mu, body, push, push_ticks, substeps, step_height,
+                   gains, leg_substeps, geometry, inertia, land, drive, ground, actual, desired, forces, feet_log, contact_log, solved,
+                   swing_log, q_log, qd_log, tau_log, foot_log, err_log, flag_log, miss_log, cmd_log, stream)
 
     def phase_swing_ptr(self, B, T, actual, desired, feet_log, gait, tick0, stand, gain, step_height, swing, feet_des=0, stream=0):
         """The swing-foot trajectories of a roll-out on a gait clock, from its logs (include/mpcqp_plan.h, mpcqp_phase_swing)."""

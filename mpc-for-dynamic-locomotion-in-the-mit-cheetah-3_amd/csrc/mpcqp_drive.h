@@ -1,0 +1,153 @@
+// mpcqp_drive.h -- what a stance leg delivers: the commanded foot force through the actuators' torque limits and the ground (the
+// C-ABI is mpcqp_stance_drive and mpcqp_rollout_drive in include/mpcqp_sim.h, which has the rule; the entry points live in
+// mpcqp_kernels.hip).  Two kernels:
+//   mpcqp_stance_drive_kernel  the rule for one (robot, leg).  mpcqp_stance_drive runs it on the caller's rows; mpcqp_rollout_drive runs
+//                              the SAME instantiation per tick on the live buffers, between the solve and the legs step: the commanded
+//                              force is stage 0 of the solve's [B,N,12] buffer (stride fstride), the stance mask the gait clock's at
+//                              max(tick, 0) (contact = null), and the applied force goes to a [B,12] side buffer of the roll-out's
+//                              reserve.  The legs step and the advance then read that side buffer as a force buffer of horizon 1, so they
+//                              keep their source and their assembly, and the solver's own buffer -- its next warm start -- is not altered.
+//   mpcqp_drive_log_kernel     after the legs step of a tick: on stance rows tau_log becomes the rule's torque and flag_log gains the
+//                              rule's bits 2 / 16 / 32 (0xff for a poisoned leg).
+// One kernel for both entry points is what makes the roll-out's logs replay bit for bit through mpcqp_stance_drive.
+//
+// Layout as mpcqp_legdyn.h states it: one thread per (robot, leg), a robot's four legs in one quad, fp64 arithmetic, no LDS, geometry
+// and limits by value.  q and tau_cmd = (R J)^T (-f) are leg_joints<true>'s, the device function of mpcqp_joint_log, with R formed as
+// that kernel forms it; J is leg_fk_jac's at that q; the 3x3 solve is adj_solve (cofactors and determinant in the order the rates
+// solve J) on J^T.  The rule's own arithmetic runs without contraction.  Masks are selects: a poisoned leg computes on and is selected
+// away at the store; no lane returns early and nothing is exchanged between lanes.
+#pragma once
+#include "mpcqp_gaits.h"
+#include "mpcqp_joints.h"
+#include "mpcqp_legsim.h"
+
+namespace {
+
+constexpr int DRIVE_IDEAL = 0, DRIVE_LIMITED = 1;   // MPCQP_DRIVE_IDEAL, MPCQP_DRIVE_LIMITED (include/mpcqp_sim.h)
+constexpr unsigned DRIVE_BITS = 2u | 16u | 32u;     // what the rule adds to a stance row's flag
+
+// Steps 2 to 5 of the rule for a stance leg: R world <- torso, J = d foot / d q at the leg's q (both by rows), reach the IK's, f the
+// commanded force and tc = (R J)^T (-f); mu < 0 means no friction limit.  Writes the applied force and torque, returns the bits.
+__device__ __forceinline__ unsigned drive_rule(const double (&R)[9], const double (&J)[9], const bool reach, const V3 f, const V3 tc,
+                                               const LegLimDev& lim, const bool limited, const bool cone_on, const double mu, V3& fo,
+                                               V3& to) {
+#pragma clang fp contract(off)
+  // 2. the actuators
+  const V3 ta = {limited ? clamp_sym(tc.x, lim.taumax[0]) : tc.x, limited ? clamp_sym(tc.y, lim.taumax[1]) : tc.y,
+                 limited ? clamp_sym(tc.z, lim.taumax[2]) : tc.z};
+  const bool clamped = ta.x != tc.x || ta.y != tc.y || ta.z != tc.z;
+  // 3. f1 = -A^-1 tau_app, A = (R J)^T = J^T R^T: g = J^-T tau_app, f1 = -(R g)
+  const M3 Jt = {{J[0], J[3], J[6]}, {J[1], J[4], J[7]}, {J[2], J[5], J[8]}};
+  double det;
+  const V3 g = adj_solve(Jt, ta, det);
+  const V3 fc = {-((R[0] * g.x + R[1] * g.y) + R[2] * g.z), -((R[3] * g.x + R[4] * g.y) + R[5] * g.z), -((R[6] * g.x + R[7] * g.y) + R[8] * g.z)};
+  const bool solve = reach && det != 0.0;
+  const V3 f1 = sel3(clamped && solve, fc, f);
+  // 4. the ground: no pull, and the tangential part on the circular cone with its direction kept
+  const bool pull = f1.z <= 0.0;
+  const double ft = sqrt(f1.x * f1.x + f1.y * f1.y), cap = mu * f1.z;
+  const bool cone = cone_on && ft > cap;
+  const double s = cap / ft;
+  const V3 f2 = {pull ? 0.0 : (cone ? f1.x * s : f1.x), pull ? 0.0 : (cone ? f1.y * s : f1.y), pull ? 0.0 : f1.z};
+  const bool ground = f2.x != f1.x || f2.y != f1.y || f2.z != f1.z;
+  fo = sel3(ground, f2, f1);   // (a select: an untouched force keeps its bits, a -0 included)
+  // 5. the torque that goes with it
+  const double h0 = -((R[0] * f2.x + R[3] * f2.y) + R[6] * f2.z), h1 = -((R[1] * f2.x + R[4] * f2.y) + R[7] * f2.z),
+               h2 = -((R[2] * f2.x + R[5] * f2.y) + R[8] * f2.z);   // R^T (-f2)
+  const V3 tg = {(J[0] * h0 + J[3] * h1) + J[6] * h2, (J[1] * h0 + J[4] * h1) + J[7] * h2, (J[2] * h0 + J[5] * h1) + J[8] * h2};
+  to = sel3(ground, tg, ta);
+  return (clamped ? 2u : 0u) | ((clamped && !solve) ? 16u : 0u) | (ground ? 32u : 0u);
+}
+
+// i = 4 b + leg.  x [B,13]; f the commanded forces, robot b's at f + b fstride; feet [B,4,3]; contact u8 [B,4], or null: the gait
+// clock of `gait` [B,9] at max(tick[b], 0); ground [B] or null.  f_out [B,12] (may be f when fstride = 12: a lane reads its own three
+// values before it writes them), tau [B,4,3] or null, flag u8 [B,4] or null, cmd or null: robot b's commanded forces as read, to
+// cmd + b cstride.
+template <typename TIO>
+__global__ void __launch_bounds__(256)
+mpcqp_stance_drive_kernel(const TIO* __restrict__ x, const TIO* f, const int64_t fstride, const TIO* __restrict__ feet,
+                          const uint8_t* __restrict__ contact, const int32_t* __restrict__ gait, const int32_t* __restrict__ tick,
+                          const TIO* __restrict__ ground, const LegGeoDev geo, const LegLimDev lim, const int drive, TIO* f_out,
+                          TIO* __restrict__ tau, uint8_t* __restrict__ flag, TIO* __restrict__ cmd, const int64_t cstride, const int64_t B) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= 4 * B) return;
+  const int64_t b = i / 4;
+  const int l = (int)(i % 4);
+  const TIO* xb = x + 13 * b;   // rotation vector, CoM, ...
+  const TIO* fb = f + b * fstride + 3 * l;
+  const TIO fr[3] = {fb[0], fb[1], fb[2]};
+  bool stance;
+  if (contact) {
+    stance = contact[i] != 0;
+  } else {
+    const GaitLeg gc = gait_leg(gait + b * GAIT_ROW, l);
+    stance = gait_phase(gc, (uint32_t)max(tick[b], 0)) < gc.st;
+  }
+  // mpcqp_joint_log's row: R from the rotation vector, the foot seen from the CoM, q and tau_cmd
+  double qt[4], pw[3], fl[3], ql[3], tl[3];
+  plant_rotvec_to_quat((double)xb[0], (double)xb[1], (double)xb[2], qt);
+  const double qw = qt[0], qx = qt[1], qy = qt[2], qz = qt[3];
+  const double R[9] = {1.0 - 2.0 * (qy * qy + qz * qz), 2.0 * (qx * qy - qw * qz), 2.0 * (qx * qz + qw * qy),
+                       2.0 * (qx * qy + qw * qz), 1.0 - 2.0 * (qx * qx + qz * qz), 2.0 * (qy * qz - qw * qx),
+                       2.0 * (qx * qz - qw * qy), 2.0 * (qy * qz + qw * qx), 1.0 - 2.0 * (qx * qx + qy * qy)};
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    pw[a] = (double)feet[3 * i + a] - (double)xb[3 + a];
+    fl[a] = (double)fr[a];
+  }
+  const bool reach = leg_joints<true>(geo, l, R, pw, fl, ql, tl);
+  double pf[3], J[9];
+  leg_fk_jac(geo, l, ql, pf, J);
+  const V3 fv = {fl[0], fl[1], fl[2]}, tc = {tl[0], tl[1], tl[2]}, q = {ql[0], ql[1], ql[2]}, zero = {0.0, 0.0, 0.0};
+  const double mu = ground ? (double)ground[b] : 0.0;
+  V3 fo, to;
+  unsigned bits = drive_rule(R, J, reach, fv, tc, lim, drive == DRIVE_LIMITED, ground != nullptr, mu, fo, to);
+  bits |= swing_limits(lim, q, zero);   // 4: q outside its limits
+  // the robot's x and ground row poison its four legs, a leg's own operands that leg
+  bool robot = isfinite(mu) && mu >= 0.0;
+#pragma unroll
+  for (int a = 0; a < 12; ++a) robot = robot && isfinite((double)xb[a]);
+  const bool good = robot && (!stance || (fin3(fv) && isfinite(pw[0]) && isfinite(pw[1]) && isfinite(pw[2]) && fin3(fo) && fin3(to)));
+  const double nan = __builtin_nan("");
+  TIO* fw = f_out + 12 * b + 3 * l;
+  if (cmd) {
+    TIO* cw = cmd + b * cstride + 3 * l;
+    cw[0] = fr[0]; cw[1] = fr[1]; cw[2] = fr[2];
+  }
+  // a swing leg keeps its commanded force as read
+  fw[0] = good ? (stance ? (TIO)fo.x : fr[0]) : (TIO)nan;
+  fw[1] = good ? (stance ? (TIO)fo.y : fr[1]) : (TIO)nan;
+  fw[2] = good ? (stance ? (TIO)fo.z : fr[2]) : (TIO)nan;
+  if (tau) store3(tau + 3 * i, good, sel3(stance, to, zero));
+  if (flag) flag[i] = good ? (uint8_t)(stance ? bits : 0u) : (uint8_t)0xff;
+}
+
+// After the legs step of tick `it`, before the advance (tick is still the row's): i = 4 b + leg.  rtau [B,4,3] and rflag [B,4] are what
+// mpcqp_stance_drive_kernel left for this tick.  A swing row keeps what the legs step logged; so does a stance row the legs step
+// poisoned (tau NaN, flag 0xff).  only_changed (MPCQP_DRIVE_IDEAL without a ground row): a stance row the rule left alone keeps the legs
+// step's torque too.  That torque and the rule's are both (R J)^T (-f) at the same operands, but the legs step's differs from
+// mpcqp_joint_log's -- which the rule's is, bit for bit -- in the last place in fp64 (its inlined copy of leg_joints is fused
+// differently), and in that mode every log has to be mpcqp_rollout_legs' bit for bit.
+template <typename TIO>
+__global__ void __launch_bounds__(256)
+mpcqp_drive_log_kernel(const int32_t* __restrict__ gait, const int32_t* __restrict__ tick, const TIO* __restrict__ rtau,
+                       const uint8_t* __restrict__ rflag, const int only_changed, const int64_t B, const int T, const int it,
+                       TIO* __restrict__ tau_log, uint8_t* __restrict__ flag_log) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= 4 * B) return;
+  const int64_t b = i / 4;
+  const int l = (int)(i % 4);
+  const GaitLeg gc = gait_leg(gait + b * GAIT_ROW, l);
+  if (!(gait_phase(gc, (uint32_t)max(tick[b], 0)) < gc.st)) return;
+  const int64_t il = 4 * (b * T + it) + l;
+  const bool was_bad = (flag_log && flag_log[il] == 0xff) || (tau_log && isnan((double)tau_log[3 * il]));
+  if (was_bad) return;
+  const unsigned rb = rflag[i];
+  if (only_changed && (rb & DRIVE_BITS) == 0u) return;   // (0xff has the bits)
+  if (tau_log) {   // (a poisoned leg's rtau is NaN already)
+    tau_log[3 * il] = rtau[3 * i]; tau_log[3 * il + 1] = rtau[3 * i + 1]; tau_log[3 * il + 2] = rtau[3 * i + 2];
+  }
+  if (flag_log) flag_log[il] = rb == 0xffu ? (uint8_t)0xff : (uint8_t)(flag_log[il] | (rb & DRIVE_BITS));
+}
+
+}  // namespace

@@ -28,6 +28,7 @@
 #include "mpcqp_legdyn.h"
 #include "mpcqp_legsim.h"
 #include "mpcqp_legroll.h"
+#include "mpcqp_drive.h"
 #include "mpcqp_score.h"
 
 #include <cstdio>
@@ -60,7 +61,8 @@ struct mpcqp_engine {
   float* wr_klane32 = nullptr;   // ... and K^-1 in lane order [NT][16]: the entries of each lane's 8 x 8 tile (w_tile_init); horizon 10: each
                                  // followed by the lane records [NT][16 values | 8 row words] of w_kq_rows_load (mpcqp_rowtab.h)
   double* wr_klane64 = nullptr;
-  void* roll_mem = nullptr;   // roll-out: u [B,N,12], X [B,N+1,13], status / iters [B] of the current tick
+  void* roll_mem = nullptr;   // roll-out: u [B,N,12], X [B,N+1,13], status / iters [B] of the current tick, then the stance drive's
+                              // side buffers: applied forces [B,12], torques [B,4,3], flags u8 [B,4] (mpcqp_rollout_drive)
   int64_t roll_cap = 0;
   void* gait_mem = nullptr;   // gait entry point: the expanded operator tuple [r | xdes | contact] of the current batch
   int64_t gait_cap = 0;
@@ -273,6 +275,7 @@ size_t ws_bytes(int64_t B, size_t N, size_t el, size_t tail) { return (size_t)B 
 
 template <typename T> struct TupleWs { T* r; T* xdes; uint8_t* contact; };
 template <typename T> struct ResultWs { T* u; T* X; int32_t* status; int32_t* iters; };
+template <typename T> struct DriveWs { T* f; T* tau; uint8_t* flag; };   // behind ResultWs in the roll-out's reserve
 
 template <typename T>
 TupleWs<T> tuple_ws(void* base, int64_t B, size_t N) {
@@ -286,6 +289,13 @@ ResultWs<T> result_ws(void* base, int64_t B, size_t N) {
   return {u, u + (size_t)B * N * 12, status, status + B};
 }
 
+template <typename T>
+DriveWs<T> drive_ws(void* base, int64_t B, size_t N) {   // (status and iters are 8 B bytes: a double stays aligned)
+  T* f = (T*)(result_ws<T>(base, B, N).iters + B);
+  return {f, f + (size_t)B * 12, (uint8_t*)(f + (size_t)B * 24)};
+}
+constexpr size_t drive_tail(size_t el) { return 24 * el + 4; }   // bytes per robot of DriveWs
+
 // Tuple workspace of the gait entry point and the roll-out, grown like the rest of the batch-dependent workspace.
 int reserve_gait(mpcqp_engine* e, int64_t B) {
   if (B <= e->gait_cap) return MPCQP_OK;
@@ -298,7 +308,7 @@ int reserve_gait(mpcqp_engine* e, int64_t B) {
 // Result workspace of the roll-out.  Zeros = "no guess" for a warm-started engine.
 int reserve_roll(mpcqp_engine* e, int64_t B) {
   if (B <= e->roll_cap) return MPCQP_OK;
-  const size_t bytes = ws_bytes(B, (size_t)e->cfg.N, io_size(e), 2 * sizeof(int32_t));
+  const size_t bytes = ws_bytes(B, (size_t)e->cfg.N, io_size(e), 2 * sizeof(int32_t) + drive_tail(io_size(e)));
   if (!grow(e->roll_mem, bytes, bytes)) return MPCQP_ENOMEM;
   e->roll_cap = B;
   return MPCQP_OK;
@@ -1389,27 +1399,39 @@ int mpcqp_swing_track(mpcqp_handle h, int64_t B, int32_t T, const void* actual, 
   return launched(h, "swing track kernel launch");
 }
 
-int mpcqp_rollout_legs(mpcqp_handle h, int64_t B, int32_t T, void* x, void* ref, void* feet, double* legs, const int32_t* gait,
-                       const void* stand, const void* gain, int32_t* tick, const void* mu, const void* body, const void* push,
-                       const int32_t* push_ticks, int32_t substeps, const void* step_height, const void* gains, int32_t leg_substeps,
-                       const MpcQpLegGeometry* geo, const MpcQpLegInertia* inr, int32_t land, void* actual, void* desired, void* forces,
-                       void* feet_log, uint8_t* contact_log, int32_t* solved, void* swing_log, void* q_log, void* qd_log, void* tau_log,
-                       void* foot_log, void* err_log, uint8_t* flag_log, void* miss_log, void* stream) {
+extern "C++" {
+namespace {
+
+// What mpcqp_rollout_drive adds to mpcqp_rollout_legs: the drive mode, the ground's friction [B] or null, the commanded-force log or null.
+struct RolloutDriveArgs { int32_t drive; const void* ground; void* cmd_log; };
+
+// mpcqp_rollout_legs (dr = null) and mpcqp_rollout_drive: one argument check, one loop.
+int rollout_legs_run(mpcqp_handle h, const char* who, int64_t B, int32_t T, void* x, void* ref, void* feet, double* legs, const int32_t* gait,
+                     const void* stand, const void* gain, int32_t* tick, const void* mu, const void* body, const void* push,
+                     const int32_t* push_ticks, int32_t substeps, const void* step_height, const void* gains, int32_t leg_substeps,
+                     const MpcQpLegGeometry* geo, const MpcQpLegInertia* inr, int32_t land, void* actual, void* desired, void* forces,
+                     void* feet_log, uint8_t* contact_log, int32_t* solved, void* swing_log, void* q_log, void* qd_log, void* tau_log,
+                     void* foot_log, void* err_log, uint8_t* flag_log, void* miss_log, void* stream, const RolloutDriveArgs* dr) {
   if (!h) return MPCQP_EINVAL;
-  if (B < 0 || B > 0x7fffffff || T < 0 || B * (int64_t)T > 0x7fffffff) return fail(h, MPCQP_EINVAL, "mpcqp_rollout_legs: size out of range");
+  const auto bad = [&](const char* what) {
+    char msg[160];
+    snprintf(msg, sizeof(msg), "%s: %s", who, what);
+    return fail(h, MPCQP_EINVAL, msg);
+  };
+  if (B < 0 || B > 0x7fffffff || T < 0 || B * (int64_t)T > 0x7fffffff) return bad("size out of range");
   const int n = plant_substeps(substeps);
-  if (n < 0) return fail(h, MPCQP_EINVAL, "mpcqp_rollout_legs: substeps out of range [0, 1000]");
-  if (leg_substeps < 0 || leg_substeps > SWING_MAX_SUBSTEPS) return fail(h, MPCQP_EINVAL, "mpcqp_rollout_legs: leg_substeps out of range [0, 1000]");
-  if (land != MPCQP_LAND_RULE && land != MPCQP_LAND_ACTUAL) return fail(h, MPCQP_EINVAL, "mpcqp_rollout_legs: land is neither MPCQP_LAND_RULE nor MPCQP_LAND_ACTUAL");
-  if (push && !push_ticks) return fail(h, MPCQP_EINVAL, "mpcqp_rollout_legs: push without push_ticks");
-  if (B > 0 && (!x || !ref || !feet || !legs || !gait || !stand || !tick || !mu || !step_height))
-    return fail(h, MPCQP_EINVAL, "mpcqp_rollout_legs: null buffer");
+  if (n < 0) return bad("substeps out of range [0, 1000]");
+  if (leg_substeps < 0 || leg_substeps > SWING_MAX_SUBSTEPS) return bad("leg_substeps out of range [0, 1000]");
+  if (land != MPCQP_LAND_RULE && land != MPCQP_LAND_ACTUAL) return bad("land is neither MPCQP_LAND_RULE nor MPCQP_LAND_ACTUAL");
+  if (dr && dr->drive != MPCQP_DRIVE_IDEAL && dr->drive != MPCQP_DRIVE_LIMITED) return bad("drive is neither MPCQP_DRIVE_IDEAL nor MPCQP_DRIVE_LIMITED");
+  if (push && !push_ticks) return bad("push without push_ticks");
+  if (B > 0 && (!x || !ref || !feet || !legs || !gait || !stand || !tick || !mu || !step_height)) return bad("null buffer");
   LegGeoDev g;
-  if (const int rc = leg_ik_geometry(h, "mpcqp_rollout_legs", geo, g)) return rc;
+  if (const int rc = leg_ik_geometry(h, who, geo, g)) return rc;
   LegInrDev r;
-  if (const int rc = leg_inertia_row(h, "mpcqp_rollout_legs", inr, r)) return rc;
+  if (const int rc = leg_inertia_row(h, who, inr, r)) return rc;
   if (B == 0 || T == 0) return MPCQP_OK;
-  if (const int rc = models_match(h, B, "mpcqp_rollout_legs")) return rc;
+  if (const int rc = models_match(h, B, who)) return rc;
   int nl = leg_substeps;
   if (nl == 0) {   // the default control period, as mpcqp_swing_track: the fewest periods of at most SWING_H0
     nl = (int)std::ceil(h->cfg.delta / SWING_H0);
@@ -1423,8 +1445,11 @@ int mpcqp_rollout_legs(mpcqp_handle h, int64_t B, int32_t T, void* x, void* ref,
   const double d = h->cfg.delta;
   const dim3 ge = expand_grid(B, N), ga = advance_grid(B), gl((unsigned)((4 * B + 255) / 256)), nt(256);
   hipStream_t st = (hipStream_t)stream;
-  // the roll-out loop of mpcqp_rollout_phase with the legs step in front of its advance and the landing behind it: 5 launches per tick
-  return rollout_loop(h, "mpcqp_rollout_legs", B, T, x, ref, mu, stream,
+  // the roll-out loop of mpcqp_rollout_phase with the legs step in front of its advance and the landing behind it: 5 launches per tick.
+  // With a drive, the rule runs between the solve and the legs step and leaves the applied forces in a [B,12] side buffer, which the legs
+  // step and the advance read as a force buffer of horizon 1 (the solve's own buffer, its next warm start, is not altered); after the legs
+  // step the rule's torques and bits go into the stance rows of tau_log / flag_log: 6 launches, 7 with one of those two logs.
+  return rollout_loop(h, who, B, T, x, ref, mu, stream,
     [&](auto tag, auto* xs, auto* rf, const auto& w) {
       using TIO = decltype(tag);
       const PhaseRows<TIO> ph = {(const TIO*)feet, gait, (const TIO*)stand, (const TIO*)gain};
@@ -1434,13 +1459,74 @@ int mpcqp_rollout_legs(mpcqp_handle h, int64_t B, int32_t T, void* x, void* ref,
       using TIO = decltype(tag);
       const PhaseRows<TIO> ph = {(const TIO*)feet, gait, (const TIO*)stand, (const TIO*)gain};
       const LegRollOut<TIO> out = {(TIO*)swing_log, (TIO*)q_log, (TIO*)qd_log, (TIO*)tau_log, (TIO*)foot_log, (TIO*)err_log, flag_log};
-      hipLaunchKernelGGL((mpcqp_legs_step_kernel<TIO>), gl, nt, 0, st, xs, rf, ph, tick, o.u, (const TIO*)step_height, (const TIO*)gains, legs,
-                         plant_in<TIO>(h, plant), g, r.k0, r.k1, r.k2, r.lim, out, d, N, B, (int)T, it, nl, d / nl);
-      hipLaunchKernelGGL((mpcqp_phase_advance_kernel<TIO>), ga, nt, 0, st, xs, rf, (TIO*)feet, ph, tick, plant_in<TIO>(h, plant), o.u, o.status, d, N, B,
+      const TIO* u = o.u;   // the forces the legs and the plant see, robot b's at u + b Nu 12
+      int Nu = N;
+      const DriveWs<TIO> dw = drive_ws<TIO>(h->roll_mem, B, N);
+      if (dr) {
+        TIO* cmd = dr->cmd_log ? (TIO*)dr->cmd_log + (size_t)it * 12 : nullptr;
+        hipLaunchKernelGGL((mpcqp_stance_drive_kernel<TIO>), gl, nt, 0, st, xs, o.u, (int64_t)N * 12, (const TIO*)feet, (const uint8_t*)nullptr,
+                           gait, tick, (const TIO*)dr->ground, g, r.lim, (int)dr->drive, dw.f, dw.tau, dw.flag, cmd, (int64_t)T * 12, B);
+        u = dw.f; Nu = 1;
+      }
+      hipLaunchKernelGGL((mpcqp_legs_step_kernel<TIO>), gl, nt, 0, st, xs, rf, ph, tick, u, (const TIO*)step_height, (const TIO*)gains, legs,
+                         plant_in<TIO>(h, plant), g, r.k0, r.k1, r.k2, r.lim, out, d, Nu, B, (int)T, it, nl, d / nl);
+      if (dr && (tau_log || flag_log))
+        hipLaunchKernelGGL((mpcqp_drive_log_kernel<TIO>), gl, nt, 0, st, gait, tick, dw.tau, dw.flag,
+                           (int)(dr->drive == MPCQP_DRIVE_IDEAL && !dr->ground), B, (int)T, it, (TIO*)tau_log, flag_log);
+      hipLaunchKernelGGL((mpcqp_phase_advance_kernel<TIO>), ga, nt, 0, st, xs, rf, (TIO*)feet, ph, tick, plant_in<TIO>(h, plant), u, o.status, d, Nu, B,
                          (int)T, it, (TIO*)actual, (TIO*)desired, (TIO*)forces, (TIO*)feet_log, contact_log, solved);
       hipLaunchKernelGGL((mpcqp_legs_land_kernel<TIO>), gl, nt, 0, st, xs, (TIO*)feet, gait, tick, legs, g, (int)land, B, (int)T, it,
                          (TIO*)miss_log);
     });
+}
+
+}  // namespace
+}  // extern "C++"
+
+int mpcqp_rollout_legs(mpcqp_handle h, int64_t B, int32_t T, void* x, void* ref, void* feet, double* legs, const int32_t* gait,
+                       const void* stand, const void* gain, int32_t* tick, const void* mu, const void* body, const void* push,
+                       const int32_t* push_ticks, int32_t substeps, const void* step_height, const void* gains, int32_t leg_substeps,
+                       const MpcQpLegGeometry* geo, const MpcQpLegInertia* inr, int32_t land, void* actual, void* desired, void* forces,
+                       void* feet_log, uint8_t* contact_log, int32_t* solved, void* swing_log, void* q_log, void* qd_log, void* tau_log,
+                       void* foot_log, void* err_log, uint8_t* flag_log, void* miss_log, void* stream) {
+  return rollout_legs_run(h, "mpcqp_rollout_legs", B, T, x, ref, feet, legs, gait, stand, gain, tick, mu, body, push, push_ticks, substeps,
+                          step_height, gains, leg_substeps, geo, inr, land, actual, desired, forces, feet_log, contact_log, solved, swing_log,
+                          q_log, qd_log, tau_log, foot_log, err_log, flag_log, miss_log, stream, nullptr);
+}
+
+int mpcqp_rollout_drive(mpcqp_handle h, int64_t B, int32_t T, void* x, void* ref, void* feet, double* legs, const int32_t* gait,
+                        const void* stand, const void* gain, int32_t* tick, const void* mu, const void* body, const void* push,
+                        const int32_t* push_ticks, int32_t substeps, const void* step_height, const void* gains, int32_t leg_substeps,
+                        const MpcQpLegGeometry* geo, const MpcQpLegInertia* inr, int32_t land, int32_t drive, const void* ground,
+                        void* actual, void* desired, void* forces, void* feet_log, uint8_t* contact_log, int32_t* solved, void* swing_log,
+                        void* q_log, void* qd_log, void* tau_log, void* foot_log, void* err_log, uint8_t* flag_log, void* miss_log,
+                        void* cmd_log, void* stream) {
+  const RolloutDriveArgs dr = {drive, ground, cmd_log};
+  return rollout_legs_run(h, "mpcqp_rollout_drive", B, T, x, ref, feet, legs, gait, stand, gain, tick, mu, body, push, push_ticks, substeps,
+                          step_height, gains, leg_substeps, geo, inr, land, actual, desired, forces, feet_log, contact_log, solved, swing_log,
+                          q_log, qd_log, tau_log, foot_log, err_log, flag_log, miss_log, stream, &dr);
+}
+
+int mpcqp_stance_drive(mpcqp_handle h, int64_t B, const void* x, const void* f, const void* feet, const uint8_t* contact, const void* ground,
+                       const MpcQpLegGeometry* geo, const MpcQpLegInertia* inr, void* f_out, void* tau, uint8_t* flag, void* stream) {
+  if (!h) return MPCQP_EINVAL;
+  if (B < 0 || B > 0x1fffffff) return fail(h, MPCQP_EINVAL, "mpcqp_stance_drive: batch size out of range");
+  if (B > 0 && (!x || !f || !feet || !contact || !f_out)) return fail(h, MPCQP_EINVAL, "mpcqp_stance_drive: null buffer");
+  LegGeoDev g;
+  if (const int rc = leg_ik_geometry(h, "mpcqp_stance_drive", geo, g)) return rc;
+  LegInrDev r;
+  if (const int rc = leg_inertia_row(h, "mpcqp_stance_drive", inr, r)) return rc;
+  if (B == 0) return MPCQP_OK;
+  DeviceGuard guard(h->cfg.device);
+  if (guard.err != hipSuccess) return fail(h, MPCQP_EHIP, "hipSetDevice", guard.err);
+  const dim3 grid((unsigned)((4 * B + 255) / 256));
+  with_io(h, [&](auto tag) {
+    using TIO = decltype(tag);
+    hipLaunchKernelGGL((mpcqp_stance_drive_kernel<TIO>), grid, dim3(256), 0, (hipStream_t)stream, (const TIO*)x, (const TIO*)f, (int64_t)12,
+                       (const TIO*)feet, contact, (const int32_t*)nullptr, (const int32_t*)nullptr, (const TIO*)ground, g, r.lim,
+                       (int)DRIVE_LIMITED, (TIO*)f_out, (TIO*)tau, flag, (TIO*)nullptr, (int64_t)0, B);
+  });
+  return launched(h, "stance drive kernel launch");
 }
 
 int mpcqp_rollout_score(mpcqp_handle h, int64_t B, int32_t T, const void* actual, const void* desired, const void* forces,

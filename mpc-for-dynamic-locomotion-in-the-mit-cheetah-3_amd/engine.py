@@ -532,6 +532,70 @@ class MPCBatch:
         out["solved"] = solved
         return out
 
+    def stance_drive(self, x, f, feet, contact, ground=None, inertia=None, geometry=None, want=("tau", "flag"), stream=None):
+        """What the stance legs deliver of a commanded force (include/mpcqp_sim.h, mpcqp_stance_drive, which has the rule; the host
+        counterpart is lite3_model.stance_drive_host): x [B,13] or [B,12] (the rule reads the rotation vector and the CoM; a 12-wide
+        row, as the roll-outs log it, is padded), f [B,12] the commanded foot forces, feet [B,4,3] the held feet, contact uint8 [B,4],
+        ground [B] the ground's friction coefficient or None (no friction limit; a foot still cannot pull); inertia, geometry as for
+        `leg_effort`: the row's tau_max, q_min and q_max are read -> {"f": [B,12] the applied forces, "tau": [B,4,3] the applied joint
+        torques (0 on a swing leg), "flag": uint8 [B,4]: 2 torque clamped, 4 joint angle outside its limits, 16 clamped but not
+        resolvable (out of reach or singular: the force is kept), 32 the ground limited the force, 0xff a non-finite leg}; "tau" /
+        "flag" are None when not in `want`.  The held foot does not move: no slip kinematics.  Asynchronous on `stream`."""
+        torch = _torch()
+        B = int(x.shape[0])
+        if x.dim() == 2 and x.shape[1] == 12:
+            with torch.cuda.stream(stream):
+                x = torch.cat([x, torch.zeros((B, 1), dtype=x.dtype, device=x.device)], dim=1).contiguous()
+        check_operands(self.device, (("x", x, (B, 13), self.tdtype), ("f", f, (B, 12), self.tdtype), ("feet", feet, (B, 4, 3), self.tdtype),
+                                     ("contact", contact, (B, 4), torch.uint8), ("ground", ground, (B,), self.tdtype)), optional=("ground",))
+        st = self._stream(stream)
+        out, tau, flag = self._alloc(stream, ((B, 12), self.tdtype), ((B, 4, 3), self.tdtype) if "tau" in want else None,
+                                     ((B, 4), torch.uint8) if "flag" in want else None)
+        self.engine.stance_drive_ptr(B, x.data_ptr(), f.data_ptr(), feet.data_ptr(), contact.data_ptr(), _ptr(ground), out.data_ptr(),
+                                     _ptr(tau), _ptr(flag), geometry, self._inertia(inertia), st.cuda_stream)
+        return {"f": out, "tau": tau, "flag": flag}
+
+    def rollout_drive(self, x, ref, feet, legs, gait, stand, gain, tick, mu, T, step_height, land="rule", drive="limited", ground=None,
+                      body=None, push=None, push_ticks=None, substeps=10, gains=None, leg_substeps=0, inertia=None, geometry=None,
+                      log=True, stream=None):
+        """`rollout_legs` with the stance legs as limited force sources (include/mpcqp_sim.h, mpcqp_rollout_drive; the host counterpart
+        is gaits.rollout_drive_host): per tick the rule of `stance_drive` runs on the solve's stage-0 forces, and the legs step's torso
+        acceleration, the plant and the "forces" log get the APPLIED forces.  drive="limited": the stance torques are clamped at the
+        inertia row's tau_max, the limit the swing legs have; drive="ideal": no torque limit.  ground [B]: the ground's friction
+        coefficient per robot (`mu` stays the controller's belief) or None.  Returns `rollout_legs`' dict plus "cmd" [B,T,12], the
+        commanded forces; on stance rows "tau" is the applied torque and "flag" has the rule's bits 2 / 16 / 32 (score.py's CLAMP_ROWS
+        then counts stance rows too).  The MPC is not told about either limit.  drive="ideal" with ground=None is `rollout_legs` bit
+        for bit.  Every other argument as in `rollout_legs`.  Asynchronous on `stream`."""
+        torch = _torch()
+        B, T = int(x.shape[0]), int(T)
+        if land not in ("rule", "actual"):
+            raise ValueError(f"land must be 'rule' or 'actual', got {land!r}")
+        modes = {"ideal": _capi.DRIVE_IDEAL, "limited": _capi.DRIVE_LIMITED}
+        if not isinstance(drive, int) and drive not in modes:
+            raise ValueError(f"drive must be 'ideal' or 'limited', got {drive!r}")
+        check_operands(self.device, self._phase_rows(B, x, ref, feet, gait, tick, stand, gain, "x") + (
+            ("legs", legs, (B, 4, 7), torch.float64), ("mu", mu, (B,), self.tdtype), ("body", body, (B, 7), self.tdtype),
+            ("push", push, (B, 6), self.tdtype), ("push_ticks", push_ticks, (B, 2), torch.int32),
+            ("step_height", step_height, (B,), self.tdtype), ("gains", gains, (B, 2), self.tdtype), ("ground", ground, (B,), self.tdtype)),
+            optional=("gain", "body", "push", "push_ticks", "gains", "ground"))
+        st = self._stream(stream)
+        rows, leg3 = ((B, T, 12), self.tdtype), ((B, T, 4, 3), self.tdtype)
+        leg1, mask = ((B, T, 4), self.tdtype), ((B, T, 4), torch.uint8)
+        spec = (rows, rows, rows, leg3, mask) + (((B, T, 4, 4, 3), self.tdtype), leg3, leg3, leg3, leg3, leg1, mask, leg1) + (rows,)
+        names = ("actual", "desired", "forces", "feet_log", "contact_log") + self.LEGS_LOGS + ("cmd",)
+        out = dict(zip(names, self._alloc(stream, *[s if log else None for s in spec])))
+        solved, = self._alloc(stream, ((B,), torch.int32, not T > 0))
+        p = lambda k: _ptr(out[k])
+        self.engine.rollout_drive_ptr(B, T, x.data_ptr(), ref.data_ptr(), feet.data_ptr(), legs.data_ptr(), gait.data_ptr(), stand.data_ptr(),
+                                      _ptr(gain), tick.data_ptr(), mu.data_ptr(), _ptr(body), _ptr(push), _ptr(push_ticks), substeps,
+                                      step_height.data_ptr(), _ptr(gains), int(leg_substeps),
+                                      _capi.LAND_ACTUAL if land == "actual" else _capi.LAND_RULE,
+                                      drive if isinstance(drive, int) else modes[drive], _ptr(ground),
+                                      *[p(k) for k in names[:5]], solved.data_ptr(), *[p(k) for k in self.LEGS_LOGS], p("cmd"),
+                                      geometry, self._inertia(inertia), st.cuda_stream)
+        out["solved"] = solved
+        return out
+
     def score(self, logs, score=None, rule=None, stream=None):
         """The score row of a roll-out's logs, reduced on the device (include/mpcqp_sim.h, mpcqp_rollout_score; the host counterpart is
         score.score_host, the field names are score.FIELDS, score.summarize reads the figures off the rows): `logs` is the dict

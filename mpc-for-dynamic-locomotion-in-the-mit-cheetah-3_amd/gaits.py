@@ -302,6 +302,27 @@ def rollout_legs_host(oracle_engine, x, ref, feet, legs, gait, stand, gain, tick
     buffers before the plant steps, under `lite3_model.plant_base_acc_host` with the robot's push; after the step the landing miss
     |c + R p_foot(q) - rule foothold| of every leg that touches down at the new tick and, with land="actual", that foot's xy in place of
     the rule's.  Returns what `rollout_phase_host` returns plus "legs" and the logs LEGS_LOGS."""
+    return _rollout_legs_loop(oracle_engine, x, ref, feet, legs, gait, stand, gain, tick, mu, T, step_height, land, body, push, push_ticks,
+                              substeps, gains, leg_substeps, inertia, None, None)
+
+
+def rollout_drive_host(oracle_engine, x, ref, feet, legs, gait, stand, gain, tick, mu, T, step_height, land="rule", drive="limited",
+                       ground=None, body=None, push=None, push_ticks=None, substeps=DEFAULT_SUBSTEPS, gains=None, leg_substeps=0,
+                       inertia=None):
+    """Closed loop of mpcqp_rollout_drive on the CPU checker: `rollout_legs_host`'s loop with `lite3_model.stance_drive_host` between the
+    solve and the legs step.  The legs step's torso acceleration, the plant and "forces" get the applied forces, "cmd" [B,T,12] the
+    commanded ones; on stance rows "tau" is the rule's torque and "flag" gains its bits 2 / 16 / 32 (0xff for a poisoned leg); "drive_margin"
+    [B,T,4] (host only) is the rule's margin.  The solver is not told: the next solve starts from what the last returned.  drive =
+    "limited" clamps at the inertia row's tau_max, "ideal" does not; ground [B] the ground's friction coefficient or None."""
+    if drive not in ("ideal", "limited"):
+        raise ValueError(f"drive must be 'ideal' or 'limited', got {drive!r}")
+    return _rollout_legs_loop(oracle_engine, x, ref, feet, legs, gait, stand, gain, tick, mu, T, step_height, land, body, push, push_ticks,
+                              substeps, gains, leg_substeps, inertia, drive, ground)
+
+
+def _rollout_legs_loop(oracle_engine, x, ref, feet, legs, gait, stand, gain, tick, mu, T, step_height, land, body, push, push_ticks, substeps,
+                       gains, leg_substeps, inertia, drive, ground):
+    """The loop of `rollout_legs_host` (drive = None) and `rollout_drive_host`."""
     from . import lite3_model
     if push is not None and push_ticks is None:
         raise ValueError("push needs push_ticks")
@@ -318,12 +339,17 @@ def rollout_legs_host(oracle_engine, x, ref, feet, legs, gait, stand, gain, tick
     feet_log = np.zeros((B, T, 4, 3)); contact_log = np.zeros((B, T, 4), np.uint8)
     out = {"swing": np.zeros((B, T, 4, 4, 3)), "err": np.zeros((B, T, 4)), "flag": np.zeros((B, T, 4), np.uint8), "miss": np.zeros((B, T, 4)),
            "margin": np.full((B, T, 4), np.inf), **{k: np.zeros((B, T, 4, 3)) for k in ("q", "qd", "tau", "foot")}}
+    if drive is not None:
+        out["cmd"], out["drive_margin"] = np.zeros((B, T, 12)), np.full((B, T, 4), np.inf)
     for t in range(T):
         e = phase_expand_host(x, ref, feet, gait, tick, stand, gain, N, delta)
         o = oracle_engine.solve_batch_host(x, e["r"], e["contact"], e["xdes"], mu, want_X=False)
         actual[:, t] = x[:, :12]
         desired[:, t, 0:6] = ref[:, 0:6]; desired[:, t, 8] = ref[:, 9]; desired[:, t, 9:12] = ref[:, 6:9]
         forces[:, t] = o["u"][:, 0]
+        if drive is not None:      # the applied forces take the place of the commanded ones from here on
+            dv = lite3_model.stance_drive_host(x, o["u"][:, 0], feet, e["contact"][:, 0], ground, drive, inertia)
+            out["cmd"][:, t], forces[:, t], out["drive_margin"][:, t] = o["u"][:, 0], dv["f"], dv["margin"]
         solved += ((o["status"] == 1) | (o["status"] == 2)).astype(np.int32)
         feet_log[:, t], contact_log[:, t] = feet, e["contact"][:, 0]
         wr = None if push is None else push_wrench(push, push_ticks, tick)
@@ -337,6 +363,10 @@ def rollout_legs_host(oracle_engine, x, ref, feet, legs, gait, stand, gain, tick
         out["swing"][:, t] = sw[:, 0]
         for k in ("q", "qd", "tau", "foot", "err", "flag", "margin"):
             out[k][:, t] = trk[k][:, 0]
+        if drive is not None:      # stance rows the legs step did not poison: the rule's torque and bits
+            m = (contact_log[:, t] != 0) & (out["flag"][:, t] != 0xff)
+            out["tau"][:, t] = np.where(m[..., None], dv["tau"], out["tau"][:, t])
+            out["flag"][:, t] = np.where(m, np.where(dv["flag"] == 0xff, 0xff, out["flag"][:, t] | (dv["flag"] & 50)), out["flag"][:, t])
         x = srb_step(x, forces[:, t], feet, e["contact"][:, 0], bd, wr, delta, substeps)
         ref[:, 3:6] = ref[:, 3:6] + ref[:, 6:9] * delta
         ref[:, 2] = ref[:, 2] + ref[:, 9] * delta

@@ -571,6 +571,85 @@ def swing_track_host(actual, forces, feet_log, contact_log, swing, base_acc=None
     return out
 
 
+# ---- the stance drive (the host counterpart of mpcqp_stance_drive, include/mpcqp_sim.h) ---------------------------------------------
+DRIVE_CLAMPED, DRIVE_QLIM, DRIVE_UNRESOLVED, DRIVE_GROUND = 2, 4, 16, 32
+
+
+def stance_drive_host(x, f, feet, contact, ground=None, drive="limited", inertia=None):
+    """What the stance legs deliver of a commanded force (the host counterpart of mpcqp_stance_drive, include/mpcqp_sim.h, which has the
+    rule; numpy in the device's order of operations): x [B,>=12] as stored, f [B,12] or [B,4,3] the commanded forces, feet [B,4,3] the
+    held feet, contact [B,4], ground [B] the ground's friction coefficient or None (no friction limit; a foot still cannot pull),
+    drive "limited" or "ideal" (the torque clamp is skipped: what mpcqp_rollout_drive does under MPCQP_DRIVE_IDEAL), inertia a dict as
+    `leg_inertia` (tau_max, q_min, q_max are read) -> {"f": [B,12] applied forces, "tau": [B,4,3] applied torques, "flag": uint8 [B,4]
+    (2 clamped, 4 q outside its limits, 16 clamped but not resolvable, 32 the ground limited the force, 0xff a non-finite leg),
+    "tau_cmd": [B,4,3] = `joint_log_host`'s torque, "q": [B,4,3], "reach": uint8 [B,4], "margin": [B,4] (host only) the smallest
+    distance |value - threshold| / max(1, |threshold|) of a stance leg to a threshold that decides a bit or a branch: |tau_cmd| at
+    tau_max and, for a clamped leg, whose f1 is computed, f1_z at 0 and the tangential force at the cone -- where it is tiny a
+    rounding difference may flip the decision}.
+    tau_cmd = (R J)^T (-f) is `joint_log_host`'s; clamped legs get f1 = -R (J^-T tau_app) by `_adj_solve` on J^T.  The held foot does
+    not move: slip kinematics are not built."""
+    from scipy.spatial.transform import Rotation
+    if drive not in ("limited", "ideal"):
+        raise ValueError(f"drive must be 'ideal' or 'limited', got {drive!r}")
+    inr = _inertia_arrays(inertia)
+    x, feet = np.asarray(x, dtype=float), np.asarray(feet, dtype=float)
+    B = x.shape[0]
+    fr = np.asarray(f, dtype=float).reshape(B, 4, 3)
+    stance = np.asarray(contact).reshape(B, 4) != 0
+    mu = None if ground is None else np.asarray(ground, dtype=float).reshape(B)
+    with np.errstate(invalid="ignore"):
+        robot = np.isfinite(x[:, :12]).all(axis=1) & (True if mu is None else (np.isfinite(mu) & (mu >= 0.0)))
+    leg = np.isfinite(fr).all(axis=-1) & np.isfinite(feet).all(axis=-1)
+    # a poisoned row computes on clean stand-ins and is selected away at the end
+    xs = np.where(robot[:, None], x[:, :12], 0.0)
+    fs, ps = np.where(leg[..., None], fr, 0.0), np.where(leg[..., None], feet, 0.0)
+    mus = np.zeros(B) if mu is None else np.where(robot, mu, 0.0)
+    q, tc, reach = (a[:, 0] for a in joint_log_host(xs[:, None], fs.reshape(B, 1, 12), ps[:, None]))
+    R = Rotation.from_rotvec(xs[:, :3]).as_matrix()
+    tmax = inr["tau_max"]
+    with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+        z, p = _leg_chain(q)[1:]
+        J = np.stack([np.cross(z[k], p[3] - p[k]) for k in range(3)], axis=-1)                  # [B,4,3,3], leg_fk_jac's
+        ta = np.minimum(np.maximum(tc, -tmax), tmax) if drive == "limited" else tc
+        clamped = (ta != tc).any(axis=-1)
+        g, det = _adj_solve(np.swapaxes(J, -1, -2), ta)                                       # J^-T tau_app
+        Rl = R[:, None]
+        fc = -np.stack([(Rl[..., a, 0] * g[..., 0] + Rl[..., a, 1] * g[..., 1]) + Rl[..., a, 2] * g[..., 2] for a in range(3)], axis=-1)
+        solve = (reach != 0) & (det != 0.0)
+        f1 = np.where((clamped & solve)[..., None], fc, fs)
+        pull = f1[..., 2] <= 0.0
+        ft = np.sqrt(f1[..., 0] * f1[..., 0] + f1[..., 1] * f1[..., 1])
+        cap = mus[:, None] * f1[..., 2]
+        cone = (ft > cap) if mu is not None else np.zeros((B, 4), bool)
+        s = cap / ft
+        f2 = np.stack([np.where(cone, f1[..., 0] * s, f1[..., 0]), np.where(cone, f1[..., 1] * s, f1[..., 1]), f1[..., 2]], axis=-1)
+        f2 = np.where(pull[..., None], 0.0, f2)
+        limited = (f2 != f1).any(axis=-1)
+        fo = np.where(limited[..., None], f2, f1)
+        h = -np.stack([(Rl[..., 0, a] * f2[..., 0] + Rl[..., 1, a] * f2[..., 1]) + Rl[..., 2, a] * f2[..., 2] for a in range(3)], axis=-1)
+        tg = np.stack([(J[..., 0, j] * h[..., 0] + J[..., 1, j] * h[..., 1]) + J[..., 2, j] * h[..., 2] for j in range(3)], axis=-1)
+        to = np.where(limited[..., None], tg, ta)
+        bits = (np.where(clamped, DRIVE_CLAMPED, 0) | np.where(clamped & ~solve, DRIVE_UNRESOLVED, 0) | np.where(limited, DRIVE_GROUND, 0)
+                | np.where(((q < inr["q_min"]) | (q > inr["q_max"])).any(axis=-1), DRIVE_QLIM, 0))
+        rel = lambda val, thr: np.abs(val - thr) / np.maximum(1.0, np.abs(thr))
+        # an unclamped leg's f1 is f as read and its ground decisions are exact comparisons of correctly rounded operations: only a
+        # clamped leg's computed f1 can fall on the other side of them
+        margin = np.full((B, 4), np.inf)
+        if drive == "limited":
+            margin = rel(np.abs(tc), tmax).min(axis=-1)
+        ground_margin = rel(f1[..., 2], 0.0)
+        if mu is not None:
+            ground_margin = np.minimum(ground_margin, np.where(pull, np.inf, rel(ft, cap)))
+        margin = np.where(clamped & solve, np.minimum(margin, ground_margin), margin)
+        good = robot[:, None] & (~stance | (leg & np.isfinite(fo).all(axis=-1) & np.isfinite(to).all(axis=-1)))
+    st3 = stance[..., None]
+    out_f = np.where(good[..., None], np.where(st3, fo, fr), np.nan)
+    out_t = np.where(good[..., None], np.where(st3, to, 0.0), np.nan)
+    flag = np.where(good, np.where(stance, bits, 0), 0xff).astype(np.uint8)
+    return {"f": out_f.reshape(B, 12), "tau": out_t, "flag": flag, "tau_cmd": np.where((good & stance)[..., None], tc, np.nan), "q": q,
+            "reach": reach, "margin": np.where(good & stance, margin, np.inf)}
+
+
 def world_jacobians(R_body, q_all):
     """{leg: 3x3 world-frame linear Jacobian block} for joint angles q_all[4,3] (src/main.py:205-210)."""
     return {LEGS[k]: R_body @ leg_fk_jac(k, q_all[k])[1] for k in range(4)}

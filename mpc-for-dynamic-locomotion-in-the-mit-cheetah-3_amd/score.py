@@ -5,7 +5,12 @@ device reduction, the per-robot figures a study reads off a score row, and the l
 row of `len(FIELDS)` values per robot; `score_host` does the same arithmetic in numpy on the same logs (every row term with the same
 operations in the same order, so the two differ by the order of the sum over the ticks alone); `summarize` turns rows into RMS errors,
 distance, duty factors, joint work, cost of transport, falls and landing misses; `scored_rollout` carries one score row through the pieces
-of a roll-out, so that 1000 ticks of 65 536 robots need the log memory of one piece."""
+of a roll-out, so that 1000 ticks of 65 536 robots need the log memory of one piece.
+
+The logs of `rollout_drive` score like `rollout_legs`': "forces" holds the APPLIED forces, so fz_max, fric_max and f_sq are what the
+plant received.  `clamp_rows` and `singular_rows` count bits 2 and 16 on any leg-row, so on a drive log they include the stance rows
+whose torque the drive clamped or could not resolve (`summarize`'s clamp_share still divides by the swing rows: on a drive log count
+the swing rows' bit 2 yourself if the share of saturated swings is what is wanted); bit 32, the ground's, is not counted by any field."""
 from __future__ import annotations
 
 import numpy as np
