@@ -8,8 +8,9 @@
  * (DESIGN.md section 4), so everything the handle precomputes from the horizon, the tick and the weights stays shared.
  *
  * The symbols declared here are exported by the product library libmpcqp.so ONLY; the CPU checker library under oracle/ does
- * not have them (the host-side counterpart is models.solve_batch_models_host / models.rollout_plant_models_host in the Python
- * package: one checker handle per distinct row).  Return codes and mpcqp_last_error() as in mpcqp.h.
+ * not have them (the host-side counterpart is models.grouped_host in the Python package, one checker handle per distinct row,
+ * behind models.solve_batch_models_host and models.rollout_models_host / rollout_plant_models_host / rollout_phase_models_host /
+ * rollout_legs_models_host / rollout_drive_models_host).  Return codes and mpcqp_last_error() as in mpcqp.h.
  *
  * Row layout: model[b] = (m, Ixx, Iyy, Izz, f_min, f_max), fp64 WHATEVER the handle's I/O dtype -- the table is small and set
  * once, not per tick, and fp64 lets a row reproduce the configuration exactly.  The first four entries are the first four of a
@@ -40,10 +41,17 @@ extern "C" {
  * synchronisation); one that is not may run before the kernel and then reports MPCQP_STATUS_NONFINITE for every QP (no table
  * on the device yet) or reads the rows of the table set before.
  *
- * While a table is set, mpcqp_solve_batch, mpcqp_solve_batch_gait, mpcqp_solve_batch_gait_steps, mpcqp_rollout and
- * mpcqp_rollout_plant read row b for batch slot b, and a call with a B other than the table's returns MPCQP_EINVAL (the message
- * names both sizes).  X_out is then the prediction under the robot's own row.  mpcqp_rollout_plant with body = NULL still steps
- * the plant with the configuration's model.
+ * While a table is set, every entry point that solves reads row b for batch slot b: mpcqp_solve_batch, mpcqp_solve_batch_gait,
+ * mpcqp_solve_batch_gait_steps and mpcqp_solve_batch_phase (mpcqp_plan.h), and, on every tick, the roll-outs mpcqp_rollout,
+ * mpcqp_rollout_plant, mpcqp_rollout_phase, mpcqp_rollout_legs and mpcqp_rollout_drive (mpcqp_sim.h).  A call of one of them with
+ * a B other than the table's returns MPCQP_EINVAL (the message names the entry point and both sizes).  X_out is then the
+ * prediction under the robot's own row, and so is the next state of mpcqp_rollout (x <- X[:,1]).
+ *
+ * The row is the MPC's model and nothing else.  The plant of mpcqp_rollout_plant / _phase / _legs / _drive and of mpcqp_plant_step,
+ * the legs step of mpcqp_rollout_legs / _drive (its torso acceleration is the plant's right-hand side) and mpcqp_leg_effort /
+ * mpcqp_swing_track (mpcqp_joints.h) take their body from `body`; with body = NULL they use the CONFIGURATION's model
+ * (MpcQpConfig.m, 1 / Ibody_inv), whatever the table says.  A robot whose plant is to be the body of its row passes
+ * body[b] = (m, Ixx, Iyy, Izz, 0, 0, 0).  The stance drive (mpcqp_stance_drive, and inside mpcqp_rollout_drive) reads neither.
  *
  * MPCQP_EINVAL for B <= 0 or a null `model`, MPCQP_ENOMEM when the table cannot be grown; the table set before, if any, then stays.
  */

@@ -133,9 +133,12 @@ class MPCBatch:
 
     def set_models(self, models, stream=None):
         """Per-robot model rows (include/mpcqp_model.h, mpcqp_set_models): `models` [B,6] = (m, Ixx, Iyy, Izz, f_min, f_max) per batch
-        slot, a float64 tensor on the engine's device or a numpy array (uploaded).  Every later solve, gait solve and roll-out of
-        this engine builds QP b from row b and must have B robots; rows are fp64 whatever the I/O dtype (mpcqp.models has the row
-        helpers and the host checker).  Asynchronous on `stream`."""
+        slot, a float64 tensor on the engine's device or a numpy array (uploaded).  Every later `solve_batch`, `solve_batch_gait`,
+        `solve_batch_phase`, `rollout`, `rollout_plant`, `rollout_phase`, `rollout_legs` and `rollout_drive` of this engine builds
+        QP b -- on every tick -- from row b and must have B robots; rows are fp64 whatever the I/O dtype (mpcqp.models has the row
+        helpers and the host checkers).  The row is the MPC's model only: the plant (`rollout_*`, `plant_step`), the legs step of
+        `rollout_legs` / `rollout_drive`, `leg_effort` and `swing_track` take `body`, and with body=None the CONFIGURATION's model,
+        whatever the table says (a matched plant is body[b] = (m, Ixx, Iyy, Izz, 0, 0, 0) of row b).  Asynchronous on `stream`."""
         torch = _torch()
         if not hasattr(models, "data_ptr"):
             models = torch.as_tensor(np.ascontiguousarray(models, dtype=np.float64)).to(self.device)
