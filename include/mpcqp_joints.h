@@ -267,6 +267,9 @@ int mpcqp_leg_accel(mpcqp_handle h, int64_t B, const void* q, const void* qd, co
  * included, whatever the input was: the miss of a poisoned swing is not known; the leg is clean from the row after -- and so does a
  * state that stops being finite; no other leg changes.
  *
+ * The clamp is the flat box of the inertia row's tau_max; with an actuator table set (include/mpcqp_actuators.h, mpcqp_set_actuators) it
+ * is robot b's torque-speed envelope at the leg state's qd at the start of the control period, and mpcqp_leg_effort's limit bit 4 is
+ * tau outside that envelope at the row's qd.
  * Not built: the legs' reaction on the torso, joint-limit stops (a joint beyond its limit is flagged, not stopped) and ground contact
  * of a swing foot (a foot below the ground is not stopped; the landing row's err says where it was).  This call runs after the roll-out,
  * on its logs; mpcqp_rollout_legs (include/mpcqp_sim.h) runs the same row inside the roll-out, tick by tick, and can land a foot where

@@ -293,7 +293,9 @@ int mpcqp_stance_drive(mpcqp_handle h, int64_t B, const void* x, const void* f, 
  * Six launches per tick, seven with tau_log or flag_log; no host synchronisation, copy or allocation inside the T ticks (the side
  * buffers are part of the roll-out's reserve).  A non-finite or negative ground row: that robot's applied forces are NaN, its solves
  * report MPCQP_STATUS_NONFINITE from the next tick with a stance leg on, and no other robot changes.
- * Not built: slip kinematics, a tau_max per robot, torque-speed curves, a variant on plan tables.
+ * A tau_max per robot and a torque-speed curve are include/mpcqp_actuators.h: while mpcqp_set_actuators has set a table, step 2 clamps at
+ * robot b's envelope at the joint rates with the foot at rest in the world, and the tau_max of `inr` is not read.
+ * Not built: slip kinematics, per-robot joint limits, a variant on plan tables.
  */
 #define MPCQP_DRIVE_IDEAL 0
 #define MPCQP_DRIVE_LIMITED 1

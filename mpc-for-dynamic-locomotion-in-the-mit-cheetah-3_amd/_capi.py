@@ -1,5 +1,5 @@
-"""ctypes binding of the C-ABI declared in include/mpcqp.h and its product-only extensions include/mpcqp_plan.h, mpcqp_sim.h, mpcqp_model.h
-and mpcqp_joints.h.
+"""ctypes binding of the C-ABI declared in include/mpcqp.h and its product-only extensions include/mpcqp_plan.h, mpcqp_sim.h, mpcqp_model.h,
+mpcqp_joints.h and mpcqp_actuators.h.
 
 The product path loads ``csrc/libmpcqp.so`` (hand-written HIP for gfx950) and nothing else: if that library is
 missing or cannot be loaded, importing the engine raises -- there is no CPU fallback.  The binding itself is
@@ -161,6 +161,16 @@ ABI = {
     ),
 }
 EXPORTED_SYMBOLS, PLAN_SYMBOLS, SIM_SYMBOLS, MODEL_SYMBOLS, JOINTS_SYMBOLS = (tuple(row[0] for row in rows) for rows in ABI.values())
+# include/mpcqp_actuators.h, the newest header, in a table of its own with the same rows: a product library built before it binds the five
+# headers above as it always did, and `has_actuators` tells the two apart.
+ACTUATORS_HEADER = "mpcqp_actuators.h"
+ACTUATORS_ABI = {
+    ACTUATORS_HEADER: (  # per-robot actuator rows
+        ("mpcqp_set_actuators", c_int, (_P, _I64, _P, _P)),
+        ("mpcqp_clear_actuators", c_int, (_P,)),
+    ),
+}
+ACTUATOR_SYMBOLS = tuple(row[0] for row in ACTUATORS_ABI[ACTUATORS_HEADER])
 # The swing-leg plant of include/mpcqp_joints.h came after the rest of that header: a product library built before it still has the
 # header's other calls (`has_joints`) and is told apart by `has_legsim`.
 LEGSIM_SYMBOLS = ("mpcqp_leg_accel", "mpcqp_swing_track")
@@ -180,8 +190,8 @@ DRIVE_CLAMPED, DRIVE_QLIM, DRIVE_UNRESOLVED, DRIVE_GROUND, DRIVE_POISONED = 2, 4
 
 
 class Library:
-    """A loaded shared object exporting the mpcqp C-ABI.  `has_plan`, `has_sim`, `has_model` and `has_joints` say whether it exports
-    all of include/mpcqp_plan.h, mpcqp_sim.h, mpcqp_model.h and mpcqp_joints.h (of the last: all but LEGSIM_SYMBOLS, which `has_legsim`
+    """A loaded shared object exporting the mpcqp C-ABI.  `has_plan`, `has_sim`, `has_model`, `has_joints` and `has_actuators` say whether
+    it exports all of include/mpcqp_plan.h, mpcqp_sim.h, mpcqp_model.h, mpcqp_joints.h and mpcqp_actuators.h (of mpcqp_joints.h: all but LEGSIM_SYMBOLS, which `has_legsim`
     answers for; of mpcqp_sim.h: all but LEGROLL_SYMBOLS, SCORE_SYMBOLS and DRIVE_SYMBOLS, `has_legroll`, `has_score` and `has_drive`).  An
     extension header's calls are bound only when the library
     has them all; `partial=True` binds whichever it has (an older build of the product library, in a comparison tool)."""
@@ -196,7 +206,7 @@ class Library:
         self.has_legroll = all(hasattr(self.lib, name) for name in LEGROLL_SYMBOLS)
         self.has_score = all(hasattr(self.lib, name) for name in SCORE_SYMBOLS)
         self.has_drive = all(hasattr(self.lib, name) for name in DRIVE_SYMBOLS)
-        for header, rows in ABI.items():
+        for header, rows in {**ABI, **ACTUATORS_ABI}.items():
             have = header == CORE_HEADER or all(hasattr(self.lib, row[0]) for row in rows if row[0] not in _GATED)
             if header != CORE_HEADER:
                 setattr(self, "has_" + header[len("mpcqp_"):-len(".h")], have)
@@ -381,6 +391,14 @@ class Engine:
     def clear_models(self):
         """mpcqp_clear_models (include/mpcqp_model.h): back to the configuration's m, Ibody_inv, f_min, f_max."""
         self._call("mpcqp_clear_models")
+
+    def set_actuators_ptr(self, B, act, stream=0):
+        """mpcqp_set_actuators (include/mpcqp_actuators.h): `act` is the address of an fp64 [B,9] device table."""
+        self._call("mpcqp_set_actuators", B, act, stream)
+
+    def clear_actuators(self):
+        """mpcqp_clear_actuators (include/mpcqp_actuators.h): back to the inertia row's tau_max for every clamp."""
+        self._call("mpcqp_clear_actuators")
 
     # (`geometry` is an MpcQpLegGeometry or None = the Lite3; ctypes passes the structure by reference)
     def leg_ik_ptr(self, B, foot, rot, origin, q, reach=0, geometry=None, stream=0):

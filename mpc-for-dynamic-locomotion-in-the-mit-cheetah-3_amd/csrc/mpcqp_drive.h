@@ -28,13 +28,20 @@ constexpr unsigned DRIVE_BITS = 2u | 16u | 32u;     // what the rule adds to a s
 
 // Steps 2 to 5 of the rule for a stance leg: R world <- torso, J = d foot / d q at the leg's q (both by rows), reach the IK's, f the
 // commanded force and tc = (R J)^T (-f); mu < 0 means no friction limit.  Writes the applied force and torque, returns the bits.
+// ACT: step 2 is the envelope of the actuator row `ar` at the joint rates qr, not the box of lim.taumax.
+template <bool ACT = false>
 __device__ __forceinline__ unsigned drive_rule(const double (&R)[9], const double (&J)[9], const bool reach, const V3 f, const V3 tc,
                                                const LegLimDev& lim, const bool limited, const bool cone_on, const double mu, V3& fo,
-                                               V3& to) {
+                                               V3& to, const double* __restrict__ ar = nullptr, const V3 qr = {0.0, 0.0, 0.0}) {
 #pragma clang fp contract(off)
   // 2. the actuators
-  const V3 ta = {limited ? clamp_sym(tc.x, lim.taumax[0]) : tc.x, limited ? clamp_sym(tc.y, lim.taumax[1]) : tc.y,
-                 limited ? clamp_sym(tc.z, lim.taumax[2]) : tc.z};
+  V3 ta;
+  if constexpr (ACT)
+    ta = {limited ? act_clamp(ar, 0, tc.x, qr.x) : tc.x, limited ? act_clamp(ar, 1, tc.y, qr.y) : tc.y,
+          limited ? act_clamp(ar, 2, tc.z, qr.z) : tc.z};
+  else
+    ta = {limited ? clamp_sym(tc.x, lim.taumax[0]) : tc.x, limited ? clamp_sym(tc.y, lim.taumax[1]) : tc.y,
+          limited ? clamp_sym(tc.z, lim.taumax[2]) : tc.z};
   const bool clamped = ta.x != tc.x || ta.y != tc.y || ta.z != tc.z;
   // 3. f1 = -A^-1 tau_app, A = (R J)^T = J^T R^T: g = J^-T tau_app, f1 = -(R g)
   const M3 Jt = {{J[0], J[3], J[6]}, {J[1], J[4], J[7]}, {J[2], J[5], J[8]}};
@@ -63,63 +70,29 @@ __device__ __forceinline__ unsigned drive_rule(const double (&R)[9], const doubl
 // clock of `gait` [B,9] at max(tick[b], 0); ground [B] or null.  f_out [B,12] (may be f when fstride = 12: a lane reads its own three
 // values before it writes them), tau [B,4,3] or null, flag u8 [B,4] or null, cmd or null: robot b's commanded forces as read, to
 // cmd + b cstride.
+// The kernel's text is mpcqp_drive_leg.inl, included once in this kernel and once in its ACT twin below: a device function shared by
+// the two changes this kernel's assembly (tried with by-reference and by-value rows), a second copy of the text would drift.
 template <typename TIO>
 __global__ void __launch_bounds__(256)
 mpcqp_stance_drive_kernel(const TIO* __restrict__ x, const TIO* f, const int64_t fstride, const TIO* __restrict__ feet,
                           const uint8_t* __restrict__ contact, const int32_t* __restrict__ gait, const int32_t* __restrict__ tick,
                           const TIO* __restrict__ ground, const LegGeoDev geo, const LegLimDev lim, const int drive, TIO* f_out,
                           TIO* __restrict__ tau, uint8_t* __restrict__ flag, TIO* __restrict__ cmd, const int64_t cstride, const int64_t B) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= 4 * B) return;
-  const int64_t b = i / 4;
-  const int l = (int)(i % 4);
-  const TIO* xb = x + 13 * b;   // rotation vector, CoM, ...
-  const TIO* fb = f + b * fstride + 3 * l;
-  const TIO fr[3] = {fb[0], fb[1], fb[2]};
-  bool stance;
-  if (contact) {
-    stance = contact[i] != 0;
-  } else {
-    const GaitLeg gc = gait_leg(gait + b * GAIT_ROW, l);
-    stance = gait_phase(gc, (uint32_t)max(tick[b], 0)) < gc.st;
-  }
-  // mpcqp_joint_log's row: R from the rotation vector, the foot seen from the CoM, q and tau_cmd
-  double qt[4], pw[3], fl[3], ql[3], tl[3];
-  plant_rotvec_to_quat((double)xb[0], (double)xb[1], (double)xb[2], qt);
-  const double qw = qt[0], qx = qt[1], qy = qt[2], qz = qt[3];
-  const double R[9] = {1.0 - 2.0 * (qy * qy + qz * qz), 2.0 * (qx * qy - qw * qz), 2.0 * (qx * qz + qw * qy),
-                       2.0 * (qx * qy + qw * qz), 1.0 - 2.0 * (qx * qx + qz * qz), 2.0 * (qy * qz - qw * qx),
-                       2.0 * (qx * qz - qw * qy), 2.0 * (qy * qz + qw * qx), 1.0 - 2.0 * (qx * qx + qy * qy)};
-#pragma unroll
-  for (int a = 0; a < 3; ++a) {
-    pw[a] = (double)feet[3 * i + a] - (double)xb[3 + a];
-    fl[a] = (double)fr[a];
-  }
-  const bool reach = leg_joints<true>(geo, l, R, pw, fl, ql, tl);
-  double pf[3], J[9];
-  leg_fk_jac(geo, l, ql, pf, J);
-  const V3 fv = {fl[0], fl[1], fl[2]}, tc = {tl[0], tl[1], tl[2]}, q = {ql[0], ql[1], ql[2]}, zero = {0.0, 0.0, 0.0};
-  const double mu = ground ? (double)ground[b] : 0.0;
-  V3 fo, to;
-  unsigned bits = drive_rule(R, J, reach, fv, tc, lim, drive == DRIVE_LIMITED, ground != nullptr, mu, fo, to);
-  bits |= swing_limits(lim, q, zero);   // 4: q outside its limits
-  // the robot's x and ground row poison its four legs, a leg's own operands that leg
-  bool robot = isfinite(mu) && mu >= 0.0;
-#pragma unroll
-  for (int a = 0; a < 12; ++a) robot = robot && isfinite((double)xb[a]);
-  const bool good = robot && (!stance || (fin3(fv) && isfinite(pw[0]) && isfinite(pw[1]) && isfinite(pw[2]) && fin3(fo) && fin3(to)));
-  const double nan = __builtin_nan("");
-  TIO* fw = f_out + 12 * b + 3 * l;
-  if (cmd) {
-    TIO* cw = cmd + b * cstride + 3 * l;
-    cw[0] = fr[0]; cw[1] = fr[1]; cw[2] = fr[2];
-  }
-  // a swing leg keeps its commanded force as read
-  fw[0] = good ? (stance ? (TIO)fo.x : fr[0]) : (TIO)nan;
-  fw[1] = good ? (stance ? (TIO)fo.y : fr[1]) : (TIO)nan;
-  fw[2] = good ? (stance ? (TIO)fo.z : fr[2]) : (TIO)nan;
-  if (tau) store3(tau + 3 * i, good, sel3(stance, to, zero));
-  if (flag) flag[i] = good ? (uint8_t)(stance ? bits : 0u) : (uint8_t)0xff;
+  constexpr bool ACT = false;
+  const double* const act = nullptr;
+#include "mpcqp_drive_leg.inl"
+}
+
+// ... with an actuator table set (include/mpcqp_actuators.h): act [B,9], lim.taumax is not read.
+template <typename TIO>
+__global__ void __launch_bounds__(256)
+mpcqp_stance_drive_act_kernel(const TIO* __restrict__ x, const TIO* f, const int64_t fstride, const TIO* __restrict__ feet,
+                              const uint8_t* __restrict__ contact, const int32_t* __restrict__ gait, const int32_t* __restrict__ tick,
+                              const TIO* __restrict__ ground, const LegGeoDev geo, const LegLimDev lim, const int drive, TIO* f_out,
+                              TIO* __restrict__ tau, uint8_t* __restrict__ flag, TIO* __restrict__ cmd, const int64_t cstride, const int64_t B,
+                              const double* __restrict__ act) {
+  constexpr bool ACT = true;
+#include "mpcqp_drive_leg.inl"
 }
 
 // After the legs step of tick `it`, before the advance (tick is still the row's): i = 4 b + leg.  rtau [B,4,3] and rflag [B,4] are what

@@ -3,7 +3,7 @@
 // Replaces, for a batch of B independent robots, the solve the reference performs once per control tick:
 // CasADi Opti('conic') -> OSQP on the QP of src/mpc.py:58-173, filled at src/mpc.py:242-255, solved at :258.
 //
-// This translation unit is the C-ABI of include/mpcqp.h, mpcqp_plan.h, mpcqp_sim.h, mpcqp_model.h and mpcqp_joints.h: the handle, its host helpers (I/O-type
+// This translation unit is the C-ABI of include/mpcqp.h, mpcqp_plan.h, mpcqp_sim.h, mpcqp_model.h, mpcqp_joints.h and mpcqp_actuators.h: the handle, its host helpers (I/O-type
 // dispatch, workspaces, the policy behind the configuration's defaults) and the extern "C" entry points.  The device code is in
 //   mpcqp_wrench.h       the engine: wrench-space (Woodbury) form, H = 2 alpha I + T'KT with a 6N x 6N system, one QP per wave
 //                        (horizon 10) or per four waves (horizon 20), fp32 or fp64 ADMM, fp64 active-set polish, ADMM-only mode
@@ -18,6 +18,7 @@
 //   mpcqp_gaits.h        per-leg periodic gaits: the phase clock, the touchdown foothold rule and their expansion into an operator tuple
 //   mpcqp_model.h        per-robot model rows: the conversion of the caller's table into the engine's
 //   mpcqp_joints.h       closed-form leg inverse kinematics and the joint-space log of a roll-out
+//   mpcqp_actuators.h    per-robot actuator rows: the conversion of the caller's table and the torque-speed envelope the leg kernels share
 // DESIGN.md has the derivations.
 
 #include "mpcqp_wrench.h"
@@ -25,6 +26,7 @@
 #include "mpcqp_elementwise.h"
 #include "mpcqp_model.h"
 #include "mpcqp_joints.h"
+#include "mpcqp_actuators.h"
 #include "mpcqp_legdyn.h"
 #include "mpcqp_legsim.h"
 #include "mpcqp_legroll.h"
@@ -75,6 +77,9 @@ struct mpcqp_engine {
   double* model_mem = nullptr;   // per-robot model rows (include/mpcqp_model.h): the converted table [model_cap][MODEL_ROW]
   int64_t model_B = 0;        // rows of the table that is set; 0 = none, every QP has the configuration's
   int64_t model_cap = 0;
+  double* act_mem = nullptr;     // per-robot actuator rows (include/mpcqp_actuators.h): the converted table [act_cap][ACT_ROW]
+  int64_t act_B = 0;          // rows of the table that is set; 0 = none, every clamp reads the call's MpcQpLegInertia.tau_max
+  int64_t act_cap = 0;
   bool timed = false;
   char err[512];
 };
@@ -213,6 +218,13 @@ hipError_t enqueue_solve(mpcqp_engine* h, int64_t B, const FastIn<T>& in, T* u, 
 int models_match(mpcqp_engine* h, int64_t B, const char* who) {
   if (h->model_B == 0 || h->model_B == B) return MPCQP_OK;
   snprintf(h->err, sizeof(h->err), "%s: batch size %lld, but the model table has %lld rows", who, (long long)B, (long long)h->model_B);
+  return MPCQP_EINVAL;
+}
+
+// The batch of a call that clamps joint torques against the actuator table, when one is set (include/mpcqp_actuators.h).
+int actuators_match(mpcqp_engine* h, int64_t B, const char* who) {
+  if (h->act_B == 0 || h->act_B == B) return MPCQP_OK;
+  snprintf(h->err, sizeof(h->err), "%s: batch size %lld, but the actuator table has %lld rows", who, (long long)B, (long long)h->act_B);
   return MPCQP_EINVAL;
 }
 
@@ -529,6 +541,7 @@ static void free_engine(mpcqp_engine* h) {
   if (h->order_mem) (void)hipFree(h->order_mem);
   if (h->dual_mem) (void)hipFree(h->dual_mem);
   if (h->model_mem) (void)hipFree(h->model_mem);
+  if (h->act_mem) (void)hipFree(h->act_mem);
   if (h->gait_mem) (void)hipFree(h->gait_mem);
   if (h->roll_mem) (void)hipFree(h->roll_mem);
   if (h->plan_ws) (void)hipFree(h->plan_ws);
@@ -931,6 +944,36 @@ int mpcqp_clear_models(mpcqp_handle h) {
   return MPCQP_OK;
 }
 
+// include/mpcqp_actuators.h.  The table is a kernel argument of the ACT instantiations, so only the host side of the handle knows it.
+int mpcqp_set_actuators(mpcqp_handle h, int64_t B, const double* act, void* stream) {
+  if (!h) return MPCQP_EINVAL;
+  if (B <= 0 || B > 0x7fffffff) return fail(h, MPCQP_EINVAL, "mpcqp_set_actuators: batch size out of range");
+  if (!act) return fail(h, MPCQP_EINVAL, "mpcqp_set_actuators: null actuator table");
+  DeviceGuard guard(h->cfg.device);
+  if (guard.err != hipSuccess) return fail(h, MPCQP_EHIP, "hipSetDevice", guard.err);
+  if (h->act_cap < B) {   // once per size, as mpcqp_set_models grows its table (grow waits for the device before it frees the old buffer)
+    if (!grow(h->act_mem, (size_t)B * ACT_ROW * sizeof(double))) return fail(h, MPCQP_ENOMEM, "mpcqp_set_actuators: table allocation failed");
+    h->act_cap = B;
+    h->act_B = 0;   // (the old rows are gone: if the launch below fails, no call may read the new buffer)
+  }
+  hipLaunchKernelGGL(mpcqp_actuator_rows_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, (hipStream_t)stream, act, h->act_mem, B);
+  const int rc = launched(h, "actuator table kernel launch");
+  h->act_B = rc == MPCQP_OK ? B : 0;
+  return rc;
+}
+
+int mpcqp_clear_actuators(mpcqp_handle h) {
+  if (!h) return MPCQP_EINVAL;
+  if (h->act_B == 0) return MPCQP_OK;
+  DeviceGuard guard(h->cfg.device);
+  if (guard.err != hipSuccess) return fail(h, MPCQP_EHIP, "hipSetDevice", guard.err);
+  // No stream argument: the calls enqueued so far (on whatever stream) finish with the table, every later one runs without it.
+  const hipError_t he = hipDeviceSynchronize();
+  if (he != hipSuccess) return fail(h, MPCQP_EHIP, "mpcqp_clear_actuators", he);
+  h->act_B = 0;
+  return MPCQP_OK;
+}
+
 int mpcqp_plant_step(mpcqp_handle h, int64_t B, const void* x, const void* f, const void* feet, const uint8_t* contact,
                      const void* body, const void* wrench, int32_t substeps, void* x_out, void* stream) {
   if (!h) return MPCQP_EINVAL;
@@ -1328,15 +1371,22 @@ int mpcqp_leg_effort(mpcqp_handle h, int64_t B, int32_t T, const void* actual, c
   LegInrDev r;
   if (const int rc = leg_inertia_row(h, "mpcqp_leg_effort", inr, r)) return rc;
   if (B == 0 || T == 0) return MPCQP_OK;
+  if (const int rc = actuators_match(h, B, "mpcqp_leg_effort")) return rc;
   DeviceGuard guard(h->cfg.device);
   if (guard.err != hipSuccess) return fail(h, MPCQP_EHIP, "hipSetDevice", guard.err);
   const int64_t rows = B * T;
   const dim3 grid((unsigned)((4 * rows + 255) / 256));
   with_io(h, [&](auto tag) {
     using TIO = decltype(tag);
-    hipLaunchKernelGGL((mpcqp_leg_effort_kernel<TIO>), grid, dim3(256), 0, (hipStream_t)stream, (const TIO*)actual, (const TIO*)forces,
-                       (const TIO*)feet, (const TIO*)foot_vel, (const TIO*)foot_acc, (const TIO*)base_acc, (const TIO*)body, plant_model(h),
-                       g, r.k0, r.k1, r.k2, r.lim, (TIO*)qdd, (TIO*)tau_dyn, (TIO*)tau, (TIO*)power, limit, rows, (int64_t)T);
+    if (h->act_B > 0)   // (a handle with an actuator table runs the instantiations that read it; without one, the kernels are what they were)
+      hipLaunchKernelGGL((mpcqp_leg_effort_act_kernel<TIO>), grid, dim3(256), 0, (hipStream_t)stream, (const TIO*)actual, (const TIO*)forces,
+                         (const TIO*)feet, (const TIO*)foot_vel, (const TIO*)foot_acc, (const TIO*)base_acc, (const TIO*)body, plant_model(h),
+                         g, r.k0, r.k1, r.k2, r.lim, (TIO*)qdd, (TIO*)tau_dyn, (TIO*)tau, (TIO*)power, limit, rows, (int64_t)T,
+                         (const double*)h->act_mem);
+    else
+      hipLaunchKernelGGL((mpcqp_leg_effort_kernel<TIO>), grid, dim3(256), 0, (hipStream_t)stream, (const TIO*)actual, (const TIO*)forces,
+                         (const TIO*)feet, (const TIO*)foot_vel, (const TIO*)foot_acc, (const TIO*)base_acc, (const TIO*)body, plant_model(h),
+                         g, r.k0, r.k1, r.k2, r.lim, (TIO*)qdd, (TIO*)tau_dyn, (TIO*)tau, (TIO*)power, limit, rows, (int64_t)T);
   });
   return launched(h, "leg effort kernel launch");
 }
@@ -1379,6 +1429,7 @@ int mpcqp_swing_track(mpcqp_handle h, int64_t B, int32_t T, const void* actual, 
   LegInrDev r;
   if (const int rc = leg_inertia_row(h, "mpcqp_swing_track", inr, r)) return rc;
   if (B == 0 || T == 0) return MPCQP_OK;
+  if (const int rc = actuators_match(h, B, "mpcqp_swing_track")) return rc;
   int n = substeps;
   if (n == 0) {   // the default control period: the fewest periods of at most SWING_H0
     n = (int)std::ceil(h->cfg.delta / SWING_H0);
@@ -1393,8 +1444,12 @@ int mpcqp_swing_track(mpcqp_handle h, int64_t B, int32_t T, const void* actual, 
     const SwingIn<TIO> in = {(const TIO*)actual, (const TIO*)forces, (const TIO*)feet_log, contact_log, (const TIO*)swing,
                              (const TIO*)base_acc, (const TIO*)body, (const TIO*)gains};
     const SwingOut<TIO> out = {(TIO*)q, (TIO*)qd, (TIO*)tau, (TIO*)foot, (TIO*)err, flag};
-    hipLaunchKernelGGL((mpcqp_swing_track_kernel<TIO>), grid, dim3(256), 0, (hipStream_t)stream, in, (TIO*)state, plant_model(h), g, r.k0,
-                       r.k1, r.k2, r.lim, out, B, (int)T, n, h->cfg.delta / n);
+    if (h->act_B > 0)
+      hipLaunchKernelGGL((mpcqp_swing_track_act_kernel<TIO>), grid, dim3(256), 0, (hipStream_t)stream, in, (TIO*)state, plant_model(h), g, r.k0,
+                         r.k1, r.k2, r.lim, out, B, (int)T, n, h->cfg.delta / n, (const double*)h->act_mem);
+    else
+      hipLaunchKernelGGL((mpcqp_swing_track_kernel<TIO>), grid, dim3(256), 0, (hipStream_t)stream, in, (TIO*)state, plant_model(h), g, r.k0,
+                         r.k1, r.k2, r.lim, out, B, (int)T, n, h->cfg.delta / n);
   });
   return launched(h, "swing track kernel launch");
 }
@@ -1432,6 +1487,8 @@ int rollout_legs_run(mpcqp_handle h, const char* who, int64_t B, int32_t T, void
   if (const int rc = leg_inertia_row(h, who, inr, r)) return rc;
   if (B == 0 || T == 0) return MPCQP_OK;
   if (const int rc = models_match(h, B, who)) return rc;
+  if (const int rc = actuators_match(h, B, who)) return rc;
+  const double* act = h->act_B > 0 ? h->act_mem : nullptr;   // (null: the kernels without a table, which are what they were)
   int nl = leg_substeps;
   if (nl == 0) {   // the default control period, as mpcqp_swing_track: the fewest periods of at most SWING_H0
     nl = (int)std::ceil(h->cfg.delta / SWING_H0);
@@ -1464,12 +1521,21 @@ int rollout_legs_run(mpcqp_handle h, const char* who, int64_t B, int32_t T, void
       const DriveWs<TIO> dw = drive_ws<TIO>(h->roll_mem, B, N);
       if (dr) {
         TIO* cmd = dr->cmd_log ? (TIO*)dr->cmd_log + (size_t)it * 12 : nullptr;
-        hipLaunchKernelGGL((mpcqp_stance_drive_kernel<TIO>), gl, nt, 0, st, xs, o.u, (int64_t)N * 12, (const TIO*)feet, (const uint8_t*)nullptr,
-                           gait, tick, (const TIO*)dr->ground, g, r.lim, (int)dr->drive, dw.f, dw.tau, dw.flag, cmd, (int64_t)T * 12, B);
+        if (act)
+          hipLaunchKernelGGL((mpcqp_stance_drive_act_kernel<TIO>), gl, nt, 0, st, xs, o.u, (int64_t)N * 12, (const TIO*)feet,
+                             (const uint8_t*)nullptr, gait, tick, (const TIO*)dr->ground, g, r.lim, (int)dr->drive, dw.f, dw.tau, dw.flag, cmd,
+                             (int64_t)T * 12, B, act);
+        else
+          hipLaunchKernelGGL((mpcqp_stance_drive_kernel<TIO>), gl, nt, 0, st, xs, o.u, (int64_t)N * 12, (const TIO*)feet, (const uint8_t*)nullptr,
+                             gait, tick, (const TIO*)dr->ground, g, r.lim, (int)dr->drive, dw.f, dw.tau, dw.flag, cmd, (int64_t)T * 12, B);
         u = dw.f; Nu = 1;
       }
-      hipLaunchKernelGGL((mpcqp_legs_step_kernel<TIO>), gl, nt, 0, st, xs, rf, ph, tick, u, (const TIO*)step_height, (const TIO*)gains, legs,
-                         plant_in<TIO>(h, plant), g, r.k0, r.k1, r.k2, r.lim, out, d, Nu, B, (int)T, it, nl, d / nl);
+      if (act)
+        hipLaunchKernelGGL((mpcqp_legs_step_act_kernel<TIO>), gl, nt, 0, st, xs, rf, ph, tick, u, (const TIO*)step_height, (const TIO*)gains,
+                           legs, plant_in<TIO>(h, plant), g, r.k0, r.k1, r.k2, r.lim, out, d, Nu, B, (int)T, it, nl, d / nl, act);
+      else
+        hipLaunchKernelGGL((mpcqp_legs_step_kernel<TIO>), gl, nt, 0, st, xs, rf, ph, tick, u, (const TIO*)step_height, (const TIO*)gains, legs,
+                           plant_in<TIO>(h, plant), g, r.k0, r.k1, r.k2, r.lim, out, d, Nu, B, (int)T, it, nl, d / nl);
       if (dr && (tau_log || flag_log))
         hipLaunchKernelGGL((mpcqp_drive_log_kernel<TIO>), gl, nt, 0, st, gait, tick, dw.tau, dw.flag,
                            (int)(dr->drive == MPCQP_DRIVE_IDEAL && !dr->ground), B, (int)T, it, (TIO*)tau_log, flag_log);
@@ -1517,14 +1583,20 @@ int mpcqp_stance_drive(mpcqp_handle h, int64_t B, const void* x, const void* f, 
   LegInrDev r;
   if (const int rc = leg_inertia_row(h, "mpcqp_stance_drive", inr, r)) return rc;
   if (B == 0) return MPCQP_OK;
+  if (const int rc = actuators_match(h, B, "mpcqp_stance_drive")) return rc;
   DeviceGuard guard(h->cfg.device);
   if (guard.err != hipSuccess) return fail(h, MPCQP_EHIP, "hipSetDevice", guard.err);
   const dim3 grid((unsigned)((4 * B + 255) / 256));
   with_io(h, [&](auto tag) {
     using TIO = decltype(tag);
-    hipLaunchKernelGGL((mpcqp_stance_drive_kernel<TIO>), grid, dim3(256), 0, (hipStream_t)stream, (const TIO*)x, (const TIO*)f, (int64_t)12,
-                       (const TIO*)feet, contact, (const int32_t*)nullptr, (const int32_t*)nullptr, (const TIO*)ground, g, r.lim,
-                       (int)DRIVE_LIMITED, (TIO*)f_out, (TIO*)tau, flag, (TIO*)nullptr, (int64_t)0, B);
+    if (h->act_B > 0)
+      hipLaunchKernelGGL((mpcqp_stance_drive_act_kernel<TIO>), grid, dim3(256), 0, (hipStream_t)stream, (const TIO*)x, (const TIO*)f, (int64_t)12,
+                         (const TIO*)feet, contact, (const int32_t*)nullptr, (const int32_t*)nullptr, (const TIO*)ground, g, r.lim,
+                         (int)DRIVE_LIMITED, (TIO*)f_out, (TIO*)tau, flag, (TIO*)nullptr, (int64_t)0, B, (const double*)h->act_mem);
+    else
+      hipLaunchKernelGGL((mpcqp_stance_drive_kernel<TIO>), grid, dim3(256), 0, (hipStream_t)stream, (const TIO*)x, (const TIO*)f, (int64_t)12,
+                         (const TIO*)feet, contact, (const int32_t*)nullptr, (const int32_t*)nullptr, (const TIO*)ground, g, r.lim,
+                         (int)DRIVE_LIMITED, (TIO*)f_out, (TIO*)tau, flag, (TIO*)nullptr, (int64_t)0, B);
   });
   return launched(h, "stance drive kernel launch");
 }

@@ -152,6 +152,27 @@ class MPCBatch:
         """Back to the configuration's model for every QP (mpcqp_clear_models; waits for the device)."""
         self.engine.clear_models()
 
+    def set_actuators(self, rows, stream=None):
+        """Per-robot actuator rows with a torque-speed curve (include/mpcqp_actuators.h, mpcqp_set_actuators, which has the envelope):
+        `rows` [B,9] = (tau_max[3], qd_knee[3], qd_free[3]) of HipX, HipY, Knee per robot, a float64 tensor on the engine's device or a
+        numpy array (uploaded); mpcqp.actuators has the row helpers and the host counterpart.  Every later `swing_track`, `leg_effort`,
+        `stance_drive`, `rollout_legs` and `rollout_drive` of this engine clamps robot b's joint torques at row b's envelope -- the
+        tau_max of `inertia` is then ignored -- and must have B robots; `stance_drive` on the B T logged rows of a roll-out wants the
+        table tiled (actuators.tile).  A table of flat rows with the inertia row's tau_max (actuators.actuator_rows(B)) is no table, bit
+        for bit.  The MPC is not told.  Asynchronous on `stream`."""
+        torch = _torch()
+        if not hasattr(rows, "data_ptr"):
+            rows = torch.as_tensor(np.ascontiguousarray(rows, dtype=np.float64)).to(self.device)
+        B = int(rows.shape[0]) if rows.dim() == 2 else 0
+        check_operands(self.device, [("rows", rows, (max(B, 1), 9), torch.float64)])   # (at least one row)
+        st = self._stream(stream)
+        rows.record_stream(st)   # (the conversion kernel reads it on `st`; the engine keeps its own table)
+        self.engine.set_actuators_ptr(B, rows.data_ptr(), st.cuda_stream)
+
+    def clear_actuators(self):
+        """Back to the inertia row's tau_max for every clamp (mpcqp_clear_actuators; waits for the device)."""
+        self.engine.clear_actuators()
+
     def solve_batch_gait(self, x0, ref, feet0, footholds, gait, feet_id, mu, want_X=False, stream=None, u_init=None):
         """Gait entry point: contact masks, stance lever arms and x_des are generated on the device (include/mpcqp.h) from S plan steps
         per robot (footholds [B,S,4,3], feet_id [B,S,4]; S = 2 is the original two-step form)."""

@@ -296,32 +296,34 @@ def leg_feet_host(x, legs):
 
 
 def rollout_legs_host(oracle_engine, x, ref, feet, legs, gait, stand, gain, tick, mu, T, step_height, land="rule", body=None, push=None,
-                      push_ticks=None, substeps=DEFAULT_SUBSTEPS, gains=None, leg_substeps=0, inertia=None):
+                      push_ticks=None, substeps=DEFAULT_SUBSTEPS, gains=None, leg_substeps=0, inertia=None, actuators=None):
     """Closed loop of mpcqp_rollout_legs on the CPU checker (host memory, fp64): `rollout_phase_host`'s loop with, per tick, one row of
     `phase_swing_host` and one row of `lite3_model.swing_track_host` (the state carried in `legs` [B,4,7]) formed from the live
     buffers before the plant steps, under `lite3_model.plant_base_acc_host` with the robot's push; after the step the landing miss
     |c + R p_foot(q) - rule foothold| of every leg that touches down at the new tick and, with land="actual", that foot's xy in place of
-    the rule's.  Returns what `rollout_phase_host` returns plus "legs" and the logs LEGS_LOGS."""
+    the rule's.  actuators [B,9]: per-robot actuator rows (actuators.py, include/mpcqp_actuators.h) in place of the inertia row's tau_max, or
+    None.  Returns what `rollout_phase_host` returns plus "legs" and the logs LEGS_LOGS."""
     return _rollout_legs_loop(oracle_engine, x, ref, feet, legs, gait, stand, gain, tick, mu, T, step_height, land, body, push, push_ticks,
-                              substeps, gains, leg_substeps, inertia, None, None)
+                              substeps, gains, leg_substeps, inertia, None, None, actuators)
 
 
 def rollout_drive_host(oracle_engine, x, ref, feet, legs, gait, stand, gain, tick, mu, T, step_height, land="rule", drive="limited",
                        ground=None, body=None, push=None, push_ticks=None, substeps=DEFAULT_SUBSTEPS, gains=None, leg_substeps=0,
-                       inertia=None):
+                       inertia=None, actuators=None):
     """Closed loop of mpcqp_rollout_drive on the CPU checker: `rollout_legs_host`'s loop with `lite3_model.stance_drive_host` between the
     solve and the legs step.  The legs step's torso acceleration, the plant and "forces" get the applied forces, "cmd" [B,T,12] the
     commanded ones; on stance rows "tau" is the rule's torque and "flag" gains its bits 2 / 16 / 32 (0xff for a poisoned leg); "drive_margin"
     [B,T,4] (host only) is the rule's margin.  The solver is not told: the next solve starts from what the last returned.  drive =
-    "limited" clamps at the inertia row's tau_max, "ideal" does not; ground [B] the ground's friction coefficient or None."""
+    "limited" clamps at the inertia row's tau_max -- with actuators [B,9] at each robot's envelope, at the stance rate with the foot at rest
+    (actuators.py) --, "ideal" does not; ground [B] the ground's friction coefficient or None."""
     if drive not in ("ideal", "limited"):
         raise ValueError(f"drive must be 'ideal' or 'limited', got {drive!r}")
     return _rollout_legs_loop(oracle_engine, x, ref, feet, legs, gait, stand, gain, tick, mu, T, step_height, land, body, push, push_ticks,
-                              substeps, gains, leg_substeps, inertia, drive, ground)
+                              substeps, gains, leg_substeps, inertia, drive, ground, actuators)
 
 
 def _rollout_legs_loop(oracle_engine, x, ref, feet, legs, gait, stand, gain, tick, mu, T, step_height, land, body, push, push_ticks, substeps,
-                       gains, leg_substeps, inertia, drive, ground):
+                       gains, leg_substeps, inertia, drive, ground, actuators=None):
     """The loop of `rollout_legs_host` (drive = None) and `rollout_drive_host`."""
     from . import lite3_model
     if push is not None and push_ticks is None:
@@ -348,7 +350,8 @@ def _rollout_legs_loop(oracle_engine, x, ref, feet, legs, gait, stand, gain, tic
         desired[:, t, 0:6] = ref[:, 0:6]; desired[:, t, 8] = ref[:, 9]; desired[:, t, 9:12] = ref[:, 6:9]
         forces[:, t] = o["u"][:, 0]
         if drive is not None:      # the applied forces take the place of the commanded ones from here on
-            dv = lite3_model.stance_drive_host(x, o["u"][:, 0], feet, e["contact"][:, 0], ground, drive, inertia)
+            akw = {} if actuators is None else {"actuators": actuators}
+            dv = lite3_model.stance_drive_host(x, o["u"][:, 0], feet, e["contact"][:, 0], ground, drive, inertia, **akw)
             out["cmd"][:, t], forces[:, t], out["drive_margin"][:, t] = o["u"][:, 0], dv["f"], dv["margin"]
         solved += ((o["status"] == 1) | (o["status"] == 2)).astype(np.int32)
         feet_log[:, t], contact_log[:, t] = feet, e["contact"][:, 0]
@@ -358,7 +361,8 @@ def _rollout_legs_loop(oracle_engine, x, ref, feet, legs, gait, stand, gain, tic
         sw = phase_swing_host(row(actual), row(desired), row(feet_log), gait, tick, stand, gain, step_height, delta)["swing"]
         acc = lite3_model.plant_base_acc_host(row(actual), row(forces), row(feet_log), bd, grav, None if wr is None else wr[:, None])
         trk = lite3_model.swing_track_host(row(actual), row(forces), row(feet_log), row(contact_log), sw, acc, gains=gains, state=legs,
-                                           substeps=leg_substeps, delta=delta, inertia=inertia)
+                                           substeps=leg_substeps, delta=delta, inertia=inertia,
+                                           **({} if actuators is None else {"actuators": actuators}))
         legs = trk["state"]
         out["swing"][:, t] = sw[:, 0]
         for k in ("q", "qd", "tau", "foot", "err", "flag", "margin"):

@@ -314,15 +314,16 @@ def plant_base_acc_host(actual, forces, feet, body=None, gravity=-9.81, wrench=N
     return np.where(ok[..., None], out, np.nan)
 
 
-def leg_effort_host(actual, forces, feet, foot_vel=None, foot_acc=None, base_acc=None, body=None, inertia=None):
+def leg_effort_host(actual, forces, feet, foot_vel=None, foot_acc=None, base_acc=None, body=None, inertia=None, actuators=None):
     """The full joint torques of a roll-out's log (the host counterpart of mpcqp_leg_effort, include/mpcqp_joints.h): the operands of
     `joint_rates_host` plus foot_acc [B,T,4,3] (None = 0), base_acc [B,T,6] world (alpha, a) of the torso / CoM (None =
     `plant_base_acc_host` with `body`) and inertia (a dict as `leg_inertia`) -> {"q", "qd", "tau_f", "reach"} of `joint_rates_host`
     and {"qdd", "tau_dyn", "tau" [B,T,4,3], "power" [B,T,4], "limit" uint8 [B,T,4]}.  qdd = J^-1 (R^T foot_acc - the foot point's
     acceleration in the recursion at qdd = 0) by the rates' adjugate and determinant; tau_dyn = the recursion at (q, qd, qdd);
     tau = tau_f + tau_dyn; power = tau_f . qd + tau_dyn . qd; limit bits 1: q, 2: qd, 4: tau beyond the row's limits, 8: out of
-    reach; a non-finite leg: NaN and 0xff."""
-    from . import plant
+    reach; a non-finite leg: NaN and 0xff.  actuators [B,9] (actuators.py) or None: bit 4 is then tau outside robot b's envelope at the
+    row's qd, and a robot with an invalid row gets limit = 0xff."""
+    from . import actuators as _act, plant
     inr = _inertia_arrays(inertia)
     q, qd, tau_f, power_f, reach = joint_rates_host(actual, forces, feet, foot_vel)
     actual, forces = np.asarray(actual, dtype=float), np.asarray(forces, dtype=float)
@@ -357,10 +358,16 @@ def leg_effort_host(actual, forces, feet, foot_vel=None, foot_acc=None, base_acc
         lim = np.where(reach != 0, 0, 8)
         lim = lim | np.where(((q < inr["q_min"]) | (q > inr["q_max"])).any(axis=-1), 1, 0)
         lim = lim | np.where((np.abs(qd) > inr["qd_max"]).any(axis=-1), 2, 0)
-        lim = lim | np.where((np.abs(tau) > inr["tau_max"]).any(axis=-1), 4, 0)
+        if actuators is None:
+            lim = lim | np.where((np.abs(tau) > inr["tau_max"]).any(axis=-1), 4, 0)
+            lim_ok = fin
+        else:
+            lo, hi = _act.limits_host(actuators, qd)
+            lim = lim | np.where(((tau > hi) | (tau < lo)).any(axis=-1), 4, 0)
+            lim_ok = fin & _act.valid_rows(actuators)[:, None, None]
     nan3 = lambda v: np.where(fin[..., None], v, np.nan)
     return {"q": q, "qd": qd, "tau_f": tau_f, "reach": reach, "qdd": nan3(qdd), "tau_dyn": nan3(tau_dyn), "tau": nan3(tau),
-            "power": np.where(fin, power, np.nan), "limit": np.where(fin, lim, 0xff).astype(np.uint8)}
+            "power": np.where(fin, power, np.nan), "limit": np.where(lim_ok, lim, 0xff).astype(np.uint8)}
 
 
 # ---- the swing leg as a controlled plant (the host counterparts of mpcqp_leg_accel / mpcqp_swing_track, include/mpcqp_joints.h) ----
@@ -440,7 +447,7 @@ def swing_gain_lambda(q, kd=SWING_KD, inertia=None):
 
 
 def swing_track_host(actual, forces, feet_log, contact_log, swing, base_acc=None, body=None, gains=None, state=None, substeps=0,
-                     delta=0.03, inertia=None):
+                     delta=0.03, inertia=None, actuators=None):
     """The swing legs of a roll-out as a controlled plant (the host counterpart of mpcqp_swing_track, include/mpcqp_joints.h, in the
     device's operation order): actual, forces [B,T,12], feet_log [B,T,4,3], contact_log [B,T,4] as `rollout_phase` logs them, swing
     [B,T,4,4,3] as `phase_swing` writes it, base_acc [B,T,6] or None (`plant_base_acc_host` at feet_log with `body`), gains [B,2] =
@@ -449,8 +456,11 @@ def swing_track_host(actual, forces, feet_log, contact_log, swing, base_acc=None
     logs `joint_rates_host`'s q, qd, tau and re-initialises the leg; a swing row logs the carried state, the applied torque of its
     first control period, and integrates the leg under computed torque plus Cartesian PD, clamped at tau_max, over the tick.
     "margin" [B,T,4] (host only) is the row's smallest distance |value - threshold| / max(1, |threshold|) to a joint, rate or torque
-    limit over its control periods, to det J = 0 and, where the leg is (re-)initialised, to the reach decision: where it is tiny a rounding difference may flip a flag bit."""
-    from . import plant
+    limit over its control periods, to det J = 0 and, where the leg is (re-)initialised, to the reach decision: where it is tiny a rounding difference may flip a flag bit.
+    actuators [B,9] (actuators.py, include/mpcqp_actuators.h) or None: each control period then clamps at robot b's envelope at the
+    rate the period starts from, not at tau_max, and the margin counts the envelope's comparisons (|qd| at qd_knee and qd_free, the
+    commanded torque at lo and hi); a robot with an invalid row logs NaN and 0xff on its swing rows."""
+    from . import actuators as _act, plant
     inr = _inertia_arrays(inertia)
     actual, forces, feet_log, swing = (np.asarray(a, dtype=float) for a in (actual, forces, feet_log, swing))
     contact = np.asarray(contact_log)
@@ -541,11 +551,14 @@ def swing_track_host(actual, forces, feet_log, contact_log, swing, base_acc=None
                     gF = _mtv(Rl, F)
                     tff = (M[..., 0] * qdes[..., 0:1] + M[..., 1] * qdes[..., 1:2]) + M[..., 2] * qdes[..., 2:3]
                     cmd = (np.stack([_dot3(J[..., j], gF) for j in range(3)], axis=-1) + tff) + bias
-                    app = np.minimum(np.maximum(cmd, -tmax), tmax)
+                    if actuators is None:
+                        app, mclamp = np.minimum(np.maximum(cmd, -tmax), tmax), rel(np.abs(cmd), tmax)
+                    else:
+                        app, mclamp = _act.clamp_host(actuators, cmd, dqd), _act.margin_host(actuators, cmd, dqd)
                     qdd, detm = _adj_solve(M, app - bias)
                     qdd = np.where((detm != 0.0)[..., None], qdd, 0.0)
                     dbits = dbits | limits(dq, dqd) | np.where((app != cmd).any(axis=-1), 2, 0) | np.where(detj == 0.0, 16, 0)
-                    marg = np.where(live, np.minimum(marg, np.minimum(np.minimum(margins(dq, dqd), rel(np.abs(cmd), tmax)), np.abs(detj))), marg)
+                    marg = np.where(live, np.minimum(marg, np.minimum(np.minimum(margins(dq, dqd), mclamp), np.abs(detj))), marg)
                     if k == 0:
                         tau_log = np.where(stance[..., None], tau_log, app)
                     dqd = dqd + h * qdd
@@ -575,7 +588,7 @@ def swing_track_host(actual, forces, feet_log, contact_log, swing, base_acc=None
 DRIVE_CLAMPED, DRIVE_QLIM, DRIVE_UNRESOLVED, DRIVE_GROUND = 2, 4, 16, 32
 
 
-def stance_drive_host(x, f, feet, contact, ground=None, drive="limited", inertia=None):
+def stance_drive_host(x, f, feet, contact, ground=None, drive="limited", inertia=None, actuators=None):
     """What the stance legs deliver of a commanded force (the host counterpart of mpcqp_stance_drive, include/mpcqp_sim.h, which has the
     rule; numpy in the device's order of operations): x [B,>=12] as stored, f [B,12] or [B,4,3] the commanded forces, feet [B,4,3] the
     held feet, contact [B,4], ground [B] the ground's friction coefficient or None (no friction limit; a foot still cannot pull),
@@ -587,8 +600,12 @@ def stance_drive_host(x, f, feet, contact, ground=None, drive="limited", inertia
     tau_max and, for a clamped leg, whose f1 is computed, f1_z at 0 and the tangential force at the cone -- where it is tiny a
     rounding difference may flip the decision}.
     tau_cmd = (R J)^T (-f) is `joint_log_host`'s; clamped legs get f1 = -R (J^-T tau_app) by `_adj_solve` on J^T.  The held foot does
-    not move: slip kinematics are not built."""
+    not move: slip kinematics are not built.
+    actuators [B,9] (actuators.py, include/mpcqp_actuators.h) or None: the clamp is then robot b's envelope at "rate" [B,4,3] (an extra
+    key of the result), `joint_rates_host`'s joint rate with the foot at rest in the world, and the margin counts the envelope's
+    comparisons; drive "ideal" does not read the table; a robot with an invalid row gets NaN and 0xff on its stance legs."""
     from scipy.spatial.transform import Rotation
+    from . import actuators as _act
     if drive not in ("limited", "ideal"):
         raise ValueError(f"drive must be 'ideal' or 'limited', got {drive!r}")
     inr = _inertia_arrays(inertia)
@@ -604,13 +621,21 @@ def stance_drive_host(x, f, feet, contact, ground=None, drive="limited", inertia
     xs = np.where(robot[:, None], x[:, :12], 0.0)
     fs, ps = np.where(leg[..., None], fr, 0.0), np.where(leg[..., None], feet, 0.0)
     mus = np.zeros(B) if mu is None else np.where(robot, mu, 0.0)
-    q, tc, reach = (a[:, 0] for a in joint_log_host(xs[:, None], fs.reshape(B, 1, 12), ps[:, None]))
+    if actuators is None:
+        q, tc, reach = (a[:, 0] for a in joint_log_host(xs[:, None], fs.reshape(B, 1, 12), ps[:, None]))
+    else:
+        q, rate, tc, _, reach = (a[:, 0] for a in joint_rates_host(xs[:, None], fs.reshape(B, 1, 12), ps[:, None]))
     R = Rotation.from_rotvec(xs[:, :3]).as_matrix()
     tmax = inr["tau_max"]
     with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
         z, p = _leg_chain(q)[1:]
         J = np.stack([np.cross(z[k], p[3] - p[k]) for k in range(3)], axis=-1)                  # [B,4,3,3], leg_fk_jac's
-        ta = np.minimum(np.maximum(tc, -tmax), tmax) if drive == "limited" else tc
+        if drive != "limited":
+            ta = tc
+        elif actuators is None:
+            ta = np.minimum(np.maximum(tc, -tmax), tmax)
+        else:
+            ta = _act.clamp_host(actuators, tc, rate)
         clamped = (ta != tc).any(axis=-1)
         g, det = _adj_solve(np.swapaxes(J, -1, -2), ta)                                       # J^-T tau_app
         Rl = R[:, None]
@@ -636,7 +661,7 @@ def stance_drive_host(x, f, feet, contact, ground=None, drive="limited", inertia
         # clamped leg's computed f1 can fall on the other side of them
         margin = np.full((B, 4), np.inf)
         if drive == "limited":
-            margin = rel(np.abs(tc), tmax).min(axis=-1)
+            margin = rel(np.abs(tc), tmax).min(axis=-1) if actuators is None else _act.margin_host(actuators, tc, rate)
         ground_margin = rel(f1[..., 2], 0.0)
         if mu is not None:
             ground_margin = np.minimum(ground_margin, np.where(pull, np.inf, rel(ft, cap)))
@@ -646,8 +671,11 @@ def stance_drive_host(x, f, feet, contact, ground=None, drive="limited", inertia
     out_f = np.where(good[..., None], np.where(st3, fo, fr), np.nan)
     out_t = np.where(good[..., None], np.where(st3, to, 0.0), np.nan)
     flag = np.where(good, np.where(stance, bits, 0), 0xff).astype(np.uint8)
-    return {"f": out_f.reshape(B, 12), "tau": out_t, "flag": flag, "tau_cmd": np.where((good & stance)[..., None], tc, np.nan), "q": q,
-            "reach": reach, "margin": np.where(good & stance, margin, np.inf)}
+    out = {"f": out_f.reshape(B, 12), "tau": out_t, "flag": flag, "tau_cmd": np.where((good & stance)[..., None], tc, np.nan), "q": q,
+           "reach": reach, "margin": np.where(good & stance, margin, np.inf)}
+    if actuators is not None:
+        out["rate"] = rate
+    return out
 
 
 def world_jacobians(R_body, q_all):

@@ -138,23 +138,26 @@ def _legs_models_host(loop, oracle_lib, cfg_overrides, models, x, ref, feet, leg
 
 
 def rollout_legs_models_host(oracle_lib, cfg_overrides, models, x, ref, feet, legs, gait, stand, gain, tick, mu, T, step_height, land="rule",
-                             body=None, push=None, push_ticks=None, substeps=DEFAULT_SUBSTEPS, gains=None, leg_substeps=0, inertia=None):
+                             body=None, push=None, push_ticks=None, substeps=DEFAULT_SUBSTEPS, gains=None, leg_substeps=0, inertia=None,
+                             actuators=None):
     """Host checker of mpcqp_rollout_legs with a model table: ``gaits.rollout_legs_host`` per group.  The legs step, like the plant,
-    uses `body` (None: the configuration's), never the row.  Returns what ``gaits.rollout_legs_host`` returns."""
+    uses `body` (None: the configuration's), never the row; actuators [B,9] (per robot) or None.  Returns what
+    ``gaits.rollout_legs_host`` returns."""
     from .gaits import rollout_legs_host
     return _legs_models_host(rollout_legs_host, oracle_lib, cfg_overrides, models, x, ref, feet, legs, gait, stand, gain, tick, mu, T, step_height,
-                             body, {"push": push, "push_ticks": push_ticks, "gains": gains},
+                             body, {"push": push, "push_ticks": push_ticks, "gains": gains, "actuators": actuators},
                              {"land": land, "substeps": substeps, "leg_substeps": leg_substeps, "inertia": inertia})
 
 
 def rollout_drive_models_host(oracle_lib, cfg_overrides, models, x, ref, feet, legs, gait, stand, gain, tick, mu, T, step_height, land="rule",
                               drive="limited", ground=None, body=None, push=None, push_ticks=None, substeps=DEFAULT_SUBSTEPS, gains=None,
-                              leg_substeps=0, inertia=None):
-    """Host checker of mpcqp_rollout_drive with a model table: ``gaits.rollout_drive_host`` per group (ground [B] is per robot).
+                              leg_substeps=0, inertia=None, actuators=None):
+    """Host checker of mpcqp_rollout_drive with a model table: ``gaits.rollout_drive_host`` per group (ground [B] and actuators [B,9] are
+    per robot).
     Returns what ``gaits.rollout_drive_host`` returns."""
     from .gaits import rollout_drive_host
     return _legs_models_host(rollout_drive_host, oracle_lib, cfg_overrides, models, x, ref, feet, legs, gait, stand, gain, tick, mu, T,
-                             step_height, body, {"push": push, "push_ticks": push_ticks, "gains": gains, "ground": ground},
+                             step_height, body, {"push": push, "push_ticks": push_ticks, "gains": gains, "ground": ground, "actuators": actuators},
                              {"land": land, "drive": drive, "substeps": substeps, "leg_substeps": leg_substeps, "inertia": inertia})
 
 
