@@ -33,6 +33,23 @@
  * legs under MPCQP_DRIVE_LIMITED get NaN applied forces and torques and flag 0xff -- in a roll-out the plant then carries the NaN
  * into x, and the robot's solves report MPCQP_STATUS_NONFINITE from the next tick on --, and mpcqp_leg_effort writes limit = 0xff.
  *
+ * The invalid row inside a roll-out, by entry point and landing (tests/test_gpu_actuator_rows.py holds each clause against the run with
+ * the row mended; "a leg log" is q_log, qd_log, tau_log, foot_log, err_log):
+ *   mpcqp_rollout_legs, and mpcqp_rollout_drive under MPCQP_DRIVE_IDEAL (with ground = NULL), MPCQP_LAND_RULE
+ *                          the legs feed nothing back: x, ref, feet, tick, the six logs of mpcqp_rollout_phase, swing_log and solved
+ *                          are the mended run's, bit for bit.  flag_log is 0xff and every leg log NaN on the robot's swing rows and
+ *                          on the stance row that follows a swing row of the same leg, the landing row, and on no other row; the
+ *                          other rows keep the mended run's values.  miss_log is NaN on its landings.
+ *   the same two, MPCQP_LAND_ACTUAL
+ *                          up to the first landing as above.  That landing writes a NaN foot into feet; the solve of the landing
+ *                          tick reports MPCQP_STATUS_NONFINITE, its row is 0xff / NaN on all four legs, and the plant carries the NaN
+ *                          into x: from the tick after it `actual` is non-finite and every row is 0xff / NaN.  solved counts the
+ *                          ticks before the first landing.
+ *   mpcqp_rollout_drive under MPCQP_DRIVE_LIMITED (the test runs it with MPCQP_LAND_ACTUAL)
+ *                          the stance rule poisons the first tick: every row, stance and swing, is 0xff / NaN from tick 0, cmd of
+ *                          tick 0 is finite, `actual` is non-finite from tick 1 and solved is 1.
+ * In every one of them every other robot's state and logs are the mended run's, bit for bit.
+ *
  * Which rate enters the envelope:
  *   swing control period   (mpcqp_swing_track; the legs step of mpcqp_rollout_legs / mpcqp_rollout_drive) the leg state's qd at the
  *                          start of that control period, the one the commanded torque was formed from
