@@ -50,6 +50,13 @@ __device__ __forceinline__ const double* act_row_here(const double* row) {
   return row;
 }
 
+// The table of a kernel whose last template argument is the pack ACTROW: nothing (no table: null), or double (one table [B,9], the
+// kernel's last parameter `const ACTROW* __restrict__... actp`).  A pack and not a bool plus a struct that holds the pointer: an
+// empty struct still takes 8 bytes of the kernel's argument block and moves the hidden arguments, and a pointer inside a struct
+// loses its no-alias marking, which schedules the table kernel differently.
+__device__ __forceinline__ const double* act_rows() { return nullptr; }
+__device__ __forceinline__ const double* act_rows(const double* act) { return act; }
+
 // mpcqp_set_actuators: one thread per row.  A row is valid when every tau_max is finite and >= 0, every qd_knee >= 0 and each joint
 // has either qd_knee = +inf (any qd_free) or finite qd_knee < qd_free < inf; an invalid row is stored as nine NaN.
 __global__ void __launch_bounds__(256)

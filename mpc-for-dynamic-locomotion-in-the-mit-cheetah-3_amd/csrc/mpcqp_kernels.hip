@@ -227,6 +227,8 @@ int actuators_match(mpcqp_engine* h, int64_t B, const char* who) {
   snprintf(h->err, sizeof(h->err), "%s: batch size %lld, but the actuator table has %lld rows", who, (long long)B, (long long)h->act_B);
   return MPCQP_EINVAL;
 }
+// The converted table, or null when none is set (launch_act)
+const double* act_table(const mpcqp_engine* h) { return h->act_B > 0 ? h->act_mem : nullptr; }
 
 // The event pair behind mpcqp_last_kernel_ms: an entry point records ev0 in front of its first launch and ev1 behind its last.
 int record(mpcqp_engine* h, hipEvent_t ev, hipStream_t st) {
@@ -794,6 +796,24 @@ int rollout_run(mpcqp_handle h, int64_t B, int32_t T, int32_t S, void* x, void* 
 int plant_substeps(int32_t substeps) {
   if (substeps < 0 || substeps > PLANT_MAX_SUBSTEPS) return -1;
   return substeps == 0 ? PLANT_DEFAULT_SUBSTEPS : substeps;
+}
+
+// leg_substeps / substeps of include/mpcqp_joints.h for a tick of `delta`: as given, or for 0 the default control period, the fewest
+// periods of at most SWING_H0 (the caller has checked the range [0, SWING_MAX_SUBSTEPS])
+int swing_substeps(double delta, int32_t substeps) {
+  if (substeps != 0) return substeps;
+  int n = (int)std::ceil(delta / SWING_H0);
+  while (n > 1 && delta / (n - 1) <= SWING_H0) --n;   // (delta / h0 a whole number up to rounding)
+  return n < 1 ? 1 : (n > SWING_MAX_SUBSTEPS ? SWING_MAX_SUBSTEPS : n);
+}
+
+// One launch of a kernel whose last template argument is the actuator pack (act_rows, mpcqp_actuators.h): `k` = K<TIO> on `args` without
+// a table (act null), `ka` = K<TIO, double> on (args..., act) with one.  A handle with a table runs the instantiations that read it;
+// without one, the kernels are what they were.
+template <typename... P, typename... A>
+void launch_act(const double* act, dim3 grid, dim3 block, hipStream_t st, void (*k)(P...), void (*ka)(P..., const double*), const A&... args) {
+  if (act) hipLaunchKernelGGL(ka, grid, block, 0, st, args..., act);
+  else hipLaunchKernelGGL(k, grid, block, 0, st, args...);
 }
 
 }  // namespace
@@ -1378,15 +1398,10 @@ int mpcqp_leg_effort(mpcqp_handle h, int64_t B, int32_t T, const void* actual, c
   const dim3 grid((unsigned)((4 * rows + 255) / 256));
   with_io(h, [&](auto tag) {
     using TIO = decltype(tag);
-    if (h->act_B > 0)   // (a handle with an actuator table runs the instantiations that read it; without one, the kernels are what they were)
-      hipLaunchKernelGGL((mpcqp_leg_effort_act_kernel<TIO>), grid, dim3(256), 0, (hipStream_t)stream, (const TIO*)actual, (const TIO*)forces,
-                         (const TIO*)feet, (const TIO*)foot_vel, (const TIO*)foot_acc, (const TIO*)base_acc, (const TIO*)body, plant_model(h),
-                         g, r.k0, r.k1, r.k2, r.lim, (TIO*)qdd, (TIO*)tau_dyn, (TIO*)tau, (TIO*)power, limit, rows, (int64_t)T,
-                         (const double*)h->act_mem);
-    else
-      hipLaunchKernelGGL((mpcqp_leg_effort_kernel<TIO>), grid, dim3(256), 0, (hipStream_t)stream, (const TIO*)actual, (const TIO*)forces,
-                         (const TIO*)feet, (const TIO*)foot_vel, (const TIO*)foot_acc, (const TIO*)base_acc, (const TIO*)body, plant_model(h),
-                         g, r.k0, r.k1, r.k2, r.lim, (TIO*)qdd, (TIO*)tau_dyn, (TIO*)tau, (TIO*)power, limit, rows, (int64_t)T);
+    launch_act(act_table(h), grid, dim3(256), (hipStream_t)stream, mpcqp_leg_effort_kernel<TIO>, mpcqp_leg_effort_kernel<TIO, double>,
+               (const TIO*)actual, (const TIO*)forces, (const TIO*)feet, (const TIO*)foot_vel, (const TIO*)foot_acc, (const TIO*)base_acc,
+               (const TIO*)body, plant_model(h), g, r.k0, r.k1, r.k2, r.lim, (TIO*)qdd, (TIO*)tau_dyn, (TIO*)tau, (TIO*)power, limit, rows,
+               (int64_t)T);
   });
   return launched(h, "leg effort kernel launch");
 }
@@ -1430,12 +1445,7 @@ int mpcqp_swing_track(mpcqp_handle h, int64_t B, int32_t T, const void* actual, 
   if (const int rc = leg_inertia_row(h, "mpcqp_swing_track", inr, r)) return rc;
   if (B == 0 || T == 0) return MPCQP_OK;
   if (const int rc = actuators_match(h, B, "mpcqp_swing_track")) return rc;
-  int n = substeps;
-  if (n == 0) {   // the default control period: the fewest periods of at most SWING_H0
-    n = (int)std::ceil(h->cfg.delta / SWING_H0);
-    while (n > 1 && h->cfg.delta / (n - 1) <= SWING_H0) --n;   // (delta / h0 a whole number up to rounding)
-    n = n < 1 ? 1 : (n > SWING_MAX_SUBSTEPS ? SWING_MAX_SUBSTEPS : n);
-  }
+  const int n = swing_substeps(h->cfg.delta, substeps);
   DeviceGuard guard(h->cfg.device);
   if (guard.err != hipSuccess) return fail(h, MPCQP_EHIP, "hipSetDevice", guard.err);
   const dim3 grid((unsigned)((4 * B + 255) / 256));
@@ -1444,12 +1454,8 @@ int mpcqp_swing_track(mpcqp_handle h, int64_t B, int32_t T, const void* actual, 
     const SwingIn<TIO> in = {(const TIO*)actual, (const TIO*)forces, (const TIO*)feet_log, contact_log, (const TIO*)swing,
                              (const TIO*)base_acc, (const TIO*)body, (const TIO*)gains};
     const SwingOut<TIO> out = {(TIO*)q, (TIO*)qd, (TIO*)tau, (TIO*)foot, (TIO*)err, flag};
-    if (h->act_B > 0)
-      hipLaunchKernelGGL((mpcqp_swing_track_act_kernel<TIO>), grid, dim3(256), 0, (hipStream_t)stream, in, (TIO*)state, plant_model(h), g, r.k0,
-                         r.k1, r.k2, r.lim, out, B, (int)T, n, h->cfg.delta / n, (const double*)h->act_mem);
-    else
-      hipLaunchKernelGGL((mpcqp_swing_track_kernel<TIO>), grid, dim3(256), 0, (hipStream_t)stream, in, (TIO*)state, plant_model(h), g, r.k0,
-                         r.k1, r.k2, r.lim, out, B, (int)T, n, h->cfg.delta / n);
+    launch_act(act_table(h), grid, dim3(256), (hipStream_t)stream, mpcqp_swing_track_kernel<TIO>, mpcqp_swing_track_kernel<TIO, double>, in,
+               (TIO*)state, plant_model(h), g, r.k0, r.k1, r.k2, r.lim, out, B, (int)T, n, h->cfg.delta / n);
   });
   return launched(h, "swing track kernel launch");
 }
@@ -1488,13 +1494,8 @@ int rollout_legs_run(mpcqp_handle h, const char* who, int64_t B, int32_t T, void
   if (B == 0 || T == 0) return MPCQP_OK;
   if (const int rc = models_match(h, B, who)) return rc;
   if (const int rc = actuators_match(h, B, who)) return rc;
-  const double* act = h->act_B > 0 ? h->act_mem : nullptr;   // (null: the kernels without a table, which are what they were)
-  int nl = leg_substeps;
-  if (nl == 0) {   // the default control period, as mpcqp_swing_track: the fewest periods of at most SWING_H0
-    nl = (int)std::ceil(h->cfg.delta / SWING_H0);
-    while (nl > 1 && h->cfg.delta / (nl - 1) <= SWING_H0) --nl;
-    nl = nl < 1 ? 1 : (nl > SWING_MAX_SUBSTEPS ? SWING_MAX_SUBSTEPS : nl);
-  }
+  const double* act = act_table(h);
+  const int nl = swing_substeps(h->cfg.delta, leg_substeps);
   DeviceGuard guard(h->cfg.device);
   if (guard.err != hipSuccess) return fail(h, MPCQP_EHIP, "hipSetDevice", guard.err);
   const RolloutPlantArgs plant = {body, push, push ? push_ticks : nullptr, n};
@@ -1521,21 +1522,13 @@ int rollout_legs_run(mpcqp_handle h, const char* who, int64_t B, int32_t T, void
       const DriveWs<TIO> dw = drive_ws<TIO>(h->roll_mem, B, N);
       if (dr) {
         TIO* cmd = dr->cmd_log ? (TIO*)dr->cmd_log + (size_t)it * 12 : nullptr;
-        if (act)
-          hipLaunchKernelGGL((mpcqp_stance_drive_act_kernel<TIO>), gl, nt, 0, st, xs, o.u, (int64_t)N * 12, (const TIO*)feet,
-                             (const uint8_t*)nullptr, gait, tick, (const TIO*)dr->ground, g, r.lim, (int)dr->drive, dw.f, dw.tau, dw.flag, cmd,
-                             (int64_t)T * 12, B, act);
-        else
-          hipLaunchKernelGGL((mpcqp_stance_drive_kernel<TIO>), gl, nt, 0, st, xs, o.u, (int64_t)N * 12, (const TIO*)feet, (const uint8_t*)nullptr,
-                             gait, tick, (const TIO*)dr->ground, g, r.lim, (int)dr->drive, dw.f, dw.tau, dw.flag, cmd, (int64_t)T * 12, B);
+        launch_act(act, gl, nt, st, mpcqp_stance_drive_kernel<TIO>, mpcqp_stance_drive_kernel<TIO, double>, xs, o.u, (int64_t)N * 12,
+                   (const TIO*)feet, (const uint8_t*)nullptr, gait, tick, (const TIO*)dr->ground, g, r.lim, (int)dr->drive, dw.f, dw.tau, dw.flag,
+                   cmd, (int64_t)T * 12, B);
         u = dw.f; Nu = 1;
       }
-      if (act)
-        hipLaunchKernelGGL((mpcqp_legs_step_act_kernel<TIO>), gl, nt, 0, st, xs, rf, ph, tick, u, (const TIO*)step_height, (const TIO*)gains,
-                           legs, plant_in<TIO>(h, plant), g, r.k0, r.k1, r.k2, r.lim, out, d, Nu, B, (int)T, it, nl, d / nl, act);
-      else
-        hipLaunchKernelGGL((mpcqp_legs_step_kernel<TIO>), gl, nt, 0, st, xs, rf, ph, tick, u, (const TIO*)step_height, (const TIO*)gains, legs,
-                           plant_in<TIO>(h, plant), g, r.k0, r.k1, r.k2, r.lim, out, d, Nu, B, (int)T, it, nl, d / nl);
+      launch_act(act, gl, nt, st, mpcqp_legs_step_kernel<TIO>, mpcqp_legs_step_kernel<TIO, double>, xs, rf, ph, tick, u, (const TIO*)step_height,
+                 (const TIO*)gains, legs, plant_in<TIO>(h, plant), g, r.k0, r.k1, r.k2, r.lim, out, d, Nu, B, (int)T, it, nl, d / nl);
       if (dr && (tau_log || flag_log))
         hipLaunchKernelGGL((mpcqp_drive_log_kernel<TIO>), gl, nt, 0, st, gait, tick, dw.tau, dw.flag,
                            (int)(dr->drive == MPCQP_DRIVE_IDEAL && !dr->ground), B, (int)T, it, (TIO*)tau_log, flag_log);
@@ -1589,14 +1582,9 @@ int mpcqp_stance_drive(mpcqp_handle h, int64_t B, const void* x, const void* f, 
   const dim3 grid((unsigned)((4 * B + 255) / 256));
   with_io(h, [&](auto tag) {
     using TIO = decltype(tag);
-    if (h->act_B > 0)
-      hipLaunchKernelGGL((mpcqp_stance_drive_act_kernel<TIO>), grid, dim3(256), 0, (hipStream_t)stream, (const TIO*)x, (const TIO*)f, (int64_t)12,
-                         (const TIO*)feet, contact, (const int32_t*)nullptr, (const int32_t*)nullptr, (const TIO*)ground, g, r.lim,
-                         (int)DRIVE_LIMITED, (TIO*)f_out, (TIO*)tau, flag, (TIO*)nullptr, (int64_t)0, B, (const double*)h->act_mem);
-    else
-      hipLaunchKernelGGL((mpcqp_stance_drive_kernel<TIO>), grid, dim3(256), 0, (hipStream_t)stream, (const TIO*)x, (const TIO*)f, (int64_t)12,
-                         (const TIO*)feet, contact, (const int32_t*)nullptr, (const int32_t*)nullptr, (const TIO*)ground, g, r.lim,
-                         (int)DRIVE_LIMITED, (TIO*)f_out, (TIO*)tau, flag, (TIO*)nullptr, (int64_t)0, B);
+    launch_act(act_table(h), grid, dim3(256), (hipStream_t)stream, mpcqp_stance_drive_kernel<TIO>, mpcqp_stance_drive_kernel<TIO, double>,
+               (const TIO*)x, (const TIO*)f, (int64_t)12, (const TIO*)feet, contact, (const int32_t*)nullptr, (const int32_t*)nullptr,
+               (const TIO*)ground, g, r.lim, (int)DRIVE_LIMITED, (TIO*)f_out, (TIO*)tau, flag, (TIO*)nullptr, (int64_t)0, B);
   });
   return launched(h, "stance drive kernel launch");
 }
