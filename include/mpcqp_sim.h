@@ -254,8 +254,9 @@ int mpcqp_rollout_score(mpcqp_handle h, int64_t B, int32_t T, const void* actual
  *      J^T solved by cofactors and determinant in the order the rates solve J.  Clamped but out of reach or singular: f1 = f, bit 16.
  *   4. the ground.  f1_z <= 0: f2 = 0, the foot cannot pull.  Otherwise, with a friction row mu_g, if sqrt(f1_x^2 + f1_y^2) > mu_g f1_z the
  *      tangential part is scaled by mu_g f1_z / sqrt(f1_x^2 + f1_y^2): onto the circular Coulomb cone, direction kept.  Otherwise f2 = f1.
- *      Bit 32 is set exactly when f2 != f1.  THE FOOT DOES NOT MOVE: slip kinematics are not built.  f2 is the force a sliding foot
- *      transmits, but the held foot stays where it is until the leg lifts off.
+ *      Bit 32 is set exactly when f2 != f1.  THE FOOT DOES NOT MOVE under this rule: f2 is the force a sliding foot transmits, but the
+ *      held foot stays where it is until the leg lifts off.  Feet that slide are include/mpcqp_slip.h: mpcqp_stance_slip and
+ *      mpcqp_rollout_slip put slip kinematics behind steps 1 to 3.
  *   5. f_out = f2; tau = tau_app where bit 32 is clear, else (R J)^T (-f2); flag bits 2 clamped, 4 q outside [q_min, q_max], 16 the leg
  *      cannot be resolved, 32 the ground limited the force.
  *   6. a swing leg (contact == 0): f_out = f bit for bit, tau = 0, flag 0.
@@ -295,7 +296,7 @@ int mpcqp_stance_drive(mpcqp_handle h, int64_t B, const void* x, const void* f, 
  * report MPCQP_STATUS_NONFINITE from the next tick with a stance leg on, and no other robot changes.
  * A tau_max per robot and a torque-speed curve are include/mpcqp_actuators.h: while mpcqp_set_actuators has set a table, step 2 clamps at
  * robot b's envelope at the joint rates with the foot at rest in the world, and the tau_max of `inr` is not read.
- * Not built: slip kinematics, per-robot joint limits, a variant on plan tables.
+ * Not built: per-robot joint limits, a variant on plan tables.  (Slip kinematics: include/mpcqp_slip.h.)
  */
 #define MPCQP_DRIVE_IDEAL 0
 #define MPCQP_DRIVE_LIMITED 1

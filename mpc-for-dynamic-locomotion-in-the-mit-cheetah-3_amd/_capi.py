@@ -1,5 +1,5 @@
 """ctypes binding of the C-ABI declared in include/mpcqp.h and its product-only extensions include/mpcqp_plan.h, mpcqp_sim.h, mpcqp_model.h,
-mpcqp_joints.h and mpcqp_actuators.h.
+mpcqp_joints.h, mpcqp_actuators.h and mpcqp_slip.h.
 
 The product path loads ``csrc/libmpcqp.so`` (hand-written HIP for gfx950) and nothing else: if that library is
 missing or cannot be loaded, importing the engine raises -- there is no CPU fallback.  The binding itself is
@@ -171,6 +171,15 @@ ACTUATORS_ABI = {
     ),
 }
 ACTUATOR_SYMBOLS = tuple(row[0] for row in ACTUATORS_ABI[ACTUATORS_HEADER])
+# include/mpcqp_slip.h came after it, again in a table of its own: `has_slip`.
+SLIP_HEADER = "mpcqp_slip.h"
+SLIP_ABI = {
+    SLIP_HEADER: (  # stance feet that slide
+        ("mpcqp_stance_slip", c_int, (_P, _I64) + (_P,) * 7 + (_I32, _GEO, _INR) + (_P,) * 6),
+        ("mpcqp_rollout_slip", c_int, (_P, _I64, _I32) + (_P,) * 12 + (_I32, _P, _P, _I32, _GEO, _INR, _I32, _I32, _P, _P, _P) + (_P,) * 18),
+    ),
+}
+SLIP_SYMBOLS = tuple(row[0] for row in SLIP_ABI[SLIP_HEADER])
 # The swing-leg plant of include/mpcqp_joints.h came after the rest of that header: a product library built before it still has the
 # header's other calls (`has_joints`) and is told apart by `has_legsim`.
 LEGSIM_SYMBOLS = ("mpcqp_leg_accel", "mpcqp_swing_track")
@@ -187,11 +196,12 @@ LAND_RULE, LAND_ACTUAL = 0, 1   # include/mpcqp_sim.h, MPCQP_LAND_*
 DRIVE_IDEAL, DRIVE_LIMITED = 0, 1   # include/mpcqp_sim.h, MPCQP_DRIVE_*
 # The flag bits the stance drive writes (include/mpcqp_sim.h): clamped, q outside its limits, not resolvable, limited by the ground.
 DRIVE_CLAMPED, DRIVE_QLIM, DRIVE_UNRESOLVED, DRIVE_GROUND, DRIVE_POISONED = 2, 4, 16, 32, 0xff
+DRIVE_SLIDING = 128   # include/mpcqp_slip.h, MPCQP_DRIVE_SLIDING: the stance foot slides
 
 
 class Library:
-    """A loaded shared object exporting the mpcqp C-ABI.  `has_plan`, `has_sim`, `has_model`, `has_joints` and `has_actuators` say whether
-    it exports all of include/mpcqp_plan.h, mpcqp_sim.h, mpcqp_model.h, mpcqp_joints.h and mpcqp_actuators.h (of mpcqp_joints.h: all but LEGSIM_SYMBOLS, which `has_legsim`
+    """A loaded shared object exporting the mpcqp C-ABI.  `has_plan`, `has_sim`, `has_model`, `has_joints`, `has_actuators` and `has_slip` say
+    whether it exports all of include/mpcqp_plan.h, mpcqp_sim.h, mpcqp_model.h, mpcqp_joints.h, mpcqp_actuators.h and mpcqp_slip.h (of mpcqp_joints.h: all but LEGSIM_SYMBOLS, which `has_legsim`
     answers for; of mpcqp_sim.h: all but LEGROLL_SYMBOLS, SCORE_SYMBOLS and DRIVE_SYMBOLS, `has_legroll`, `has_score` and `has_drive`).  An
     extension header's calls are bound only when the library
     has them all; `partial=True` binds whichever it has (an older build of the product library, in a comparison tool)."""
@@ -206,7 +216,7 @@ class Library:
         self.has_legroll = all(hasattr(self.lib, name) for name in LEGROLL_SYMBOLS)
         self.has_score = all(hasattr(self.lib, name) for name in SCORE_SYMBOLS)
         self.has_drive = all(hasattr(self.lib, name) for name in DRIVE_SYMBOLS)
-        for header, rows in {**ABI, **ACTUATORS_ABI}.items():
+        for header, rows in {**ABI, **ACTUATORS_ABI, **SLIP_ABI}.items():
             have = header == CORE_HEADER or all(hasattr(self.lib, row[0]) for row in rows if row[0] not in _GATED)
             if header != CORE_HEADER:
                 setattr(self, "has_" + header[len("mpcqp_"):-len(".h")], have)
@@ -379,6 +389,21 @@ class Engine:
         self._call("mpcqp_rollout_drive", B, T, x, ref, feet, legs, gait, stand, gain, tick, mu, body, push, push_ticks, substeps, step_height,
                    gains, leg_substeps, geometry, inertia, land, drive, ground, actual, desired, forces, feet_log, contact_log, solved,
                    swing_log, q_log, qd_log, tau_log, foot_log, err_log, flag_log, miss_log, cmd_log, stream)
+
+    def stance_slip_ptr(self, B, x, f, feet, contact, ground, foot_mass, slip_in, f_out, tau=0, flag=0, slip_out=0, disp=0, substeps=0,
+                        geometry=None, inertia=None, stream=0):
+        """The stance drive with slip kinematics on the caller's rows (include/mpcqp_slip.h, mpcqp_stance_slip)."""
+        self._call("mpcqp_stance_slip", B, x, f, feet, contact, ground, foot_mass, slip_in, substeps, geometry, inertia, f_out, tau, flag,
+                   slip_out, disp, stream)
+
+    def rollout_slip_ptr(self, B, T, x, ref, feet, legs, gait, stand, gain, tick, mu, body, push, push_ticks, substeps, step_height, gains,
+                         leg_substeps, land, drive, ground, foot_mass, slip, actual, desired, forces, feet_log, contact_log, solved, swing_log,
+                         q_log, qd_log, tau_log, foot_log, err_log, flag_log, miss_log, cmd_log, slip_log, disp_log, geometry=None,
+                         inertia=None, stream=0):
+        """`rollout_drive_ptr` with stance feet that slide (include/mpcqp_slip.h, mpcqp_rollout_slip)."""
+        self._call("mpcqp_rollout_slip", B, T, x, ref, feet, legs, gait, stand, gain, tick, mu, body, push, push_ticks, substeps, step_height,
+                   gains, leg_substeps, geometry, inertia, land, drive, ground, foot_mass, slip, actual, desired, forces, feet_log, contact_log,
+                   solved, swing_log, q_log, qd_log, tau_log, foot_log, err_log, flag_log, miss_log, cmd_log, slip_log, disp_log, stream)
 
     def phase_swing_ptr(self, B, T, actual, desired, feet_log, gait, tick0, stand, gain, step_height, swing, feet_des=0, stream=0):
         """The swing-foot trajectories of a roll-out on a gait clock, from its logs (include/mpcqp_plan.h, mpcqp_phase_swing)."""

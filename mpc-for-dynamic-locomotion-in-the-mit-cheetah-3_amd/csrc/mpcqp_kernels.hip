@@ -3,7 +3,7 @@
 // Replaces, for a batch of B independent robots, the solve the reference performs once per control tick:
 // CasADi Opti('conic') -> OSQP on the QP of src/mpc.py:58-173, filled at src/mpc.py:242-255, solved at :258.
 //
-// This translation unit is the C-ABI of include/mpcqp.h, mpcqp_plan.h, mpcqp_sim.h, mpcqp_model.h, mpcqp_joints.h and mpcqp_actuators.h: the handle, its host helpers (I/O-type
+// This translation unit is the C-ABI of include/mpcqp.h, mpcqp_plan.h, mpcqp_sim.h, mpcqp_model.h, mpcqp_joints.h, mpcqp_actuators.h and mpcqp_slip.h: the handle, its host helpers (I/O-type
 // dispatch, workspaces, the policy behind the configuration's defaults) and the extern "C" entry points.  The device code is in
 //   mpcqp_wrench.h       the engine: wrench-space (Woodbury) form, H = 2 alpha I + T'KT with a 6N x 6N system, one QP per wave
 //                        (horizon 10) or per four waves (horizon 20), fp32 or fp64 ADMM, fp64 active-set polish, ADMM-only mode
@@ -19,6 +19,7 @@
 //   mpcqp_model.h        per-robot model rows: the conversion of the caller's table into the engine's
 //   mpcqp_joints.h       closed-form leg inverse kinematics and the joint-space log of a roll-out
 //   mpcqp_actuators.h    per-robot actuator rows: the conversion of the caller's table and the torque-speed envelope the leg kernels share
+//   mpcqp_slip.h         stance feet that slide: the stance drive's rule with slip kinematics, and the foot move of its roll-out
 // DESIGN.md has the derivations.
 
 #include "mpcqp_wrench.h"
@@ -31,6 +32,7 @@
 #include "mpcqp_legsim.h"
 #include "mpcqp_legroll.h"
 #include "mpcqp_drive.h"
+#include "mpcqp_slip.h"
 #include "mpcqp_score.h"
 
 #include <cstdio>
@@ -64,7 +66,8 @@ struct mpcqp_engine {
                                  // followed by the lane records [NT][16 values | 8 row words] of w_kq_rows_load (mpcqp_rowtab.h)
   double* wr_klane64 = nullptr;
   void* roll_mem = nullptr;   // roll-out: u [B,N,12], X [B,N+1,13], status / iters [B] of the current tick, then the stance drive's
-                              // side buffers: applied forces [B,12], torques [B,4,3], flags u8 [B,4] (mpcqp_rollout_drive)
+                              // side buffers: applied forces [B,12], torques [B,4,3], flags u8 [B,4] (mpcqp_rollout_drive), then the
+                              // slip rule's: displacements [B,4,2] (mpcqp_rollout_slip)
   int64_t roll_cap = 0;
   void* gait_mem = nullptr;   // gait entry point: the expanded operator tuple [r | xdes | contact] of the current batch
   int64_t gait_cap = 0;
@@ -310,6 +313,15 @@ DriveWs<T> drive_ws(void* base, int64_t B, size_t N) {   // (status and iters ar
 }
 constexpr size_t drive_tail(size_t el) { return 24 * el + 4; }   // bytes per robot of DriveWs
 
+// The displacement side buffer of mpcqp_rollout_slip, [B,4,2] in the I/O type behind DriveWs (the flags end on a multiple of 4 bytes:
+// the buffer starts at the next multiple of 8, which the reserve's 8 spare bytes pay for).
+template <typename T>
+T* slip_ws(void* base, int64_t B, size_t N) {
+  const uintptr_t end = (uintptr_t)(drive_ws<T>(base, B, N).flag + (size_t)B * 4);
+  return (T*)((end + 7) & ~(uintptr_t)7);
+}
+constexpr size_t slip_tail(size_t el) { return 8 * el; }   // bytes per robot of the displacement buffer
+
 // Tuple workspace of the gait entry point and the roll-out, grown like the rest of the batch-dependent workspace.
 int reserve_gait(mpcqp_engine* e, int64_t B) {
   if (B <= e->gait_cap) return MPCQP_OK;
@@ -322,7 +334,7 @@ int reserve_gait(mpcqp_engine* e, int64_t B) {
 // Result workspace of the roll-out.  Zeros = "no guess" for a warm-started engine.
 int reserve_roll(mpcqp_engine* e, int64_t B) {
   if (B <= e->roll_cap) return MPCQP_OK;
-  const size_t bytes = ws_bytes(B, (size_t)e->cfg.N, io_size(e), 2 * sizeof(int32_t) + drive_tail(io_size(e)));
+  const size_t bytes = ws_bytes(B, (size_t)e->cfg.N, io_size(e), 2 * sizeof(int32_t) + drive_tail(io_size(e)) + slip_tail(io_size(e))) + 8;
   if (!grow(e->roll_mem, bytes, bytes)) return MPCQP_ENOMEM;
   e->roll_cap = B;
   return MPCQP_OK;
@@ -1465,14 +1477,17 @@ namespace {
 
 // What mpcqp_rollout_drive adds to mpcqp_rollout_legs: the drive mode, the ground's friction [B] or null, the commanded-force log or null.
 struct RolloutDriveArgs { int32_t drive; const void* ground; void* cmd_log; };
+// What mpcqp_rollout_slip adds to mpcqp_rollout_drive: the feet's effective mass [B], the slip state [B,4,2], its two logs or null.
+struct RolloutSlipArgs { const void* foot_mass; double* slip; double* slip_log; void* disp_log; };
 
-// mpcqp_rollout_legs (dr = null) and mpcqp_rollout_drive: one argument check, one loop.
+// mpcqp_rollout_legs (dr = null), mpcqp_rollout_drive and mpcqp_rollout_slip (sl, with dr): one argument check, one loop.
 int rollout_legs_run(mpcqp_handle h, const char* who, int64_t B, int32_t T, void* x, void* ref, void* feet, double* legs, const int32_t* gait,
                      const void* stand, const void* gain, int32_t* tick, const void* mu, const void* body, const void* push,
                      const int32_t* push_ticks, int32_t substeps, const void* step_height, const void* gains, int32_t leg_substeps,
                      const MpcQpLegGeometry* geo, const MpcQpLegInertia* inr, int32_t land, void* actual, void* desired, void* forces,
                      void* feet_log, uint8_t* contact_log, int32_t* solved, void* swing_log, void* q_log, void* qd_log, void* tau_log,
-                     void* foot_log, void* err_log, uint8_t* flag_log, void* miss_log, void* stream, const RolloutDriveArgs* dr) {
+                     void* foot_log, void* err_log, uint8_t* flag_log, void* miss_log, void* stream, const RolloutDriveArgs* dr,
+                     const RolloutSlipArgs* sl = nullptr) {
   if (!h) return MPCQP_EINVAL;
   const auto bad = [&](const char* what) {
     char msg[160];
@@ -1487,6 +1502,7 @@ int rollout_legs_run(mpcqp_handle h, const char* who, int64_t B, int32_t T, void
   if (dr && dr->drive != MPCQP_DRIVE_IDEAL && dr->drive != MPCQP_DRIVE_LIMITED) return bad("drive is neither MPCQP_DRIVE_IDEAL nor MPCQP_DRIVE_LIMITED");
   if (push && !push_ticks) return bad("push without push_ticks");
   if (B > 0 && (!x || !ref || !feet || !legs || !gait || !stand || !tick || !mu || !step_height)) return bad("null buffer");
+  if (B > 0 && sl && (!dr->ground || !sl->foot_mass || !sl->slip)) return bad("null buffer");
   LegGeoDev g;
   if (const int rc = leg_ik_geometry(h, who, geo, g)) return rc;
   LegInrDev r;
@@ -1507,6 +1523,7 @@ int rollout_legs_run(mpcqp_handle h, const char* who, int64_t B, int32_t T, void
   // With a drive, the rule runs between the solve and the legs step and leaves the applied forces in a [B,12] side buffer, which the legs
   // step and the advance read as a force buffer of horizon 1 (the solve's own buffer, its next warm start, is not altered); after the legs
   // step the rule's torques and bits go into the stance rows of tau_log / flag_log: 6 launches, 7 with one of those two logs.
+  // With the slip rule in the drive's place the log step waits until after the landing and moves the feet in the same launch: 7.
   return rollout_loop(h, who, B, T, x, ref, mu, stream,
     [&](auto tag, auto* xs, auto* rf, const auto& w) {
       using TIO = decltype(tag);
@@ -1520,7 +1537,16 @@ int rollout_legs_run(mpcqp_handle h, const char* who, int64_t B, int32_t T, void
       const TIO* u = o.u;   // the forces the legs and the plant see, robot b's at u + b Nu 12
       int Nu = N;
       const DriveWs<TIO> dw = drive_ws<TIO>(h->roll_mem, B, N);
-      if (dr) {
+      TIO* const rdisp = sl ? slip_ws<TIO>(h->roll_mem, B, N) : nullptr;
+      if (sl) {
+        TIO* cmd = dr->cmd_log ? (TIO*)dr->cmd_log + (size_t)it * 12 : nullptr;
+        double* slog = sl->slip_log ? sl->slip_log + (size_t)it * 8 : nullptr;
+        launch_act(act, gl, nt, st, mpcqp_stance_slip_kernel<TIO>, mpcqp_stance_slip_kernel<TIO, double>, xs, o.u, (int64_t)N * 12,
+                   (const TIO*)feet, (const uint8_t*)nullptr, gait, tick, (const TIO*)dr->ground, (const TIO*)sl->foot_mass,
+                   (const double*)sl->slip, g, r.lim, (int)dr->drive, n, d / n, d, dw.f, dw.tau, dw.flag, cmd, (int64_t)T * 12, sl->slip, rdisp,
+                   slog, (int64_t)T * 8, B);
+        u = dw.f; Nu = 1;
+      } else if (dr) {
         TIO* cmd = dr->cmd_log ? (TIO*)dr->cmd_log + (size_t)it * 12 : nullptr;
         launch_act(act, gl, nt, st, mpcqp_stance_drive_kernel<TIO>, mpcqp_stance_drive_kernel<TIO, double>, xs, o.u, (int64_t)N * 12,
                    (const TIO*)feet, (const uint8_t*)nullptr, gait, tick, (const TIO*)dr->ground, g, r.lim, (int)dr->drive, dw.f, dw.tau, dw.flag,
@@ -1529,13 +1555,16 @@ int rollout_legs_run(mpcqp_handle h, const char* who, int64_t B, int32_t T, void
       }
       launch_act(act, gl, nt, st, mpcqp_legs_step_kernel<TIO>, mpcqp_legs_step_kernel<TIO, double>, xs, rf, ph, tick, u, (const TIO*)step_height,
                  (const TIO*)gains, legs, plant_in<TIO>(h, plant), g, r.k0, r.k1, r.k2, r.lim, out, d, Nu, B, (int)T, it, nl, d / nl);
-      if (dr && (tau_log || flag_log))
+      if (dr && !sl && (tau_log || flag_log))
         hipLaunchKernelGGL((mpcqp_drive_log_kernel<TIO>), gl, nt, 0, st, gait, tick, dw.tau, dw.flag,
                            (int)(dr->drive == MPCQP_DRIVE_IDEAL && !dr->ground), B, (int)T, it, (TIO*)tau_log, flag_log);
       hipLaunchKernelGGL((mpcqp_phase_advance_kernel<TIO>), ga, nt, 0, st, xs, rf, (TIO*)feet, ph, tick, plant_in<TIO>(h, plant), u, o.status, d, Nu, B,
                          (int)T, it, (TIO*)actual, (TIO*)desired, (TIO*)forces, (TIO*)feet_log, contact_log, solved);
       hipLaunchKernelGGL((mpcqp_legs_land_kernel<TIO>), gl, nt, 0, st, xs, (TIO*)feet, gait, tick, legs, g, (int)land, B, (int)T, it,
                          (TIO*)miss_log);
+      if (sl)
+        hipLaunchKernelGGL((mpcqp_slip_finish_kernel<TIO>), gl, nt, 0, st, gait, tick, (const TIO*)dw.tau, (const uint8_t*)dw.flag,
+                           (const TIO*)rdisp, B, (int)T, it, (TIO*)feet, sl->slip, (TIO*)tau_log, flag_log, (TIO*)sl->disp_log);
     });
 }
 
@@ -1587,6 +1616,49 @@ int mpcqp_stance_drive(mpcqp_handle h, int64_t B, const void* x, const void* f, 
                (const TIO*)ground, g, r.lim, (int)DRIVE_LIMITED, (TIO*)f_out, (TIO*)tau, flag, (TIO*)nullptr, (int64_t)0, B);
   });
   return launched(h, "stance drive kernel launch");
+}
+
+int mpcqp_rollout_slip(mpcqp_handle h, int64_t B, int32_t T, void* x, void* ref, void* feet, double* legs, const int32_t* gait,
+                       const void* stand, const void* gain, int32_t* tick, const void* mu, const void* body, const void* push,
+                       const int32_t* push_ticks, int32_t substeps, const void* step_height, const void* gains, int32_t leg_substeps,
+                       const MpcQpLegGeometry* geo, const MpcQpLegInertia* inr, int32_t land, int32_t drive, const void* ground,
+                       const void* foot_mass, double* slip, void* actual, void* desired, void* forces, void* feet_log, uint8_t* contact_log,
+                       int32_t* solved, void* swing_log, void* q_log, void* qd_log, void* tau_log, void* foot_log, void* err_log,
+                       uint8_t* flag_log, void* miss_log, void* cmd_log, double* slip_log, void* disp_log, void* stream) {
+  const RolloutDriveArgs dr = {drive, ground, cmd_log};
+  const RolloutSlipArgs sl = {foot_mass, slip, slip_log, disp_log};
+  return rollout_legs_run(h, "mpcqp_rollout_slip", B, T, x, ref, feet, legs, gait, stand, gain, tick, mu, body, push, push_ticks, substeps,
+                          step_height, gains, leg_substeps, geo, inr, land, actual, desired, forces, feet_log, contact_log, solved, swing_log,
+                          q_log, qd_log, tau_log, foot_log, err_log, flag_log, miss_log, stream, &dr, &sl);
+}
+
+int mpcqp_stance_slip(mpcqp_handle h, int64_t B, const void* x, const void* f, const void* feet, const uint8_t* contact, const void* ground,
+                      const void* foot_mass, const double* slip_in, int32_t substeps, const MpcQpLegGeometry* geo, const MpcQpLegInertia* inr,
+                      void* f_out, void* tau, uint8_t* flag, double* slip_out, void* disp, void* stream) {
+  if (!h) return MPCQP_EINVAL;
+  if (B < 0 || B > 0x1fffffff) return fail(h, MPCQP_EINVAL, "mpcqp_stance_slip: batch size out of range");
+  const int n = plant_substeps(substeps);
+  if (n < 0) return fail(h, MPCQP_EINVAL, "mpcqp_stance_slip: substeps out of range [0, 1000]");
+  if (B > 0 && (!x || !f || !feet || !contact || !ground || !foot_mass || !slip_in || !f_out))
+    return fail(h, MPCQP_EINVAL, "mpcqp_stance_slip: null buffer");
+  LegGeoDev g;
+  if (const int rc = leg_ik_geometry(h, "mpcqp_stance_slip", geo, g)) return rc;
+  LegInrDev r;
+  if (const int rc = leg_inertia_row(h, "mpcqp_stance_slip", inr, r)) return rc;
+  if (B == 0) return MPCQP_OK;
+  if (const int rc = actuators_match(h, B, "mpcqp_stance_slip")) return rc;
+  DeviceGuard guard(h->cfg.device);
+  if (guard.err != hipSuccess) return fail(h, MPCQP_EHIP, "hipSetDevice", guard.err);
+  const dim3 grid((unsigned)((4 * B + 255) / 256));
+  const double d = h->cfg.delta;
+  with_io(h, [&](auto tag) {
+    using TIO = decltype(tag);
+    launch_act(act_table(h), grid, dim3(256), (hipStream_t)stream, mpcqp_stance_slip_kernel<TIO>, mpcqp_stance_slip_kernel<TIO, double>,
+               (const TIO*)x, (const TIO*)f, (int64_t)12, (const TIO*)feet, contact, (const int32_t*)nullptr, (const int32_t*)nullptr,
+               (const TIO*)ground, (const TIO*)foot_mass, slip_in, g, r.lim, (int)DRIVE_LIMITED, n, d / n, d, (TIO*)f_out, (TIO*)tau, flag,
+               (TIO*)nullptr, (int64_t)0, slip_out, (TIO*)disp, (double*)nullptr, (int64_t)0, B);
+  });
+  return launched(h, "stance slip kernel launch");
 }
 
 int mpcqp_rollout_score(mpcqp_handle h, int64_t B, int32_t T, const void* actual, const void* desired, const void* forces,

@@ -564,7 +564,7 @@ class MPCBatch:
         `leg_effort`: the row's tau_max, q_min and q_max are read -> {"f": [B,12] the applied forces, "tau": [B,4,3] the applied joint
         torques (0 on a swing leg), "flag": uint8 [B,4]: 2 torque clamped, 4 joint angle outside its limits, 16 clamped but not
         resolvable (out of reach or singular: the force is kept), 32 the ground limited the force, 0xff a non-finite leg}; "tau" /
-        "flag" are None when not in `want`.  The held foot does not move: no slip kinematics.  Asynchronous on `stream`."""
+        "flag" are None when not in `want`.  The held foot does not move (`stance_slip` lets it slide).  Asynchronous on `stream`."""
         torch = _torch()
         B = int(x.shape[0])
         if x.dim() == 2 and x.shape[1] == 12:
@@ -617,6 +617,74 @@ class MPCBatch:
                                       drive if isinstance(drive, int) else modes[drive], _ptr(ground),
                                       *[p(k) for k in names[:5]], solved.data_ptr(), *[p(k) for k in self.LEGS_LOGS], p("cmd"),
                                       geometry, self._inertia(inertia), st.cuda_stream)
+        out["solved"] = solved
+        return out
+
+    def stance_slip(self, x, f, feet, contact, ground, foot_mass, slip, substeps=10, inertia=None, geometry=None, want=("tau", "flag"),
+                    stream=None):
+        """`stance_drive` with stance feet that slide (include/mpcqp_slip.h, mpcqp_stance_slip, which has the rule; the host counterpart
+        is lite3_model.stance_slip_host): x, f, feet, contact as for `stance_drive`; ground [B] the ground's friction coefficient and
+        foot_mass [B] the effective mass of a sliding foot (lite3_model.foot_mass()), both required; slip float64 [B,4,2] the world xy
+        velocity of each held foot at the start of the tick (not altered); `substeps` the plant's substeps of the tick (0 means 10) ->
+        {"f": [B,12] the applied forces, "tau": [B,4,3], "flag": uint8 [B,4], `stance_drive`'s bits and 128 = the foot slides, "slip":
+        float64 [B,4,2] the velocities at the end of the tick (0 on a swing leg), "disp": [B,4,2] how far each foot slid}; "tau" /
+        "flag" are None when not in `want`.  Asynchronous on `stream`."""
+        torch = _torch()
+        B = int(x.shape[0])
+        if x.dim() == 2 and x.shape[1] == 12:
+            with torch.cuda.stream(stream):
+                x = torch.cat([x, torch.zeros((B, 1), dtype=x.dtype, device=x.device)], dim=1).contiguous()
+        check_operands(self.device, (("x", x, (B, 13), self.tdtype), ("f", f, (B, 12), self.tdtype), ("feet", feet, (B, 4, 3), self.tdtype),
+                                     ("contact", contact, (B, 4), torch.uint8), ("ground", ground, (B,), self.tdtype),
+                                     ("foot_mass", foot_mass, (B,), self.tdtype), ("slip", slip, (B, 4, 2), torch.float64)))
+        st = self._stream(stream)
+        out, tau, flag, slip_out, disp = self._alloc(stream, ((B, 12), self.tdtype), ((B, 4, 3), self.tdtype) if "tau" in want else None,
+                                                     ((B, 4), torch.uint8) if "flag" in want else None, ((B, 4, 2), torch.float64),
+                                                     ((B, 4, 2), self.tdtype))
+        self.engine.stance_slip_ptr(B, x.data_ptr(), f.data_ptr(), feet.data_ptr(), contact.data_ptr(), ground.data_ptr(), foot_mass.data_ptr(),
+                                    slip.data_ptr(), out.data_ptr(), _ptr(tau), _ptr(flag), slip_out.data_ptr(), disp.data_ptr(), int(substeps),
+                                    geometry, self._inertia(inertia), st.cuda_stream)
+        return {"f": out, "tau": tau, "flag": flag, "slip": slip_out, "disp": disp}
+
+    def rollout_slip(self, x, ref, feet, legs, gait, stand, gain, tick, mu, T, step_height, ground, foot_mass, slip, land="rule",
+                     drive="limited", body=None, push=None, push_ticks=None, substeps=10, gains=None, leg_substeps=0, inertia=None,
+                     geometry=None, log=True, stream=None):
+        """`rollout_drive` with stance feet that slide (include/mpcqp_slip.h, mpcqp_rollout_slip; the host counterpart is
+        gaits.rollout_slip_host): the rule of `stance_slip` takes the place of `stance_drive`'s, and after each tick every foot that
+        stays in stance is moved by how far it slid.  ground [B] and foot_mass [B] are required; slip float64 [B,4,2], the feet's
+        velocities, is state next to `x`, `ref`, `feet`, `legs` and `tick`, all advanced IN PLACE (zeros: every foot at rest).  Returns
+        `rollout_drive`'s dict plus "slip_log" float64 [B,T,4,2], the velocities at the start of each row, and "disp" [B,T,4,2], what
+        was added to the feet after the row; "flag" has bit 128 on the rows of a sliding leg.  On a ground that never limits (1e3) it is
+        `rollout_drive` on that ground, bit for bit.  Every other argument as in `rollout_drive`.  Asynchronous on `stream`."""
+        torch = _torch()
+        B, T = int(x.shape[0]), int(T)
+        if land not in ("rule", "actual"):
+            raise ValueError(f"land must be 'rule' or 'actual', got {land!r}")
+        modes = {"ideal": _capi.DRIVE_IDEAL, "limited": _capi.DRIVE_LIMITED}
+        if not isinstance(drive, int) and drive not in modes:
+            raise ValueError(f"drive must be 'ideal' or 'limited', got {drive!r}")
+        check_operands(self.device, self._phase_rows(B, x, ref, feet, gait, tick, stand, gain, "x") + (
+            ("legs", legs, (B, 4, 7), torch.float64), ("mu", mu, (B,), self.tdtype), ("body", body, (B, 7), self.tdtype),
+            ("push", push, (B, 6), self.tdtype), ("push_ticks", push_ticks, (B, 2), torch.int32),
+            ("step_height", step_height, (B,), self.tdtype), ("gains", gains, (B, 2), self.tdtype), ("ground", ground, (B,), self.tdtype),
+            ("foot_mass", foot_mass, (B,), self.tdtype), ("slip", slip, (B, 4, 2), torch.float64)),
+            optional=("gain", "body", "push", "push_ticks", "gains"))
+        st = self._stream(stream)
+        rows, leg3 = ((B, T, 12), self.tdtype), ((B, T, 4, 3), self.tdtype)
+        leg1, mask = ((B, T, 4), self.tdtype), ((B, T, 4), torch.uint8)
+        spec = (rows, rows, rows, leg3, mask) + (((B, T, 4, 4, 3), self.tdtype), leg3, leg3, leg3, leg3, leg1, mask, leg1) + (
+            rows, ((B, T, 4, 2), torch.float64), ((B, T, 4, 2), self.tdtype))
+        names = ("actual", "desired", "forces", "feet_log", "contact_log") + self.LEGS_LOGS + ("cmd", "slip_log", "disp")
+        out = dict(zip(names, self._alloc(stream, *[s if log else None for s in spec])))
+        solved, = self._alloc(stream, ((B,), torch.int32, not T > 0))
+        p = lambda k: _ptr(out[k])
+        self.engine.rollout_slip_ptr(B, T, x.data_ptr(), ref.data_ptr(), feet.data_ptr(), legs.data_ptr(), gait.data_ptr(), stand.data_ptr(),
+                                     _ptr(gain), tick.data_ptr(), mu.data_ptr(), _ptr(body), _ptr(push), _ptr(push_ticks), substeps,
+                                     step_height.data_ptr(), _ptr(gains), int(leg_substeps),
+                                     _capi.LAND_ACTUAL if land == "actual" else _capi.LAND_RULE,
+                                     drive if isinstance(drive, int) else modes[drive], ground.data_ptr(), foot_mass.data_ptr(), slip.data_ptr(),
+                                     *[p(k) for k in names[:5]], solved.data_ptr(), *[p(k) for k in self.LEGS_LOGS], p("cmd"), p("slip_log"),
+                                     p("disp"), geometry, self._inertia(inertia), st.cuda_stream)
         out["solved"] = solved
         return out
 

@@ -322,9 +322,29 @@ def rollout_drive_host(oracle_engine, x, ref, feet, legs, gait, stand, gain, tic
                               substeps, gains, leg_substeps, inertia, drive, ground, actuators)
 
 
+def rollout_slip_host(oracle_engine, x, ref, feet, legs, gait, stand, gain, tick, mu, T, step_height, ground, foot_mass, slip=None,
+                      land="rule", drive="limited", body=None, push=None, push_ticks=None, substeps=DEFAULT_SUBSTEPS, gains=None,
+                      leg_substeps=0, inertia=None, actuators=None):
+    """Closed loop of mpcqp_rollout_slip (include/mpcqp_slip.h) on the CPU checker: `rollout_drive_host`'s loop with
+    `lite3_model.stance_slip_host` in the place of `stance_drive_host` and, after the landing, the foot move: every leg that was in
+    stance on the row's tick and does not touch down on the new one has its foot's xy moved by how far it slid; a leg that touches
+    down is at rest.  ground [B] and foot_mass [B] (or a number) are required; slip [B,4,2] the feet's velocities (None: at rest).
+    Returns `rollout_drive_host`'s dict -- "flag" with bit 128 on the rows of a sliding leg -- plus "slip" [B,4,2], "slip_log"
+    [B,T,4,2] the velocities at the start of each row and "disp" [B,T,4,2] what was added to the feet after the row."""
+    if drive not in ("ideal", "limited"):
+        raise ValueError(f"drive must be 'ideal' or 'limited', got {drive!r}")
+    if ground is None or foot_mass is None:
+        raise ValueError("rollout_slip_host needs ground and foot_mass")
+    B = np.asarray(x).shape[0]
+    state = {"foot_mass": np.broadcast_to(_f64(foot_mass), (B,)).copy(),
+             "slip": np.zeros((B, 4, 2)) if slip is None else _f64(slip).reshape(B, 4, 2).copy()}
+    return _rollout_legs_loop(oracle_engine, x, ref, feet, legs, gait, stand, gain, tick, mu, T, step_height, land, body, push, push_ticks,
+                              substeps, gains, leg_substeps, inertia, drive, ground, actuators, state)
+
+
 def _rollout_legs_loop(oracle_engine, x, ref, feet, legs, gait, stand, gain, tick, mu, T, step_height, land, body, push, push_ticks, substeps,
-                       gains, leg_substeps, inertia, drive, ground, actuators=None):
-    """The loop of `rollout_legs_host` (drive = None) and `rollout_drive_host`."""
+                       gains, leg_substeps, inertia, drive, ground, actuators=None, slide=None):
+    """The loop of `rollout_legs_host` (drive = None), `rollout_drive_host` and `rollout_slip_host` (slide = its foot_mass and slip)."""
     from . import lite3_model
     if push is not None and push_ticks is None:
         raise ValueError("push needs push_ticks")
@@ -343,6 +363,8 @@ def _rollout_legs_loop(oracle_engine, x, ref, feet, legs, gait, stand, gain, tic
            "margin": np.full((B, T, 4), np.inf), **{k: np.zeros((B, T, 4, 3)) for k in ("q", "qd", "tau", "foot")}}
     if drive is not None:
         out["cmd"], out["drive_margin"] = np.zeros((B, T, 12)), np.full((B, T, 4), np.inf)
+    if slide is not None:
+        out["slip_log"], out["disp"] = np.zeros((B, T, 4, 2)), np.zeros((B, T, 4, 2))
     for t in range(T):
         e = phase_expand_host(x, ref, feet, gait, tick, stand, gain, N, delta)
         o = oracle_engine.solve_batch_host(x, e["r"], e["contact"], e["xdes"], mu, want_X=False)
@@ -351,7 +373,12 @@ def _rollout_legs_loop(oracle_engine, x, ref, feet, legs, gait, stand, gain, tic
         forces[:, t] = o["u"][:, 0]
         if drive is not None:      # the applied forces take the place of the commanded ones from here on
             akw = {} if actuators is None else {"actuators": actuators}
-            dv = lite3_model.stance_drive_host(x, o["u"][:, 0], feet, e["contact"][:, 0], ground, drive, inertia, **akw)
+            if slide is None:
+                dv = lite3_model.stance_drive_host(x, o["u"][:, 0], feet, e["contact"][:, 0], ground, drive, inertia, **akw)
+            else:
+                out["slip_log"][:, t] = slide["slip"]
+                dv = lite3_model.stance_slip_host(x, o["u"][:, 0], feet, e["contact"][:, 0], ground, slide["foot_mass"], slide["slip"], drive,
+                                                  inertia, delta=delta, substeps=substeps, **akw)
             out["cmd"][:, t], forces[:, t], out["drive_margin"][:, t] = o["u"][:, 0], dv["f"], dv["margin"]
         solved += ((o["status"] == 1) | (o["status"] == 2)).astype(np.int32)
         feet_log[:, t], contact_log[:, t] = feet, e["contact"][:, 0]
@@ -370,7 +397,7 @@ def _rollout_legs_loop(oracle_engine, x, ref, feet, legs, gait, stand, gain, tic
         if drive is not None:      # stance rows the legs step did not poison: the rule's torque and bits
             m = (contact_log[:, t] != 0) & (out["flag"][:, t] != 0xff)
             out["tau"][:, t] = np.where(m[..., None], dv["tau"], out["tau"][:, t])
-            out["flag"][:, t] = np.where(m, np.where(dv["flag"] == 0xff, 0xff, out["flag"][:, t] | (dv["flag"] & 50)), out["flag"][:, t])
+            out["flag"][:, t] = np.where(m, np.where(dv["flag"] == 0xff, 0xff, out["flag"][:, t] | (dv["flag"] & (50 if slide is None else 178))), out["flag"][:, t])
         x = srb_step(x, forces[:, t], feet, e["contact"][:, 0], bd, wr, delta, substeps)
         ref[:, 3:6] = ref[:, 3:6] + ref[:, 6:9] * delta
         ref[:, 2] = ref[:, 2] + ref[:, 9] * delta
@@ -386,8 +413,15 @@ def _rollout_legs_loop(oracle_engine, x, ref, feet, legs, gait, stand, gain, tic
             if land == "actual":
                 p[:, :, 0:2] = pa[:, :, 0:2]
             feet = np.where(td[:, :, None], p, feet)
+        if slide is not None:      # the foot move: a leg that stays down, or lifts off, carries its slide; a landing foot is at rest
+            move = (contact_log[:, t] != 0) & ~td
+            out["disp"][:, t] = np.where(move[..., None], dv["disp"], 0.0)
+            with np.errstate(invalid="ignore"):
+                feet[:, :, 0:2] = np.where(move[..., None], feet[:, :, 0:2] + dv["disp"], feet[:, :, 0:2])
+            slide["slip"] = np.where(td[..., None], 0.0, dv["slip"])
     return {"x": x, "ref": ref, "tick": tick, "feet": feet, "legs": legs, "actual": actual, "desired": desired, "forces": forces,
-            "solved": solved, "feet_log": feet_log, "contact_log": contact_log, **out}
+            "solved": solved, "feet_log": feet_log, "contact_log": contact_log, **out,
+            **({} if slide is None else {"slip": slide["slip"]})}
 
 
 def make_phase_batch(B, names=("trot", "bound"), period=12, seed=20251018, mus=(0.5, 0.7, 1.0), v_ref=(0.18, 0.0, 0.0), theta_dot=0.0,

@@ -600,7 +600,7 @@ def stance_drive_host(x, f, feet, contact, ground=None, drive="limited", inertia
     tau_max and, for a clamped leg, whose f1 is computed, f1_z at 0 and the tangential force at the cone -- where it is tiny a
     rounding difference may flip the decision}.
     tau_cmd = (R J)^T (-f) is `joint_log_host`'s; clamped legs get f1 = -R (J^-T tau_app) by `_adj_solve` on J^T.  The held foot does
-    not move: slip kinematics are not built.
+    not move (`stance_slip_host` lets it slide).
     actuators [B,9] (actuators.py, include/mpcqp_actuators.h) or None: the clamp is then robot b's envelope at "rate" [B,4,3] (an extra
     key of the result), `joint_rates_host`'s joint rate with the foot at rest in the world, and the margin counts the envelope's
     comparisons; drive "ideal" does not read the table; a robot with an invalid row gets NaN and 0xff on its stance legs."""
@@ -673,6 +673,132 @@ def stance_drive_host(x, f, feet, contact, ground=None, drive="limited", inertia
     flag = np.where(good, np.where(stance, bits, 0), 0xff).astype(np.uint8)
     out = {"f": out_f.reshape(B, 12), "tau": out_t, "flag": flag, "tau_cmd": np.where((good & stance)[..., None], tc, np.nan), "q": q,
            "reach": reach, "margin": np.where(good & stance, margin, np.inf)}
+    if actuators is not None:
+        out["rate"] = rate
+    return out
+
+
+# ---- stance feet that slide (the host counterpart of mpcqp_stance_slip, include/mpcqp_slip.h) ----------------------------------------
+DRIVE_SLIDING = 128
+
+
+def foot_mass(inertia=None):
+    """The effective mass m_e [kg] a sliding foot presents (include/mpcqp_slip.h): 1 / mean eig((J M^-1 J^T)_xy) over the four legs at
+    the nominal stance (synth.NOMINAL_FEET seen from the CoM, torso level), M the leg's joint-space mass matrix of `leg_dynamics_host`
+    with the row `inertia` (None: the Lite3's, about 0.258 kg)."""
+    from .synth import NOMINAL_FEET
+    q, reach = leg_ik_closed(NOMINAL_FEET[None])
+    assert reach.all()
+    M = leg_dynamics_host(q, inertia=inertia)[1][0]
+    eig = []
+    for l in range(4):
+        J = leg_fk_jac(l, q[0, l])[1]
+        eig.extend(np.linalg.eigvalsh((J @ np.linalg.solve(M[l], J.T))[:2, :2]))
+    return float(1.0 / np.mean(eig))
+
+
+def stance_slip_host(x, f, feet, contact, ground, foot_mass, slip, drive="limited", inertia=None, actuators=None, delta=0.03, substeps=10):
+    """`stance_drive_host` with stance feet that slide (the host counterpart of mpcqp_stance_slip, include/mpcqp_slip.h, which has the
+    rule; numpy in the device's order of operations): x, f, feet, contact, drive, inertia, actuators as for `stance_drive_host`; ground
+    [B] the ground's friction coefficient and foot_mass [B] (or a number) the feet's effective mass, both required; slip [B,4,2] the
+    world xy velocity of each held foot at the start of the tick; delta the tick and `substeps` the plant's substeps (0 means 10) ->
+    `stance_drive_host`'s dict with flag bit 128 = the foot slides, plus "slip" [B,4,2] the velocities at the end of the tick (0 on a
+    swing leg) and "disp" [B,4,2] how far each foot slid.  With actuators the envelope's rate is that of a foot moving at `slip`.
+    "margin" [B,4] (host only) also covers, for every leg, the |s*| versus cap decision of each substep, and the ground's decisions
+    no longer (the rule has no cone scaling; f1_z at 0 stays, for a clamped leg)."""
+    from scipy.spatial.transform import Rotation
+    from . import actuators as _act
+    if drive not in ("limited", "ideal"):
+        raise ValueError(f"drive must be 'ideal' or 'limited', got {drive!r}")
+    n = 10 if int(substeps) == 0 else int(substeps)
+    if not 1 <= n <= 1000:
+        raise ValueError(f"substeps must be in [0, 1000], got {substeps}")
+    inr = _inertia_arrays(inertia)
+    x, feet = np.asarray(x, dtype=float), np.asarray(feet, dtype=float)
+    B = x.shape[0]
+    fr = np.asarray(f, dtype=float).reshape(B, 4, 3)
+    stance = np.asarray(contact).reshape(B, 4) != 0
+    mu = np.asarray(ground, dtype=float).reshape(B)
+    me = np.broadcast_to(np.asarray(foot_mass, dtype=float), (B,)).copy()
+    s0 = np.asarray(slip, dtype=float).reshape(B, 4, 2)
+    with np.errstate(invalid="ignore"):
+        robot = np.isfinite(x[:, :12]).all(axis=1) & np.isfinite(mu) & (mu >= 0.0) & np.isfinite(me) & (me > 0.0)
+    leg = np.isfinite(fr).all(axis=-1) & np.isfinite(feet).all(axis=-1) & np.isfinite(s0).all(axis=-1)
+    # a poisoned row computes on clean stand-ins and is selected away at the end
+    xs = np.where(robot[:, None], x[:, :12], 0.0)
+    fs, ps, ss = np.where(leg[..., None], fr, 0.0), np.where(leg[..., None], feet, 0.0), np.where(leg[..., None], s0, 0.0)
+    mus, mes = np.where(robot, mu, 0.0)[:, None], np.where(robot, me, 1.0)[:, None]
+    if actuators is None:
+        q, tc, reach = (a[:, 0] for a in joint_log_host(xs[:, None], fs.reshape(B, 1, 12), ps[:, None]))
+    else:
+        fv = np.concatenate([ss, np.zeros((B, 4, 1))], axis=-1)
+        q, rate, tc, _, reach = (a[:, 0] for a in joint_rates_host(xs[:, None], fs.reshape(B, 1, 12), ps[:, None], fv[:, None]))
+    R = Rotation.from_rotvec(xs[:, :3]).as_matrix()
+    tmax = inr["tau_max"]
+    h = float(delta) / n
+    with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+        z, p = _leg_chain(q)[1:]
+        J = np.stack([np.cross(z[k], p[3] - p[k]) for k in range(3)], axis=-1)                  # [B,4,3,3], leg_fk_jac's
+        if drive != "limited":
+            ta = tc
+        elif actuators is None:
+            ta = np.minimum(np.maximum(tc, -tmax), tmax)
+        else:
+            ta = _act.clamp_host(actuators, tc, rate)
+        clamped = (ta != tc).any(axis=-1)
+        g, det = _adj_solve(np.swapaxes(J, -1, -2), ta)                                       # J^-T tau_app
+        Rl = R[:, None]
+        fc = -np.stack([(Rl[..., a, 0] * g[..., 0] + Rl[..., a, 1] * g[..., 1]) + Rl[..., a, 2] * g[..., 2] for a in range(3)], axis=-1)
+        solve = (reach != 0) & (det != 0.0)
+        f1 = np.where((clamped & solve)[..., None], fc, fs)
+        # the slide
+        rel = lambda val, thr: np.abs(val - thr) / np.maximum(1.0, np.abs(thr))
+        pull = f1[..., 2] <= 0.0
+        fn = np.where(pull, 0.0, f1[..., 2])
+        hm = h / mes
+        cap = (mus * fn) * hm
+        vx, vy = -f1[..., 0] * hm, -f1[..., 1] * hm
+        sx, sy = ss[..., 0].copy(), ss[..., 1].copy()
+        dx, dy = np.zeros((B, 4)), np.zeros((B, 4))
+        slide_margin = np.full((B, 4), np.inf)
+        for _ in range(n):
+            tx, ty = sx + vx, sy + vy
+            nrm = np.sqrt(tx * tx + ty * ty)
+            stick = nrm <= cap
+            # (cap = 0 -- a pull, or ice -- is an exact zero on both sides: |s*| <= 0 is then decided by exact zeros too)
+            slide_margin = np.minimum(slide_margin, np.where(cap == 0.0, np.inf, rel(nrm, cap)))
+            keep = 1.0 - cap / nrm
+            sx, sy = np.where(stick, 0.0, tx * keep), np.where(stick, 0.0, ty * keep)
+            dx, dy = dx + h * sx, dy + h * sy
+        sliding = (ss[..., 0] != 0.0) | (ss[..., 1] != 0.0) | (sx != 0.0) | (sy != 0.0)
+        med = mes / float(delta)
+        f2 = np.stack([np.where(sliding, f1[..., 0] + med * (sx - ss[..., 0]), f1[..., 0]),
+                       np.where(sliding, f1[..., 1] + med * (sy - ss[..., 1]), f1[..., 1]), f1[..., 2]], axis=-1)
+        f2 = np.where(pull[..., None], 0.0, f2)
+        limited = (f2 != f1).any(axis=-1)
+        fo = np.where(limited[..., None], f2, f1)
+        hh = -np.stack([(Rl[..., 0, a] * f2[..., 0] + Rl[..., 1, a] * f2[..., 1]) + Rl[..., 2, a] * f2[..., 2] for a in range(3)], axis=-1)
+        tg = np.stack([(J[..., 0, j] * hh[..., 0] + J[..., 1, j] * hh[..., 1]) + J[..., 2, j] * hh[..., 2] for j in range(3)], axis=-1)
+        to = np.where(limited[..., None], tg, ta)
+        bits = (np.where(clamped, DRIVE_CLAMPED, 0) | np.where(clamped & ~solve, DRIVE_UNRESOLVED, 0) | np.where(limited, DRIVE_GROUND, 0)
+                | np.where(sliding, DRIVE_SLIDING, 0) | np.where(((q < inr["q_min"]) | (q > inr["q_max"])).any(axis=-1), DRIVE_QLIM, 0))
+        margin = np.full((B, 4), np.inf)
+        if drive == "limited":
+            margin = rel(np.abs(tc), tmax).min(axis=-1) if actuators is None else _act.margin_host(actuators, tc, rate)
+        # an unclamped leg's f1 is f as read: its pull decision is exact.  The stick decisions compare computed values on every leg.
+        margin = np.where(clamped & solve, np.minimum(margin, rel(f1[..., 2], 0.0)), margin)
+        margin = np.minimum(margin, slide_margin)
+        own = (leg & np.isfinite(fo).all(axis=-1) & np.isfinite(to).all(axis=-1) & np.isfinite(sx) & np.isfinite(sy) & np.isfinite(dx)
+               & np.isfinite(dy))
+        good = robot[:, None] & (~stance | own)
+    st3 = stance[..., None]
+    out_f = np.where(good[..., None], np.where(st3, fo, fr), np.nan)
+    out_t = np.where(good[..., None], np.where(st3, to, 0.0), np.nan)
+    flag = np.where(good, np.where(stance, bits, 0), 0xff).astype(np.uint8)
+    out_s = np.where(good[..., None], np.where(st3, np.stack([sx, sy], axis=-1), 0.0), np.nan)
+    out_d = np.where(good[..., None], np.where(st3, np.stack([dx, dy], axis=-1), 0.0), np.nan)
+    out = {"f": out_f.reshape(B, 12), "tau": out_t, "flag": flag, "slip": out_s, "disp": out_d,
+           "tau_cmd": np.where((good & stance)[..., None], tc, np.nan), "q": q, "reach": reach, "margin": np.where(good & stance, margin, np.inf)}
     if actuators is not None:
         out["rate"] = rate
     return out
