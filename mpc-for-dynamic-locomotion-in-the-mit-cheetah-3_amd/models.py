@@ -4,7 +4,7 @@ A model row is ``(m, Ixx, Iyy, Izz, f_min, f_max)`` -- the mass, the principal i
 robot's MPC, fp64.  ``MPCBatch.set_models`` hands a table of them to the device engine.  The CPU checker under ``oracle/`` has one
 model per handle, so the checkers here group the batch by identical row and solve each group with a handle of its own, created
 with that row's ``m``, ``Ibody_inv = 1 / I``, ``f_min`` and ``f_max`` (``grouped_host``): one checker per entry point that reads
-the table -- the solves, ``rollout``, ``rollout_plant``, ``rollout_phase``, ``rollout_legs`` and ``rollout_drive``.  The row is the
+the table -- the solves, ``rollout``, ``rollout_plant``, ``rollout_phase``, ``rollout_legs``, ``rollout_drive`` and ``rollout_slip``.  The row is the
 MPC's model only: the plant and the legs step of a roll-out use `body`, and with ``body=None`` the CONFIGURATION's model, whatever
 the table says.  ``replay_rows`` turns a roll-out's logs back into the QPs it solved, one per (robot, tick).
 """
@@ -158,6 +158,24 @@ def rollout_drive_models_host(oracle_lib, cfg_overrides, models, x, ref, feet, l
     from .gaits import rollout_drive_host
     return _legs_models_host(rollout_drive_host, oracle_lib, cfg_overrides, models, x, ref, feet, legs, gait, stand, gain, tick, mu, T,
                              step_height, body, {"push": push, "push_ticks": push_ticks, "gains": gains, "ground": ground, "actuators": actuators},
+                             {"land": land, "drive": drive, "substeps": substeps, "leg_substeps": leg_substeps, "inertia": inertia})
+
+
+def rollout_slip_models_host(oracle_lib, cfg_overrides, models, x, ref, feet, legs, gait, stand, gain, tick, mu, T, step_height, ground,
+                             foot_mass, slip=None, land="rule", drive="limited", body=None, push=None, push_ticks=None,
+                             substeps=DEFAULT_SUBSTEPS, gains=None, leg_substeps=0, inertia=None, actuators=None):
+    """Host checker of mpcqp_rollout_slip with a model table: ``gaits.rollout_slip_host`` per group (ground [B], foot_mass [B] or a
+    number, slip [B,4,2] or None and actuators [B,9] are per robot).
+    Returns what ``gaits.rollout_slip_host`` returns."""
+    from .gaits import rollout_slip_host
+    if ground is None or foot_mass is None:
+        raise ValueError("rollout_slip_models_host needs ground and foot_mass")
+    B = np.asarray(x).shape[0]
+    foot_mass = np.broadcast_to(np.asarray(foot_mass, np.float64), (B,))
+    slip = None if slip is None else np.asarray(slip, np.float64).reshape(B, 4, 2)
+    return _legs_models_host(rollout_slip_host, oracle_lib, cfg_overrides, models, x, ref, feet, legs, gait, stand, gain, tick, mu, T,
+                             step_height, body, {"push": push, "push_ticks": push_ticks, "gains": gains, "ground": ground,
+                                                 "foot_mass": foot_mass, "slip": slip, "actuators": actuators},
                              {"land": land, "drive": drive, "substeps": substeps, "leg_substeps": leg_substeps, "inertia": inertia})
 
 
