@@ -11,7 +11,9 @@
 // One kernel for both entry points is what makes the roll-out's logs replay bit for bit through mpcqp_stance_slip.
 //
 // Layout and conventions are mpcqp_drive.h's: one thread per (robot, leg), fp64, no LDS, geometry and limits by value, the rule's own
-// arithmetic without contraction, masks as selects.  q, tau_cmd, J and the 3x3 solve are the drive's, from the same device functions.
+// arithmetic without contraction, masks as selects.  The rule is mpcqp_drive.h's device functions -- stance mask, steps 2, 3 and 5,
+// common stores, log step --; this file has what a sliding foot adds: step 4 (slip_slide), the slip kernel's own operands, poison
+// test and stores, and the foot move.  The row (R, pw, q, tau_cmd, J) is the drive kernel's lines, in both kernels (see there).
 // Not built: a reach stop, static versus kinetic friction, anisotropic foot inertia, a landing foot's residual velocity, the legs'
 // reaction on the torso; the stance rows of the q / qd logs still assume the held foot at rest (include/mpcqp_slip.h).
 #pragma once
@@ -23,30 +25,9 @@ namespace {
 constexpr unsigned SLIP_SLIDING = 128u;                   // MPCQP_DRIVE_SLIDING (include/mpcqp_slip.h)
 constexpr unsigned SLIP_BITS = DRIVE_BITS | SLIP_SLIDING;   // what the rule adds to a stance row's flag
 
-// Steps 2 and 3 of drive_rule (mpcqp_drive.h), operation for operation: the applied torque ta, the force f1 it delivers, the bits 2 / 16.
-template <bool ACT>
-__device__ __forceinline__ unsigned slip_drive_force(const double (&R)[9], const double (&J)[9], const bool reach, const V3 f, const V3 tc,
-                                                     const LegLimDev& lim, const bool limited, V3& ta, V3& f1,
-                                                     const double* __restrict__ ar, const V3 qr) {
-#pragma clang fp contract(off)
-  if constexpr (ACT)
-    ta = {limited ? act_clamp(ar, 0, tc.x, qr.x) : tc.x, limited ? act_clamp(ar, 1, tc.y, qr.y) : tc.y,
-          limited ? act_clamp(ar, 2, tc.z, qr.z) : tc.z};
-  else
-    ta = {limited ? clamp_sym(tc.x, lim.taumax[0]) : tc.x, limited ? clamp_sym(tc.y, lim.taumax[1]) : tc.y,
-          limited ? clamp_sym(tc.z, lim.taumax[2]) : tc.z};
-  const bool clamped = ta.x != tc.x || ta.y != tc.y || ta.z != tc.z;
-  const M3 Jt = {{J[0], J[3], J[6]}, {J[1], J[4], J[7]}, {J[2], J[5], J[8]}};
-  double det;
-  const V3 g = adj_solve(Jt, ta, det);
-  const V3 fc = {-((R[0] * g.x + R[1] * g.y) + R[2] * g.z), -((R[3] * g.x + R[4] * g.y) + R[5] * g.z), -((R[6] * g.x + R[7] * g.y) + R[8] * g.z)};
-  const bool solve = reach && det != 0.0;
-  f1 = sel3(clamped && solve, fc, f);
-  return (clamped ? 2u : 0u) | ((clamped && !solve) ? 16u : 0u);
-}
-
-// The slide of one foot over a tick and the force the ground returned: f1 the force the leg delivers, s0 the foot's velocity, mu the
-// ground's friction, me the foot's effective mass, n substeps of h = delta / n.  s and d are the end velocity and the displacement.
+// Step 4 for a sliding foot, in the place of drive_cone: the slide of one foot over a tick and the force the ground returned.  f1 the
+// force the leg delivers, s0 the foot's velocity, mu the ground's friction, me the foot's effective mass, n substeps of h = delta / n.
+// s and d are the end velocity and the displacement.
 // Returns f2, the applied force (a pull: 0; a sliding leg: the tick average; any other leg: f1 by value, the caller selects).
 __device__ __forceinline__ V3 slip_slide(const V3 f1, const double s0x, const double s0y, const double mu, const double me, const int n,
                                          const double h, const double delta, double& sx, double& sy, double& dx, double& dy, bool& sliding) {
@@ -94,14 +75,8 @@ mpcqp_stance_slip_kernel(const TIO* __restrict__ x, const TIO* f, const int64_t 
   const TIO* fb = f + b * fstride + 3 * l;
   const TIO fr[3] = {fb[0], fb[1], fb[2]};
   const double s0x = slip_in[2 * i], s0y = slip_in[2 * i + 1];
-  bool stance;
-  if (contact) {
-    stance = contact[i] != 0;
-  } else {
-    const GaitLeg gc = gait_leg(gait + b * GAIT_ROW, l);
-    stance = gait_phase(gc, (uint32_t)max(tick[b], 0)) < gc.st;
-  }
-  // the drive's row: R from the rotation vector, the foot seen from the CoM, q and tau_cmd
+  const bool stance = stance_mask(contact, gait, tick, i, b, l);
+  // the drive's row: R from the rotation vector, the foot seen from the CoM, q and tau_cmd (in the kernel: see mpcqp_stance_drive_kernel)
   double qt[4], pw[3], fl[3], ql[3], tl[3];
   plant_rotvec_to_quat((double)xb[0], (double)xb[1], (double)xb[2], qt);
   const double qw = qt[0], qx = qt[1], qy = qt[2], qz = qt[3];
@@ -131,45 +106,29 @@ mpcqp_stance_slip_kernel(const TIO* __restrict__ x, const TIO* f, const int64_t 
   leg_fk_jac(geo, l, ql, pf, J);
   const V3 fv = {fl[0], fl[1], fl[2]}, tc = {tl[0], tl[1], tl[2]}, q = {ql[0], ql[1], ql[2]}, zero = {0.0, 0.0, 0.0};
   const double mu = (double)ground[b], me = (double)foot_mass[b];
-  V3 ta, f1, to;
-  unsigned bits = slip_drive_force<ACT>(R, J, reach, fv, tc, lim, drive == DRIVE_LIMITED, ta, f1, ACT ? act + ACT_ROW * b : nullptr, rate);
+  V3 ta, f1;
+  unsigned bits = drive_force<ACT>(R, J, reach, fv, tc, lim, drive == DRIVE_LIMITED, ta, f1, ACT ? act + ACT_ROW * b : nullptr, rate);
   double sx, sy, dx, dy;
   bool sliding;
   const V3 f2 = slip_slide(f1, s0x, s0y, mu, me, n, h, delta, sx, sy, dx, dy, sliding);
-  const bool limited = f2.x != f1.x || f2.y != f1.y || f2.z != f1.z;
-  const V3 fo = sel3(limited, f2, f1);   // (a select: an untouched force keeps its bits, a -0 included)
-  {
-#pragma clang fp contract(off)
-    // step 5 of the drive's rule: the torque that goes with f2
-    const double h0 = -((R[0] * f2.x + R[3] * f2.y) + R[6] * f2.z), h1 = -((R[1] * f2.x + R[4] * f2.y) + R[7] * f2.z),
-                 h2 = -((R[2] * f2.x + R[5] * f2.y) + R[8] * f2.z);   // R^T (-f2)
-    const V3 tg = {(J[0] * h0 + J[3] * h1) + J[6] * h2, (J[1] * h0 + J[4] * h1) + J[7] * h2, (J[2] * h0 + J[5] * h1) + J[8] * h2};
-    to = sel3(limited, tg, ta);
-  }
-  bits |= (limited ? 32u : 0u) | (sliding ? SLIP_SLIDING : 0u) | swing_limits(lim, q, zero);   // 4: q outside its limits
-  // the robot's x, ground and foot-mass rows poison its four legs, a leg's own operands that leg
+  const bool changed = f2.x != f1.x || f2.y != f1.y || f2.z != f1.z;   // the ground changed the force
+  const V3 fo = sel3(changed, f2, f1);   // (a select: an untouched force keeps its bits, a -0 included)
+  const V3 to = drive_torque(R, J, f2, changed, ta);
+  bits |= (changed ? 32u : 0u) | (sliding ? SLIP_SLIDING : 0u) | swing_limits(lim, q, zero);   // 4: q outside its limits
+  // the robot's x, ground and foot-mass rows poison its four legs, a leg's own operands that leg (in the kernel: see mpcqp_stance_drive_kernel)
   bool robot = isfinite(mu) && mu >= 0.0 && isfinite(me) && me > 0.0;
 #pragma unroll
   for (int a = 0; a < 12; ++a) robot = robot && isfinite((double)xb[a]);
   const bool own = fin3(fv) && isfinite(pw[0]) && isfinite(pw[1]) && isfinite(pw[2]) && isfinite(s0x) && isfinite(s0y) && fin3(fo) &&
                    fin3(to) && isfinite(sx) && isfinite(sy) && isfinite(dx) && isfinite(dy);
   const bool good = robot && (!stance || own);
-  const double nan = __builtin_nan("");
-  TIO* fw = f_out + 12 * b + 3 * l;
-  if (cmd) {
-    TIO* cw = cmd + b * cstride + 3 * l;
-    cw[0] = fr[0]; cw[1] = fr[1]; cw[2] = fr[2];
-  }
   if (slog) {
     double* sw = slog + b * sstride + 2 * l;
     sw[0] = s0x; sw[1] = s0y;
   }
-  // a swing leg keeps its commanded force as read; its foot is in the air, at rest for the rule
-  fw[0] = good ? (stance ? (TIO)fo.x : fr[0]) : (TIO)nan;
-  fw[1] = good ? (stance ? (TIO)fo.y : fr[1]) : (TIO)nan;
-  fw[2] = good ? (stance ? (TIO)fo.z : fr[2]) : (TIO)nan;
-  if (tau) store3(tau + 3 * i, good, sel3(stance, to, zero));
-  if (flag) flag[i] = good ? (uint8_t)(stance ? bits : 0u) : (uint8_t)0xff;
+  drive_store(i, b, l, fr, good, stance, fo, to, bits, f_out, tau, flag, cmd, cstride);
+  // a swing leg's foot is in the air, at rest for the rule
+  const double nan = __builtin_nan("");
   if (slip_out) {
     slip_out[2 * i] = good ? (stance ? sx : 0.0) : nan;
     slip_out[2 * i + 1] = good ? (stance ? sy : 0.0) : nan;
@@ -181,9 +140,10 @@ mpcqp_stance_slip_kernel(const TIO* __restrict__ x, const TIO* f, const int64_t 
 }
 
 // After the landing of tick `it` (tick is the new one): i = 4 b + leg.  rtau [B,4,3], rflag [B,4] and rdisp [B,4,2] are what
-// mpcqp_stance_slip_kernel left for this tick.  The log step is mpcqp_drive_log_kernel's with bit 128: a swing row keeps what the legs
-// step logged, and so does a stance row the legs step poisoned.  Then the feet: a leg in stance on the row's tick that does not touch
-// down on the new one moves by the displacement as the I/O type holds it (z is never touched); a leg that touches down is at rest.
+// mpcqp_stance_slip_kernel left for this tick.  The log step is drive_log_step (mpcqp_drive.h) with bit 128 in its mask: a swing row
+// keeps what the legs step logged, and so does a stance row the legs step poisoned.  Then the feet: a leg in stance on the row's tick
+// that does not touch down on the new one moves by the displacement as the I/O type holds it (z is never touched); a leg that touches
+// down is at rest.
 template <typename TIO>
 __global__ void __launch_bounds__(256)
 mpcqp_slip_finish_kernel(const int32_t* __restrict__ gait, const int32_t* __restrict__ tick, const TIO* __restrict__ rtau,
@@ -202,16 +162,7 @@ mpcqp_slip_finish_kernel(const int32_t* __restrict__ gait, const int32_t* __rest
   const bool stance = gait_phase(gc, tr) < gc.st;
   const bool td = gait_steps(gc) && gait_phase(gc, tc) == 0;
   const int64_t il = 4 * (b * T + it) + l;
-  if (stance) {
-    const bool was_bad = (flag_log && flag_log[il] == 0xff) || (tau_log && isnan((double)tau_log[3 * il]));
-    if (!was_bad) {
-      const unsigned rb = rflag[i];
-      if (tau_log) {   // (a poisoned leg's rtau is NaN already)
-        tau_log[3 * il] = rtau[3 * i]; tau_log[3 * il + 1] = rtau[3 * i + 1]; tau_log[3 * il + 2] = rtau[3 * i + 2];
-      }
-      if (flag_log) flag_log[il] = rb == 0xffu ? (uint8_t)0xff : (uint8_t)(flag_log[il] | (rb & SLIP_BITS));
-    }
-  }
+  if (stance) drive_log_step(i, il, rtau, rflag, SLIP_BITS, false, tau_log, flag_log);
   const bool move = stance && !td;
   const TIO dx = rdisp[2 * i], dy = rdisp[2 * i + 1];
   if (move) {

@@ -33,6 +33,9 @@ def _ptr(t):
     return t.data_ptr() if t is not None else 0
 
 
+_NO_DRIVE = object()      # MPCBatch._rollout_legs: the entry point takes no drive mode (a caller's drive=None is a wrong mode, not this)
+
+
 class MPCBatch:
     """One engine handle on one GPU.  All tensors live on ``cuda:<device>``; nothing is copied to the host."""
 
@@ -518,6 +521,41 @@ class MPCBatch:
 
     LEGS_LOGS = ("swing",) + SWING_OUT + ("miss",)      # the logs `rollout_legs` adds to `rollout_phase`'s, in the C order
 
+    def _rollout_legs(self, call, x, ref, feet, legs, gait, stand, gain, tick, mu, T, step_height, land, body, push, push_ticks, substeps,
+                      gains, leg_substeps, inertia, geometry, log, stream, drive=_NO_DRIVE, operands=(), optional=(), logs=()):
+        """What `rollout_legs`, `rollout_drive` and `rollout_slip` share: the checks, the log spec, the allocation and the addresses
+        for `call`, the engine's entry point.  drive (left out: `call` takes no drive mode) goes to `call` after the landing mode, then the
+        tensors of `operands`, rows as `check_operands` takes them (None passes for the names in `optional`); `logs`, rows (name,
+        shape after [B,T], dtype), follow `rollout_legs`' logs in the result and in the call."""
+        torch = _torch()
+        B, T = int(x.shape[0]), int(T)
+        if land not in ("rule", "actual"):
+            raise ValueError(f"land must be 'rule' or 'actual', got {land!r}")
+        modes = {"ideal": _capi.DRIVE_IDEAL, "limited": _capi.DRIVE_LIMITED}
+        if drive is not _NO_DRIVE and not isinstance(drive, int) and drive not in modes:
+            raise ValueError(f"drive must be 'ideal' or 'limited', got {drive!r}")
+        check_operands(self.device, self._phase_rows(B, x, ref, feet, gait, tick, stand, gain, "x") + (
+            ("legs", legs, (B, 4, 7), torch.float64), ("mu", mu, (B,), self.tdtype), ("body", body, (B, 7), self.tdtype),
+            ("push", push, (B, 6), self.tdtype), ("push_ticks", push_ticks, (B, 2), torch.int32),
+            ("step_height", step_height, (B,), self.tdtype), ("gains", gains, (B, 2), self.tdtype)) + operands,
+            optional=("gain", "body", "push", "push_ticks", "gains") + tuple(optional))
+        st = self._stream(stream)
+        rows, leg3 = ((B, T, 12), self.tdtype), ((B, T, 4, 3), self.tdtype)
+        leg1, mask = ((B, T, 4), self.tdtype), ((B, T, 4), torch.uint8)
+        spec = (rows, rows, rows, leg3, mask) + (((B, T, 4, 4, 3), self.tdtype), leg3, leg3, leg3, leg3, leg1, mask, leg1)
+        spec += tuple(((B, T) + tail, dt) for _, tail, dt in logs)
+        names = ("actual", "desired", "forces", "feet_log", "contact_log") + self.LEGS_LOGS + tuple(k for k, _, _ in logs)
+        out = dict(zip(names, self._alloc(stream, *[s if log else None for s in spec])))
+        solved, = self._alloc(stream, ((B,), torch.int32, not T > 0))
+        p = lambda k: _ptr(out[k])
+        mode = () if drive is _NO_DRIVE else (drive if isinstance(drive, int) else modes[drive],)
+        call(B, T, x.data_ptr(), ref.data_ptr(), feet.data_ptr(), legs.data_ptr(), gait.data_ptr(), stand.data_ptr(), _ptr(gain),
+             tick.data_ptr(), mu.data_ptr(), _ptr(body), _ptr(push), _ptr(push_ticks), substeps, step_height.data_ptr(), _ptr(gains),
+             int(leg_substeps), _capi.LAND_ACTUAL if land == "actual" else _capi.LAND_RULE, *mode, *[_ptr(t) for _, t, _, _ in operands],
+             *[p(k) for k in names[:5]], solved.data_ptr(), *[p(k) for k in names[5:]], geometry, self._inertia(inertia), st.cuda_stream)
+        out["solved"] = solved
+        return out
+
     def rollout_legs(self, x, ref, feet, legs, gait, stand, gain, tick, mu, T, step_height, land="rule", body=None, push=None,
                      push_ticks=None, substeps=10, gains=None, leg_substeps=0, inertia=None, geometry=None, log=True, stream=None):
         """`rollout_phase` with the swing legs integrated inside the roll-out (include/mpcqp_sim.h, mpcqp_rollout_legs; the host
@@ -530,31 +568,19 @@ class MPCBatch:
         `rollout_phase` plus "swing" [B,T,4,4,3] (`phase_swing`'s), "q", "qd", "tau", "foot" [B,T,4,3], "err" [B,T,4], "flag" uint8
         [B,T,4] (`swing_track`'s) and "miss" [B,T,4]: the distance between the delivered foot and the rule's foothold of a leg that
         touches down after tick t, 0 elsewhere.  Asynchronous on `stream`."""
+        return self._rollout_legs(self.engine.rollout_legs_ptr, x, ref, feet, legs, gait, stand, gain, tick, mu, T, step_height, land, body,
+                                  push, push_ticks, substeps, gains, leg_substeps, inertia, geometry, log, stream)
+
+    def _stance_rows(self, x, f, feet, contact, stream):
+        """What `stance_drive` and `stance_slip` share of their operands: B, x (a 12-wide row padded to 13 columns on `stream`) and the
+        rows of x, f, feet and contact for `check_operands`."""
         torch = _torch()
-        B, T = int(x.shape[0]), int(T)
-        if land not in ("rule", "actual"):
-            raise ValueError(f"land must be 'rule' or 'actual', got {land!r}")
-        check_operands(self.device, self._phase_rows(B, x, ref, feet, gait, tick, stand, gain, "x") + (
-            ("legs", legs, (B, 4, 7), torch.float64), ("mu", mu, (B,), self.tdtype), ("body", body, (B, 7), self.tdtype),
-            ("push", push, (B, 6), self.tdtype), ("push_ticks", push_ticks, (B, 2), torch.int32),
-            ("step_height", step_height, (B,), self.tdtype), ("gains", gains, (B, 2), self.tdtype)),
-            optional=("gain", "body", "push", "push_ticks", "gains"))
-        st = self._stream(stream)
-        rows, leg3 = ((B, T, 12), self.tdtype), ((B, T, 4, 3), self.tdtype)
-        leg1, mask = ((B, T, 4), self.tdtype), ((B, T, 4), torch.uint8)
-        spec = (rows, rows, rows, leg3, mask) + (((B, T, 4, 4, 3), self.tdtype), leg3, leg3, leg3, leg3, leg1, mask, leg1)
-        names = ("actual", "desired", "forces", "feet_log", "contact_log") + self.LEGS_LOGS
-        out = dict(zip(names, self._alloc(stream, *[s if log else None for s in spec])))
-        solved, = self._alloc(stream, ((B,), torch.int32, not T > 0))
-        p = lambda k: _ptr(out[k])
-        self.engine.rollout_legs_ptr(B, T, x.data_ptr(), ref.data_ptr(), feet.data_ptr(), legs.data_ptr(), gait.data_ptr(), stand.data_ptr(),
-                                     _ptr(gain), tick.data_ptr(), mu.data_ptr(), _ptr(body), _ptr(push), _ptr(push_ticks), substeps,
-                                     step_height.data_ptr(), _ptr(gains), int(leg_substeps),
-                                     _capi.LAND_ACTUAL if land == "actual" else _capi.LAND_RULE,
-                                     *[p(k) for k in names[:5]], solved.data_ptr(), *[p(k) for k in self.LEGS_LOGS],
-                                     geometry, self._inertia(inertia), st.cuda_stream)
-        out["solved"] = solved
-        return out
+        B = int(x.shape[0])
+        if x.dim() == 2 and x.shape[1] == 12:
+            with torch.cuda.stream(stream):
+                x = torch.cat([x, torch.zeros((B, 1), dtype=x.dtype, device=x.device)], dim=1).contiguous()
+        return B, x, (("x", x, (B, 13), self.tdtype), ("f", f, (B, 12), self.tdtype), ("feet", feet, (B, 4, 3), self.tdtype),
+                      ("contact", contact, (B, 4), torch.uint8))
 
     def stance_drive(self, x, f, feet, contact, ground=None, inertia=None, geometry=None, want=("tau", "flag"), stream=None):
         """What the stance legs deliver of a commanded force (include/mpcqp_sim.h, mpcqp_stance_drive, which has the rule; the host
@@ -566,12 +592,8 @@ class MPCBatch:
         resolvable (out of reach or singular: the force is kept), 32 the ground limited the force, 0xff a non-finite leg}; "tau" /
         "flag" are None when not in `want`.  The held foot does not move (`stance_slip` lets it slide).  Asynchronous on `stream`."""
         torch = _torch()
-        B = int(x.shape[0])
-        if x.dim() == 2 and x.shape[1] == 12:
-            with torch.cuda.stream(stream):
-                x = torch.cat([x, torch.zeros((B, 1), dtype=x.dtype, device=x.device)], dim=1).contiguous()
-        check_operands(self.device, (("x", x, (B, 13), self.tdtype), ("f", f, (B, 12), self.tdtype), ("feet", feet, (B, 4, 3), self.tdtype),
-                                     ("contact", contact, (B, 4), torch.uint8), ("ground", ground, (B,), self.tdtype)), optional=("ground",))
+        B, x, rows = self._stance_rows(x, f, feet, contact, stream)
+        check_operands(self.device, rows + (("ground", ground, (B,), self.tdtype),), optional=("ground",))
         st = self._stream(stream)
         out, tau, flag = self._alloc(stream, ((B, 12), self.tdtype), ((B, 4, 3), self.tdtype) if "tau" in want else None,
                                      ((B, 4), torch.uint8) if "flag" in want else None)
@@ -590,35 +612,10 @@ class MPCBatch:
         commanded forces; on stance rows "tau" is the applied torque and "flag" has the rule's bits 2 / 16 / 32 (score.py's CLAMP_ROWS
         then counts stance rows too).  The MPC is not told about either limit.  drive="ideal" with ground=None is `rollout_legs` bit
         for bit.  Every other argument as in `rollout_legs`.  Asynchronous on `stream`."""
-        torch = _torch()
-        B, T = int(x.shape[0]), int(T)
-        if land not in ("rule", "actual"):
-            raise ValueError(f"land must be 'rule' or 'actual', got {land!r}")
-        modes = {"ideal": _capi.DRIVE_IDEAL, "limited": _capi.DRIVE_LIMITED}
-        if not isinstance(drive, int) and drive not in modes:
-            raise ValueError(f"drive must be 'ideal' or 'limited', got {drive!r}")
-        check_operands(self.device, self._phase_rows(B, x, ref, feet, gait, tick, stand, gain, "x") + (
-            ("legs", legs, (B, 4, 7), torch.float64), ("mu", mu, (B,), self.tdtype), ("body", body, (B, 7), self.tdtype),
-            ("push", push, (B, 6), self.tdtype), ("push_ticks", push_ticks, (B, 2), torch.int32),
-            ("step_height", step_height, (B,), self.tdtype), ("gains", gains, (B, 2), self.tdtype), ("ground", ground, (B,), self.tdtype)),
-            optional=("gain", "body", "push", "push_ticks", "gains", "ground"))
-        st = self._stream(stream)
-        rows, leg3 = ((B, T, 12), self.tdtype), ((B, T, 4, 3), self.tdtype)
-        leg1, mask = ((B, T, 4), self.tdtype), ((B, T, 4), torch.uint8)
-        spec = (rows, rows, rows, leg3, mask) + (((B, T, 4, 4, 3), self.tdtype), leg3, leg3, leg3, leg3, leg1, mask, leg1) + (rows,)
-        names = ("actual", "desired", "forces", "feet_log", "contact_log") + self.LEGS_LOGS + ("cmd",)
-        out = dict(zip(names, self._alloc(stream, *[s if log else None for s in spec])))
-        solved, = self._alloc(stream, ((B,), torch.int32, not T > 0))
-        p = lambda k: _ptr(out[k])
-        self.engine.rollout_drive_ptr(B, T, x.data_ptr(), ref.data_ptr(), feet.data_ptr(), legs.data_ptr(), gait.data_ptr(), stand.data_ptr(),
-                                      _ptr(gain), tick.data_ptr(), mu.data_ptr(), _ptr(body), _ptr(push), _ptr(push_ticks), substeps,
-                                      step_height.data_ptr(), _ptr(gains), int(leg_substeps),
-                                      _capi.LAND_ACTUAL if land == "actual" else _capi.LAND_RULE,
-                                      drive if isinstance(drive, int) else modes[drive], _ptr(ground),
-                                      *[p(k) for k in names[:5]], solved.data_ptr(), *[p(k) for k in self.LEGS_LOGS], p("cmd"),
-                                      geometry, self._inertia(inertia), st.cuda_stream)
-        out["solved"] = solved
-        return out
+        return self._rollout_legs(self.engine.rollout_drive_ptr, x, ref, feet, legs, gait, stand, gain, tick, mu, T, step_height, land, body,
+                                  push, push_ticks, substeps, gains, leg_substeps, inertia, geometry, log, stream, drive,
+                                  operands=(("ground", ground, (int(x.shape[0]),), self.tdtype),), optional=("ground",),
+                                  logs=(("cmd", (12,), self.tdtype),))
 
     def stance_slip(self, x, f, feet, contact, ground, foot_mass, slip, substeps=10, inertia=None, geometry=None, want=("tau", "flag"),
                     stream=None):
@@ -630,13 +627,9 @@ class MPCBatch:
         float64 [B,4,2] the velocities at the end of the tick (0 on a swing leg), "disp": [B,4,2] how far each foot slid}; "tau" /
         "flag" are None when not in `want`.  Asynchronous on `stream`."""
         torch = _torch()
-        B = int(x.shape[0])
-        if x.dim() == 2 and x.shape[1] == 12:
-            with torch.cuda.stream(stream):
-                x = torch.cat([x, torch.zeros((B, 1), dtype=x.dtype, device=x.device)], dim=1).contiguous()
-        check_operands(self.device, (("x", x, (B, 13), self.tdtype), ("f", f, (B, 12), self.tdtype), ("feet", feet, (B, 4, 3), self.tdtype),
-                                     ("contact", contact, (B, 4), torch.uint8), ("ground", ground, (B,), self.tdtype),
-                                     ("foot_mass", foot_mass, (B,), self.tdtype), ("slip", slip, (B, 4, 2), torch.float64)))
+        B, x, rows = self._stance_rows(x, f, feet, contact, stream)
+        check_operands(self.device, rows + (("ground", ground, (B,), self.tdtype), ("foot_mass", foot_mass, (B,), self.tdtype),
+                                            ("slip", slip, (B, 4, 2), torch.float64)))
         st = self._stream(stream)
         out, tau, flag, slip_out, disp = self._alloc(stream, ((B, 12), self.tdtype), ((B, 4, 3), self.tdtype) if "tau" in want else None,
                                                      ((B, 4), torch.uint8) if "flag" in want else None, ((B, 4, 2), torch.float64),
@@ -656,37 +649,12 @@ class MPCBatch:
         `rollout_drive`'s dict plus "slip_log" float64 [B,T,4,2], the velocities at the start of each row, and "disp" [B,T,4,2], what
         was added to the feet after the row; "flag" has bit 128 on the rows of a sliding leg.  On a ground that never limits (1e3) it is
         `rollout_drive` on that ground, bit for bit.  Every other argument as in `rollout_drive`.  Asynchronous on `stream`."""
-        torch = _torch()
-        B, T = int(x.shape[0]), int(T)
-        if land not in ("rule", "actual"):
-            raise ValueError(f"land must be 'rule' or 'actual', got {land!r}")
-        modes = {"ideal": _capi.DRIVE_IDEAL, "limited": _capi.DRIVE_LIMITED}
-        if not isinstance(drive, int) and drive not in modes:
-            raise ValueError(f"drive must be 'ideal' or 'limited', got {drive!r}")
-        check_operands(self.device, self._phase_rows(B, x, ref, feet, gait, tick, stand, gain, "x") + (
-            ("legs", legs, (B, 4, 7), torch.float64), ("mu", mu, (B,), self.tdtype), ("body", body, (B, 7), self.tdtype),
-            ("push", push, (B, 6), self.tdtype), ("push_ticks", push_ticks, (B, 2), torch.int32),
-            ("step_height", step_height, (B,), self.tdtype), ("gains", gains, (B, 2), self.tdtype), ("ground", ground, (B,), self.tdtype),
-            ("foot_mass", foot_mass, (B,), self.tdtype), ("slip", slip, (B, 4, 2), torch.float64)),
-            optional=("gain", "body", "push", "push_ticks", "gains"))
-        st = self._stream(stream)
-        rows, leg3 = ((B, T, 12), self.tdtype), ((B, T, 4, 3), self.tdtype)
-        leg1, mask = ((B, T, 4), self.tdtype), ((B, T, 4), torch.uint8)
-        spec = (rows, rows, rows, leg3, mask) + (((B, T, 4, 4, 3), self.tdtype), leg3, leg3, leg3, leg3, leg1, mask, leg1) + (
-            rows, ((B, T, 4, 2), torch.float64), ((B, T, 4, 2), self.tdtype))
-        names = ("actual", "desired", "forces", "feet_log", "contact_log") + self.LEGS_LOGS + ("cmd", "slip_log", "disp")
-        out = dict(zip(names, self._alloc(stream, *[s if log else None for s in spec])))
-        solved, = self._alloc(stream, ((B,), torch.int32, not T > 0))
-        p = lambda k: _ptr(out[k])
-        self.engine.rollout_slip_ptr(B, T, x.data_ptr(), ref.data_ptr(), feet.data_ptr(), legs.data_ptr(), gait.data_ptr(), stand.data_ptr(),
-                                     _ptr(gain), tick.data_ptr(), mu.data_ptr(), _ptr(body), _ptr(push), _ptr(push_ticks), substeps,
-                                     step_height.data_ptr(), _ptr(gains), int(leg_substeps),
-                                     _capi.LAND_ACTUAL if land == "actual" else _capi.LAND_RULE,
-                                     drive if isinstance(drive, int) else modes[drive], ground.data_ptr(), foot_mass.data_ptr(), slip.data_ptr(),
-                                     *[p(k) for k in names[:5]], solved.data_ptr(), *[p(k) for k in self.LEGS_LOGS], p("cmd"), p("slip_log"),
-                                     p("disp"), geometry, self._inertia(inertia), st.cuda_stream)
-        out["solved"] = solved
-        return out
+        B, f64 = int(x.shape[0]), _torch().float64
+        return self._rollout_legs(self.engine.rollout_slip_ptr, x, ref, feet, legs, gait, stand, gain, tick, mu, T, step_height, land, body,
+                                  push, push_ticks, substeps, gains, leg_substeps, inertia, geometry, log, stream, drive,
+                                  operands=(("ground", ground, (B,), self.tdtype), ("foot_mass", foot_mass, (B,), self.tdtype),
+                                            ("slip", slip, (B, 4, 2), f64)),
+                                  logs=(("cmd", (12,), self.tdtype), ("slip_log", (4, 2), f64), ("disp", (4, 2), self.tdtype)))
 
     def score(self, logs, score=None, rule=None, stream=None):
         """The score row of a roll-out's logs, reduced on the device (include/mpcqp_sim.h, mpcqp_rollout_score; the host counterpart is

@@ -357,6 +357,10 @@ def _rollout_legs_loop(oracle_engine, x, ref, feet, legs, gait, stand, gain, tic
     B = x.shape[0]
     bd = model_body(cfg.m, list(cfg.Ibody_inv), B) if body is None else _f64(body)
     grav = lite3_model._inertia_arrays(inertia)["gravity"]
+    # what the stance rule adds to a stance row's flag
+    rule_bits = lite3_model.DRIVE_CLAMPED | lite3_model.DRIVE_UNRESOLVED | lite3_model.DRIVE_GROUND
+    if slide is not None:
+        rule_bits |= lite3_model.DRIVE_SLIDING
     actual = np.zeros((B, T, 12)); desired = np.zeros((B, T, 12)); forces = np.zeros((B, T, 12)); solved = np.zeros(B, np.int32)
     feet_log = np.zeros((B, T, 4, 3)); contact_log = np.zeros((B, T, 4), np.uint8)
     out = {"swing": np.zeros((B, T, 4, 4, 3)), "err": np.zeros((B, T, 4)), "flag": np.zeros((B, T, 4), np.uint8), "miss": np.zeros((B, T, 4)),
@@ -397,7 +401,7 @@ def _rollout_legs_loop(oracle_engine, x, ref, feet, legs, gait, stand, gain, tic
         if drive is not None:      # stance rows the legs step did not poison: the rule's torque and bits
             m = (contact_log[:, t] != 0) & (out["flag"][:, t] != 0xff)
             out["tau"][:, t] = np.where(m[..., None], dv["tau"], out["tau"][:, t])
-            out["flag"][:, t] = np.where(m, np.where(dv["flag"] == 0xff, 0xff, out["flag"][:, t] | (dv["flag"] & (50 if slide is None else 178))), out["flag"][:, t])
+            out["flag"][:, t] = np.where(m, np.where(dv["flag"] == 0xff, 0xff, out["flag"][:, t] | (dv["flag"] & rule_bits)), out["flag"][:, t])
         x = srb_step(x, forces[:, t], feet, e["contact"][:, 0], bd, wr, delta, substeps)
         ref[:, 3:6] = ref[:, 3:6] + ref[:, 6:9] * delta
         ref[:, 2] = ref[:, 2] + ref[:, 9] * delta

@@ -588,6 +588,126 @@ def swing_track_host(actual, forces, feet_log, contact_log, swing, base_acc=None
 DRIVE_CLAMPED, DRIVE_QLIM, DRIVE_UNRESOLVED, DRIVE_GROUND = 2, 4, 16, 32
 
 
+def _stance_rule(x, f, feet, contact, ground, drive, inertia, actuators, slide=None):
+    """The rule of `stance_drive_host` (slide = None: a held foot) and of `stance_slip_host` (slide = (foot_mass, slip, delta, n): a
+    foot that slides), numpy in the device's order of operations.  The two differ in the poison terms, the foot velocity behind the
+    envelope's rate, step 4, the margin and the "slip" / "disp" outputs; everything else is written once, here."""
+    from scipy.spatial.transform import Rotation
+    from . import actuators as _act
+    inr = _inertia_arrays(inertia)
+    x, feet = np.asarray(x, dtype=float), np.asarray(feet, dtype=float)
+    B = x.shape[0]
+    fr = np.asarray(f, dtype=float).reshape(B, 4, 3)
+    stance = np.asarray(contact).reshape(B, 4) != 0
+    mu = None if ground is None and slide is None else np.asarray(ground, dtype=float).reshape(B)
+    with np.errstate(invalid="ignore"):
+        robot = np.isfinite(x[:, :12]).all(axis=1) & (True if mu is None else (np.isfinite(mu) & (mu >= 0.0)))
+    leg = np.isfinite(fr).all(axis=-1) & np.isfinite(feet).all(axis=-1)
+    if slide is not None:
+        me = np.broadcast_to(np.asarray(slide[0], dtype=float), (B,)).copy()
+        s0 = np.asarray(slide[1], dtype=float).reshape(B, 4, 2)
+        delta, n = float(slide[2]), slide[3]
+        with np.errstate(invalid="ignore"):
+            robot = robot & np.isfinite(me) & (me > 0.0)
+        leg = leg & np.isfinite(s0).all(axis=-1)
+    # a poisoned row computes on clean stand-ins and is selected away at the end
+    xs = np.where(robot[:, None], x[:, :12], 0.0)
+    fs, ps = np.where(leg[..., None], fr, 0.0), np.where(leg[..., None], feet, 0.0)
+    mus = np.zeros((B, 1)) if mu is None else np.where(robot, mu, 0.0)[:, None]
+    fv = ()       # the held foot is at rest in the world
+    if slide is not None:
+        ss, mes = np.where(leg[..., None], s0, 0.0), np.where(robot, me, 1.0)[:, None]
+        fv = (np.concatenate([ss, np.zeros((B, 4, 1))], axis=-1)[:, None],)
+    if actuators is None:
+        q, tc, reach = (a[:, 0] for a in joint_log_host(xs[:, None], fs.reshape(B, 1, 12), ps[:, None]))
+    else:
+        q, rate, tc, _, reach = (a[:, 0] for a in joint_rates_host(xs[:, None], fs.reshape(B, 1, 12), ps[:, None], *fv))
+    R = Rotation.from_rotvec(xs[:, :3]).as_matrix()
+    tmax = inr["tau_max"]
+    with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+        z, p = _leg_chain(q)[1:]
+        J = np.stack([np.cross(z[k], p[3] - p[k]) for k in range(3)], axis=-1)                  # [B,4,3,3], leg_fk_jac's
+        # 2. the actuators
+        if drive != "limited":
+            ta = tc
+        elif actuators is None:
+            ta = np.minimum(np.maximum(tc, -tmax), tmax)
+        else:
+            ta = _act.clamp_host(actuators, tc, rate)
+        clamped = (ta != tc).any(axis=-1)
+        # 3. the force the applied torque delivers
+        g, det = _adj_solve(np.swapaxes(J, -1, -2), ta)                                       # J^-T tau_app
+        Rl = R[:, None]
+        fc = -np.stack([(Rl[..., a, 0] * g[..., 0] + Rl[..., a, 1] * g[..., 1]) + Rl[..., a, 2] * g[..., 2] for a in range(3)], axis=-1)
+        solve = (reach != 0) & (det != 0.0)
+        f1 = np.where((clamped & solve)[..., None], fc, fs)
+        # 4. the ground
+        rel = lambda val, thr: np.abs(val - thr) / np.maximum(1.0, np.abs(thr))
+        pull = f1[..., 2] <= 0.0
+        if slide is None:      # the held foot: the tangential part on the circular cone with its direction kept
+            ft = np.sqrt(f1[..., 0] * f1[..., 0] + f1[..., 1] * f1[..., 1])
+            cap = mus * f1[..., 2]
+            cone = (ft > cap) if mu is not None else np.zeros((B, 4), bool)
+            s = cap / ft
+            f2 = np.stack([np.where(cone, f1[..., 0] * s, f1[..., 0]), np.where(cone, f1[..., 1] * s, f1[..., 1]), f1[..., 2]], axis=-1)
+        else:                  # the slide
+            h = delta / n
+            fn = np.where(pull, 0.0, f1[..., 2])
+            hm = h / mes
+            cap = (mus * fn) * hm
+            vx, vy = -f1[..., 0] * hm, -f1[..., 1] * hm
+            sx, sy = ss[..., 0].copy(), ss[..., 1].copy()
+            dx, dy = np.zeros((B, 4)), np.zeros((B, 4))
+            slide_margin = np.full((B, 4), np.inf)
+            for _ in range(n):
+                tx, ty = sx + vx, sy + vy
+                nrm = np.sqrt(tx * tx + ty * ty)
+                stick = nrm <= cap
+                # (cap = 0 -- a pull, or ice -- is an exact zero on both sides: |s*| <= 0 is then decided by exact zeros too)
+                slide_margin = np.minimum(slide_margin, np.where(cap == 0.0, np.inf, rel(nrm, cap)))
+                keep = 1.0 - cap / nrm
+                sx, sy = np.where(stick, 0.0, tx * keep), np.where(stick, 0.0, ty * keep)
+                dx, dy = dx + h * sx, dy + h * sy
+            sliding = (ss[..., 0] != 0.0) | (ss[..., 1] != 0.0) | (sx != 0.0) | (sy != 0.0)
+            med = mes / delta
+            f2 = np.stack([np.where(sliding, f1[..., 0] + med * (sx - ss[..., 0]), f1[..., 0]),
+                           np.where(sliding, f1[..., 1] + med * (sy - ss[..., 1]), f1[..., 1]), f1[..., 2]], axis=-1)
+        f2 = np.where(pull[..., None], 0.0, f2)
+        limited = (f2 != f1).any(axis=-1)
+        fo = np.where(limited[..., None], f2, f1)
+        # 5. the torque that goes with it
+        h5 = -np.stack([(Rl[..., 0, a] * f2[..., 0] + Rl[..., 1, a] * f2[..., 1]) + Rl[..., 2, a] * f2[..., 2] for a in range(3)], axis=-1)
+        tg = np.stack([(J[..., 0, j] * h5[..., 0] + J[..., 1, j] * h5[..., 1]) + J[..., 2, j] * h5[..., 2] for j in range(3)], axis=-1)
+        to = np.where(limited[..., None], tg, ta)
+        bits = (np.where(clamped, DRIVE_CLAMPED, 0) | np.where(clamped & ~solve, DRIVE_UNRESOLVED, 0) | np.where(limited, DRIVE_GROUND, 0)
+                | np.where(((q < inr["q_min"]) | (q > inr["q_max"])).any(axis=-1), DRIVE_QLIM, 0))
+        margin = np.full((B, 4), np.inf)
+        if drive == "limited":
+            margin = rel(np.abs(tc), tmax).min(axis=-1) if actuators is None else _act.margin_host(actuators, tc, rate)
+        # an unclamped leg's f1 is f as read and its ground decisions are exact comparisons of correctly rounded operations: only a
+        # clamped leg's computed f1 can fall on the other side of them.  The stick decisions compare computed values on every leg.
+        ground_margin = rel(f1[..., 2], 0.0)
+        if slide is None and mu is not None:
+            ground_margin = np.minimum(ground_margin, np.where(pull, np.inf, rel(ft, cap)))
+        margin = np.where(clamped & solve, np.minimum(margin, ground_margin), margin)
+        own = leg & np.isfinite(fo).all(axis=-1) & np.isfinite(to).all(axis=-1)
+        if slide is not None:
+            bits = bits | np.where(sliding, DRIVE_SLIDING, 0)
+            margin = np.minimum(margin, slide_margin)
+            own = own & np.isfinite(sx) & np.isfinite(sy) & np.isfinite(dx) & np.isfinite(dy)
+        good = robot[:, None] & (~stance | own)
+    st3 = stance[..., None]
+    sel = lambda a, off: np.where(good[..., None], np.where(st3, a, off), np.nan)
+    out = {"f": sel(fo, fr).reshape(B, 12), "tau": sel(to, 0.0), "flag": np.where(good, np.where(stance, bits, 0), 0xff).astype(np.uint8)}
+    if slide is not None:
+        out["slip"], out["disp"] = sel(np.stack([sx, sy], axis=-1), 0.0), sel(np.stack([dx, dy], axis=-1), 0.0)
+    out.update({"tau_cmd": np.where((good & stance)[..., None], tc, np.nan), "q": q, "reach": reach,
+                "margin": np.where(good & stance, margin, np.inf)})
+    if actuators is not None:
+        out["rate"] = rate
+    return out
+
+
 def stance_drive_host(x, f, feet, contact, ground=None, drive="limited", inertia=None, actuators=None):
     """What the stance legs deliver of a commanded force (the host counterpart of mpcqp_stance_drive, include/mpcqp_sim.h, which has the
     rule; numpy in the device's order of operations): x [B,>=12] as stored, f [B,12] or [B,4,3] the commanded forces, feet [B,4,3] the
@@ -604,78 +724,9 @@ def stance_drive_host(x, f, feet, contact, ground=None, drive="limited", inertia
     actuators [B,9] (actuators.py, include/mpcqp_actuators.h) or None: the clamp is then robot b's envelope at "rate" [B,4,3] (an extra
     key of the result), `joint_rates_host`'s joint rate with the foot at rest in the world, and the margin counts the envelope's
     comparisons; drive "ideal" does not read the table; a robot with an invalid row gets NaN and 0xff on its stance legs."""
-    from scipy.spatial.transform import Rotation
-    from . import actuators as _act
     if drive not in ("limited", "ideal"):
         raise ValueError(f"drive must be 'ideal' or 'limited', got {drive!r}")
-    inr = _inertia_arrays(inertia)
-    x, feet = np.asarray(x, dtype=float), np.asarray(feet, dtype=float)
-    B = x.shape[0]
-    fr = np.asarray(f, dtype=float).reshape(B, 4, 3)
-    stance = np.asarray(contact).reshape(B, 4) != 0
-    mu = None if ground is None else np.asarray(ground, dtype=float).reshape(B)
-    with np.errstate(invalid="ignore"):
-        robot = np.isfinite(x[:, :12]).all(axis=1) & (True if mu is None else (np.isfinite(mu) & (mu >= 0.0)))
-    leg = np.isfinite(fr).all(axis=-1) & np.isfinite(feet).all(axis=-1)
-    # a poisoned row computes on clean stand-ins and is selected away at the end
-    xs = np.where(robot[:, None], x[:, :12], 0.0)
-    fs, ps = np.where(leg[..., None], fr, 0.0), np.where(leg[..., None], feet, 0.0)
-    mus = np.zeros(B) if mu is None else np.where(robot, mu, 0.0)
-    if actuators is None:
-        q, tc, reach = (a[:, 0] for a in joint_log_host(xs[:, None], fs.reshape(B, 1, 12), ps[:, None]))
-    else:
-        q, rate, tc, _, reach = (a[:, 0] for a in joint_rates_host(xs[:, None], fs.reshape(B, 1, 12), ps[:, None]))
-    R = Rotation.from_rotvec(xs[:, :3]).as_matrix()
-    tmax = inr["tau_max"]
-    with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
-        z, p = _leg_chain(q)[1:]
-        J = np.stack([np.cross(z[k], p[3] - p[k]) for k in range(3)], axis=-1)                  # [B,4,3,3], leg_fk_jac's
-        if drive != "limited":
-            ta = tc
-        elif actuators is None:
-            ta = np.minimum(np.maximum(tc, -tmax), tmax)
-        else:
-            ta = _act.clamp_host(actuators, tc, rate)
-        clamped = (ta != tc).any(axis=-1)
-        g, det = _adj_solve(np.swapaxes(J, -1, -2), ta)                                       # J^-T tau_app
-        Rl = R[:, None]
-        fc = -np.stack([(Rl[..., a, 0] * g[..., 0] + Rl[..., a, 1] * g[..., 1]) + Rl[..., a, 2] * g[..., 2] for a in range(3)], axis=-1)
-        solve = (reach != 0) & (det != 0.0)
-        f1 = np.where((clamped & solve)[..., None], fc, fs)
-        pull = f1[..., 2] <= 0.0
-        ft = np.sqrt(f1[..., 0] * f1[..., 0] + f1[..., 1] * f1[..., 1])
-        cap = mus[:, None] * f1[..., 2]
-        cone = (ft > cap) if mu is not None else np.zeros((B, 4), bool)
-        s = cap / ft
-        f2 = np.stack([np.where(cone, f1[..., 0] * s, f1[..., 0]), np.where(cone, f1[..., 1] * s, f1[..., 1]), f1[..., 2]], axis=-1)
-        f2 = np.where(pull[..., None], 0.0, f2)
-        limited = (f2 != f1).any(axis=-1)
-        fo = np.where(limited[..., None], f2, f1)
-        h = -np.stack([(Rl[..., 0, a] * f2[..., 0] + Rl[..., 1, a] * f2[..., 1]) + Rl[..., 2, a] * f2[..., 2] for a in range(3)], axis=-1)
-        tg = np.stack([(J[..., 0, j] * h[..., 0] + J[..., 1, j] * h[..., 1]) + J[..., 2, j] * h[..., 2] for j in range(3)], axis=-1)
-        to = np.where(limited[..., None], tg, ta)
-        bits = (np.where(clamped, DRIVE_CLAMPED, 0) | np.where(clamped & ~solve, DRIVE_UNRESOLVED, 0) | np.where(limited, DRIVE_GROUND, 0)
-                | np.where(((q < inr["q_min"]) | (q > inr["q_max"])).any(axis=-1), DRIVE_QLIM, 0))
-        rel = lambda val, thr: np.abs(val - thr) / np.maximum(1.0, np.abs(thr))
-        # an unclamped leg's f1 is f as read and its ground decisions are exact comparisons of correctly rounded operations: only a
-        # clamped leg's computed f1 can fall on the other side of them
-        margin = np.full((B, 4), np.inf)
-        if drive == "limited":
-            margin = rel(np.abs(tc), tmax).min(axis=-1) if actuators is None else _act.margin_host(actuators, tc, rate)
-        ground_margin = rel(f1[..., 2], 0.0)
-        if mu is not None:
-            ground_margin = np.minimum(ground_margin, np.where(pull, np.inf, rel(ft, cap)))
-        margin = np.where(clamped & solve, np.minimum(margin, ground_margin), margin)
-        good = robot[:, None] & (~stance | (leg & np.isfinite(fo).all(axis=-1) & np.isfinite(to).all(axis=-1)))
-    st3 = stance[..., None]
-    out_f = np.where(good[..., None], np.where(st3, fo, fr), np.nan)
-    out_t = np.where(good[..., None], np.where(st3, to, 0.0), np.nan)
-    flag = np.where(good, np.where(stance, bits, 0), 0xff).astype(np.uint8)
-    out = {"f": out_f.reshape(B, 12), "tau": out_t, "flag": flag, "tau_cmd": np.where((good & stance)[..., None], tc, np.nan), "q": q,
-           "reach": reach, "margin": np.where(good & stance, margin, np.inf)}
-    if actuators is not None:
-        out["rate"] = rate
-    return out
+    return _stance_rule(x, f, feet, contact, ground, drive, inertia, actuators)
 
 
 # ---- stance feet that slide (the host counterpart of mpcqp_stance_slip, include/mpcqp_slip.h) ----------------------------------------
@@ -706,102 +757,12 @@ def stance_slip_host(x, f, feet, contact, ground, foot_mass, slip, drive="limite
     swing leg) and "disp" [B,4,2] how far each foot slid.  With actuators the envelope's rate is that of a foot moving at `slip`.
     "margin" [B,4] (host only) also covers, for every leg, the |s*| versus cap decision of each substep, and the ground's decisions
     no longer (the rule has no cone scaling; f1_z at 0 stays, for a clamped leg)."""
-    from scipy.spatial.transform import Rotation
-    from . import actuators as _act
     if drive not in ("limited", "ideal"):
         raise ValueError(f"drive must be 'ideal' or 'limited', got {drive!r}")
     n = 10 if int(substeps) == 0 else int(substeps)
     if not 1 <= n <= 1000:
         raise ValueError(f"substeps must be in [0, 1000], got {substeps}")
-    inr = _inertia_arrays(inertia)
-    x, feet = np.asarray(x, dtype=float), np.asarray(feet, dtype=float)
-    B = x.shape[0]
-    fr = np.asarray(f, dtype=float).reshape(B, 4, 3)
-    stance = np.asarray(contact).reshape(B, 4) != 0
-    mu = np.asarray(ground, dtype=float).reshape(B)
-    me = np.broadcast_to(np.asarray(foot_mass, dtype=float), (B,)).copy()
-    s0 = np.asarray(slip, dtype=float).reshape(B, 4, 2)
-    with np.errstate(invalid="ignore"):
-        robot = np.isfinite(x[:, :12]).all(axis=1) & np.isfinite(mu) & (mu >= 0.0) & np.isfinite(me) & (me > 0.0)
-    leg = np.isfinite(fr).all(axis=-1) & np.isfinite(feet).all(axis=-1) & np.isfinite(s0).all(axis=-1)
-    # a poisoned row computes on clean stand-ins and is selected away at the end
-    xs = np.where(robot[:, None], x[:, :12], 0.0)
-    fs, ps, ss = np.where(leg[..., None], fr, 0.0), np.where(leg[..., None], feet, 0.0), np.where(leg[..., None], s0, 0.0)
-    mus, mes = np.where(robot, mu, 0.0)[:, None], np.where(robot, me, 1.0)[:, None]
-    if actuators is None:
-        q, tc, reach = (a[:, 0] for a in joint_log_host(xs[:, None], fs.reshape(B, 1, 12), ps[:, None]))
-    else:
-        fv = np.concatenate([ss, np.zeros((B, 4, 1))], axis=-1)
-        q, rate, tc, _, reach = (a[:, 0] for a in joint_rates_host(xs[:, None], fs.reshape(B, 1, 12), ps[:, None], fv[:, None]))
-    R = Rotation.from_rotvec(xs[:, :3]).as_matrix()
-    tmax = inr["tau_max"]
-    h = float(delta) / n
-    with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
-        z, p = _leg_chain(q)[1:]
-        J = np.stack([np.cross(z[k], p[3] - p[k]) for k in range(3)], axis=-1)                  # [B,4,3,3], leg_fk_jac's
-        if drive != "limited":
-            ta = tc
-        elif actuators is None:
-            ta = np.minimum(np.maximum(tc, -tmax), tmax)
-        else:
-            ta = _act.clamp_host(actuators, tc, rate)
-        clamped = (ta != tc).any(axis=-1)
-        g, det = _adj_solve(np.swapaxes(J, -1, -2), ta)                                       # J^-T tau_app
-        Rl = R[:, None]
-        fc = -np.stack([(Rl[..., a, 0] * g[..., 0] + Rl[..., a, 1] * g[..., 1]) + Rl[..., a, 2] * g[..., 2] for a in range(3)], axis=-1)
-        solve = (reach != 0) & (det != 0.0)
-        f1 = np.where((clamped & solve)[..., None], fc, fs)
-        # the slide
-        rel = lambda val, thr: np.abs(val - thr) / np.maximum(1.0, np.abs(thr))
-        pull = f1[..., 2] <= 0.0
-        fn = np.where(pull, 0.0, f1[..., 2])
-        hm = h / mes
-        cap = (mus * fn) * hm
-        vx, vy = -f1[..., 0] * hm, -f1[..., 1] * hm
-        sx, sy = ss[..., 0].copy(), ss[..., 1].copy()
-        dx, dy = np.zeros((B, 4)), np.zeros((B, 4))
-        slide_margin = np.full((B, 4), np.inf)
-        for _ in range(n):
-            tx, ty = sx + vx, sy + vy
-            nrm = np.sqrt(tx * tx + ty * ty)
-            stick = nrm <= cap
-            # (cap = 0 -- a pull, or ice -- is an exact zero on both sides: |s*| <= 0 is then decided by exact zeros too)
-            slide_margin = np.minimum(slide_margin, np.where(cap == 0.0, np.inf, rel(nrm, cap)))
-            keep = 1.0 - cap / nrm
-            sx, sy = np.where(stick, 0.0, tx * keep), np.where(stick, 0.0, ty * keep)
-            dx, dy = dx + h * sx, dy + h * sy
-        sliding = (ss[..., 0] != 0.0) | (ss[..., 1] != 0.0) | (sx != 0.0) | (sy != 0.0)
-        med = mes / float(delta)
-        f2 = np.stack([np.where(sliding, f1[..., 0] + med * (sx - ss[..., 0]), f1[..., 0]),
-                       np.where(sliding, f1[..., 1] + med * (sy - ss[..., 1]), f1[..., 1]), f1[..., 2]], axis=-1)
-        f2 = np.where(pull[..., None], 0.0, f2)
-        limited = (f2 != f1).any(axis=-1)
-        fo = np.where(limited[..., None], f2, f1)
-        hh = -np.stack([(Rl[..., 0, a] * f2[..., 0] + Rl[..., 1, a] * f2[..., 1]) + Rl[..., 2, a] * f2[..., 2] for a in range(3)], axis=-1)
-        tg = np.stack([(J[..., 0, j] * hh[..., 0] + J[..., 1, j] * hh[..., 1]) + J[..., 2, j] * hh[..., 2] for j in range(3)], axis=-1)
-        to = np.where(limited[..., None], tg, ta)
-        bits = (np.where(clamped, DRIVE_CLAMPED, 0) | np.where(clamped & ~solve, DRIVE_UNRESOLVED, 0) | np.where(limited, DRIVE_GROUND, 0)
-                | np.where(sliding, DRIVE_SLIDING, 0) | np.where(((q < inr["q_min"]) | (q > inr["q_max"])).any(axis=-1), DRIVE_QLIM, 0))
-        margin = np.full((B, 4), np.inf)
-        if drive == "limited":
-            margin = rel(np.abs(tc), tmax).min(axis=-1) if actuators is None else _act.margin_host(actuators, tc, rate)
-        # an unclamped leg's f1 is f as read: its pull decision is exact.  The stick decisions compare computed values on every leg.
-        margin = np.where(clamped & solve, np.minimum(margin, rel(f1[..., 2], 0.0)), margin)
-        margin = np.minimum(margin, slide_margin)
-        own = (leg & np.isfinite(fo).all(axis=-1) & np.isfinite(to).all(axis=-1) & np.isfinite(sx) & np.isfinite(sy) & np.isfinite(dx)
-               & np.isfinite(dy))
-        good = robot[:, None] & (~stance | own)
-    st3 = stance[..., None]
-    out_f = np.where(good[..., None], np.where(st3, fo, fr), np.nan)
-    out_t = np.where(good[..., None], np.where(st3, to, 0.0), np.nan)
-    flag = np.where(good, np.where(stance, bits, 0), 0xff).astype(np.uint8)
-    out_s = np.where(good[..., None], np.where(st3, np.stack([sx, sy], axis=-1), 0.0), np.nan)
-    out_d = np.where(good[..., None], np.where(st3, np.stack([dx, dy], axis=-1), 0.0), np.nan)
-    out = {"f": out_f.reshape(B, 12), "tau": out_t, "flag": flag, "slip": out_s, "disp": out_d,
-           "tau_cmd": np.where((good & stance)[..., None], tc, np.nan), "q": q, "reach": reach, "margin": np.where(good & stance, margin, np.inf)}
-    if actuators is not None:
-        out["rate"] = rate
-    return out
+    return _stance_rule(x, f, feet, contact, ground, drive, inertia, actuators, (foot_mass, slip, delta, n))
 
 
 def world_jacobians(R_body, q_all):

@@ -390,8 +390,9 @@ def test_poison_arguments_and_empty_calls():
     for k in ALL_LOGS:
         assert _same(nan[k][keep], whole[k][keep]), k
     # argument errors, by message
-    with pytest.raises(ValueError, match="drive must be"):
-        run(ops.state(), 1, drive="strong")
+    for bad in ("strong", None):                                               # (None is a wrong mode too, not "no mode")
+        with pytest.raises(ValueError, match=f"drive must be 'ideal' or 'limited', got {bad!r}"):
+            run(ops.state(), 1, drive=bad)
     with pytest.raises(ValueError, match="land must be"):
         run(ops.state(), 1, land="soft")
     for bad in (2, -1):

@@ -310,8 +310,9 @@ def test_pieces_land_actual_null_logs_and_arguments():
     torch.cuda.synchronize()
     assert torch.equal(rep["f"], lim["forces"].reshape(B * T, 12))
     # the drive argument
-    with pytest.raises(ValueError, match="drive must be"):
-        run(ops.state(), 1, drive="strong")
+    for bad in ("strong", None):                                               # (None is a wrong mode too, not "no mode")
+        with pytest.raises(ValueError, match=f"drive must be 'ideal' or 'limited', got {bad!r}"):
+            run(ops.state(), 1, drive=bad)
     for bad in (2, -1):
         with pytest.raises(mpcqp.MpcQpError, match="code -1: mpcqp_rollout_drive: drive is neither MPCQP_DRIVE_IDEAL nor MPCQP_DRIVE_LIMITED"):
             run(ops.state(), 1, drive=bad)
