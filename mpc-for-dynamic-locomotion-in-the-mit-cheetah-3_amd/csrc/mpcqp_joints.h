@@ -17,7 +17,7 @@
 
 namespace {
 
-// The geometry's structure is checked on the host (leg_ik_geometry in mpcqp_kernels.hip): ax = (s_x, 0, 0), ay = (0, s_y, 0),
+// The geometry's structure is checked on the host (leg_geometry in mpcqp_kernels.hip): ax = (s_x, 0, 0), ay = (0, s_y, 0),
 // hy[l] = (0, d_l, 0), kn = (0, 0, -l1), ft = (0, 0, -l2).
 //
 // One leg: R world <- torso (row-major), pw = foot - torso origin in world orientation, f the leg's force (world).  Writes q (HipX,

@@ -3,8 +3,10 @@
 // Replaces, for a batch of B independent robots, the solve the reference performs once per control tick:
 // CasADi Opti('conic') -> OSQP on the QP of src/mpc.py:58-173, filled at src/mpc.py:242-255, solved at :258.
 //
-// This translation unit is the C-ABI of include/mpcqp.h, mpcqp_plan.h, mpcqp_sim.h, mpcqp_model.h, mpcqp_joints.h, mpcqp_actuators.h and mpcqp_slip.h: the handle, its host helpers (I/O-type
-// dispatch, workspaces, the policy behind the configuration's defaults) and the extern "C" entry points.  The device code is in
+// This translation unit is the C-ABI of include/mpcqp.h, mpcqp_plan.h, mpcqp_sim.h, mpcqp_model.h, mpcqp_joints.h, mpcqp_actuators.h and mpcqp_slip.h,
+// in three parts: the handle; its host helpers in one anonymous namespace, in order of use (errors, I/O-type dispatch, the solve, workspaces,
+// the device guard and the launch tail `on_device`, grids, the policy behind the configuration's defaults, the engine's tables, the roll-out
+// loops, the leg rows, the row tables); one extern "C" block of entry points, each its own checks and its own launches.  The device code is in
 //   mpcqp_wrench.h       the engine: wrench-space (Woodbury) form, H = 2 alpha I + T'KT with a 6N x 6N system, one QP per wave
 //                        (horizon 10) or per four waves (horizon 20), fp32 or fp64 ADMM, fp64 active-set polish, ADMM-only mode
 //   mpcqp_stage.h        stage-wise (Riccati) form of the same engine for any other horizon up to 64 -- the reference's own N = 60
@@ -95,6 +97,12 @@ int fail(mpcqp_engine* e, int code, const char* what, hipError_t he = hipSuccess
     else snprintf(e->err, sizeof(e->err), "%s", what);
   }
   return code;
+}
+
+// MPCQP_EINVAL with the text "who: what" (what = head + tail), for the checks that several entry points share.
+int bad(mpcqp_engine* e, const char* who, const char* head, const char* tail = "") {
+  snprintf(e->err, sizeof(e->err), "%s: %s%s", who, head, tail);
+  return MPCQP_EINVAL;
 }
 
 // The launch check of the entry points that enqueue element-wise kernels.
@@ -217,22 +225,6 @@ hipError_t enqueue_solve(mpcqp_engine* h, int64_t B, const FastIn<T>& in, T* u, 
   return launch_wrench<T, 20>(h, B, in, u, X, status, iters, res, st);
 }
 
-// A solving entry point's batch against the model table, when one is set (include/mpcqp_model.h): row b belongs to batch slot b.
-int models_match(mpcqp_engine* h, int64_t B, const char* who) {
-  if (h->model_B == 0 || h->model_B == B) return MPCQP_OK;
-  snprintf(h->err, sizeof(h->err), "%s: batch size %lld, but the model table has %lld rows", who, (long long)B, (long long)h->model_B);
-  return MPCQP_EINVAL;
-}
-
-// The batch of a call that clamps joint torques against the actuator table, when one is set (include/mpcqp_actuators.h).
-int actuators_match(mpcqp_engine* h, int64_t B, const char* who) {
-  if (h->act_B == 0 || h->act_B == B) return MPCQP_OK;
-  snprintf(h->err, sizeof(h->err), "%s: batch size %lld, but the actuator table has %lld rows", who, (long long)B, (long long)h->act_B);
-  return MPCQP_EINVAL;
-}
-// The converted table, or null when none is set (launch_act)
-const double* act_table(const mpcqp_engine* h) { return h->act_B > 0 ? h->act_mem : nullptr; }
-
 // The event pair behind mpcqp_last_kernel_ms: an entry point records ev0 in front of its first launch and ev1 behind its last.
 int record(mpcqp_engine* h, hipEvent_t ev, hipStream_t st) {
   if (h->cfg.flags & MPCQP_FLAG_NO_TIMING) return MPCQP_OK;
@@ -240,6 +232,15 @@ int record(mpcqp_engine* h, hipEvent_t ev, hipStream_t st) {
   if (he != hipSuccess) return fail(h, MPCQP_EHIP, "hipEventRecord", he);
   if (ev == h->ev1) h->timed = true;
   return MPCQP_OK;
+}
+
+// ... around what a solving entry point enqueues: ev0, enqueue() -> hipError_t (`what` names it when it fails), ev1.
+template <typename F>
+int timed(mpcqp_engine* h, hipStream_t st, const char* what, F&& enqueue) {
+  if (const int rc = record(h, h->ev0, st)) return rc;
+  const hipError_t he = enqueue();
+  if (he != hipSuccess) return fail(h, MPCQP_EHIP, what, he);
+  return record(h, h->ev1, st);
 }
 
 // Grows a device buffer to `bytes` (contents are not kept), the first `zero` of them cleared; false when the allocation fails, and
@@ -254,6 +255,33 @@ bool grow(P*& buf, size_t bytes, size_t zero = 0) {
     (void)hipDeviceSynchronize();   // (the fill runs on the null stream: work on a non-blocking stream must not overtake it and read garbage)
   }
   buf = (P*)mem;
+  return true;
+}
+
+// The handle's two per-robot row tables (include/mpcqp_model.h, mpcqp_actuators.h) behind one view: the converted rows, how many of
+// them are set (0 = no table) and how many the buffer holds.  (A view, not a member: launch_wrench and launch_stage read model_B by name.)
+struct RowTable { double*& mem; int64_t& B; int64_t& cap; };
+RowTable models(mpcqp_engine* h) { return {h->model_mem, h->model_B, h->model_cap}; }
+RowTable actuators(mpcqp_engine* h) { return {h->act_mem, h->act_B, h->act_cap}; }
+// The converted actuator rows, or null when none are set (launch_act)
+const double* act_table(const mpcqp_engine* h) { return h->act_B > 0 ? h->act_mem : nullptr; }
+
+// The batch of a call that reads a table against the table, when one is set: row b belongs to batch slot b.
+int table_match(mpcqp_engine* h, const RowTable& t, const char* noun, int64_t B, const char* who) {
+  if (t.B == 0 || t.B == B) return MPCQP_OK;
+  snprintf(h->err, sizeof(h->err), "%s: batch size %lld, but the %s table has %lld rows", who, (long long)B, noun, (long long)t.B);
+  return MPCQP_EINVAL;
+}
+int models_match(mpcqp_engine* h, int64_t B, const char* who) { return table_match(h, models(h), "model", B, who); }
+int actuators_match(mpcqp_engine* h, int64_t B, const char* who) { return table_match(h, actuators(h), "actuator", B, who); }
+
+// Room for B rows of `width` doubles, once per size like the mpcqp_reserve workspace (grow waits for the device before it frees the old
+// buffer; when the allocation fails -- false -- the old table stays set).  After growth no table is set: the old rows are gone, and until
+// the caller's conversion kernel has run nothing may read the new buffer.
+bool table_reserve(const RowTable& t, int64_t B, int width) {
+  if (t.cap >= B) return true;
+  if (!grow(t.mem, (size_t)B * width * sizeof(double))) return false;
+  t.cap = B; t.B = 0;
   return true;
 }
 
@@ -349,6 +377,26 @@ struct DeviceGuard {
   }
   ~DeviceGuard() { if (switched) (void)hipSetDevice(prev); }
 };
+// ... as one statement of an entry point, behind its own checks: from here to the end of the scope the handle's device is current.
+#define GUARD(h) \
+  DeviceGuard guard((h)->cfg.device); \
+  if (guard.err != hipSuccess) return fail(h, MPCQP_EHIP, "hipSetDevice", guard.err)
+
+// The tail of every entry point that ends in element-wise launches: the guard, f(tag) with the I/O type (with_io) enqueues, and the
+// launch check under the name `what`.
+template <typename F>
+int on_device(mpcqp_engine* h, const char* what, F&& f) {
+  GUARD(h);
+  with_io(h, f);
+  return launched(h, what);
+}
+
+// Launch grids: `per` threads a block over n threads, and the three that recur -- one thread per leg of `rows` robots or log rows, one per
+// robot (the roll-outs' advance), one per tuple element (their expand).
+dim3 blocks(int64_t n, int per = 256) { return dim3((unsigned)((n + per - 1) / per)); }
+dim3 leg_grid(int64_t rows) { return blocks(4 * rows); }
+dim3 advance_grid(int64_t B) { return blocks(B); }
+dim3 expand_grid(int64_t B, int N) { return blocks(B * (int64_t)tuple_elems(N)); }
 
 // mpcqp_create, step 1: is this a configuration an engine can serve?
 bool config_valid(const MpcQpConfig& c) {
@@ -436,11 +484,26 @@ void resolve_policy(const MpcQpConfig& cfg, DevCfg& d, int& listed_max) {
   d.refine_admm = (!polish && cfg.precision == MPCQP_PREC_F64 && cfg.eps_abs < 1e-6) ? 1 : 0;
 }
 
-}  // namespace
+// A host array that owns its memory and reads as the pointer to it; null (no exception) when there is none.
+template <typename T>
+struct HostArray {
+  T* const p;
+  explicit HostArray(size_t n) : p(new (std::nothrow) T[n]) {}
+  HostArray(const HostArray&) = delete;
+  ~HostArray() { delete[] p; }
+  operator T*() const { return p; }
+};
+
+// A device buffer of `bytes` filled from the host.
+template <typename P>
+hipError_t upload(P*& dst, const void* src, size_t bytes) {
+  const hipError_t he = hipMalloc((void**)&dst, bytes);
+  return he == hipSuccess ? hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice) : he;
+}
 
 // Inverse of a small SPD matrix by Gauss-Jordan with partial pivoting (host, fp64); returns false when singular.
-static bool invert_small(int n, const double* A, double* Ai) {
-  double* M = new (std::nothrow) double[2 * n * n];
+bool invert_small(int n, const double* A, double* Ai) {
+  const HostArray<double> M((size_t)2 * n * n);
   if (!M) return false;
   for (int i = 0; i < n; ++i)
     for (int j = 0; j < n; ++j) { M[i * 2 * n + j] = A[i * n + j]; M[i * 2 * n + n + j] = i == j ? 1.0 : 0.0; }
@@ -459,7 +522,6 @@ static bool invert_small(int n, const double* A, double* Ai) {
     }
   }
   if (ok) for (int i = 0; i < n; ++i) for (int j = 0; j < n; ++j) Ai[i * n + j] = M[i * 2 * n + n + j];
-  delete[] M;
   return ok;
 }
 
@@ -474,7 +536,7 @@ static bool invert_small(int n, const double* A, double* Ai) {
 // Row r of the tile has its first K^-1 entry at tile column c0 = (r + 2 k) mod 6 with k = (gr - gc) mod 3, and a second one at
 // c0 + 6 when c0 < 2: slot [t][r] = S0[R][8 gc + c0], slot [t][8 + r] = S0[R][8 gc + c0 + 6] (0 when c0 >= 2).
 template <int N>
-static void lane_order_kinv(const double* Ki, double* lane) {
+void lane_order_kinv(const double* Ki, double* lane) {
   constexpr int G = WG<N>::G, NQ = WG<N>::NQ;
   auto S0 = [&](int R, int C) -> double {
     if (R >= NQ || C >= NQ) return R == C ? 1.0 : 0.0;
@@ -491,84 +553,348 @@ static void lane_order_kinv(const double* Ki, double* lane) {
 }
 
 template <int N>
-static int build_wrench_tables(mpcqp_engine* e) {
+int build_wrench_tables(mpcqp_engine* e) {
   const MpcQpConfig& c = e->cfg;
-  double* tab = new (std::nothrow) double[2 * N * N];   // c0 | c1
-  double* K = new (std::nothrow) double[6 * N * N];
-  double* Ki = new (std::nothrow) double[6 * N * N];
-  float* Ki32 = new (std::nothrow) float[6 * N * N];
-  constexpr int NLANE = 16 * WG<N>::NT;
-  double* Kl = new (std::nothrow) double[NLANE];
-  float* Kl32 = new (std::nothrow) float[NLANE];
+  constexpr int NK = 6 * N * N, NLANE = 16 * WG<N>::NT;
   // The device images of the two lane tables: [NT][16] values and, at horizon 10 (whose MIXED kernels read them), one record per lane
   // behind them -- the same sixteen values and the lane's eight row words of the tile build (mpcqp_rowtab.h)
   constexpr int NREC = N == 10 ? WG<N>::NT : 0;
   constexpr size_t L32 = sizeof(float) * NLANE + NREC * mpcqp_rowtab::record_bytes<float>();
   constexpr size_t L64 = sizeof(double) * NLANE + NREC * mpcqp_rowtab::record_bytes<double>();
-  unsigned* rows = new (std::nothrow) unsigned[mpcqp_rowtab::ROW_WORDS * WG<N>::NT];
-  unsigned char* img = new (std::nothrow) unsigned char[L32 + L64];
-  int rc = tab && K && Ki && Ki32 && Kl && Kl32 && rows && img ? MPCQP_OK : MPCQP_ENOMEM;
-  if (rc == MPCQP_OK) {
-    const double dl = c.delta, th = e->dev.theta;
-    for (int a = 0; a < N; ++a)
-      for (int bq = 0; bq < N; ++bq) {
-        const int mx = a > bq ? a : bq;
-        tab[a * N + bq] = dl * dl * (double)(N - mx);
-        double sacc = 0;
-        for (int k = mx + 1; k <= N; ++k) sacc += ((double)(k - 1 - a) + th) * ((double)(k - 1 - bq) + th);
-        tab[N * N + a * N + bq] = dl * dl * dl * dl * sacc;
-      }
-  }
-  for (int q = 0; q < 6 && rc == MPCQP_OK; ++q) {
-    for (int i = 0; i < N * N; ++i) K[q * N * N + i] = 2.0 * (c.w[q] * tab[N * N + i] + c.w[6 + q] * tab[i]);
-    if (!invert_small(N, K + q * N * N, Ki + q * N * N)) rc = MPCQP_EINVAL;
-  }
-  if (rc == MPCQP_OK && NREC > 0 && !mpcqp_rowtab::lane_order_rows(N, WG<N>::G, rows)) rc = MPCQP_EINVAL;   // (a rule of N alone: holds for N = 10)
-  if (rc == MPCQP_OK) {
-    for (int i = 0; i < 6 * N * N; ++i) Ki32[i] = (float)Ki[i];
-    lane_order_kinv<N>(Ki, Kl);
-    for (int i = 0; i < NLANE; ++i) Kl32[i] = (float)Kl[i];   // (the same rounding of the same fp64 entries as Ki32)
-    hipError_t he = hipMalloc((void**)&e->wr_K, sizeof(double) * 6 * N * N);
-    if (he == hipSuccess) he = hipMemcpy(e->wr_K, K, sizeof(double) * 6 * N * N, hipMemcpyHostToDevice);
-    if (he == hipSuccess) he = hipMalloc((void**)&e->wr_kinv32, sizeof(float) * 6 * N * N);
-    if (he == hipSuccess) he = hipMemcpy(e->wr_kinv32, Ki32, sizeof(float) * 6 * N * N, hipMemcpyHostToDevice);
-    if (he == hipSuccess) he = hipMalloc((void**)&e->wr_kinv64, sizeof(double) * 6 * N * N);
-    if (he == hipSuccess) he = hipMemcpy(e->wr_kinv64, Ki, sizeof(double) * 6 * N * N, hipMemcpyHostToDevice);
-    memcpy(img, Kl32, sizeof(float) * NLANE);
-    memcpy(img + L32, Kl, sizeof(double) * NLANE);
-    if (NREC > 0) {
-      mpcqp_rowtab::pack_records<float>(NREC, Kl32, rows, img + sizeof(float) * NLANE);
-      mpcqp_rowtab::pack_records<double>(NREC, Kl, rows, img + L32 + sizeof(double) * NLANE);
+  const HostArray<double> tab(2 * N * N), K(NK), Ki(NK), Kl(NLANE);   // tab: c0 | c1
+  const HostArray<float> Ki32(NK), Kl32(NLANE);
+  const HostArray<unsigned> rows(mpcqp_rowtab::ROW_WORDS * WG<N>::NT);
+  const HostArray<unsigned char> img(L32 + L64);
+  if (!(tab && K && Ki && Ki32 && Kl && Kl32 && rows && img)) return MPCQP_ENOMEM;
+  const double dl = c.delta, th = e->dev.theta;
+  for (int a = 0; a < N; ++a)
+    for (int bq = 0; bq < N; ++bq) {
+      const int mx = a > bq ? a : bq;
+      tab[a * N + bq] = dl * dl * (double)(N - mx);
+      double sacc = 0;
+      for (int k = mx + 1; k <= N; ++k) sacc += ((double)(k - 1 - a) + th) * ((double)(k - 1 - bq) + th);
+      tab[N * N + a * N + bq] = dl * dl * dl * dl * sacc;
     }
-    if (he == hipSuccess) he = hipMalloc((void**)&e->wr_klane32, L32);
-    if (he == hipSuccess) he = hipMemcpy(e->wr_klane32, img, L32, hipMemcpyHostToDevice);
-    if (he == hipSuccess) he = hipMalloc((void**)&e->wr_klane64, L64);
-    if (he == hipSuccess) he = hipMemcpy(e->wr_klane64, img + L32, L64, hipMemcpyHostToDevice);
-    if (he != hipSuccess) { (void)hipGetLastError(); rc = MPCQP_ENOMEM; }
+  for (int q = 0; q < 6; ++q) {
+    for (int i = 0; i < N * N; ++i) K[q * N * N + i] = 2.0 * (c.w[q] * tab[N * N + i] + c.w[6 + q] * tab[i]);
+    if (!invert_small(N, K + q * N * N, Ki + q * N * N)) return MPCQP_EINVAL;
   }
-  delete[] tab; delete[] K; delete[] Ki; delete[] Ki32; delete[] Kl; delete[] Kl32; delete[] rows; delete[] img;
-  return rc;
+  if (NREC > 0 && !mpcqp_rowtab::lane_order_rows(N, WG<N>::G, rows)) return MPCQP_EINVAL;   // (a rule of N alone: holds for N = 10)
+  for (int i = 0; i < NK; ++i) Ki32[i] = (float)Ki[i];
+  lane_order_kinv<N>(Ki, Kl);
+  for (int i = 0; i < NLANE; ++i) Kl32[i] = (float)Kl[i];   // (the same rounding of the same fp64 entries as Ki32)
+  memcpy(img, Kl32, sizeof(float) * NLANE);
+  memcpy(img + L32, Kl, sizeof(double) * NLANE);
+  if (NREC > 0) {
+    mpcqp_rowtab::pack_records<float>(NREC, Kl32, rows, img + sizeof(float) * NLANE);
+    mpcqp_rowtab::pack_records<double>(NREC, Kl, rows, img + L32 + sizeof(double) * NLANE);
+  }
+  hipError_t he = upload(e->wr_K, K, sizeof(double) * NK);
+  if (he == hipSuccess) he = upload(e->wr_kinv32, Ki32, sizeof(float) * NK);
+  if (he == hipSuccess) he = upload(e->wr_kinv64, Ki, sizeof(double) * NK);
+  if (he == hipSuccess) he = upload(e->wr_klane32, img, L32);
+  if (he == hipSuccess) he = upload(e->wr_klane64, img + L32, L64);
+  if (he == hipSuccess) return MPCQP_OK;
+  (void)hipGetLastError();   // (what has been allocated stays with the handle: mpcqp_create frees it)
+  return MPCQP_ENOMEM;
 }
 
-static void free_engine(mpcqp_engine* h) {
-  if (h->dcfg) (void)hipFree(h->dcfg);
-  if (h->order_mem) (void)hipFree(h->order_mem);
-  if (h->dual_mem) (void)hipFree(h->dual_mem);
-  if (h->model_mem) (void)hipFree(h->model_mem);
-  if (h->act_mem) (void)hipFree(h->act_mem);
-  if (h->gait_mem) (void)hipFree(h->gait_mem);
-  if (h->roll_mem) (void)hipFree(h->roll_mem);
-  if (h->plan_ws) (void)hipFree(h->plan_ws);
-  if (h->wr_K) (void)hipFree(h->wr_K);
-  if (h->wr_kinv32) (void)hipFree(h->wr_kinv32);
-  if (h->wr_kinv64) (void)hipFree(h->wr_kinv64);
-  if (h->wr_klane32) (void)hipFree(h->wr_klane32);
-  if (h->wr_klane64) (void)hipFree(h->wr_klane64);
-  if (h->stage_ws) (void)hipFree(h->stage_ws);
-  if (h->ev0) (void)hipEventDestroy(h->ev0);
-  if (h->ev1) (void)hipEventDestroy(h->ev1);
+void free_engine(mpcqp_engine* h) {
+  for (void* p : {(void*)h->dcfg, (void*)h->order_mem, (void*)h->dual_mem, (void*)h->model_mem, (void*)h->act_mem, h->gait_mem, h->roll_mem,
+                  (void*)h->plan_ws, (void*)h->wr_K, (void*)h->wr_kinv32, (void*)h->wr_kinv64, (void*)h->wr_klane32, (void*)h->wr_klane64,
+                  (void*)h->stage_ws})
+    if (p) (void)hipFree(p);
+  for (hipEvent_t ev : {h->ev0, h->ev1})
+    if (ev) (void)hipEventDestroy(ev);
   delete h;
 }
+
+// Roll-out arguments of the plant (mpcqp_rollout_plant); null for mpcqp_rollout, whose world step is x <- X[:,1].
+struct RolloutPlantArgs { const void* body; const void* push; const int32_t* push_ticks; int n; };
+
+PlantModel plant_model(const mpcqp_engine* h) {
+  return {h->cfg.m, 1.0 / h->cfg.Ibody_inv[0], 1.0 / h->cfg.Ibody_inv[1], 1.0 / h->cfg.Ibody_inv[2]};
+}
+
+// The roll-out loop behind mpcqp_rollout, mpcqp_rollout_plant and mpcqp_rollout_phase: workspace reserved once, then 3 launches per
+// tick on the caller's stream, no host synchronisation and no copies in between.  expand(tag, x, ref, w) launches the tick's expand
+// kernel into the tuple workspace w, advance(tag, x, ref, o, it) the advance kernel on the results o; tag carries the I/O type.
+// The caller has made its checks; the device guard is here.  (mpcqp_last_kernel_ms after a roll-out: all T ticks)
+template <typename Expand, typename Advance>
+int rollout_loop(mpcqp_handle h, const char* who, int64_t B, int32_t T, void* x, void* ref, const void* mu, void* stream, Expand&& expand,
+                 Advance&& advance) {
+  GUARD(h);
+  if (reserve_workspace(h, B) != MPCQP_OK || reserve_gait(h, B) != MPCQP_OK || reserve_roll(h, B) != MPCQP_OK) {
+    snprintf(h->err, sizeof(h->err), "%s: workspace allocation failed", who);
+    return MPCQP_ENOMEM;
+  }
+  const int N = h->cfg.N;
+  hipStream_t st = (hipStream_t)stream;
+  return timed(h, st, "roll-out kernel launch", [&] { return with_io(h, [&](auto tag) {
+    using TIO = decltype(tag);
+    const TupleWs<TIO> w = tuple_ws<TIO>(h->gait_mem, B, N);
+    const ResultWs<TIO> o = result_ws<TIO>(h->roll_mem, B, N);
+    const FastIn<TIO> in = tuple_in<TIO>(h, x, w.r, w.contact, w.xdes, mu, o.u);
+    TIO* xs = (TIO*)x;
+    TIO* rf = (TIO*)ref;
+    for (int it = 0; it < T; ++it) {
+      expand(tag, xs, rf, w);
+      hipError_t e = enqueue_solve<TIO>(h, B, in, o.u, o.X, o.status, o.iters, nullptr, st);
+      if (e != hipSuccess) return e;
+      advance(tag, xs, rf, o, it);
+      e = hipGetLastError();
+      if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+  }); });
+}
+
+// "Expand into the tuple workspace, then solve", behind the checks of mpcqp_solve_batch_gait_steps and mpcqp_solve_batch_phase: expand(tag, w)
+// launches the expansion into the engine's tuple workspace w, the normal solve runs on that tuple; the timing covers both.
+template <typename Expand>
+int solve_expanded(mpcqp_handle h, int64_t B, const void* x0, const void* mu, void* u_out, void* X_out, int32_t* status, int32_t* iters,
+                   float* res, hipStream_t st, const char* no_memory, const char* no_launch, Expand&& expand) {
+  GUARD(h);
+  if (reserve_workspace(h, B) != MPCQP_OK || reserve_gait(h, B) != MPCQP_OK) return fail(h, MPCQP_ENOMEM, no_memory);
+  return timed(h, st, no_launch, [&] { return with_io(h, [&](auto tag) {
+    using T = decltype(tag);
+    const TupleWs<T> w = tuple_ws<T>(h->gait_mem, B, (size_t)h->cfg.N);
+    expand(tag, w);
+    return enqueue_solve<T>(h, B, tuple_in<T>(h, x0, w.r, w.contact, w.xdes, mu, u_out), (T*)u_out, (T*)X_out, status, iters, res, st);
+  }); });
+}
+
+// The per-leg gait rows of include/mpcqp_plan.h as the phase kernels take them, and their expansion of B robots at (x, ref, tick) into w.
+template <typename T>
+PhaseRows<T> phase_rows(const void* feet, const int32_t* gait, const void* stand, const void* gain) {
+  return {(const T*)feet, gait, (const T*)stand, (const T*)gain};
+}
+template <typename T>
+void launch_phase_expand(const mpcqp_engine* h, int64_t B, hipStream_t st, const T* x, const T* ref, const PhaseRows<T>& ph, const int32_t* tick,
+                         const TupleWs<T>& w) {
+  hipLaunchKernelGGL((mpcqp_phase_expand_kernel<T>), expand_grid(B, h->cfg.N), dim3(256), 0, st, x, ref, ph, tick, h->cfg.delta, h->cfg.N, B, w.r,
+                     w.contact, w.xdes);
+}
+
+template <typename TIO>
+PlantIn<TIO> plant_in(const mpcqp_engine* h, const RolloutPlantArgs& p) {
+  return {(const TIO*)p.body, (const TIO*)p.push, p.push_ticks, plant_model(h), p.n, h->cfg.delta / p.n};
+}
+
+// The roll-out on a plan table: mpcqp_rollout (plant = null) and mpcqp_rollout_plant.
+int rollout_run(mpcqp_handle h, int64_t B, int32_t T, int32_t S, void* x, void* ref, const void* plan_pos, const uint8_t* plan_feet_id,
+                const int32_t* plan_meta, int32_t* tick, const void* mu, void* actual, void* desired, void* forces, int32_t* solved,
+                void* stream, const RolloutPlantArgs* plant) {
+  const int N = h->cfg.N;
+  const double d = h->cfg.delta;
+  const dim3 ge = expand_grid(B, N), ga = advance_grid(B), nt(256);
+  hipStream_t st = (hipStream_t)stream;
+  return rollout_loop(h, "mpcqp_rollout", B, T, x, ref, mu, stream,
+    [&](auto tag, auto* xs, auto* rf, const auto& w) {
+      using TIO = decltype(tag);
+      const RolloutPlan<TIO> plan = {(const TIO*)plan_pos, plan_feet_id, plan_meta};
+      hipLaunchKernelGGL((mpcqp_rollout_expand_kernel<TIO>), ge, nt, 0, st, xs, rf, plan, tick, d, N, (int)S, B, w.r, w.contact, w.xdes);
+    },
+    [&](auto tag, auto* xs, auto* rf, const auto& o, int it) {
+      using TIO = decltype(tag);
+      const RolloutPlan<TIO> plan = {(const TIO*)plan_pos, plan_feet_id, plan_meta};
+      if (plant) {
+        hipLaunchKernelGGL((mpcqp_rollout_advance_kernel<TIO, PlantIn<TIO>>), ga, nt, 0, st, xs, rf, plan, tick, plant_in<TIO>(h, *plant), o.u,
+                           o.status, d, N, B, (int)T, it, (int)S, (TIO*)actual, (TIO*)desired, (TIO*)forces, solved);
+      } else {
+        const ModelWorld<TIO> world = {o.X};
+        hipLaunchKernelGGL((mpcqp_rollout_advance_kernel<TIO, ModelWorld<TIO>>), ga, nt, 0, st, xs, rf, plan, tick, world, o.u, o.status, d, N, B,
+                           (int)T, it, (int)S, (TIO*)actual, (TIO*)desired, (TIO*)forces, solved);
+      }
+    });
+}
+
+// substeps of include/mpcqp_sim.h: 0 means the default, [1, 1000] as given; -1 for out of range
+int plant_substeps(int32_t substeps) {
+  if (substeps < 0 || substeps > PLANT_MAX_SUBSTEPS) return -1;
+  return substeps == 0 ? PLANT_DEFAULT_SUBSTEPS : substeps;
+}
+
+// leg_substeps / substeps of include/mpcqp_joints.h for a tick of `delta`: as given, or for 0 the default control period, the fewest
+// periods of at most SWING_H0 (the caller has checked the range [0, SWING_MAX_SUBSTEPS])
+int swing_substeps(double delta, int32_t substeps) {
+  if (substeps != 0) return substeps;
+  int n = (int)std::ceil(delta / SWING_H0);
+  while (n > 1 && delta / (n - 1) <= SWING_H0) --n;   // (delta / h0 a whole number up to rounding)
+  return n < 1 ? 1 : (n > SWING_MAX_SUBSTEPS ? SWING_MAX_SUBSTEPS : n);
+}
+
+// One launch, 256 threads a block, of a kernel whose last template argument is the actuator pack (act_rows, mpcqp_actuators.h): `k` = K<TIO>
+// on `args` without a table, `ka` = K<TIO, double> on (args..., the table) with one.  A handle with a table runs the instantiations that
+// read it; without one, the kernels are what they were.
+template <typename... P, typename... A>
+void launch_act(const mpcqp_engine* h, dim3 grid, hipStream_t st, void (*k)(P...), void (*ka)(P..., const double*), const A&... args) {
+  if (const double* act = act_table(h)) hipLaunchKernelGGL(ka, grid, dim3(256), 0, st, args..., act);
+  else hipLaunchKernelGGL(k, grid, dim3(256), 0, st, args...);
+}
+
+// The leg geometry of a call (null = the Lite3's) as the kernels take it, or the text of what does not fit.  closed_form: the geometry of
+// include/mpcqp_joints.h, a HipX joint about +-e_x followed by a planar chain about +-e_y; otherwise as mpcqp_leg_jacobians takes it, any
+// chain with non-zero joint axes.  g gets unit axes either way.
+int leg_geometry(mpcqp_handle h, const char* who, const MpcQpLegGeometry* geo, bool closed_form, LegGeoDev& g) {
+  MpcQpLegGeometry lite3;
+  if (!geo) { (void)mpcqp_default_leg_geometry(&lite3); geo = &lite3; }
+  if (geo->size != sizeof(MpcQpLegGeometry)) return bad(h, who, "geometry struct size mismatch");
+  memcpy(g.hx, geo->hip_x, sizeof(g.hx)); memcpy(g.hy, geo->hip_y, sizeof(g.hy));
+  memcpy(g.kn, geo->knee, sizeof(g.kn)); memcpy(g.ft, geo->foot, sizeof(g.ft));
+  if (!closed_form) {
+    for (int k = 0; k < 2; ++k) {   // unit axes (Rodrigues' formula assumes them)
+      const double* a = k ? geo->axis_y : geo->axis_x;
+      const double nrm = std::sqrt(a[0] * a[0] + a[1] * a[1] + a[2] * a[2]);
+      if (!(nrm > 0) || !std::isfinite(nrm)) return bad(h, who, "zero joint axis");
+      for (int c = 0; c < 3; ++c) (k ? g.ay : g.ax)[c] = a[c] / nrm;
+    }
+    return MPCQP_OK;
+  }
+  const char* field = nullptr;
+  const auto fin3 = [](const double* a) { return std::isfinite(a[0]) && std::isfinite(a[1]) && std::isfinite(a[2]); };
+  if (!fin3(geo->axis_x) || geo->axis_x[0] == 0.0 || geo->axis_x[1] != 0.0 || geo->axis_x[2] != 0.0) field = "axis_x is not +-e_x";
+  else if (!fin3(geo->axis_y) || geo->axis_y[1] == 0.0 || geo->axis_y[0] != 0.0 || geo->axis_y[2] != 0.0) field = "axis_y is not +-e_y";
+  else if (!fin3(geo->knee) || geo->knee[0] != 0.0 || geo->knee[1] != 0.0 || !(geo->knee[2] < 0.0)) field = "knee is not (0, 0, -l1), l1 > 0";
+  else if (!fin3(geo->foot) || geo->foot[0] != 0.0 || geo->foot[1] != 0.0 || !(geo->foot[2] < 0.0)) field = "foot is not (0, 0, -l2), l2 > 0";
+  for (int l = 0; l < 4 && !field; ++l) {
+    if (!fin3(geo->hip_y[l]) || geo->hip_y[l][0] != 0.0 || geo->hip_y[l][2] != 0.0) field = "hip_y is not (0, d, 0)";
+    else if (!fin3(geo->hip_x[l])) field = "hip_x is not finite";
+  }
+  if (field) return bad(h, who, "the closed form needs the Lite3's leg structure: ", field);
+  for (int c = 0; c < 3; ++c) { g.ax[c] = 0.0; g.ay[c] = 0.0; }
+  g.ax[0] = geo->axis_x[0] > 0.0 ? 1.0 : -1.0;
+  g.ay[1] = geo->axis_y[1] > 0.0 ? 1.0 : -1.0;
+  return MPCQP_OK;
+}
+
+// The inertial row of include/mpcqp_joints.h (null = the Lite3's): fills r or names the field that is not valid.
+int leg_inertia_row(mpcqp_handle h, const char* who, const MpcQpLegInertia* inr, LegInrDev& r) {
+  MpcQpLegInertia lite3;
+  if (!inr) { (void)mpcqp_default_leg_inertia(&lite3); inr = &lite3; }
+  if (inr->size != sizeof(MpcQpLegInertia)) return bad(h, who, "inertia struct size mismatch");
+  const char* field = nullptr;
+  const auto fin = [](const double* a, int n) { for (int i = 0; i < n; ++i) if (!std::isfinite(a[i])) return false; return true; };
+  if (!fin(&inr->mass[0][0], 12)) field = "mass is not finite";
+  else if (!fin(&inr->com[0][0][0], 36)) field = "com is not finite";
+  else if (!fin(&inr->inertia[0][0][0], 72)) field = "inertia is not finite";
+  else if (!fin(inr->q_min, 3)) field = "q_min is not finite";
+  else if (!fin(inr->q_max, 3)) field = "q_max is not finite";
+  else if (!fin(inr->qd_max, 3)) field = "qd_max is not finite";
+  else if (!fin(inr->tau_max, 3)) field = "tau_max is not finite";
+  else if (!std::isfinite(inr->gravity) || !(inr->gravity < 0.0)) field = "gravity is not negative and finite";
+  for (int i = 0; i < 12 && !field; ++i) if ((&inr->mass[0][0])[i] < 0.0) field = "mass is negative";
+  for (int j = 0; j < 3 && !field; ++j) {
+    if (inr->q_min[j] > inr->q_max[j]) field = "q_min > q_max";
+    else if (inr->qd_max[j] < 0.0) field = "qd_max is negative";
+    else if (inr->tau_max[j] < 0.0) field = "tau_max is negative";
+  }
+  if (field) return bad(h, who, "invalid leg inertia row: ", field);
+  LegLinkInr* link[3] = {&r.k0, &r.k1, &r.k2};
+  for (int l = 0; l < 4; ++l)
+    for (int k = 0; k < 3; ++k) {
+      link[k]->m[l] = inr->mass[l][k];
+      memcpy(link[k]->c[l], inr->com[l][k], sizeof(link[k]->c[l]));
+      memcpy(link[k]->I[l], inr->inertia[l][k], sizeof(link[k]->I[l]));
+    }
+  memcpy(r.lim.qmin, inr->q_min, sizeof(r.lim.qmin)); memcpy(r.lim.qmax, inr->q_max, sizeof(r.lim.qmax));
+  memcpy(r.lim.qdmax, inr->qd_max, sizeof(r.lim.qdmax)); memcpy(r.lim.taumax, inr->tau_max, sizeof(r.lim.taumax));
+  r.lim.g = inr->gravity;
+  return MPCQP_OK;
+}
+
+// The two rows of a leg call in the order every entry point checks them: the geometry, then the inertia.
+int leg_rows(mpcqp_handle h, const char* who, const MpcQpLegGeometry* geo, const MpcQpLegInertia* inr, bool closed_form, LegGeoDev& g,
+             LegInrDev& r) {
+  if (const int rc = leg_geometry(h, who, geo, closed_form, g)) return rc;
+  return leg_inertia_row(h, who, inr, r);
+}
+
+// What mpcqp_rollout_drive adds to mpcqp_rollout_legs: the drive mode, the ground's friction [B] or null, the commanded-force log or null.
+struct RolloutDriveArgs { int32_t drive; const void* ground; void* cmd_log; };
+// What mpcqp_rollout_slip adds to mpcqp_rollout_drive: the feet's effective mass [B], the slip state [B,4,2], its two logs or null.
+struct RolloutSlipArgs { const void* foot_mass; double* slip; double* slip_log; void* disp_log; };
+
+// mpcqp_rollout_legs (dr = null), mpcqp_rollout_drive and mpcqp_rollout_slip (sl, with dr): one argument check, one loop.
+int rollout_legs_run(mpcqp_handle h, const char* who, int64_t B, int32_t T, void* x, void* ref, void* feet, double* legs, const int32_t* gait,
+                     const void* stand, const void* gain, int32_t* tick, const void* mu, const void* body, const void* push,
+                     const int32_t* push_ticks, int32_t substeps, const void* step_height, const void* gains, int32_t leg_substeps,
+                     const MpcQpLegGeometry* geo, const MpcQpLegInertia* inr, int32_t land, void* actual, void* desired, void* forces,
+                     void* feet_log, uint8_t* contact_log, int32_t* solved, void* swing_log, void* q_log, void* qd_log, void* tau_log,
+                     void* foot_log, void* err_log, uint8_t* flag_log, void* miss_log, void* stream, const RolloutDriveArgs* dr,
+                     const RolloutSlipArgs* sl = nullptr) {
+  if (!h) return MPCQP_EINVAL;
+  if (B < 0 || B > 0x7fffffff || T < 0 || B * (int64_t)T > 0x7fffffff) return bad(h, who, "size out of range");
+  const int n = plant_substeps(substeps);
+  if (n < 0) return bad(h, who, "substeps out of range [0, 1000]");
+  if (leg_substeps < 0 || leg_substeps > SWING_MAX_SUBSTEPS) return bad(h, who, "leg_substeps out of range [0, 1000]");
+  if (land != MPCQP_LAND_RULE && land != MPCQP_LAND_ACTUAL) return bad(h, who, "land is neither MPCQP_LAND_RULE nor MPCQP_LAND_ACTUAL");
+  if (dr && dr->drive != MPCQP_DRIVE_IDEAL && dr->drive != MPCQP_DRIVE_LIMITED)
+    return bad(h, who, "drive is neither MPCQP_DRIVE_IDEAL nor MPCQP_DRIVE_LIMITED");
+  if (push && !push_ticks) return bad(h, who, "push without push_ticks");
+  if (B > 0 && (!x || !ref || !feet || !legs || !gait || !stand || !tick || !mu || !step_height)) return bad(h, who, "null buffer");
+  if (B > 0 && sl && (!dr->ground || !sl->foot_mass || !sl->slip)) return bad(h, who, "null buffer");
+  LegGeoDev g;
+  LegInrDev r;
+  if (const int rc = leg_rows(h, who, geo, inr, true, g, r)) return rc;
+  if (B == 0 || T == 0) return MPCQP_OK;
+  if (const int rc = models_match(h, B, who)) return rc;
+  if (const int rc = actuators_match(h, B, who)) return rc;
+  const int nl = swing_substeps(h->cfg.delta, leg_substeps);
+  const RolloutPlantArgs plant = {body, push, push ? push_ticks : nullptr, n};
+  const int N = h->cfg.N;
+  const double d = h->cfg.delta;
+  const dim3 ga = advance_grid(B), gl = leg_grid(B), nt(256);
+  hipStream_t st = (hipStream_t)stream;
+  // the roll-out loop of mpcqp_rollout_phase with the legs step in front of its advance and the landing behind it: 5 launches per tick.
+  // With a drive, the rule runs between the solve and the legs step and leaves the applied forces in a [B,12] side buffer, which the legs
+  // step and the advance read as a force buffer of horizon 1 (the solve's own buffer, its next warm start, is not altered); after the legs
+  // step the rule's torques and bits go into the stance rows of tau_log / flag_log: 6 launches, 7 with one of those two logs.
+  // With the slip rule in the drive's place the log step waits until after the landing and moves the feet in the same launch: 7.
+  return rollout_loop(h, who, B, T, x, ref, mu, stream,
+    [&](auto tag, auto* xs, auto* rf, const auto& w) {
+      using TIO = decltype(tag);
+      launch_phase_expand<TIO>(h, B, st, xs, rf, phase_rows<TIO>(feet, gait, stand, gain), tick, w);
+    },
+    [&](auto tag, auto* xs, auto* rf, const auto& o, int it) {
+      using TIO = decltype(tag);
+      const PhaseRows<TIO> ph = phase_rows<TIO>(feet, gait, stand, gain);
+      const LegRollOut<TIO> out = {(TIO*)swing_log, (TIO*)q_log, (TIO*)qd_log, (TIO*)tau_log, (TIO*)foot_log, (TIO*)err_log, flag_log};
+      const TIO* u = o.u;   // the forces the legs and the plant see, robot b's at u + b Nu 12
+      int Nu = N;
+      const DriveWs<TIO> dw = drive_ws<TIO>(h->roll_mem, B, N);
+      TIO* const rdisp = sl ? slip_ws<TIO>(h->roll_mem, B, N) : nullptr;
+      if (sl) {
+        TIO* cmd = dr->cmd_log ? (TIO*)dr->cmd_log + (size_t)it * 12 : nullptr;
+        double* slog = sl->slip_log ? sl->slip_log + (size_t)it * 8 : nullptr;
+        launch_act(h, gl, st, mpcqp_stance_slip_kernel<TIO>, mpcqp_stance_slip_kernel<TIO, double>, xs, o.u, (int64_t)N * 12,
+                   (const TIO*)feet, (const uint8_t*)nullptr, gait, tick, (const TIO*)dr->ground, (const TIO*)sl->foot_mass,
+                   (const double*)sl->slip, g, r.lim, (int)dr->drive, n, d / n, d, dw.f, dw.tau, dw.flag, cmd, (int64_t)T * 12, sl->slip, rdisp,
+                   slog, (int64_t)T * 8, B);
+        u = dw.f; Nu = 1;
+      } else if (dr) {
+        TIO* cmd = dr->cmd_log ? (TIO*)dr->cmd_log + (size_t)it * 12 : nullptr;
+        launch_act(h, gl, st, mpcqp_stance_drive_kernel<TIO>, mpcqp_stance_drive_kernel<TIO, double>, xs, o.u, (int64_t)N * 12,
+                   (const TIO*)feet, (const uint8_t*)nullptr, gait, tick, (const TIO*)dr->ground, g, r.lim, (int)dr->drive, dw.f, dw.tau, dw.flag,
+                   cmd, (int64_t)T * 12, B);
+        u = dw.f; Nu = 1;
+      }
+      launch_act(h, gl, st, mpcqp_legs_step_kernel<TIO>, mpcqp_legs_step_kernel<TIO, double>, xs, rf, ph, tick, u, (const TIO*)step_height,
+                 (const TIO*)gains, legs, plant_in<TIO>(h, plant), g, r.k0, r.k1, r.k2, r.lim, out, d, Nu, B, (int)T, it, nl, d / nl);
+      if (dr && !sl && (tau_log || flag_log))
+        hipLaunchKernelGGL((mpcqp_drive_log_kernel<TIO>), gl, nt, 0, st, gait, tick, dw.tau, dw.flag,
+                           (int)(dr->drive == MPCQP_DRIVE_IDEAL && !dr->ground), B, (int)T, it, (TIO*)tau_log, flag_log);
+      hipLaunchKernelGGL((mpcqp_phase_advance_kernel<TIO>), ga, nt, 0, st, xs, rf, (TIO*)feet, ph, tick, plant_in<TIO>(h, plant), u, o.status, d, Nu, B,
+                         (int)T, it, (TIO*)actual, (TIO*)desired, (TIO*)forces, (TIO*)feet_log, contact_log, solved);
+      hipLaunchKernelGGL((mpcqp_legs_land_kernel<TIO>), gl, nt, 0, st, xs, (TIO*)feet, gait, tick, legs, g, (int)land, B, (int)T, it,
+                         (TIO*)miss_log);
+      if (sl)
+        hipLaunchKernelGGL((mpcqp_slip_finish_kernel<TIO>), gl, nt, 0, st, gait, tick, (const TIO*)dw.tau, (const uint8_t*)dw.flag,
+                           (const TIO*)rdisp, B, (int)T, it, (TIO*)feet, sl->slip, (TIO*)tau_log, flag_log, (TIO*)sl->disp_log);
+    });
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -635,8 +961,7 @@ int mpcqp_create(const MpcQpConfig* cfg, mpcqp_handle* out) {
     if (oe != hipSuccess || per_cu < 1) { (void)hipGetLastError(); per_cu = 1; }
     e->stage_slots = per_cu * prop.multiProcessorCount;
   }
-  hipError_t he = hipMalloc((void**)&e->dcfg, sizeof(DevCfg));
-  if (he == hipSuccess) he = hipMemcpy(e->dcfg, &e->dev, sizeof(DevCfg), hipMemcpyHostToDevice);
+  hipError_t he = upload(e->dcfg, &e->dev, sizeof(DevCfg));
   if (he == hipSuccess) he = hipEventCreate(&e->ev0);
   if (he == hipSuccess) he = hipEventCreate(&e->ev1);
   if (he != hipSuccess) return reject(MPCQP_EHIP);
@@ -656,8 +981,7 @@ const char* mpcqp_last_error(mpcqp_handle h) { return h ? h->err : "null handle"
 int mpcqp_reserve(mpcqp_handle h, int64_t B) {
   if (!h) return MPCQP_EINVAL;
   if (B < 0 || B > 0x7fffffff) return fail(h, MPCQP_EINVAL, "mpcqp_reserve: batch size out of range");
-  DeviceGuard guard(h->cfg.device);
-  if (guard.err != hipSuccess) return fail(h, MPCQP_EHIP, "hipSetDevice", guard.err);
+  GUARD(h);
   const int rc = reserve_workspace(h, B);
   return rc == MPCQP_OK ? rc : fail(h, rc, "mpcqp_reserve: workspace allocation failed");
 }
@@ -669,19 +993,16 @@ int mpcqp_solve_batch(mpcqp_handle h, int64_t B, const void* x0, const void* r, 
   if (B > 0 && (!x0 || !r || !contact || !xdes || !mu || !u_out || !status || !iters))
     return fail(h, MPCQP_EINVAL, "mpcqp_solve_batch: null buffer");
   if (B > 0) if (const int rc = models_match(h, B, "mpcqp_solve_batch")) return rc;
-  DeviceGuard guard(h->cfg.device);
-  if (guard.err != hipSuccess) return fail(h, MPCQP_EHIP, "hipSetDevice", guard.err);
+  GUARD(h);
   if (reserve_workspace(h, B) != MPCQP_OK) return fail(h, MPCQP_ENOMEM, "mpcqp_solve_batch: workspace allocation failed");
   hipStream_t st = (hipStream_t)stream;
-  if (const int rc = record(h, h->ev0, st)) return rc;
-  if (B > 0) {
-    const hipError_t he = with_io(h, [&](auto tag) {
+  return timed(h, st, "kernel launch", [&] {
+    if (B == 0) return hipSuccess;
+    return with_io(h, [&](auto tag) {
       using T = decltype(tag);
       return enqueue_solve<T>(h, B, tuple_in<T>(h, x0, r, contact, xdes, mu, u_out), (T*)u_out, (T*)X_out, status, iters, res, st);
     });
-    if (he != hipSuccess) return fail(h, MPCQP_EHIP, "kernel launch", he);
-  }
-  return record(h, h->ev1, st);
+  });
 }
 
 int mpcqp_solve_batch_gait_steps(mpcqp_handle h, int64_t B, int32_t S, const void* x0, const void* ref, const void* feet0, const void* footholds,
@@ -694,26 +1015,13 @@ int mpcqp_solve_batch_gait_steps(mpcqp_handle h, int64_t B, int32_t S, const voi
     return fail(h, MPCQP_EINVAL, "mpcqp_solve_batch_gait_steps: null buffer");
   if (B == 0) return mpcqp_solve_batch(h, 0, x0, nullptr, nullptr, nullptr, mu, u_out, X_out, status, iters, res, stream);
   if (const int rc = models_match(h, B, "mpcqp_solve_batch_gait_steps")) return rc;
-  DeviceGuard guard(h->cfg.device);
-  if (guard.err != hipSuccess) return fail(h, MPCQP_EHIP, "hipSetDevice", guard.err);
-  if (reserve_workspace(h, B) != MPCQP_OK || reserve_gait(h, B) != MPCQP_OK)
-    return fail(h, MPCQP_ENOMEM, "mpcqp_solve_batch_gait_steps: workspace allocation failed");
-  // expand the descriptors on the device into the engine's tuple workspace, then the normal solve on that tuple; the timing
-  // covers both
-  const size_t N = (size_t)h->cfg.N;
-  const dim3 grid((unsigned)((B * (int64_t)tuple_elems(N) + 255) / 256));
   hipStream_t st = (hipStream_t)stream;
-  if (const int rc = record(h, h->ev0, st)) return rc;
-  const hipError_t he = with_io(h, [&](auto tag) {
+  return solve_expanded(h, B, x0, mu, u_out, X_out, status, iters, res, st, "mpcqp_solve_batch_gait_steps: workspace allocation failed",
+                        "gait expansion / solve kernel launch", [&](auto tag, const auto& w) {
     using T = decltype(tag);
-    const TupleWs<T> w = tuple_ws<T>(h->gait_mem, B, N);
-    hipLaunchKernelGGL((mpcqp_gait_expand_kernel<T>), grid, dim3(256), 0, st, gait_in<T>(x0, mu, ref, feet0, footholds, gait, feet_id),
-                       h->cfg.delta, (int)N, (int)S, B, w.r, w.contact, w.xdes);
-    const FastIn<T> in = tuple_in<T>(h, x0, w.r, w.contact, w.xdes, mu, u_out);
-    return enqueue_solve<T>(h, B, in, (T*)u_out, (T*)X_out, status, iters, res, st);
+    hipLaunchKernelGGL((mpcqp_gait_expand_kernel<T>), expand_grid(B, h->cfg.N), dim3(256), 0, st,
+                       gait_in<T>(x0, mu, ref, feet0, footholds, gait, feet_id), h->cfg.delta, h->cfg.N, (int)S, B, w.r, w.contact, w.xdes);
   });
-  if (he != hipSuccess) return fail(h, MPCQP_EHIP, "gait expansion / solve kernel launch", he);
-  return record(h, h->ev1, st);
 }
 
 int mpcqp_solve_batch_gait(mpcqp_handle h, int64_t B, const void* x0, const void* ref, const void* feet0, const void* footholds,
@@ -721,115 +1029,6 @@ int mpcqp_solve_batch_gait(mpcqp_handle h, int64_t B, const void* x0, const void
                            int32_t* status, int32_t* iters, float* res, void* stream) {
   return mpcqp_solve_batch_gait_steps(h, B, 2, x0, ref, feet0, footholds, gait, feet_id, mu, u_out, X_out, status, iters, res, stream);
 }
-
-extern "C++" {   // (inside the C-ABI block: the roll-out driver and its plant arguments are C++)
-namespace {
-
-// Roll-out arguments of the plant (mpcqp_rollout_plant); null for mpcqp_rollout, whose world step is x <- X[:,1].
-struct RolloutPlantArgs { const void* body; const void* push; const int32_t* push_ticks; int n; };
-
-PlantModel plant_model(const mpcqp_engine* h) {
-  return {h->cfg.m, 1.0 / h->cfg.Ibody_inv[0], 1.0 / h->cfg.Ibody_inv[1], 1.0 / h->cfg.Ibody_inv[2]};
-}
-
-// The roll-out loop behind mpcqp_rollout, mpcqp_rollout_plant and mpcqp_rollout_phase: workspace reserved once, then 3 launches per
-// tick on the caller's stream, no host synchronisation and no copies in between.  expand(tag, x, ref, w) launches the tick's expand
-// kernel into the tuple workspace w, advance(tag, x, ref, o, it) the advance kernel on the results o; tag carries the I/O type.
-// (mpcqp_last_kernel_ms after a roll-out: all T ticks)
-template <typename Expand, typename Advance>
-int rollout_loop(mpcqp_handle h, const char* who, int64_t B, int32_t T, void* x, void* ref, const void* mu, void* stream, Expand&& expand,
-                 Advance&& advance) {
-  if (reserve_workspace(h, B) != MPCQP_OK || reserve_gait(h, B) != MPCQP_OK || reserve_roll(h, B) != MPCQP_OK) {
-    snprintf(h->err, sizeof(h->err), "%s: workspace allocation failed", who);
-    return MPCQP_ENOMEM;
-  }
-  const int N = h->cfg.N;
-  hipStream_t st = (hipStream_t)stream;
-  if (const int rc = record(h, h->ev0, st)) return rc;
-  const hipError_t he = with_io(h, [&](auto tag) {
-    using TIO = decltype(tag);
-    const TupleWs<TIO> w = tuple_ws<TIO>(h->gait_mem, B, N);
-    const ResultWs<TIO> o = result_ws<TIO>(h->roll_mem, B, N);
-    const FastIn<TIO> in = tuple_in<TIO>(h, x, w.r, w.contact, w.xdes, mu, o.u);
-    TIO* xs = (TIO*)x;
-    TIO* rf = (TIO*)ref;
-    for (int it = 0; it < T; ++it) {
-      expand(tag, xs, rf, w);
-      hipError_t e = enqueue_solve<TIO>(h, B, in, o.u, o.X, o.status, o.iters, nullptr, st);
-      if (e != hipSuccess) return e;
-      advance(tag, xs, rf, o, it);
-      e = hipGetLastError();
-      if (e != hipSuccess) return e;
-    }
-    return hipSuccess;
-  });
-  if (he != hipSuccess) return fail(h, MPCQP_EHIP, "roll-out kernel launch", he);
-  return record(h, h->ev1, st);
-}
-
-// Launch grids of the roll-out's element-wise kernels: one thread per tuple element (expand), one per robot (advance).
-dim3 expand_grid(int64_t B, int N) { return dim3((unsigned)((B * (int64_t)tuple_elems(N) + 255) / 256)); }
-dim3 advance_grid(int64_t B) { return dim3((unsigned)((B + 255) / 256)); }
-
-template <typename TIO>
-PlantIn<TIO> plant_in(const mpcqp_engine* h, const RolloutPlantArgs& p) {
-  return {(const TIO*)p.body, (const TIO*)p.push, p.push_ticks, plant_model(h), p.n, h->cfg.delta / p.n};
-}
-
-// The roll-out on a plan table: mpcqp_rollout (plant = null) and mpcqp_rollout_plant.
-int rollout_run(mpcqp_handle h, int64_t B, int32_t T, int32_t S, void* x, void* ref, const void* plan_pos, const uint8_t* plan_feet_id,
-                const int32_t* plan_meta, int32_t* tick, const void* mu, void* actual, void* desired, void* forces, int32_t* solved,
-                void* stream, const RolloutPlantArgs* plant) {
-  const int N = h->cfg.N;
-  const double d = h->cfg.delta;
-  const dim3 ge = expand_grid(B, N), ga = advance_grid(B), nt(256);
-  hipStream_t st = (hipStream_t)stream;
-  return rollout_loop(h, "mpcqp_rollout", B, T, x, ref, mu, stream,
-    [&](auto tag, auto* xs, auto* rf, const auto& w) {
-      using TIO = decltype(tag);
-      const RolloutPlan<TIO> plan = {(const TIO*)plan_pos, plan_feet_id, plan_meta};
-      hipLaunchKernelGGL((mpcqp_rollout_expand_kernel<TIO>), ge, nt, 0, st, xs, rf, plan, tick, d, N, (int)S, B, w.r, w.contact, w.xdes);
-    },
-    [&](auto tag, auto* xs, auto* rf, const auto& o, int it) {
-      using TIO = decltype(tag);
-      const RolloutPlan<TIO> plan = {(const TIO*)plan_pos, plan_feet_id, plan_meta};
-      if (plant) {
-        hipLaunchKernelGGL((mpcqp_rollout_advance_kernel<TIO, PlantIn<TIO>>), ga, nt, 0, st, xs, rf, plan, tick, plant_in<TIO>(h, *plant), o.u,
-                           o.status, d, N, B, (int)T, it, (int)S, (TIO*)actual, (TIO*)desired, (TIO*)forces, solved);
-      } else {
-        const ModelWorld<TIO> world = {o.X};
-        hipLaunchKernelGGL((mpcqp_rollout_advance_kernel<TIO, ModelWorld<TIO>>), ga, nt, 0, st, xs, rf, plan, tick, world, o.u, o.status, d, N, B,
-                           (int)T, it, (int)S, (TIO*)actual, (TIO*)desired, (TIO*)forces, solved);
-      }
-    });
-}
-
-// substeps of include/mpcqp_sim.h: 0 means the default, [1, 1000] as given; -1 for out of range
-int plant_substeps(int32_t substeps) {
-  if (substeps < 0 || substeps > PLANT_MAX_SUBSTEPS) return -1;
-  return substeps == 0 ? PLANT_DEFAULT_SUBSTEPS : substeps;
-}
-
-// leg_substeps / substeps of include/mpcqp_joints.h for a tick of `delta`: as given, or for 0 the default control period, the fewest
-// periods of at most SWING_H0 (the caller has checked the range [0, SWING_MAX_SUBSTEPS])
-int swing_substeps(double delta, int32_t substeps) {
-  if (substeps != 0) return substeps;
-  int n = (int)std::ceil(delta / SWING_H0);
-  while (n > 1 && delta / (n - 1) <= SWING_H0) --n;   // (delta / h0 a whole number up to rounding)
-  return n < 1 ? 1 : (n > SWING_MAX_SUBSTEPS ? SWING_MAX_SUBSTEPS : n);
-}
-
-// One launch of a kernel whose last template argument is the actuator pack (act_rows, mpcqp_actuators.h): `k` = K<TIO> on `args` without
-// a table (act null), `ka` = K<TIO, double> on (args..., act) with one.  A handle with a table runs the instantiations that read it;
-// without one, the kernels are what they were.
-template <typename... P, typename... A>
-void launch_act(const double* act, dim3 grid, dim3 block, hipStream_t st, void (*k)(P...), void (*ka)(P..., const double*), const A&... args) {
-  if (act) hipLaunchKernelGGL(ka, grid, block, 0, st, args..., act);
-  else hipLaunchKernelGGL(k, grid, block, 0, st, args...);
-}
-
-}  // namespace
-}  // extern "C++"
 
 int mpcqp_rollout(mpcqp_handle h, int64_t B, int32_t T, int32_t S, void* x, void* ref, const void* plan_pos, const uint8_t* plan_feet_id,
                   const int32_t* plan_meta, int32_t* tick, const void* mu, void* actual, void* desired, void* forces, int32_t* solved,
@@ -839,8 +1038,6 @@ int mpcqp_rollout(mpcqp_handle h, int64_t B, int32_t T, int32_t S, void* x, void
   if (B > 0 && (!x || !ref || !plan_pos || !plan_feet_id || !plan_meta || !tick || !mu)) return fail(h, MPCQP_EINVAL, "mpcqp_rollout: null buffer");
   if (B == 0 || T == 0) return MPCQP_OK;
   if (const int rc = models_match(h, B, "mpcqp_rollout")) return rc;
-  DeviceGuard guard(h->cfg.device);
-  if (guard.err != hipSuccess) return fail(h, MPCQP_EHIP, "hipSetDevice", guard.err);
   return rollout_run(h, B, T, S, x, ref, plan_pos, plan_feet_id, plan_meta, tick, mu, actual, desired, forces, solved, stream, nullptr);
 }
 
@@ -857,8 +1054,6 @@ int mpcqp_rollout_plant(mpcqp_handle h, int64_t B, int32_t T, int32_t S, void* x
     return fail(h, MPCQP_EINVAL, "mpcqp_rollout_plant: null buffer");
   if (B == 0 || T == 0) return MPCQP_OK;
   if (const int rc = models_match(h, B, "mpcqp_rollout_plant")) return rc;
-  DeviceGuard guard(h->cfg.device);
-  if (guard.err != hipSuccess) return fail(h, MPCQP_EHIP, "hipSetDevice", guard.err);
   const RolloutPlantArgs plant = {body, push, push ? push_ticks : nullptr, n};
   return rollout_run(h, B, T, S, x, ref, plan_pos, plan_feet_id, plan_meta, tick, mu, actual, desired, forces, solved, stream, &plant);
 }
@@ -870,16 +1065,11 @@ int mpcqp_phase_expand(mpcqp_handle h, int64_t B, const void* x0, const void* re
   if (B > 0 && (!x0 || !ref || !feet || !gait || !tick || !stand || !r || !contact || !xdes))
     return fail(h, MPCQP_EINVAL, "mpcqp_phase_expand: null buffer");
   if (B == 0) return MPCQP_OK;
-  DeviceGuard guard(h->cfg.device);
-  if (guard.err != hipSuccess) return fail(h, MPCQP_EHIP, "hipSetDevice", guard.err);
-  const int N = h->cfg.N;
-  with_io(h, [&](auto tag) {
+  return on_device(h, "phase expansion kernel launch", [&](auto tag) {
     using T = decltype(tag);
-    const PhaseRows<T> ph = {(const T*)feet, gait, (const T*)stand, (const T*)gain};
-    hipLaunchKernelGGL((mpcqp_phase_expand_kernel<T>), expand_grid(B, N), dim3(256), 0, (hipStream_t)stream, (const T*)x0, (const T*)ref, ph,
-                       tick, h->cfg.delta, N, B, (T*)r, contact, (T*)xdes);
+    launch_phase_expand<T>(h, B, (hipStream_t)stream, (const T*)x0, (const T*)ref, phase_rows<T>(feet, gait, stand, gain), tick,
+                           {(T*)r, (T*)xdes, contact});
   });
-  return launched(h, "phase expansion kernel launch");
 }
 
 int mpcqp_solve_batch_phase(mpcqp_handle h, int64_t B, const void* x0, const void* ref, const void* feet, const int32_t* gait,
@@ -891,24 +1081,12 @@ int mpcqp_solve_batch_phase(mpcqp_handle h, int64_t B, const void* x0, const voi
     return fail(h, MPCQP_EINVAL, "mpcqp_solve_batch_phase: null buffer");
   if (B == 0) return mpcqp_solve_batch(h, 0, x0, nullptr, nullptr, nullptr, mu, u_out, X_out, status, iters, res, stream);
   if (const int rc = models_match(h, B, "mpcqp_solve_batch_phase")) return rc;
-  DeviceGuard guard(h->cfg.device);
-  if (guard.err != hipSuccess) return fail(h, MPCQP_EHIP, "hipSetDevice", guard.err);
-  if (reserve_workspace(h, B) != MPCQP_OK || reserve_gait(h, B) != MPCQP_OK)
-    return fail(h, MPCQP_ENOMEM, "mpcqp_solve_batch_phase: workspace allocation failed");
-  // as the gait entry point: the expansion into the engine's tuple workspace, then the normal solve on that tuple; the timing covers both
-  const int N = h->cfg.N;
   hipStream_t st = (hipStream_t)stream;
-  if (const int rc = record(h, h->ev0, st)) return rc;
-  const hipError_t he = with_io(h, [&](auto tag) {
+  return solve_expanded(h, B, x0, mu, u_out, X_out, status, iters, res, st, "mpcqp_solve_batch_phase: workspace allocation failed",
+                        "phase expansion / solve kernel launch", [&](auto tag, const auto& w) {
     using T = decltype(tag);
-    const TupleWs<T> w = tuple_ws<T>(h->gait_mem, B, N);
-    const PhaseRows<T> ph = {(const T*)feet, gait, (const T*)stand, (const T*)gain};
-    hipLaunchKernelGGL((mpcqp_phase_expand_kernel<T>), expand_grid(B, N), dim3(256), 0, st, (const T*)x0, (const T*)ref, ph, tick, h->cfg.delta,
-                       N, B, w.r, w.contact, w.xdes);
-    return enqueue_solve<T>(h, B, tuple_in<T>(h, x0, w.r, w.contact, w.xdes, mu, u_out), (T*)u_out, (T*)X_out, status, iters, res, st);
+    launch_phase_expand<T>(h, B, st, (const T*)x0, (const T*)ref, phase_rows<T>(feet, gait, stand, gain), tick, w);
   });
-  if (he != hipSuccess) return fail(h, MPCQP_EHIP, "phase expansion / solve kernel launch", he);
-  return record(h, h->ev1, st);
 }
 
 int mpcqp_rollout_phase(mpcqp_handle h, int64_t B, int32_t T, void* x, void* ref, void* feet, const int32_t* gait, const void* stand,
@@ -923,24 +1101,18 @@ int mpcqp_rollout_phase(mpcqp_handle h, int64_t B, int32_t T, void* x, void* ref
   if (B > 0 && (!x || !ref || !feet || !gait || !stand || !tick || !mu)) return fail(h, MPCQP_EINVAL, "mpcqp_rollout_phase: null buffer");
   if (B == 0 || T == 0) return MPCQP_OK;
   if (const int rc = models_match(h, B, "mpcqp_rollout_phase")) return rc;
-  DeviceGuard guard(h->cfg.device);
-  if (guard.err != hipSuccess) return fail(h, MPCQP_EHIP, "hipSetDevice", guard.err);
   const RolloutPlantArgs plant = {body, push, push ? push_ticks : nullptr, n};
-  const int N = h->cfg.N;
-  const double d = h->cfg.delta;
-  const dim3 ge = expand_grid(B, N), ga = advance_grid(B), nt(256);
   hipStream_t st = (hipStream_t)stream;
   return rollout_loop(h, "mpcqp_rollout_phase", B, T, x, ref, mu, stream,
     [&](auto tag, auto* xs, auto* rf, const auto& w) {
       using TIO = decltype(tag);
-      const PhaseRows<TIO> ph = {(const TIO*)feet, gait, (const TIO*)stand, (const TIO*)gain};
-      hipLaunchKernelGGL((mpcqp_phase_expand_kernel<TIO>), ge, nt, 0, st, xs, rf, ph, tick, d, N, B, w.r, w.contact, w.xdes);
+      launch_phase_expand<TIO>(h, B, st, xs, rf, phase_rows<TIO>(feet, gait, stand, gain), tick, w);
     },
     [&](auto tag, auto* xs, auto* rf, const auto& o, int it) {
       using TIO = decltype(tag);
-      const PhaseRows<TIO> ph = {(const TIO*)feet, gait, (const TIO*)stand, (const TIO*)gain};
-      hipLaunchKernelGGL((mpcqp_phase_advance_kernel<TIO>), ga, nt, 0, st, xs, rf, (TIO*)feet, ph, tick, plant_in<TIO>(h, plant), o.u, o.status, d, N, B,
-                         (int)T, it, (TIO*)actual, (TIO*)desired, (TIO*)forces, (TIO*)feet_log, contact_log, solved);
+      hipLaunchKernelGGL((mpcqp_phase_advance_kernel<TIO>), advance_grid(B), dim3(256), 0, st, xs, rf, (TIO*)feet, phase_rows<TIO>(feet, gait, stand, gain),
+                         tick, plant_in<TIO>(h, plant), o.u, o.status, h->cfg.delta, h->cfg.N, B, (int)T, it, (TIO*)actual, (TIO*)desired,
+                         (TIO*)forces, (TIO*)feet_log, contact_log, solved);
     });
 }
 
@@ -948,15 +1120,10 @@ int mpcqp_set_models(mpcqp_handle h, int64_t B, const double* model, void* strea
   if (!h) return MPCQP_EINVAL;
   if (B <= 0 || B > 0x7fffffff) return fail(h, MPCQP_EINVAL, "mpcqp_set_models: batch size out of range");
   if (!model) return fail(h, MPCQP_EINVAL, "mpcqp_set_models: null model table");
-  DeviceGuard guard(h->cfg.device);
-  if (guard.err != hipSuccess) return fail(h, MPCQP_EHIP, "hipSetDevice", guard.err);
-  if (h->model_cap < B) {   // once per size, like the mpcqp_reserve workspace (grow waits for the device before it frees the old
-                            // buffer; when the allocation fails the old table stays set)
-    if (!grow(h->model_mem, (size_t)B * MODEL_ROW * sizeof(double))) return fail(h, MPCQP_ENOMEM, "mpcqp_set_models: table allocation failed");
-    h->model_cap = B;
-    h->model_B = 0;   // (the device's pointer is the freed buffer until the kernel below has run: if its launch fails, no solve may read it)
-  }
-  hipLaunchKernelGGL(mpcqp_model_rows_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, (hipStream_t)stream, model, h->model_mem, B, h->dcfg);
+  GUARD(h);
+  // (after growth the device's pointer is the freed buffer until the kernel below has run: if its launch fails, no solve may read it)
+  if (!table_reserve(models(h), B, MODEL_ROW)) return fail(h, MPCQP_ENOMEM, "mpcqp_set_models: table allocation failed");
+  hipLaunchKernelGGL(mpcqp_model_rows_kernel, blocks(B), dim3(256), 0, (hipStream_t)stream, model, h->model_mem, B, h->dcfg);
   const int rc = launched(h, "model table kernel launch");
   h->model_B = rc == MPCQP_OK ? B : 0;
   return rc;
@@ -965,8 +1132,7 @@ int mpcqp_set_models(mpcqp_handle h, int64_t B, const double* model, void* strea
 int mpcqp_clear_models(mpcqp_handle h) {
   if (!h) return MPCQP_EINVAL;
   if (h->model_B == 0) return MPCQP_OK;
-  DeviceGuard guard(h->cfg.device);
-  if (guard.err != hipSuccess) return fail(h, MPCQP_EHIP, "hipSetDevice", guard.err);
+  GUARD(h);
   // No stream argument: the solves enqueued so far (on whatever stream) finish with the table, every later one starts without it.
   hipError_t he = hipDeviceSynchronize();
   if (he == hipSuccess) { hipLaunchKernelGGL(mpcqp_model_clear_kernel, dim3(1), dim3(1), 0, nullptr, h->dcfg); he = hipGetLastError(); }
@@ -981,14 +1147,9 @@ int mpcqp_set_actuators(mpcqp_handle h, int64_t B, const double* act, void* stre
   if (!h) return MPCQP_EINVAL;
   if (B <= 0 || B > 0x7fffffff) return fail(h, MPCQP_EINVAL, "mpcqp_set_actuators: batch size out of range");
   if (!act) return fail(h, MPCQP_EINVAL, "mpcqp_set_actuators: null actuator table");
-  DeviceGuard guard(h->cfg.device);
-  if (guard.err != hipSuccess) return fail(h, MPCQP_EHIP, "hipSetDevice", guard.err);
-  if (h->act_cap < B) {   // once per size, as mpcqp_set_models grows its table (grow waits for the device before it frees the old buffer)
-    if (!grow(h->act_mem, (size_t)B * ACT_ROW * sizeof(double))) return fail(h, MPCQP_ENOMEM, "mpcqp_set_actuators: table allocation failed");
-    h->act_cap = B;
-    h->act_B = 0;   // (the old rows are gone: if the launch below fails, no call may read the new buffer)
-  }
-  hipLaunchKernelGGL(mpcqp_actuator_rows_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, (hipStream_t)stream, act, h->act_mem, B);
+  GUARD(h);
+  if (!table_reserve(actuators(h), B, ACT_ROW)) return fail(h, MPCQP_ENOMEM, "mpcqp_set_actuators: table allocation failed");
+  hipLaunchKernelGGL(mpcqp_actuator_rows_kernel, blocks(B), dim3(256), 0, (hipStream_t)stream, act, h->act_mem, B);
   const int rc = launched(h, "actuator table kernel launch");
   h->act_B = rc == MPCQP_OK ? B : 0;
   return rc;
@@ -997,8 +1158,7 @@ int mpcqp_set_actuators(mpcqp_handle h, int64_t B, const double* act, void* stre
 int mpcqp_clear_actuators(mpcqp_handle h) {
   if (!h) return MPCQP_EINVAL;
   if (h->act_B == 0) return MPCQP_OK;
-  DeviceGuard guard(h->cfg.device);
-  if (guard.err != hipSuccess) return fail(h, MPCQP_EHIP, "hipSetDevice", guard.err);
+  GUARD(h);
   // No stream argument: the calls enqueued so far (on whatever stream) finish with the table, every later one runs without it.
   const hipError_t he = hipDeviceSynchronize();
   if (he != hipSuccess) return fail(h, MPCQP_EHIP, "mpcqp_clear_actuators", he);
@@ -1014,16 +1174,11 @@ int mpcqp_plant_step(mpcqp_handle h, int64_t B, const void* x, const void* f, co
   if (n < 0) return fail(h, MPCQP_EINVAL, "mpcqp_plant_step: substeps out of range [0, 1000]");
   if (B > 0 && (!x || !f || !feet || !contact || !x_out)) return fail(h, MPCQP_EINVAL, "mpcqp_plant_step: null buffer");
   if (B == 0) return MPCQP_OK;
-  DeviceGuard guard(h->cfg.device);
-  if (guard.err != hipSuccess) return fail(h, MPCQP_EHIP, "hipSetDevice", guard.err);
-  const dim3 grid((unsigned)((B + 255) / 256));
-  const double hstep = h->cfg.delta / n;
-  with_io(h, [&](auto tag) {
+  return on_device(h, "plant kernel launch", [&](auto tag) {
     using T = decltype(tag);
-    hipLaunchKernelGGL((mpcqp_plant_step_kernel<T>), grid, dim3(256), 0, (hipStream_t)stream, (const T*)x, (const T*)f, (const T*)feet,
-                       contact, (const T*)body, (const T*)wrench, plant_model(h), n, hstep, B, (T*)x_out);
+    hipLaunchKernelGGL((mpcqp_plant_step_kernel<T>), blocks(B), dim3(256), 0, (hipStream_t)stream, (const T*)x, (const T*)f, (const T*)feet,
+                       contact, (const T*)body, (const T*)wrench, plant_model(h), n, h->cfg.delta / n, B, (T*)x_out);
   });
-  return launched(h, "plant kernel launch");
 }
 
 int mpcqp_plan_footsteps(mpcqp_handle h, int64_t B, int32_t S, const void* feet0, const void* cmd, const int32_t* gait, void* plan_pos,
@@ -1033,8 +1188,7 @@ int mpcqp_plan_footsteps(mpcqp_handle h, int64_t B, int32_t S, const void* feet0
   if (B > 0 && (!feet0 || !cmd || !gait || !plan_pos || !plan_feet_id || !plan_meta))
     return fail(h, MPCQP_EINVAL, "mpcqp_plan_footsteps: null buffer");
   if (B == 0) return MPCQP_OK;
-  DeviceGuard guard(h->cfg.device);
-  if (guard.err != hipSuccess) return fail(h, MPCQP_EHIP, "hipSetDevice", guard.err);
+  GUARD(h);
   const int64_t rows = B * S;
   if (h->plan_cap < rows) {   // once per size; later calls at this size or smaller allocate nothing
     if (!grow(h->plan_ws, (size_t)rows * PLAN_WS * sizeof(double)))
@@ -1042,12 +1196,11 @@ int mpcqp_plan_footsteps(mpcqp_handle h, int64_t B, int32_t S, const void* feet0
     h->plan_cap = rows;
   }
   hipStream_t st = (hipStream_t)stream;
-  const dim3 g1((unsigned)((B + 63) / 64)), g2((unsigned)((rows + PLAN_BLOCK - 1) / PLAN_BLOCK));
   with_io(h, [&](auto tag) {
     using T = decltype(tag);
-    hipLaunchKernelGGL((mpcqp_plan_unicycle_kernel<T>), g1, dim3(64), 0, st, (const T*)feet0, (const T*)cmd, gait, h->cfg.delta, (int)S, B,
-                       h->plan_ws);
-    hipLaunchKernelGGL((mpcqp_plan_tables_kernel<T>), g2, dim3(PLAN_BLOCK), 0, st, (const T*)feet0, (const T*)cmd, gait,
+    hipLaunchKernelGGL((mpcqp_plan_unicycle_kernel<T>), blocks(B, 64), dim3(64), 0, st, (const T*)feet0, (const T*)cmd, gait, h->cfg.delta, (int)S,
+                       B, h->plan_ws);
+    hipLaunchKernelGGL((mpcqp_plan_tables_kernel<T>), blocks(rows, PLAN_BLOCK), dim3(PLAN_BLOCK), 0, st, (const T*)feet0, (const T*)cmd, gait,
                        (const double*)h->plan_ws, (int)S, B, (T*)plan_pos, plan_feet_id, plan_meta, (T*)plan_ang, (T*)plan_hip);
   });
   return launched(h, "footstep planner kernel launch");
@@ -1062,15 +1215,12 @@ int mpcqp_swing_trajectories(mpcqp_handle h, int64_t B, int32_t K, int32_t S, co
   if (B > 0 && K > 0 && (!plan_pos || !plan_feet_id || !plan_meta || !plan_ang || !tick || !step_height || !traj))
     return fail(h, MPCQP_EINVAL, "mpcqp_swing_trajectories: null buffer");
   if (B == 0 || K == 0) return MPCQP_OK;
-  DeviceGuard guard(h->cfg.device);
-  if (guard.err != hipSuccess) return fail(h, MPCQP_EHIP, "hipSetDevice", guard.err);
-  const dim3 grid((unsigned)((B * K * 4 + PLAN_BLOCK - 1) / PLAN_BLOCK));
-  with_io(h, [&](auto tag) {
+  return on_device(h, "swing trajectory kernel launch", [&](auto tag) {
     using T = decltype(tag);
-    hipLaunchKernelGGL((mpcqp_swing_kernel<T>), grid, dim3(PLAN_BLOCK), 0, (hipStream_t)stream, (const T*)plan_pos, plan_feet_id, plan_meta,
-                       (const T*)plan_ang, tick, (const T*)step_height, h->cfg.delta, (int)K, (int)S, B, (T*)traj, (T*)feet_des);
+    hipLaunchKernelGGL((mpcqp_swing_kernel<T>), blocks(B * K * 4, PLAN_BLOCK), dim3(PLAN_BLOCK), 0, (hipStream_t)stream, (const T*)plan_pos,
+                       plan_feet_id, plan_meta, (const T*)plan_ang, tick, (const T*)step_height, h->cfg.delta, (int)K, (int)S, B, (T*)traj,
+                       (T*)feet_des);
   });
-  return launched(h, "swing trajectory kernel launch");
 }
 
 int mpcqp_phase_swing(mpcqp_handle h, int64_t B, int32_t T, const void* actual, const void* desired, const void* feet_log, const int32_t* gait,
@@ -1081,16 +1231,12 @@ int mpcqp_phase_swing(mpcqp_handle h, int64_t B, int32_t T, const void* actual, 
   if (B > 0 && T > 0 && (!actual || !desired || !feet_log || !gait || !tick0 || !stand || !step_height || !swing))
     return fail(h, MPCQP_EINVAL, "mpcqp_phase_swing: null buffer");
   if (B == 0 || T == 0) return MPCQP_OK;
-  DeviceGuard guard(h->cfg.device);
-  if (guard.err != hipSuccess) return fail(h, MPCQP_EHIP, "hipSetDevice", guard.err);
-  const dim3 grid((unsigned)((4 * B * T + 255) / 256));
-  with_io(h, [&](auto tag) {
+  return on_device(h, "phase swing kernel launch", [&](auto tag) {
     using TIO = decltype(tag);
-    hipLaunchKernelGGL((mpcqp_phase_swing_kernel<TIO>), grid, dim3(256), 0, (hipStream_t)stream, (const TIO*)actual, (const TIO*)desired,
+    hipLaunchKernelGGL((mpcqp_phase_swing_kernel<TIO>), leg_grid(B * T), dim3(256), 0, (hipStream_t)stream, (const TIO*)actual, (const TIO*)desired,
                        (const TIO*)feet_log, gait, tick0, (const TIO*)stand, (const TIO*)gain, (const TIO*)step_height, h->cfg.delta, (int)T, B,
                        (TIO*)swing, (TIO*)feet_des);
   });
-  return launched(h, "phase swing kernel launch");
 }
 
 int mpcqp_torque_map(mpcqp_handle h, int64_t B, const void* u, const void* jac, void* tau, void* stream) {
@@ -1098,14 +1244,10 @@ int mpcqp_torque_map(mpcqp_handle h, int64_t B, const void* u, const void* jac, 
   if (B < 0 || B > 0x1fffffff) return fail(h, MPCQP_EINVAL, "mpcqp_torque_map: batch size out of range");
   if (B > 0 && (!u || !jac || !tau)) return fail(h, MPCQP_EINVAL, "mpcqp_torque_map: null buffer");
   if (B == 0) return MPCQP_OK;
-  DeviceGuard guard(h->cfg.device);
-  if (guard.err != hipSuccess) return fail(h, MPCQP_EHIP, "hipSetDevice", guard.err);
-  const dim3 grid((unsigned)((4 * B + 255) / 256));
-  with_io(h, [&](auto tag) {
+  return on_device(h, "torque kernel launch", [&](auto tag) {
     using T = decltype(tag);
-    hipLaunchKernelGGL((mpcqp_torque_kernel<T>), grid, dim3(256), 0, (hipStream_t)stream, (const T*)u, (const T*)jac, (T*)tau, B, h->cfg.N);
+    hipLaunchKernelGGL((mpcqp_torque_kernel<T>), leg_grid(B), dim3(256), 0, (hipStream_t)stream, (const T*)u, (const T*)jac, (T*)tau, B, h->cfg.N);
   });
-  return launched(h, "torque kernel launch");
 }
 
 int mpcqp_default_leg_geometry(MpcQpLegGeometry* g) {   // lite3_urdf/urdf/Lite3.urdf:44-124 (joint origins and axes; data)
@@ -1129,67 +1271,15 @@ int mpcqp_leg_jacobians(mpcqp_handle h, int64_t B, const void* q, const void* ro
   if (!h) return MPCQP_EINVAL;
   if (B < 0 || B > 0x1fffffff) return fail(h, MPCQP_EINVAL, "mpcqp_leg_jacobians: batch size out of range");
   if (B > 0 && (!q || !jac)) return fail(h, MPCQP_EINVAL, "mpcqp_leg_jacobians: null buffer");
-  MpcQpLegGeometry lite3;
-  if (!geo) { (void)mpcqp_default_leg_geometry(&lite3); geo = &lite3; }
-  if (geo->size != sizeof(MpcQpLegGeometry)) return fail(h, MPCQP_EINVAL, "mpcqp_leg_jacobians: geometry struct size mismatch");
   LegGeoDev g;
-  memcpy(g.hx, geo->hip_x, sizeof(g.hx)); memcpy(g.hy, geo->hip_y, sizeof(g.hy));
-  memcpy(g.kn, geo->knee, sizeof(g.kn)); memcpy(g.ft, geo->foot, sizeof(g.ft));
-  for (int k = 0; k < 2; ++k) {   // unit axes (Rodrigues' formula assumes them)
-    const double* a = k ? geo->axis_y : geo->axis_x;
-    const double nrm = std::sqrt(a[0] * a[0] + a[1] * a[1] + a[2] * a[2]);
-    if (!(nrm > 0) || !std::isfinite(nrm)) return fail(h, MPCQP_EINVAL, "mpcqp_leg_jacobians: zero joint axis");
-    for (int c = 0; c < 3; ++c) (k ? g.ay : g.ax)[c] = a[c] / nrm;
-  }
+  if (const int rc = leg_geometry(h, "mpcqp_leg_jacobians", geo, false, g)) return rc;
   if (B == 0) return MPCQP_OK;
-  DeviceGuard guard(h->cfg.device);
-  if (guard.err != hipSuccess) return fail(h, MPCQP_EHIP, "hipSetDevice", guard.err);
-  const dim3 grid((unsigned)((4 * B + 255) / 256));
-  with_io(h, [&](auto tag) {
+  return on_device(h, "leg Jacobian kernel launch", [&](auto tag) {
     using T = decltype(tag);
-    hipLaunchKernelGGL((mpcqp_leg_jacobian_kernel<T>), grid, dim3(256), 0, (hipStream_t)stream, (const T*)q, (const T*)rot, g, (T*)jac,
+    hipLaunchKernelGGL((mpcqp_leg_jacobian_kernel<T>), leg_grid(B), dim3(256), 0, (hipStream_t)stream, (const T*)q, (const T*)rot, g, (T*)jac,
                        (T*)foot, B);
   });
-  return launched(h, "leg Jacobian kernel launch");
 }
-
-extern "C++" {
-namespace {
-
-// The geometry of include/mpcqp_joints.h: the closed form needs a HipX joint about +-e_x followed by a planar chain about +-e_y.
-// Fills g (unit axes) or names the field that does not fit.
-int leg_ik_geometry(mpcqp_handle h, const char* who, const MpcQpLegGeometry* geo, LegGeoDev& g) {
-  MpcQpLegGeometry lite3;
-  if (!geo) { (void)mpcqp_default_leg_geometry(&lite3); geo = &lite3; }
-  char msg[160];
-  const char* bad = nullptr;
-  if (geo->size != sizeof(MpcQpLegGeometry)) {
-    snprintf(msg, sizeof(msg), "%s: geometry struct size mismatch", who);
-    return fail(h, MPCQP_EINVAL, msg);
-  }
-  const auto fin3 = [](const double* a) { return std::isfinite(a[0]) && std::isfinite(a[1]) && std::isfinite(a[2]); };
-  if (!fin3(geo->axis_x) || geo->axis_x[0] == 0.0 || geo->axis_x[1] != 0.0 || geo->axis_x[2] != 0.0) bad = "axis_x is not +-e_x";
-  else if (!fin3(geo->axis_y) || geo->axis_y[1] == 0.0 || geo->axis_y[0] != 0.0 || geo->axis_y[2] != 0.0) bad = "axis_y is not +-e_y";
-  else if (!fin3(geo->knee) || geo->knee[0] != 0.0 || geo->knee[1] != 0.0 || !(geo->knee[2] < 0.0)) bad = "knee is not (0, 0, -l1), l1 > 0";
-  else if (!fin3(geo->foot) || geo->foot[0] != 0.0 || geo->foot[1] != 0.0 || !(geo->foot[2] < 0.0)) bad = "foot is not (0, 0, -l2), l2 > 0";
-  for (int l = 0; l < 4 && !bad; ++l) {
-    if (!fin3(geo->hip_y[l]) || geo->hip_y[l][0] != 0.0 || geo->hip_y[l][2] != 0.0) bad = "hip_y is not (0, d, 0)";
-    else if (!fin3(geo->hip_x[l])) bad = "hip_x is not finite";
-  }
-  if (bad) {
-    snprintf(msg, sizeof(msg), "%s: the closed form needs the Lite3's leg structure: %s", who, bad);
-    return fail(h, MPCQP_EINVAL, msg);
-  }
-  memcpy(g.hx, geo->hip_x, sizeof(g.hx)); memcpy(g.hy, geo->hip_y, sizeof(g.hy));
-  memcpy(g.kn, geo->knee, sizeof(g.kn)); memcpy(g.ft, geo->foot, sizeof(g.ft));
-  for (int c = 0; c < 3; ++c) { g.ax[c] = 0.0; g.ay[c] = 0.0; }
-  g.ax[0] = geo->axis_x[0] > 0.0 ? 1.0 : -1.0;
-  g.ay[1] = geo->axis_y[1] > 0.0 ? 1.0 : -1.0;
-  return MPCQP_OK;
-}
-
-}  // namespace
-}  // extern "C++"
 
 int mpcqp_leg_ik(mpcqp_handle h, int64_t B, const void* foot, const void* rot, const void* origin, const MpcQpLegGeometry* geo, void* q,
                  uint8_t* reach, void* stream) {
@@ -1198,17 +1288,13 @@ int mpcqp_leg_ik(mpcqp_handle h, int64_t B, const void* foot, const void* rot, c
   if (B > 0 && !foot) return fail(h, MPCQP_EINVAL, "mpcqp_leg_ik: null foot buffer");
   if (B > 0 && !q) return fail(h, MPCQP_EINVAL, "mpcqp_leg_ik: null q buffer");
   LegGeoDev g;
-  if (const int rc = leg_ik_geometry(h, "mpcqp_leg_ik", geo, g)) return rc;
+  if (const int rc = leg_geometry(h, "mpcqp_leg_ik", geo, true, g)) return rc;
   if (B == 0) return MPCQP_OK;
-  DeviceGuard guard(h->cfg.device);
-  if (guard.err != hipSuccess) return fail(h, MPCQP_EHIP, "hipSetDevice", guard.err);
-  const dim3 grid((unsigned)((4 * B + 255) / 256));
-  with_io(h, [&](auto tag) {
+  return on_device(h, "leg inverse kinematics kernel launch", [&](auto tag) {
     using T = decltype(tag);
-    hipLaunchKernelGGL((mpcqp_leg_ik_kernel<T>), grid, dim3(256), 0, (hipStream_t)stream, (const T*)foot, (const T*)rot, (const T*)origin, g,
-                       (T*)q, reach, B);
+    hipLaunchKernelGGL((mpcqp_leg_ik_kernel<T>), leg_grid(B), dim3(256), 0, (hipStream_t)stream, (const T*)foot, (const T*)rot, (const T*)origin,
+                       g, (T*)q, reach, B);
   });
-  return launched(h, "leg inverse kinematics kernel launch");
 }
 
 int mpcqp_joint_log(mpcqp_handle h, int64_t B, int32_t T, const void* actual, const void* forces, const void* feet,
@@ -1218,18 +1304,14 @@ int mpcqp_joint_log(mpcqp_handle h, int64_t B, int32_t T, const void* actual, co
   if (!q && !tau && !reach) return fail(h, MPCQP_EINVAL, "mpcqp_joint_log: no output buffer (q, tau and reach are all null)");
   if (B > 0 && T > 0 && (!actual || !forces || !feet)) return fail(h, MPCQP_EINVAL, "mpcqp_joint_log: null buffer");
   LegGeoDev g;
-  if (const int rc = leg_ik_geometry(h, "mpcqp_joint_log", geo, g)) return rc;
+  if (const int rc = leg_geometry(h, "mpcqp_joint_log", geo, true, g)) return rc;
   if (B == 0 || T == 0) return MPCQP_OK;
-  DeviceGuard guard(h->cfg.device);
-  if (guard.err != hipSuccess) return fail(h, MPCQP_EHIP, "hipSetDevice", guard.err);
   const int64_t rows = B * T;
-  const dim3 grid((unsigned)((4 * rows + 255) / 256));
-  with_io(h, [&](auto tag) {
+  return on_device(h, "joint log kernel launch", [&](auto tag) {
     using TIO = decltype(tag);
-    hipLaunchKernelGGL((mpcqp_joint_log_kernel<TIO>), grid, dim3(256), 0, (hipStream_t)stream, (const TIO*)actual, (const TIO*)forces,
+    hipLaunchKernelGGL((mpcqp_joint_log_kernel<TIO>), leg_grid(rows), dim3(256), 0, (hipStream_t)stream, (const TIO*)actual, (const TIO*)forces,
                        (const TIO*)feet, g, (TIO*)q, (TIO*)tau, reach, rows);
   });
-  return launched(h, "joint log kernel launch");
 }
 
 int mpcqp_joint_rates(mpcqp_handle h, int64_t B, int32_t T, const void* actual, const void* forces, const void* feet, const void* foot_vel,
@@ -1240,18 +1322,14 @@ int mpcqp_joint_rates(mpcqp_handle h, int64_t B, int32_t T, const void* actual, 
     return fail(h, MPCQP_EINVAL, "mpcqp_joint_rates: no output buffer (q, qd, tau, power and reach are all null)");
   if (B > 0 && T > 0 && (!actual || !forces || !feet)) return fail(h, MPCQP_EINVAL, "mpcqp_joint_rates: null buffer");
   LegGeoDev g;
-  if (const int rc = leg_ik_geometry(h, "mpcqp_joint_rates", geo, g)) return rc;
+  if (const int rc = leg_geometry(h, "mpcqp_joint_rates", geo, true, g)) return rc;
   if (B == 0 || T == 0) return MPCQP_OK;
-  DeviceGuard guard(h->cfg.device);
-  if (guard.err != hipSuccess) return fail(h, MPCQP_EHIP, "hipSetDevice", guard.err);
   const int64_t rows = B * T;
-  const dim3 grid((unsigned)((4 * rows + 255) / 256));
-  with_io(h, [&](auto tag) {
+  return on_device(h, "joint rates kernel launch", [&](auto tag) {
     using TIO = decltype(tag);
-    hipLaunchKernelGGL((mpcqp_joint_rates_kernel<TIO>), grid, dim3(256), 0, (hipStream_t)stream, (const TIO*)actual, (const TIO*)forces,
+    hipLaunchKernelGGL((mpcqp_joint_rates_kernel<TIO>), leg_grid(rows), dim3(256), 0, (hipStream_t)stream, (const TIO*)actual, (const TIO*)forces,
                        (const TIO*)feet, (const TIO*)foot_vel, g, (TIO*)q, (TIO*)qd, (TIO*)tau, (TIO*)power, reach, rows);
   });
-  return launched(h, "joint rates kernel launch");
 }
 
 int mpcqp_default_leg_inertia(MpcQpLegInertia* r) {   // lite3_urdf/urdf/Lite3.urdf: <inertial> of the HIP / THIGH / SHANK / FOOT links, joint <limit> rows (data)
@@ -1297,77 +1375,6 @@ int mpcqp_default_leg_inertia(MpcQpLegInertia* r) {   // lite3_urdf/urdf/Lite3.u
   return MPCQP_OK;
 }
 
-extern "C++" {
-namespace {
-
-// The geometry as mpcqp_leg_jacobians takes it: any chain with non-zero joint axes (normalised here).
-int leg_fk_geometry(mpcqp_handle h, const char* who, const MpcQpLegGeometry* geo, LegGeoDev& g) {
-  MpcQpLegGeometry lite3;
-  if (!geo) { (void)mpcqp_default_leg_geometry(&lite3); geo = &lite3; }
-  char msg[160];
-  if (geo->size != sizeof(MpcQpLegGeometry)) {
-    snprintf(msg, sizeof(msg), "%s: geometry struct size mismatch", who);
-    return fail(h, MPCQP_EINVAL, msg);
-  }
-  memcpy(g.hx, geo->hip_x, sizeof(g.hx)); memcpy(g.hy, geo->hip_y, sizeof(g.hy));
-  memcpy(g.kn, geo->knee, sizeof(g.kn)); memcpy(g.ft, geo->foot, sizeof(g.ft));
-  for (int k = 0; k < 2; ++k) {   // unit axes (Rodrigues' formula assumes them)
-    const double* a = k ? geo->axis_y : geo->axis_x;
-    const double nrm = std::sqrt(a[0] * a[0] + a[1] * a[1] + a[2] * a[2]);
-    if (!(nrm > 0) || !std::isfinite(nrm)) {
-      snprintf(msg, sizeof(msg), "%s: zero joint axis", who);
-      return fail(h, MPCQP_EINVAL, msg);
-    }
-    for (int c = 0; c < 3; ++c) (k ? g.ay : g.ax)[c] = a[c] / nrm;
-  }
-  return MPCQP_OK;
-}
-
-// The inertial row of include/mpcqp_joints.h: fills r or names the field that is not valid.
-int leg_inertia_row(mpcqp_handle h, const char* who, const MpcQpLegInertia* inr, LegInrDev& r) {
-  MpcQpLegInertia lite3;
-  if (!inr) { (void)mpcqp_default_leg_inertia(&lite3); inr = &lite3; }
-  char msg[160];
-  const char* bad = nullptr;
-  if (inr->size != sizeof(MpcQpLegInertia)) {
-    snprintf(msg, sizeof(msg), "%s: inertia struct size mismatch", who);
-    return fail(h, MPCQP_EINVAL, msg);
-  }
-  const auto fin = [](const double* a, int n) { for (int i = 0; i < n; ++i) if (!std::isfinite(a[i])) return false; return true; };
-  if (!fin(&inr->mass[0][0], 12)) bad = "mass is not finite";
-  else if (!fin(&inr->com[0][0][0], 36)) bad = "com is not finite";
-  else if (!fin(&inr->inertia[0][0][0], 72)) bad = "inertia is not finite";
-  else if (!fin(inr->q_min, 3)) bad = "q_min is not finite";
-  else if (!fin(inr->q_max, 3)) bad = "q_max is not finite";
-  else if (!fin(inr->qd_max, 3)) bad = "qd_max is not finite";
-  else if (!fin(inr->tau_max, 3)) bad = "tau_max is not finite";
-  else if (!std::isfinite(inr->gravity) || !(inr->gravity < 0.0)) bad = "gravity is not negative and finite";
-  for (int i = 0; i < 12 && !bad; ++i) if ((&inr->mass[0][0])[i] < 0.0) bad = "mass is negative";
-  for (int j = 0; j < 3 && !bad; ++j) {
-    if (inr->q_min[j] > inr->q_max[j]) bad = "q_min > q_max";
-    else if (inr->qd_max[j] < 0.0) bad = "qd_max is negative";
-    else if (inr->tau_max[j] < 0.0) bad = "tau_max is negative";
-  }
-  if (bad) {
-    snprintf(msg, sizeof(msg), "%s: invalid leg inertia row: %s", who, bad);
-    return fail(h, MPCQP_EINVAL, msg);
-  }
-  LegLinkInr* link[3] = {&r.k0, &r.k1, &r.k2};
-  for (int l = 0; l < 4; ++l)
-    for (int k = 0; k < 3; ++k) {
-      link[k]->m[l] = inr->mass[l][k];
-      memcpy(link[k]->c[l], inr->com[l][k], sizeof(link[k]->c[l]));
-      memcpy(link[k]->I[l], inr->inertia[l][k], sizeof(link[k]->I[l]));
-    }
-  memcpy(r.lim.qmin, inr->q_min, sizeof(r.lim.qmin)); memcpy(r.lim.qmax, inr->q_max, sizeof(r.lim.qmax));
-  memcpy(r.lim.qdmax, inr->qd_max, sizeof(r.lim.qdmax)); memcpy(r.lim.taumax, inr->tau_max, sizeof(r.lim.taumax));
-  r.lim.g = inr->gravity;
-  return MPCQP_OK;
-}
-
-}  // namespace
-}  // extern "C++"
-
 int mpcqp_leg_dynamics(mpcqp_handle h, int64_t B, const void* q, const void* qd, const void* qdd, const void* rot, const void* base,
                        const MpcQpLegGeometry* geo, const MpcQpLegInertia* inr, void* tau, void* mass, void* bias, void* stream) {
   if (!h) return MPCQP_EINVAL;
@@ -1375,19 +1382,14 @@ int mpcqp_leg_dynamics(mpcqp_handle h, int64_t B, const void* q, const void* qd,
   if (!tau && !mass && !bias) return fail(h, MPCQP_EINVAL, "mpcqp_leg_dynamics: no output buffer (tau, mass and bias are all null)");
   if (B > 0 && !q) return fail(h, MPCQP_EINVAL, "mpcqp_leg_dynamics: null q buffer");
   LegGeoDev g;
-  if (const int rc = leg_fk_geometry(h, "mpcqp_leg_dynamics", geo, g)) return rc;
   LegInrDev r;
-  if (const int rc = leg_inertia_row(h, "mpcqp_leg_dynamics", inr, r)) return rc;
+  if (const int rc = leg_rows(h, "mpcqp_leg_dynamics", geo, inr, false, g, r)) return rc;
   if (B == 0) return MPCQP_OK;
-  DeviceGuard guard(h->cfg.device);
-  if (guard.err != hipSuccess) return fail(h, MPCQP_EHIP, "hipSetDevice", guard.err);
-  const dim3 grid((unsigned)((4 * B + 255) / 256));
-  with_io(h, [&](auto tag) {
+  return on_device(h, "leg dynamics kernel launch", [&](auto tag) {
     using T = decltype(tag);
-    hipLaunchKernelGGL((mpcqp_leg_dynamics_kernel<T>), grid, dim3(256), 0, (hipStream_t)stream, (const T*)q, (const T*)qd, (const T*)qdd,
+    hipLaunchKernelGGL((mpcqp_leg_dynamics_kernel<T>), leg_grid(B), dim3(256), 0, (hipStream_t)stream, (const T*)q, (const T*)qd, (const T*)qdd,
                        (const T*)rot, (const T*)base, g, r.k0, r.k1, r.k2, r.lim, (T*)tau, (T*)mass, (T*)bias, B);
   });
-  return launched(h, "leg dynamics kernel launch");
 }
 
 int mpcqp_leg_effort(mpcqp_handle h, int64_t B, int32_t T, const void* actual, const void* forces, const void* feet, const void* foot_vel,
@@ -1399,23 +1401,18 @@ int mpcqp_leg_effort(mpcqp_handle h, int64_t B, int32_t T, const void* actual, c
     return fail(h, MPCQP_EINVAL, "mpcqp_leg_effort: no output buffer (qdd, tau_dyn, tau, power and limit are all null)");
   if (B > 0 && T > 0 && (!actual || !forces || !feet)) return fail(h, MPCQP_EINVAL, "mpcqp_leg_effort: null buffer");
   LegGeoDev g;
-  if (const int rc = leg_ik_geometry(h, "mpcqp_leg_effort", geo, g)) return rc;
   LegInrDev r;
-  if (const int rc = leg_inertia_row(h, "mpcqp_leg_effort", inr, r)) return rc;
+  if (const int rc = leg_rows(h, "mpcqp_leg_effort", geo, inr, true, g, r)) return rc;
   if (B == 0 || T == 0) return MPCQP_OK;
   if (const int rc = actuators_match(h, B, "mpcqp_leg_effort")) return rc;
-  DeviceGuard guard(h->cfg.device);
-  if (guard.err != hipSuccess) return fail(h, MPCQP_EHIP, "hipSetDevice", guard.err);
   const int64_t rows = B * T;
-  const dim3 grid((unsigned)((4 * rows + 255) / 256));
-  with_io(h, [&](auto tag) {
+  return on_device(h, "leg effort kernel launch", [&](auto tag) {
     using TIO = decltype(tag);
-    launch_act(act_table(h), grid, dim3(256), (hipStream_t)stream, mpcqp_leg_effort_kernel<TIO>, mpcqp_leg_effort_kernel<TIO, double>,
+    launch_act(h, leg_grid(rows), (hipStream_t)stream, mpcqp_leg_effort_kernel<TIO>, mpcqp_leg_effort_kernel<TIO, double>,
                (const TIO*)actual, (const TIO*)forces, (const TIO*)feet, (const TIO*)foot_vel, (const TIO*)foot_acc, (const TIO*)base_acc,
                (const TIO*)body, plant_model(h), g, r.k0, r.k1, r.k2, r.lim, (TIO*)qdd, (TIO*)tau_dyn, (TIO*)tau, (TIO*)power, limit, rows,
                (int64_t)T);
   });
-  return launched(h, "leg effort kernel launch");
 }
 
 int mpcqp_leg_accel(mpcqp_handle h, int64_t B, const void* q, const void* qd, const void* tau, const void* rot, const void* base,
@@ -1426,19 +1423,14 @@ int mpcqp_leg_accel(mpcqp_handle h, int64_t B, const void* q, const void* qd, co
   if (B > 0 && !tau) return fail(h, MPCQP_EINVAL, "mpcqp_leg_accel: null tau buffer");
   if (B > 0 && !qdd) return fail(h, MPCQP_EINVAL, "mpcqp_leg_accel: null qdd buffer");
   LegGeoDev g;
-  if (const int rc = leg_fk_geometry(h, "mpcqp_leg_accel", geo, g)) return rc;
   LegInrDev r;
-  if (const int rc = leg_inertia_row(h, "mpcqp_leg_accel", inr, r)) return rc;
+  if (const int rc = leg_rows(h, "mpcqp_leg_accel", geo, inr, false, g, r)) return rc;
   if (B == 0) return MPCQP_OK;
-  DeviceGuard guard(h->cfg.device);
-  if (guard.err != hipSuccess) return fail(h, MPCQP_EHIP, "hipSetDevice", guard.err);
-  const dim3 grid((unsigned)((4 * B + 255) / 256));
-  with_io(h, [&](auto tag) {
+  return on_device(h, "leg acceleration kernel launch", [&](auto tag) {
     using T = decltype(tag);
-    hipLaunchKernelGGL((mpcqp_leg_accel_kernel<T>), grid, dim3(256), 0, (hipStream_t)stream, (const T*)q, (const T*)qd, (const T*)tau,
+    hipLaunchKernelGGL((mpcqp_leg_accel_kernel<T>), leg_grid(B), dim3(256), 0, (hipStream_t)stream, (const T*)q, (const T*)qd, (const T*)tau,
                        (const T*)rot, (const T*)base, g, r.k0, r.k1, r.k2, r.lim, (T*)qdd, (T*)det, B);
   });
-  return launched(h, "leg acceleration kernel launch");
 }
 
 int mpcqp_swing_track(mpcqp_handle h, int64_t B, int32_t T, const void* actual, const void* forces, const void* feet_log,
@@ -1452,124 +1444,20 @@ int mpcqp_swing_track(mpcqp_handle h, int64_t B, int32_t T, const void* actual, 
     return fail(h, MPCQP_EINVAL, "mpcqp_swing_track: no output buffer (q, qd, tau, foot, err and flag are all null)");
   if (B > 0 && T > 0 && (!actual || !forces || !feet_log || !contact_log || !swing)) return fail(h, MPCQP_EINVAL, "mpcqp_swing_track: null buffer");
   LegGeoDev g;
-  if (const int rc = leg_ik_geometry(h, "mpcqp_swing_track", geo, g)) return rc;
   LegInrDev r;
-  if (const int rc = leg_inertia_row(h, "mpcqp_swing_track", inr, r)) return rc;
+  if (const int rc = leg_rows(h, "mpcqp_swing_track", geo, inr, true, g, r)) return rc;
   if (B == 0 || T == 0) return MPCQP_OK;
   if (const int rc = actuators_match(h, B, "mpcqp_swing_track")) return rc;
   const int n = swing_substeps(h->cfg.delta, substeps);
-  DeviceGuard guard(h->cfg.device);
-  if (guard.err != hipSuccess) return fail(h, MPCQP_EHIP, "hipSetDevice", guard.err);
-  const dim3 grid((unsigned)((4 * B + 255) / 256));
-  with_io(h, [&](auto tag) {
+  return on_device(h, "swing track kernel launch", [&](auto tag) {
     using TIO = decltype(tag);
     const SwingIn<TIO> in = {(const TIO*)actual, (const TIO*)forces, (const TIO*)feet_log, contact_log, (const TIO*)swing,
                              (const TIO*)base_acc, (const TIO*)body, (const TIO*)gains};
     const SwingOut<TIO> out = {(TIO*)q, (TIO*)qd, (TIO*)tau, (TIO*)foot, (TIO*)err, flag};
-    launch_act(act_table(h), grid, dim3(256), (hipStream_t)stream, mpcqp_swing_track_kernel<TIO>, mpcqp_swing_track_kernel<TIO, double>, in,
-               (TIO*)state, plant_model(h), g, r.k0, r.k1, r.k2, r.lim, out, B, (int)T, n, h->cfg.delta / n);
+    launch_act(h, leg_grid(B), (hipStream_t)stream, mpcqp_swing_track_kernel<TIO>, mpcqp_swing_track_kernel<TIO, double>, in, (TIO*)state,
+               plant_model(h), g, r.k0, r.k1, r.k2, r.lim, out, B, (int)T, n, h->cfg.delta / n);
   });
-  return launched(h, "swing track kernel launch");
 }
-
-extern "C++" {
-namespace {
-
-// What mpcqp_rollout_drive adds to mpcqp_rollout_legs: the drive mode, the ground's friction [B] or null, the commanded-force log or null.
-struct RolloutDriveArgs { int32_t drive; const void* ground; void* cmd_log; };
-// What mpcqp_rollout_slip adds to mpcqp_rollout_drive: the feet's effective mass [B], the slip state [B,4,2], its two logs or null.
-struct RolloutSlipArgs { const void* foot_mass; double* slip; double* slip_log; void* disp_log; };
-
-// mpcqp_rollout_legs (dr = null), mpcqp_rollout_drive and mpcqp_rollout_slip (sl, with dr): one argument check, one loop.
-int rollout_legs_run(mpcqp_handle h, const char* who, int64_t B, int32_t T, void* x, void* ref, void* feet, double* legs, const int32_t* gait,
-                     const void* stand, const void* gain, int32_t* tick, const void* mu, const void* body, const void* push,
-                     const int32_t* push_ticks, int32_t substeps, const void* step_height, const void* gains, int32_t leg_substeps,
-                     const MpcQpLegGeometry* geo, const MpcQpLegInertia* inr, int32_t land, void* actual, void* desired, void* forces,
-                     void* feet_log, uint8_t* contact_log, int32_t* solved, void* swing_log, void* q_log, void* qd_log, void* tau_log,
-                     void* foot_log, void* err_log, uint8_t* flag_log, void* miss_log, void* stream, const RolloutDriveArgs* dr,
-                     const RolloutSlipArgs* sl = nullptr) {
-  if (!h) return MPCQP_EINVAL;
-  const auto bad = [&](const char* what) {
-    char msg[160];
-    snprintf(msg, sizeof(msg), "%s: %s", who, what);
-    return fail(h, MPCQP_EINVAL, msg);
-  };
-  if (B < 0 || B > 0x7fffffff || T < 0 || B * (int64_t)T > 0x7fffffff) return bad("size out of range");
-  const int n = plant_substeps(substeps);
-  if (n < 0) return bad("substeps out of range [0, 1000]");
-  if (leg_substeps < 0 || leg_substeps > SWING_MAX_SUBSTEPS) return bad("leg_substeps out of range [0, 1000]");
-  if (land != MPCQP_LAND_RULE && land != MPCQP_LAND_ACTUAL) return bad("land is neither MPCQP_LAND_RULE nor MPCQP_LAND_ACTUAL");
-  if (dr && dr->drive != MPCQP_DRIVE_IDEAL && dr->drive != MPCQP_DRIVE_LIMITED) return bad("drive is neither MPCQP_DRIVE_IDEAL nor MPCQP_DRIVE_LIMITED");
-  if (push && !push_ticks) return bad("push without push_ticks");
-  if (B > 0 && (!x || !ref || !feet || !legs || !gait || !stand || !tick || !mu || !step_height)) return bad("null buffer");
-  if (B > 0 && sl && (!dr->ground || !sl->foot_mass || !sl->slip)) return bad("null buffer");
-  LegGeoDev g;
-  if (const int rc = leg_ik_geometry(h, who, geo, g)) return rc;
-  LegInrDev r;
-  if (const int rc = leg_inertia_row(h, who, inr, r)) return rc;
-  if (B == 0 || T == 0) return MPCQP_OK;
-  if (const int rc = models_match(h, B, who)) return rc;
-  if (const int rc = actuators_match(h, B, who)) return rc;
-  const double* act = act_table(h);
-  const int nl = swing_substeps(h->cfg.delta, leg_substeps);
-  DeviceGuard guard(h->cfg.device);
-  if (guard.err != hipSuccess) return fail(h, MPCQP_EHIP, "hipSetDevice", guard.err);
-  const RolloutPlantArgs plant = {body, push, push ? push_ticks : nullptr, n};
-  const int N = h->cfg.N;
-  const double d = h->cfg.delta;
-  const dim3 ge = expand_grid(B, N), ga = advance_grid(B), gl((unsigned)((4 * B + 255) / 256)), nt(256);
-  hipStream_t st = (hipStream_t)stream;
-  // the roll-out loop of mpcqp_rollout_phase with the legs step in front of its advance and the landing behind it: 5 launches per tick.
-  // With a drive, the rule runs between the solve and the legs step and leaves the applied forces in a [B,12] side buffer, which the legs
-  // step and the advance read as a force buffer of horizon 1 (the solve's own buffer, its next warm start, is not altered); after the legs
-  // step the rule's torques and bits go into the stance rows of tau_log / flag_log: 6 launches, 7 with one of those two logs.
-  // With the slip rule in the drive's place the log step waits until after the landing and moves the feet in the same launch: 7.
-  return rollout_loop(h, who, B, T, x, ref, mu, stream,
-    [&](auto tag, auto* xs, auto* rf, const auto& w) {
-      using TIO = decltype(tag);
-      const PhaseRows<TIO> ph = {(const TIO*)feet, gait, (const TIO*)stand, (const TIO*)gain};
-      hipLaunchKernelGGL((mpcqp_phase_expand_kernel<TIO>), ge, nt, 0, st, xs, rf, ph, tick, d, N, B, w.r, w.contact, w.xdes);
-    },
-    [&](auto tag, auto* xs, auto* rf, const auto& o, int it) {
-      using TIO = decltype(tag);
-      const PhaseRows<TIO> ph = {(const TIO*)feet, gait, (const TIO*)stand, (const TIO*)gain};
-      const LegRollOut<TIO> out = {(TIO*)swing_log, (TIO*)q_log, (TIO*)qd_log, (TIO*)tau_log, (TIO*)foot_log, (TIO*)err_log, flag_log};
-      const TIO* u = o.u;   // the forces the legs and the plant see, robot b's at u + b Nu 12
-      int Nu = N;
-      const DriveWs<TIO> dw = drive_ws<TIO>(h->roll_mem, B, N);
-      TIO* const rdisp = sl ? slip_ws<TIO>(h->roll_mem, B, N) : nullptr;
-      if (sl) {
-        TIO* cmd = dr->cmd_log ? (TIO*)dr->cmd_log + (size_t)it * 12 : nullptr;
-        double* slog = sl->slip_log ? sl->slip_log + (size_t)it * 8 : nullptr;
-        launch_act(act, gl, nt, st, mpcqp_stance_slip_kernel<TIO>, mpcqp_stance_slip_kernel<TIO, double>, xs, o.u, (int64_t)N * 12,
-                   (const TIO*)feet, (const uint8_t*)nullptr, gait, tick, (const TIO*)dr->ground, (const TIO*)sl->foot_mass,
-                   (const double*)sl->slip, g, r.lim, (int)dr->drive, n, d / n, d, dw.f, dw.tau, dw.flag, cmd, (int64_t)T * 12, sl->slip, rdisp,
-                   slog, (int64_t)T * 8, B);
-        u = dw.f; Nu = 1;
-      } else if (dr) {
-        TIO* cmd = dr->cmd_log ? (TIO*)dr->cmd_log + (size_t)it * 12 : nullptr;
-        launch_act(act, gl, nt, st, mpcqp_stance_drive_kernel<TIO>, mpcqp_stance_drive_kernel<TIO, double>, xs, o.u, (int64_t)N * 12,
-                   (const TIO*)feet, (const uint8_t*)nullptr, gait, tick, (const TIO*)dr->ground, g, r.lim, (int)dr->drive, dw.f, dw.tau, dw.flag,
-                   cmd, (int64_t)T * 12, B);
-        u = dw.f; Nu = 1;
-      }
-      launch_act(act, gl, nt, st, mpcqp_legs_step_kernel<TIO>, mpcqp_legs_step_kernel<TIO, double>, xs, rf, ph, tick, u, (const TIO*)step_height,
-                 (const TIO*)gains, legs, plant_in<TIO>(h, plant), g, r.k0, r.k1, r.k2, r.lim, out, d, Nu, B, (int)T, it, nl, d / nl);
-      if (dr && !sl && (tau_log || flag_log))
-        hipLaunchKernelGGL((mpcqp_drive_log_kernel<TIO>), gl, nt, 0, st, gait, tick, dw.tau, dw.flag,
-                           (int)(dr->drive == MPCQP_DRIVE_IDEAL && !dr->ground), B, (int)T, it, (TIO*)tau_log, flag_log);
-      hipLaunchKernelGGL((mpcqp_phase_advance_kernel<TIO>), ga, nt, 0, st, xs, rf, (TIO*)feet, ph, tick, plant_in<TIO>(h, plant), u, o.status, d, Nu, B,
-                         (int)T, it, (TIO*)actual, (TIO*)desired, (TIO*)forces, (TIO*)feet_log, contact_log, solved);
-      hipLaunchKernelGGL((mpcqp_legs_land_kernel<TIO>), gl, nt, 0, st, xs, (TIO*)feet, gait, tick, legs, g, (int)land, B, (int)T, it,
-                         (TIO*)miss_log);
-      if (sl)
-        hipLaunchKernelGGL((mpcqp_slip_finish_kernel<TIO>), gl, nt, 0, st, gait, tick, (const TIO*)dw.tau, (const uint8_t*)dw.flag,
-                           (const TIO*)rdisp, B, (int)T, it, (TIO*)feet, sl->slip, (TIO*)tau_log, flag_log, (TIO*)sl->disp_log);
-    });
-}
-
-}  // namespace
-}  // extern "C++"
 
 int mpcqp_rollout_legs(mpcqp_handle h, int64_t B, int32_t T, void* x, void* ref, void* feet, double* legs, const int32_t* gait,
                        const void* stand, const void* gain, int32_t* tick, const void* mu, const void* body, const void* push,
@@ -1601,21 +1489,16 @@ int mpcqp_stance_drive(mpcqp_handle h, int64_t B, const void* x, const void* f, 
   if (B < 0 || B > 0x1fffffff) return fail(h, MPCQP_EINVAL, "mpcqp_stance_drive: batch size out of range");
   if (B > 0 && (!x || !f || !feet || !contact || !f_out)) return fail(h, MPCQP_EINVAL, "mpcqp_stance_drive: null buffer");
   LegGeoDev g;
-  if (const int rc = leg_ik_geometry(h, "mpcqp_stance_drive", geo, g)) return rc;
   LegInrDev r;
-  if (const int rc = leg_inertia_row(h, "mpcqp_stance_drive", inr, r)) return rc;
+  if (const int rc = leg_rows(h, "mpcqp_stance_drive", geo, inr, true, g, r)) return rc;
   if (B == 0) return MPCQP_OK;
   if (const int rc = actuators_match(h, B, "mpcqp_stance_drive")) return rc;
-  DeviceGuard guard(h->cfg.device);
-  if (guard.err != hipSuccess) return fail(h, MPCQP_EHIP, "hipSetDevice", guard.err);
-  const dim3 grid((unsigned)((4 * B + 255) / 256));
-  with_io(h, [&](auto tag) {
+  return on_device(h, "stance drive kernel launch", [&](auto tag) {
     using TIO = decltype(tag);
-    launch_act(act_table(h), grid, dim3(256), (hipStream_t)stream, mpcqp_stance_drive_kernel<TIO>, mpcqp_stance_drive_kernel<TIO, double>,
+    launch_act(h, leg_grid(B), (hipStream_t)stream, mpcqp_stance_drive_kernel<TIO>, mpcqp_stance_drive_kernel<TIO, double>,
                (const TIO*)x, (const TIO*)f, (int64_t)12, (const TIO*)feet, contact, (const int32_t*)nullptr, (const int32_t*)nullptr,
                (const TIO*)ground, g, r.lim, (int)DRIVE_LIMITED, (TIO*)f_out, (TIO*)tau, flag, (TIO*)nullptr, (int64_t)0, B);
   });
-  return launched(h, "stance drive kernel launch");
 }
 
 int mpcqp_rollout_slip(mpcqp_handle h, int64_t B, int32_t T, void* x, void* ref, void* feet, double* legs, const int32_t* gait,
@@ -1642,23 +1525,18 @@ int mpcqp_stance_slip(mpcqp_handle h, int64_t B, const void* x, const void* f, c
   if (B > 0 && (!x || !f || !feet || !contact || !ground || !foot_mass || !slip_in || !f_out))
     return fail(h, MPCQP_EINVAL, "mpcqp_stance_slip: null buffer");
   LegGeoDev g;
-  if (const int rc = leg_ik_geometry(h, "mpcqp_stance_slip", geo, g)) return rc;
   LegInrDev r;
-  if (const int rc = leg_inertia_row(h, "mpcqp_stance_slip", inr, r)) return rc;
+  if (const int rc = leg_rows(h, "mpcqp_stance_slip", geo, inr, true, g, r)) return rc;
   if (B == 0) return MPCQP_OK;
   if (const int rc = actuators_match(h, B, "mpcqp_stance_slip")) return rc;
-  DeviceGuard guard(h->cfg.device);
-  if (guard.err != hipSuccess) return fail(h, MPCQP_EHIP, "hipSetDevice", guard.err);
-  const dim3 grid((unsigned)((4 * B + 255) / 256));
   const double d = h->cfg.delta;
-  with_io(h, [&](auto tag) {
+  return on_device(h, "stance slip kernel launch", [&](auto tag) {
     using TIO = decltype(tag);
-    launch_act(act_table(h), grid, dim3(256), (hipStream_t)stream, mpcqp_stance_slip_kernel<TIO>, mpcqp_stance_slip_kernel<TIO, double>,
+    launch_act(h, leg_grid(B), (hipStream_t)stream, mpcqp_stance_slip_kernel<TIO>, mpcqp_stance_slip_kernel<TIO, double>,
                (const TIO*)x, (const TIO*)f, (int64_t)12, (const TIO*)feet, contact, (const int32_t*)nullptr, (const int32_t*)nullptr,
                (const TIO*)ground, (const TIO*)foot_mass, slip_in, g, r.lim, (int)DRIVE_LIMITED, n, d / n, d, (TIO*)f_out, (TIO*)tau, flag,
                (TIO*)nullptr, (int64_t)0, slip_out, (TIO*)disp, (double*)nullptr, (int64_t)0, B);
   });
-  return launched(h, "stance slip kernel launch");
 }
 
 int mpcqp_rollout_score(mpcqp_handle h, int64_t B, int32_t T, const void* actual, const void* desired, const void* forces,
@@ -1680,17 +1558,14 @@ int mpcqp_rollout_score(mpcqp_handle h, int64_t B, int32_t T, const void* actual
   if ((uintptr_t)contact_log % 4 || (uintptr_t)flag % 4 || (uintptr_t)score % 8)
     return fail(h, MPCQP_EINVAL, "mpcqp_rollout_score: contact_log / flag not 4-byte or score not 8-byte aligned");
   if (B == 0 || (T == 0 && accumulate)) return MPCQP_OK;
-  DeviceGuard guard(h->cfg.device);
-  if (guard.err != hipSuccess) return fail(h, MPCQP_EHIP, "hipSetDevice", guard.err);
-  const dim3 grid((unsigned)((B + 3) / 4));   // one wave per robot
-  with_io(h, [&](auto tag) {
+  return on_device(h, "score kernel launch", [&](auto tag) {
     using TIO = decltype(tag);
     const ScoreIn<TIO> in = {(const TIO*)actual, (const TIO*)desired, (const TIO*)forces, contact_log, (const TIO*)tau, (const TIO*)qd, flag,
                              (const TIO*)miss};
-    hipLaunchKernelGGL((mpcqp_score_kernel<TIO>), grid, dim3(256), 0, (hipStream_t)stream, in, rule->z_frac, rule->tilt_max, (int)(accumulate != 0),
-                       score, (int)B, (int)T);
+    // one wave per robot
+    hipLaunchKernelGGL((mpcqp_score_kernel<TIO>), blocks(B, 4), dim3(256), 0, (hipStream_t)stream, in, rule->z_frac, rule->tilt_max,
+                       (int)(accumulate != 0), score, (int)B, (int)T);
   });
-  return launched(h, "score kernel launch");
 }
 
 int mpcqp_last_kernel_ms(mpcqp_handle h, float* ms) {

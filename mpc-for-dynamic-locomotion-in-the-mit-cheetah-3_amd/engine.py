@@ -142,14 +142,18 @@ class MPCBatch:
         helpers and the host checkers).  The row is the MPC's model only: the plant (`rollout_*`, `plant_step`), the legs step of
         `rollout_legs` / `rollout_drive`, `leg_effort` and `swing_track` take `body`, and with body=None the CONFIGURATION's model,
         whatever the table says (a matched plant is body[b] = (m, Ixx, Iyy, Izz, 0, 0, 0) of row b).  Asynchronous on `stream`."""
+        self._set_rows(self.engine.set_models_ptr, "models", models, 6, stream)
+
+    def _set_rows(self, set_ptr, name, rows, width, stream):
+        """`set_models` / `set_actuators`: a float64 [B,width] table, uploaded when it is a numpy array, handed to the library on `stream`."""
         torch = _torch()
-        if not hasattr(models, "data_ptr"):
-            models = torch.as_tensor(np.ascontiguousarray(models, dtype=np.float64)).to(self.device)
-        B = int(models.shape[0]) if models.dim() == 2 else 0
-        check_operands(self.device, [("models", models, (max(B, 1), 6), torch.float64)])   # (at least one row)
+        if not hasattr(rows, "data_ptr"):
+            rows = torch.as_tensor(np.ascontiguousarray(rows, dtype=np.float64)).to(self.device)
+        B = int(rows.shape[0]) if rows.dim() == 2 else 0
+        check_operands(self.device, [(name, rows, (max(B, 1), width), torch.float64)])   # (at least one row)
         st = self._stream(stream)
-        models.record_stream(st)   # (the conversion kernel reads it on `st`; the engine keeps its own table)
-        self.engine.set_models_ptr(B, models.data_ptr(), st.cuda_stream)
+        rows.record_stream(st)   # (the conversion kernel reads it on `st`; the engine keeps its own table)
+        set_ptr(B, rows.data_ptr(), st.cuda_stream)
 
     def clear_models(self):
         """Back to the configuration's model for every QP (mpcqp_clear_models; waits for the device)."""
@@ -163,14 +167,7 @@ class MPCBatch:
         tau_max of `inertia` is then ignored -- and must have B robots; `stance_drive` on the B T logged rows of a roll-out wants the
         table tiled (actuators.tile).  A table of flat rows with the inertia row's tau_max (actuators.actuator_rows(B)) is no table, bit
         for bit.  The MPC is not told.  Asynchronous on `stream`."""
-        torch = _torch()
-        if not hasattr(rows, "data_ptr"):
-            rows = torch.as_tensor(np.ascontiguousarray(rows, dtype=np.float64)).to(self.device)
-        B = int(rows.shape[0]) if rows.dim() == 2 else 0
-        check_operands(self.device, [("rows", rows, (max(B, 1), 9), torch.float64)])   # (at least one row)
-        st = self._stream(stream)
-        rows.record_stream(st)   # (the conversion kernel reads it on `st`; the engine keeps its own table)
-        self.engine.set_actuators_ptr(B, rows.data_ptr(), st.cuda_stream)
+        self._set_rows(self.engine.set_actuators_ptr, "rows", rows, 9, stream)
 
     def clear_actuators(self):
         """Back to the inertia row's tau_max for every clamp (mpcqp_clear_actuators; waits for the device)."""

@@ -3,7 +3,9 @@ is in place, as raw arrays in one .npz, and their comparison byte for byte (inte
 Solves (tuple, gait S = 2, gait steps S = 4; f32 / f64 I/O; N = 10 / 20 / 60; MIXED / F64; warm start + shift over three calls),
 the stage-wise engine at N = 60 and, by MPCQP_FLAG_STAGE_KERNEL, at N = 10 (MIXED / F64, cold and warm-started with shift),
 roll-outs on the model and on the plant (T = 50, B = 1024, cold and warm, with the malformed plan rows of tests/test_rollout.py),
-planner + swing trajectories, plant step, leg Jacobians and torque map.  One process per library build: copy the wanted build over
+planner + swing trajectories, plant step, leg Jacobians and torque map, and the newer entry points (phase gaits, joints, leg dynamics,
+leg simulation, leg roll-outs, score; with and without the model and actuator tables; at the tests' small shapes and at a ragged B = 333:
+the last section).  The stance rule's calls are in tools/stance_rule_compare.py.  One process per library build: copy the wanted build over
 csrc/libmpcqp.so before starting each.
 usage: dump_outputs.py OUT.npz            (needs a GPU)
        dump_outputs.py --compare A.npz B.npz"""
@@ -137,5 +139,88 @@ for io in ("f32", "f64"):
     put(f"tau_{io}", sol.torque_map(u, J))
     torch.cuda.synchronize()
     del sol
+
+# ---- the entry points that came after the ones above and that tools/stance_rule_compare.py does not run: phase_expand, solve_batch_phase,
+#      rollout_phase, phase_swing, rollout_legs, joint_log, joint_rates, leg_effort, swing_track, rollout_score, leg_ik, leg_dynamics, leg_accel.
+#      Inputs: the legs batch of tests/models_rollout_cases.py (B = 16, T = 25), the joint rows of tests/legsim_cases.py (33), the synthetic
+#      logs of tests/score_cases.py (24 x 25), at their own shapes without and with the two row tables (model rows: every solve and roll-out;
+#      actuator rows of tests/actuator_cases.py: rollout_legs, swing_track, leg_effort), and tiled and cut to B = 333 (T = 4 for the roll-outs):
+#      more than one block of 256 threads and a ragged last one, whether a kernel runs one thread per leg, per robot or per tuple element.
+#      Outputs start zero-filled, so a row that a build does not write cannot compare equal by accident.
+import actuator_cases as ac, legsim_cases as lc, models_rollout_cases as C, score_cases as scc
+import test_gpu_models_rollouts as mr
+
+
+def puts(prefix, out):
+    for k, v in out.items(): put(f"{prefix}_{k}", v)
+
+
+def zero_filled(sol):
+    alloc = sol._alloc
+    sol._alloc = lambda stream, *specs: alloc(stream, *[s and (s[0], s[1], True) for s in specs])
+    return sol
+
+
+def tiled(d, B):
+    """Every array of d repeated along its first axis and cut to B rows."""
+    if d is None or isinstance(d, np.ndarray):
+        return d if d is None else np.tile(d, (-(-B // len(d)),) + (1,) * (d.ndim - 1))[:B]
+    return {k: (tiled(v, B) if isinstance(v, np.ndarray) else v) for k, v in d.items()}
+
+
+def newer(tag, io, pb, pr, T, rows, acts, q, ops, slog):
+    tdt = torch.float32 if io == "f32" else torch.float64
+    sol = zero_filled(mr._engine(io))
+    if rows is not None:
+        sol.set_models(rows); sol.set_actuators(acts)
+    plant = mr._plant(sol, pr)
+    d = mr._dev(sol, pb)
+    phase = [d[k] for k in ("x", "ref", "feet", "gait", "tick", "stand")]
+    puts(f"{tag}_expand", sol.phase_expand(*phase, d.get("gain")))
+    puts(f"{tag}_solvephase", sol.solve_batch_phase(*phase, d.get("gain"), d["mu"], want_X=True))
+    logs = sol.rollout_phase(*[d[k] for k in C.PHASE_ARGS], T, **plant)
+    puts(f"{tag}_rollphase", logs); puts(f"{tag}_rollphase_end", {k: d[k] for k in C.PHASE_STATE})
+    sw = sol.phase_swing(logs, d["gait"], dev(pb["tick"], torch.int32), d["stand"], d.get("gain"), d["step_height"])
+    puts(f"{tag}_phaseswing", sw)
+    vel, acc = sw["swing"][:, :, :, 1].contiguous(), sw["swing"][:, :, :, 2].contiguous()
+    puts(f"{tag}_jointlog", sol.joint_log(logs["actual"], logs["forces"], sw["feet_des"]))
+    puts(f"{tag}_jointrates", sol.joint_rates(logs["actual"], logs["forces"], sw["feet_des"], vel))
+    puts(f"{tag}_effort", sol.leg_effort(logs["actual"], logs["forces"], sw["feet_des"], vel, acc, body=plant["body"]))
+    puts(f"{tag}_effort_bare", sol.leg_effort(logs["actual"], logs["forces"], sw["feet_des"]))
+    state = torch.zeros((len(pb["x"]), 4, 7), dtype=tdt, device="cuda")
+    puts(f"{tag}_track", sol.swing_track(logs, sw["swing"], body=plant["body"], state=state)); put(f"{tag}_track_state", state)
+    d = mr._dev(sol, pb)
+    for land in ("rule", "actual"):
+        legs = sol.rollout_legs(*[d[k] for k in C.LEGS_ARGS], T, d["step_height"], land=land, **plant)
+        puts(f"{tag}_rolllegs_{land}", legs); puts(f"{tag}_rolllegs_{land}_end", {k: d[k] for k in C.LEGS_ARGS[:4] + ("tick",)})
+        put(f"{tag}_score_{land}", sol.score(legs))
+    sl = {k: dev(v, torch.uint8 if v.dtype == np.uint8 else tdt) for k, v in slog.items()}
+    score = sol.score(sl); put(f"{tag}_score_synthetic", score.clone())
+    put(f"{tag}_score_accumulated", sol.score(sl, score=score))
+    put(f"{tag}_score_body_only", sol.score({k: sl[k] for k in ("actual", "desired", "forces", "contact_log")}))
+    tq, o = dev(q, tdt), {k: dev(v, tdt) for k, v in ops.items()}
+    J, P = sol.leg_jacobians(tq, o["rot"])
+    for name, (iq, reach) in (("ik", sol.leg_ik(P, o["rot"])), ("ik0", sol.leg_ik(sol.leg_jacobians(tq, None)[1]))):
+        put(f"{tag}_{name}_q", iq); put(f"{tag}_{name}_reach", reach)
+    dyn = sol.leg_dynamics(tq, o["qd"], o["qdd"], o["rot"], o["base"])
+    puts(f"{tag}_dynamics", dyn); puts(f"{tag}_dynamics_bare", sol.leg_dynamics(tq))
+    puts(f"{tag}_accel", sol.leg_accel(tq, dyn["tau"], o["qd"], o["rot"], o["base"])); puts(f"{tag}_accel_bare", sol.leg_accel(tq, dyn["tau"]))
+    torch.cuda.synchronize()
+    if rows is not None:
+        sol.clear_actuators(); sol.clear_models()
+
+
+pb, pr, rows, T = C.legs_case()
+acts = ac.combined_tables(len(rows))[0]
+q, ops = lc.box_rows()
+RAGGED = 333
+for io in ("f32", "f64"):
+    slog = scc.synthetic_logs(24, 25, 8, np.float32)
+    newer(f"new_{io}", io, pb, pr, T, None, None, q, ops, slog)
+    newer(f"new_{io}_tables", io, pb, pr, T, rows, acts, q, ops, slog)
+    for name, tables in (("ragged", False), ("ragged_tables", True)):
+        newer(f"new_{io}_{name}", io, tiled(pb, RAGGED), tiled(pr, RAGGED), 4, tiled(rows, RAGGED) if tables else None, tiled(acts, RAGGED),
+              tiled(q, RAGGED), tiled(ops, RAGGED), tiled(slog, RAGGED))
+    print("newer entry points", io, "done", flush=True)
 np.savez(sys.argv[1], **OUT)
 print("dumped", len(OUT), "arrays", flush=True)
