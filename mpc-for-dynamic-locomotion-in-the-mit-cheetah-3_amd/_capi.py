@@ -1,5 +1,5 @@
 """ctypes binding of the C-ABI declared in include/mpcqp.h and its product-only extensions include/mpcqp_plan.h, mpcqp_sim.h, mpcqp_model.h,
-mpcqp_joints.h, mpcqp_actuators.h and mpcqp_slip.h.
+mpcqp_joints.h, mpcqp_actuators.h, mpcqp_slip.h and mpcqp_estimate.h.
 
 The product path loads ``csrc/libmpcqp.so`` (hand-written HIP for gfx950) and nothing else: if that library is
 missing or cannot be loaded, importing the engine raises -- there is no CPU fallback.  The binding itself is
@@ -80,6 +80,14 @@ class MpcQpScoreRule(ctypes.Structure):
     _fields_ = [("size", c_uint32), ("z_frac", c_double), ("tilt_max", c_double)]
 
 
+class MpcQpEstimator(ctypes.Structure):
+    """Mirror of struct MpcQpEstimator (include/mpcqp_estimate.h): the state estimator's gains and noise figures."""
+    _fields_ = [("size", c_uint32), ("gravity", c_double), ("kappa", c_double), ("q_p", c_double), ("q_v", c_double), ("q_f", c_double),
+                ("r_p", c_double), ("r_v", c_double), ("r_z", c_double), ("k_swing", c_double), ("p0_p", c_double), ("p0_v", c_double),
+                ("p0_f", c_double)]
+    FIELDS = tuple(name for name, _ in _fields_[1:])
+
+
 class MpcQpConfig(ctypes.Structure):
     """Mirror of ``struct MpcQpConfig`` (include/mpcqp.h)."""
     _fields_ = [
@@ -111,6 +119,7 @@ class MpcQpError(RuntimeError):
 _P, _I32, _I64 = c_void_p, c_int32, c_int64   # any address (handle, buffer, stream), int32_t, int64_t
 _CFG, _GEO, _INR = ctypes.POINTER(MpcQpConfig), ctypes.POINTER(MpcQpLegGeometry), ctypes.POINTER(MpcQpLegInertia)
 _RULE = ctypes.POINTER(MpcQpScoreRule)
+_EST = ctypes.POINTER(MpcQpEstimator)
 CORE_HEADER = "mpcqp.h"
 ABI = {
     "mpcqp.h": (
@@ -180,6 +189,17 @@ SLIP_ABI = {
     ),
 }
 SLIP_SYMBOLS = tuple(row[0] for row in SLIP_ABI[SLIP_HEADER])
+# include/mpcqp_estimate.h, the state estimator, likewise: `has_estimate`.
+ESTIMATE_HEADER = "mpcqp_estimate.h"
+ESTIMATE_ABI = {
+    ESTIMATE_HEADER: (  # the torso state from an IMU and leg kinematics
+        ("mpcqp_default_estimator", c_int, (_EST,)),
+        ("mpcqp_imu_log", c_int, (_P, _I64, _I32) + (_P,) * 7 + (_EST, _P, _P)),
+        ("mpcqp_estimate_track", c_int, (_P, _I64, _I32) + (_P,) * 7 + (_EST, _GEO) + (_P,) * 6),
+    ),
+}
+ESTIMATE_SYMBOLS = tuple(row[0] for row in ESTIMATE_ABI[ESTIMATE_HEADER])
+EST_STATE = 131   # include/mpcqp_estimate.h, MPCQP_EST_STATE: doubles per robot of the filter state
 # The swing-leg plant of include/mpcqp_joints.h came after the rest of that header: a product library built before it still has the
 # header's other calls (`has_joints`) and is told apart by `has_legsim`.
 LEGSIM_SYMBOLS = ("mpcqp_leg_accel", "mpcqp_swing_track")
@@ -200,8 +220,9 @@ DRIVE_SLIDING = 128   # include/mpcqp_slip.h, MPCQP_DRIVE_SLIDING: the stance fo
 
 
 class Library:
-    """A loaded shared object exporting the mpcqp C-ABI.  `has_plan`, `has_sim`, `has_model`, `has_joints`, `has_actuators` and `has_slip` say
-    whether it exports all of include/mpcqp_plan.h, mpcqp_sim.h, mpcqp_model.h, mpcqp_joints.h, mpcqp_actuators.h and mpcqp_slip.h (of mpcqp_joints.h: all but LEGSIM_SYMBOLS, which `has_legsim`
+    """A loaded shared object exporting the mpcqp C-ABI.  `has_plan`, `has_sim`, `has_model`, `has_joints`, `has_actuators`, `has_slip` and
+    `has_estimate` say whether it exports all of include/mpcqp_plan.h, mpcqp_sim.h, mpcqp_model.h, mpcqp_joints.h, mpcqp_actuators.h,
+    mpcqp_slip.h and mpcqp_estimate.h (of mpcqp_joints.h: all but LEGSIM_SYMBOLS, which `has_legsim`
     answers for; of mpcqp_sim.h: all but LEGROLL_SYMBOLS, SCORE_SYMBOLS and DRIVE_SYMBOLS, `has_legroll`, `has_score` and `has_drive`).  An
     extension header's calls are bound only when the library
     has them all; `partial=True` binds whichever it has (an older build of the product library, in a comparison tool)."""
@@ -216,7 +237,7 @@ class Library:
         self.has_legroll = all(hasattr(self.lib, name) for name in LEGROLL_SYMBOLS)
         self.has_score = all(hasattr(self.lib, name) for name in SCORE_SYMBOLS)
         self.has_drive = all(hasattr(self.lib, name) for name in DRIVE_SYMBOLS)
-        for header, rows in {**ABI, **ACTUATORS_ABI, **SLIP_ABI}.items():
+        for header, rows in {**ABI, **ACTUATORS_ABI, **SLIP_ABI, **ESTIMATE_ABI}.items():
             have = header == CORE_HEADER or all(hasattr(self.lib, row[0]) for row in rows if row[0] not in _GATED)
             if header != CORE_HEADER:
                 setattr(self, "has_" + header[len("mpcqp_"):-len(".h")], have)
@@ -240,6 +261,17 @@ class Library:
         rc = fn(ctypes.byref(row))
         if rc != 0:
             raise MpcQpError(f"mpcqp_default_leg_inertia failed: {rc}")
+        return row
+
+    def default_estimator(self) -> "MpcQpEstimator":
+        """The estimator's default gains and noise figures (include/mpcqp_estimate.h, mpcqp_default_estimator; product library only)."""
+        fn, header, _ = self.calls["mpcqp_default_estimator"]
+        if fn is None:
+            raise MpcQpError(f"mpcqp_default_estimator: {self.path} does not export include/{header} (product library only)")
+        row = MpcQpEstimator()
+        rc = fn(ctypes.byref(row))
+        if rc != 0:
+            raise MpcQpError(f"mpcqp_default_estimator failed: {rc}")
         return row
 
     def default_config(self, **overrides) -> MpcQpConfig:
@@ -404,6 +436,17 @@ class Engine:
         self._call("mpcqp_rollout_slip", B, T, x, ref, feet, legs, gait, stand, gain, tick, mu, body, push, push_ticks, substeps, step_height,
                    gains, leg_substeps, geometry, inertia, land, drive, ground, foot_mass, slip, actual, desired, forces, feet_log, contact_log,
                    solved, swing_log, q_log, qd_log, tau_log, foot_log, err_log, flag_log, miss_log, cmd_log, slip_log, disp_log, stream)
+
+    # (`estimator` is an MpcQpEstimator or None = the defaults)
+    def imu_log_ptr(self, B, T, actual, forces, feet, base_acc, body, bias, noise, imu, estimator=None, stream=0):
+        """What an IMU at the CoM reads on every row of a log (include/mpcqp_estimate.h, mpcqp_imu_log)."""
+        self._call("mpcqp_imu_log", B, T, actual, forces, feet, base_acc, body, bias, noise, estimator, imu, stream)
+
+    def estimate_track_ptr(self, B, T, imu, q, qd, contact_log, trust, height, init, state, est, feet_est, sigma, nis, estimator=None,
+                           geometry=None, stream=0):
+        """The state estimator over the rows of a log (include/mpcqp_estimate.h, mpcqp_estimate_track)."""
+        self._call("mpcqp_estimate_track", B, T, imu, q, qd, contact_log, trust, height, init, estimator, geometry, state, est, feet_est,
+                   sigma, nis, stream)
 
     def phase_swing_ptr(self, B, T, actual, desired, feet_log, gait, tick0, stand, gain, step_height, swing, feet_des=0, stream=0):
         """The swing-foot trajectories of a roll-out on a gait clock, from its logs (include/mpcqp_plan.h, mpcqp_phase_swing)."""

@@ -1,0 +1,288 @@
+// mpcqp_estimate.h -- the torso state estimated from an IMU and leg kinematics (the C-ABI is include/mpcqp_estimate.h, which has the
+// rule; the entry points live in mpcqp_kernels.hip): mpcqp_imu_log (what an IMU at the CoM reads on every row of a log) and
+// mpcqp_estimate_track (orientation filter plus three 6-state Kalman filters over the rows).
+//
+// The filter is serial in T and parallel in B.  Four lanes per robot, the mapping of the leg kernels: lane l does leg l's forward map,
+// then lanes 0..2 own one axis each (xi[a] and the upper triangle of P[a], 6 + 21 doubles in registers) and take the four legs' rho,
+// rhod components from their quad neighbours by DPP lane moves.  The orientation step is a few dozen flops on values every lane has,
+// so every lane carries it and nothing is sent back; lane 3 runs the z axis a second time and stores the quaternion, the rotation
+// vector, omega and nis.  Every lane of a quad runs the same instructions but for the height rows, which only the z lanes enter.
+// No LDS, no scratch: the measurement order is unrolled, so every index into xi and P is a constant.
+// Poison is a per-robot flag, combined over the quad once per row; outputs and the returned state are selects on it.
+#pragma once
+#include "mpcqp_legsim.h"
+#include "../../include/mpcqp_estimate.h"
+
+namespace {
+
+constexpr int EST_STATE = MPCQP_EST_STATE, EST_XI = 4, EST_P = 22, EST_LIVE = 130;
+
+// MpcQpEstimator as the kernels take it (checked on the host, estimator_row in mpcqp_kernels.hip), with the handle's delta.
+struct EstPar { double g, kappa, qp, qv, qf, rp, rv, rz, ks, p0p, p0v, p0f, d, hd2; };
+
+// P[i][j], i <= j, of a symmetric 6 x 6 kept as its upper triangle by rows
+__host__ __device__ constexpr int est_ut(const int i, const int j) { return i * 6 - (i * (i - 1)) / 2 + (j - i); }
+__host__ __device__ constexpr int est_sym(const int i, const int j) { return i <= j ? est_ut(i, j) : est_ut(j, i); }
+
+// The small-vector arithmetic of the filter, not contracted (the V3 operators of mpcqp_legdyn.h are).
+__device__ __forceinline__ V3 est_add(const V3 a, const V3 b) {
+#pragma clang fp contract(off)
+  return {a.x + b.x, a.y + b.y, a.z + b.z};
+}
+__device__ __forceinline__ V3 est_cross(const V3 a, const V3 b) {
+#pragma clang fp contract(off)
+  return {a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x};
+}
+__device__ __forceinline__ V3 est_mv(const M3& A, const V3 v) {
+#pragma clang fp contract(off)
+  return {(A.r0.x * v.x + A.r0.y * v.y) + A.r0.z * v.z, (A.r1.x * v.x + A.r1.y * v.y) + A.r1.z * v.z, (A.r2.x * v.x + A.r2.y * v.y) + A.r2.z * v.z};
+}
+__device__ __forceinline__ V3 est_mtv(const M3& A, const V3 v) {   // A^T v
+#pragma clang fp contract(off)
+  return {(A.r0.x * v.x + A.r1.x * v.y) + A.r2.x * v.z, (A.r0.y * v.x + A.r1.y * v.y) + A.r2.y * v.z, (A.r0.z * v.x + A.r1.z * v.y) + A.r2.z * v.z};
+}
+__device__ __forceinline__ M3 est_rot(const double (&qt)[4]) {   // quat_rot's formula
+#pragma clang fp contract(off)
+  const double qw = qt[0], qx = qt[1], qy = qt[2], qz = qt[3];
+  return {{1.0 - 2.0 * (qy * qy + qz * qz), 2.0 * (qx * qy - qw * qz), 2.0 * (qx * qz + qw * qy)},
+          {2.0 * (qx * qy + qw * qz), 1.0 - 2.0 * (qx * qx + qz * qz), 2.0 * (qy * qz - qw * qx)},
+          {2.0 * (qx * qz - qw * qy), 2.0 * (qy * qz + qw * qx), 1.0 - 2.0 * (qx * qx + qy * qy)}};
+}
+__device__ __forceinline__ double est_norm(const V3 d) {
+#pragma clang fp contract(off)
+  return sqrt((d.x * d.x + d.y * d.y) + d.z * d.z);
+}
+
+template <int J>
+__device__ __forceinline__ double quad_bcast(const double v) { return dpp_mov<J * 0x55>(v); }   // quad_perm [J,J,J,J]
+
+// One scalar measurement z with variance r on an axis.  KIND 0: h = e_C - e_p, 1: h = e_v, 2: h = e_C.
+template <int KIND, int C>
+__device__ __forceinline__ void est_update(double (&xi)[6], double (&U)[21], const double z, const double r, double& nis) {
+#pragma clang fp contract(off)
+  double w[6], k[6];
+#pragma unroll
+  for (int i = 0; i < 6; ++i) w[i] = KIND == 0 ? U[est_sym(i, C)] - U[est_sym(i, 0)] : (KIND == 1 ? U[est_sym(i, 1)] : U[est_sym(i, C)]);
+  const double hw = KIND == 0 ? w[C] - w[0] : (KIND == 1 ? w[1] : w[C]);
+  const double hx = KIND == 0 ? xi[C] - xi[0] : (KIND == 1 ? xi[1] : xi[C]);
+  const double S = hw + r, e = z - hx;
+#pragma unroll
+  for (int i = 0; i < 6; ++i) { k[i] = w[i] / S; xi[i] = xi[i] + k[i] * e; }
+#pragma unroll
+  for (int i = 0; i < 6; ++i)
+#pragma unroll
+    for (int j = i; j < 6; ++j) U[est_ut(i, j)] = U[est_ut(i, j)] - k[i] * w[j];
+  nis = nis + (e * e) / S;
+}
+
+// The three measurements of leg J on an axis; `hgt` only where the lane owns z and height is given.
+template <int J>
+__device__ __forceinline__ void est_leg(const EstPar& par, double (&xi)[6], double (&U)[21], const double zr, const double zv, const double tr,
+                                        const bool hgt, const double hz, double& nis) {
+#pragma clang fp contract(off)
+  const double s = 1.0 + (1.0 - tr) * par.ks;
+  est_update<0, 2 + J>(xi, U, zr, par.rp * s, nis);
+  est_update<1, 2 + J>(xi, U, -zv, par.rv * s, nis);
+  if (hgt) est_update<2, 2 + J>(xi, U, hz, par.rz * s, nis);
+}
+
+__device__ __forceinline__ double est_pick(const int a, const double x, const double y, const double z) { return a == 0 ? x : (a == 1 ? y : z); }
+
+// mpcqp_estimate_track: i = 4 b + lane.  trust / height / state and each output may be null.
+template <typename TIO>
+__global__ void __launch_bounds__(256)
+mpcqp_estimate_track_kernel(const TIO* __restrict__ imu, const TIO* __restrict__ q, const TIO* __restrict__ qd,
+                            const uint8_t* __restrict__ contact, const TIO* __restrict__ trust, const TIO* __restrict__ height,
+                            const TIO* __restrict__ init, const EstPar par, const LegGeoDev geo, double* state, TIO* __restrict__ est,
+                            TIO* __restrict__ feet_est, TIO* __restrict__ sigma, TIO* __restrict__ nis_out, const int64_t B, const int T) {
+#pragma clang fp contract(off)
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= 4 * B) return;   // (whole quads leave: the lane moves below see all four lanes or none)
+  const int64_t b = i / 4;
+  const int l = (int)(i % 4), a = l < 3 ? l : 2;
+  const double nan = __builtin_nan("");
+  double* const sb = state ? state + b * EST_STATE : nullptr;
+  const bool fresh = !sb || sb[EST_LIVE] == 0.0;
+  double qh[4], xi[6], U[21], hl[4] = {0.0, 0.0, 0.0, 0.0};
+  bool mine = true;   // this lane's operands are finite
+  if (fresh) {
+    const TIO* x0 = init + 12 * b;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) mine = mine && isfinite((double)x0[c]) && isfinite((double)x0[3 + c]) && isfinite((double)x0[9 + c]);
+    plant_rotvec_to_quat((double)x0[0], (double)x0[1], (double)x0[2], qh);
+    xi[0] = (double)x0[3 + a]; xi[1] = (double)x0[9 + a];
+#pragma unroll
+    for (int c = 2; c < 6; ++c) xi[c] = 0.0;   // (the feet are set on row 0, from its rho)
+#pragma unroll
+    for (int r = 0; r < 6; ++r)
+#pragma unroll
+      for (int c = r; c < 6; ++c) U[est_ut(r, c)] = r != c ? 0.0 : (r == 0 ? par.p0p : (r == 1 ? par.p0v : par.p0f));
+  } else {
+    mine = isfinite(sb[EST_LIVE]);
+#pragma unroll
+    for (int c = 0; c < 4; ++c) { qh[c] = sb[c]; mine = mine && isfinite(qh[c]); }
+#pragma unroll
+    for (int c = 0; c < 6; ++c) { xi[c] = sb[EST_XI + 6 * a + c]; mine = mine && isfinite(xi[c]); }
+#pragma unroll
+    for (int r = 0; r < 6; ++r)
+#pragma unroll
+      for (int c = r; c < 6; ++c) { U[est_ut(r, c)] = sb[EST_P + 36 * a + 6 * r + c]; mine = mine && isfinite(U[est_ut(r, c)]); }
+  }
+  if (height) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) { hl[j] = (double)height[4 * b + j]; mine = mine && isfinite(hl[j]); }
+  }
+  const bool hgt = height != nullptr && a == 2;
+  bool ok = true;   // the robot's flag: the same in its four lanes
+  for (int t = 0; t < T; ++t) {
+    const int64_t row = b * T + t;
+    const TIO* m = imu + 6 * row;
+    const V3 gy = load3(m), sf = load3(m + 3);
+    const double ql[3] = {(double)q[3 * (4 * row + l)], (double)q[3 * (4 * row + l) + 1], (double)q[3 * (4 * row + l) + 2]};
+    const V3 qr = load3(qd + 3 * (4 * row + l));
+    double tr[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) tr[j] = trust ? (double)trust[4 * row + j] : (contact[4 * row + j] != 0 ? 1.0 : 0.0);
+    mine = mine && fin3(gy) && fin3(sf) && fin3(qr) && isfinite(ql[0]) && isfinite(ql[1]) && isfinite(ql[2]) && isfinite(tr[0]) &&
+           isfinite(tr[1]) && isfinite(tr[2]) && isfinite(tr[3]);
+    float bad = mine ? 0.0f : 1.0f;
+    bad = bad + dpp_mov<0xB1>(bad);
+    bad = bad + dpp_mov<0x4E>(bad);
+    ok = ok && bad == 0.0f;
+    // 1. the leg's foot and its velocity relative to the CoM, world axes
+    const M3 R = est_rot(qh);
+    double pf[3], J[9];
+    leg_fk_jac(geo, l, ql, pf, J);
+    const V3 pb = {pf[0], pf[1], pf[2]};
+    const V3 jq = {(J[0] * qr.x + J[1] * qr.y) + J[2] * qr.z, (J[3] * qr.x + J[4] * qr.y) + J[5] * qr.z, (J[6] * qr.x + J[7] * qr.y) + J[8] * qr.z};
+    const V3 rho = est_mv(R, pb), rhod = est_mv(R, est_add(est_cross(gy, pb), jq));
+    // ... and what this lane's axis sees of the four legs
+    const double zr[4] = {est_pick(a, quad_bcast<0>(rho.x), quad_bcast<0>(rho.y), quad_bcast<0>(rho.z)),
+                          est_pick(a, quad_bcast<1>(rho.x), quad_bcast<1>(rho.y), quad_bcast<1>(rho.z)),
+                          est_pick(a, quad_bcast<2>(rho.x), quad_bcast<2>(rho.y), quad_bcast<2>(rho.z)),
+                          est_pick(a, quad_bcast<3>(rho.x), quad_bcast<3>(rho.y), quad_bcast<3>(rho.z))};
+    const double zv[4] = {est_pick(a, quad_bcast<0>(rhod.x), quad_bcast<0>(rhod.y), quad_bcast<0>(rhod.z)),
+                          est_pick(a, quad_bcast<1>(rhod.x), quad_bcast<1>(rhod.y), quad_bcast<1>(rhod.z)),
+                          est_pick(a, quad_bcast<2>(rhod.x), quad_bcast<2>(rhod.y), quad_bcast<2>(rhod.z)),
+                          est_pick(a, quad_bcast<3>(rhod.x), quad_bcast<3>(rhod.y), quad_bcast<3>(rhod.z))};
+    if (fresh && t == 0) {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) xi[2 + j] = xi[0] + zr[j];
+    }
+    // 2. the scalar updates
+    double na = 0.0;
+    est_leg<0>(par, xi, U, zr[0], zv[0], tr[0], hgt, hl[0], na);
+    est_leg<1>(par, xi, U, zr[1], zv[1], tr[1], hgt, hl[1], na);
+    est_leg<2>(par, xi, U, zr[2], zv[2], tr[2], hgt, hl[2], na);
+    est_leg<3>(par, xi, U, zr[3], zv[3], tr[3], hgt, hl[3], na);
+    const double nis = (quad_bcast<0>(na) + quad_bcast<1>(na)) + quad_bcast<2>(na);
+    // 3. outputs: lanes 0..2 their axis, lane 3 the orientation's
+    const V3 om = est_mv(R, gy);
+    if (l < 3) {
+      if (est) { est[12 * row + 3 + a] = (TIO)(ok ? xi[0] : nan); est[12 * row + 9 + a] = (TIO)(ok ? xi[1] : nan); }
+      if (feet_est) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) feet_est[3 * (4 * row + j) + a] = (TIO)(ok ? xi[2 + j] : nan);
+      }
+      if (sigma) { sigma[6 * row + a] = (TIO)(ok ? sqrt(U[est_ut(0, 0)]) : nan); sigma[6 * row + 3 + a] = (TIO)(ok ? sqrt(U[est_ut(1, 1)]) : nan); }
+    } else {
+      if (est) {
+        double th[3];
+        plant_quat_to_rotvec(qh, th);
+        store3(est + 12 * row, ok, V3{th[0], th[1], th[2]});
+        store3(est + 12 * row + 6, ok, om);
+      }
+      if (nis_out) nis_out[row] = (TIO)(ok ? nis : nan);
+    }
+    // 4. predict
+    const double aw = ((est_pick(a, R.r0.x, R.r1.x, R.r2.x) * sf.x + est_pick(a, R.r0.y, R.r1.y, R.r2.y) * sf.y) +
+                       est_pick(a, R.r0.z, R.r1.z, R.r2.z) * sf.z) + (a == 2 ? par.g : 0.0);
+    xi[0] = (xi[0] + par.d * xi[1]) + par.hd2 * aw;
+    xi[1] = xi[1] + par.d * aw;
+    U[est_ut(0, 0)] = (U[est_ut(0, 0)] + par.d * U[est_ut(0, 1)]) + par.d * (U[est_ut(0, 1)] + par.d * U[est_ut(1, 1)]);
+#pragma unroll
+    for (int j = 1; j < 6; ++j) U[est_ut(0, j)] = U[est_ut(0, j)] + par.d * U[est_ut(1, j)];
+    U[est_ut(0, 0)] = U[est_ut(0, 0)] + par.d * par.qp;
+    U[est_ut(1, 1)] = U[est_ut(1, 1)] + par.d * par.qv;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) U[est_ut(2 + j, 2 + j)] = U[est_ut(2 + j, 2 + j)] + par.d * (par.qf * (1.0 + (1.0 - tr[j]) * par.ks));
+    const double sn = est_norm(sf), ga = fabs(par.g);
+    const bool pull = sn > 0.0;
+    const V3 sh = {pull ? sf.x / sn : 0.0, pull ? sf.y / sn : 0.0, pull ? sf.z / sn : 0.0};
+    const double c0 = 1.0 - fabs(sn - ga) / ga;
+    const double kap = pull ? par.kappa * (c0 < 0.0 ? 0.0 : (c0 > 1.0 ? 1.0 : c0)) : 0.0;
+    const V3 cr = est_cross(sh, R.r2);
+    const V3 wh = est_mv(R, V3{gy.x + kap * cr.x, gy.y + kap * cr.y, gy.z + kap * cr.z});
+    double dq[4];
+    plant_rotvec_to_quat(par.d * wh.x, par.d * wh.y, par.d * wh.z, dq);
+    const double n0 = ((dq[0] * qh[0] - dq[1] * qh[1]) - dq[2] * qh[2]) - dq[3] * qh[3];
+    const double n1 = ((dq[0] * qh[1] + dq[1] * qh[0]) + dq[2] * qh[3]) - dq[3] * qh[2];
+    const double n2 = ((dq[0] * qh[2] - dq[1] * qh[3]) + dq[2] * qh[0]) + dq[3] * qh[1];
+    const double n3 = ((dq[0] * qh[3] + dq[1] * qh[2]) - dq[2] * qh[1]) + dq[3] * qh[0];
+    const double nq = sqrt(((n0 * n0 + n1 * n1) + n2 * n2) + n3 * n3);
+    qh[0] = n0 / nq; qh[1] = n1 / nq; qh[2] = n2 / nq; qh[3] = n3 / nq;
+  }
+  if (!sb) return;
+  if (l < 3) {
+#pragma unroll
+    for (int c = 0; c < 6; ++c) sb[EST_XI + 6 * a + c] = ok ? xi[c] : nan;
+#pragma unroll
+    for (int r = 0; r < 6; ++r)
+#pragma unroll
+      for (int c = 0; c < 6; ++c) sb[EST_P + 36 * a + 6 * r + c] = ok ? U[est_sym(r, c)] : nan;
+  } else {
+#pragma unroll
+    for (int c = 0; c < 4; ++c) sb[c] = ok ? qh[c] : nan;
+    sb[EST_LIVE] = ok ? 1.0 : nan;
+  }
+}
+
+// mpcqp_imu_log: one lane per row of the log.  base_acc / body / bias / noise may be null.
+template <typename TIO>
+__global__ void __launch_bounds__(256)
+mpcqp_imu_log_kernel(const TIO* __restrict__ actual, const TIO* __restrict__ forces, const TIO* __restrict__ base_acc,
+                     const TIO* __restrict__ body, const TIO* __restrict__ bias, const TIO* __restrict__ noise, const PlantModel model,
+                     const double g, TIO* __restrict__ imu, const int64_t rows, const int64_t T) {
+#pragma clang fp contract(off)
+  const int64_t row = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (row >= rows) return;
+  const int64_t b = row / T;
+  const TIO* x = actual + 12 * row;
+  const V3 th = load3(x), om = load3(x + 6);
+  double qt[4];
+  plant_rotvec_to_quat(th.x, th.y, th.z, qt);
+  const M3 R = est_rot(qt);
+  bool fin = fin3(th) && fin3(om);
+  V3 aw;
+  if (base_acc) {
+    const TIO* s = base_acc + 6 * row;
+    aw = load3(s + 3);
+    fin = fin && fin3(load3(s)) && fin3(aw);
+  } else {   // the unpushed plant's right-hand side: the sum across the four legs in mpcqp_leg_effort's order, (0 + 1) + (2 + 3)
+    const TIO* f = forces + 12 * row;
+    double bd[7], Ii[6];
+    plant_body_row(body, model, b, bd);
+    const double Ib[6] = {bd[1], bd[2], bd[3], bd[4], bd[5], bd[6]};
+    fin = fin && plant_inertia(bd[0], Ib, Ii);
+    const V3 f0 = load3(f), f1 = load3(f + 3), f2 = load3(f + 6), f3 = load3(f + 9);
+    const V3 Fs = est_add(est_add(f0, f1), est_add(f2, f3));
+    fin = fin && fin3(f0) && fin3(f1) && fin3(f2) && fin3(f3);
+    aw = {Fs.x / bd[0], Fs.y / bd[0], Fs.z / bd[0] + g};
+  }
+  const V3 sp = {aw.x, aw.y, aw.z - g};
+  V3 gyro = est_mtv(R, om), acc = est_mtv(R, sp);
+  if (bias) {
+    const V3 bg = load3(bias + 6 * b), ba = load3(bias + 6 * b + 3);
+    gyro = est_add(gyro, bg); acc = est_add(acc, ba);
+    fin = fin && fin3(bg) && fin3(ba);
+  }
+  if (noise) {
+    const V3 ng = load3(noise + 6 * row), na = load3(noise + 6 * row + 3);
+    gyro = est_add(gyro, ng); acc = est_add(acc, na);
+    fin = fin && fin3(ng) && fin3(na);
+  }
+  store3(imu + 6 * row, fin, gyro);
+  store3(imu + 6 * row + 3, fin, acc);
+}
+
+}  // namespace

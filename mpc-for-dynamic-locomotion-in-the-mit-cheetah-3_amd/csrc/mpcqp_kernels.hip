@@ -3,7 +3,8 @@
 // Replaces, for a batch of B independent robots, the solve the reference performs once per control tick:
 // CasADi Opti('conic') -> OSQP on the QP of src/mpc.py:58-173, filled at src/mpc.py:242-255, solved at :258.
 //
-// This translation unit is the C-ABI of include/mpcqp.h, mpcqp_plan.h, mpcqp_sim.h, mpcqp_model.h, mpcqp_joints.h, mpcqp_actuators.h and mpcqp_slip.h,
+// This translation unit is the C-ABI of include/mpcqp.h, mpcqp_plan.h, mpcqp_sim.h, mpcqp_model.h, mpcqp_joints.h, mpcqp_actuators.h, mpcqp_slip.h and
+// mpcqp_estimate.h,
 // in three parts: the handle; its host helpers in one anonymous namespace, in order of use (errors, I/O-type dispatch, the solve, workspaces,
 // the device guard and the launch tail `on_device`, grids, the policy behind the configuration's defaults, the engine's tables, the roll-out
 // loops, the leg rows, the row tables); one extern "C" block of entry points, each its own checks and its own launches.  The device code is in
@@ -22,6 +23,7 @@
 //   mpcqp_joints.h       closed-form leg inverse kinematics and the joint-space log of a roll-out
 //   mpcqp_actuators.h    per-robot actuator rows: the conversion of the caller's table and the torque-speed envelope the leg kernels share
 //   mpcqp_slip.h         stance feet that slide: the stance drive's rule with slip kinematics, and the foot move of its roll-out
+//   mpcqp_estimate.h     the torso state from an IMU and leg kinematics: the IMU rows of a log and the filter over them
 // DESIGN.md has the derivations.
 
 #include "mpcqp_wrench.h"
@@ -36,6 +38,7 @@
 #include "mpcqp_drive.h"
 #include "mpcqp_slip.h"
 #include "mpcqp_score.h"
+#include "mpcqp_estimate.h"
 
 #include <cstdio>
 #include <cstdlib>
@@ -894,6 +897,21 @@ int rollout_legs_run(mpcqp_handle h, const char* who, int64_t B, int32_t T, void
     });
 }
 
+// The estimator's parameters of an entry point `who` (null: the defaults), checked and with the handle's delta.
+int estimator_row(mpcqp_handle h, const char* who, const MpcQpEstimator* par, EstPar& e) {
+  MpcQpEstimator dflt;
+  if (!par) { (void)mpcqp_default_estimator(&dflt); par = &dflt; }
+  if (par->size != sizeof(MpcQpEstimator)) return bad(h, who, "estimator struct size mismatch");
+  const double nn[11] = {par->kappa, par->q_p, par->q_v, par->q_f, par->r_p, par->r_v, par->r_z, par->k_swing, par->p0_p, par->p0_v, par->p0_f};
+  if (!std::isfinite(par->gravity) || !(par->gravity < 0)) return bad(h, who, "estimator: gravity must be finite and negative");
+  for (const double v : nn)
+    if (!std::isfinite(v) || !(v >= 0)) return bad(h, who, "estimator: kappa, q_*, r_*, k_swing and p0_* must be finite and non-negative");
+  const double d = h->cfg.delta;
+  e = {par->gravity, par->kappa, par->q_p, par->q_v, par->q_f, par->r_p, par->r_v, par->r_z, par->k_swing, par->p0_p, par->p0_v, par->p0_f,
+       d, 0.5 * d * d};
+  return MPCQP_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1565,6 +1583,60 @@ int mpcqp_rollout_score(mpcqp_handle h, int64_t B, int32_t T, const void* actual
     // one wave per robot
     hipLaunchKernelGGL((mpcqp_score_kernel<TIO>), blocks(B, 4), dim3(256), 0, (hipStream_t)stream, in, rule->z_frac, rule->tilt_max,
                        (int)(accumulate != 0), score, (int)B, (int)T);
+  });
+}
+
+int mpcqp_default_estimator(MpcQpEstimator* par) {
+  if (!par) return MPCQP_EINVAL;
+  memset(par, 0, sizeof(*par));
+  par->size = (uint32_t)sizeof(*par);
+  par->gravity = -9.81;
+  par->kappa = 2.0;
+  par->q_p = 0.02; par->q_v = 0.02; par->q_f = 0.002;
+  par->r_p = 0.001; par->r_v = 0.1; par->r_z = 0.001;
+  par->k_swing = 100.0;
+  par->p0_p = 0.01; par->p0_v = 1.0; par->p0_f = 0.01;
+  return MPCQP_OK;
+}
+
+int mpcqp_imu_log(mpcqp_handle h, int64_t B, int32_t T, const void* actual, const void* forces, const void* feet, const void* base_acc,
+                  const void* body, const void* bias, const void* noise, const MpcQpEstimator* par, void* imu, void* stream) {
+  if (!h) return MPCQP_EINVAL;
+  if (B < 0 || B > 0x7fffffff || T < 0 || B * (int64_t)T > 0x1fffffff) return fail(h, MPCQP_EINVAL, "mpcqp_imu_log: size out of range");
+  if (B > 0 && T > 0 && (!actual || !forces || !feet)) return fail(h, MPCQP_EINVAL, "mpcqp_imu_log: null buffer (actual, forces, feet)");
+  if (B > 0 && T > 0 && !imu) return fail(h, MPCQP_EINVAL, "mpcqp_imu_log: null imu buffer");
+  EstPar e;
+  if (const int rc = estimator_row(h, "mpcqp_imu_log", par, e)) return rc;
+  if (B == 0 || T == 0) return MPCQP_OK;
+  const int64_t rows = B * T;
+  return on_device(h, "imu log kernel launch", [&](auto tag) {
+    using TIO = decltype(tag);
+    hipLaunchKernelGGL((mpcqp_imu_log_kernel<TIO>), blocks(rows), dim3(256), 0, (hipStream_t)stream, (const TIO*)actual, (const TIO*)forces,
+                       (const TIO*)base_acc, (const TIO*)body, (const TIO*)bias, (const TIO*)noise, plant_model(h), e.g, (TIO*)imu, rows,
+                       (int64_t)T);
+  });
+}
+
+int mpcqp_estimate_track(mpcqp_handle h, int64_t B, int32_t T, const void* imu, const void* q, const void* qd, const uint8_t* contact_log,
+                         const void* trust, const void* height, const void* init, const MpcQpEstimator* par, const MpcQpLegGeometry* geo,
+                         double* state, void* est, void* feet_est, void* sigma, void* nis, void* stream) {
+  if (!h) return MPCQP_EINVAL;
+  if (B < 0 || B > 0x7fffffff || T < 0 || B * (int64_t)T > 0x1fffffff) return fail(h, MPCQP_EINVAL, "mpcqp_estimate_track: size out of range");
+  if (!est && !feet_est && !sigma && !nis)
+    return fail(h, MPCQP_EINVAL, "mpcqp_estimate_track: no output buffer (est, feet_est, sigma and nis are all null)");
+  if (B > 0 && T > 0 && (!imu || !q || !qd)) return fail(h, MPCQP_EINVAL, "mpcqp_estimate_track: null buffer (imu, q, qd)");
+  if (B > 0 && T > 0 && !init) return fail(h, MPCQP_EINVAL, "mpcqp_estimate_track: null init buffer");
+  if (B > 0 && T > 0 && !trust && !contact_log) return fail(h, MPCQP_EINVAL, "mpcqp_estimate_track: null contact_log buffer without trust");
+  EstPar e;
+  if (const int rc = estimator_row(h, "mpcqp_estimate_track", par, e)) return rc;
+  LegGeoDev g;
+  if (const int rc = leg_geometry(h, "mpcqp_estimate_track", geo, false, g)) return rc;
+  if (B == 0 || T == 0) return MPCQP_OK;
+  return on_device(h, "estimate track kernel launch", [&](auto tag) {
+    using TIO = decltype(tag);
+    hipLaunchKernelGGL((mpcqp_estimate_track_kernel<TIO>), leg_grid(B), dim3(256), 0, (hipStream_t)stream, (const TIO*)imu, (const TIO*)q,
+                       (const TIO*)qd, contact_log, (const TIO*)trust, (const TIO*)height, (const TIO*)init, e, g, state, (TIO*)est,
+                       (TIO*)feet_est, (TIO*)sigma, (TIO*)nis, B, (int)T);
   });
 }
 

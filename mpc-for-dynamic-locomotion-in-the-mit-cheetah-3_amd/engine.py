@@ -686,5 +686,57 @@ class MPCBatch:
                                       _score.rule_struct(rule), st.cuda_stream)
         return score
 
+    def imu_log(self, logs, base_acc=None, body=None, bias=None, noise=None, estimator=None, stream=None):
+        """What an IMU at the CoM reads on every row of a roll-out's logs (include/mpcqp_estimate.h, mpcqp_imu_log; the host counterpart
+        is estimator.imu_log_host): `logs` with "actual", "forces" [B,T,12] and "feet_log" [B,T,4,3]; base_acc [B,T,6] = (alpha, a) or
+        None for the unpushed plant's right-hand side formed with body [B,7] (None = the engine's model); bias [B,6] and noise [B,T,6]
+        or None, added as given (draw the noise with torch); `estimator` None, a dict of estimator.estimator_row's fields or an
+        MpcQpEstimator -> imu [B,T,6] = (gyro, specific force) in the torso's axes.  Asynchronous on `stream`."""
+        from . import estimator as _est
+        actual, forces, feet = logs.get("actual"), logs.get("forces"), logs.get("feet_log")
+        if actual is None or actual.dim() != 3:
+            raise ValueError("imu_log needs the logs of a roll-out run with log=True")
+        B, T = int(actual.shape[0]), int(actual.shape[1])
+        rows = ((B, T, 6), self.tdtype)
+        check_operands(self.device, (("actual", actual, (B, T, 12), self.tdtype), ("forces", forces, (B, T, 12), self.tdtype),
+                                     ("feet_log", feet, (B, T, 4, 3), self.tdtype), ("base_acc", base_acc, *rows),
+                                     ("body", body, (B, 7), self.tdtype), ("bias", bias, (B, 6), self.tdtype), ("noise", noise, *rows)),
+                       optional=("base_acc", "body", "bias", "noise"))
+        st = self._stream(stream)
+        imu, = self._alloc(stream, rows)
+        self.engine.imu_log_ptr(B, T, actual.data_ptr(), forces.data_ptr(), feet.data_ptr(), _ptr(base_acc), _ptr(body), _ptr(bias),
+                                _ptr(noise), imu.data_ptr(), _est.estimator_struct(estimator), st.cuda_stream)
+        return imu
+
+    from .estimator import OUT as EST_OUT      # ("est", "feet", "sigma", "nis"): the host counterpart's names, in the C order
+
+    def estimate_track(self, imu, q, qd, contact_log, init, trust=None, height=None, state=None, estimator=None, geometry=None,
+                       want=EST_OUT, stream=None):
+        """The torso state estimated from the IMU and the leg encoders over the rows of a log (include/mpcqp_estimate.h,
+        mpcqp_estimate_track, which has the rule; the host counterparts are estimator.estimate_track_host and estimate_joint_host):
+        imu [B,T,6] as `imu_log` returns it, q, qd [B,T,4,3] the "q" / "qd" logs of `rollout_legs`, `rollout_drive`, `rollout_slip` or
+        of `joint_rates`, contact_log uint8 [B,T,4], init [B,12] in the layout of an `actual` row; trust [B,T,4] in [0,1] or None
+        (contact != 0), height [B,4] the ground under each foot or None, state float64 [B,131] advanced IN PLACE (zeros: start from
+        init) or None -> {"est" [B,T,12] in the layout of `actual`, "feet" [B,T,4,3], "sigma" [B,T,6], "nis" [B,T]}; an output not in
+        `want` is None.  Asynchronous on `stream`."""
+        from . import estimator as _est
+        torch = _torch()
+        B, T = int(imu.shape[0]), int(imu.shape[1]) if imu.dim() == 3 else -1
+        legs = ((B, T, 4, 3), self.tdtype)
+        check_operands(self.device, (("imu", imu, (B, T, 6), self.tdtype), ("q", q, *legs), ("qd", qd, *legs),
+                                     ("contact_log", contact_log, (B, T, 4), torch.uint8), ("init", init, (B, 12), self.tdtype),
+                                     ("trust", trust, (B, T, 4), self.tdtype), ("height", height, (B, 4), self.tdtype),
+                                     ("state", state, (B, _capi.EST_STATE), torch.float64)), optional=("trust", "height", "state"))
+        unknown = set(want) - set(self.EST_OUT)
+        if unknown or not want:
+            raise ValueError(f"want must name at least one of {self.EST_OUT}, got {tuple(want)}")
+        st = self._stream(stream)
+        spec = {"est": ((B, T, 12), self.tdtype), "feet": legs, "sigma": ((B, T, 6), self.tdtype), "nis": ((B, T), self.tdtype)}
+        out = dict(zip(self.EST_OUT, self._alloc(stream, *[spec[k] if k in want else None for k in self.EST_OUT])))
+        self.engine.estimate_track_ptr(B, T, imu.data_ptr(), q.data_ptr(), qd.data_ptr(), contact_log.data_ptr(), _ptr(trust), _ptr(height),
+                                       init.data_ptr(), _ptr(state), *[_ptr(out[k]) for k in self.EST_OUT],
+                                       _est.estimator_struct(estimator), geometry, st.cuda_stream)
+        return out
+
     def last_kernel_ms(self):
         return self.engine.last_kernel_ms()
