@@ -1,5 +1,5 @@
 """ctypes binding of the C-ABI declared in include/mpcqp.h and its product-only extensions include/mpcqp_plan.h, mpcqp_sim.h, mpcqp_model.h,
-mpcqp_joints.h, mpcqp_actuators.h, mpcqp_slip.h and mpcqp_estimate.h.
+mpcqp_joints.h, mpcqp_actuators.h, mpcqp_slip.h, mpcqp_estimate.h and mpcqp_observe.h.
 
 The product path loads ``csrc/libmpcqp.so`` (hand-written HIP for gfx950) and nothing else: if that library is
 missing or cannot be loaded, importing the engine raises -- there is no CPU fallback.  The binding itself is
@@ -200,6 +200,15 @@ ESTIMATE_ABI = {
 }
 ESTIMATE_SYMBOLS = tuple(row[0] for row in ESTIMATE_ABI[ESTIMATE_HEADER])
 EST_STATE = 131   # include/mpcqp_estimate.h, MPCQP_EST_STATE: doubles per robot of the filter state
+# include/mpcqp_observe.h, the slip roll-out with the estimator inside its tick loop, likewise: `has_observe`.
+OBSERVE_HEADER = "mpcqp_observe.h"
+OBSERVE_ABI = {
+    OBSERVE_HEADER: (  # sensors and the state estimator inside the roll-out
+        ("mpcqp_rollout_observe", c_int, SLIP_ABI[SLIP_HEADER][1][2][:-1] + (_I32,) + (_P,) * 6 + (_EST,) + (_P,) * 8),
+    ),
+}
+OBSERVE_SYMBOLS = tuple(row[0] for row in OBSERVE_ABI[OBSERVE_HEADER])
+FEED_TRUTH, FEED_ESTIMATE = 0, 1   # include/mpcqp_observe.h, MPCQP_FEED_*
 # The swing-leg plant of include/mpcqp_joints.h came after the rest of that header: a product library built before it still has the
 # header's other calls (`has_joints`) and is told apart by `has_legsim`.
 LEGSIM_SYMBOLS = ("mpcqp_leg_accel", "mpcqp_swing_track")
@@ -220,9 +229,9 @@ DRIVE_SLIDING = 128   # include/mpcqp_slip.h, MPCQP_DRIVE_SLIDING: the stance fo
 
 
 class Library:
-    """A loaded shared object exporting the mpcqp C-ABI.  `has_plan`, `has_sim`, `has_model`, `has_joints`, `has_actuators`, `has_slip` and
-    `has_estimate` say whether it exports all of include/mpcqp_plan.h, mpcqp_sim.h, mpcqp_model.h, mpcqp_joints.h, mpcqp_actuators.h,
-    mpcqp_slip.h and mpcqp_estimate.h (of mpcqp_joints.h: all but LEGSIM_SYMBOLS, which `has_legsim`
+    """A loaded shared object exporting the mpcqp C-ABI.  `has_plan`, `has_sim`, `has_model`, `has_joints`, `has_actuators`, `has_slip`,
+    `has_estimate` and `has_observe` say whether it exports all of include/mpcqp_plan.h, mpcqp_sim.h, mpcqp_model.h, mpcqp_joints.h,
+    mpcqp_actuators.h, mpcqp_slip.h, mpcqp_estimate.h and mpcqp_observe.h (of mpcqp_joints.h: all but LEGSIM_SYMBOLS, which `has_legsim`
     answers for; of mpcqp_sim.h: all but LEGROLL_SYMBOLS, SCORE_SYMBOLS and DRIVE_SYMBOLS, `has_legroll`, `has_score` and `has_drive`).  An
     extension header's calls are bound only when the library
     has them all; `partial=True` binds whichever it has (an older build of the product library, in a comparison tool)."""
@@ -237,7 +246,7 @@ class Library:
         self.has_legroll = all(hasattr(self.lib, name) for name in LEGROLL_SYMBOLS)
         self.has_score = all(hasattr(self.lib, name) for name in SCORE_SYMBOLS)
         self.has_drive = all(hasattr(self.lib, name) for name in DRIVE_SYMBOLS)
-        for header, rows in {**ABI, **ACTUATORS_ABI, **SLIP_ABI, **ESTIMATE_ABI}.items():
+        for header, rows in {**ABI, **ACTUATORS_ABI, **SLIP_ABI, **ESTIMATE_ABI, **OBSERVE_ABI}.items():
             have = header == CORE_HEADER or all(hasattr(self.lib, row[0]) for row in rows if row[0] not in _GATED)
             if header != CORE_HEADER:
                 setattr(self, "has_" + header[len("mpcqp_"):-len(".h")], have)
@@ -436,6 +445,20 @@ class Engine:
         self._call("mpcqp_rollout_slip", B, T, x, ref, feet, legs, gait, stand, gain, tick, mu, body, push, push_ticks, substeps, step_height,
                    gains, leg_substeps, geometry, inertia, land, drive, ground, foot_mass, slip, actual, desired, forces, feet_log, contact_log,
                    solved, swing_log, q_log, qd_log, tau_log, foot_log, err_log, flag_log, miss_log, cmd_log, slip_log, disp_log, stream)
+
+    def rollout_observe_ptr(self, B, T, x, ref, feet, legs, gait, stand, gain, tick, mu, body, push, push_ticks, substeps, step_height, gains,
+                            leg_substeps, land, drive, ground, foot_mass, slip, actual, desired, forces, feet_log, contact_log, solved,
+                            swing_log, q_log, qd_log, tau_log, foot_log, err_log, flag_log, miss_log, cmd_log, slip_log, disp_log, imu_log,
+                            q_enc_log, qd_enc_log, est_log, feet_est_log, sigma_log, nis_log, feed, est_state, est_init=0, height=0, bias=0,
+                            noise=0, enc_noise=0, estimator=None, geometry=None, inertia=None, stream=0):
+        """`rollout_slip_ptr` with sensors and the state estimator inside the tick loop (include/mpcqp_observe.h, mpcqp_rollout_observe).
+        As in the other roll-outs every log comes before what is not one: the seven logs of the estimator follow disp_log here, the feed,
+        the filter state and the sensors' operands follow them (the C order has them in between)."""
+        self._call("mpcqp_rollout_observe", B, T, x, ref, feet, legs, gait, stand, gain, tick, mu, body, push, push_ticks, substeps, step_height,
+                   gains, leg_substeps, geometry, inertia, land, drive, ground, foot_mass, slip, actual, desired, forces, feet_log, contact_log,
+                   solved, swing_log, q_log, qd_log, tau_log, foot_log, err_log, flag_log, miss_log, cmd_log, slip_log, disp_log, feed,
+                   est_state, est_init, height, bias, noise, enc_noise, estimator, imu_log, q_enc_log, qd_enc_log, est_log, feet_est_log,
+                   sigma_log, nis_log, stream)
 
     # (`estimator` is an MpcQpEstimator or None = the defaults)
     def imu_log_ptr(self, B, T, actual, forces, feet, base_acc, body, bias, noise, imu, estimator=None, stream=0):

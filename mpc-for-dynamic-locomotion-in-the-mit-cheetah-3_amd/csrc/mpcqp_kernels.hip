@@ -39,6 +39,7 @@
 #include "mpcqp_slip.h"
 #include "mpcqp_score.h"
 #include "mpcqp_estimate.h"
+#include "mpcqp_observe.h"
 
 #include <cstdio>
 #include <cstdlib>
@@ -353,6 +354,15 @@ T* slip_ws(void* base, int64_t B, size_t N) {
 }
 constexpr size_t slip_tail(size_t el) { return 8 * el; }   // bytes per robot of the displacement buffer
 
+// The side buffers of mpcqp_rollout_observe behind the displacement buffer (which ends on a multiple of 8 bytes): the state the
+// controller reads, x^ [B,13] and f^eet [B,4,3], and the sensor row its predict step reads back, [B,OBS_SENSE], in the I/O type.
+template <typename T>
+ObsWs<T> observe_ws(void* base, int64_t B, size_t N) {
+  T* xhat = slip_ws<T>(base, B, N) + (size_t)B * 8;
+  return {xhat, xhat + (size_t)B * 13, xhat + (size_t)B * 25};
+}
+constexpr size_t observe_tail(size_t el) { return (25 + OBS_SENSE) * el; }   // bytes per robot of the three
+
 // Tuple workspace of the gait entry point and the roll-out, grown like the rest of the batch-dependent workspace.
 int reserve_gait(mpcqp_engine* e, int64_t B) {
   if (B <= e->gait_cap) return MPCQP_OK;
@@ -362,10 +372,13 @@ int reserve_gait(mpcqp_engine* e, int64_t B) {
   return MPCQP_OK;
 }
 
-// Result workspace of the roll-out.  Zeros = "no guess" for a warm-started engine.
+// Result workspace of the roll-out.  Zeros = "no guess" for a warm-started engine.  One reserve serves every roll-out entry point, so
+// all of them pay for the side buffers of the drive, the slip rule and mpcqp_rollout_observe (the last: 33 I/O elements per robot),
+// whichever of them the handle goes on to call.
 int reserve_roll(mpcqp_engine* e, int64_t B) {
   if (B <= e->roll_cap) return MPCQP_OK;
-  const size_t bytes = ws_bytes(B, (size_t)e->cfg.N, io_size(e), 2 * sizeof(int32_t) + drive_tail(io_size(e)) + slip_tail(io_size(e))) + 8;
+  const size_t bytes = ws_bytes(B, (size_t)e->cfg.N, io_size(e), 2 * sizeof(int32_t) + drive_tail(io_size(e)) + slip_tail(io_size(e)) +
+                                                                               observe_tail(io_size(e))) + 8;
   if (!grow(e->roll_mem, bytes, bytes)) return MPCQP_ENOMEM;
   e->roll_cap = B;
   return MPCQP_OK;
@@ -620,12 +633,15 @@ PlantModel plant_model(const mpcqp_engine* h) {
 }
 
 // The roll-out loop behind mpcqp_rollout, mpcqp_rollout_plant and mpcqp_rollout_phase: workspace reserved once, then 3 launches per
-// tick on the caller's stream, no host synchronisation and no copies in between.  expand(tag, x, ref, w) launches the tick's expand
+// tick on the caller's stream, no host synchronisation and no copies in between.  expand(tag, x, ref, w, it) launches the tick's expand
 // kernel into the tuple workspace w, advance(tag, x, ref, o, it) the advance kernel on the results o; tag carries the I/O type.
+// xc(tag) is the state the controller reads, the solve's x0 -- a buffer the expand fills inside the roll-out's reserve, which is why it
+// is asked for after the reserve --, or null for x itself.
 // The caller has made its checks; the device guard is here.  (mpcqp_last_kernel_ms after a roll-out: all T ticks)
-template <typename Expand, typename Advance>
+struct ReadsPlant { template <typename TIO> const TIO* operator()(TIO) const { return nullptr; } };
+template <typename Expand, typename Advance, typename Reads = ReadsPlant>
 int rollout_loop(mpcqp_handle h, const char* who, int64_t B, int32_t T, void* x, void* ref, const void* mu, void* stream, Expand&& expand,
-                 Advance&& advance) {
+                 Advance&& advance, Reads&& xc = ReadsPlant()) {
   GUARD(h);
   if (reserve_workspace(h, B) != MPCQP_OK || reserve_gait(h, B) != MPCQP_OK || reserve_roll(h, B) != MPCQP_OK) {
     snprintf(h->err, sizeof(h->err), "%s: workspace allocation failed", who);
@@ -637,11 +653,12 @@ int rollout_loop(mpcqp_handle h, const char* who, int64_t B, int32_t T, void* x,
     using TIO = decltype(tag);
     const TupleWs<TIO> w = tuple_ws<TIO>(h->gait_mem, B, N);
     const ResultWs<TIO> o = result_ws<TIO>(h->roll_mem, B, N);
-    const FastIn<TIO> in = tuple_in<TIO>(h, x, w.r, w.contact, w.xdes, mu, o.u);
+    const TIO* xr = xc(tag);
+    const FastIn<TIO> in = tuple_in<TIO>(h, xr ? (const void*)xr : x, w.r, w.contact, w.xdes, mu, o.u);
     TIO* xs = (TIO*)x;
     TIO* rf = (TIO*)ref;
     for (int it = 0; it < T; ++it) {
-      expand(tag, xs, rf, w);
+      expand(tag, xs, rf, w, it);
       hipError_t e = enqueue_solve<TIO>(h, B, in, o.u, o.X, o.status, o.iters, nullptr, st);
       if (e != hipSuccess) return e;
       advance(tag, xs, rf, o, it);
@@ -693,7 +710,7 @@ int rollout_run(mpcqp_handle h, int64_t B, int32_t T, int32_t S, void* x, void* 
   const dim3 ge = expand_grid(B, N), ga = advance_grid(B), nt(256);
   hipStream_t st = (hipStream_t)stream;
   return rollout_loop(h, "mpcqp_rollout", B, T, x, ref, mu, stream,
-    [&](auto tag, auto* xs, auto* rf, const auto& w) {
+    [&](auto tag, auto* xs, auto* rf, const auto& w, int) {
       using TIO = decltype(tag);
       const RolloutPlan<TIO> plan = {(const TIO*)plan_pos, plan_feet_id, plan_meta};
       hipLaunchKernelGGL((mpcqp_rollout_expand_kernel<TIO>), ge, nt, 0, st, xs, rf, plan, tick, d, N, (int)S, B, w.r, w.contact, w.xdes);
@@ -817,15 +834,22 @@ int leg_rows(mpcqp_handle h, const char* who, const MpcQpLegGeometry* geo, const
 struct RolloutDriveArgs { int32_t drive; const void* ground; void* cmd_log; };
 // What mpcqp_rollout_slip adds to mpcqp_rollout_drive: the feet's effective mass [B], the slip state [B,4,2], its two logs or null.
 struct RolloutSlipArgs { const void* foot_mass; double* slip; double* slip_log; void* disp_log; };
+// What mpcqp_rollout_observe adds to mpcqp_rollout_slip: what the MPC reads, the filter state [B,131], the optional operands of the
+// sensors and the filter, the checked parameters, the seven logs or null.
+struct RolloutObserveArgs {
+  int32_t feed; double* est_state; const void *est_init, *height, *bias, *noise, *enc_noise; EstPar par;
+  void *imu_log, *q_enc_log, *qd_enc_log, *est_log, *feet_est_log, *sigma_log, *nis_log;
+};
 
-// mpcqp_rollout_legs (dr = null), mpcqp_rollout_drive and mpcqp_rollout_slip (sl, with dr): one argument check, one loop.
+// mpcqp_rollout_legs (dr = null), mpcqp_rollout_drive, mpcqp_rollout_slip (sl, with dr) and mpcqp_rollout_observe (ob, with both): one
+// argument check, one loop.
 int rollout_legs_run(mpcqp_handle h, const char* who, int64_t B, int32_t T, void* x, void* ref, void* feet, double* legs, const int32_t* gait,
                      const void* stand, const void* gain, int32_t* tick, const void* mu, const void* body, const void* push,
                      const int32_t* push_ticks, int32_t substeps, const void* step_height, const void* gains, int32_t leg_substeps,
                      const MpcQpLegGeometry* geo, const MpcQpLegInertia* inr, int32_t land, void* actual, void* desired, void* forces,
                      void* feet_log, uint8_t* contact_log, int32_t* solved, void* swing_log, void* q_log, void* qd_log, void* tau_log,
                      void* foot_log, void* err_log, uint8_t* flag_log, void* miss_log, void* stream, const RolloutDriveArgs* dr,
-                     const RolloutSlipArgs* sl = nullptr) {
+                     const RolloutSlipArgs* sl = nullptr, const RolloutObserveArgs* ob = nullptr) {
   if (!h) return MPCQP_EINVAL;
   if (B < 0 || B > 0x7fffffff || T < 0 || B * (int64_t)T > 0x7fffffff) return bad(h, who, "size out of range");
   const int n = plant_substeps(substeps);
@@ -837,6 +861,7 @@ int rollout_legs_run(mpcqp_handle h, const char* who, int64_t B, int32_t T, void
   if (push && !push_ticks) return bad(h, who, "push without push_ticks");
   if (B > 0 && (!x || !ref || !feet || !legs || !gait || !stand || !tick || !mu || !step_height)) return bad(h, who, "null buffer");
   if (B > 0 && sl && (!dr->ground || !sl->foot_mass || !sl->slip)) return bad(h, who, "null buffer");
+  if (B > 0 && ob && !ob->est_state) return bad(h, who, "null buffer");
   LegGeoDev g;
   LegInrDev r;
   if (const int rc = leg_rows(h, who, geo, inr, true, g, r)) return rc;
@@ -854,10 +879,28 @@ int rollout_legs_run(mpcqp_handle h, const char* who, int64_t B, int32_t T, void
   // step and the advance read as a force buffer of horizon 1 (the solve's own buffer, its next warm start, is not altered); after the legs
   // step the rule's torques and bits go into the stance rows of tau_log / flag_log: 6 launches, 7 with one of those two logs.
   // With the slip rule in the drive's place the log step waits until after the landing and moves the feet in the same launch: 7.
+  // With the estimator (ob) its update runs in front of the expand and its predict between the slip rule and the legs step: 9; with
+  // MPCQP_FEED_ESTIMATE the expand and the solve read the update's side buffers in place of x and feet.
+  const auto observe_in = [&](auto tag) {
+    using TIO = decltype(tag);
+    return ObsIn<TIO>{(const TIO*)ob->est_init, (const TIO*)ob->height, (const TIO*)ob->bias, (const TIO*)ob->noise, (const TIO*)ob->enc_noise};
+  };
+  const auto observe_out = [&](auto tag) {
+    using TIO = decltype(tag);
+    return ObsOut<TIO>{(TIO*)ob->imu_log, (TIO*)ob->q_enc_log, (TIO*)ob->qd_enc_log, (TIO*)ob->est_log, (TIO*)ob->feet_est_log,
+                       (TIO*)ob->sigma_log, (TIO*)ob->nis_log};
+  };
+  const bool fed = ob && ob->feed == MPCQP_FEED_ESTIMATE;
   return rollout_loop(h, who, B, T, x, ref, mu, stream,
-    [&](auto tag, auto* xs, auto* rf, const auto& w) {
+    [&](auto tag, auto* xs, auto* rf, const auto& w, int it) {
       using TIO = decltype(tag);
-      launch_phase_expand<TIO>(h, B, st, xs, rf, phase_rows<TIO>(feet, gait, stand, gain), tick, w);
+      if (!ob) return launch_phase_expand<TIO>(h, B, st, xs, rf, phase_rows<TIO>(feet, gait, stand, gain), tick, w);
+      const ObsWs<TIO> ow = observe_ws<TIO>(h->roll_mem, B, N);
+      hipLaunchKernelGGL((mpcqp_observe_update_kernel<TIO>), gl, nt, 0, st, (const TIO*)xs, (const TIO*)rf,
+                         phase_rows<TIO>(feet, gait, stand, gain), (const int32_t*)tick, (const double*)sl->slip, (const double*)legs,
+                         (const TIO*)step_height, observe_in(tag), ob->par, g, ob->est_state, ow, observe_out(tag), d, B, (int)T, it);
+      launch_phase_expand<TIO>(h, B, st, fed ? (const TIO*)ow.xhat : (const TIO*)xs, rf, phase_rows<TIO>(fed ? (void*)ow.feet : feet, gait, stand, gain),
+                               tick, w);
     },
     [&](auto tag, auto* xs, auto* rf, const auto& o, int it) {
       using TIO = decltype(tag);
@@ -875,6 +918,9 @@ int rollout_legs_run(mpcqp_handle h, const char* who, int64_t B, int32_t T, void
                    (const double*)sl->slip, g, r.lim, (int)dr->drive, n, d / n, d, dw.f, dw.tau, dw.flag, cmd, (int64_t)T * 12, sl->slip, rdisp,
                    slog, (int64_t)T * 8, B);
         u = dw.f; Nu = 1;
+        if (ob)
+          hipLaunchKernelGGL((mpcqp_observe_predict_kernel<TIO>), gl, nt, 0, st, (const TIO*)xs, (const int32_t*)tick, u, plant_in<TIO>(h, plant),
+                             observe_in(tag), ob->par, ob->est_state, observe_ws<TIO>(h->roll_mem, B, N), observe_out(tag), B, (int)T, it);
       } else if (dr) {
         TIO* cmd = dr->cmd_log ? (TIO*)dr->cmd_log + (size_t)it * 12 : nullptr;
         launch_act(h, gl, st, mpcqp_stance_drive_kernel<TIO>, mpcqp_stance_drive_kernel<TIO, double>, xs, o.u, (int64_t)N * 12,
@@ -894,6 +940,10 @@ int rollout_legs_run(mpcqp_handle h, const char* who, int64_t B, int32_t T, void
       if (sl)
         hipLaunchKernelGGL((mpcqp_slip_finish_kernel<TIO>), gl, nt, 0, st, gait, tick, (const TIO*)dw.tau, (const uint8_t*)dw.flag,
                            (const TIO*)rdisp, B, (int)T, it, (TIO*)feet, sl->slip, (TIO*)tau_log, flag_log, (TIO*)sl->disp_log);
+    },
+    [&](auto tag) {
+      using TIO = decltype(tag);
+      return fed ? (const TIO*)observe_ws<TIO>(h->roll_mem, B, N).xhat : (const TIO*)nullptr;
     });
 }
 
@@ -1122,7 +1172,7 @@ int mpcqp_rollout_phase(mpcqp_handle h, int64_t B, int32_t T, void* x, void* ref
   const RolloutPlantArgs plant = {body, push, push ? push_ticks : nullptr, n};
   hipStream_t st = (hipStream_t)stream;
   return rollout_loop(h, "mpcqp_rollout_phase", B, T, x, ref, mu, stream,
-    [&](auto tag, auto* xs, auto* rf, const auto& w) {
+    [&](auto tag, auto* xs, auto* rf, const auto& w, int) {
       using TIO = decltype(tag);
       launch_phase_expand<TIO>(h, B, st, xs, rf, phase_rows<TIO>(feet, gait, stand, gain), tick, w);
     },
@@ -1555,6 +1605,29 @@ int mpcqp_stance_slip(mpcqp_handle h, int64_t B, const void* x, const void* f, c
                (const TIO*)ground, (const TIO*)foot_mass, slip_in, g, r.lim, (int)DRIVE_LIMITED, n, d / n, d, (TIO*)f_out, (TIO*)tau, flag,
                (TIO*)nullptr, (int64_t)0, slip_out, (TIO*)disp, (double*)nullptr, (int64_t)0, B);
   });
+}
+
+int mpcqp_rollout_observe(mpcqp_handle h, int64_t B, int32_t T, void* x, void* ref, void* feet, double* legs, const int32_t* gait,
+                          const void* stand, const void* gain, int32_t* tick, const void* mu, const void* body, const void* push,
+                          const int32_t* push_ticks, int32_t substeps, const void* step_height, const void* gains, int32_t leg_substeps,
+                          const MpcQpLegGeometry* geo, const MpcQpLegInertia* inr, int32_t land, int32_t drive, const void* ground,
+                          const void* foot_mass, double* slip, void* actual, void* desired, void* forces, void* feet_log, uint8_t* contact_log,
+                          int32_t* solved, void* swing_log, void* q_log, void* qd_log, void* tau_log, void* foot_log, void* err_log,
+                          uint8_t* flag_log, void* miss_log, void* cmd_log, double* slip_log, void* disp_log, int32_t feed, double* est_state,
+                          const void* est_init, const void* height, const void* bias, const void* noise, const void* enc_noise,
+                          const MpcQpEstimator* par, void* imu_log, void* q_enc_log, void* qd_enc_log, void* est_log, void* feet_est_log,
+                          void* sigma_log, void* nis_log, void* stream) {
+  if (!h) return MPCQP_EINVAL;
+  const char* who = "mpcqp_rollout_observe";
+  if (feed != MPCQP_FEED_TRUTH && feed != MPCQP_FEED_ESTIMATE) return bad(h, who, "feed is neither MPCQP_FEED_TRUTH nor MPCQP_FEED_ESTIMATE");
+  RolloutObserveArgs ob = {feed, est_state, est_init, height, bias, noise, enc_noise, {}, imu_log, q_enc_log, qd_enc_log, est_log, feet_est_log,
+                           sigma_log, nis_log};
+  if (const int rc = estimator_row(h, who, par, ob.par)) return rc;
+  const RolloutDriveArgs dr = {drive, ground, cmd_log};
+  const RolloutSlipArgs sl = {foot_mass, slip, slip_log, disp_log};
+  return rollout_legs_run(h, who, B, T, x, ref, feet, legs, gait, stand, gain, tick, mu, body, push, push_ticks, substeps, step_height, gains,
+                          leg_substeps, geo, inr, land, actual, desired, forces, feet_log, contact_log, solved, swing_log, q_log, qd_log,
+                          tau_log, foot_log, err_log, flag_log, miss_log, stream, &dr, &sl, &ob);
 }
 
 int mpcqp_rollout_score(mpcqp_handle h, int64_t B, int32_t T, const void* actual, const void* desired, const void* forces,

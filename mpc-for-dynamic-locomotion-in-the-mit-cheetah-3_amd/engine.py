@@ -519,11 +519,12 @@ class MPCBatch:
     LEGS_LOGS = ("swing",) + SWING_OUT + ("miss",)      # the logs `rollout_legs` adds to `rollout_phase`'s, in the C order
 
     def _rollout_legs(self, call, x, ref, feet, legs, gait, stand, gain, tick, mu, T, step_height, land, body, push, push_ticks, substeps,
-                      gains, leg_substeps, inertia, geometry, log, stream, drive=_NO_DRIVE, operands=(), optional=(), logs=()):
+                      gains, leg_substeps, inertia, geometry, log, stream, drive=_NO_DRIVE, operands=(), optional=(), logs=(), tail=()):
         """What `rollout_legs`, `rollout_drive` and `rollout_slip` share: the checks, the log spec, the allocation and the addresses
         for `call`, the engine's entry point.  drive (left out: `call` takes no drive mode) goes to `call` after the landing mode, then the
         tensors of `operands`, rows as `check_operands` takes them (None passes for the names in `optional`); `logs`, rows (name,
-        shape after [B,T], dtype), follow `rollout_legs`' logs in the result and in the call."""
+        shape after [B,T], dtype), follow `rollout_legs`' logs in the result and in the call; `tail`, arguments as `call` takes them, go
+        between the logs and the geometry."""
         torch = _torch()
         B, T = int(x.shape[0]), int(T)
         if land not in ("rule", "actual"):
@@ -549,7 +550,7 @@ class MPCBatch:
         call(B, T, x.data_ptr(), ref.data_ptr(), feet.data_ptr(), legs.data_ptr(), gait.data_ptr(), stand.data_ptr(), _ptr(gain),
              tick.data_ptr(), mu.data_ptr(), _ptr(body), _ptr(push), _ptr(push_ticks), substeps, step_height.data_ptr(), _ptr(gains),
              int(leg_substeps), _capi.LAND_ACTUAL if land == "actual" else _capi.LAND_RULE, *mode, *[_ptr(t) for _, t, _, _ in operands],
-             *[p(k) for k in names[:5]], solved.data_ptr(), *[p(k) for k in names[5:]], geometry, self._inertia(inertia), st.cuda_stream)
+             *[p(k) for k in names[:5]], solved.data_ptr(), *[p(k) for k in names[5:]], *tail, geometry, self._inertia(inertia), st.cuda_stream)
         out["solved"] = solved
         return out
 
@@ -652,6 +653,41 @@ class MPCBatch:
                                   operands=(("ground", ground, (B,), self.tdtype), ("foot_mass", foot_mass, (B,), self.tdtype),
                                             ("slip", slip, (B, 4, 2), f64)),
                                   logs=(("cmd", (12,), self.tdtype), ("slip_log", (4, 2), f64), ("disp", (4, 2), self.tdtype)))
+
+    OBSERVE_LOGS = ("imu", "q_enc", "qd_enc", "est", "feet_est", "sigma", "nis")      # what `rollout_observe` adds, in the C order
+
+    def rollout_observe(self, x, ref, feet, legs, gait, stand, gain, tick, mu, T, step_height, ground, foot_mass, slip, est_state,
+                        feed="estimate", est_init=None, height=None, bias=None, noise=None, enc_noise=None, estimator=None, land="rule",
+                        drive="limited", body=None, push=None, push_ticks=None, substeps=10, gains=None, leg_substeps=0, inertia=None,
+                        geometry=None, log=True, stream=None):
+        """`rollout_slip` with sensors and the state estimator inside the tick loop (include/mpcqp_observe.h, mpcqp_rollout_observe,
+        which has the rule; the host counterpart is gaits.rollout_observe_host): per tick the encoders and the IMU are read off the
+        live state, one row of `estimate_track` runs on est_state float64 [B,131] (state next to `x`, ..., `slip`, advanced IN PLACE;
+        zeros: every filter starts from est_init [B,12], None = the robot's x), and with feed="estimate" the MPC's expand and solve read
+        the estimate of the torso state and of the feet; with feed="truth" the estimator only shadows the loop, which is then
+        `rollout_slip`'s bit for bit.  height [B,4] as in `estimate_track`, bias [B,6] and noise [B,T,6] as in `imu_log`, enc_noise
+        [B,T,4,6] the (q, qd) noise per leg, `estimator` as in `estimate_track`.  Returns `rollout_slip`'s dict (the plant's truth) plus
+        "imu" [B,T,6], "q_enc", "qd_enc" [B,T,4,3], "est" [B,T,12], "feet_est" [B,T,4,3], "sigma" [B,T,6] and "nis" [B,T].  Every
+        other argument as in `rollout_slip`.  Asynchronous on `stream`."""
+        from . import estimator as _est
+        B, T, f64 = int(x.shape[0]), int(T), _torch().float64
+        feeds = {"truth": _capi.FEED_TRUTH, "estimate": _capi.FEED_ESTIMATE}
+        if not isinstance(feed, int) and feed not in feeds:
+            raise ValueError(f"feed must be 'truth' or 'estimate', got {feed!r}")
+        check_operands(self.device, (("est_state", est_state, (B, _capi.EST_STATE), f64), ("est_init", est_init, (B, 12), self.tdtype),
+                                     ("height", height, (B, 4), self.tdtype), ("bias", bias, (B, 6), self.tdtype),
+                                     ("noise", noise, (B, T, 6), self.tdtype), ("enc_noise", enc_noise, (B, T, 4, 6), self.tdtype)),
+                       optional=("est_init", "height", "bias", "noise", "enc_noise"))
+        tail = (feed if isinstance(feed, int) else feeds[feed], est_state.data_ptr(), _ptr(est_init), _ptr(height), _ptr(bias), _ptr(noise),
+                _ptr(enc_noise), _est.estimator_struct(estimator))
+        leg3 = ((4, 3), self.tdtype)
+        return self._rollout_legs(self.engine.rollout_observe_ptr, x, ref, feet, legs, gait, stand, gain, tick, mu, T, step_height, land, body, push, push_ticks, substeps,
+                                  gains, leg_substeps, inertia, geometry, log, stream, drive,
+                                  operands=(("ground", ground, (B,), self.tdtype), ("foot_mass", foot_mass, (B,), self.tdtype),
+                                            ("slip", slip, (B, 4, 2), f64)),
+                                  logs=(("cmd", (12,), self.tdtype), ("slip_log", (4, 2), f64), ("disp", (4, 2), self.tdtype),
+                                        ("imu", (6,), self.tdtype), ("q_enc", *leg3), ("qd_enc", *leg3), ("est", (12,), self.tdtype),
+                                        ("feet_est", *leg3), ("sigma", (6,), self.tdtype), ("nis", (), self.tdtype)), tail=tail)
 
     def score(self, logs, score=None, rule=None, stream=None):
         """The score row of a roll-out's logs, reduced on the device (include/mpcqp_sim.h, mpcqp_rollout_score; the host counterpart is

@@ -342,9 +342,89 @@ def rollout_slip_host(oracle_engine, x, ref, feet, legs, gait, stand, gain, tick
                               substeps, gains, leg_substeps, inertia, drive, ground, actuators, state)
 
 
+def rollout_observe_host(oracle_engine, x, ref, feet, legs, gait, stand, gain, tick, mu, T, step_height, ground, foot_mass, slip=None,
+                         est_state=None, feed="estimate", est_init=None, height=None, bias=None, noise=None, enc_noise=None, estimator=None,
+                         land="rule", drive="limited", body=None, push=None, push_ticks=None, substeps=DEFAULT_SUBSTEPS, gains=None,
+                         leg_substeps=0, inertia=None, actuators=None):
+    """Closed loop of mpcqp_rollout_observe (include/mpcqp_observe.h, which has the rule) on the CPU checker: `rollout_slip_host`'s loop
+    with, per tick, the encoder and gyro rows read off the live state, one row of `estimator.estimate_track_host` on est_state [B,131]
+    (None: every filter starts, from est_init [B,12] or the robot's x) and, once the slip rule has given the applied forces, the
+    accelerometer row and the filter's predict.  feed="estimate": the expand and the solve read the estimate of the torso state and of
+    the feet; feed="truth": they read x and feet, and every shared key is `rollout_slip_host`'s.  height [B,4], bias [B,6], noise
+    [B,T,6], enc_noise [B,T,4,6] or None.  Returns `rollout_slip_host`'s dict (the plant's truth) plus "imu" [B,T,6], "q_enc", "qd_enc"
+    [B,T,4,3], "est" [B,T,12], "feet_est" [B,T,4,3], "sigma" [B,T,6], "nis" [B,T] and "est_state" [B,131].
+    The device uses every sensor value, and a stance foot's slip velocity in its encoder row, as its I/O type holds it; nothing is rounded
+    here, which is that rule only because the checker's I/O type is fp64: this is the counterpart of an fp64-I/O handle."""
+    if drive not in ("ideal", "limited"):
+        raise ValueError(f"drive must be 'ideal' or 'limited', got {drive!r}")
+    if feed not in ("truth", "estimate"):
+        raise ValueError(f"feed must be 'truth' or 'estimate', got {feed!r}")
+    if ground is None or foot_mass is None:
+        raise ValueError("rollout_observe_host needs ground and foot_mass")
+    B = np.asarray(x).shape[0]
+    state = {"foot_mass": np.broadcast_to(_f64(foot_mass), (B,)).copy(),
+             "slip": np.zeros((B, 4, 2)) if slip is None else _f64(slip).reshape(B, 4, 2).copy()}
+    opt = lambda a: None if a is None else _f64(a)
+    observe = {"feed": feed, "state": None if est_state is None else _f64(est_state).copy(), "init": opt(est_init), "height": opt(height),
+               "bias": opt(bias), "noise": opt(noise), "enc_noise": opt(enc_noise), "estimator": estimator}
+    return _rollout_legs_loop(oracle_engine, x, ref, feet, legs, gait, stand, gain, tick, mu, T, step_height, land, body, push, push_ticks,
+                              substeps, gains, leg_substeps, inertia, drive, ground, actuators, state, observe)
+
+
+def _observe_sense(ob, t, x, ref, feet, legs, slip, contact, gait, tick, stand, gain, step_height, delta):
+    """Step 1 of mpcqp_rollout_observe's tick on the host: the encoder and gyro rows of tick t from the live state, and the row's
+    estimate from a one-row call of `estimate_track_host` with the gyro alone (the row's outputs do not depend on the specific force)
+    -> (q_enc, qd_enc [B,4,3], gyro [B,3], est row [B,12], feet_est row [B,4,3])."""
+    from . import estimator as _est, lite3_model
+    B = x.shape[0]
+    act = x[:, None, :12]
+    des = np.zeros((B, 1, 12))
+    des[:, 0, 0:6] = ref[:, 0:6]; des[:, 0, 8] = ref[:, 9]; des[:, 0, 9:12] = ref[:, 6:9]
+    sw = phase_swing_host(act, des, feet[:, None], gait, tick, stand, gain, step_height, delta)["swing"]
+    stance = contact != 0
+    vel = np.where(stance[..., None], np.concatenate([slip, np.zeros((B, 4, 1))], axis=-1), sw[:, 0, :, 1])
+    on = lite3_model.joint_rates_host(act, np.zeros((B, 1, 12)), sw[:, :, :, 0], vel[:, None])
+    carried = (~stance & (legs[:, :, 6] != 0.0))[..., None]
+    q, qd = np.where(carried, legs[:, :, 0:3], on[0][:, 0]), np.where(carried, legs[:, :, 3:6], on[1][:, 0])
+    if ob["enc_noise"] is not None:
+        with np.errstate(invalid="ignore"):
+            q, qd = q + ob["enc_noise"][:, t, :, 0:3], qd + ob["enc_noise"][:, t, :, 3:6]
+    nz = None if ob["noise"] is None else ob["noise"][:, t:t + 1]
+    gyro = _est.imu_log_host(act, np.zeros((B, 1, 12)), feet[:, None], base_acc=np.zeros((B, 1, 6)), bias=ob["bias"], noise=nz,
+                             estimator=ob["estimator"])[:, 0, 0:3]
+    if ob["state"] is None:
+        ob["state"] = np.zeros((B, _est.EST_STATE))
+    if ob["init"] is None:
+        ob["init"] = x[:, :12].copy()
+    imu = np.concatenate([gyro, np.zeros((B, 3))], axis=-1)[:, None]
+    row = _est.estimate_track_host(imu, q[:, None], qd[:, None], contact[:, None], ob["init"], height=ob["height"], state=ob["state"],
+                                   estimator=ob["estimator"], delta=delta)
+    return q, qd, gyro, row["est"][:, 0], row["feet"][:, 0]
+
+
+def _observe_predict(ob, t, out, x, forces, feet, contact, q, qd, gyro, bd, wr, delta):
+    """Step 4: the accelerometer row under the applied forces and the push, the row's logs and the filter's state after its predict."""
+    from . import estimator as _est, lite3_model
+    B = x.shape[0]
+    act = x[:, None, :12]
+    g = _est.estimator_row(**(ob["estimator"] or {}))["gravity"]
+    acc = lite3_model.plant_base_acc_host(act, forces[:, None], feet[:, None], bd, g, None if wr is None else wr[:, None])
+    nz = None if ob["noise"] is None else ob["noise"][:, t:t + 1]
+    sf = _est.imu_log_host(act, forces[:, None], feet[:, None], base_acc=acc, bias=ob["bias"], noise=nz, estimator=ob["estimator"])[:, 0, 3:6]
+    with np.errstate(invalid="ignore"):
+        imu = np.where(np.isfinite(sf).all(-1)[:, None], np.concatenate([gyro, sf], axis=-1), np.nan)
+    row = _est.estimate_track_host(imu[:, None], q[:, None], qd[:, None], contact[:, None], ob["init"], height=ob["height"], state=ob["state"],
+                                   estimator=ob["estimator"], delta=delta)
+    ob["state"] = row["state"]
+    out["imu"][:, t], out["q_enc"][:, t], out["qd_enc"][:, t] = imu, q, qd
+    for k, src in (("est", "est"), ("feet_est", "feet"), ("sigma", "sigma"), ("nis", "nis")):
+        out[k][:, t] = row[src][:, 0]
+
+
 def _rollout_legs_loop(oracle_engine, x, ref, feet, legs, gait, stand, gain, tick, mu, T, step_height, land, body, push, push_ticks, substeps,
-                       gains, leg_substeps, inertia, drive, ground, actuators=None, slide=None):
-    """The loop of `rollout_legs_host` (drive = None), `rollout_drive_host` and `rollout_slip_host` (slide = its foot_mass and slip)."""
+                       gains, leg_substeps, inertia, drive, ground, actuators=None, slide=None, observe=None):
+    """The loop of `rollout_legs_host` (drive = None), `rollout_drive_host`, `rollout_slip_host` (slide = its foot_mass and slip) and
+    `rollout_observe_host` (observe = its feed, filter state and sensor operands; None: the controller reads the plant's state)."""
     from . import lite3_model
     if push is not None and push_ticks is None:
         raise ValueError("push needs push_ticks")
@@ -369,9 +449,18 @@ def _rollout_legs_loop(oracle_engine, x, ref, feet, legs, gait, stand, gain, tic
         out["cmd"], out["drive_margin"] = np.zeros((B, T, 12)), np.full((B, T, 4), np.inf)
     if slide is not None:
         out["slip_log"], out["disp"] = np.zeros((B, T, 4, 2)), np.zeros((B, T, 4, 2))
+    if observe is not None:
+        out.update({"imu": np.zeros((B, T, 6)), "est": np.zeros((B, T, 12)), "sigma": np.zeros((B, T, 6)), "nis": np.zeros((B, T)),
+                    **{k: np.zeros((B, T, 4, 3)) for k in ("q_enc", "qd_enc", "feet_est")}})
     for t in range(T):
         e = phase_expand_host(x, ref, feet, gait, tick, stand, gain, N, delta)
-        o = oracle_engine.solve_batch_host(x, e["r"], e["contact"], e["xdes"], mu, want_X=False)
+        xc = x
+        if observe is not None:     # sense and update; with feed = "estimate" the controller reads the estimate (the contact is the clock's)
+            sense = _observe_sense(observe, t, x, ref, feet, legs, slide["slip"], e["contact"][:, 0], gait, tick, stand, gain, step_height, delta)
+            if observe["feed"] == "estimate":
+                xc = np.concatenate([sense[3], x[:, 12:]], axis=1)
+                e = dict(phase_expand_host(xc, ref, sense[4], gait, tick, stand, gain, N, delta), contact=e["contact"])
+        o = oracle_engine.solve_batch_host(xc, e["r"], e["contact"], e["xdes"], mu, want_X=False)
         actual[:, t] = x[:, :12]
         desired[:, t, 0:6] = ref[:, 0:6]; desired[:, t, 8] = ref[:, 9]; desired[:, t, 9:12] = ref[:, 6:9]
         forces[:, t] = o["u"][:, 0]
@@ -387,6 +476,8 @@ def _rollout_legs_loop(oracle_engine, x, ref, feet, legs, gait, stand, gain, tic
         solved += ((o["status"] == 1) | (o["status"] == 2)).astype(np.int32)
         feet_log[:, t], contact_log[:, t] = feet, e["contact"][:, 0]
         wr = None if push is None else push_wrench(push, push_ticks, tick)
+        if observe is not None:
+            _observe_predict(observe, t, out, x, forces[:, t], feet, contact_log[:, t], *sense[:3], bd, wr, delta)
         # the legs step: the row of the logs at this tick, through phase_swing and swing_track
         row = lambda a: a[:, t:t + 1]
         sw = phase_swing_host(row(actual), row(desired), row(feet_log), gait, tick, stand, gain, step_height, delta)["swing"]
@@ -425,7 +516,7 @@ def _rollout_legs_loop(oracle_engine, x, ref, feet, legs, gait, stand, gain, tic
             slide["slip"] = np.where(td[..., None], 0.0, dv["slip"])
     return {"x": x, "ref": ref, "tick": tick, "feet": feet, "legs": legs, "actual": actual, "desired": desired, "forces": forces,
             "solved": solved, "feet_log": feet_log, "contact_log": contact_log, **out,
-            **({} if slide is None else {"slip": slide["slip"]})}
+            **({} if slide is None else {"slip": slide["slip"]}), **({} if observe is None else {"est_state": observe["state"]})}
 
 
 def make_phase_batch(B, names=("trot", "bound"), period=12, seed=20251018, mus=(0.5, 0.7, 1.0), v_ref=(0.18, 0.0, 0.0), theta_dot=0.0,
