@@ -13,8 +13,9 @@
  * allocated.  All arithmetic is fp64; the filter's own arithmetic (everything below but the leg's forward map) is not contracted;
  * float32 outputs are rounded once.  Return codes and mpcqp_last_error() as in mpcqp.h.
  *
- * Not built: gyro and accelerometer bias states (a given bias is read as it is), contact detection (trust is given), an IMU off the
- * CoM, telling the MPC the estimate's covariance.  (The estimate inside a roll-out's tick loop is mpcqp_observe.h.)
+ * Not built: gyro and accelerometer bias states (a given bias is read as it is), contact detection from forces (trust is given;
+ * gating it on the legs' velocity innovations is mpcqp_gate.h), an IMU off the CoM, telling the MPC the estimate's covariance.  (The
+ * estimate inside a roll-out's tick loop is mpcqp_observe.h.)
  */
 #ifndef MPCQP_ESTIMATE_H_
 #define MPCQP_ESTIMATE_H_

@@ -1,5 +1,5 @@
 """ctypes binding of the C-ABI declared in include/mpcqp.h and its product-only extensions include/mpcqp_plan.h, mpcqp_sim.h, mpcqp_model.h,
-mpcqp_joints.h, mpcqp_actuators.h, mpcqp_slip.h, mpcqp_estimate.h and mpcqp_observe.h.
+mpcqp_joints.h, mpcqp_actuators.h, mpcqp_slip.h, mpcqp_estimate.h, mpcqp_observe.h and mpcqp_gate.h.
 
 The product path loads ``csrc/libmpcqp.so`` (hand-written HIP for gfx950) and nothing else: if that library is
 missing or cannot be loaded, importing the engine raises -- there is no CPU fallback.  The binding itself is
@@ -88,6 +88,12 @@ class MpcQpEstimator(ctypes.Structure):
     FIELDS = tuple(name for name, _ in _fields_[1:])
 
 
+class MpcQpTrustGate(ctypes.Structure):
+    """Mirror of struct MpcQpTrustGate (include/mpcqp_gate.h): the thresholds of the estimator's per-leg trust gate."""
+    _fields_ = [("size", c_uint32), ("d_lo", c_double), ("d_hi", c_double)]
+    FIELDS = tuple(name for name, _ in _fields_[1:])
+
+
 class MpcQpConfig(ctypes.Structure):
     """Mirror of ``struct MpcQpConfig`` (include/mpcqp.h)."""
     _fields_ = [
@@ -120,6 +126,7 @@ _P, _I32, _I64 = c_void_p, c_int32, c_int64   # any address (handle, buffer, str
 _CFG, _GEO, _INR = ctypes.POINTER(MpcQpConfig), ctypes.POINTER(MpcQpLegGeometry), ctypes.POINTER(MpcQpLegInertia)
 _RULE = ctypes.POINTER(MpcQpScoreRule)
 _EST = ctypes.POINTER(MpcQpEstimator)
+_GATE = ctypes.POINTER(MpcQpTrustGate)
 CORE_HEADER = "mpcqp.h"
 ABI = {
     "mpcqp.h": (
@@ -209,6 +216,17 @@ OBSERVE_ABI = {
 }
 OBSERVE_SYMBOLS = tuple(row[0] for row in OBSERVE_ABI[OBSERVE_HEADER])
 FEED_TRUTH, FEED_ESTIMATE = 0, 1   # include/mpcqp_observe.h, MPCQP_FEED_*
+# include/mpcqp_gate.h, the estimator's trust gated on the legs' velocity innovations, likewise: `has_gate`.  Each gated call is its
+# ungated row with the thresholds and the trust output in front of the stream.
+GATE_HEADER = "mpcqp_gate.h"
+GATE_ABI = {
+    GATE_HEADER: (  # the per-leg trust gate of the estimator, over a log and inside the roll-out
+        ("mpcqp_default_trust_gate", c_int, (_GATE,)),
+        ("mpcqp_estimate_track_gated", c_int, ESTIMATE_ABI[ESTIMATE_HEADER][2][2][:-1] + (_GATE, _P, _P)),
+        ("mpcqp_rollout_observe_gated", c_int, OBSERVE_ABI[OBSERVE_HEADER][0][2][:-1] + (_GATE, _P, _P)),
+    ),
+}
+GATE_SYMBOLS = tuple(row[0] for row in GATE_ABI[GATE_HEADER])
 # The swing-leg plant of include/mpcqp_joints.h came after the rest of that header: a product library built before it still has the
 # header's other calls (`has_joints`) and is told apart by `has_legsim`.
 LEGSIM_SYMBOLS = ("mpcqp_leg_accel", "mpcqp_swing_track")
@@ -230,8 +248,8 @@ DRIVE_SLIDING = 128   # include/mpcqp_slip.h, MPCQP_DRIVE_SLIDING: the stance fo
 
 class Library:
     """A loaded shared object exporting the mpcqp C-ABI.  `has_plan`, `has_sim`, `has_model`, `has_joints`, `has_actuators`, `has_slip`,
-    `has_estimate` and `has_observe` say whether it exports all of include/mpcqp_plan.h, mpcqp_sim.h, mpcqp_model.h, mpcqp_joints.h,
-    mpcqp_actuators.h, mpcqp_slip.h, mpcqp_estimate.h and mpcqp_observe.h (of mpcqp_joints.h: all but LEGSIM_SYMBOLS, which `has_legsim`
+    `has_estimate`, `has_observe` and `has_gate` say whether it exports all of include/mpcqp_plan.h, mpcqp_sim.h, mpcqp_model.h,
+    mpcqp_joints.h, mpcqp_actuators.h, mpcqp_slip.h, mpcqp_estimate.h, mpcqp_observe.h and mpcqp_gate.h (of mpcqp_joints.h: all but LEGSIM_SYMBOLS, which `has_legsim`
     answers for; of mpcqp_sim.h: all but LEGROLL_SYMBOLS, SCORE_SYMBOLS and DRIVE_SYMBOLS, `has_legroll`, `has_score` and `has_drive`).  An
     extension header's calls are bound only when the library
     has them all; `partial=True` binds whichever it has (an older build of the product library, in a comparison tool)."""
@@ -246,7 +264,7 @@ class Library:
         self.has_legroll = all(hasattr(self.lib, name) for name in LEGROLL_SYMBOLS)
         self.has_score = all(hasattr(self.lib, name) for name in SCORE_SYMBOLS)
         self.has_drive = all(hasattr(self.lib, name) for name in DRIVE_SYMBOLS)
-        for header, rows in {**ABI, **ACTUATORS_ABI, **SLIP_ABI, **ESTIMATE_ABI, **OBSERVE_ABI}.items():
+        for header, rows in {**ABI, **ACTUATORS_ABI, **SLIP_ABI, **ESTIMATE_ABI, **OBSERVE_ABI, **GATE_ABI}.items():
             have = header == CORE_HEADER or all(hasattr(self.lib, row[0]) for row in rows if row[0] not in _GATED)
             if header != CORE_HEADER:
                 setattr(self, "has_" + header[len("mpcqp_"):-len(".h")], have)
@@ -281,6 +299,17 @@ class Library:
         rc = fn(ctypes.byref(row))
         if rc != 0:
             raise MpcQpError(f"mpcqp_default_estimator failed: {rc}")
+        return row
+
+    def default_trust_gate(self) -> "MpcQpTrustGate":
+        """The trust gate's default thresholds (include/mpcqp_gate.h, mpcqp_default_trust_gate; product library only)."""
+        fn, header, _ = self.calls["mpcqp_default_trust_gate"]
+        if fn is None:
+            raise MpcQpError(f"mpcqp_default_trust_gate: {self.path} does not export include/{header} (product library only)")
+        row = MpcQpTrustGate()
+        rc = fn(ctypes.byref(row))
+        if rc != 0:
+            raise MpcQpError(f"mpcqp_default_trust_gate failed: {rc}")
         return row
 
     def default_config(self, **overrides) -> MpcQpConfig:
@@ -460,6 +489,20 @@ class Engine:
                    est_state, est_init, height, bias, noise, enc_noise, estimator, imu_log, q_enc_log, qd_enc_log, est_log, feet_est_log,
                    sigma_log, nis_log, stream)
 
+    def rollout_observe_gated_ptr(self, B, T, x, ref, feet, legs, gait, stand, gain, tick, mu, body, push, push_ticks, substeps, step_height,
+                                  gains, leg_substeps, land, drive, ground, foot_mass, slip, actual, desired, forces, feet_log, contact_log,
+                                  solved, swing_log, q_log, qd_log, tau_log, foot_log, err_log, flag_log, miss_log, cmd_log, slip_log, disp_log,
+                                  imu_log, q_enc_log, qd_enc_log, est_log, feet_est_log, sigma_log, nis_log, trust_log, feed, est_state,
+                                  est_init=0, height=0, bias=0, noise=0, enc_noise=0, estimator=None, gate=None, geometry=None, inertia=None,
+                                  stream=0):
+        """`rollout_observe_ptr` with the estimator's trust gated per leg (include/mpcqp_gate.h, mpcqp_rollout_observe_gated): trust_log
+        follows nis_log among the logs, `gate` (an MpcQpTrustGate or None = the defaults) follows `estimator`."""
+        self._call("mpcqp_rollout_observe_gated", B, T, x, ref, feet, legs, gait, stand, gain, tick, mu, body, push, push_ticks, substeps,
+                   step_height, gains, leg_substeps, geometry, inertia, land, drive, ground, foot_mass, slip, actual, desired, forces, feet_log,
+                   contact_log, solved, swing_log, q_log, qd_log, tau_log, foot_log, err_log, flag_log, miss_log, cmd_log, slip_log, disp_log,
+                   feed, est_state, est_init, height, bias, noise, enc_noise, estimator, imu_log, q_enc_log, qd_enc_log, est_log, feet_est_log,
+                   sigma_log, nis_log, gate, trust_log, stream)
+
     # (`estimator` is an MpcQpEstimator or None = the defaults)
     def imu_log_ptr(self, B, T, actual, forces, feet, base_acc, body, bias, noise, imu, estimator=None, stream=0):
         """What an IMU at the CoM reads on every row of a log (include/mpcqp_estimate.h, mpcqp_imu_log)."""
@@ -470,6 +513,13 @@ class Engine:
         """The state estimator over the rows of a log (include/mpcqp_estimate.h, mpcqp_estimate_track)."""
         self._call("mpcqp_estimate_track", B, T, imu, q, qd, contact_log, trust, height, init, estimator, geometry, state, est, feet_est,
                    sigma, nis, stream)
+
+    def estimate_track_gated_ptr(self, B, T, imu, q, qd, contact_log, trust, height, init, state, est, feet_est, sigma, nis, trust_out,
+                                 estimator=None, gate=None, geometry=None, stream=0):
+        """`estimate_track_ptr` with the trust gated per leg (include/mpcqp_gate.h, mpcqp_estimate_track_gated); `gate` is an
+        MpcQpTrustGate or None = the defaults."""
+        self._call("mpcqp_estimate_track_gated", B, T, imu, q, qd, contact_log, trust, height, init, estimator, geometry, state, est, feet_est,
+                   sigma, nis, gate, trust_out, stream)
 
     def phase_swing_ptr(self, B, T, actual, desired, feet_log, gait, tick0, stand, gain, step_height, swing, feet_des=0, stream=0):
         """The swing-foot trajectories of a roll-out on a gait clock, from its logs (include/mpcqp_plan.h, mpcqp_phase_swing)."""

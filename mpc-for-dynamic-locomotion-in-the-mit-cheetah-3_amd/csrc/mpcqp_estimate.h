@@ -1,6 +1,7 @@
 // mpcqp_estimate.h -- the torso state estimated from an IMU and leg kinematics (the C-ABI is include/mpcqp_estimate.h, which has the
 // rule; the entry points live in mpcqp_kernels.hip): mpcqp_imu_log (what an IMU at the CoM reads on every row of a log) and
-// mpcqp_estimate_track (orientation filter plus three 6-state Kalman filters over the rows).
+// mpcqp_estimate_track (orientation filter plus three 6-state Kalman filters over the rows) and, as a compile-time variant of its
+// kernel, mpcqp_estimate_track_gated (include/mpcqp_gate.h: the trust of each leg gated on its velocity innovation before the updates).
 //
 // The filter is serial in T and parallel in B.  Four lanes per robot, the mapping of the leg kernels: lane l does leg l's forward map,
 // then lanes 0..2 own one axis each (xi[a] and the upper triangle of P[a], 6 + 21 doubles in registers) and take the four legs' rho,
@@ -9,6 +10,8 @@
 // vector, omega and nis.  Every lane of a quad runs the same instructions but for the height rows, which only the z lanes enter.
 // No LDS, no scratch: the measurement order is unrolled, so every index into xi and P is a constant.
 // Poison is a per-robot flag, combined over the quad once per row; outputs and the returned state are selects on it.
+// The gate (est_gate) keeps the mapping: lanes 0 and 1 form the legs' normalised innovations along x and y from their own xi and P, two
+// quad broadcasts per leg sum them in every lane, and every lane then holds the four gated trusts; lane 3 stores them.
 #pragma once
 #include "mpcqp_legsim.h"
 #include "../../include/mpcqp_estimate.h"
@@ -88,13 +91,36 @@ __device__ __forceinline__ void est_leg(const EstPar& par, double (&xi)[6], doub
 
 __device__ __forceinline__ double est_pick(const int a, const double x, const double y, const double z) { return a == 0 ? x : (a == 1 ? y : z); }
 
-// mpcqp_estimate_track: i = 4 b + lane.  trust / height / state and each output may be null.
+// MpcQpTrustGate as the kernels take it (checked on the host, gate_row in mpcqp_kernels.hip): d_lo, d_hi, d_hi - d_lo.
+struct EstGate { double lo, hi, span; };
+
+// Step 1g of the row (include/mpcqp_gate.h): the four legs' trust c gated on the legs' velocity innovations along x and y against the
+// predicted state, in place.  Lanes 0 and 1 own x and y and form the four m_la from their xi and U; lanes 2 and 3 run the same
+// instructions on z and their values are not read.  Afterwards every lane of the quad holds the four w_l, as the I/O type holds them.
 template <typename TIO>
+__device__ __forceinline__ void est_gate(const EstGate& gate, const EstPar& par, const double (&xi)[6], const double (&U)[21],
+                                         const double (&zv)[4], double (&tr)[4]) {
+#pragma clang fp contract(off)
+  const double S = U[est_ut(1, 1)] + par.rv;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const double e = (-zv[j]) - xi[1];
+    const double m = (e * e) / S;
+    const double dl = quad_bcast<0>(m) + quad_bcast<1>(m);
+    const double g = dl <= gate.lo ? 1.0 : (dl < gate.hi ? (gate.hi - dl) / gate.span : 0.0);
+    tr[j] = (double)(TIO)(tr[j] * g);
+  }
+}
+
+// mpcqp_estimate_track (GATE = false) and mpcqp_estimate_track_gated: i = 4 b + lane.  trust / height / state and each output may be
+// null.  GATE adds step 1g and the trust_out rows (lane 3's); without it `gate` and `trust_out`, the last two arguments, are not read.
+template <typename TIO, bool GATE>
 __global__ void __launch_bounds__(256)
 mpcqp_estimate_track_kernel(const TIO* __restrict__ imu, const TIO* __restrict__ q, const TIO* __restrict__ qd,
                             const uint8_t* __restrict__ contact, const TIO* __restrict__ trust, const TIO* __restrict__ height,
                             const TIO* __restrict__ init, const EstPar par, const LegGeoDev geo, double* state, TIO* __restrict__ est,
-                            TIO* __restrict__ feet_est, TIO* __restrict__ sigma, TIO* __restrict__ nis_out, const int64_t B, const int T) {
+                            TIO* __restrict__ feet_est, TIO* __restrict__ sigma, TIO* __restrict__ nis_out, const int64_t B, const int T,
+                            const EstGate gate, TIO* __restrict__ trust_out) {
 #pragma clang fp contract(off)
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= 4 * B) return;   // (whole quads leave: the lane moves below see all four lanes or none)
@@ -169,6 +195,8 @@ mpcqp_estimate_track_kernel(const TIO* __restrict__ imu, const TIO* __restrict__
 #pragma unroll
       for (int j = 0; j < 4; ++j) xi[2 + j] = xi[0] + zr[j];
     }
+    // 1g. the gate: tr becomes w
+    if constexpr (GATE) est_gate<TIO>(gate, par, xi, U, zv, tr);
     // 2. the scalar updates
     double na = 0.0;
     est_leg<0>(par, xi, U, zr[0], zv[0], tr[0], hgt, hl[0], na);
@@ -193,6 +221,12 @@ mpcqp_estimate_track_kernel(const TIO* __restrict__ imu, const TIO* __restrict__
         store3(est + 12 * row + 6, ok, om);
       }
       if (nis_out) nis_out[row] = (TIO)(ok ? nis : nan);
+      if constexpr (GATE) {
+        if (trust_out) {
+#pragma unroll
+          for (int j = 0; j < 4; ++j) trust_out[4 * row + j] = (TIO)(ok ? tr[j] : nan);
+        }
+      }
     }
     // 4. predict
     const double aw = ((est_pick(a, R.r0.x, R.r1.x, R.r2.x) * sf.x + est_pick(a, R.r0.y, R.r1.y, R.r2.y) * sf.y) +

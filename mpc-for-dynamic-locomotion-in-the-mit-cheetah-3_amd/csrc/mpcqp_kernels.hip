@@ -3,8 +3,8 @@
 // Replaces, for a batch of B independent robots, the solve the reference performs once per control tick:
 // CasADi Opti('conic') -> OSQP on the QP of src/mpc.py:58-173, filled at src/mpc.py:242-255, solved at :258.
 //
-// This translation unit is the C-ABI of include/mpcqp.h, mpcqp_plan.h, mpcqp_sim.h, mpcqp_model.h, mpcqp_joints.h, mpcqp_actuators.h, mpcqp_slip.h and
-// mpcqp_estimate.h,
+// This translation unit is the C-ABI of include/mpcqp.h, mpcqp_plan.h, mpcqp_sim.h, mpcqp_model.h, mpcqp_joints.h, mpcqp_actuators.h, mpcqp_slip.h,
+// mpcqp_estimate.h, mpcqp_observe.h and mpcqp_gate.h,
 // in three parts: the handle; its host helpers in one anonymous namespace, in order of use (errors, I/O-type dispatch, the solve, workspaces,
 // the device guard and the launch tail `on_device`, grids, the policy behind the configuration's defaults, the engine's tables, the roll-out
 // loops, the leg rows, the row tables); one extern "C" block of entry points, each its own checks and its own launches.  The device code is in
@@ -23,7 +23,9 @@
 //   mpcqp_joints.h       closed-form leg inverse kinematics and the joint-space log of a roll-out
 //   mpcqp_actuators.h    per-robot actuator rows: the conversion of the caller's table and the torque-speed envelope the leg kernels share
 //   mpcqp_slip.h         stance feet that slide: the stance drive's rule with slip kinematics, and the foot move of its roll-out
-//   mpcqp_estimate.h     the torso state from an IMU and leg kinematics: the IMU rows of a log and the filter over them
+//   mpcqp_estimate.h     the torso state from an IMU and leg kinematics: the IMU rows of a log and the filter over them, without and
+//                        with the per-leg trust gate
+//   mpcqp_observe.h      sensors and that filter inside the slip roll-out's tick loop, without and with the gate
 // DESIGN.md has the derivations.
 
 #include "mpcqp_wrench.h"
@@ -40,6 +42,7 @@
 #include "mpcqp_score.h"
 #include "mpcqp_estimate.h"
 #include "mpcqp_observe.h"
+#include "../../include/mpcqp_gate.h"
 
 #include <cstdio>
 #include <cstdlib>
@@ -835,10 +838,12 @@ struct RolloutDriveArgs { int32_t drive; const void* ground; void* cmd_log; };
 // What mpcqp_rollout_slip adds to mpcqp_rollout_drive: the feet's effective mass [B], the slip state [B,4,2], its two logs or null.
 struct RolloutSlipArgs { const void* foot_mass; double* slip; double* slip_log; void* disp_log; };
 // What mpcqp_rollout_observe adds to mpcqp_rollout_slip: what the MPC reads, the filter state [B,131], the optional operands of the
-// sensors and the filter, the checked parameters, the seven logs or null.
+// sensors and the filter, the checked parameters, the seven logs or null; for mpcqp_rollout_observe_gated the checked thresholds (null: no
+// gate) and the trust log or null.
 struct RolloutObserveArgs {
   int32_t feed; double* est_state; const void *est_init, *height, *bias, *noise, *enc_noise; EstPar par;
   void *imu_log, *q_enc_log, *qd_enc_log, *est_log, *feet_est_log, *sigma_log, *nis_log;
+  const EstGate* gate; void* trust_log;
 };
 
 // mpcqp_rollout_legs (dr = null), mpcqp_rollout_drive, mpcqp_rollout_slip (sl, with dr) and mpcqp_rollout_observe (ob, with both): one
@@ -896,9 +901,10 @@ int rollout_legs_run(mpcqp_handle h, const char* who, int64_t B, int32_t T, void
       using TIO = decltype(tag);
       if (!ob) return launch_phase_expand<TIO>(h, B, st, xs, rf, phase_rows<TIO>(feet, gait, stand, gain), tick, w);
       const ObsWs<TIO> ow = observe_ws<TIO>(h->roll_mem, B, N);
-      hipLaunchKernelGGL((mpcqp_observe_update_kernel<TIO>), gl, nt, 0, st, (const TIO*)xs, (const TIO*)rf,
-                         phase_rows<TIO>(feet, gait, stand, gain), (const int32_t*)tick, (const double*)sl->slip, (const double*)legs,
-                         (const TIO*)step_height, observe_in(tag), ob->par, g, ob->est_state, ow, observe_out(tag), d, B, (int)T, it);
+      const auto update = ob->gate ? mpcqp_observe_update_kernel<TIO, true> : mpcqp_observe_update_kernel<TIO, false>;
+      hipLaunchKernelGGL(update, gl, nt, 0, st, (const TIO*)xs, (const TIO*)rf, phase_rows<TIO>(feet, gait, stand, gain),
+                         (const int32_t*)tick, (const double*)sl->slip, (const double*)legs, (const TIO*)step_height, observe_in(tag), ob->par, g,
+                         ob->est_state, ow, observe_out(tag), d, B, (int)T, it, ob->gate ? *ob->gate : EstGate{}, (TIO*)ob->trust_log);
       launch_phase_expand<TIO>(h, B, st, fed ? (const TIO*)ow.xhat : (const TIO*)xs, rf, phase_rows<TIO>(fed ? (void*)ow.feet : feet, gait, stand, gain),
                                tick, w);
     },
@@ -960,6 +966,79 @@ int estimator_row(mpcqp_handle h, const char* who, const MpcQpEstimator* par, Es
   e = {par->gravity, par->kappa, par->q_p, par->q_v, par->q_f, par->r_p, par->r_v, par->r_z, par->k_swing, par->p0_p, par->p0_v, par->p0_f,
        d, 0.5 * d * d};
   return MPCQP_OK;
+}
+
+// The gate's thresholds of an entry point `who` (null: the defaults), checked.
+int gate_row(mpcqp_handle h, const char* who, const MpcQpTrustGate* gate, EstGate& e) {
+  MpcQpTrustGate dflt;
+  if (!gate) { (void)mpcqp_default_trust_gate(&dflt); gate = &dflt; }
+  if (gate->size != sizeof(MpcQpTrustGate)) return bad(h, who, "trust gate struct size mismatch");
+  if (!std::isfinite(gate->d_lo) || !std::isfinite(gate->d_hi) || !(gate->d_lo >= 0) || !(gate->d_hi > gate->d_lo))
+    return bad(h, who, "trust gate: d_lo and d_hi must be finite with 0 <= d_lo < d_hi");
+  e = {gate->d_lo, gate->d_hi, gate->d_hi - gate->d_lo};
+  return MPCQP_OK;
+}
+
+// mpcqp_estimate_track (gated = false: no gate, no trust_out) and mpcqp_estimate_track_gated: one argument check, one launch each.
+int estimate_track_run(mpcqp_handle h, const char* who, int64_t B, int32_t T, const void* imu, const void* q, const void* qd,
+                       const uint8_t* contact_log, const void* trust, const void* height, const void* init, const MpcQpEstimator* par,
+                       const MpcQpLegGeometry* geo, double* state, void* est, void* feet_est, void* sigma, void* nis, bool gated,
+                       const MpcQpTrustGate* gate, void* trust_out, void* stream) {
+  if (!h) return MPCQP_EINVAL;
+  if (B < 0 || B > 0x7fffffff || T < 0 || B * (int64_t)T > 0x1fffffff) return bad(h, who, "size out of range");
+  if (!est && !feet_est && !sigma && !nis && !trust_out)
+    return bad(h, who, gated ? "no output buffer (est, feet_est, sigma, nis and trust_out are all null)"
+                             : "no output buffer (est, feet_est, sigma and nis are all null)");
+  if (B > 0 && T > 0 && (!imu || !q || !qd)) return bad(h, who, "null buffer (imu, q, qd)");
+  if (B > 0 && T > 0 && !init) return bad(h, who, "null init buffer");
+  if (B > 0 && T > 0 && !trust && !contact_log) return bad(h, who, "null contact_log buffer without trust");
+  EstPar e;
+  if (const int rc = estimator_row(h, who, par, e)) return rc;
+  EstGate eg = {};
+  if (gated)
+    if (const int rc = gate_row(h, who, gate, eg)) return rc;
+  LegGeoDev g;
+  if (const int rc = leg_geometry(h, who, geo, false, g)) return rc;
+  if (B == 0 || T == 0) return MPCQP_OK;
+  return on_device(h, gated ? "gated estimate track kernel launch" : "estimate track kernel launch", [&](auto tag) {
+    using TIO = decltype(tag);
+    const auto track = gated ? mpcqp_estimate_track_kernel<TIO, true> : mpcqp_estimate_track_kernel<TIO, false>;
+    hipLaunchKernelGGL(track, leg_grid(B), dim3(256), 0, (hipStream_t)stream, (const TIO*)imu, (const TIO*)q, (const TIO*)qd, contact_log,
+                       (const TIO*)trust, (const TIO*)height, (const TIO*)init, e, g, state, (TIO*)est, (TIO*)feet_est, (TIO*)sigma,
+                       (TIO*)nis, B, (int)T, eg, (TIO*)trust_out);
+  });
+}
+
+// The slip roll-out's arguments as mpcqp_rollout_slip, _observe and _observe_gated take them, in their order.
+struct RolloutSlipCall {
+  int64_t B; int32_t T; void *x, *ref, *feet; double* legs; const int32_t* gait; const void *stand, *gain; int32_t* tick;
+  const void *mu, *body, *push; const int32_t* push_ticks; int32_t substeps; const void *step_height, *gains; int32_t leg_substeps;
+  const MpcQpLegGeometry* geo; const MpcQpLegInertia* inr; int32_t land, drive; const void *ground, *foot_mass; double* slip;
+  void *actual, *desired, *forces, *feet_log; uint8_t* contact_log; int32_t* solved; void *swing_log, *q_log, *qd_log, *tau_log, *foot_log,
+      *err_log; uint8_t* flag_log; void *miss_log, *cmd_log; double* slip_log; void* disp_log;
+};
+
+// mpcqp_rollout_observe (gated = false) and mpcqp_rollout_observe_gated: the checks of what they add to mpcqp_rollout_slip, then its loop.
+int rollout_observe_run(mpcqp_handle h, const char* who, const RolloutSlipCall& c, int32_t feed, double* est_state, const void* est_init,
+                        const void* height, const void* bias, const void* noise, const void* enc_noise, const MpcQpEstimator* par,
+                        void* imu_log, void* q_enc_log, void* qd_enc_log, void* est_log, void* feet_est_log, void* sigma_log, void* nis_log,
+                        bool gated, const MpcQpTrustGate* gate, void* trust_log, void* stream) {
+  if (!h) return MPCQP_EINVAL;
+  if (feed != MPCQP_FEED_TRUTH && feed != MPCQP_FEED_ESTIMATE) return bad(h, who, "feed is neither MPCQP_FEED_TRUTH nor MPCQP_FEED_ESTIMATE");
+  RolloutObserveArgs ob = {feed, est_state, est_init, height, bias, noise, enc_noise, {}, imu_log, q_enc_log, qd_enc_log, est_log, feet_est_log,
+                           sigma_log, nis_log, nullptr, trust_log};
+  if (const int rc = estimator_row(h, who, par, ob.par)) return rc;
+  EstGate eg = {};
+  if (gated) {
+    if (const int rc = gate_row(h, who, gate, eg)) return rc;
+    ob.gate = &eg;
+  }
+  const RolloutDriveArgs dr = {c.drive, c.ground, c.cmd_log};
+  const RolloutSlipArgs sl = {c.foot_mass, c.slip, c.slip_log, c.disp_log};
+  return rollout_legs_run(h, who, c.B, c.T, c.x, c.ref, c.feet, c.legs, c.gait, c.stand, c.gain, c.tick, c.mu, c.body, c.push, c.push_ticks,
+                          c.substeps, c.step_height, c.gains, c.leg_substeps, c.geo, c.inr, c.land, c.actual, c.desired, c.forces, c.feet_log,
+                          c.contact_log, c.solved, c.swing_log, c.q_log, c.qd_log, c.tau_log, c.foot_log, c.err_log, c.flag_log, c.miss_log,
+                          stream, &dr, &sl, &ob);
 }
 
 }  // namespace
@@ -1617,17 +1696,29 @@ int mpcqp_rollout_observe(mpcqp_handle h, int64_t B, int32_t T, void* x, void* r
                           const void* est_init, const void* height, const void* bias, const void* noise, const void* enc_noise,
                           const MpcQpEstimator* par, void* imu_log, void* q_enc_log, void* qd_enc_log, void* est_log, void* feet_est_log,
                           void* sigma_log, void* nis_log, void* stream) {
-  if (!h) return MPCQP_EINVAL;
-  const char* who = "mpcqp_rollout_observe";
-  if (feed != MPCQP_FEED_TRUTH && feed != MPCQP_FEED_ESTIMATE) return bad(h, who, "feed is neither MPCQP_FEED_TRUTH nor MPCQP_FEED_ESTIMATE");
-  RolloutObserveArgs ob = {feed, est_state, est_init, height, bias, noise, enc_noise, {}, imu_log, q_enc_log, qd_enc_log, est_log, feet_est_log,
-                           sigma_log, nis_log};
-  if (const int rc = estimator_row(h, who, par, ob.par)) return rc;
-  const RolloutDriveArgs dr = {drive, ground, cmd_log};
-  const RolloutSlipArgs sl = {foot_mass, slip, slip_log, disp_log};
-  return rollout_legs_run(h, who, B, T, x, ref, feet, legs, gait, stand, gain, tick, mu, body, push, push_ticks, substeps, step_height, gains,
-                          leg_substeps, geo, inr, land, actual, desired, forces, feet_log, contact_log, solved, swing_log, q_log, qd_log,
-                          tau_log, foot_log, err_log, flag_log, miss_log, stream, &dr, &sl, &ob);
+  const RolloutSlipCall c = {B, T, x, ref, feet, legs, gait, stand, gain, tick, mu, body, push, push_ticks, substeps, step_height, gains,
+                             leg_substeps, geo, inr, land, drive, ground, foot_mass, slip, actual, desired, forces, feet_log, contact_log,
+                             solved, swing_log, q_log, qd_log, tau_log, foot_log, err_log, flag_log, miss_log, cmd_log, slip_log, disp_log};
+  return rollout_observe_run(h, "mpcqp_rollout_observe", c, feed, est_state, est_init, height, bias, noise, enc_noise, par, imu_log, q_enc_log,
+                             qd_enc_log, est_log, feet_est_log, sigma_log, nis_log, false, nullptr, nullptr, stream);
+}
+
+int mpcqp_rollout_observe_gated(mpcqp_handle h, int64_t B, int32_t T, void* x, void* ref, void* feet, double* legs, const int32_t* gait,
+                                const void* stand, const void* gain, int32_t* tick, const void* mu, const void* body, const void* push,
+                                const int32_t* push_ticks, int32_t substeps, const void* step_height, const void* gains,
+                                int32_t leg_substeps, const MpcQpLegGeometry* geo, const MpcQpLegInertia* inr, int32_t land, int32_t drive,
+                                const void* ground, const void* foot_mass, double* slip, void* actual, void* desired, void* forces,
+                                void* feet_log, uint8_t* contact_log, int32_t* solved, void* swing_log, void* q_log, void* qd_log,
+                                void* tau_log, void* foot_log, void* err_log, uint8_t* flag_log, void* miss_log, void* cmd_log,
+                                double* slip_log, void* disp_log, int32_t feed, double* est_state, const void* est_init, const void* height,
+                                const void* bias, const void* noise, const void* enc_noise, const MpcQpEstimator* par, void* imu_log,
+                                void* q_enc_log, void* qd_enc_log, void* est_log, void* feet_est_log, void* sigma_log, void* nis_log,
+                                const MpcQpTrustGate* gate, void* trust_log, void* stream) {
+  const RolloutSlipCall c = {B, T, x, ref, feet, legs, gait, stand, gain, tick, mu, body, push, push_ticks, substeps, step_height, gains,
+                             leg_substeps, geo, inr, land, drive, ground, foot_mass, slip, actual, desired, forces, feet_log, contact_log,
+                             solved, swing_log, q_log, qd_log, tau_log, foot_log, err_log, flag_log, miss_log, cmd_log, slip_log, disp_log};
+  return rollout_observe_run(h, "mpcqp_rollout_observe_gated", c, feed, est_state, est_init, height, bias, noise, enc_noise, par, imu_log,
+                             q_enc_log, qd_enc_log, est_log, feet_est_log, sigma_log, nis_log, true, gate, trust_log, stream);
 }
 
 int mpcqp_rollout_score(mpcqp_handle h, int64_t B, int32_t T, const void* actual, const void* desired, const void* forces,
@@ -1693,24 +1784,25 @@ int mpcqp_imu_log(mpcqp_handle h, int64_t B, int32_t T, const void* actual, cons
 int mpcqp_estimate_track(mpcqp_handle h, int64_t B, int32_t T, const void* imu, const void* q, const void* qd, const uint8_t* contact_log,
                          const void* trust, const void* height, const void* init, const MpcQpEstimator* par, const MpcQpLegGeometry* geo,
                          double* state, void* est, void* feet_est, void* sigma, void* nis, void* stream) {
-  if (!h) return MPCQP_EINVAL;
-  if (B < 0 || B > 0x7fffffff || T < 0 || B * (int64_t)T > 0x1fffffff) return fail(h, MPCQP_EINVAL, "mpcqp_estimate_track: size out of range");
-  if (!est && !feet_est && !sigma && !nis)
-    return fail(h, MPCQP_EINVAL, "mpcqp_estimate_track: no output buffer (est, feet_est, sigma and nis are all null)");
-  if (B > 0 && T > 0 && (!imu || !q || !qd)) return fail(h, MPCQP_EINVAL, "mpcqp_estimate_track: null buffer (imu, q, qd)");
-  if (B > 0 && T > 0 && !init) return fail(h, MPCQP_EINVAL, "mpcqp_estimate_track: null init buffer");
-  if (B > 0 && T > 0 && !trust && !contact_log) return fail(h, MPCQP_EINVAL, "mpcqp_estimate_track: null contact_log buffer without trust");
-  EstPar e;
-  if (const int rc = estimator_row(h, "mpcqp_estimate_track", par, e)) return rc;
-  LegGeoDev g;
-  if (const int rc = leg_geometry(h, "mpcqp_estimate_track", geo, false, g)) return rc;
-  if (B == 0 || T == 0) return MPCQP_OK;
-  return on_device(h, "estimate track kernel launch", [&](auto tag) {
-    using TIO = decltype(tag);
-    hipLaunchKernelGGL((mpcqp_estimate_track_kernel<TIO>), leg_grid(B), dim3(256), 0, (hipStream_t)stream, (const TIO*)imu, (const TIO*)q,
-                       (const TIO*)qd, contact_log, (const TIO*)trust, (const TIO*)height, (const TIO*)init, e, g, state, (TIO*)est,
-                       (TIO*)feet_est, (TIO*)sigma, (TIO*)nis, B, (int)T);
-  });
+  return estimate_track_run(h, "mpcqp_estimate_track", B, T, imu, q, qd, contact_log, trust, height, init, par, geo, state, est, feet_est,
+                            sigma, nis, false, nullptr, nullptr, stream);
+}
+
+int mpcqp_default_trust_gate(MpcQpTrustGate* gate) {
+  if (!gate) return MPCQP_EINVAL;
+  memset(gate, 0, sizeof(*gate));
+  gate->size = (uint32_t)sizeof(*gate);
+  gate->d_lo = 1.0;
+  gate->d_hi = 4.0;
+  return MPCQP_OK;
+}
+
+int mpcqp_estimate_track_gated(mpcqp_handle h, int64_t B, int32_t T, const void* imu, const void* q, const void* qd,
+                               const uint8_t* contact_log, const void* trust, const void* height, const void* init,
+                               const MpcQpEstimator* par, const MpcQpLegGeometry* geo, double* state, void* est, void* feet_est, void* sigma,
+                               void* nis, const MpcQpTrustGate* gate, void* trust_out, void* stream) {
+  return estimate_track_run(h, "mpcqp_estimate_track_gated", B, T, imu, q, qd, contact_log, trust, height, init, par, geo, state, est,
+                            feet_est, sigma, nis, true, gate, trust_out, stream);
 }
 
 int mpcqp_last_kernel_ms(mpcqp_handle h, float* ms) {

@@ -12,6 +12,9 @@
 // the order of mpcqp_legs_step_kernel.  Between the two kernels the state passes through est_state in fp64, so the two halves of a row
 // are the row of mpcqp_estimate_track_kernel bit for bit.  Poison is the state itself: a robot whose row is not finite gets a NaN
 // state, and a NaN state poisons every later row.
+// mpcqp_rollout_observe_gated (include/mpcqp_gate.h) launches the update kernel's GATE variant: the same kernel with est_gate between
+// steps 1 and 2, which leaves the gated trust where the update leaves "the trust of step 1" for the predict kernel; the predict kernel,
+// the side buffers and the launch count are the ungated call's.
 #pragma once
 #include "mpcqp_estimate.h"
 #include "mpcqp_legroll.h"
@@ -83,13 +86,16 @@ __device__ __forceinline__ void obs_encoders(const TIO* __restrict__ xb, const T
   qde = carried ? V3{leg7[3], leg7[4], leg7[5]} : V3{qr[0], qr[1], qr[2]};
 }
 
-// Sense and update of tick `it`: i = 4 b + lane.
-template <typename TIO>
+// Sense and update of tick `it`: i = 4 b + lane.  GATE (mpcqp_rollout_observe_gated) adds step 1g of the filter's row (est_gate,
+// include/mpcqp_gate.h): the sensor row the predict reads back then carries w in the place of the clock's trust, and trust_log (may be
+// null) gets the row's w; without it `gate` and `trust_log`, the last two arguments, are not read.
+template <typename TIO, bool GATE>
 __global__ void __launch_bounds__(256)
 mpcqp_observe_update_kernel(const TIO* __restrict__ x, const TIO* __restrict__ ref, const PhaseRows<TIO> ph, const int32_t* __restrict__ tick,
                             const double* __restrict__ slip, const double* __restrict__ legs, const TIO* __restrict__ step_height,
                             const ObsIn<TIO> in, const EstPar par, const LegGeoDev geo, double* state, const ObsWs<TIO> ws,
-                            const ObsOut<TIO> out, const double d, const int64_t B, const int T, const int it) {
+                            const ObsOut<TIO> out, const double d, const int64_t B, const int T, const int it, const EstGate gate,
+                            TIO* __restrict__ trust_log) {
 #pragma clang fp contract(off)
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= 4 * B) return;   // (whole quads leave: the lane moves below see all four lanes or none)
@@ -138,12 +144,14 @@ mpcqp_observe_update_kernel(const TIO* __restrict__ x, const TIO* __restrict__ r
   }
   mine = mine && fin3(gy);
   const double tme = stance ? 1.0 : 0.0;
-  const double tr[4] = {quad_bcast<0>(tme), quad_bcast<1>(tme), quad_bcast<2>(tme), quad_bcast<3>(tme)};
-  if (l == 3) {
-    TIO* s = ws.sense + OBS_SENSE * b;
-    store3(s, true, gy);
+  double tr[4] = {quad_bcast<0>(tme), quad_bcast<1>(tme), quad_bcast<2>(tme), quad_bcast<3>(tme)};
+  if constexpr (!GATE) {
+    if (l == 3) {
+      TIO* s = ws.sense + OBS_SENSE * b;
+      store3(s, true, gy);
 #pragma unroll
-    for (int j = 0; j < 4; ++j) s[3 + j] = (TIO)tr[j];
+      for (int j = 0; j < 4; ++j) s[3 + j] = (TIO)tr[j];
+    }
   }
   // ---- the filter state: a fresh start from est_init (null: the robot's x as stored), or est_state
   double* const sb = state + b * EST_STATE;
@@ -201,6 +209,20 @@ mpcqp_observe_update_kernel(const TIO* __restrict__ x, const TIO* __restrict__ r
   if (fresh) {
 #pragma unroll
     for (int j = 0; j < 4; ++j) xi[2 + j] = xi[0] + zr[j];
+  }
+  // 1g. the gate: tr becomes w, which is what the predict reads back (a poisoned robot's predict does not use it: its state is NaN)
+  if constexpr (GATE) {
+    est_gate<TIO>(gate, par, xi, U, zv, tr);
+    if (l == 3) {
+      TIO* s = ws.sense + OBS_SENSE * b;
+      store3(s, true, gy);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) s[3 + j] = (TIO)tr[j];
+      if (trust_log) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) trust_log[4 * row + j] = (TIO)(ok ? tr[j] : nan);
+      }
+    }
   }
   // 2. the scalar updates
   double na = 0.0;

@@ -659,7 +659,7 @@ class MPCBatch:
     def rollout_observe(self, x, ref, feet, legs, gait, stand, gain, tick, mu, T, step_height, ground, foot_mass, slip, est_state,
                         feed="estimate", est_init=None, height=None, bias=None, noise=None, enc_noise=None, estimator=None, land="rule",
                         drive="limited", body=None, push=None, push_ticks=None, substeps=10, gains=None, leg_substeps=0, inertia=None,
-                        geometry=None, log=True, stream=None):
+                        geometry=None, log=True, stream=None, gate=None):
         """`rollout_slip` with sensors and the state estimator inside the tick loop (include/mpcqp_observe.h, mpcqp_rollout_observe,
         which has the rule; the host counterpart is gaits.rollout_observe_host): per tick the encoders and the IMU are read off the
         live state, one row of `estimate_track` runs on est_state float64 [B,131] (state next to `x`, ..., `slip`, advanced IN PLACE;
@@ -668,7 +668,9 @@ class MPCBatch:
         `rollout_slip`'s bit for bit.  height [B,4] as in `estimate_track`, bias [B,6] and noise [B,T,6] as in `imu_log`, enc_noise
         [B,T,4,6] the (q, qd) noise per leg, `estimator` as in `estimate_track`.  Returns `rollout_slip`'s dict (the plant's truth) plus
         "imu" [B,T,6], "q_enc", "qd_enc" [B,T,4,3], "est" [B,T,12], "feet_est" [B,T,4,3], "sigma" [B,T,6] and "nis" [B,T].  Every
-        other argument as in `rollout_slip`.  Asynchronous on `stream`."""
+        other argument as in `rollout_slip`.  gate: None, or a dict of estimator.gate_row's fields ({} = the defaults) or an
+        MpcQpTrustGate for mpcqp_rollout_observe_gated (include/mpcqp_gate.h): the filter's trust is the clock's gated per leg on the
+        leg's velocity innovation, and the dict gains "trust" [B,T,4].  Asynchronous on `stream`."""
         from . import estimator as _est
         B, T, f64 = int(x.shape[0]), int(T), _torch().float64
         feeds = {"truth": _capi.FEED_TRUTH, "estimate": _capi.FEED_ESTIMATE}
@@ -681,13 +683,16 @@ class MPCBatch:
         tail = (feed if isinstance(feed, int) else feeds[feed], est_state.data_ptr(), _ptr(est_init), _ptr(height), _ptr(bias), _ptr(noise),
                 _ptr(enc_noise), _est.estimator_struct(estimator))
         leg3 = ((4, 3), self.tdtype)
-        return self._rollout_legs(self.engine.rollout_observe_ptr, x, ref, feet, legs, gait, stand, gain, tick, mu, T, step_height, land, body, push, push_ticks, substeps,
+        call, more = self.engine.rollout_observe_ptr, ()
+        if gate is not None:
+            call, more, tail = self.engine.rollout_observe_gated_ptr, (("trust", (4,), self.tdtype),), tail + (_est.gate_struct(gate),)
+        return self._rollout_legs(call, x, ref, feet, legs, gait, stand, gain, tick, mu, T, step_height, land, body, push, push_ticks, substeps,
                                   gains, leg_substeps, inertia, geometry, log, stream, drive,
                                   operands=(("ground", ground, (B,), self.tdtype), ("foot_mass", foot_mass, (B,), self.tdtype),
                                             ("slip", slip, (B, 4, 2), f64)),
                                   logs=(("cmd", (12,), self.tdtype), ("slip_log", (4, 2), f64), ("disp", (4, 2), self.tdtype),
                                         ("imu", (6,), self.tdtype), ("q_enc", *leg3), ("qd_enc", *leg3), ("est", (12,), self.tdtype),
-                                        ("feet_est", *leg3), ("sigma", (6,), self.tdtype), ("nis", (), self.tdtype)), tail=tail)
+                                        ("feet_est", *leg3), ("sigma", (6,), self.tdtype), ("nis", (), self.tdtype)) + more, tail=tail)
 
     def score(self, logs, score=None, rule=None, stream=None):
         """The score row of a roll-out's logs, reduced on the device (include/mpcqp_sim.h, mpcqp_rollout_score; the host counterpart is
@@ -747,14 +752,16 @@ class MPCBatch:
     from .estimator import OUT as EST_OUT      # ("est", "feet", "sigma", "nis"): the host counterpart's names, in the C order
 
     def estimate_track(self, imu, q, qd, contact_log, init, trust=None, height=None, state=None, estimator=None, geometry=None,
-                       want=EST_OUT, stream=None):
+                       want=EST_OUT, stream=None, gate=None):
         """The torso state estimated from the IMU and the leg encoders over the rows of a log (include/mpcqp_estimate.h,
         mpcqp_estimate_track, which has the rule; the host counterparts are estimator.estimate_track_host and estimate_joint_host):
         imu [B,T,6] as `imu_log` returns it, q, qd [B,T,4,3] the "q" / "qd" logs of `rollout_legs`, `rollout_drive`, `rollout_slip` or
         of `joint_rates`, contact_log uint8 [B,T,4], init [B,12] in the layout of an `actual` row; trust [B,T,4] in [0,1] or None
         (contact != 0), height [B,4] the ground under each foot or None, state float64 [B,131] advanced IN PLACE (zeros: start from
         init) or None -> {"est" [B,T,12] in the layout of `actual`, "feet" [B,T,4,3], "sigma" [B,T,6], "nis" [B,T]}; an output not in
-        `want` is None.  Asynchronous on `stream`."""
+        `want` is None.  gate: None, or a dict of estimator.gate_row's fields ({} = the defaults) or an MpcQpTrustGate for
+        mpcqp_estimate_track_gated (include/mpcqp_gate.h): every row's trust is gated per leg on the leg's velocity innovation, and the
+        dict gains "trust" [B,T,4], the trust the rows used.  Asynchronous on `stream`."""
         from . import estimator as _est
         torch = _torch()
         B, T = int(imu.shape[0]), int(imu.shape[1]) if imu.dim() == 3 else -1
@@ -769,9 +776,14 @@ class MPCBatch:
         st = self._stream(stream)
         spec = {"est": ((B, T, 12), self.tdtype), "feet": legs, "sigma": ((B, T, 6), self.tdtype), "nis": ((B, T), self.tdtype)}
         out = dict(zip(self.EST_OUT, self._alloc(stream, *[spec[k] if k in want else None for k in self.EST_OUT])))
-        self.engine.estimate_track_ptr(B, T, imu.data_ptr(), q.data_ptr(), qd.data_ptr(), contact_log.data_ptr(), _ptr(trust), _ptr(height),
-                                       init.data_ptr(), _ptr(state), *[_ptr(out[k]) for k in self.EST_OUT],
-                                       _est.estimator_struct(estimator), geometry, st.cuda_stream)
+        head = (B, T, imu.data_ptr(), q.data_ptr(), qd.data_ptr(), contact_log.data_ptr(), _ptr(trust), _ptr(height), init.data_ptr(), _ptr(state),
+                *[_ptr(out[k]) for k in self.EST_OUT])
+        if gate is None:
+            self.engine.estimate_track_ptr(*head, _est.estimator_struct(estimator), geometry, st.cuda_stream)
+        else:
+            out["trust"], = self._alloc(stream, ((B, T, 4), self.tdtype))
+            self.engine.estimate_track_gated_ptr(*head, out["trust"].data_ptr(), _est.estimator_struct(estimator), _est.gate_struct(gate),
+                                                 geometry, st.cuda_stream)
         return out
 
     def last_kernel_ms(self):

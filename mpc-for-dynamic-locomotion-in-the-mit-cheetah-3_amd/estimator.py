@@ -15,6 +15,7 @@ _XI, _P, _LIVE = 4, 22, 130
 DEFAULTS = {"gravity": -9.81, "kappa": 2.0, "q_p": 0.02, "q_v": 0.02, "q_f": 0.002, "r_p": 0.001, "r_v": 0.1, "r_z": 0.001,
             "k_swing": 100.0, "p0_p": 0.01, "p0_v": 1.0, "p0_f": 0.01}
 OUT = ("est", "feet", "sigma", "nis")
+GATE_DEFAULTS = {"d_lo": 1.0, "d_hi": 4.0}            # include/mpcqp_gate.h, mpcqp_default_trust_gate
 
 
 def estimator_row(**kw):
@@ -47,6 +48,44 @@ def estimator_struct(estimator):
 
 def _row(estimator):
     return estimator_row(**(estimator or {}))
+
+
+def gate_row(**kw):
+    """The trust gate's thresholds as a dict: the defaults of mpcqp_default_trust_gate with `kw` over them, checked as the library
+    checks an MpcQpTrustGate (finite, 0 <= d_lo < d_hi)."""
+    unknown = set(kw) - set(GATE_DEFAULTS)
+    if unknown:
+        raise ValueError(f"MpcQpTrustGate has no field {sorted(unknown)}; the fields are {tuple(GATE_DEFAULTS)}")
+    row = {k: float(kw.get(k, v)) for k, v in GATE_DEFAULTS.items()}
+    if not (np.isfinite(row["d_lo"]) and np.isfinite(row["d_hi"]) and 0 <= row["d_lo"] < row["d_hi"]):
+        raise ValueError("trust gate: d_lo and d_hi must be finite with 0 <= d_lo < d_hi")
+    return row
+
+
+def gate_struct(gate):
+    """An MpcQpTrustGate, or a dict of `gate_row`'s fields ({} = the defaults) -> the structure the binding passes."""
+    from . import _capi
+    if isinstance(gate, _capi.MpcQpTrustGate):
+        return gate
+    row = gate_row(**gate)
+    par = _capi.MpcQpTrustGate()
+    par.size = _capi.ctypes.sizeof(_capi.MpcQpTrustGate)
+    par.d_lo, par.d_hi = row["d_lo"], row["d_hi"]
+    return par
+
+
+def trust_gate(gate, par, xi, P, rhod, c, io_dtype=np.float64):
+    """Step 1g of the row (include/mpcqp_gate.h) in the device's order: xi [3,6,B] and P [3,6,6,B] the predicted state, rhod [B,4,3], c
+    [B,4] the ungated trust -> (w [B,4] as `io_dtype` holds it, d [B,4])."""
+    lo, hi = gate["d_lo"], gate["d_hi"]
+    m = []
+    for a in range(2):
+        e = (-rhod[:, :, a]) - xi[a, 1][:, None]
+        S = P[a, 1, 1] + par["r_v"]
+        m.append((e * e) / S[:, None])
+    d = m[0] + m[1]
+    g = np.where(d <= lo, 1.0, np.where(d < hi, (hi - d) / (hi - lo), 0.0))
+    return (c * g).astype(io_dtype).astype(np.float64), d
 
 
 def _f64(a):
@@ -174,16 +213,22 @@ def _update(xi, P, kind, c, z, r):
     return (e * e) / S
 
 
-def estimate_track_host(imu, q, qd, contact_log, init, trust=None, height=None, state=None, estimator=None, delta=0.03):
+def estimate_track_host(imu, q, qd, contact_log, init, trust=None, height=None, state=None, estimator=None, delta=0.03, gate=None,
+                        io_dtype=np.float64):
     """The filter over the rows of a log (mpcqp_estimate_track), per axis and measurement by measurement in the device's order: imu
     [B,T,6], q, qd [B,T,4,3], contact_log [B,T,4], init [B,12], trust [B,T,4] or None (contact != 0), height [B,4] or None, state
     [B,131] or None (not modified) -> {"est" [B,T,12], "feet" [B,T,4,3], "sigma" [B,T,6], "nis" [B,T], "state" [B,131]: the predicted
     state for row T, live = 1, to be passed to the next piece}.  A robot with a non-finite operand is NaN from that row on and its
-    returned state is NaN."""
+    returned state is NaN.
+    gate: None, or a dict of `gate_row`'s fields ({} = the defaults) for mpcqp_estimate_track_gated (include/mpcqp_gate.h): every row's
+    trust is gated on the legs' velocity innovations before the row's updates, w is rounded through `io_dtype` (the handle's I/O type:
+    with it this is the counterpart of either handle), and the result has "trust" [B,T,4] = w and "gate_d" [B,T,4] = d."""
     par = _row(estimator)
+    gpar = None if gate is None else gate_row(**gate)
     imu, q, qd, init, tr, hz, st, fresh, q0, ok, rows_ok, B, T = _operands(imu, q, qd, contact_log, init, trust, height, state)
     d, hd2, g = float(delta), 0.5 * float(delta) * float(delta), par["gravity"]
     est, feet, sigma, nis = np.zeros((B, T, 12)), np.zeros((B, T, 4, 3)), np.zeros((B, T, 6)), np.zeros((B, T))
+    wlog, dlog = np.zeros((B, T, 4)), np.zeros((B, T, 4))
     with np.errstate(all="ignore"):
         qh = q0 if st is None else np.where(fresh[:, None], q0, st[:, 0:4])
         xi, P = np.zeros((3, 6, B)), np.zeros((3, 6, 6, B))
@@ -207,7 +252,11 @@ def estimate_track_host(imu, q, qd, contact_log, init, trust=None, height=None, 
                 for a in range(3):
                     for l in range(4):
                         xi[a, 2 + l] = np.where(fresh, xi[a, 0] + rho[:, l, a], xi[a, 2 + l])
-            s = [1.0 + (1.0 - tr[:, t, l]) * par["k_swing"] for l in range(4)]
+            w = tr[:, t]
+            if gpar is not None:
+                w, dlog[:, t] = trust_gate(gpar, par, xi, P, rhod, w, io_dtype)
+                wlog[:, t] = w
+            s = [1.0 + (1.0 - w[:, l]) * par["k_swing"] for l in range(4)]
             na = []
             for a in range(3):
                 n = np.zeros(B)
@@ -225,7 +274,7 @@ def estimate_track_host(imu, q, qd, contact_log, init, trust=None, height=None, 
                 sigma[:, t, a], sigma[:, t, 3 + a] = np.sqrt(P[a, 0, 0]), np.sqrt(P[a, 1, 1])
             nis[:, t] = (na[0] + na[1]) + na[2]
             bad = ~ok
-            est[bad, t], feet[bad, t], sigma[bad, t], nis[bad, t] = np.nan, np.nan, np.nan, np.nan
+            est[bad, t], feet[bad, t], sigma[bad, t], nis[bad, t], wlog[bad, t] = np.nan, np.nan, np.nan, np.nan, np.nan
             # predict
             for a in range(3):
                 aw = (R[:, a, 0] * sf[:, 0] + R[:, a, 1] * sf[:, 1]) + R[:, a, 2] * sf[:, 2]
@@ -254,7 +303,8 @@ def estimate_track_host(imu, q, qd, contact_log, init, trust=None, height=None, 
         out_state[:, _P + 36 * a:_P + 36 * a + 36] = P[a].transpose(2, 0, 1).reshape(B, 36)
     out_state[:, _LIVE] = 1.0
     out_state[~ok] = np.nan
-    return {"est": est, "feet": feet, "sigma": sigma, "nis": nis, "state": out_state}
+    res = {"est": est, "feet": feet, "sigma": sigma, "nis": nis, "state": out_state}
+    return res if gpar is None else dict(res, trust=wlog, gate_d=dlog)
 
 
 def estimate_joint_host(imu, q, qd, contact_log, init, trust=None, height=None, state=None, estimator=None, delta=0.03):
