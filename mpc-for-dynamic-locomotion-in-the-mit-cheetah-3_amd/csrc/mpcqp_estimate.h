@@ -12,6 +12,15 @@
 // Poison is a per-robot flag, combined over the quad once per row; outputs and the returned state are selects on it.
 // The gate (est_gate) keeps the mapping: lanes 0 and 1 form the legs' normalised innovations along x and y from their own xi and P, two
 // quad broadcasts per leg sum them in every lane, and every lane then holds the four gated trusts; lane 3 stores them.
+//
+// One row of the filter is written once, as the helpers below, for this file's kernel over a log and for the two kernels of
+// mpcqp_observe.h, which run the same row around a tick of the slip roll-out; that the three compute the same bits rests on that:
+//   state      est_fresh / est_load / est_heights (each folds what it read into the lane's finite flag), est_quad_all, est_store
+//   step 1     est_foot (a leg's rho and rhod), est_across (what a lane's axis sees of the four legs)
+//   steps 1g-2 est_first_feet on a fresh start's first row; est_measure: est_gate, the four legs' scalar updates (est_leg, est_update), nis
+//   step 3     est_out, est_sigma, est_rotvec: the values; each kernel stores them where it keeps them
+//   step 4     est_predict
+//   sensors    est_rotvec_rot, est_sense (R^T v + bias + noise), est_specific_force (applied forces over the body row)
 #pragma once
 #include "mpcqp_legsim.h"
 #include "../../include/mpcqp_estimate.h"
@@ -112,6 +121,205 @@ __device__ __forceinline__ void est_gate(const EstGate& gate, const EstPar& par,
   }
 }
 
+// ---- the filter's state of lane axis a: qh, xi[a] and the upper triangle of P[a].  What is read folds into the lane's finite flag.
+
+// A fresh start from a row that holds rotation vector, CoM and velocity at 0, 3 and 9 (a 12-wide init row, a 13-wide x row).
+template <typename TIO>
+__device__ __forceinline__ void est_fresh(const TIO* __restrict__ x0, const EstPar& par, const int a, double (&qh)[4], double (&xi)[6],
+                                          double (&U)[21], bool& fin) {
+#pragma unroll
+  for (int c = 0; c < 3; ++c) fin = fin && isfinite((double)x0[c]) && isfinite((double)x0[3 + c]) && isfinite((double)x0[9 + c]);
+  plant_rotvec_to_quat((double)x0[0], (double)x0[1], (double)x0[2], qh);
+  xi[0] = (double)x0[3 + a]; xi[1] = (double)x0[9 + a];
+#pragma unroll
+  for (int c = 2; c < 6; ++c) xi[c] = 0.0;   // (the feet are set on the first row, from its rho: est_first_feet)
+#pragma unroll
+  for (int r = 0; r < 6; ++r)
+#pragma unroll
+    for (int c = r; c < 6; ++c) U[est_ut(r, c)] = r != c ? 0.0 : (r == 0 ? par.p0p : (r == 1 ? par.p0v : par.p0f));
+}
+__device__ __forceinline__ void est_load(const double* sb, const int a, double (&qh)[4], double (&xi)[6], double (&U)[21], bool& fin) {
+  fin = fin && isfinite(sb[EST_LIVE]);
+#pragma unroll
+  for (int c = 0; c < 4; ++c) { qh[c] = sb[c]; fin = fin && isfinite(qh[c]); }
+#pragma unroll
+  for (int c = 0; c < 6; ++c) { xi[c] = sb[EST_XI + 6 * a + c]; fin = fin && isfinite(xi[c]); }
+#pragma unroll
+  for (int r = 0; r < 6; ++r)
+#pragma unroll
+    for (int c = r; c < 6; ++c) { U[est_ut(r, c)] = sb[EST_P + 36 * a + 6 * r + c]; fin = fin && isfinite(U[est_ut(r, c)]); }
+}
+// Lanes 0..2 store their axis a, lane 3 the quaternion and the live flag; a poisoned robot's state is NaN.
+__device__ __forceinline__ void est_store(double* sb, const int l, const int a, const bool ok, const double (&qh)[4], const double (&xi)[6],
+                                          const double (&U)[21]) {
+  const double nan = __builtin_nan("");
+  if (l < 3) {
+    double* const xa = sb + EST_XI + 6 * a;
+    double* const Pa = sb + EST_P + 36 * a;   // (the full 6 x 6 of the axis, where est_load reads the upper triangle)
+#pragma unroll
+    for (int c = 0; c < 6; ++c) xa[c] = ok ? xi[c] : nan;
+#pragma unroll
+    for (int r = 0; r < 6; ++r)
+#pragma unroll
+      for (int c = 0; c < 6; ++c) Pa[6 * r + c] = ok ? U[est_sym(r, c)] : nan;
+  } else {
+#pragma unroll
+    for (int c = 0; c < 4; ++c) sb[c] = ok ? qh[c] : nan;
+    sb[EST_LIVE] = ok ? 1.0 : nan;
+  }
+}
+// The ground heights under robot b's four feet (height may be null: zeros, which are not read).
+template <typename TIO>
+__device__ __forceinline__ void est_heights(const TIO* __restrict__ height, const int64_t b, double (&hl)[4], bool& fin) {
+#pragma unroll
+  for (int j = 0; j < 4; ++j) hl[j] = 0.0;
+  if (height) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) { hl[j] = (double)height[4 * b + j]; fin = fin && isfinite(hl[j]); }
+  }
+}
+// Whether all four lanes of the quad say `mine`: the robot's flag, the same in its four lanes.  (Call it where the whole quad runs.)
+__device__ __forceinline__ bool est_quad_all(const bool mine) {
+  float bad = mine ? 0.0f : 1.0f;
+  bad = bad + dpp_mov<0xB1>(bad);
+  bad = bad + dpp_mov<0x4E>(bad);
+  return bad == 0.0f;
+}
+
+// ---- the row
+
+// Step 1: the foot of the leg in geometry slot `slot` and its velocity, relative to the CoM, world axes, from the leg's q and qd.
+__device__ __forceinline__ void est_foot(const LegGeoDev& geo, const int slot, const V3 q, const V3 qd, const M3& R, const V3 gy, V3& rho,
+                                         V3& rhod) {
+#pragma clang fp contract(off)
+  const double ql[3] = {q.x, q.y, q.z};
+  double pf[3], J[9];
+  leg_fk_jac(geo, slot, ql, pf, J);
+  const V3 pb = {pf[0], pf[1], pf[2]};
+  const V3 jq = {(J[0] * qd.x + J[1] * qd.y) + J[2] * qd.z, (J[3] * qd.x + J[4] * qd.y) + J[5] * qd.z, (J[6] * qd.x + J[7] * qd.y) + J[8] * qd.z};
+  rho = est_mv(R, pb); rhod = est_mv(R, est_add(est_cross(gy, pb), jq));
+}
+// ... and what lane axis a sees of a vector that lane j of the quad holds for leg j
+__device__ __forceinline__ void est_across(const int a, const V3 v, double (&z)[4]) {
+  z[0] = est_pick(a, quad_bcast<0>(v.x), quad_bcast<0>(v.y), quad_bcast<0>(v.z));
+  z[1] = est_pick(a, quad_bcast<1>(v.x), quad_bcast<1>(v.y), quad_bcast<1>(v.z));
+  z[2] = est_pick(a, quad_bcast<2>(v.x), quad_bcast<2>(v.y), quad_bcast<2>(v.z));
+  z[3] = est_pick(a, quad_bcast<3>(v.x), quad_bcast<3>(v.y), quad_bcast<3>(v.z));
+}
+
+// The first row of a fresh start: the feet from the row's rho (est_fresh left them zero).
+__device__ __forceinline__ void est_first_feet(const double (&zr)[4], double (&xi)[6]) {
+#pragma clang fp contract(off)
+#pragma unroll
+  for (int j = 0; j < 4; ++j) xi[2 + j] = xi[0] + zr[j];
+}
+// Steps 1g and 2: with GATE tr becomes w (else `gate` is not read), then the scalar updates of the four legs.  Returns the row's nis,
+// the sum over the three axes.
+template <typename TIO, bool GATE>
+__device__ __forceinline__ double est_measure(const EstPar& par, const EstGate& gate, const bool hgt, const double (&hl)[4],
+                                              const double (&zr)[4], const double (&zv)[4], double (&tr)[4], double (&xi)[6], double (&U)[21]) {
+#pragma clang fp contract(off)
+  if constexpr (GATE) est_gate<TIO>(gate, par, xi, U, zv, tr);
+  double na = 0.0;
+  est_leg<0>(par, xi, U, zr[0], zv[0], tr[0], hgt, hl[0], na);
+  est_leg<1>(par, xi, U, zr[1], zv[1], tr[1], hgt, hl[1], na);
+  est_leg<2>(par, xi, U, zr[2], zv[2], tr[2], hgt, hl[2], na);
+  est_leg<3>(par, xi, U, zr[3], zv[3], tr[3], hgt, hl[3], na);
+  return (quad_bcast<0>(na) + quad_bcast<1>(na)) + quad_bcast<2>(na);
+}
+
+// Step 3, what a row puts out after the updates: xi as it stands, the sigma of the axis' position (i = 0) or velocity (i = 1), the
+// rotation vector of qh and omega = est_mv(R, gyro); est_out is a value as a log holds it, NaN for a poisoned robot (store3 takes ok).
+template <typename TIO>
+__device__ __forceinline__ TIO est_out(const bool ok, const double v) { return (TIO)(ok ? v : __builtin_nan("")); }
+__device__ __forceinline__ double est_sigma(const double (&U)[21], const int i) { return sqrt(U[est_ut(i, i)]); }
+__device__ __forceinline__ V3 est_rotvec(const double (&qh)[4]) {
+  double th[3];
+  plant_quat_to_rotvec(qh, th);
+  return {th[0], th[1], th[2]};
+}
+
+// Step 4, the predict of lane axis a from the row's gyro, accelerometer and (gated) trust; R is est_rot(qh).  Leaves the normalised
+// quaternion in qh.
+__device__ __forceinline__ void est_predict(const EstPar& par, const int a, const M3& R, const V3 gy, const V3 sf, const double (&tr)[4],
+                                            double (&qh)[4], double (&xi)[6], double (&U)[21]) {
+#pragma clang fp contract(off)
+  const double aw = ((est_pick(a, R.r0.x, R.r1.x, R.r2.x) * sf.x + est_pick(a, R.r0.y, R.r1.y, R.r2.y) * sf.y) +
+                     est_pick(a, R.r0.z, R.r1.z, R.r2.z) * sf.z) + (a == 2 ? par.g : 0.0);
+  xi[0] = (xi[0] + par.d * xi[1]) + par.hd2 * aw;
+  xi[1] = xi[1] + par.d * aw;
+  U[est_ut(0, 0)] = (U[est_ut(0, 0)] + par.d * U[est_ut(0, 1)]) + par.d * (U[est_ut(0, 1)] + par.d * U[est_ut(1, 1)]);
+#pragma unroll
+  for (int j = 1; j < 6; ++j) U[est_ut(0, j)] = U[est_ut(0, j)] + par.d * U[est_ut(1, j)];
+  U[est_ut(0, 0)] = U[est_ut(0, 0)] + par.d * par.qp;
+  U[est_ut(1, 1)] = U[est_ut(1, 1)] + par.d * par.qv;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) U[est_ut(2 + j, 2 + j)] = U[est_ut(2 + j, 2 + j)] + par.d * (par.qf * (1.0 + (1.0 - tr[j]) * par.ks));
+  const double sn = est_norm(sf), ga = fabs(par.g);
+  const bool pull = sn > 0.0;
+  const V3 sh = {pull ? sf.x / sn : 0.0, pull ? sf.y / sn : 0.0, pull ? sf.z / sn : 0.0};
+  const double c0 = 1.0 - fabs(sn - ga) / ga;
+  const double kap = pull ? par.kappa * (c0 < 0.0 ? 0.0 : (c0 > 1.0 ? 1.0 : c0)) : 0.0;
+  const V3 cr = est_cross(sh, R.r2);
+  const V3 wh = est_mv(R, V3{gy.x + kap * cr.x, gy.y + kap * cr.y, gy.z + kap * cr.z});
+  double dq[4];
+  plant_rotvec_to_quat(par.d * wh.x, par.d * wh.y, par.d * wh.z, dq);
+  const double n0 = ((dq[0] * qh[0] - dq[1] * qh[1]) - dq[2] * qh[2]) - dq[3] * qh[3];
+  const double n1 = ((dq[0] * qh[1] + dq[1] * qh[0]) + dq[2] * qh[3]) - dq[3] * qh[2];
+  const double n2 = ((dq[0] * qh[2] - dq[1] * qh[3]) + dq[2] * qh[0]) + dq[3] * qh[1];
+  const double n3 = ((dq[0] * qh[3] + dq[1] * qh[2]) - dq[2] * qh[1]) + dq[3] * qh[0];
+  const double nq = sqrt(((n0 * n0 + n1 * n1) + n2 * n2) + n3 * n3);
+  qh[0] = n0 / nq; qh[1] = n1 / nq; qh[2] = n2 / nq; qh[3] = n3 / nq;
+}
+
+// ---- the sensor rows: what an IMU at the CoM of the true state reads
+
+__device__ __forceinline__ M3 est_rotvec_rot(const V3 th) {
+  double qt[4];
+  plant_rotvec_to_quat(th.x, th.y, th.z, qt);
+  return est_rot(qt);
+}
+// The body-frame readings of the world vectors wg (the gyro's) and wa (the accelerometer's): R^T w plus row b of bias and row `row` of
+// noise (rows of [gyro 3, acc 3]; either may be null).  Both halves of a row given fold into fin, whichever reading the caller keeps.
+template <typename TIO>
+__device__ __forceinline__ void est_sense(const M3& R, const V3 wg, const V3 wa, const TIO* __restrict__ bias, const int64_t b,
+                                          const TIO* __restrict__ noise, const int64_t row, bool& fin, V3& gyro, V3& acc) {
+  gyro = est_mtv(R, wg); acc = est_mtv(R, wa);
+  if (bias) {
+    const V3 bg = load3(bias + 6 * b), ba = load3(bias + 6 * b + 3);
+    gyro = est_add(gyro, bg); acc = est_add(acc, ba);
+    fin = fin && fin3(bg) && fin3(ba);
+  }
+  if (noise) {
+    const V3 ng = load3(noise + 6 * row), na = load3(noise + 6 * row + 3);
+    gyro = est_add(gyro, ng); acc = est_add(acc, na);
+    fin = fin && fin3(ng) && fin3(na);
+  }
+}
+// The specific force, world axes, of the plant's right-hand side under the applied leg forces f [4,3] and, where `pushed`, the force of
+// row b of push: the sum across the four legs in mpcqp_leg_effort's order, (0 + 1) + (2 + 3), over the mass of robot b's body row,
+// through the acceleration the plant forms.  The body row's check and the operands fold into fin.
+template <typename TIO>
+__device__ __forceinline__ V3 est_specific_force(const TIO* __restrict__ f, const bool pushed, const TIO* __restrict__ push,
+                                                 const TIO* __restrict__ body, const PlantModel& model, const int64_t b, const double g,
+                                                 bool& fin) {
+#pragma clang fp contract(off)
+  double bd[7], Ii[6];
+  plant_body_row(body, model, b, bd);
+  const double Ib[6] = {bd[1], bd[2], bd[3], bd[4], bd[5], bd[6]};
+  fin = fin && plant_inertia(bd[0], Ib, Ii);
+  const V3 f0 = load3(f), f1 = load3(f + 3), f2 = load3(f + 6), f3 = load3(f + 9);
+  V3 Fs = est_add(est_add(f0, f1), est_add(f2, f3));
+  fin = fin && fin3(f0) && fin3(f1) && fin3(f2) && fin3(f3);
+  if (pushed) {
+    const V3 Fp = load3(push + 6 * b);
+    Fs = est_add(Fs, Fp);
+    fin = fin && fin3(Fp);
+  }
+  const V3 aw = {Fs.x / bd[0], Fs.y / bd[0], Fs.z / bd[0] + g};
+  return {aw.x, aw.y, aw.z - g};
+}
+
 // mpcqp_estimate_track (GATE = false) and mpcqp_estimate_track_gated: i = 4 b + lane.  trust / height / state and each output may be
 // null.  GATE adds step 1g and the trust_out rows (lane 3's); without it `gate` and `trust_out`, the last two arguments, are not read.
 template <typename TIO, bool GATE>
@@ -126,149 +334,58 @@ mpcqp_estimate_track_kernel(const TIO* __restrict__ imu, const TIO* __restrict__
   if (i >= 4 * B) return;   // (whole quads leave: the lane moves below see all four lanes or none)
   const int64_t b = i / 4;
   const int l = (int)(i % 4), a = l < 3 ? l : 2;
-  const double nan = __builtin_nan("");
   double* const sb = state ? state + b * EST_STATE : nullptr;
   const bool fresh = !sb || sb[EST_LIVE] == 0.0;
-  double qh[4], xi[6], U[21], hl[4] = {0.0, 0.0, 0.0, 0.0};
+  double qh[4], xi[6], U[21], hl[4];
   bool mine = true;   // this lane's operands are finite
-  if (fresh) {
-    const TIO* x0 = init + 12 * b;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) mine = mine && isfinite((double)x0[c]) && isfinite((double)x0[3 + c]) && isfinite((double)x0[9 + c]);
-    plant_rotvec_to_quat((double)x0[0], (double)x0[1], (double)x0[2], qh);
-    xi[0] = (double)x0[3 + a]; xi[1] = (double)x0[9 + a];
-#pragma unroll
-    for (int c = 2; c < 6; ++c) xi[c] = 0.0;   // (the feet are set on row 0, from its rho)
-#pragma unroll
-    for (int r = 0; r < 6; ++r)
-#pragma unroll
-      for (int c = r; c < 6; ++c) U[est_ut(r, c)] = r != c ? 0.0 : (r == 0 ? par.p0p : (r == 1 ? par.p0v : par.p0f));
-  } else {
-    mine = isfinite(sb[EST_LIVE]);
-#pragma unroll
-    for (int c = 0; c < 4; ++c) { qh[c] = sb[c]; mine = mine && isfinite(qh[c]); }
-#pragma unroll
-    for (int c = 0; c < 6; ++c) { xi[c] = sb[EST_XI + 6 * a + c]; mine = mine && isfinite(xi[c]); }
-#pragma unroll
-    for (int r = 0; r < 6; ++r)
-#pragma unroll
-      for (int c = r; c < 6; ++c) { U[est_ut(r, c)] = sb[EST_P + 36 * a + 6 * r + c]; mine = mine && isfinite(U[est_ut(r, c)]); }
-  }
-  if (height) {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) { hl[j] = (double)height[4 * b + j]; mine = mine && isfinite(hl[j]); }
-  }
+  if (fresh) est_fresh(init + 12 * b, par, a, qh, xi, U, mine); else est_load(sb, a, qh, xi, U, mine);
+  est_heights(height, b, hl, mine);
   const bool hgt = height != nullptr && a == 2;
-  bool ok = true;   // the robot's flag: the same in its four lanes
+  bool ok = true;   // the robot's flag
   for (int t = 0; t < T; ++t) {
     const int64_t row = b * T + t;
-    const TIO* m = imu + 6 * row;
-    const V3 gy = load3(m), sf = load3(m + 3);
-    const double ql[3] = {(double)q[3 * (4 * row + l)], (double)q[3 * (4 * row + l) + 1], (double)q[3 * (4 * row + l) + 2]};
-    const V3 qr = load3(qd + 3 * (4 * row + l));
+    const V3 gy = load3(imu + 6 * row), sf = load3(imu + 6 * row + 3);
+    const V3 ql = load3(q + 3 * (4 * row + l)), qr = load3(qd + 3 * (4 * row + l));
     double tr[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) tr[j] = trust ? (double)trust[4 * row + j] : (contact[4 * row + j] != 0 ? 1.0 : 0.0);
-    mine = mine && fin3(gy) && fin3(sf) && fin3(qr) && isfinite(ql[0]) && isfinite(ql[1]) && isfinite(ql[2]) && isfinite(tr[0]) &&
-           isfinite(tr[1]) && isfinite(tr[2]) && isfinite(tr[3]);
-    float bad = mine ? 0.0f : 1.0f;
-    bad = bad + dpp_mov<0xB1>(bad);
-    bad = bad + dpp_mov<0x4E>(bad);
-    ok = ok && bad == 0.0f;
-    // 1. the leg's foot and its velocity relative to the CoM, world axes
+    mine = mine && fin3(gy) && fin3(sf) && fin3(qr) && fin3(ql) && isfinite(tr[0]) && isfinite(tr[1]) && isfinite(tr[2]) && isfinite(tr[3]);
+    const bool row_ok = est_quad_all(mine);
+    ok = ok && row_ok;
+    // 1, 1g, 2
     const M3 R = est_rot(qh);
-    double pf[3], J[9];
-    leg_fk_jac(geo, l, ql, pf, J);
-    const V3 pb = {pf[0], pf[1], pf[2]};
-    const V3 jq = {(J[0] * qr.x + J[1] * qr.y) + J[2] * qr.z, (J[3] * qr.x + J[4] * qr.y) + J[5] * qr.z, (J[6] * qr.x + J[7] * qr.y) + J[8] * qr.z};
-    const V3 rho = est_mv(R, pb), rhod = est_mv(R, est_add(est_cross(gy, pb), jq));
-    // ... and what this lane's axis sees of the four legs
-    const double zr[4] = {est_pick(a, quad_bcast<0>(rho.x), quad_bcast<0>(rho.y), quad_bcast<0>(rho.z)),
-                          est_pick(a, quad_bcast<1>(rho.x), quad_bcast<1>(rho.y), quad_bcast<1>(rho.z)),
-                          est_pick(a, quad_bcast<2>(rho.x), quad_bcast<2>(rho.y), quad_bcast<2>(rho.z)),
-                          est_pick(a, quad_bcast<3>(rho.x), quad_bcast<3>(rho.y), quad_bcast<3>(rho.z))};
-    const double zv[4] = {est_pick(a, quad_bcast<0>(rhod.x), quad_bcast<0>(rhod.y), quad_bcast<0>(rhod.z)),
-                          est_pick(a, quad_bcast<1>(rhod.x), quad_bcast<1>(rhod.y), quad_bcast<1>(rhod.z)),
-                          est_pick(a, quad_bcast<2>(rhod.x), quad_bcast<2>(rhod.y), quad_bcast<2>(rhod.z)),
-                          est_pick(a, quad_bcast<3>(rhod.x), quad_bcast<3>(rhod.y), quad_bcast<3>(rhod.z))};
-    if (fresh && t == 0) {
-#pragma unroll
-      for (int j = 0; j < 4; ++j) xi[2 + j] = xi[0] + zr[j];
-    }
-    // 1g. the gate: tr becomes w
-    if constexpr (GATE) est_gate<TIO>(gate, par, xi, U, zv, tr);
-    // 2. the scalar updates
-    double na = 0.0;
-    est_leg<0>(par, xi, U, zr[0], zv[0], tr[0], hgt, hl[0], na);
-    est_leg<1>(par, xi, U, zr[1], zv[1], tr[1], hgt, hl[1], na);
-    est_leg<2>(par, xi, U, zr[2], zv[2], tr[2], hgt, hl[2], na);
-    est_leg<3>(par, xi, U, zr[3], zv[3], tr[3], hgt, hl[3], na);
-    const double nis = (quad_bcast<0>(na) + quad_bcast<1>(na)) + quad_bcast<2>(na);
+    V3 rho, rhod;
+    double zr[4], zv[4];
+    est_foot(geo, l, ql, qr, R, gy, rho, rhod);
+    est_across(a, rho, zr); est_across(a, rhod, zv);
+    if (fresh && t == 0) est_first_feet(zr, xi);
+    const double nis = est_measure<TIO, GATE>(par, gate, hgt, hl, zr, zv, tr, xi, U);
     // 3. outputs: lanes 0..2 their axis, lane 3 the orientation's
     const V3 om = est_mv(R, gy);
     if (l < 3) {
-      if (est) { est[12 * row + 3 + a] = (TIO)(ok ? xi[0] : nan); est[12 * row + 9 + a] = (TIO)(ok ? xi[1] : nan); }
+      if (est) { est[12 * row + 3 + a] = est_out<TIO>(ok, xi[0]); est[12 * row + 9 + a] = est_out<TIO>(ok, xi[1]); }
       if (feet_est) {
 #pragma unroll
-        for (int j = 0; j < 4; ++j) feet_est[3 * (4 * row + j) + a] = (TIO)(ok ? xi[2 + j] : nan);
+        for (int j = 0; j < 4; ++j) feet_est[3 * (4 * row + j) + a] = est_out<TIO>(ok, xi[2 + j]);
       }
-      if (sigma) { sigma[6 * row + a] = (TIO)(ok ? sqrt(U[est_ut(0, 0)]) : nan); sigma[6 * row + 3 + a] = (TIO)(ok ? sqrt(U[est_ut(1, 1)]) : nan); }
+      if (sigma) { sigma[6 * row + a] = est_out<TIO>(ok, est_sigma(U, 0)); sigma[6 * row + 3 + a] = est_out<TIO>(ok, est_sigma(U, 1)); }
     } else {
       if (est) {
-        double th[3];
-        plant_quat_to_rotvec(qh, th);
-        store3(est + 12 * row, ok, V3{th[0], th[1], th[2]});
+        store3(est + 12 * row, ok, est_rotvec(qh));
         store3(est + 12 * row + 6, ok, om);
       }
-      if (nis_out) nis_out[row] = (TIO)(ok ? nis : nan);
+      if (nis_out) nis_out[row] = est_out<TIO>(ok, nis);
       if constexpr (GATE) {
         if (trust_out) {
 #pragma unroll
-          for (int j = 0; j < 4; ++j) trust_out[4 * row + j] = (TIO)(ok ? tr[j] : nan);
+          for (int j = 0; j < 4; ++j) trust_out[4 * row + j] = est_out<TIO>(ok, tr[j]);
         }
       }
     }
-    // 4. predict
-    const double aw = ((est_pick(a, R.r0.x, R.r1.x, R.r2.x) * sf.x + est_pick(a, R.r0.y, R.r1.y, R.r2.y) * sf.y) +
-                       est_pick(a, R.r0.z, R.r1.z, R.r2.z) * sf.z) + (a == 2 ? par.g : 0.0);
-    xi[0] = (xi[0] + par.d * xi[1]) + par.hd2 * aw;
-    xi[1] = xi[1] + par.d * aw;
-    U[est_ut(0, 0)] = (U[est_ut(0, 0)] + par.d * U[est_ut(0, 1)]) + par.d * (U[est_ut(0, 1)] + par.d * U[est_ut(1, 1)]);
-#pragma unroll
-    for (int j = 1; j < 6; ++j) U[est_ut(0, j)] = U[est_ut(0, j)] + par.d * U[est_ut(1, j)];
-    U[est_ut(0, 0)] = U[est_ut(0, 0)] + par.d * par.qp;
-    U[est_ut(1, 1)] = U[est_ut(1, 1)] + par.d * par.qv;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) U[est_ut(2 + j, 2 + j)] = U[est_ut(2 + j, 2 + j)] + par.d * (par.qf * (1.0 + (1.0 - tr[j]) * par.ks));
-    const double sn = est_norm(sf), ga = fabs(par.g);
-    const bool pull = sn > 0.0;
-    const V3 sh = {pull ? sf.x / sn : 0.0, pull ? sf.y / sn : 0.0, pull ? sf.z / sn : 0.0};
-    const double c0 = 1.0 - fabs(sn - ga) / ga;
-    const double kap = pull ? par.kappa * (c0 < 0.0 ? 0.0 : (c0 > 1.0 ? 1.0 : c0)) : 0.0;
-    const V3 cr = est_cross(sh, R.r2);
-    const V3 wh = est_mv(R, V3{gy.x + kap * cr.x, gy.y + kap * cr.y, gy.z + kap * cr.z});
-    double dq[4];
-    plant_rotvec_to_quat(par.d * wh.x, par.d * wh.y, par.d * wh.z, dq);
-    const double n0 = ((dq[0] * qh[0] - dq[1] * qh[1]) - dq[2] * qh[2]) - dq[3] * qh[3];
-    const double n1 = ((dq[0] * qh[1] + dq[1] * qh[0]) + dq[2] * qh[3]) - dq[3] * qh[2];
-    const double n2 = ((dq[0] * qh[2] - dq[1] * qh[3]) + dq[2] * qh[0]) + dq[3] * qh[1];
-    const double n3 = ((dq[0] * qh[3] + dq[1] * qh[2]) - dq[2] * qh[1]) + dq[3] * qh[0];
-    const double nq = sqrt(((n0 * n0 + n1 * n1) + n2 * n2) + n3 * n3);
-    qh[0] = n0 / nq; qh[1] = n1 / nq; qh[2] = n2 / nq; qh[3] = n3 / nq;
+    // 4
+    est_predict(par, a, R, gy, sf, tr, qh, xi, U);
   }
-  if (!sb) return;
-  if (l < 3) {
-#pragma unroll
-    for (int c = 0; c < 6; ++c) sb[EST_XI + 6 * a + c] = ok ? xi[c] : nan;
-#pragma unroll
-    for (int r = 0; r < 6; ++r)
-#pragma unroll
-      for (int c = 0; c < 6; ++c) sb[EST_P + 36 * a + 6 * r + c] = ok ? U[est_sym(r, c)] : nan;
-  } else {
-#pragma unroll
-    for (int c = 0; c < 4; ++c) sb[c] = ok ? qh[c] : nan;
-    sb[EST_LIVE] = ok ? 1.0 : nan;
-  }
+  if (sb) est_store(sb, l, a, ok, qh, xi, U);
 }
 
 // mpcqp_imu_log: one lane per row of the log.  base_acc / body / bias / noise may be null.
@@ -281,40 +398,19 @@ mpcqp_imu_log_kernel(const TIO* __restrict__ actual, const TIO* __restrict__ for
   const int64_t row = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (row >= rows) return;
   const int64_t b = row / T;
-  const TIO* x = actual + 12 * row;
-  const V3 th = load3(x), om = load3(x + 6);
-  double qt[4];
-  plant_rotvec_to_quat(th.x, th.y, th.z, qt);
-  const M3 R = est_rot(qt);
+  const V3 th = load3(actual + 12 * row), om = load3(actual + 12 * row + 6);
+  const M3 R = est_rotvec_rot(th);
   bool fin = fin3(th) && fin3(om);
-  V3 aw;
+  V3 sp;
   if (base_acc) {
-    const TIO* s = base_acc + 6 * row;
-    aw = load3(s + 3);
-    fin = fin && fin3(load3(s)) && fin3(aw);
-  } else {   // the unpushed plant's right-hand side: the sum across the four legs in mpcqp_leg_effort's order, (0 + 1) + (2 + 3)
-    const TIO* f = forces + 12 * row;
-    double bd[7], Ii[6];
-    plant_body_row(body, model, b, bd);
-    const double Ib[6] = {bd[1], bd[2], bd[3], bd[4], bd[5], bd[6]};
-    fin = fin && plant_inertia(bd[0], Ib, Ii);
-    const V3 f0 = load3(f), f1 = load3(f + 3), f2 = load3(f + 6), f3 = load3(f + 9);
-    const V3 Fs = est_add(est_add(f0, f1), est_add(f2, f3));
-    fin = fin && fin3(f0) && fin3(f1) && fin3(f2) && fin3(f3);
-    aw = {Fs.x / bd[0], Fs.y / bd[0], Fs.z / bd[0] + g};
+    const V3 al = load3(base_acc + 6 * row), aw = load3(base_acc + 6 * row + 3);
+    fin = fin && fin3(al) && fin3(aw);
+    sp = {aw.x, aw.y, aw.z - g};
+  } else {   // the unpushed plant's right-hand side
+    sp = est_specific_force(forces + 12 * row, false, (const TIO*)nullptr, body, model, b, g, fin);
   }
-  const V3 sp = {aw.x, aw.y, aw.z - g};
-  V3 gyro = est_mtv(R, om), acc = est_mtv(R, sp);
-  if (bias) {
-    const V3 bg = load3(bias + 6 * b), ba = load3(bias + 6 * b + 3);
-    gyro = est_add(gyro, bg); acc = est_add(acc, ba);
-    fin = fin && fin3(bg) && fin3(ba);
-  }
-  if (noise) {
-    const V3 ng = load3(noise + 6 * row), na = load3(noise + 6 * row + 3);
-    gyro = est_add(gyro, ng); acc = est_add(acc, na);
-    fin = fin && fin3(ng) && fin3(na);
-  }
+  V3 gyro, acc;
+  est_sense(R, om, sp, bias, b, noise, row, fin, gyro, acc);
   store3(imu + 6 * row, fin, gyro);
   store3(imu + 6 * row + 3, fin, acc);
 }

@@ -24,8 +24,9 @@
 //   mpcqp_actuators.h    per-robot actuator rows: the conversion of the caller's table and the torque-speed envelope the leg kernels share
 //   mpcqp_slip.h         stance feet that slide: the stance drive's rule with slip kinematics, and the foot move of its roll-out
 //   mpcqp_estimate.h     the torso state from an IMU and leg kinematics: the IMU rows of a log and the filter over them, without and
-//                        with the per-leg trust gate
-//   mpcqp_observe.h      sensors and that filter inside the slip roll-out's tick loop, without and with the gate
+//                        with the per-leg trust gate; the filter's row and the sensor rows as helpers, written once
+//   mpcqp_observe.h      sensors and that filter inside the slip roll-out's tick loop, without and with the gate: the encoder row and
+//                        two kernels that call mpcqp_estimate.h's helpers around a tick
 // DESIGN.md has the derivations.
 
 #include "mpcqp_wrench.h"

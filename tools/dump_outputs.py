@@ -5,7 +5,8 @@ the stage-wise engine at N = 60 and, by MPCQP_FLAG_STAGE_KERNEL, at N = 10 (MIXE
 roll-outs on the model and on the plant (T = 50, B = 1024, cold and warm, with the malformed plan rows of tests/test_rollout.py),
 planner + swing trajectories, plant step, leg Jacobians and torque map, and the newer entry points (phase gaits, joints, leg dynamics,
 leg simulation, leg roll-outs, score; with and without the model and actuator tables; at the tests' small shapes and at a ragged B = 333:
-the last section).  The stance rule's calls are in tools/stance_rule_compare.py.  One process per library build: copy the wanted build over
+the section before the last), and the state estimator (imu_log, estimate_track and rollout_observe with their gated forms, every output and
+the final est_state: the last section).  The stance rule's calls are in tools/stance_rule_compare.py.  One process per library build: copy the wanted build over
 csrc/libmpcqp.so before starting each.
 usage: dump_outputs.py OUT.npz            (needs a GPU)
        dump_outputs.py --compare A.npz B.npz"""
@@ -222,5 +223,62 @@ for io in ("f32", "f64"):
         newer(f"new_{io}_{name}", io, tiled(pb, RAGGED), tiled(pr, RAGGED), 4, tiled(rows, RAGGED) if tables else None, tiled(acts, RAGGED),
               tiled(q, RAGGED), tiled(ops, RAGGED), tiled(slog, RAGGED))
     print("newer entry points", io, "done", flush=True)
+
+# ---- the state estimator: imu_log, estimate_track and rollout_observe with their gated forms, at the shapes of their tests.
+#      imu_log: the real case (16 x 25) and every synthetic edge of tests/estimate_cases.py with the edge's own optional operands, and on one
+#      edge every combination of base_acc, bias and noise given or not.  estimate_track: the same cases as they come; on the real case and
+#      on one edge with and without height, trust and state, in two pieces (13 + 12 rows) through the state, and each of these ungated and
+#      gated (tests/gate_cases.py's thresholds); the real case tiled and cut to B = 333.  rollout_observe: the 16 x 25 batch of
+#      tests/test_gpu_rollout_observe.py on the ice with its sensor draws, both feeds, with and without the gate and the height rows.
+import drive_cases as dc, estimate_cases as ec, gate_cases as gc
+import test_gpu_rollout_observe as ro
+
+
+def est_track(tag, sol, ops, state=True, pieces=False, gate=None):
+    tdt = sol.tdtype
+    d = {k: (None if v is None else dev(v, torch.uint8 if k == "contact_log" else tdt)) for k, v in ops.items()}
+    st = torch.zeros((len(ops["imu"]), 131), dtype=torch.float64, device="cuda") if state else None
+    T = ops["imu"].shape[1]
+    for name, rows in (("a", slice(0, 13)), ("b", slice(13, T))) if pieces else (("", slice(None)),):
+        part = {k: (v[:, rows].contiguous() if v is not None and k in ("imu", "q", "qd", "contact_log", "trust") else v) for k, v in d.items()}
+        puts(tag + name, sol.estimate_track(part["imu"], part["q"], part["qd"], part["contact_log"], part["init"], trust=part["trust"],
+                                            height=part["height"], state=st, gate=gate))
+    put(tag + "_state", st)
+
+
+for io in ("f32", "f64"):
+    tdt = torch.float32 if io == "f32" else torch.float64
+    sol = zero_filled(mpcqp.MPCBatch(N=10, delta=ec.DELTA, io_dtype=io))
+    cases = [("real", ec.as_io(ec.real_case(), io))] + [("edge_%d_%d" % k[:2], ec.as_io(ec.edge_case(*k), io)) for k in ec.edge_cases()]
+    for name, case in cases:
+        logs = {k: dev(case[k], tdt) for k in ("actual", "forces", "feet_log")}
+        put(f"est_{io}_{name}_imu", sol.imu_log(logs, **{k: (None if v is None else dev(v, tdt)) for k, v in ec.imu_operands(case).items()}))
+        est_track(f"est_{io}_{name}_track", sol, ec.operands(case))
+    edge = ec.as_io(ec.edge_case(65, 25, True), io)
+    logs = {k: dev(edge[k], tdt) for k in ("actual", "forces", "feet_log")}
+    for bits in range(8):
+        kw = {k: (dev(edge[k], tdt) if bits >> i & 1 else None) for i, k in enumerate(("base_acc", "bias", "noise"))}
+        put(f"est_{io}_imu_operands{bits}", sol.imu_log(logs, body=dev(edge["body"], tdt), **kw))
+    for name, case in (("real", dict(cases[0][1], trust=edge["trust"][:16], height=edge["height"][:16])), ("edge", edge)):
+        for gname, gate in (("", None), ("_gated", gc.GATE)):
+            for bits in range(8):
+                ops = dict(ec.operands(case), **{k: (case[k] if bits >> i & 1 else None) for i, k in enumerate(("height", "trust"))})
+                est_track(f"est_{io}_{name}{gname}_variant{bits}", sol, ops, state=bool(bits & 4), gate=gate)
+            est_track(f"est_{io}_{name}{gname}_pieces", sol, ec.operands(case), pieces=True, gate=gate)
+    ragged = tiled(dict(cases[0][1], trust=edge["trust"][:16], height=edge["height"][:16]), RAGGED)
+    put(f"est_{io}_ragged_imu", sol.imu_log({k: dev(ragged[k], tdt) for k in ("actual", "forces", "feet_log")}, body=dev(ragged["body"], tdt)))
+    for gname, gate in (("", None), ("_gated", gc.GATE)):
+        est_track(f"est_{io}_ragged{gname}", sol, ec.operands(ragged), gate=gate)
+    ops = ro._Ops(io)
+    zero_filled(ops.sol)
+    for feed in ("truth", "estimate"):
+        for gname, gate in (("", None), ("_gated", gc.GATE)):
+            for hname, height in (("", None), ("_height", ops.height)):
+                st = ops.state()
+                tag = f"observe_{io}_{feed}{gname}{hname}"
+                puts(tag, ops.observe(st, ro.ROLL_T, feed, inertia=dc.weak_row(0.5), height=height, gate=gate))
+                puts(tag + "_end", st)
+    torch.cuda.synchronize()
+    print("estimator", io, "done", flush=True)
 np.savez(sys.argv[1], **OUT)
 print("dumped", len(OUT), "arrays", flush=True)
