@@ -13,7 +13,8 @@
  * allocated.  All arithmetic is fp64; the filter's own arithmetic (everything below but the leg's forward map) is not contracted;
  * float32 outputs are rounded once.  Return codes and mpcqp_last_error() as in mpcqp.h.
  *
- * Not built: gyro and accelerometer bias states (a given bias is read as it is), contact detection from forces (trust is given;
+ * Not built: accelerometer bias states (a given bias is read as it is; a gyro-bias state and an orientation steered by the velocity
+ * update are mpcqp_attitude.h), contact detection from forces (trust is given;
  * gating it on the legs' velocity innovations is mpcqp_gate.h), an IMU off the CoM, telling the MPC the estimate's covariance.  (The
  * estimate inside a roll-out's tick loop is mpcqp_observe.h.)
  */

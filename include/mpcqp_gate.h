@@ -31,6 +31,7 @@
  *
  * Not built: hysteresis (a leg's gate has no memory: it opens again on the first row whose innovation is small); a force cue (the
  * commanded or applied force against the friction cone); a gate on z; telling the MPC (the solve still plans with the clock's contact).
+ * (What the gated updates do to the orientation -- the velocity-aided attitude and gyro-bias states -- is mpcqp_attitude.h.)
  */
 #ifndef MPCQP_GATE_H_
 #define MPCQP_GATE_H_

@@ -51,7 +51,8 @@
  *
  * Not built: the foothold rule at touchdown and the swing-leg controller still read the true state (they live inside the advance and
  * the legs step, which are mpcqp_rollout_slip's); contact detection from forces (trust is the clock; gating it on the legs' velocity
- * innovations is mpcqp_rollout_observe_gated, mpcqp_gate.h); bias states; an IMU off the CoM; a host checker with model tables.
+ * innovations is mpcqp_rollout_observe_gated, mpcqp_gate.h); accelerometer bias states (the gyro-bias state is
+ * mpcqp_rollout_observe_aided, mpcqp_attitude.h); an IMU off the CoM; a host checker with model tables.
  */
 #ifndef MPCQP_OBSERVE_H_
 #define MPCQP_OBSERVE_H_

@@ -94,6 +94,12 @@ class MpcQpTrustGate(ctypes.Structure):
     FIELDS = tuple(name for name, _ in _fields_[1:])
 
 
+class MpcQpAttitude(ctypes.Structure):
+    """Mirror of struct MpcQpAttitude (include/mpcqp_attitude.h): the gains of the estimator's velocity-aided attitude rule."""
+    _fields_ = [("size", c_uint32), ("k_s", c_double), ("k_v", c_double), ("k_b", c_double), ("b_max", c_double)]
+    FIELDS = tuple(name for name, _ in _fields_[1:])
+
+
 class MpcQpConfig(ctypes.Structure):
     """Mirror of ``struct MpcQpConfig`` (include/mpcqp.h)."""
     _fields_ = [
@@ -127,6 +133,7 @@ _CFG, _GEO, _INR = ctypes.POINTER(MpcQpConfig), ctypes.POINTER(MpcQpLegGeometry)
 _RULE = ctypes.POINTER(MpcQpScoreRule)
 _EST = ctypes.POINTER(MpcQpEstimator)
 _GATE = ctypes.POINTER(MpcQpTrustGate)
+_ATT = ctypes.POINTER(MpcQpAttitude)
 CORE_HEADER = "mpcqp.h"
 ABI = {
     "mpcqp.h": (
@@ -227,6 +234,19 @@ GATE_ABI = {
     ),
 }
 GATE_SYMBOLS = tuple(row[0] for row in GATE_ABI[GATE_HEADER])
+# include/mpcqp_attitude.h, the velocity-aided attitude and gyro-bias states, likewise: `has_attitude`.  Each aided call is its gated
+# row with the flags, the gains, att_state and the bias output in front of the stream.
+ATTITUDE_HEADER = "mpcqp_attitude.h"
+ATTITUDE_ABI = {
+    ATTITUDE_HEADER: (  # the aided rule of the estimator, over a log and inside the roll-out
+        ("mpcqp_default_attitude", c_int, (_ATT,)),
+        ("mpcqp_estimate_track_aided", c_int, GATE_ABI[GATE_HEADER][1][2][:-1] + (_I32, _ATT, _P, _P, _P)),
+        ("mpcqp_rollout_observe_aided", c_int, GATE_ABI[GATE_HEADER][2][2][:-1] + (_I32, _ATT, _P, _P, _P)),
+    ),
+}
+ATTITUDE_SYMBOLS = tuple(row[0] for row in ATTITUDE_ABI[ATTITUDE_HEADER])
+ATT_STATE = 8     # include/mpcqp_attitude.h, MPCQP_ATT_STATE: doubles per robot of the attitude state
+AIDED_GATE = 1    # include/mpcqp_attitude.h, MPCQP_AIDED_GATE
 # The swing-leg plant of include/mpcqp_joints.h came after the rest of that header: a product library built before it still has the
 # header's other calls (`has_joints`) and is told apart by `has_legsim`.
 LEGSIM_SYMBOLS = ("mpcqp_leg_accel", "mpcqp_swing_track")
@@ -248,8 +268,8 @@ DRIVE_SLIDING = 128   # include/mpcqp_slip.h, MPCQP_DRIVE_SLIDING: the stance fo
 
 class Library:
     """A loaded shared object exporting the mpcqp C-ABI.  `has_plan`, `has_sim`, `has_model`, `has_joints`, `has_actuators`, `has_slip`,
-    `has_estimate`, `has_observe` and `has_gate` say whether it exports all of include/mpcqp_plan.h, mpcqp_sim.h, mpcqp_model.h,
-    mpcqp_joints.h, mpcqp_actuators.h, mpcqp_slip.h, mpcqp_estimate.h, mpcqp_observe.h and mpcqp_gate.h (of mpcqp_joints.h: all but LEGSIM_SYMBOLS, which `has_legsim`
+    `has_estimate`, `has_observe`, `has_gate` and `has_attitude` say whether it exports all of include/mpcqp_plan.h, mpcqp_sim.h, mpcqp_model.h,
+    mpcqp_joints.h, mpcqp_actuators.h, mpcqp_slip.h, mpcqp_estimate.h, mpcqp_observe.h, mpcqp_gate.h and mpcqp_attitude.h (of mpcqp_joints.h: all but LEGSIM_SYMBOLS, which `has_legsim`
     answers for; of mpcqp_sim.h: all but LEGROLL_SYMBOLS, SCORE_SYMBOLS and DRIVE_SYMBOLS, `has_legroll`, `has_score` and `has_drive`).  An
     extension header's calls are bound only when the library
     has them all; `partial=True` binds whichever it has (an older build of the product library, in a comparison tool)."""
@@ -264,7 +284,7 @@ class Library:
         self.has_legroll = all(hasattr(self.lib, name) for name in LEGROLL_SYMBOLS)
         self.has_score = all(hasattr(self.lib, name) for name in SCORE_SYMBOLS)
         self.has_drive = all(hasattr(self.lib, name) for name in DRIVE_SYMBOLS)
-        for header, rows in {**ABI, **ACTUATORS_ABI, **SLIP_ABI, **ESTIMATE_ABI, **OBSERVE_ABI, **GATE_ABI}.items():
+        for header, rows in {**ABI, **ACTUATORS_ABI, **SLIP_ABI, **ESTIMATE_ABI, **OBSERVE_ABI, **GATE_ABI, **ATTITUDE_ABI}.items():
             have = header == CORE_HEADER or all(hasattr(self.lib, row[0]) for row in rows if row[0] not in _GATED)
             if header != CORE_HEADER:
                 setattr(self, "has_" + header[len("mpcqp_"):-len(".h")], have)
@@ -310,6 +330,17 @@ class Library:
         rc = fn(ctypes.byref(row))
         if rc != 0:
             raise MpcQpError(f"mpcqp_default_trust_gate failed: {rc}")
+        return row
+
+    def default_attitude(self) -> "MpcQpAttitude":
+        """The aided attitude rule's default gains (include/mpcqp_attitude.h, mpcqp_default_attitude; product library only)."""
+        fn, header, _ = self.calls["mpcqp_default_attitude"]
+        if fn is None:
+            raise MpcQpError(f"mpcqp_default_attitude: {self.path} does not export include/{header} (product library only)")
+        row = MpcQpAttitude()
+        rc = fn(ctypes.byref(row))
+        if rc != 0:
+            raise MpcQpError(f"mpcqp_default_attitude failed: {rc}")
         return row
 
     def default_config(self, **overrides) -> MpcQpConfig:
@@ -503,6 +534,21 @@ class Engine:
                    feed, est_state, est_init, height, bias, noise, enc_noise, estimator, imu_log, q_enc_log, qd_enc_log, est_log, feet_est_log,
                    sigma_log, nis_log, gate, trust_log, stream)
 
+    def rollout_observe_aided_ptr(self, B, T, x, ref, feet, legs, gait, stand, gain, tick, mu, body, push, push_ticks, substeps, step_height,
+                                  gains, leg_substeps, land, drive, ground, foot_mass, slip, actual, desired, forces, feet_log, contact_log,
+                                  solved, swing_log, q_log, qd_log, tau_log, foot_log, err_log, flag_log, miss_log, cmd_log, slip_log, disp_log,
+                                  imu_log, q_enc_log, qd_enc_log, est_log, feet_est_log, sigma_log, nis_log, trust_log, bias_log, feed,
+                                  est_state, est_init=0, height=0, bias=0, noise=0, enc_noise=0, estimator=None, gate=None, flags=0,
+                                  attitude=None, att_state=0, geometry=None, inertia=None, stream=0):
+        """`rollout_observe_gated_ptr` with the aided attitude rule (include/mpcqp_attitude.h, mpcqp_rollout_observe_aided): bias_log
+        follows trust_log among the logs; `flags` (AIDED_GATE: run the gate), `attitude` (an MpcQpAttitude or None = the defaults) and
+        att_state follow `gate`."""
+        self._call("mpcqp_rollout_observe_aided", B, T, x, ref, feet, legs, gait, stand, gain, tick, mu, body, push, push_ticks, substeps,
+                   step_height, gains, leg_substeps, geometry, inertia, land, drive, ground, foot_mass, slip, actual, desired, forces, feet_log,
+                   contact_log, solved, swing_log, q_log, qd_log, tau_log, foot_log, err_log, flag_log, miss_log, cmd_log, slip_log, disp_log,
+                   feed, est_state, est_init, height, bias, noise, enc_noise, estimator, imu_log, q_enc_log, qd_enc_log, est_log, feet_est_log,
+                   sigma_log, nis_log, gate, trust_log, flags, attitude, att_state, bias_log, stream)
+
     # (`estimator` is an MpcQpEstimator or None = the defaults)
     def imu_log_ptr(self, B, T, actual, forces, feet, base_acc, body, bias, noise, imu, estimator=None, stream=0):
         """What an IMU at the CoM reads on every row of a log (include/mpcqp_estimate.h, mpcqp_imu_log)."""
@@ -520,6 +566,13 @@ class Engine:
         MpcQpTrustGate or None = the defaults."""
         self._call("mpcqp_estimate_track_gated", B, T, imu, q, qd, contact_log, trust, height, init, estimator, geometry, state, est, feet_est,
                    sigma, nis, gate, trust_out, stream)
+
+    def estimate_track_aided_ptr(self, B, T, imu, q, qd, contact_log, trust, height, init, state, est, feet_est, sigma, nis, trust_out,
+                                 bias_log, estimator=None, gate=None, flags=0, attitude=None, att_state=0, geometry=None, stream=0):
+        """`estimate_track_gated_ptr` with the aided attitude rule (include/mpcqp_attitude.h, mpcqp_estimate_track_aided): `flags`
+        (AIDED_GATE: run the gate), `attitude` an MpcQpAttitude or None = the defaults, att_state the address of float64 [B,8] or 0."""
+        self._call("mpcqp_estimate_track_aided", B, T, imu, q, qd, contact_log, trust, height, init, estimator, geometry, state, est, feet_est,
+                   sigma, nis, gate, trust_out, flags, attitude, att_state, bias_log, stream)
 
     def phase_swing_ptr(self, B, T, actual, desired, feet_log, gait, tick0, stand, gain, step_height, swing, feet_des=0, stream=0):
         """The swing-foot trajectories of a roll-out on a gait clock, from its logs (include/mpcqp_plan.h, mpcqp_phase_swing)."""

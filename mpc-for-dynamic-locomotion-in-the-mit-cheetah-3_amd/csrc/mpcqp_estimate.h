@@ -1,7 +1,9 @@
 // mpcqp_estimate.h -- the torso state estimated from an IMU and leg kinematics (the C-ABI is include/mpcqp_estimate.h, which has the
 // rule; the entry points live in mpcqp_kernels.hip): mpcqp_imu_log (what an IMU at the CoM reads on every row of a log) and
 // mpcqp_estimate_track (orientation filter plus three 6-state Kalman filters over the rows) and, as a compile-time variant of its
-// kernel, mpcqp_estimate_track_gated (include/mpcqp_gate.h: the trust of each leg gated on its velocity innovation before the updates).
+// kernel, mpcqp_estimate_track_gated (include/mpcqp_gate.h: the trust of each leg gated on its velocity innovation before the updates),
+// and as a second one mpcqp_estimate_track_aided (include/mpcqp_attitude.h: the velocity update's correction fed back into the
+// orientation as a PI term whose integral is a gyro-bias state).
 //
 // The filter is serial in T and parallel in B.  Four lanes per robot, the mapping of the leg kernels: lane l does leg l's forward map,
 // then lanes 0..2 own one axis each (xi[a] and the upper triangle of P[a], 6 + 21 doubles in registers) and take the four legs' rho,
@@ -12,6 +14,8 @@
 // Poison is a per-robot flag, combined over the quad once per row; outputs and the returned state are selects on it.
 // The gate (est_gate) keeps the mapping: lanes 0 and 1 form the legs' normalised innovations along x and y from their own xi and P, two
 // quad broadcasts per leg sum them in every lane, and every lane then holds the four gated trusts; lane 3 stores them.
+// The aided rule (est_aid_*) keeps it too: every lane carries b^ (it needs g' = gyro - b^ for its leg), lanes 0 and 1 hold dv along x and
+// y, two quad broadcasts give both to every lane, and every lane forms e_b and the orientation step; lane 3 stores b^, e_b and bias_log.
 //
 // One row of the filter is written once, as the helpers below, for this file's kernel over a log and for the two kernels of
 // mpcqp_observe.h, which run the same row around a tick of the slip roll-out; that the three compute the same bits rests on that:
@@ -20,10 +24,11 @@
 //   steps 1g-2 est_first_feet on a fresh start's first row; est_measure: est_gate, the four legs' scalar updates (est_leg, est_update), nis
 //   step 3     est_out, est_sigma, est_rotvec: the values; each kernel stores them where it keeps them
 //   step 4     est_predict
+//   aided      est_aid_load, est_aid_sense (g'), est_aid_error (e_b from dv), est_aid_orient (inside est_predict: w^ and b^), est_aid_store
 //   sensors    est_rotvec_rot, est_sense (R^T v + bias + noise), est_specific_force (applied forces over the body row)
 #pragma once
 #include "mpcqp_legsim.h"
-#include "../../include/mpcqp_estimate.h"
+#include "../../include/mpcqp_attitude.h"
 
 namespace {
 
@@ -119,6 +124,48 @@ __device__ __forceinline__ void est_gate(const EstGate& gate, const EstPar& par,
     const double g = dl <= gate.lo ? 1.0 : (dl < gate.hi ? (gate.hi - dl) / gate.span : 0.0);
     tr[j] = (double)(TIO)(tr[j] * g);
   }
+}
+
+// MpcQpAttitude as the kernels take it (checked on the host, attitude_row in mpcqp_kernels.hip): k_s, k_v, k_b delta, b_max, delta |g|.
+struct EstAid { double ks, kv, kbd, bmax, dg; };
+constexpr int ATT_STATE = MPCQP_ATT_STATE;
+
+// The aided rule (include/mpcqp_attitude.h).  b^ of a live robot from its att_state row (null or fresh: zero), folded into the lane's
+// finite flag.
+__device__ __forceinline__ V3 est_aid_load(const double* ab, const bool fresh, bool& fin) {
+  if (!ab || fresh) return {0.0, 0.0, 0.0};
+  const V3 bh = {ab[0], ab[1], ab[2]};
+  fin = fin && fin3(bh);
+  return bh;
+}
+// g' = gyro - b^
+__device__ __forceinline__ V3 est_aid_sense(const V3 gy, const V3 bh) {
+#pragma clang fp contract(off)
+  return {gy.x - bh.x, gy.y - bh.y, gy.z - bh.z};
+}
+// e_b of the row from what step 2 did to this lane's velocity entry: lanes 0 and 1 own x and y, every lane gets both.
+__device__ __forceinline__ V3 est_aid_error(const EstAid& aid, const M3& R, const double vpred, const double vpost) {
+#pragma clang fp contract(off)
+  const double dv = vpost - vpred;
+  const double dx = quad_bcast<0>(dv), dy = quad_bcast<1>(dv);
+  return est_mtv(R, V3{(-dy) / aid.dg, dx / aid.dg, 0.0});
+}
+// The body rate the orientation step integrates, before R: (g' + (k_s kap) (s^ x u)) + k_v e_b; and b^'s step, clamped.
+__device__ __forceinline__ V3 est_aid_orient(const EstAid& aid, const V3 gp, const double kap, const V3 cr, const V3 eb, V3& bh) {
+#pragma clang fp contract(off)
+  const double kk = aid.ks * kap;
+  const V3 w = {(gp.x + kk * cr.x) + aid.kv * eb.x, (gp.y + kk * cr.y) + aid.kv * eb.y, (gp.z + kk * cr.z) + aid.kv * eb.z};
+  const double nx = bh.x - aid.kbd * eb.x, ny = bh.y - aid.kbd * eb.y, nz = bh.z - aid.kbd * eb.z;
+  bh = {nx < -aid.bmax ? -aid.bmax : (nx > aid.bmax ? aid.bmax : nx), ny < -aid.bmax ? -aid.bmax : (ny > aid.bmax ? aid.bmax : ny),
+        nz < -aid.bmax ? -aid.bmax : (nz > aid.bmax ? aid.bmax : nz)};
+  return w;
+}
+// One lane stores the row: b^, e_b and the reserved pair; a poisoned robot's row is NaN.
+__device__ __forceinline__ void est_aid_store(double* ab, const bool ok, const V3 bh, const V3 eb) {
+  const double nan = __builtin_nan("");
+  ab[0] = ok ? bh.x : nan; ab[1] = ok ? bh.y : nan; ab[2] = ok ? bh.z : nan;
+  ab[3] = ok ? eb.x : nan; ab[4] = ok ? eb.y : nan; ab[5] = ok ? eb.z : nan;
+  ab[6] = ok ? 0.0 : nan; ab[7] = ok ? 0.0 : nan;
 }
 
 // ---- the filter's state of lane axis a: qh, xi[a] and the upper triangle of P[a].  What is read folds into the lane's finite flag.
@@ -240,9 +287,12 @@ __device__ __forceinline__ V3 est_rotvec(const double (&qh)[4]) {
 }
 
 // Step 4, the predict of lane axis a from the row's gyro, accelerometer and (gated) trust; R is est_rot(qh).  Leaves the normalised
-// quaternion in qh.
+// quaternion in qh.  AIDED: gy is g', the rate gets est_aid_orient's terms from the row's e_b, and bh is stepped; without it `aid`,
+// `eb` and `bh`, the last three arguments, are not read.
+template <bool AIDED = false>
 __device__ __forceinline__ void est_predict(const EstPar& par, const int a, const M3& R, const V3 gy, const V3 sf, const double (&tr)[4],
-                                            double (&qh)[4], double (&xi)[6], double (&U)[21]) {
+                                            double (&qh)[4], double (&xi)[6], double (&U)[21], const EstAid& aid = EstAid{},
+                                            const V3 eb = V3{0.0, 0.0, 0.0}, V3* bh = nullptr) {
 #pragma clang fp contract(off)
   const double aw = ((est_pick(a, R.r0.x, R.r1.x, R.r2.x) * sf.x + est_pick(a, R.r0.y, R.r1.y, R.r2.y) * sf.y) +
                      est_pick(a, R.r0.z, R.r1.z, R.r2.z) * sf.z) + (a == 2 ? par.g : 0.0);
@@ -261,7 +311,10 @@ __device__ __forceinline__ void est_predict(const EstPar& par, const int a, cons
   const double c0 = 1.0 - fabs(sn - ga) / ga;
   const double kap = pull ? par.kappa * (c0 < 0.0 ? 0.0 : (c0 > 1.0 ? 1.0 : c0)) : 0.0;
   const V3 cr = est_cross(sh, R.r2);
-  const V3 wh = est_mv(R, V3{gy.x + kap * cr.x, gy.y + kap * cr.y, gy.z + kap * cr.z});
+  V3 wb;
+  if constexpr (AIDED) wb = est_aid_orient(aid, gy, kap, cr, eb, *bh);
+  else wb = V3{gy.x + kap * cr.x, gy.y + kap * cr.y, gy.z + kap * cr.z};
+  const V3 wh = est_mv(R, wb);
   double dq[4];
   plant_rotvec_to_quat(par.d * wh.x, par.d * wh.y, par.d * wh.z, dq);
   const double n0 = ((dq[0] * qh[0] - dq[1] * qh[1]) - dq[2] * qh[2]) - dq[3] * qh[3];
@@ -321,14 +374,17 @@ __device__ __forceinline__ V3 est_specific_force(const TIO* __restrict__ f, cons
 }
 
 // mpcqp_estimate_track (GATE = false) and mpcqp_estimate_track_gated: i = 4 b + lane.  trust / height / state and each output may be
-// null.  GATE adds step 1g and the trust_out rows (lane 3's); without it `gate` and `trust_out`, the last two arguments, are not read.
-template <typename TIO, bool GATE>
+// null.  GATE adds step 1g and the trust_out rows (lane 3's); without it `gate` and `trust_out` are not read.  AIDED
+// (mpcqp_estimate_track_aided) adds the rule of include/mpcqp_attitude.h, writes trust_out with or without GATE, and reads the last
+// three arguments: the gains, att_state (may be null) and bias_log (may be null).
+template <typename TIO, bool GATE, bool AIDED = false>
 __global__ void __launch_bounds__(256)
 mpcqp_estimate_track_kernel(const TIO* __restrict__ imu, const TIO* __restrict__ q, const TIO* __restrict__ qd,
                             const uint8_t* __restrict__ contact, const TIO* __restrict__ trust, const TIO* __restrict__ height,
                             const TIO* __restrict__ init, const EstPar par, const LegGeoDev geo, double* state, TIO* __restrict__ est,
                             TIO* __restrict__ feet_est, TIO* __restrict__ sigma, TIO* __restrict__ nis_out, const int64_t B, const int T,
-                            const EstGate gate, TIO* __restrict__ trust_out) {
+                            const EstGate gate, TIO* __restrict__ trust_out, const EstAid aid = EstAid{}, double* att = nullptr,
+                            TIO* __restrict__ bias_log = nullptr) {
 #pragma clang fp contract(off)
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= 4 * B) return;   // (whole quads leave: the lane moves below see all four lanes or none)
@@ -340,6 +396,12 @@ mpcqp_estimate_track_kernel(const TIO* __restrict__ imu, const TIO* __restrict__
   bool mine = true;   // this lane's operands are finite
   if (fresh) est_fresh(init + 12 * b, par, a, qh, xi, U, mine); else est_load(sb, a, qh, xi, U, mine);
   est_heights(height, b, hl, mine);
+  double* ab = nullptr;
+  V3 bh = {0.0, 0.0, 0.0}, eb = {0.0, 0.0, 0.0};
+  if constexpr (AIDED) {
+    ab = att ? att + b * ATT_STATE : nullptr;
+    bh = est_aid_load(ab, fresh, mine);
+  }
   const bool hgt = height != nullptr && a == 2;
   bool ok = true;   // the robot's flag
   for (int t = 0; t < T; ++t) {
@@ -354,14 +416,17 @@ mpcqp_estimate_track_kernel(const TIO* __restrict__ imu, const TIO* __restrict__
     ok = ok && row_ok;
     // 1, 1g, 2
     const M3 R = est_rot(qh);
-    V3 rho, rhod;
+    V3 rho, rhod, gp = gy;
     double zr[4], zv[4];
-    est_foot(geo, l, ql, qr, R, gy, rho, rhod);
+    if constexpr (AIDED) gp = est_aid_sense(gy, bh);
+    est_foot(geo, l, ql, qr, R, gp, rho, rhod);
     est_across(a, rho, zr); est_across(a, rhod, zv);
     if (fresh && t == 0) est_first_feet(zr, xi);
+    const double vpred = xi[1];
     const double nis = est_measure<TIO, GATE>(par, gate, hgt, hl, zr, zv, tr, xi, U);
+    if constexpr (AIDED) eb = est_aid_error(aid, R, vpred, xi[1]);
     // 3. outputs: lanes 0..2 their axis, lane 3 the orientation's
-    const V3 om = est_mv(R, gy);
+    const V3 om = est_mv(R, gp);
     if (l < 3) {
       if (est) { est[12 * row + 3 + a] = est_out<TIO>(ok, xi[0]); est[12 * row + 9 + a] = est_out<TIO>(ok, xi[1]); }
       if (feet_est) {
@@ -375,17 +440,24 @@ mpcqp_estimate_track_kernel(const TIO* __restrict__ imu, const TIO* __restrict__
         store3(est + 12 * row + 6, ok, om);
       }
       if (nis_out) nis_out[row] = est_out<TIO>(ok, nis);
-      if constexpr (GATE) {
+      if constexpr (GATE || AIDED) {
         if (trust_out) {
 #pragma unroll
           for (int j = 0; j < 4; ++j) trust_out[4 * row + j] = est_out<TIO>(ok, tr[j]);
         }
       }
+      if constexpr (AIDED) {
+        if (bias_log) store3(bias_log + 3 * row, ok, bh);
+      }
     }
     // 4
-    est_predict(par, a, R, gy, sf, tr, qh, xi, U);
+    if constexpr (AIDED) est_predict<true>(par, a, R, gp, sf, tr, qh, xi, U, aid, eb, &bh);
+    else est_predict(par, a, R, gy, sf, tr, qh, xi, U);
   }
   if (sb) est_store(sb, l, a, ok, qh, xi, U);
+  if constexpr (AIDED) {
+    if (ab && l == 3) est_aid_store(ab, ok, bh, eb);
+  }
 }
 
 // mpcqp_imu_log: one lane per row of the log.  base_acc / body / bias / noise may be null.

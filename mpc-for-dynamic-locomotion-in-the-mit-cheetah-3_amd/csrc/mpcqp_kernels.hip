@@ -4,7 +4,7 @@
 // CasADi Opti('conic') -> OSQP on the QP of src/mpc.py:58-173, filled at src/mpc.py:242-255, solved at :258.
 //
 // This translation unit is the C-ABI of include/mpcqp.h, mpcqp_plan.h, mpcqp_sim.h, mpcqp_model.h, mpcqp_joints.h, mpcqp_actuators.h, mpcqp_slip.h,
-// mpcqp_estimate.h, mpcqp_observe.h and mpcqp_gate.h,
+// mpcqp_estimate.h, mpcqp_observe.h, mpcqp_gate.h and mpcqp_attitude.h,
 // in three parts: the handle; its host helpers in one anonymous namespace, in order of use (errors, I/O-type dispatch, the solve, workspaces,
 // the device guard and the launch tail `on_device`, grids, the policy behind the configuration's defaults, the engine's tables, the roll-out
 // loops, the leg rows, the row tables); one extern "C" block of entry points, each its own checks and its own launches.  The device code is in
@@ -24,7 +24,8 @@
 //   mpcqp_actuators.h    per-robot actuator rows: the conversion of the caller's table and the torque-speed envelope the leg kernels share
 //   mpcqp_slip.h         stance feet that slide: the stance drive's rule with slip kinematics, and the foot move of its roll-out
 //   mpcqp_estimate.h     the torso state from an IMU and leg kinematics: the IMU rows of a log and the filter over them, without and
-//                        with the per-leg trust gate; the filter's row and the sensor rows as helpers, written once
+//                        with the per-leg trust gate and the velocity-aided attitude rule; the filter's row and the sensor rows as
+//                        helpers, written once
 //   mpcqp_observe.h      sensors and that filter inside the slip roll-out's tick loop, without and with the gate: the encoder row and
 //                        two kernels that call mpcqp_estimate.h's helpers around a tick
 // DESIGN.md has the derivations.
@@ -44,6 +45,7 @@
 #include "mpcqp_estimate.h"
 #include "mpcqp_observe.h"
 #include "../../include/mpcqp_gate.h"
+#include "../../include/mpcqp_attitude.h"
 
 #include <cstdio>
 #include <cstdlib>
@@ -840,11 +842,13 @@ struct RolloutDriveArgs { int32_t drive; const void* ground; void* cmd_log; };
 struct RolloutSlipArgs { const void* foot_mass; double* slip; double* slip_log; void* disp_log; };
 // What mpcqp_rollout_observe adds to mpcqp_rollout_slip: what the MPC reads, the filter state [B,131], the optional operands of the
 // sensors and the filter, the checked parameters, the seven logs or null; for mpcqp_rollout_observe_gated the checked thresholds (null: no
-// gate) and the trust log or null.
+// gate) and the trust log or null; for mpcqp_rollout_observe_aided the checked gains (null: not aided), att_state [B,8] and the bias log
+// or null.
 struct RolloutObserveArgs {
   int32_t feed; double* est_state; const void *est_init, *height, *bias, *noise, *enc_noise; EstPar par;
   void *imu_log, *q_enc_log, *qd_enc_log, *est_log, *feet_est_log, *sigma_log, *nis_log;
   const EstGate* gate; void* trust_log;
+  const EstAid* aid; double* att_state; void* bias_log;
 };
 
 // mpcqp_rollout_legs (dr = null), mpcqp_rollout_drive, mpcqp_rollout_slip (sl, with dr) and mpcqp_rollout_observe (ob, with both): one
@@ -868,6 +872,7 @@ int rollout_legs_run(mpcqp_handle h, const char* who, int64_t B, int32_t T, void
   if (B > 0 && (!x || !ref || !feet || !legs || !gait || !stand || !tick || !mu || !step_height)) return bad(h, who, "null buffer");
   if (B > 0 && sl && (!dr->ground || !sl->foot_mass || !sl->slip)) return bad(h, who, "null buffer");
   if (B > 0 && ob && !ob->est_state) return bad(h, who, "null buffer");
+  if (B > 0 && ob && ob->aid && !ob->att_state) return bad(h, who, "null att_state buffer");
   LegGeoDev g;
   LegInrDev r;
   if (const int rc = leg_rows(h, who, geo, inr, true, g, r)) return rc;
@@ -902,10 +907,12 @@ int rollout_legs_run(mpcqp_handle h, const char* who, int64_t B, int32_t T, void
       using TIO = decltype(tag);
       if (!ob) return launch_phase_expand<TIO>(h, B, st, xs, rf, phase_rows<TIO>(feet, gait, stand, gain), tick, w);
       const ObsWs<TIO> ow = observe_ws<TIO>(h->roll_mem, B, N);
-      const auto update = ob->gate ? mpcqp_observe_update_kernel<TIO, true> : mpcqp_observe_update_kernel<TIO, false>;
+      const auto update = ob->aid ? (ob->gate ? mpcqp_observe_update_kernel<TIO, true, true> : mpcqp_observe_update_kernel<TIO, false, true>)
+                                  : (ob->gate ? mpcqp_observe_update_kernel<TIO, true> : mpcqp_observe_update_kernel<TIO, false>);
       hipLaunchKernelGGL(update, gl, nt, 0, st, (const TIO*)xs, (const TIO*)rf, phase_rows<TIO>(feet, gait, stand, gain),
                          (const int32_t*)tick, (const double*)sl->slip, (const double*)legs, (const TIO*)step_height, observe_in(tag), ob->par, g,
-                         ob->est_state, ow, observe_out(tag), d, B, (int)T, it, ob->gate ? *ob->gate : EstGate{}, (TIO*)ob->trust_log);
+                         ob->est_state, ow, observe_out(tag), d, B, (int)T, it, ob->gate ? *ob->gate : EstGate{}, (TIO*)ob->trust_log,
+                         ob->aid ? *ob->aid : EstAid{}, ob->att_state, (TIO*)ob->bias_log);
       launch_phase_expand<TIO>(h, B, st, fed ? (const TIO*)ow.xhat : (const TIO*)xs, rf, phase_rows<TIO>(fed ? (void*)ow.feet : feet, gait, stand, gain),
                                tick, w);
     },
@@ -925,9 +932,12 @@ int rollout_legs_run(mpcqp_handle h, const char* who, int64_t B, int32_t T, void
                    (const double*)sl->slip, g, r.lim, (int)dr->drive, n, d / n, d, dw.f, dw.tau, dw.flag, cmd, (int64_t)T * 12, sl->slip, rdisp,
                    slog, (int64_t)T * 8, B);
         u = dw.f; Nu = 1;
-        if (ob)
-          hipLaunchKernelGGL((mpcqp_observe_predict_kernel<TIO>), gl, nt, 0, st, (const TIO*)xs, (const int32_t*)tick, u, plant_in<TIO>(h, plant),
-                             observe_in(tag), ob->par, ob->est_state, observe_ws<TIO>(h->roll_mem, B, N), observe_out(tag), B, (int)T, it);
+        if (ob) {
+          const auto predict = ob->aid ? mpcqp_observe_predict_kernel<TIO, true> : mpcqp_observe_predict_kernel<TIO, false>;
+          hipLaunchKernelGGL(predict, gl, nt, 0, st, (const TIO*)xs, (const int32_t*)tick, u, plant_in<TIO>(h, plant), observe_in(tag), ob->par,
+                             ob->est_state, observe_ws<TIO>(h->roll_mem, B, N), observe_out(tag), B, (int)T, it,
+                             ob->aid ? *ob->aid : EstAid{}, ob->att_state, (TIO*)ob->bias_log);
+        }
       } else if (dr) {
         TIO* cmd = dr->cmd_log ? (TIO*)dr->cmd_log + (size_t)it * 12 : nullptr;
         launch_act(h, gl, st, mpcqp_stance_drive_kernel<TIO>, mpcqp_stance_drive_kernel<TIO, double>, xs, o.u, (int64_t)N * 12,
@@ -980,33 +990,57 @@ int gate_row(mpcqp_handle h, const char* who, const MpcQpTrustGate* gate, EstGat
   return MPCQP_OK;
 }
 
-// mpcqp_estimate_track (gated = false: no gate, no trust_out) and mpcqp_estimate_track_gated: one argument check, one launch each.
+// The aided rule's gains of an entry point `who` (null: the defaults) and its flags, checked, with the estimator's checked row e.
+int attitude_row(mpcqp_handle h, const char* who, int32_t flags, const MpcQpAttitude* att, const EstPar& e, EstAid& a) {
+  MpcQpAttitude dflt;
+  if (!att) { (void)mpcqp_default_attitude(&dflt); att = &dflt; }
+  if (flags & ~MPCQP_AIDED_GATE) return bad(h, who, "flags has a bit other than MPCQP_AIDED_GATE");
+  if (att->size != sizeof(MpcQpAttitude)) return bad(h, who, "attitude struct size mismatch");
+  for (const double v : {att->k_s, att->k_v, att->k_b, att->b_max})
+    if (!std::isfinite(v) || !(v >= 0)) return bad(h, who, "attitude: k_s, k_v, k_b and b_max must be finite and non-negative");
+  a = {att->k_s, att->k_v, att->k_b * e.d, att->b_max, e.d * std::fabs(e.g)};
+  return MPCQP_OK;
+}
+
+// What mpcqp_estimate_track_aided adds to mpcqp_estimate_track_gated.
+struct EstimateAidedArgs { int32_t flags; const MpcQpAttitude* att; double* att_state; void* bias_log; };
+
+// mpcqp_estimate_track (gated = false: no gate, no trust_out), mpcqp_estimate_track_gated and mpcqp_estimate_track_aided (ad: whether
+// the gate runs is its flags'): one argument check, one launch each.
 int estimate_track_run(mpcqp_handle h, const char* who, int64_t B, int32_t T, const void* imu, const void* q, const void* qd,
                        const uint8_t* contact_log, const void* trust, const void* height, const void* init, const MpcQpEstimator* par,
                        const MpcQpLegGeometry* geo, double* state, void* est, void* feet_est, void* sigma, void* nis, bool gated,
-                       const MpcQpTrustGate* gate, void* trust_out, void* stream) {
+                       const MpcQpTrustGate* gate, void* trust_out, void* stream, const EstimateAidedArgs* ad = nullptr) {
   if (!h) return MPCQP_EINVAL;
   if (B < 0 || B > 0x7fffffff || T < 0 || B * (int64_t)T > 0x1fffffff) return bad(h, who, "size out of range");
-  if (!est && !feet_est && !sigma && !nis && !trust_out)
-    return bad(h, who, gated ? "no output buffer (est, feet_est, sigma, nis and trust_out are all null)"
-                             : "no output buffer (est, feet_est, sigma and nis are all null)");
+  if (!est && !feet_est && !sigma && !nis && !trust_out && !(ad && ad->bias_log))
+    return bad(h, who, ad      ? "no output buffer (est, feet_est, sigma, nis, trust_out and bias_log are all null)"
+                       : gated ? "no output buffer (est, feet_est, sigma, nis and trust_out are all null)"
+                               : "no output buffer (est, feet_est, sigma and nis are all null)");
   if (B > 0 && T > 0 && (!imu || !q || !qd)) return bad(h, who, "null buffer (imu, q, qd)");
   if (B > 0 && T > 0 && !init) return bad(h, who, "null init buffer");
   if (B > 0 && T > 0 && !trust && !contact_log) return bad(h, who, "null contact_log buffer without trust");
   EstPar e;
   if (const int rc = estimator_row(h, who, par, e)) return rc;
   EstGate eg = {};
+  EstAid ea = {};
+  if (ad) {
+    if (const int rc = attitude_row(h, who, ad->flags, ad->att, e, ea)) return rc;
+    gated = (ad->flags & MPCQP_AIDED_GATE) != 0;
+  }
   if (gated)
     if (const int rc = gate_row(h, who, gate, eg)) return rc;
   LegGeoDev g;
   if (const int rc = leg_geometry(h, who, geo, false, g)) return rc;
   if (B == 0 || T == 0) return MPCQP_OK;
-  return on_device(h, gated ? "gated estimate track kernel launch" : "estimate track kernel launch", [&](auto tag) {
+  const char* what = ad ? "aided estimate track kernel launch" : (gated ? "gated estimate track kernel launch" : "estimate track kernel launch");
+  return on_device(h, what, [&](auto tag) {
     using TIO = decltype(tag);
-    const auto track = gated ? mpcqp_estimate_track_kernel<TIO, true> : mpcqp_estimate_track_kernel<TIO, false>;
+    const auto track = ad ? (gated ? mpcqp_estimate_track_kernel<TIO, true, true> : mpcqp_estimate_track_kernel<TIO, false, true>)
+                          : (gated ? mpcqp_estimate_track_kernel<TIO, true> : mpcqp_estimate_track_kernel<TIO, false>);
     hipLaunchKernelGGL(track, leg_grid(B), dim3(256), 0, (hipStream_t)stream, (const TIO*)imu, (const TIO*)q, (const TIO*)qd, contact_log,
                        (const TIO*)trust, (const TIO*)height, (const TIO*)init, e, g, state, (TIO*)est, (TIO*)feet_est, (TIO*)sigma,
-                       (TIO*)nis, B, (int)T, eg, (TIO*)trust_out);
+                       (TIO*)nis, B, (int)T, eg, (TIO*)trust_out, ea, ad ? ad->att_state : nullptr, (TIO*)(ad ? ad->bias_log : nullptr));
   });
 }
 
@@ -1019,16 +1053,23 @@ struct RolloutSlipCall {
       *err_log; uint8_t* flag_log; void *miss_log, *cmd_log; double* slip_log; void* disp_log;
 };
 
-// mpcqp_rollout_observe (gated = false) and mpcqp_rollout_observe_gated: the checks of what they add to mpcqp_rollout_slip, then its loop.
+// mpcqp_rollout_observe (gated = false), mpcqp_rollout_observe_gated and mpcqp_rollout_observe_aided (ad: whether the gate runs is its
+// flags'): the checks of what they add to mpcqp_rollout_slip, then its loop.
 int rollout_observe_run(mpcqp_handle h, const char* who, const RolloutSlipCall& c, int32_t feed, double* est_state, const void* est_init,
                         const void* height, const void* bias, const void* noise, const void* enc_noise, const MpcQpEstimator* par,
                         void* imu_log, void* q_enc_log, void* qd_enc_log, void* est_log, void* feet_est_log, void* sigma_log, void* nis_log,
-                        bool gated, const MpcQpTrustGate* gate, void* trust_log, void* stream) {
+                        bool gated, const MpcQpTrustGate* gate, void* trust_log, void* stream, const EstimateAidedArgs* ad = nullptr) {
   if (!h) return MPCQP_EINVAL;
   if (feed != MPCQP_FEED_TRUTH && feed != MPCQP_FEED_ESTIMATE) return bad(h, who, "feed is neither MPCQP_FEED_TRUTH nor MPCQP_FEED_ESTIMATE");
   RolloutObserveArgs ob = {feed, est_state, est_init, height, bias, noise, enc_noise, {}, imu_log, q_enc_log, qd_enc_log, est_log, feet_est_log,
-                           sigma_log, nis_log, nullptr, trust_log};
+                           sigma_log, nis_log, nullptr, trust_log, nullptr, nullptr, nullptr};
   if (const int rc = estimator_row(h, who, par, ob.par)) return rc;
+  EstAid ea = {};
+  if (ad) {
+    if (const int rc = attitude_row(h, who, ad->flags, ad->att, ob.par, ea)) return rc;
+    gated = (ad->flags & MPCQP_AIDED_GATE) != 0;
+    ob.aid = &ea; ob.att_state = ad->att_state; ob.bias_log = ad->bias_log;
+  }
   EstGate eg = {};
   if (gated) {
     if (const int rc = gate_row(h, who, gate, eg)) return rc;
@@ -1704,6 +1745,26 @@ int mpcqp_rollout_observe(mpcqp_handle h, int64_t B, int32_t T, void* x, void* r
                              qd_enc_log, est_log, feet_est_log, sigma_log, nis_log, false, nullptr, nullptr, stream);
 }
 
+int mpcqp_rollout_observe_aided(mpcqp_handle h, int64_t B, int32_t T, void* x, void* ref, void* feet, double* legs, const int32_t* gait,
+                                const void* stand, const void* gain, int32_t* tick, const void* mu, const void* body, const void* push,
+                                const int32_t* push_ticks, int32_t substeps, const void* step_height, const void* gains,
+                                int32_t leg_substeps, const MpcQpLegGeometry* geo, const MpcQpLegInertia* inr, int32_t land, int32_t drive,
+                                const void* ground, const void* foot_mass, double* slip, void* actual, void* desired, void* forces,
+                                void* feet_log, uint8_t* contact_log, int32_t* solved, void* swing_log, void* q_log, void* qd_log,
+                                void* tau_log, void* foot_log, void* err_log, uint8_t* flag_log, void* miss_log, void* cmd_log,
+                                double* slip_log, void* disp_log, int32_t feed, double* est_state, const void* est_init, const void* height,
+                                const void* bias, const void* noise, const void* enc_noise, const MpcQpEstimator* par, void* imu_log,
+                                void* q_enc_log, void* qd_enc_log, void* est_log, void* feet_est_log, void* sigma_log, void* nis_log,
+                                const MpcQpTrustGate* gate, void* trust_log, int32_t flags, const MpcQpAttitude* att, double* att_state,
+                                void* bias_log, void* stream) {
+  const RolloutSlipCall c = {B, T, x, ref, feet, legs, gait, stand, gain, tick, mu, body, push, push_ticks, substeps, step_height, gains,
+                             leg_substeps, geo, inr, land, drive, ground, foot_mass, slip, actual, desired, forces, feet_log, contact_log,
+                             solved, swing_log, q_log, qd_log, tau_log, foot_log, err_log, flag_log, miss_log, cmd_log, slip_log, disp_log};
+  const EstimateAidedArgs ad = {flags, att, att_state, bias_log};
+  return rollout_observe_run(h, "mpcqp_rollout_observe_aided", c, feed, est_state, est_init, height, bias, noise, enc_noise, par, imu_log,
+                             q_enc_log, qd_enc_log, est_log, feet_est_log, sigma_log, nis_log, false, gate, trust_log, stream, &ad);
+}
+
 int mpcqp_rollout_observe_gated(mpcqp_handle h, int64_t B, int32_t T, void* x, void* ref, void* feet, double* legs, const int32_t* gait,
                                 const void* stand, const void* gain, int32_t* tick, const void* mu, const void* body, const void* push,
                                 const int32_t* push_ticks, int32_t substeps, const void* step_height, const void* gains,
@@ -1796,6 +1857,27 @@ int mpcqp_default_trust_gate(MpcQpTrustGate* gate) {
   gate->d_lo = 1.0;
   gate->d_hi = 4.0;
   return MPCQP_OK;
+}
+
+int mpcqp_default_attitude(MpcQpAttitude* att) {
+  if (!att) return MPCQP_EINVAL;
+  memset(att, 0, sizeof(*att));
+  att->size = (uint32_t)sizeof(*att);
+  att->k_s = 0.0;
+  att->k_v = 2.0;
+  att->k_b = 5.0;
+  att->b_max = 0.1;
+  return MPCQP_OK;
+}
+
+int mpcqp_estimate_track_aided(mpcqp_handle h, int64_t B, int32_t T, const void* imu, const void* q, const void* qd,
+                               const uint8_t* contact_log, const void* trust, const void* height, const void* init,
+                               const MpcQpEstimator* par, const MpcQpLegGeometry* geo, double* state, void* est, void* feet_est, void* sigma,
+                               void* nis, const MpcQpTrustGate* gate, void* trust_out, int32_t flags, const MpcQpAttitude* att,
+                               double* att_state, void* bias_log, void* stream) {
+  const EstimateAidedArgs ad = {flags, att, att_state, bias_log};
+  return estimate_track_run(h, "mpcqp_estimate_track_aided", B, T, imu, q, qd, contact_log, trust, height, init, par, geo, state, est,
+                            feet_est, sigma, nis, false, gate, trust_out, stream, &ad);
 }
 
 int mpcqp_estimate_track_gated(mpcqp_handle h, int64_t B, int32_t T, const void* imu, const void* q, const void* qd,

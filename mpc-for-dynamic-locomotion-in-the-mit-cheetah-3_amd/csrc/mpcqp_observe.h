@@ -16,6 +16,9 @@
 // mpcqp_rollout_observe_gated (include/mpcqp_gate.h) launches the update kernel's GATE variant: est_measure then runs est_gate between
 // steps 1 and 2, and the gated trust goes where the update leaves "the trust of step 1" for the predict kernel; the predict kernel,
 // the side buffers and the launch count are the ungated call's.
+// mpcqp_rollout_observe_aided (include/mpcqp_attitude.h) launches the AIDED variants of both: the update reads b^ from att_state, runs the
+// row with g' = gyro - b^ and stores e_b there; the predict reads b^ and e_b back, forms g' from the raw gyro of the sensor row again,
+// and steps the orientation and b^ with est_predict<true>.  Nothing else passes between the two, and the side buffers are unchanged.
 #pragma once
 #include "mpcqp_estimate.h"
 #include "mpcqp_legroll.h"
@@ -95,14 +98,17 @@ __device__ __forceinline__ void obs_encoders(const TIO* __restrict__ xb, const T
 
 // Sense and update of tick `it`: i = 4 b + lane.  GATE (mpcqp_rollout_observe_gated) adds step 1g of the filter's row (est_gate,
 // include/mpcqp_gate.h): the sensor row the predict reads back then carries w in the place of the clock's trust, and trust_log (may be
-// null) gets the row's w; without it `gate` and `trust_log`, the last two arguments, are not read.
-template <typename TIO, bool GATE>
+// null) gets the row's w; without it `gate` and `trust_log` are not read.  AIDED (mpcqp_rollout_observe_aided) adds items 1 to 4 of
+// include/mpcqp_attitude.h's rule, writes trust_log with or without GATE, and reads the last two arguments: att_state and bias_log (may
+// be null).
+template <typename TIO, bool GATE, bool AIDED = false>
 __global__ void __launch_bounds__(256)
 mpcqp_observe_update_kernel(const TIO* __restrict__ x, const TIO* __restrict__ ref, const PhaseRows<TIO> ph, const int32_t* __restrict__ tick,
                             const double* __restrict__ slip, const double* __restrict__ legs, const TIO* __restrict__ step_height,
                             const ObsIn<TIO> in, const EstPar par, const LegGeoDev geo, double* state, const ObsWs<TIO> ws,
                             const ObsOut<TIO> out, const double d, const int64_t B, const int T, const int it, const EstGate gate,
-                            TIO* __restrict__ trust_log) {
+                            TIO* __restrict__ trust_log, const EstAid aid = EstAid{}, double* att = nullptr,
+                            TIO* __restrict__ bias_log = nullptr) {
 #pragma clang fp contract(off)
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= 4 * B) return;   // (whole quads leave: the lane moves below see all four lanes or none)
@@ -140,18 +146,24 @@ mpcqp_observe_update_kernel(const TIO* __restrict__ x, const TIO* __restrict__ r
   if (fresh) est_fresh(in.est_init ? in.est_init + 12 * b : xb, par, a, qh, xi, U, mine); else est_load(sb, a, qh, xi, U, mine);
   est_heights(in.height, b, hl, mine);
   const bool hgt = in.height != nullptr && a == 2;
+  V3 bh = {0.0, 0.0, 0.0}, gp = gy;
+  if constexpr (AIDED) {
+    bh = est_aid_load(att + b * ATT_STATE, fresh, mine);
+    gp = est_aid_sense(gy, bh);
+  }
   const bool ok = est_quad_all(mine);   // the robot's flag
   // ---- steps 1, 1g and 2 of the row.  With GATE tr becomes w, which is what the predict reads back (a poisoned robot's predict does not
   //      use it: its state is NaN).
   const M3 R = est_rot(qh);
   V3 rho, rhod;
   double zr[4], zv[4];
-  est_foot(geo, l, qe, qde, R, gy, rho, rhod);
+  est_foot(geo, l, qe, qde, R, gp, rho, rhod);
   est_across(a, rho, zr); est_across(a, rhod, zv);
   if (fresh) est_first_feet(zr, xi);
+  const double vpred = xi[1];
   const double nis = est_measure<TIO, GATE>(par, gate, hgt, hl, zr, zv, tr, xi, U);
   // ---- step 3: the log rows, the controller's side buffers, the sensor row for the predict, and the posterior
-  const V3 omh = est_mv(R, gy);
+  const V3 omh = est_mv(R, gp);
   if (l < 3) {
     const TIO ep = est_out<TIO>(ok, xi[0]), ev = est_out<TIO>(ok, xi[1]);
     if (out.est) { out.est[12 * row + 3 + a] = ep; out.est[12 * row + 9 + a] = ev; }
@@ -177,22 +189,31 @@ mpcqp_observe_update_kernel(const TIO* __restrict__ x, const TIO* __restrict__ r
     store3(s, true, gy);
 #pragma unroll
     for (int j = 0; j < 4; ++j) s[3 + j] = (TIO)tr[j];
-    if constexpr (GATE) {
+    if constexpr (GATE || AIDED) {
       if (trust_log) {
 #pragma unroll
         for (int j = 0; j < 4; ++j) trust_log[4 * row + j] = est_out<TIO>(ok, tr[j]);
       }
     }
   }
+  if constexpr (AIDED) {   // (every lane runs the broadcasts of est_aid_error; lane 3 stores)
+    const V3 eb = est_aid_error(aid, R, vpred, xi[1]);
+    if (l == 3) {
+      if (bias_log) store3(bias_log + 3 * row, ok, bh);
+      est_aid_store(att + b * ATT_STATE, ok, bh, eb);
+    }
+  }
   est_store(sb, l, a, ok, qh, xi, U);
 }
 
-// Predict of tick `it`: i = 4 b + lane.  u is the applied forces of the tick, [B,12] (the slip rule's side buffer).
-template <typename TIO>
+// Predict of tick `it`: i = 4 b + lane.  u is the applied forces of the tick, [B,12] (the slip rule's side buffer).  AIDED reads the
+// last three arguments: the gains, att_state (b^ and the e_b the update left) and bias_log (may be null; a poisoned row's is NaN).
+template <typename TIO, bool AIDED = false>
 __global__ void __launch_bounds__(256)
 mpcqp_observe_predict_kernel(const TIO* __restrict__ x, const int32_t* __restrict__ tick, const TIO* __restrict__ u, const PlantIn<TIO> pin,
                              const ObsIn<TIO> in, const EstPar par, double* state, const ObsWs<TIO> ws, const ObsOut<TIO> out,
-                             const int64_t B, const int T, const int it) {
+                             const int64_t B, const int T, const int it, const EstAid aid = EstAid{}, double* att = nullptr,
+                             TIO* __restrict__ bias_log = nullptr) {
 #pragma clang fp contract(off)
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= 4 * B) return;
@@ -221,6 +242,21 @@ mpcqp_observe_predict_kernel(const TIO* __restrict__ x, const int32_t* __restric
   double qh[4], xi[6], U[21];
   bool mine = fin3(gy) && fin3(sf);
   est_load(sb, a, qh, xi, U, mine);
+  if constexpr (AIDED) {
+    double* const ab = att + b * ATT_STATE;
+    V3 bh = {ab[0], ab[1], ab[2]};
+    const V3 eb = {ab[3], ab[4], ab[5]};
+    mine = mine && fin3(bh) && fin3(eb);
+    const bool ok = est_quad_all(mine);
+    est_predict<true>(par, a, est_rot(qh), est_aid_sense(gy, bh), sf, tr, qh, xi, U, aid, eb, &bh);
+    if (!ok) obs_nan_row(out, row, l);
+    if (l == 3) {
+      if (!ok && bias_log) store3(bias_log + 3 * row, false, bh);
+      est_aid_store(ab, ok, bh, eb);
+    }
+    est_store(sb, l, a, ok, qh, xi, U);
+    return;
+  }
   const bool ok = est_quad_all(mine);
   est_predict(par, a, est_rot(qh), gy, sf, tr, qh, xi, U);
   if (!ok) obs_nan_row(out, row, l);   // (a row whose accelerometer is not finite: mpcqp_estimate_track's outputs of that row are NaN)

@@ -659,7 +659,7 @@ class MPCBatch:
     def rollout_observe(self, x, ref, feet, legs, gait, stand, gain, tick, mu, T, step_height, ground, foot_mass, slip, est_state,
                         feed="estimate", est_init=None, height=None, bias=None, noise=None, enc_noise=None, estimator=None, land="rule",
                         drive="limited", body=None, push=None, push_ticks=None, substeps=10, gains=None, leg_substeps=0, inertia=None,
-                        geometry=None, log=True, stream=None, gate=None):
+                        geometry=None, log=True, stream=None, gate=None, attitude=None, att_state=None):
         """`rollout_slip` with sensors and the state estimator inside the tick loop (include/mpcqp_observe.h, mpcqp_rollout_observe,
         which has the rule; the host counterpart is gaits.rollout_observe_host): per tick the encoders and the IMU are read off the
         live state, one row of `estimate_track` runs on est_state float64 [B,131] (state next to `x`, ..., `slip`, advanced IN PLACE;
@@ -670,29 +670,47 @@ class MPCBatch:
         "imu" [B,T,6], "q_enc", "qd_enc" [B,T,4,3], "est" [B,T,12], "feet_est" [B,T,4,3], "sigma" [B,T,6] and "nis" [B,T].  Every
         other argument as in `rollout_slip`.  gate: None, or a dict of estimator.gate_row's fields ({} = the defaults) or an
         MpcQpTrustGate for mpcqp_rollout_observe_gated (include/mpcqp_gate.h): the filter's trust is the clock's gated per leg on the
-        leg's velocity innovation, and the dict gains "trust" [B,T,4].  Asynchronous on `stream`."""
+        leg's velocity innovation, and the dict gains "trust" [B,T,4].  attitude: None (today's call through today's entry point), or a
+        dict of estimator.attitude_row's fields ({} = the defaults) or an MpcQpAttitude for mpcqp_rollout_observe_aided
+        (include/mpcqp_attitude.h): the velocity update's correction steers the orientation and a gyro-bias state; att_state float64
+        [B,8] is state like est_state, advanced IN PLACE (None: a fresh zero one), and the dict gains "gyro_bias" [B,T,3] and
+        "att_state".  Asynchronous on `stream`."""
         from . import estimator as _est
         B, T, f64 = int(x.shape[0]), int(T), _torch().float64
+        if attitude is None and att_state is not None:
+            raise ValueError("att_state needs attitude")
         feeds = {"truth": _capi.FEED_TRUTH, "estimate": _capi.FEED_ESTIMATE}
         if not isinstance(feed, int) and feed not in feeds:
             raise ValueError(f"feed must be 'truth' or 'estimate', got {feed!r}")
         check_operands(self.device, (("est_state", est_state, (B, _capi.EST_STATE), f64), ("est_init", est_init, (B, 12), self.tdtype),
                                      ("height", height, (B, 4), self.tdtype), ("bias", bias, (B, 6), self.tdtype),
-                                     ("noise", noise, (B, T, 6), self.tdtype), ("enc_noise", enc_noise, (B, T, 4, 6), self.tdtype)),
-                       optional=("est_init", "height", "bias", "noise", "enc_noise"))
+                                     ("noise", noise, (B, T, 6), self.tdtype), ("enc_noise", enc_noise, (B, T, 4, 6), self.tdtype),
+                                     ("att_state", att_state, (B, _capi.ATT_STATE), f64)),
+                       optional=("est_init", "height", "bias", "noise", "enc_noise", "att_state"))
         tail = (feed if isinstance(feed, int) else feeds[feed], est_state.data_ptr(), _ptr(est_init), _ptr(height), _ptr(bias), _ptr(noise),
                 _ptr(enc_noise), _est.estimator_struct(estimator))
         leg3 = ((4, 3), self.tdtype)
         call, more = self.engine.rollout_observe_ptr, ()
-        if gate is not None:
+        if attitude is not None:
+            if att_state is None:
+                att_state, = self._alloc(stream, ((B, _capi.ATT_STATE), f64, True))
+            call, more = self.engine.rollout_observe_aided_ptr, (("trust", (4,), self.tdtype), ("gyro_bias", (3,), self.tdtype))
+            tail += (None if gate is None else _est.gate_struct(gate), 0 if gate is None else _capi.AIDED_GATE,
+                     _est.attitude_struct(attitude), att_state.data_ptr())
+        elif gate is not None:
             call, more, tail = self.engine.rollout_observe_gated_ptr, (("trust", (4,), self.tdtype),), tail + (_est.gate_struct(gate),)
-        return self._rollout_legs(call, x, ref, feet, legs, gait, stand, gain, tick, mu, T, step_height, land, body, push, push_ticks, substeps,
+        out = self._rollout_legs(call, x, ref, feet, legs, gait, stand, gain, tick, mu, T, step_height, land, body, push, push_ticks, substeps,
                                   gains, leg_substeps, inertia, geometry, log, stream, drive,
                                   operands=(("ground", ground, (B,), self.tdtype), ("foot_mass", foot_mass, (B,), self.tdtype),
                                             ("slip", slip, (B, 4, 2), f64)),
                                   logs=(("cmd", (12,), self.tdtype), ("slip_log", (4, 2), f64), ("disp", (4, 2), self.tdtype),
                                         ("imu", (6,), self.tdtype), ("q_enc", *leg3), ("qd_enc", *leg3), ("est", (12,), self.tdtype),
                                         ("feet_est", *leg3), ("sigma", (6,), self.tdtype), ("nis", (), self.tdtype)) + more, tail=tail)
+        if attitude is not None:
+            out["att_state"] = att_state
+            if gate is None:
+                del out["trust"]
+        return out
 
     def score(self, logs, score=None, rule=None, stream=None):
         """The score row of a roll-out's logs, reduced on the device (include/mpcqp_sim.h, mpcqp_rollout_score; the host counterpart is
@@ -752,7 +770,7 @@ class MPCBatch:
     from .estimator import OUT as EST_OUT      # ("est", "feet", "sigma", "nis"): the host counterpart's names, in the C order
 
     def estimate_track(self, imu, q, qd, contact_log, init, trust=None, height=None, state=None, estimator=None, geometry=None,
-                       want=EST_OUT, stream=None, gate=None):
+                       want=EST_OUT, stream=None, gate=None, attitude=None, att_state=None):
         """The torso state estimated from the IMU and the leg encoders over the rows of a log (include/mpcqp_estimate.h,
         mpcqp_estimate_track, which has the rule; the host counterparts are estimator.estimate_track_host and estimate_joint_host):
         imu [B,T,6] as `imu_log` returns it, q, qd [B,T,4,3] the "q" / "qd" logs of `rollout_legs`, `rollout_drive`, `rollout_slip` or
@@ -761,15 +779,22 @@ class MPCBatch:
         init) or None -> {"est" [B,T,12] in the layout of `actual`, "feet" [B,T,4,3], "sigma" [B,T,6], "nis" [B,T]}; an output not in
         `want` is None.  gate: None, or a dict of estimator.gate_row's fields ({} = the defaults) or an MpcQpTrustGate for
         mpcqp_estimate_track_gated (include/mpcqp_gate.h): every row's trust is gated per leg on the leg's velocity innovation, and the
-        dict gains "trust" [B,T,4], the trust the rows used.  Asynchronous on `stream`."""
+        dict gains "trust" [B,T,4], the trust the rows used.  attitude: None (today's call through today's entry point), or a dict of
+        estimator.attitude_row's fields ({} = the defaults) or an MpcQpAttitude for mpcqp_estimate_track_aided
+        (include/mpcqp_attitude.h); att_state float64 [B,8] goes with `state` and is advanced IN PLACE (None: a fresh zero one), and the
+        dict gains "gyro_bias" [B,T,3] and "att_state".  Asynchronous on `stream`."""
         from . import estimator as _est
         torch = _torch()
+        if attitude is None and att_state is not None:
+            raise ValueError("att_state needs attitude")
         B, T = int(imu.shape[0]), int(imu.shape[1]) if imu.dim() == 3 else -1
         legs = ((B, T, 4, 3), self.tdtype)
         check_operands(self.device, (("imu", imu, (B, T, 6), self.tdtype), ("q", q, *legs), ("qd", qd, *legs),
                                      ("contact_log", contact_log, (B, T, 4), torch.uint8), ("init", init, (B, 12), self.tdtype),
                                      ("trust", trust, (B, T, 4), self.tdtype), ("height", height, (B, 4), self.tdtype),
-                                     ("state", state, (B, _capi.EST_STATE), torch.float64)), optional=("trust", "height", "state"))
+                                     ("state", state, (B, _capi.EST_STATE), torch.float64),
+                                     ("att_state", att_state, (B, _capi.ATT_STATE), torch.float64)),
+                       optional=("trust", "height", "state", "att_state"))
         unknown = set(want) - set(self.EST_OUT)
         if unknown or not want:
             raise ValueError(f"want must name at least one of {self.EST_OUT}, got {tuple(want)}")
@@ -778,7 +803,17 @@ class MPCBatch:
         out = dict(zip(self.EST_OUT, self._alloc(stream, *[spec[k] if k in want else None for k in self.EST_OUT])))
         head = (B, T, imu.data_ptr(), q.data_ptr(), qd.data_ptr(), contact_log.data_ptr(), _ptr(trust), _ptr(height), init.data_ptr(), _ptr(state),
                 *[_ptr(out[k]) for k in self.EST_OUT])
-        if gate is None:
+        if attitude is not None:
+            if att_state is None:
+                att_state, = self._alloc(stream, ((B, _capi.ATT_STATE), torch.float64, True))
+            if gate is not None:
+                out["trust"], = self._alloc(stream, ((B, T, 4), self.tdtype))
+            out["gyro_bias"], = self._alloc(stream, ((B, T, 3), self.tdtype))
+            out["att_state"] = att_state
+            self.engine.estimate_track_aided_ptr(*head, _ptr(out.get("trust")), out["gyro_bias"].data_ptr(), _est.estimator_struct(estimator),
+                                                 None if gate is None else _est.gate_struct(gate), 0 if gate is None else _capi.AIDED_GATE,
+                                                 _est.attitude_struct(attitude), att_state.data_ptr(), geometry, st.cuda_stream)
+        elif gate is None:
             self.engine.estimate_track_ptr(*head, _est.estimator_struct(estimator), geometry, st.cuda_stream)
         else:
             out["trust"], = self._alloc(stream, ((B, T, 4), self.tdtype))

@@ -16,6 +16,8 @@ DEFAULTS = {"gravity": -9.81, "kappa": 2.0, "q_p": 0.02, "q_v": 0.02, "q_f": 0.0
             "k_swing": 100.0, "p0_p": 0.01, "p0_v": 1.0, "p0_f": 0.01}
 OUT = ("est", "feet", "sigma", "nis")
 GATE_DEFAULTS = {"d_lo": 1.0, "d_hi": 4.0}            # include/mpcqp_gate.h, mpcqp_default_trust_gate
+ATT_STATE = 8              # include/mpcqp_attitude.h, MPCQP_ATT_STATE
+ATT_DEFAULTS = {"k_s": 0.0, "k_v": 2.0, "k_b": 5.0, "b_max": 0.1}            # include/mpcqp_attitude.h, mpcqp_default_attitude
 
 
 def estimator_row(**kw):
@@ -72,6 +74,48 @@ def gate_struct(gate):
     par.size = _capi.ctypes.sizeof(_capi.MpcQpTrustGate)
     par.d_lo, par.d_hi = row["d_lo"], row["d_hi"]
     return par
+
+
+def attitude_row(**kw):
+    """The aided attitude rule's gains as a dict: the defaults of mpcqp_default_attitude with `kw` over them, checked as the library
+    checks an MpcQpAttitude (finite and non-negative)."""
+    unknown = set(kw) - set(ATT_DEFAULTS)
+    if unknown:
+        raise ValueError(f"MpcQpAttitude has no field {sorted(unknown)}; the fields are {tuple(ATT_DEFAULTS)}")
+    row = {k: float(kw.get(k, v)) for k, v in ATT_DEFAULTS.items()}
+    for k, v in row.items():
+        if not np.isfinite(v) or not v >= 0:
+            raise ValueError(f"attitude: {k} must be finite and non-negative")
+    return row
+
+
+def attitude_struct(attitude):
+    """An MpcQpAttitude, or a dict of `attitude_row`'s fields ({} = the defaults) -> the structure the binding passes."""
+    from . import _capi
+    if isinstance(attitude, _capi.MpcQpAttitude):
+        return attitude
+    row = attitude_row(**attitude)
+    par = _capi.MpcQpAttitude()
+    par.size = _capi.ctypes.sizeof(_capi.MpcQpAttitude)
+    for k, v in row.items():
+        setattr(par, k, v)
+    return par
+
+
+def _att_operands(att_state, fresh, B):
+    """b^ [B,3] at the start of a call (zero for a fresh robot and without att_state) and whether what was read is finite [B]."""
+    if att_state is None:
+        return np.zeros((B, 3)), np.ones(B, bool)
+    ast = np.array(att_state, dtype=np.float64).reshape(B, ATT_STATE)
+    bh = np.where(fresh[:, None], 0.0, ast[:, 0:3])
+    return bh, np.isfinite(bh).all(-1)
+
+
+def _att_state(bh, eb, ok):
+    out = np.zeros((bh.shape[0], ATT_STATE))
+    out[:, 0:3], out[:, 3:6] = bh, eb
+    out[~ok] = np.nan
+    return out
 
 
 def trust_gate(gate, par, xi, P, rhod, c, io_dtype=np.float64):
@@ -214,7 +258,7 @@ def _update(xi, P, kind, c, z, r):
 
 
 def estimate_track_host(imu, q, qd, contact_log, init, trust=None, height=None, state=None, estimator=None, delta=0.03, gate=None,
-                        io_dtype=np.float64):
+                        io_dtype=np.float64, attitude=None, att_state=None):
     """The filter over the rows of a log (mpcqp_estimate_track), per axis and measurement by measurement in the device's order: imu
     [B,T,6], q, qd [B,T,4,3], contact_log [B,T,4], init [B,12], trust [B,T,4] or None (contact != 0), height [B,4] or None, state
     [B,131] or None (not modified) -> {"est" [B,T,12], "feet" [B,T,4,3], "sigma" [B,T,6], "nis" [B,T], "state" [B,131]: the predicted
@@ -222,10 +266,22 @@ def estimate_track_host(imu, q, qd, contact_log, init, trust=None, height=None, 
     returned state is NaN.
     gate: None, or a dict of `gate_row`'s fields ({} = the defaults) for mpcqp_estimate_track_gated (include/mpcqp_gate.h): every row's
     trust is gated on the legs' velocity innovations before the row's updates, w is rounded through `io_dtype` (the handle's I/O type:
-    with it this is the counterpart of either handle), and the result has "trust" [B,T,4] = w and "gate_d" [B,T,4] = d."""
+    with it this is the counterpart of either handle), and the result has "trust" [B,T,4] = w and "gate_d" [B,T,4] = d.
+    attitude: None, or a dict of `attitude_row`'s fields ({} = the defaults) for mpcqp_estimate_track_aided (include/mpcqp_attitude.h,
+    which has the rule), with att_state [B,8] or None (not modified; read where `state` is live): the rows use g' = gyro - b^, the
+    velocity update's correction steers the orientation and b^, and the result has "gyro_bias" [B,T,3] = b^ as each row found it and
+    "att_state" [B,8], to be passed to the next piece with "state"."""
     par = _row(estimator)
     gpar = None if gate is None else gate_row(**gate)
+    apar = None if attitude is None else attitude_row(**attitude)
+    if apar is None and att_state is not None:
+        raise ValueError("att_state needs attitude")
     imu, q, qd, init, tr, hz, st, fresh, q0, ok, rows_ok, B, T = _operands(imu, q, qd, contact_log, init, trust, height, state)
+    if apar is not None:
+        bh, bok = _att_operands(att_state, fresh, B)
+        ok = ok & bok
+        eb, blog = np.zeros((B, 3)), np.zeros((B, T, 3))
+        dg, kbd = float(delta) * abs(par["gravity"]), apar["k_b"] * float(delta)
     d, hd2, g = float(delta), 0.5 * float(delta) * float(delta), par["gravity"]
     est, feet, sigma, nis = np.zeros((B, T, 12)), np.zeros((B, T, 4, 3)), np.zeros((B, T, 6)), np.zeros((B, T))
     wlog, dlog = np.zeros((B, T, 4)), np.zeros((B, T, 4))
@@ -247,11 +303,15 @@ def estimate_track_host(imu, q, qd, contact_log, init, trust=None, height=None, 
             ok = ok & rows_ok[:, t]
             gy, sf = imu[:, t, 0:3], imu[:, t, 3:6]
             R = plant.quat_to_matrix(qh)
+            if apar is not None:
+                blog[:, t] = bh
+                gy = gy - bh
             rho, rhod = leg_kinematics(q[:, t], qd[:, t], R, gy)
             if t == 0:
                 for a in range(3):
                     for l in range(4):
                         xi[a, 2 + l] = np.where(fresh, xi[a, 0] + rho[:, l, a], xi[a, 2 + l])
+            vpred = xi[0:2, 1].copy()
             w = tr[:, t]
             if gpar is not None:
                 w, dlog[:, t] = trust_gate(gpar, par, xi, P, rhod, w, io_dtype)
@@ -266,6 +326,9 @@ def estimate_track_host(imu, q, qd, contact_log, init, trust=None, height=None, 
                     if a == 2 and hz is not None:
                         n = n + _update(xi[a], P[a], 2, 2 + l, hz[:, l], par["r_z"] * s[l])
                 na.append(n)
+            if apar is not None:
+                dv = xi[0:2, 1] - vpred
+                eb = _mtv(R, np.stack([(-dv[1]) / dg, dv[0] / dg, np.zeros(B)], axis=-1))
             est[:, t, 0:3] = plant.quat_to_rotvec(qh)
             est[:, t, 6:9] = _mv(R, gy)
             for a in range(3):
@@ -275,6 +338,8 @@ def estimate_track_host(imu, q, qd, contact_log, init, trust=None, height=None, 
             nis[:, t] = (na[0] + na[1]) + na[2]
             bad = ~ok
             est[bad, t], feet[bad, t], sigma[bad, t], nis[bad, t], wlog[bad, t] = np.nan, np.nan, np.nan, np.nan, np.nan
+            if apar is not None:
+                blog[bad, t] = np.nan
             # predict
             for a in range(3):
                 aw = (R[:, a, 0] * sf[:, 0] + R[:, a, 1] * sf[:, 1]) + R[:, a, 2] * sf[:, 2]
@@ -292,7 +357,12 @@ def estimate_track_host(imu, q, qd, contact_log, init, trust=None, height=None, 
                 for l in range(4):
                     Pa[2 + l, 2 + l] = Pa[2 + l, 2 + l] + d * (par["q_f"] * s[l])
             kap, sh = _kappa(par, sf)
-            wh = _mv(R, gy + kap[:, None] * _cross(sh, R[:, 2, :]))
+            if apar is None:
+                wh = _mv(R, gy + kap[:, None] * _cross(sh, R[:, 2, :]))
+            else:
+                wh = _mv(R, (gy + (apar["k_s"] * kap)[:, None] * _cross(sh, R[:, 2, :])) + apar["k_v"] * eb)
+                nb = bh - kbd * eb
+                bh = np.where(nb < -apar["b_max"], -apar["b_max"], np.where(nb > apar["b_max"], apar["b_max"], nb))
             n = quat_mul(plant.rotvec_to_quat(d * wh), qh)
             nq = np.sqrt(((n[:, 0] * n[:, 0] + n[:, 1] * n[:, 1]) + n[:, 2] * n[:, 2]) + n[:, 3] * n[:, 3])
             qh = n / nq[:, None]
@@ -304,17 +374,28 @@ def estimate_track_host(imu, q, qd, contact_log, init, trust=None, height=None, 
     out_state[:, _LIVE] = 1.0
     out_state[~ok] = np.nan
     res = {"est": est, "feet": feet, "sigma": sigma, "nis": nis, "state": out_state}
+    if apar is not None:
+        res.update(gyro_bias=blog, att_state=_att_state(bh, eb, ok))
     return res if gpar is None else dict(res, trust=wlog, gate_d=dlog)
 
 
-def estimate_joint_host(imu, q, qd, contact_log, init, trust=None, height=None, state=None, estimator=None, delta=0.03):
+def estimate_joint_host(imu, q, qd, contact_log, init, trust=None, height=None, state=None, estimator=None, delta=0.03, attitude=None,
+                        att_state=None):
     """`estimate_track_host` in the textbook form: one filter with the 18 states (p, v, c_FL, c_FR, c_HL, c_HR), every measurement of a
     row in one batch update -- K = P H^T S^-1 by np.linalg.solve, P = (I - K H) P, nis = e^T S^-1 e -- and the orientation through
     scipy's Rotation.  Operands and results as there (the state's layout too); only `leg_kinematics`, the operand check and the tilt
-    gain are shared."""
+    gain are shared.  attitude / att_state as there (include/mpcqp_attitude.h): dv is read off the batch update's state step, e_b, the
+    rate and b^ are formed with numpy's matrix products, cross and clip, and the result has "gyro_bias" and "att_state"."""
     from scipy.spatial.transform import Rotation
     par = _row(estimator)
+    apar = None if attitude is None else attitude_row(**attitude)
+    if apar is None and att_state is not None:
+        raise ValueError("att_state needs attitude")
     imu, q, qd, init, tr, hz, st, fresh, q0, ok, rows_ok, B, T = _operands(imu, q, qd, contact_log, init, trust, height, state)
+    if apar is not None:
+        bh, bok = _att_operands(att_state, fresh, B)
+        ok = ok & bok
+        bh, eb, blog = np.nan_to_num(bh), np.zeros((B, 3)), np.zeros((B, T, 3))
     d, g = float(delta), par["gravity"]
     est, feet, sigma, nis = np.zeros((B, T, 12)), np.zeros((B, T, 4, 3)), np.zeros((B, T, 6)), np.zeros((B, T))
     nz = np.nan_to_num                      # (a poisoned robot is masked by `ok`; its rows are computed on zeros)
@@ -352,6 +433,9 @@ def estimate_joint_host(imu, q, qd, contact_log, init, trust=None, height=None, 
             gy, sf = nz(imu[:, t, 0:3]), nz(imu[:, t, 3:6])
             rot = Rotation.from_quat(nz(qh)[:, [1, 2, 3, 0]] + np.where(np.isfinite(qh).all(-1), 0.0, 1.0)[:, None] * np.array([0, 0, 0, 1.0]))
             R = rot.as_matrix()
+            if apar is not None:
+                blog[:, t] = bh
+                gy = gy - bh
             rho, rhod = leg_kinematics(nz(q[:, t]), nz(qd[:, t]), R, gy)
             if t == 0:
                 for l in range(4):
@@ -369,7 +453,11 @@ def estimate_joint_host(imu, q, qd, contact_log, init, trust=None, height=None, 
             S = H @ PHt + rv[:, :, None] * np.eye(M)
             K = np.transpose(np.linalg.solve(S, np.transpose(PHt, (0, 2, 1))), (0, 2, 1))       # (S symmetric)
             nis[:, t] = np.einsum("bi,bi->b", e, np.linalg.solve(S, e[:, :, None])[:, :, 0])
-            x = x + np.einsum("bij,bj->bi", K, e)
+            step = np.einsum("bij,bj->bi", K, e)
+            x = x + step
+            if apar is not None:        # dv = what the update did to v_x and v_y
+                ew = np.stack([-step[:, idx(1, 1)], step[:, idx(1, 0)], np.zeros(B)], axis=-1) / (d * abs(g))
+                eb = np.einsum("bji,bj->bi", R, ew)
             P = P - K @ (H @ P)
             P = 0.5 * (P + np.transpose(P, (0, 2, 1)))
             est[:, t, 0:3], est[:, t, 6:9] = rot.as_rotvec(), np.einsum("bij,bj->bi", R, gy)
@@ -380,6 +468,8 @@ def estimate_joint_host(imu, q, qd, contact_log, init, trust=None, height=None, 
                     feet[:, t, l, a] = x[:, idx(2 + l, a)]
             bad = ~ok
             est[bad, t], feet[bad, t], sigma[bad, t], nis[bad, t] = np.nan, np.nan, np.nan, np.nan
+            if apar is not None:
+                blog[bad, t] = np.nan
             # predict
             aw = np.einsum("bij,bj->bi", R, sf) + np.array([0.0, 0.0, g])
             Bu = np.zeros((B, 18))
@@ -391,7 +481,11 @@ def estimate_joint_host(imu, q, qd, contact_log, init, trust=None, height=None, 
                 Q[:, 6 + 3 * l:9 + 3 * l] = par["q_f"] * s[:, l, None]
             P = A @ P @ A.T + d * Q[:, :, None] * np.eye(18)
             kap, sh = _kappa(par, sf)
-            wb = gy + kap[:, None] * np.cross(sh, R[:, 2, :])
+            if apar is None:
+                wb = gy + kap[:, None] * np.cross(sh, R[:, 2, :])
+            else:
+                wb = gy + apar["k_s"] * kap[:, None] * np.cross(sh, R[:, 2, :]) + apar["k_v"] * eb
+                bh = np.clip(bh - apar["k_b"] * d * eb, -apar["b_max"], apar["b_max"])
             rot = Rotation.from_rotvec(d * np.einsum("bij,bj->bi", R, wb)) * rot
             qh = rot.as_quat()[:, [3, 0, 1, 2]]
     out_state = np.empty((B, EST_STATE))
@@ -403,4 +497,5 @@ def estimate_joint_host(imu, q, qd, contact_log, init, trust=None, height=None, 
                 out_state[:, _P + 36 * a + 6 * k + j] = P[:, idx(k, a), idx(j, a)]
     out_state[:, _LIVE] = 1.0
     out_state[~ok] = np.nan
-    return {"est": est, "feet": feet, "sigma": sigma, "nis": nis, "state": out_state}
+    res = {"est": est, "feet": feet, "sigma": sigma, "nis": nis, "state": out_state}
+    return res if apar is None else dict(res, gyro_bias=blog, att_state=_att_state(bh, eb, ok))

@@ -345,7 +345,7 @@ def rollout_slip_host(oracle_engine, x, ref, feet, legs, gait, stand, gain, tick
 def rollout_observe_host(oracle_engine, x, ref, feet, legs, gait, stand, gain, tick, mu, T, step_height, ground, foot_mass, slip=None,
                          est_state=None, feed="estimate", est_init=None, height=None, bias=None, noise=None, enc_noise=None, estimator=None,
                          land="rule", drive="limited", body=None, push=None, push_ticks=None, substeps=DEFAULT_SUBSTEPS, gains=None,
-                         leg_substeps=0, inertia=None, actuators=None, gate=None):
+                         leg_substeps=0, inertia=None, actuators=None, gate=None, attitude=None, att_state=None):
     """Closed loop of mpcqp_rollout_observe (include/mpcqp_observe.h, which has the rule) on the CPU checker: `rollout_slip_host`'s loop
     with, per tick, the encoder and gyro rows read off the live state, one row of `estimator.estimate_track_host` on est_state [B,131]
     (None: every filter starts, from est_init [B,12] or the robot's x) and, once the slip rule has given the applied forces, the
@@ -355,6 +355,9 @@ def rollout_observe_host(oracle_engine, x, ref, feet, legs, gait, stand, gain, t
     [B,T,4,3], "est" [B,T,12], "feet_est" [B,T,4,3], "sigma" [B,T,6], "nis" [B,T] and "est_state" [B,131].
     gate: None, or a dict of estimator.gate_row's fields ({} = the defaults) for mpcqp_rollout_observe_gated (include/mpcqp_gate.h): the
     row's trust is the clock's gated on the legs' velocity innovations, and the result has "trust" [B,T,4].
+    attitude: None, or a dict of estimator.attitude_row's fields ({} = the defaults) for mpcqp_rollout_observe_aided
+    (include/mpcqp_attitude.h), with att_state [B,8] or None (zeros): the rows are `estimate_track_host`'s with attitude=, the controller
+    reads the aided estimate, and the result has "gyro_bias" [B,T,3] and "att_state" [B,8].
     The device uses every sensor value, and a stance foot's slip velocity in its encoder row, as its I/O type holds it; nothing is rounded
     here, which is that rule only because the checker's I/O type is fp64: this is the counterpart of an fp64-I/O handle."""
     if drive not in ("ideal", "limited"):
@@ -368,7 +371,10 @@ def rollout_observe_host(oracle_engine, x, ref, feet, legs, gait, stand, gain, t
              "slip": np.zeros((B, 4, 2)) if slip is None else _f64(slip).reshape(B, 4, 2).copy()}
     opt = lambda a: None if a is None else _f64(a)
     observe = {"feed": feed, "state": None if est_state is None else _f64(est_state).copy(), "init": opt(est_init), "height": opt(height),
-               "bias": opt(bias), "noise": opt(noise), "enc_noise": opt(enc_noise), "estimator": estimator, "gate": gate}
+               "bias": opt(bias), "noise": opt(noise), "enc_noise": opt(enc_noise), "estimator": estimator, "gate": gate,
+               "attitude": attitude, "att_state": None if attitude is None else (np.zeros((B, 8)) if att_state is None else _f64(att_state).copy())}
+    if attitude is None and att_state is not None:
+        raise ValueError("att_state needs attitude")
     return _rollout_legs_loop(oracle_engine, x, ref, feet, legs, gait, stand, gain, tick, mu, T, step_height, land, body, push, push_ticks,
                               substeps, gains, leg_substeps, inertia, drive, ground, actuators, state, observe)
 
@@ -400,7 +406,7 @@ def _observe_sense(ob, t, x, ref, feet, legs, slip, contact, gait, tick, stand, 
         ob["init"] = x[:, :12].copy()
     imu = np.concatenate([gyro, np.zeros((B, 3))], axis=-1)[:, None]
     row = _est.estimate_track_host(imu, q[:, None], qd[:, None], contact[:, None], ob["init"], height=ob["height"], state=ob["state"],
-                                   estimator=ob["estimator"], delta=delta, gate=ob["gate"])
+                                   estimator=ob["estimator"], delta=delta, gate=ob["gate"], attitude=ob["attitude"], att_state=ob["att_state"])
     return q, qd, gyro, row["est"][:, 0], row["feet"][:, 0]
 
 
@@ -416,8 +422,11 @@ def _observe_predict(ob, t, out, x, forces, feet, contact, q, qd, gyro, bd, wr, 
     with np.errstate(invalid="ignore"):
         imu = np.where(np.isfinite(sf).all(-1)[:, None], np.concatenate([gyro, sf], axis=-1), np.nan)
     row = _est.estimate_track_host(imu[:, None], q[:, None], qd[:, None], contact[:, None], ob["init"], height=ob["height"], state=ob["state"],
-                                   estimator=ob["estimator"], delta=delta, gate=ob["gate"])
+                                   estimator=ob["estimator"], delta=delta, gate=ob["gate"], attitude=ob["attitude"], att_state=ob["att_state"])
     ob["state"] = row["state"]
+    if ob["attitude"] is not None:
+        ob["att_state"] = row["att_state"]
+        out["gyro_bias"][:, t] = row["gyro_bias"][:, 0]
     if ob["gate"] is not None:
         out["trust"][:, t] = row["trust"][:, 0]
     out["imu"][:, t], out["q_enc"][:, t], out["qd_enc"][:, t] = imu, q, qd
@@ -458,6 +467,8 @@ def _rollout_legs_loop(oracle_engine, x, ref, feet, legs, gait, stand, gain, tic
                     **{k: np.zeros((B, T, 4, 3)) for k in ("q_enc", "qd_enc", "feet_est")}})
         if observe["gate"] is not None:
             out["trust"] = np.zeros((B, T, 4))
+        if observe["attitude"] is not None:
+            out["gyro_bias"] = np.zeros((B, T, 3))
     for t in range(T):
         e = phase_expand_host(x, ref, feet, gait, tick, stand, gain, N, delta)
         xc = x
@@ -522,7 +533,8 @@ def _rollout_legs_loop(oracle_engine, x, ref, feet, legs, gait, stand, gain, tic
             slide["slip"] = np.where(td[..., None], 0.0, dv["slip"])
     return {"x": x, "ref": ref, "tick": tick, "feet": feet, "legs": legs, "actual": actual, "desired": desired, "forces": forces,
             "solved": solved, "feet_log": feet_log, "contact_log": contact_log, **out,
-            **({} if slide is None else {"slip": slide["slip"]}), **({} if observe is None else {"est_state": observe["state"]})}
+            **({} if slide is None else {"slip": slide["slip"]}), **({} if observe is None else {"est_state": observe["state"]}),
+            **({} if observe is None or observe["attitude"] is None else {"att_state": observe["att_state"]})}
 
 
 def make_phase_batch(B, names=("trot", "bound"), period=12, seed=20251018, mus=(0.5, 0.7, 1.0), v_ref=(0.18, 0.0, 0.0), theta_dot=0.0,
