@@ -16,7 +16,7 @@
  * Not built: accelerometer bias states (a given bias is read as it is; a gyro-bias state and an orientation steered by the velocity
  * update are mpcqp_attitude.h), contact detection from forces (trust is given;
  * gating it on the legs' velocity innovations is mpcqp_gate.h), an IMU off the CoM, telling the MPC the estimate's covariance.  (The
- * estimate inside a roll-out's tick loop is mpcqp_observe.h.)
+ * estimate inside a roll-out's tick loop is mpcqp_observe.h; an external wrench estimated from a roll-out's logs is mpcqp_disturb.h.)
  */
 #ifndef MPCQP_ESTIMATE_H_
 #define MPCQP_ESTIMATE_H_

@@ -20,6 +20,7 @@
  *
  * Invalid rows: a non-finite entry, m <= 0, an inertia <= 0, f_min < 0 or f_max < f_min.  Such a row is kept as NaN and every
  * solve reports MPCQP_STATUS_NONFINITE with zero outputs for that QP; no other QP changes (the `body` rule of mpcqp_sim.h).
+ * (A constant external wrench per robot, which the shift rule of mpcqp_disturb.h scales by this row's 1 / m and 1 / I, is set there.)
  */
 #ifndef MPCQP_MODEL_H_
 #define MPCQP_MODEL_H_

@@ -31,7 +31,8 @@
  *            the end; both conversions use a series below an angle of 1e-3 (exact in the limit 0) and atan2 near pi.
  *            substeps = 0 means 10; substeps < 0 or > 1000 is MPCQP_EINVAL.
  *   wrench   push / wrench rows are (F_x, F_y, F_z, tau_x, tau_y, tau_z): a world-frame force (N) at the CoM and a world-frame
- *            torque about the CoM (N m).
+ *            torque about the CoM (N m).  The plant's push is not told to the MPC; rows of the same layout that are, and an observer
+ *            that estimates them from a roll-out's logs, are mpcqp_disturb.h.
  */
 #ifndef MPCQP_SIM_H_
 #define MPCQP_SIM_H_

@@ -1,5 +1,5 @@
 """ctypes binding of the C-ABI declared in include/mpcqp.h and its product-only extensions include/mpcqp_plan.h, mpcqp_sim.h, mpcqp_model.h,
-mpcqp_joints.h, mpcqp_actuators.h, mpcqp_slip.h, mpcqp_estimate.h, mpcqp_observe.h and mpcqp_gate.h.
+mpcqp_joints.h, mpcqp_actuators.h, mpcqp_slip.h, mpcqp_estimate.h, mpcqp_observe.h, mpcqp_gate.h, mpcqp_attitude.h and mpcqp_disturb.h.
 
 The product path loads ``csrc/libmpcqp.so`` (hand-written HIP for gfx950) and nothing else: if that library is
 missing or cannot be loaded, importing the engine raises -- there is no CPU fallback.  The binding itself is
@@ -97,6 +97,12 @@ class MpcQpTrustGate(ctypes.Structure):
 class MpcQpAttitude(ctypes.Structure):
     """Mirror of struct MpcQpAttitude (include/mpcqp_attitude.h): the gains of the estimator's velocity-aided attitude rule."""
     _fields_ = [("size", c_uint32), ("k_s", c_double), ("k_v", c_double), ("k_b", c_double), ("b_max", c_double)]
+    FIELDS = tuple(name for name, _ in _fields_[1:])
+
+
+class MpcQpWrenchObserver(ctypes.Structure):
+    """Mirror of struct MpcQpWrenchObserver (include/mpcqp_disturb.h): the wrench observer's gravity, gain and clamps."""
+    _fields_ = [("size", c_uint32), ("gravity", c_double), ("kappa", c_double), ("f_lim", c_double), ("t_lim", c_double)]
     FIELDS = tuple(name for name, _ in _fields_[1:])
 
 
@@ -247,6 +253,21 @@ ATTITUDE_ABI = {
 ATTITUDE_SYMBOLS = tuple(row[0] for row in ATTITUDE_ABI[ATTITUDE_HEADER])
 ATT_STATE = 8     # include/mpcqp_attitude.h, MPCQP_ATT_STATE: doubles per robot of the attitude state
 AIDED_GATE = 1    # include/mpcqp_attitude.h, MPCQP_AIDED_GATE
+# include/mpcqp_disturb.h, the disturbance wrench rows of the MPC and the wrench observer, likewise: `has_disturb`.  The table calls are
+# mpcqp_model.h's rows under their own names.
+DISTURB_HEADER = "mpcqp_disturb.h"
+_OBS = ctypes.POINTER(MpcQpWrenchObserver)
+DISTURB_ABI = {
+    DISTURB_HEADER: (  # per-robot disturbance wrench rows and the observer over a roll-out's logs
+        ("mpcqp_set_disturbance", c_int, ABI["mpcqp_model.h"][0][2]),
+        ("mpcqp_clear_disturbance", c_int, ABI["mpcqp_model.h"][1][2]),
+        ("mpcqp_disturbance_shift", c_int, (_P, _I64, _P, _P, _P, _P)),
+        ("mpcqp_default_wrench_observer", c_int, (_OBS,)),
+        ("mpcqp_disturbance_track", c_int, (_P, _I64, _I32, _P, _P, _P, _P, _OBS, _P, _P, _P, _P)),
+    ),
+}
+DISTURB_SYMBOLS = tuple(row[0] for row in DISTURB_ABI[DISTURB_HEADER])
+DIST_STATE = 40   # include/mpcqp_disturb.h, MPCQP_DIST_STATE: doubles per robot of the observer's state
 # The swing-leg plant of include/mpcqp_joints.h came after the rest of that header: a product library built before it still has the
 # header's other calls (`has_joints`) and is told apart by `has_legsim`.
 LEGSIM_SYMBOLS = ("mpcqp_leg_accel", "mpcqp_swing_track")
@@ -268,8 +289,8 @@ DRIVE_SLIDING = 128   # include/mpcqp_slip.h, MPCQP_DRIVE_SLIDING: the stance fo
 
 class Library:
     """A loaded shared object exporting the mpcqp C-ABI.  `has_plan`, `has_sim`, `has_model`, `has_joints`, `has_actuators`, `has_slip`,
-    `has_estimate`, `has_observe`, `has_gate` and `has_attitude` say whether it exports all of include/mpcqp_plan.h, mpcqp_sim.h, mpcqp_model.h,
-    mpcqp_joints.h, mpcqp_actuators.h, mpcqp_slip.h, mpcqp_estimate.h, mpcqp_observe.h, mpcqp_gate.h and mpcqp_attitude.h (of mpcqp_joints.h: all but LEGSIM_SYMBOLS, which `has_legsim`
+    `has_estimate`, `has_observe`, `has_gate`, `has_attitude` and `has_disturb` say whether it exports all of include/mpcqp_plan.h, mpcqp_sim.h, mpcqp_model.h,
+    mpcqp_joints.h, mpcqp_actuators.h, mpcqp_slip.h, mpcqp_estimate.h, mpcqp_observe.h, mpcqp_gate.h, mpcqp_attitude.h and mpcqp_disturb.h (of mpcqp_joints.h: all but LEGSIM_SYMBOLS, which `has_legsim`
     answers for; of mpcqp_sim.h: all but LEGROLL_SYMBOLS, SCORE_SYMBOLS and DRIVE_SYMBOLS, `has_legroll`, `has_score` and `has_drive`).  An
     extension header's calls are bound only when the library
     has them all; `partial=True` binds whichever it has (an older build of the product library, in a comparison tool)."""
@@ -284,7 +305,7 @@ class Library:
         self.has_legroll = all(hasattr(self.lib, name) for name in LEGROLL_SYMBOLS)
         self.has_score = all(hasattr(self.lib, name) for name in SCORE_SYMBOLS)
         self.has_drive = all(hasattr(self.lib, name) for name in DRIVE_SYMBOLS)
-        for header, rows in {**ABI, **ACTUATORS_ABI, **SLIP_ABI, **ESTIMATE_ABI, **OBSERVE_ABI, **GATE_ABI, **ATTITUDE_ABI}.items():
+        for header, rows in {**ABI, **ACTUATORS_ABI, **SLIP_ABI, **ESTIMATE_ABI, **OBSERVE_ABI, **GATE_ABI, **ATTITUDE_ABI, **DISTURB_ABI}.items():
             have = header == CORE_HEADER or all(hasattr(self.lib, row[0]) for row in rows if row[0] not in _GATED)
             if header != CORE_HEADER:
                 setattr(self, "has_" + header[len("mpcqp_"):-len(".h")], have)
@@ -341,6 +362,17 @@ class Library:
         rc = fn(ctypes.byref(row))
         if rc != 0:
             raise MpcQpError(f"mpcqp_default_attitude failed: {rc}")
+        return row
+
+    def default_wrench_observer(self) -> "MpcQpWrenchObserver":
+        """The wrench observer's default parameters (include/mpcqp_disturb.h, mpcqp_default_wrench_observer; product library only)."""
+        fn, header, _ = self.calls["mpcqp_default_wrench_observer"]
+        if fn is None:
+            raise MpcQpError(f"mpcqp_default_wrench_observer: {self.path} does not export include/{header} (product library only)")
+        row = MpcQpWrenchObserver()
+        rc = fn(ctypes.byref(row))
+        if rc != 0:
+            raise MpcQpError(f"mpcqp_default_wrench_observer failed: {rc}")
         return row
 
     def default_config(self, **overrides) -> MpcQpConfig:
@@ -585,6 +617,22 @@ class Engine:
     def clear_models(self):
         """mpcqp_clear_models (include/mpcqp_model.h): back to the configuration's m, Ibody_inv, f_min, f_max."""
         self._call("mpcqp_clear_models")
+
+    def set_disturbance_ptr(self, B, rows, stream=0):
+        """mpcqp_set_disturbance (include/mpcqp_disturb.h): `rows` is the address of an fp64 [B,6] device table."""
+        self._call("mpcqp_set_disturbance", B, rows, stream)
+
+    def clear_disturbance(self):
+        """mpcqp_clear_disturbance (include/mpcqp_disturb.h): back to no disturbance for every QP."""
+        self._call("mpcqp_clear_disturbance")
+
+    def disturbance_shift_ptr(self, B, x0, xdes, out, stream=0):
+        """mpcqp_disturbance_shift (include/mpcqp_disturb.h): out = xdes - s with the table that is set."""
+        self._call("mpcqp_disturbance_shift", B, x0, xdes, out, stream)
+
+    def disturbance_track_ptr(self, B, T, actual, forces, feet, body, state, dist, resid, observer=None, stream=0):
+        """The wrench observer over the rows of a log (include/mpcqp_disturb.h, mpcqp_disturbance_track)."""
+        self._call("mpcqp_disturbance_track", B, T, actual, forces, feet, body, observer, state, dist, resid, stream)
 
     def set_actuators_ptr(self, B, act, stream=0):
         """mpcqp_set_actuators (include/mpcqp_actuators.h): `act` is the address of an fp64 [B,9] device table."""

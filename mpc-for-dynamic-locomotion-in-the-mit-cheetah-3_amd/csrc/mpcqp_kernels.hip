@@ -4,7 +4,7 @@
 // CasADi Opti('conic') -> OSQP on the QP of src/mpc.py:58-173, filled at src/mpc.py:242-255, solved at :258.
 //
 // This translation unit is the C-ABI of include/mpcqp.h, mpcqp_plan.h, mpcqp_sim.h, mpcqp_model.h, mpcqp_joints.h, mpcqp_actuators.h, mpcqp_slip.h,
-// mpcqp_estimate.h, mpcqp_observe.h, mpcqp_gate.h and mpcqp_attitude.h,
+// mpcqp_estimate.h, mpcqp_observe.h, mpcqp_gate.h, mpcqp_attitude.h and mpcqp_disturb.h,
 // in three parts: the handle; its host helpers in one anonymous namespace, in order of use (errors, I/O-type dispatch, the solve, workspaces,
 // the device guard and the launch tail `on_device`, grids, the policy behind the configuration's defaults, the engine's tables, the roll-out
 // loops, the leg rows, the row tables); one extern "C" block of entry points, each its own checks and its own launches.  The device code is in
@@ -28,6 +28,8 @@
 //                        helpers, written once
 //   mpcqp_observe.h      sensors and that filter inside the slip roll-out's tick loop, without and with the gate: the encoder row and
 //                        two kernels that call mpcqp_estimate.h's helpers around a tick
+//   mpcqp_disturb.h      per-robot disturbance wrench rows: the kernels in front of and behind a solve that shift xdes and add the shift back
+//                        to the predicted states, and the wrench observer over a roll-out's logs
 // DESIGN.md has the derivations.
 
 #include "mpcqp_wrench.h"
@@ -44,6 +46,7 @@
 #include "mpcqp_score.h"
 #include "mpcqp_estimate.h"
 #include "mpcqp_observe.h"
+#include "mpcqp_disturb.h"
 #include "../../include/mpcqp_gate.h"
 #include "../../include/mpcqp_attitude.h"
 
@@ -54,6 +57,9 @@
 #include <new>
 #include <type_traits>
 
+#ifndef MPCQP_DIST_LANE_PER_ELEMENT   // (measurement builds only: the shift and add-back kernels with one lane per element, mpcqp_disturb.h)
+#define MPCQP_DIST_LANE_PER_ELEMENT 0
+#endif
 #ifndef MPCQP_DIAG_LDSPAD   // (diagnostic builds only: dynamic LDS that limits the resident workgroups per CU, profiles/r03f_occupancy_study.txt)
 #define MPCQP_DIAG_LDSPAD 0
 #endif
@@ -95,6 +101,10 @@ struct mpcqp_engine {
   double* act_mem = nullptr;     // per-robot actuator rows (include/mpcqp_actuators.h): the converted table [act_cap][ACT_ROW]
   int64_t act_B = 0;          // rows of the table that is set; 0 = none, every clamp reads the call's MpcQpLegInertia.tau_max
   int64_t act_cap = 0;
+  double* dist_mem = nullptr;    // per-robot disturbance wrench rows (include/mpcqp_disturb.h): the converted table [dist_cap][DIST_ROW]
+  int64_t dist_B = 0;         // rows of the table that is set; 0 = none, a solve launches what it launches without the feature
+  int64_t dist_cap = 0;
+  void* dshift_mem = nullptr;    // ... and the shifted xdes [dist_cap][N+1][13] in the I/O type that a solve reads while a table is set
   bool timed = false;
   char err[512];
 };
@@ -225,14 +235,61 @@ FastIn<T> gait_in(const void* x0, const void* mu, const void* ref, const void* f
   return in;
 }
 
-// The solve proper, shared by every entry point that solves: picks the engine and launches.  No checks, no events; the caller has
-// reserved the workspace for B (reserve_workspace) and holds the device.
+dim3 blocks(int64_t n, int per = 256);   // (with the launch grids, below)
+
+// Picks the engine and launches it.
 template <typename T>
-hipError_t enqueue_solve(mpcqp_engine* h, int64_t B, const FastIn<T>& in, T* u, T* X, int32_t* status, int32_t* iters, float* res,
-                         hipStream_t st) {
+hipError_t enqueue_engine(mpcqp_engine* h, int64_t B, const FastIn<T>& in, T* u, T* X, int32_t* status, int32_t* iters, float* res,
+                          hipStream_t st) {
   if (!wrench_serves(h->cfg)) return launch_stage<T>(h, B, in, u, X, status, iters, res, st);
   if (h->cfg.N == 10) return launch_wrench<T, 10>(h, B, in, u, X, status, iters, res, st);
   return launch_wrench<T, 20>(h, B, in, u, X, status, iters, res, st);
+}
+
+// What the shift rule of include/mpcqp_disturb.h takes from the configuration, and the model table it reads when one is set.
+DistCfg dist_cfg(const mpcqp_engine* h) {
+  return {h->cfg.delta, h->dev.theta, h->dev.inv_m, {h->dev.Ib[0], h->dev.Ib[1], h->dev.Ib[2]}};
+}
+const double* model_table(const mpcqp_engine* h) { return h->model_B > 0 ? h->model_mem : nullptr; }
+
+// The shift kernel on B robots: out = xdes - s.
+template <typename T>
+void launch_disturb_shift(const mpcqp_engine* h, int64_t B, const T* x0, const T* xdes, T* out, hipStream_t st) {
+  const int64_t rows = B * (h->cfg.N + 1);
+#if MPCQP_DIST_LANE_PER_ELEMENT
+  hipLaunchKernelGGL((mpcqp_disturb_element_kernel<T, false>), blocks(rows * 13), dim3(256), 0, st, (const double*)h->dist_mem, model_table(h),
+                     dist_cfg(h), x0, xdes, out, h->cfg.N + 1, rows * 13);
+#else
+  hipLaunchKernelGGL((mpcqp_disturb_shift_kernel<T>), blocks(rows), dim3(256), 0, st, (const double*)h->dist_mem, model_table(h), dist_cfg(h), x0,
+                     xdes, out, h->cfg.N + 1, rows);
+#endif
+}
+
+// The solve proper, shared by every entry point that solves and every roll-out's tick.  No checks, no events; the caller has
+// reserved the workspace for B (reserve_workspace) and holds the device.  This is the single hook of the disturbance table
+// (include/mpcqp_disturb.h): while one is set -- the caller has matched its size against B -- the solve reads xdes - s from the
+// engine's buffer, written here before anything reads in.xdes (the dispatch-order pre-pass is inside launch_wrench), and s is added
+// to X behind it.  Without a table this is enqueue_engine and nothing else.
+template <typename T>
+hipError_t enqueue_solve(mpcqp_engine* h, int64_t B, const FastIn<T>& in, T* u, T* X, int32_t* status, int32_t* iters, float* res,
+                         hipStream_t st) {
+  if (h->dist_B == 0) return enqueue_engine<T>(h, B, in, u, X, status, iters, res, st);
+  FastIn<T> shifted = in;
+  shifted.xdes = (const T*)h->dshift_mem;
+  launch_disturb_shift<T>(h, B, in.x0, in.xdes, (T*)h->dshift_mem, st);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  e = enqueue_engine<T>(h, B, shifted, u, X, status, iters, res, st);
+  if (e != hipSuccess || !X) return e;
+  const int64_t rows = B * (h->cfg.N + 1);
+#if MPCQP_DIST_LANE_PER_ELEMENT
+  hipLaunchKernelGGL((mpcqp_disturb_element_kernel<T, true>), blocks(rows * 13), dim3(256), 0, st, (const double*)h->dist_mem, model_table(h),
+                     dist_cfg(h), in.x0, (const T*)X, X, h->cfg.N + 1, rows * 13);
+#else
+  hipLaunchKernelGGL((mpcqp_disturb_addback_kernel<T>), blocks(rows), dim3(256), 0, st, (const double*)h->dist_mem, model_table(h), dist_cfg(h),
+                     in.x0, X, h->cfg.N + 1, rows);
+#endif
+  return hipGetLastError();
 }
 
 // The event pair behind mpcqp_last_kernel_ms: an entry point records ev0 in front of its first launch and ev1 behind its last.
@@ -268,11 +325,12 @@ bool grow(P*& buf, size_t bytes, size_t zero = 0) {
   return true;
 }
 
-// The handle's two per-robot row tables (include/mpcqp_model.h, mpcqp_actuators.h) behind one view: the converted rows, how many of
+// The handle's three per-robot row tables (include/mpcqp_model.h, mpcqp_actuators.h, mpcqp_disturb.h) behind one view: the converted rows, how many of
 // them are set (0 = no table) and how many the buffer holds.  (A view, not a member: launch_wrench and launch_stage read model_B by name.)
 struct RowTable { double*& mem; int64_t& B; int64_t& cap; };
 RowTable models(mpcqp_engine* h) { return {h->model_mem, h->model_B, h->model_cap}; }
 RowTable actuators(mpcqp_engine* h) { return {h->act_mem, h->act_B, h->act_cap}; }
+RowTable disturbances(mpcqp_engine* h) { return {h->dist_mem, h->dist_B, h->dist_cap}; }
 // The converted actuator rows, or null when none are set (launch_act)
 const double* act_table(const mpcqp_engine* h) { return h->act_B > 0 ? h->act_mem : nullptr; }
 
@@ -282,7 +340,11 @@ int table_match(mpcqp_engine* h, const RowTable& t, const char* noun, int64_t B,
   snprintf(h->err, sizeof(h->err), "%s: batch size %lld, but the %s table has %lld rows", who, (long long)B, noun, (long long)t.B);
   return MPCQP_EINVAL;
 }
-int models_match(mpcqp_engine* h, int64_t B, const char* who) { return table_match(h, models(h), "model", B, who); }
+// ... of an entry point that solves: the two tables a solve reads, the model rows and the disturbance rows.
+int solve_tables_match(mpcqp_engine* h, int64_t B, const char* who) {
+  if (const int rc = table_match(h, models(h), "model", B, who)) return rc;
+  return table_match(h, disturbances(h), "disturbance", B, who);
+}
 int actuators_match(mpcqp_engine* h, int64_t B, const char* who) { return table_match(h, actuators(h), "actuator", B, who); }
 
 // Room for B rows of `width` doubles, once per size like the mpcqp_reserve workspace (grow waits for the device before it frees the old
@@ -415,7 +477,7 @@ int on_device(mpcqp_engine* h, const char* what, F&& f) {
 
 // Launch grids: `per` threads a block over n threads, and the three that recur -- one thread per leg of `rows` robots or log rows, one per
 // robot (the roll-outs' advance), one per tuple element (their expand).
-dim3 blocks(int64_t n, int per = 256) { return dim3((unsigned)((n + per - 1) / per)); }
+dim3 blocks(int64_t n, int per) { return dim3((unsigned)((n + per - 1) / per)); }
 dim3 leg_grid(int64_t rows) { return blocks(4 * rows); }
 dim3 advance_grid(int64_t B) { return blocks(B); }
 dim3 expand_grid(int64_t B, int N) { return blocks(B * (int64_t)tuple_elems(N)); }
@@ -622,7 +684,7 @@ int build_wrench_tables(mpcqp_engine* e) {
 }
 
 void free_engine(mpcqp_engine* h) {
-  for (void* p : {(void*)h->dcfg, (void*)h->order_mem, (void*)h->dual_mem, (void*)h->model_mem, (void*)h->act_mem, h->gait_mem, h->roll_mem,
+  for (void* p : {(void*)h->dcfg, (void*)h->order_mem, (void*)h->dual_mem, (void*)h->model_mem, (void*)h->act_mem, (void*)h->dist_mem, h->dshift_mem, h->gait_mem, h->roll_mem,
                   (void*)h->plan_ws, (void*)h->wr_K, (void*)h->wr_kinv32, (void*)h->wr_kinv64, (void*)h->wr_klane32, (void*)h->wr_klane64,
                   (void*)h->stage_ws})
     if (p) (void)hipFree(p);
@@ -877,7 +939,7 @@ int rollout_legs_run(mpcqp_handle h, const char* who, int64_t B, int32_t T, void
   LegInrDev r;
   if (const int rc = leg_rows(h, who, geo, inr, true, g, r)) return rc;
   if (B == 0 || T == 0) return MPCQP_OK;
-  if (const int rc = models_match(h, B, who)) return rc;
+  if (const int rc = solve_tables_match(h, B, who)) return rc;
   if (const int rc = actuators_match(h, B, who)) return rc;
   const int nl = swing_substeps(h->cfg.delta, leg_substeps);
   const RolloutPlantArgs plant = {body, push, push ? push_ticks : nullptr, n};
@@ -999,6 +1061,18 @@ int attitude_row(mpcqp_handle h, const char* who, int32_t flags, const MpcQpAtti
   for (const double v : {att->k_s, att->k_v, att->k_b, att->b_max})
     if (!std::isfinite(v) || !(v >= 0)) return bad(h, who, "attitude: k_s, k_v, k_b and b_max must be finite and non-negative");
   a = {att->k_s, att->k_v, att->k_b * e.d, att->b_max, e.d * std::fabs(e.g)};
+  return MPCQP_OK;
+}
+
+// The wrench observer's parameters of include/mpcqp_disturb.h (null: the defaults), checked and with the handle's delta.
+int observer_row(mpcqp_handle h, const char* who, const MpcQpWrenchObserver* par, DistPar& e) {
+  MpcQpWrenchObserver dflt;
+  if (!par) { (void)mpcqp_default_wrench_observer(&dflt); par = &dflt; }
+  if (par->size != sizeof(MpcQpWrenchObserver)) return bad(h, who, "wrench observer struct size mismatch");
+  if (!std::isfinite(par->gravity) || !(par->gravity < 0)) return bad(h, who, "wrench observer: gravity must be finite and negative");
+  if (!(par->kappa >= 0 && par->kappa <= 1)) return bad(h, who, "wrench observer: kappa must be in [0, 1]");
+  if (!(par->f_lim >= 0) || !(par->t_lim >= 0)) return bad(h, who, "wrench observer: f_lim and t_lim must be non-negative (infinity: no clamp)");
+  e = {par->gravity, par->kappa, par->f_lim, par->t_lim, h->cfg.delta};
   return MPCQP_OK;
 }
 
@@ -1181,7 +1255,7 @@ int mpcqp_solve_batch(mpcqp_handle h, int64_t B, const void* x0, const void* r, 
   if (B < 0 || B > 0x7fffffff) return fail(h, MPCQP_EINVAL, "mpcqp_solve_batch: batch size out of range");
   if (B > 0 && (!x0 || !r || !contact || !xdes || !mu || !u_out || !status || !iters))
     return fail(h, MPCQP_EINVAL, "mpcqp_solve_batch: null buffer");
-  if (B > 0) if (const int rc = models_match(h, B, "mpcqp_solve_batch")) return rc;
+  if (B > 0) if (const int rc = solve_tables_match(h, B, "mpcqp_solve_batch")) return rc;
   GUARD(h);
   if (reserve_workspace(h, B) != MPCQP_OK) return fail(h, MPCQP_ENOMEM, "mpcqp_solve_batch: workspace allocation failed");
   hipStream_t st = (hipStream_t)stream;
@@ -1203,7 +1277,7 @@ int mpcqp_solve_batch_gait_steps(mpcqp_handle h, int64_t B, int32_t S, const voi
   if (B > 0 && (!x0 || !ref || !feet0 || !footholds || !gait || !feet_id || !mu || !u_out || !status || !iters))
     return fail(h, MPCQP_EINVAL, "mpcqp_solve_batch_gait_steps: null buffer");
   if (B == 0) return mpcqp_solve_batch(h, 0, x0, nullptr, nullptr, nullptr, mu, u_out, X_out, status, iters, res, stream);
-  if (const int rc = models_match(h, B, "mpcqp_solve_batch_gait_steps")) return rc;
+  if (const int rc = solve_tables_match(h, B, "mpcqp_solve_batch_gait_steps")) return rc;
   hipStream_t st = (hipStream_t)stream;
   return solve_expanded(h, B, x0, mu, u_out, X_out, status, iters, res, st, "mpcqp_solve_batch_gait_steps: workspace allocation failed",
                         "gait expansion / solve kernel launch", [&](auto tag, const auto& w) {
@@ -1226,7 +1300,7 @@ int mpcqp_rollout(mpcqp_handle h, int64_t B, int32_t T, int32_t S, void* x, void
   if (B < 0 || B > 0x7fffffff || T < 0 || S < 1) return fail(h, MPCQP_EINVAL, "mpcqp_rollout: size out of range");
   if (B > 0 && (!x || !ref || !plan_pos || !plan_feet_id || !plan_meta || !tick || !mu)) return fail(h, MPCQP_EINVAL, "mpcqp_rollout: null buffer");
   if (B == 0 || T == 0) return MPCQP_OK;
-  if (const int rc = models_match(h, B, "mpcqp_rollout")) return rc;
+  if (const int rc = solve_tables_match(h, B, "mpcqp_rollout")) return rc;
   return rollout_run(h, B, T, S, x, ref, plan_pos, plan_feet_id, plan_meta, tick, mu, actual, desired, forces, solved, stream, nullptr);
 }
 
@@ -1242,7 +1316,7 @@ int mpcqp_rollout_plant(mpcqp_handle h, int64_t B, int32_t T, int32_t S, void* x
   if (B > 0 && (!x || !ref || !plan_pos || !plan_feet_id || !plan_meta || !tick || !mu))
     return fail(h, MPCQP_EINVAL, "mpcqp_rollout_plant: null buffer");
   if (B == 0 || T == 0) return MPCQP_OK;
-  if (const int rc = models_match(h, B, "mpcqp_rollout_plant")) return rc;
+  if (const int rc = solve_tables_match(h, B, "mpcqp_rollout_plant")) return rc;
   const RolloutPlantArgs plant = {body, push, push ? push_ticks : nullptr, n};
   return rollout_run(h, B, T, S, x, ref, plan_pos, plan_feet_id, plan_meta, tick, mu, actual, desired, forces, solved, stream, &plant);
 }
@@ -1269,7 +1343,7 @@ int mpcqp_solve_batch_phase(mpcqp_handle h, int64_t B, const void* x0, const voi
   if (B > 0 && (!x0 || !ref || !feet || !gait || !tick || !stand || !mu || !u_out || !status || !iters))
     return fail(h, MPCQP_EINVAL, "mpcqp_solve_batch_phase: null buffer");
   if (B == 0) return mpcqp_solve_batch(h, 0, x0, nullptr, nullptr, nullptr, mu, u_out, X_out, status, iters, res, stream);
-  if (const int rc = models_match(h, B, "mpcqp_solve_batch_phase")) return rc;
+  if (const int rc = solve_tables_match(h, B, "mpcqp_solve_batch_phase")) return rc;
   hipStream_t st = (hipStream_t)stream;
   return solve_expanded(h, B, x0, mu, u_out, X_out, status, iters, res, st, "mpcqp_solve_batch_phase: workspace allocation failed",
                         "phase expansion / solve kernel launch", [&](auto tag, const auto& w) {
@@ -1289,7 +1363,7 @@ int mpcqp_rollout_phase(mpcqp_handle h, int64_t B, int32_t T, void* x, void* ref
   if (push && !push_ticks) return fail(h, MPCQP_EINVAL, "mpcqp_rollout_phase: push without push_ticks");
   if (B > 0 && (!x || !ref || !feet || !gait || !stand || !tick || !mu)) return fail(h, MPCQP_EINVAL, "mpcqp_rollout_phase: null buffer");
   if (B == 0 || T == 0) return MPCQP_OK;
-  if (const int rc = models_match(h, B, "mpcqp_rollout_phase")) return rc;
+  if (const int rc = solve_tables_match(h, B, "mpcqp_rollout_phase")) return rc;
   const RolloutPlantArgs plant = {body, push, push ? push_ticks : nullptr, n};
   hipStream_t st = (hipStream_t)stream;
   return rollout_loop(h, "mpcqp_rollout_phase", B, T, x, ref, mu, stream,
@@ -1329,6 +1403,77 @@ int mpcqp_clear_models(mpcqp_handle h) {
   if (he != hipSuccess) return fail(h, MPCQP_EHIP, "mpcqp_clear_models", he);
   h->model_B = 0;
   return MPCQP_OK;
+}
+
+// include/mpcqp_disturb.h.  The table is a kernel argument of the two kernels around a solve, so only the host side of the handle knows it.
+int mpcqp_set_disturbance(mpcqp_handle h, int64_t B, const double* rows, void* stream) {
+  if (!h) return MPCQP_EINVAL;
+  if (B <= 0 || B > 0x7fffffff) return fail(h, MPCQP_EINVAL, "mpcqp_set_disturbance: batch size out of range");
+  if (!rows) return fail(h, MPCQP_EINVAL, "mpcqp_set_disturbance: null disturbance table");
+  GUARD(h);
+  if (h->dist_cap < B) {   // the shifted-xdes buffer first: when it cannot be grown, the table set before stays
+    if (!grow(h->dshift_mem, (size_t)B * (h->cfg.N + 1) * 13 * io_size(h)))
+      return fail(h, MPCQP_ENOMEM, "mpcqp_set_disturbance: buffer allocation failed");
+    if (!table_reserve(disturbances(h), B, DIST_ROW)) {   // (the buffer is larger than the table's rows need: harmless)
+      return fail(h, MPCQP_ENOMEM, "mpcqp_set_disturbance: table allocation failed");
+    }
+  }
+  hipLaunchKernelGGL(mpcqp_disturb_rows_kernel, blocks(B), dim3(256), 0, (hipStream_t)stream, rows, h->dist_mem, B);
+  const int rc = launched(h, "disturbance table kernel launch");
+  h->dist_B = rc == MPCQP_OK ? B : 0;
+  return rc;
+}
+
+int mpcqp_clear_disturbance(mpcqp_handle h) {
+  if (!h) return MPCQP_EINVAL;
+  if (h->dist_B == 0) return MPCQP_OK;
+  GUARD(h);
+  // No stream argument: the solves enqueued so far (on whatever stream) finish with the table, every later one runs without it.
+  const hipError_t he = hipDeviceSynchronize();
+  if (he != hipSuccess) return fail(h, MPCQP_EHIP, "mpcqp_clear_disturbance", he);
+  h->dist_B = 0;
+  return MPCQP_OK;
+}
+
+int mpcqp_disturbance_shift(mpcqp_handle h, int64_t B, const void* x0, const void* xdes, void* out, void* stream) {
+  if (!h) return MPCQP_EINVAL;
+  if (B < 0 || B > 0x7fffffff) return fail(h, MPCQP_EINVAL, "mpcqp_disturbance_shift: batch size out of range");
+  if (h->dist_B == 0) return fail(h, MPCQP_EINVAL, "mpcqp_disturbance_shift: no disturbance table is set");
+  if (B > 0 && (!x0 || !xdes || !out)) return fail(h, MPCQP_EINVAL, "mpcqp_disturbance_shift: null buffer");
+  if (const int rc = solve_tables_match(h, B, "mpcqp_disturbance_shift")) return rc;
+  if (B == 0) return MPCQP_OK;
+  return on_device(h, "disturbance shift kernel launch", [&](auto tag) {
+    using T = decltype(tag);
+    launch_disturb_shift<T>(h, B, (const T*)x0, (const T*)xdes, (T*)out, (hipStream_t)stream);
+  });
+}
+
+int mpcqp_default_wrench_observer(MpcQpWrenchObserver* par) {
+  if (!par) return MPCQP_EINVAL;
+  memset(par, 0, sizeof(*par));
+  par->size = (uint32_t)sizeof(*par);
+  par->gravity = -9.81;
+  par->kappa = 0.2;
+  par->f_lim = INFINITY;
+  par->t_lim = INFINITY;
+  return MPCQP_OK;
+}
+
+int mpcqp_disturbance_track(mpcqp_handle h, int64_t B, int32_t T, const void* actual, const void* forces, const void* feet, const void* body,
+                            const MpcQpWrenchObserver* par, double* state, void* dist, void* resid, void* stream) {
+  const char* who = "mpcqp_disturbance_track";
+  if (!h) return MPCQP_EINVAL;
+  if (B < 0 || B > 0x7fffffff || T < 0 || B * (int64_t)T > 0x1fffffff) return bad(h, who, "size out of range");
+  if (!dist && !resid) return bad(h, who, "no output buffer (dist and resid are both null)");
+  if (B > 0 && T > 0 && (!actual || !forces || !feet)) return bad(h, who, "null buffer (actual, forces, feet)");
+  DistPar e;
+  if (const int rc = observer_row(h, who, par, e)) return rc;
+  if (B == 0 || T == 0) return MPCQP_OK;
+  return on_device(h, "disturbance track kernel launch", [&](auto tag) {
+    using TIO = decltype(tag);
+    hipLaunchKernelGGL((mpcqp_disturb_track_kernel<TIO>), blocks(B), dim3(256), 0, (hipStream_t)stream, (const TIO*)actual, (const TIO*)forces,
+                       (const TIO*)feet, (const TIO*)body, plant_model(h), e, state, (TIO*)dist, (TIO*)resid, B, (int)T);
+  });
 }
 
 // include/mpcqp_actuators.h.  The table is a kernel argument of the ACT instantiations, so only the host side of the handle knows it.

@@ -173,6 +173,56 @@ class MPCBatch:
         """Back to the inertia row's tau_max for every clamp (mpcqp_clear_actuators; waits for the device)."""
         self.engine.clear_actuators()
 
+    def set_disturbance(self, rows, stream=None):
+        """Per-robot disturbance wrench rows (include/mpcqp_disturb.h, mpcqp_set_disturbance, which has the rule): `rows` [B,6] =
+        (F_x, F_y, F_z, tau_x, tau_y, tau_z), a world-frame force at the CoM and torque about it -- the layout of a `push` row --, a
+        float64 tensor on the engine's device or a numpy array (uploaded); mpcqp.disturbance has the row helper and the host
+        counterparts.  Every later solve and every tick of every roll-out of this engine plans robot b under row b (xdes - s goes into
+        the solve, s is added to "X") and must have B robots.  The plant is not told: its push stays `push`.  Asynchronous on `stream`."""
+        self._set_rows(self.engine.set_disturbance_ptr, "rows", rows, 6, stream)
+
+    def clear_disturbance(self):
+        """Back to no disturbance for every QP (mpcqp_clear_disturbance; waits for the device)."""
+        self.engine.clear_disturbance()
+
+    def disturbance_shift(self, x0, xdes, stream=None):
+        """The shift kernel alone (include/mpcqp_disturb.h, mpcqp_disturbance_shift; the host counterpart is disturbance.shift_host):
+        x0 [B,13], xdes [B,N+1,13] -> xdes - s [B,N+1,13] under the table that is set (an error without one).  Asynchronous on `stream`."""
+        B, N = int(x0.shape[0]), self.N
+        check_operands(self.device, (("x0", x0, (B, 13), self.tdtype), ("xdes", xdes, (B, N + 1, 13), self.tdtype)))
+        st = self._stream(stream)
+        out, = self._alloc(stream, ((B, N + 1, 13), self.tdtype))
+        self.engine.disturbance_shift_ptr(B, x0.data_ptr(), xdes.data_ptr(), out.data_ptr(), st.cuda_stream)
+        return out
+
+    def disturbance_track(self, logs, body=None, observer=None, state=None, feet="feet_log", want=("dist", "resid"), stream=None):
+        """The wrench observer over the rows of a roll-out's logs (include/mpcqp_disturb.h, mpcqp_disturbance_track, which has the rule;
+        the host counterpart is disturbance.disturbance_track_host): `logs` with "actual", "forces" [B,T,12] and logs[feet] [B,T,4,3] --
+        the plant's truth, or a dict made of the "est" and "cmd" logs of `rollout_observe` under those names; body [B,7] or None (the
+        engine's model); `observer` None, a dict of disturbance.observer_row's fields or an MpcQpWrenchObserver; state float64 [B,40]
+        advanced IN PLACE (zeros: a fresh observer) or None (a fresh one is made) -> {"dist", "resid" [B,T,6], "state"}; an output not
+        in `want` is None.  Asynchronous on `stream`."""
+        from . import disturbance as _dist
+        torch = _torch()
+        actual = logs.get("actual")
+        if actual is None or actual.dim() != 3:
+            raise ValueError("disturbance_track needs the logs of a roll-out run with log=True")
+        B, T = int(actual.shape[0]), int(actual.shape[1])
+        rows = ((B, T, 6), self.tdtype)
+        check_operands(self.device, (("actual", actual, (B, T, 12), self.tdtype), ("forces", logs.get("forces"), (B, T, 12), self.tdtype),
+                                     (feet, logs.get(feet), (B, T, 4, 3), self.tdtype), ("body", body, (B, 7), self.tdtype),
+                                     ("state", state, (B, _capi.DIST_STATE), torch.float64)), optional=("body", "state"))
+        unknown = set(want) - set(_dist.OUT)
+        if unknown or not want:
+            raise ValueError(f"want must name at least one of {_dist.OUT}, got {tuple(want)}")
+        st = self._stream(stream)
+        if state is None:
+            state, = self._alloc(stream, ((B, _capi.DIST_STATE), torch.float64, True))
+        dist, resid = self._alloc(stream, *[rows if k in want else None for k in _dist.OUT])
+        self.engine.disturbance_track_ptr(B, T, actual.data_ptr(), logs["forces"].data_ptr(), logs[feet].data_ptr(), _ptr(body), state.data_ptr(),
+                                          _ptr(dist), _ptr(resid), _dist.observer_struct(observer), st.cuda_stream)
+        return {"dist": dist, "resid": resid, "state": state}
+
     def solve_batch_gait(self, x0, ref, feet0, footholds, gait, feet_id, mu, want_X=False, stream=None, u_init=None):
         """Gait entry point: contact masks, stance lever arms and x_des are generated on the device (include/mpcqp.h) from S plan steps
         per robot (footholds [B,S,4,3], feet_id [B,S,4]; S = 2 is the original two-step form)."""
