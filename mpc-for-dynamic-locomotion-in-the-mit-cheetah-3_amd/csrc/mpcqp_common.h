@@ -2,6 +2,7 @@
 // policy constants, the element arithmetic of the tuple expansions, and the dispatch-order pre-pass (dearest-expected-first order of a batch that oversubscribes the device).
 #pragma once
 #include "mpcqp_device.h"
+#include "mpcqp_order.h"   // the dispatch-order score: plain C++, also compiled on the host
 
 namespace {
 
@@ -76,90 +77,92 @@ constexpr float WARM_KKT_TOL = 1e-3f;            // (u0, y0) counts as a KKT poi
 
 // ------------------------------------------------------------------------------------------------------ dispatch order
 // Workgroups are handed out in blockIdx order, and the solve time of a QP varies by 7x (one early rho check, up to four
-// ADMM blocks, 1-8 polish steps): with 4096 QPs on 512 workgroup slots the stragglers that start late set the time of
-// the launch (measured 1.49 ms against 1.0 ms of evenly spread work).  A pre-pass therefore sorts the QPs into
-// ORDER_BUCKETS classes of expected cost and the solve kernel takes the dearest class first.  The predictor is the
-// FRICTION DEMAND of the support pattern: for a stage carried by two feet, the horizontal distance d of the com from
-// the line through the feet over the com height h is the friction coefficient a static stance would need, so
-// (d / h) / mu > 1 means saturated cones, a large active set and slow ADMM convergence (two-legged "amble" support at
-// mu = 0.3: 95 % of those QPs trigger the rho adaptation; diagonal "trot" support: 1 %).  Order only: results are per QP.
-constexpr int ORDER_BUCKETS = 16;
+// ADMM blocks, 1-8 polish steps): with 4096 QPs on 2048 workgroup slots the two-round QPs that start in the second fill set
+// the time of the launch (measured 0.32-0.33 ms against 0.25-0.26 ms for the same QPs dispatched dearest-first by their realised
+// cost, profiles/r30_order_predictor.txt).  A pre-pass therefore sorts the QPs into ORDER_BUCKETS classes of expected cost and
+// the solve kernel takes the dearest class first.  The score and its fit live in mpcqp_order.h (plain C++, checked on the
+// host): the log-odds of a second ADMM round from the shape of the support schedule (a horizon that BEGINS in a run of
+// friction-saturated two-legged stages; a four-legged start that goes to two legs early), the friction demand and the commanded
+// horizontal velocity correction over mu.  Order only: results are per QP.
 struct OrderBuf { int* cnt; int* list; int cap; int* head; int* zero; };   // cnt[ORDER_BUCKETS], list[ORDER_BUCKETS][cap], queue head;
                                                                            // zero: the OTHER call's 32 header ints, cleared by this call's pre-pass
+static_assert(ORDER_BUCKETS + 1 <= 32, "class counters and the queue head share a header set of 32 ints");
 
-__device__ __forceinline__ float support_demand(int nst, const float (&fx)[4], const float (&fy)[4], const float (&fz)[4],
-                                                const bool (&st)[4]) {
-  if (nst == 2) {
-    int a = -1, bidx = -1;
-#pragma unroll
-    for (int l = 0; l < 4; ++l) { if (st[l]) { if (a < 0) a = l; else bidx = l; } }
-    const float dx = fx[a] - fx[bidx], dy = fy[a] - fy[bidx];
-    const float d = fabsf(fx[a] * fy[bidx] - fy[a] * fx[bidx]) / fmaxf(sqrtf(dx * dx + dy * dy), 1e-6f);
-    const float h = fmaxf(-0.5f * (fz[a] + fz[bidx]), 1e-3f);
-    return d / h;
-  }
-  if (nst == 1) {
-#pragma unroll
-    for (int l = 0; l < 4; ++l) if (st[l]) return sqrtf(fx[l] * fx[l] + fy[l] * fy[l]) / fmaxf(-fz[l], 1e-3f);
-  }
-  return 0.f;   // three or four feet (or flight): no friction-limited moment balance
-}
-
-// Expected cost of a QP in microseconds above the cheapest one: every stance leg-stage is three pivots in each of the
-// ~2.5 sweeps of a solve (2.2 us), and a unit of friction demand (capped at 2) costs 34 us of extra ADMM blocks and polish
-// steps -- least squares on measured per-QP times of the bench workload (tools/timeline.py; correlation 0.48, enough for
-// the order: the makespan model drops from 1.36 to 1.24 ms, a clairvoyant order reaches 1.19 ms).
-__device__ __forceinline__ int cost_class(float nst, float demand_over_mu) {
-  const float us = 2.2f * nst + 34.f * fminf(demand_over_mu, 2.f);
-  return isfinite(us) ? (int)fminf(us * 0.1f, (float)(ORDER_BUCKETS - 1)) : 0;
-}
-
-// 16 lanes per QP, one stage per lane: the loads of a QP go out together, DPP row reductions take the maximum demand and
-// the stance count, lane 0 files the QP.  The class counters are bumped once per workgroup of 64 QPs (a global atomic
-// per QP on a handful of addresses serialises).
+// 16 lanes per QP, one stage per lane (horizons beyond 16: a lane takes stages k0, k0 + 16): the loads of a QP go out together,
+// ballots collect the rows' two-legged / saturated stage masks, DPP row reductions the maxima and the stance count, lane 0 of the
+// row classes the QP.  The first wave then files the workgroup's 64 QPs: a ballot per class gives each QP its position among
+// the workgroup's QPs of its class IN BATCH ORDER (a prefix count, no atomic) and the class its count, the class counters are
+// bumped once per workgroup (a global atomic per QP on a handful of addresses serialises) -- so the order inside a class is
+// that of the batch within a workgroup, and the workgroups' arrival across them.
 template <typename TIO, int N>
 __global__ void __launch_bounds__(1024)
 mpcqp_order_kernel(const FastIn<TIO> in, const int B, const OrderBuf ob) {
-  __shared__ int lcnt[ORDER_BUCKETS], lbase[ORDER_BUCKETS];
-  if (threadIdx.x < ORDER_BUCKETS) lcnt[threadIdx.x] = 0;
+  static_assert(N <= 32, "one mask bit per stage");
+  __shared__ int lcls[64];
   // Two sets of class counters + queue head alternate between calls: this pre-pass counts into one (cleared by the previous call's
   // pre-pass, whose solve has finished with it: one stream per handle) and clears the other for the next call -- no memset launch.
   if (blockIdx.x == 0 && threadIdx.x < 32 && ob.zero) ob.zero[threadIdx.x] = 0;
-  __syncthreads();
-  const int b = blockIdx.x * 64 + (threadIdx.x >> 4), k0 = threadIdx.x & 15;
-  float score = 0.f, cnt = 0.f;
-  for (int k = k0; k < N && b < B; k += 16) {   // (horizons beyond 16: a lane takes stages k0, k0 + 16, ..)
-    float fx[4], fy[4], fz[4]; bool st[4]; int nst = 0;
-#pragma unroll
-    for (int l = 0; l < 4; ++l) {
-      const TIO* rp = in.r + ((size_t)b * N + k) * 12 + 3 * l;
-      fx[l] = (float)rp[0]; fy[l] = (float)rp[1]; fz[l] = (float)rp[2];
-      st[l] = in.contact[((size_t)b * N + k) * 4 + l] != 0;
-      nst += st[l] ? 1 : 0;
-    }
-    float sc = support_demand(nst, fx, fy, fz, st);
-    if (!isfinite(sc)) sc = 0.f;
-    score = fmaxf(score, sc);
-    cnt += (float)nst;
+  const int q = threadIdx.x >> 4, b = blockIdx.x * 64 + q, k0 = threadIdx.x & 15, row = 16 * (q & 3);
+  const bool live = b < B;
+  float inv_mu = 0.f, vx = 0.f, vy = 0.f;
+  bool bad = false;
+  if (live) {
+    const float mu = (float)in.mu[b];
+    bad = !isfinite(mu);
+    inv_mu = 1.f / fmaxf(fabsf(mu), 1e-3f);
+    vx = (float)in.x0[(size_t)b * 13 + 9]; vy = (float)in.x0[(size_t)b * 13 + 10];
   }
-  score = fmaxf(score, dpp_mov<0xB1>(score));    // max / sum over the row of 16 lanes (all lanes of the wave are active here)
-  score = fmaxf(score, dpp_mov<0x4E>(score));
-  score = fmaxf(score, dpp_mov<0x141>(score));
-  score = fmaxf(score, dpp_mov<0x140>(score));
+  uint32_t two = 0, sat = 0;
+  float dmax = 0.f, hvmax = 0.f, cnt = 0.f;
+#pragma unroll
+  for (int p = 0; p < (N + 15) / 16; ++p) {
+    const int k = k0 + 16 * p;
+    OrderStage s = {0.f, 0.f, 0.f, false, false, false};
+    if (live && k < N) {
+      float r[12]; bool ct[4];
+      const TIO* rp = in.r + ((size_t)b * N + k) * 12;
+#pragma unroll
+      for (int i = 0; i < 12; ++i) r[i] = (float)rp[i];
+#pragma unroll
+      for (int l = 0; l < 4; ++l) ct[l] = in.contact[((size_t)b * N + k) * 4 + l] != 0;
+      const TIO* xk = in.xdes + ((size_t)b * (N + 1) + k + 1) * 13;   // stage k steers towards x_des[k + 1]
+      s = order_stage(r, ct, vx - (float)xk[9], vy - (float)xk[10], inv_mu);
+    }
+    // (all lanes of the wave are here: the ballots and the DPP moves below see every row)
+    const unsigned long long m2 = __ballot(s.two), ms = __ballot(s.sat), mb = __ballot(s.bad);
+    two |= (uint32_t)((m2 >> row) & 0xffffu) << (16 * p);
+    sat |= (uint32_t)((ms >> row) & 0xffffu) << (16 * p);
+    bad = bad || ((mb >> row) & 0xffffu) != 0;
+    dmax = fmaxf(dmax, s.demand); hvmax = fmaxf(hvmax, s.hv); cnt += s.nst;   // (fmaxf drops a NaN: `bad` has it)
+  }
+  dmax = fmaxf(dmax, dpp_mov<0xB1>(dmax));    // max / sum over the row of 16 lanes
+  dmax = fmaxf(dmax, dpp_mov<0x4E>(dmax));
+  dmax = fmaxf(dmax, dpp_mov<0x141>(dmax));
+  dmax = fmaxf(dmax, dpp_mov<0x140>(dmax));
+  hvmax = fmaxf(hvmax, dpp_mov<0xB1>(hvmax));
+  hvmax = fmaxf(hvmax, dpp_mov<0x4E>(hvmax));
+  hvmax = fmaxf(hvmax, dpp_mov<0x141>(hvmax));
+  hvmax = fmaxf(hvmax, dpp_mov<0x140>(hvmax));
   cnt += dpp_mov<0xB1>(cnt);
   cnt += dpp_mov<0x4E>(cnt);
   cnt += dpp_mov<0x141>(cnt);
   cnt += dpp_mov<0x140>(cnt);
-  int bucket = 0, pos = 0;
-  const bool filer = b < B && k0 == 0;
-  if (filer) {
-    bucket = cost_class(cnt * (10.f / N), score / fmaxf(fabsf((float)in.mu[b]), 1e-3f));
-    pos = atomicAdd(&lcnt[bucket], 1);
+  if (k0 == 0) lcls[q] = live ? cost_class(N, two, sat, cnt, dmax, hvmax, bad) : -1;
+  __syncthreads();
+  if (threadIdx.x < 64) {   // the first wave: lane = QP of the workgroup
+    const int lane = threadIdx.x, cls = lcls[lane];
+    int pos = 0, mine = 0;
+#pragma unroll
+    for (int c = 0; c < ORDER_BUCKETS; ++c) {
+      const unsigned long long m = __ballot(cls == c);
+      if (cls == c) pos = __popcll(m & ((1ull << lane) - 1ull));
+      if (lane == c) mine = __popcll(m);
+    }
+    int base = 0;
+    if (lane < ORDER_BUCKETS && mine) base = atomicAdd(&ob.cnt[lane], mine);
+    base = __shfl(base, cls < 0 ? 0 : cls);   // cls is cost_class's clamped integer, or -1 past the end of the batch
+    if (cls >= 0) ob.list[(size_t)cls * ob.cap + base + pos] = blockIdx.x * 64 + lane;
   }
-  __syncthreads();
-  if (threadIdx.x < ORDER_BUCKETS) lbase[threadIdx.x] = lcnt[threadIdx.x] ? atomicAdd(&ob.cnt[threadIdx.x], lcnt[threadIdx.x]) : 0;
-  __syncthreads();
-  if (filer) ob.list[(size_t)bucket * ob.cap + lbase[bucket] + pos] = b;
 }
 
 }  // namespace

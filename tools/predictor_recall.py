@@ -1,41 +1,29 @@
-"""Developer study: how many of the QPs that need three or four ADMM rounds are among the H dearest-PREDICTED ones of the dispatch order
-(the friction-demand predictor of mpcqp_common.h, restated in numpy)?  Decides whether giving the first H workgroups a SIMD of their own pays."""
+"""Developer study: where do the QPs that need a second ADMM round stand in the dispatch order?  The pre-pass's score (csrc/mpcqp_order.h,
+restated in numpy by tools/order_fit.py) next to the round-1 score it replaced: class sizes, two-round QPs among the first H ranks
+(H = 2048 is the first fill of a launch of 4096), and the costliest QPs' classes and ranks.  Needs a GPU for the iteration counts."""
 import os, sys
 import numpy as np, torch
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
+sys.path.insert(0, os.path.join(REPO, "tools"))
 import mpcqp
-allg = ("trot", "pronk", "amble", "gallop")
+import order_fit
+B = 4096
 for seed in (20250809, 1, 2, 3, 4):
-    b = mpcqp.synth.make_batch(4096, 10, 0.03, seed, allg, (0.3, 0.5, 0.7, 1.0))
-    r, c, mu = b["r"], b["contact"].astype(bool), b["mu"]
-    B = 4096
-    score = np.zeros(B); nst_tot = c.sum(axis=(1, 2)).astype(float)
-    for k in range(10):
-        n = c[:, k].sum(axis=1)
-        for i in np.where(n == 2)[0]:
-            a, bb = np.where(c[i, k])[0]
-            ra, rb = r[i, k, a], r[i, k, bb]
-            d = abs(ra[0] * rb[1] - ra[1] * rb[0]) / max(np.hypot(ra[0] - rb[0], ra[1] - rb[1]), 1e-6)
-            h = max(-0.5 * (ra[2] + rb[2]), 1e-3)
-            score[i] = max(score[i], d / h)
-        for i in np.where(n == 1)[0]:
-            a = np.where(c[i, k])[0][0]
-            score[i] = max(score[i], np.hypot(r[i, k, a, 0], r[i, k, a, 1]) / max(-r[i, k, a, 2], 1e-3))
-    us = 2.2 * nst_tot + 34.0 * np.minimum(score / np.maximum(np.abs(mu), 1e-3), 2.0)
-    cls = np.minimum((us * 0.1).astype(int), 15)
+    b = mpcqp.synth.make_batch(B, 10, 0.03, seed, order_fit.ALLG, order_fit.MUS)
+    T, old = order_fit.terms(b)
+    new = order_fit.classes(order_fit.score(T, order_fit.IN_SOURCE))
     sol = mpcqp.MPCBatch(N=10, precision="mixed")
     dev = sol.upload(b)
     o = sol.solve_batch(dev["x0"], dev["r"], dev["contact"], dev["xdes"], dev["mu"]); torch.cuda.synchronize()
-    it = o["iters"].cpu().numpy(); admm = mpcqp.split_iters(it)[0]; ps = mpcqp.split_iters(it)[1]
-    cost = admm * 0.4 + ps * 12.0
-    hard = admm > 200
-    order = np.argsort(-cls, kind="stable")            # dearest class first (position inside a class: arrival order on the device)
-    rank = np.empty(B, int); rank[order] = np.arange(B)
-    line = f"seed {seed}: class sizes {np.bincount(cls, minlength=16).tolist()}; QPs with > 200 iterations: {hard.sum()}"
-    for H in (64, 128, 256, 512, 1024):
-        line += f" | top {H}: {int((hard & (rank < H)).sum())}"
-    # an oracle order for comparison
-    print(line, flush=True)
+    it = o["iters"].cpu().numpy(); admm, ps = mpcqp.split_iters(it)[0], mpcqp.split_iters(it)[1]
+    hard = admm > 100
+    cost = admm * 1.1 + ps * 9.0                     # us in a full device (profiles/r30_order_predictor.txt)
     top = np.argsort(-cost)[:12]
-    print("   the 12 costliest: class", cls[top].tolist(), "rank", rank[top].tolist(), "iters", admm[top].tolist())
+    for name, cls in (("round-1 score", old), ("this score   ", new)):
+        rank = np.empty(B, int); rank[np.argsort(-cls, kind="stable")] = np.arange(B)   # dearest class first, batch order inside a class
+        line = f"seed {seed} {name}: class sizes {np.bincount(cls, minlength=16).tolist()}; two-round QPs: {int(hard.sum())}"
+        for H in (256, 512, 1024, 2048):
+            line += f" | top {H}: {int((hard & (rank < H)).sum())}"
+        print(line, flush=True)
+        print("   the 12 costliest: class", cls[top].tolist(), "rank", rank[top].tolist(), "iters", admm[top].tolist())
