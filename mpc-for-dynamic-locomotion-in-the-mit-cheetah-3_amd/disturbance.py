@@ -4,7 +4,7 @@ numpy fp64, vectorised over robots.
 A constant wrench on the MPC's model adds an affine term to every stage of X[k+1] = Ad X[k] + Bd_k U[k].  With s[0] = 0,
 s[k+1] = Ad s[k] + Cd the disturbed QP is the undisturbed one with xdes - s in the place of xdes, and its states are the solver's
 plus s.  ``shift_host`` forms s by that recursion with explicit 13 x 13 matrices -- the device writes the closed form --,
-``DisturbedEngine`` wraps a checker handle so that every host roll-out of ``gaits`` runs with a table unchanged,
+``DisturbedEngine`` wraps a checker handle so that every host roll-out of ``gaits`` and ``plant`` runs with a table unchanged,
 ``disturbance_track_host`` is the observer in the device's operation order, and ``compensated_rollout`` closes the loop between the
 two piece by piece, on either side.
 """
@@ -13,7 +13,7 @@ from __future__ import annotations
 import numpy as np
 
 from . import _capi
-from .plant import inertia_inverse, model_body, quat_to_matrix, rotvec_to_quat
+from .plant import inertia_inverse, model_body, quat_to_matrix, rollout_loop_host, rotvec_to_quat
 
 ROW = 6                       # (F_x, F_y, F_z, tau_x, tau_y, tau_z): a `push` row
 STATE = _capi.DIST_STATE      # d^ (6) | previous row: L (3), v (3), p (3), f (12), feet (12) | live
@@ -104,9 +104,12 @@ def shift_host(x0, xdes, rows, cfg, models=None):
 
 class DisturbedEngine:
     """A checker handle (``Engine`` on the CPU checker library) with a disturbance table: ``solve_batch_host`` solves the tuple with
-    xdes - s and returns X + s, every other attribute is the handle's -- so ``gaits.rollout_*_host`` and ``plant.rollout_plant_host`` run
-    with it unchanged.  rows [B,6] or None (no table); `models` [B,6] only where the device has a model table set as well (the
-    handle itself has one model: group the robots by row, models.grouped_host, and wrap each group's handle)."""
+    xdes - s and returns X + s, and ``rollout_host`` -- the handle's is the checker's C loop, which calls the C solve and never sees the
+    table -- runs ``plant.rollout_loop_host``, the same loop in Python over that ``solve_batch_host``, while rows are set.  Every other
+    attribute is the handle's.  So the host loops that solve through ``solve_batch_host`` (``gaits.rollout_phase_host``, ``_legs_``,
+    ``_drive_``, ``_slip_`` and ``_observe_host``) and those that solve through ``rollout_host`` (``plant.rollout_plant_host``) run under a
+    table unchanged.  rows [B,6] or None (no table); `models` [B,6] only where the device has a model table set as well (the handle
+    itself has one model: group the robots by row, models.grouped_host, and wrap each group's handle)."""
 
     def __init__(self, oracle_engine, rows=None, models=None):
         self._engine, self.models = oracle_engine, models
@@ -126,6 +129,11 @@ class DisturbedEngine:
         if want_X and out.get("X") is not None:
             out["X"] = out["X"] + np.where(fin[:, None, None], s, 0.0)
         return out
+
+    def rollout_host(self, x, ref, plan_pos, plan_feet_id, plan_meta, tick, mu, T):
+        if self.rows is None:
+            return self._engine.rollout_host(x, ref, plan_pos, plan_feet_id, plan_meta, tick, mu, T)
+        return rollout_loop_host(self, x, ref, plan_pos, plan_feet_id, plan_meta, tick, mu, T)
 
 
 def _mv(R, v):    # R v and R^T v in the device's order (csrc/mpcqp_estimate.h, est_mv / est_mtv); R [B,3,3], v a list of three [B]

@@ -192,11 +192,78 @@ def push_wrench(push, push_ticks, tick):
     return np.where(on[:, None], push, 0.0)
 
 
+def _plan_clock(plan_pos, plan_meta, tick):
+    """The clamped plan row of mpcqp_rollout (include/mpcqp.h): S_b in [1, S], ss >= 0, ss + ds >= 1, t0 = max(tick, 0), and the
+    gate on the reference velocities, 0 on the plan's last step.  Each [B]."""
+    meta = np.asarray(plan_meta).astype(np.int64)
+    S = np.minimum(np.maximum(meta[:, 0], 1), np.shape(plan_pos)[1])
+    ss = np.maximum(meta[:, 1], 0)
+    period = np.maximum(ss + np.maximum(meta[:, 2], 0), 1)
+    t0 = np.maximum(np.asarray(tick).astype(np.int64), 0)
+    gate = np.where(np.minimum(t0 // period, S - 1) == S - 1, 0.0, 1.0)
+    return S, ss, period, t0, gate
+
+
+def plan_expand_host(x, ref, plan_pos, plan_feet_id, plan_meta, tick, N, delta):
+    """The operator tuple of one tick of mpcqp_rollout (include/mpcqp.h), numpy fp64 in the checker's operation order: stage k lies in
+    step min((t0 + k) / (ss + ds), S_b - 1) of the clamped plan row (``stance_feet``'s arithmetic), every foot stands on the plan,
+    and the reference velocities are gated off on the plan's last step.  Returns {"r" [B,N,4,3], "contact" [B,N,4], "xdes" [B,N+1,13]}."""
+    x, ref, pos = _f64(x), _f64(ref), _f64(plan_pos)
+    fid = np.asarray(plan_feet_id)
+    B, N, d = x.shape[0], int(N), float(delta)
+    S, ss, period, t0, gate = _plan_clock(pos, plan_meta, tick)
+    kd = (np.arange(N + 1) * d)[None, :] * gate[:, None]                                          # (k delta) gate, [B,N+1]
+    xdes = np.zeros((B, N + 1, 13))
+    xdes[:, :, 0], xdes[:, :, 1] = ref[:, None, 0], ref[:, None, 1]
+    xdes[:, :, 2] = ref[:, None, 2] + kd * ref[:, None, 9]
+    xdes[:, :, 3:6] = ref[:, None, 3:6] + kd[:, :, None] * ref[:, None, 6:9]
+    xdes[:, :, 8] = (gate * ref[:, 9])[:, None]
+    xdes[:, :, 9:12] = (gate[:, None] * ref[:, 6:9])[:, None, :]
+    xdes[:, :, 12] = x[:, None, 12]
+    tau = t0[:, None] + np.arange(N)[None, :]
+    st = np.minimum(tau // period[:, None], (S - 1)[:, None])
+    tin = tau - st * period[:, None]
+    rows = np.arange(B)[:, None]
+    contact = np.where((tin < ss[:, None])[:, :, None], fid[rows, st] != 0, True).astype(np.uint8)
+    com = xdes[:, :N, 3:6].copy()
+    com[:, 0] = x[:, 3:6]
+    return {"r": pos[rows, st] - com[:, :, None, :], "contact": contact, "xdes": xdes}
+
+
+def rollout_loop_host(engine, x, ref, plan_pos, plan_feet_id, plan_meta, tick, mu, T):
+    """mpcqp_rollout tick by tick in Python, on any object with `cfg` and `solve_batch_host` (a checker ``Engine``, or a
+    ``disturbance.DisturbedEngine`` -- whose table the checker's C loop cannot see).  Per tick: ``plan_expand_host``, one
+    ``solve_batch_host`` with want_X, the log rows, x[:, :12] <- X[:, 1, :12], the reference rolled forward, the tick advanced.
+    Without a table it reproduces ``Engine.rollout_host``, and it returns what that returns."""
+    cfg = engine.cfg
+    N, d = int(cfg.N), float(cfg.delta)
+    x = _f64(x).copy(); ref = _f64(ref).copy(); mu = _f64(mu)
+    tick = np.asarray(tick, dtype=np.int32).copy()
+    B, T = x.shape[0], int(T)
+    actual = np.zeros((B, T, 12)); desired = np.zeros((B, T, 12)); forces = np.zeros((B, T, 12)); solved = np.zeros(B, np.int32)
+    for t in range(T if B else 0):
+        gate = _plan_clock(plan_pos, plan_meta, tick)[4]
+        e = plan_expand_host(x, ref, plan_pos, plan_feet_id, plan_meta, tick, N, d)
+        o = engine.solve_batch_host(x, e["r"], e["contact"], e["xdes"], mu, want_X=True)
+        actual[:, t] = x[:, :12]
+        desired[:, t, 0:6] = ref[:, 0:6]
+        desired[:, t, 8] = gate * ref[:, 9]
+        desired[:, t, 9:12] = gate[:, None] * ref[:, 6:9]
+        forces[:, t] = np.asarray(o["u"], np.float64).reshape(B, N, 12)[:, 0]
+        solved += np.isin(o["status"], (1, 2)).astype(np.int32)
+        x[:, :12] = np.asarray(o["X"], np.float64).reshape(B, N + 1, 13)[:, 1, :12]
+        ref[:, 3:6] += (gate[:, None] * ref[:, 6:9]) * d
+        ref[:, 2] += (gate * ref[:, 9]) * d
+        tick += 1
+    return {"x": x, "ref": ref, "tick": tick, "actual": actual, "desired": desired, "forces": forces, "solved": solved}
+
+
 def rollout_plant_host(oracle_engine, x, ref, plan_pos, plan_feet_id, plan_meta, tick, mu, T, body=None, push=None, push_ticks=None,
                        substeps=DEFAULT_SUBSTEPS):
     """Closed loop of mpcqp_rollout_plant on the CPU checker (host memory, fp64).  Per tick: the checker's roll-out of one tick
     (solve, log rows, ref roll-forward, tick advance) with its world step discarded, then ``srb_step`` under the stage-0 forces it
-    logged.  Returns the advanced (x, ref, tick) and the logs, as ``Engine.rollout_host``."""
+    logged.  `oracle_engine` is a checker ``Engine`` or a ``disturbance.DisturbedEngine``, whose ``rollout_host`` makes that tick's solve
+    under its table.  Returns the advanced (x, ref, tick) and the logs, as ``Engine.rollout_host``."""
     if push is not None and push_ticks is None:
         raise ValueError("push needs push_ticks")
     cfg = oracle_engine.cfg
