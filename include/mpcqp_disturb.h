@@ -26,6 +26,9 @@
  * Row layout: rows[b] = (F_x, F_y, F_z, tau_x, tau_y, tau_z), fp64 WHATEVER the handle's I/O dtype: the layout of a `push` row.
  * A row with a non-finite entry is kept as NaN: that robot's shifted xdes is NaN, its solve reports MPCQP_STATUS_NONFINITE with zero
  * outputs (nothing is added to its X_out), and no other QP changes.  So does a robot whose x0[2] or whose model row is not finite.
+ *
+ * The observer inside a roll-out's tick loop, with the table updated on the device every few ticks, is mpcqp_compensate.h.
+ * Not built: a disturbance-aware foothold rule; a wrench that varies over the horizon; telling the plant.
  */
 #ifndef MPCQP_DISTURB_H_
 #define MPCQP_DISTURB_H_

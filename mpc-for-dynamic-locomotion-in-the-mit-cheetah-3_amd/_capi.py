@@ -1,5 +1,6 @@
 """ctypes binding of the C-ABI declared in include/mpcqp.h and its product-only extensions include/mpcqp_plan.h, mpcqp_sim.h, mpcqp_model.h,
-mpcqp_joints.h, mpcqp_actuators.h, mpcqp_slip.h, mpcqp_estimate.h, mpcqp_observe.h, mpcqp_gate.h, mpcqp_attitude.h and mpcqp_disturb.h.
+mpcqp_joints.h, mpcqp_actuators.h, mpcqp_slip.h, mpcqp_estimate.h, mpcqp_observe.h, mpcqp_gate.h, mpcqp_attitude.h, mpcqp_disturb.h and
+mpcqp_compensate.h.
 
 The product path loads ``csrc/libmpcqp.so`` (hand-written HIP for gfx950) and nothing else: if that library is
 missing or cannot be loaded, importing the engine raises -- there is no CPU fallback.  The binding itself is
@@ -104,6 +105,12 @@ class MpcQpWrenchObserver(ctypes.Structure):
     """Mirror of struct MpcQpWrenchObserver (include/mpcqp_disturb.h): the wrench observer's gravity, gain and clamps."""
     _fields_ = [("size", c_uint32), ("gravity", c_double), ("kappa", c_double), ("f_lim", c_double), ("t_lim", c_double)]
     FIELDS = tuple(name for name, _ in _fields_[1:])
+
+
+class MpcQpCompensate(ctypes.Structure):
+    """Mirror of struct MpcQpCompensate (include/mpcqp_compensate.h): the estimator variant, the observer's source, the ticks between
+    two table updates and the observer's parameters."""
+    _fields_ = [("size", c_uint32), ("flags", c_uint32), ("source", c_int32), ("hold", c_int32), ("observer", MpcQpWrenchObserver)]
 
 
 class MpcQpConfig(ctypes.Structure):
@@ -268,6 +275,19 @@ DISTURB_ABI = {
 }
 DISTURB_SYMBOLS = tuple(row[0] for row in DISTURB_ABI[DISTURB_HEADER])
 DIST_STATE = 40   # include/mpcqp_disturb.h, MPCQP_DIST_STATE: doubles per robot of the observer's state
+# include/mpcqp_compensate.h, that observer and the table update inside the roll-out's tick loop, likewise: `has_compensate`.  The call is
+# the aided roll-out's row with the parameters, the observer's body, its state and its two logs in front of the stream.
+COMPENSATE_HEADER = "mpcqp_compensate.h"
+_COMP = ctypes.POINTER(MpcQpCompensate)
+COMPENSATE_ABI = {
+    COMPENSATE_HEADER: (  # the wrench observer inside mpcqp_rollout_observe
+        ("mpcqp_default_compensate", c_int, (_COMP,)),
+        ("mpcqp_rollout_observe_compensated", c_int, ATTITUDE_ABI[ATTITUDE_HEADER][2][2][:-1] + (_COMP, _P, _P, _P, _P, _P)),
+    ),
+}
+COMPENSATE_SYMBOLS = tuple(row[0] for row in COMPENSATE_ABI[COMPENSATE_HEADER])
+WRENCH_TRUTH, WRENCH_SENSED = 0, 1   # include/mpcqp_compensate.h, MPCQP_WRENCH_*
+COMP_GATED, COMP_AIDED = 1, 2        # include/mpcqp_compensate.h, MPCQP_COMP_*
 # The swing-leg plant of include/mpcqp_joints.h came after the rest of that header: a product library built before it still has the
 # header's other calls (`has_joints`) and is told apart by `has_legsim`.
 LEGSIM_SYMBOLS = ("mpcqp_leg_accel", "mpcqp_swing_track")
@@ -305,7 +325,8 @@ class Library:
         self.has_legroll = all(hasattr(self.lib, name) for name in LEGROLL_SYMBOLS)
         self.has_score = all(hasattr(self.lib, name) for name in SCORE_SYMBOLS)
         self.has_drive = all(hasattr(self.lib, name) for name in DRIVE_SYMBOLS)
-        for header, rows in {**ABI, **ACTUATORS_ABI, **SLIP_ABI, **ESTIMATE_ABI, **OBSERVE_ABI, **GATE_ABI, **ATTITUDE_ABI, **DISTURB_ABI}.items():
+        for header, rows in {**ABI, **ACTUATORS_ABI, **SLIP_ABI, **ESTIMATE_ABI, **OBSERVE_ABI, **GATE_ABI, **ATTITUDE_ABI, **DISTURB_ABI,
+                             **COMPENSATE_ABI}.items():
             have = header == CORE_HEADER or all(hasattr(self.lib, row[0]) for row in rows if row[0] not in _GATED)
             if header != CORE_HEADER:
                 setattr(self, "has_" + header[len("mpcqp_"):-len(".h")], have)
@@ -373,6 +394,17 @@ class Library:
         rc = fn(ctypes.byref(row))
         if rc != 0:
             raise MpcQpError(f"mpcqp_default_wrench_observer failed: {rc}")
+        return row
+
+    def default_compensate(self) -> "MpcQpCompensate":
+        """The compensated roll-out's default parameters (include/mpcqp_compensate.h, mpcqp_default_compensate; product library only)."""
+        fn, header, _ = self.calls["mpcqp_default_compensate"]
+        if fn is None:
+            raise MpcQpError(f"mpcqp_default_compensate: {self.path} does not export include/{header} (product library only)")
+        row = MpcQpCompensate()
+        rc = fn(ctypes.byref(row))
+        if rc != 0:
+            raise MpcQpError(f"mpcqp_default_compensate failed: {rc}")
         return row
 
     def default_config(self, **overrides) -> MpcQpConfig:
@@ -580,6 +612,23 @@ class Engine:
                    contact_log, solved, swing_log, q_log, qd_log, tau_log, foot_log, err_log, flag_log, miss_log, cmd_log, slip_log, disp_log,
                    feed, est_state, est_init, height, bias, noise, enc_noise, estimator, imu_log, q_enc_log, qd_enc_log, est_log, feet_est_log,
                    sigma_log, nis_log, gate, trust_log, flags, attitude, att_state, bias_log, stream)
+
+    def rollout_observe_compensated_ptr(self, B, T, x, ref, feet, legs, gait, stand, gain, tick, mu, body, push, push_ticks, substeps,
+                                        step_height, gains, leg_substeps, land, drive, ground, foot_mass, slip, actual, desired, forces,
+                                        feet_log, contact_log, solved, swing_log, q_log, qd_log, tau_log, foot_log, err_log, flag_log,
+                                        miss_log, cmd_log, slip_log, disp_log, imu_log, q_enc_log, qd_enc_log, est_log, feet_est_log,
+                                        sigma_log, nis_log, trust_log, bias_log, dist_log, resid_log, feed, est_state, est_init=0, height=0,
+                                        bias=0, noise=0, enc_noise=0, estimator=None, gate=None, flags=0, attitude=None, att_state=0,
+                                        compensate=None, obs_body=0, dist_state=0, geometry=None, inertia=None, stream=0):
+        """`rollout_observe_aided_ptr` with the wrench observer and the table update inside the tick (include/mpcqp_compensate.h,
+        mpcqp_rollout_observe_compensated): dist_log and resid_log follow bias_log among the logs; `compensate` (an MpcQpCompensate or
+        None = the defaults), obs_body and dist_state follow att_state."""
+        self._call("mpcqp_rollout_observe_compensated", B, T, x, ref, feet, legs, gait, stand, gain, tick, mu, body, push, push_ticks, substeps,
+                   step_height, gains, leg_substeps, geometry, inertia, land, drive, ground, foot_mass, slip, actual, desired, forces, feet_log,
+                   contact_log, solved, swing_log, q_log, qd_log, tau_log, foot_log, err_log, flag_log, miss_log, cmd_log, slip_log, disp_log,
+                   feed, est_state, est_init, height, bias, noise, enc_noise, estimator, imu_log, q_enc_log, qd_enc_log, est_log, feet_est_log,
+                   sigma_log, nis_log, gate, trust_log, flags, attitude, att_state, bias_log, compensate, obs_body, dist_state, dist_log,
+                   resid_log, stream)
 
     # (`estimator` is an MpcQpEstimator or None = the defaults)
     def imu_log_ptr(self, B, T, actual, forces, feet, base_acc, body, bias, noise, imu, estimator=None, stream=0):

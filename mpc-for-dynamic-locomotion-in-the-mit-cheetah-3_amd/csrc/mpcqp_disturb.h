@@ -9,7 +9,8 @@
 // cost of the row form at 65 536 robots (+149 against +68 us per roll-out tick for the pair, profiles/r29_disturbance.txt).  What a lane
 // reads besides -- the wrench row, the model row, x0[2] -- is the same address in the N + 1 lanes of a robot.
 // The observer is serial in T and parallel in B: one lane per robot carries d^ and the previous row (39 doubles) in registers.
-// No LDS, no scratch (every index is a constant after unrolling); masks and poison are selects.
+// No LDS, no scratch (every index is a constant after unrolling); masks and poison are selects.  Its row is written once, as a device
+// function, for the pass over a log here and for the tick kernel of mpcqp_compensate.h.
 #pragma once
 #include "mpcqp_estimate.h"
 #include "../../include/mpcqp_disturb.h"
@@ -127,107 +128,129 @@ struct DistPar { double g, kappa, flim, tlim, d; };
 
 __device__ __forceinline__ double dist_clamp(const double v, const double lim) { return v > lim ? lim : (v < -lim ? -lim : v); }
 
+// The observer of one robot as a lane carries it: the robot's flag, d^ and the previous row.  dist_state_load / dist_state_store move it
+// between the lane and the robot's 40 doubles of `state`, dist_observer_row is one row of the rule: mpcqp_disturb_track_kernel runs it over
+// the T rows of a log, mpcqp_compensate_tick_kernel (mpcqp_compensate.h) once per tick of a roll-out.
+struct DistLane { bool ok, live; double dh[6], Lp[3], vp[3], pp[3], fp[12], ftp[12]; };
+
+// A fresh observer under the body row `ok` speaks for, then, where there is a state, the robot's.
+__device__ __forceinline__ void dist_state_load(const double* sb, const bool ok, DistLane& s) {
+  s.ok = ok;
+  s.live = false;
+#pragma unroll
+  for (int i = 0; i < 6; ++i) s.dh[i] = 0.0;
+#pragma unroll
+  for (int i = 0; i < 3; ++i) { s.Lp[i] = 0.0; s.vp[i] = 0.0; s.pp[i] = 0.0; }
+#pragma unroll
+  for (int i = 0; i < 12; ++i) { s.fp[i] = 0.0; s.ftp[i] = 0.0; }
+  if (sb) {
+#pragma unroll
+    for (int i = 0; i < DIST_STATE; ++i) s.ok = s.ok && isfinite(sb[i]);
+    s.live = sb[DIST_LIVE] != 0.0;
+#pragma unroll
+    for (int i = 0; i < 6; ++i) s.dh[i] = sb[i];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) { s.Lp[i] = sb[DIST_PREV + i]; s.vp[i] = sb[DIST_PREV + 3 + i]; s.pp[i] = sb[DIST_PREV + 6 + i]; }
+#pragma unroll
+    for (int i = 0; i < 12; ++i) { s.fp[i] = sb[DIST_PREV + 9 + i]; s.ftp[i] = sb[DIST_PREV + 21 + i]; }
+  }
+}
+
+__device__ __forceinline__ void dist_state_store(double* sb, const DistLane& s) {
+  const double nan = __builtin_nan("");
+#pragma unroll
+  for (int i = 0; i < 6; ++i) sb[i] = s.ok ? s.dh[i] : nan;
+#pragma unroll
+  for (int i = 0; i < 3; ++i) { sb[DIST_PREV + i] = s.ok ? s.Lp[i] : nan; sb[DIST_PREV + 3 + i] = s.ok ? s.vp[i] : nan; sb[DIST_PREV + 6 + i] = s.ok ? s.pp[i] : nan; }
+#pragma unroll
+  for (int i = 0; i < 12; ++i) { sb[DIST_PREV + 9 + i] = s.ok ? s.fp[i] : nan; sb[DIST_PREV + 21 + i] = s.ok ? s.ftp[i] : nan; }
+  sb[DIST_LIVE] = s.ok ? (s.live ? 1.0 : 0.0) : nan;
+}
+
+// One row of the rule of include/mpcqp_disturb.h on the lane's observer: xr the torso row (12), fr the forces over the row's tick (12),
+// ftr the feet (12), each as the I/O type holds it; m, Ib the body the observer believes.  Folds the row's operands into s.ok, leaves
+// the residual in res and d^ in s.dh, and makes the row the previous one.  fp64, not contracted; masks and poison are selects.
+template <typename TIO>
+__device__ __forceinline__ void dist_observer_row(const TIO* __restrict__ xr, const TIO* __restrict__ fr, const TIO* __restrict__ ftr,
+                                                  const double m, const double (&Ib)[6], const DistPar& par, DistLane& s, double (&res)[6]) {
+#pragma clang fp contract(off)
+  const V3 th = load3(xr), pc = load3(xr + 3), om = load3(xr + 6), vc = load3(xr + 9);
+  double f[12], ft[12];
+  bool fin = fin3(th) && fin3(pc) && fin3(om) && fin3(vc);
+#pragma unroll
+  for (int i = 0; i < 12; ++i) { f[i] = (double)fr[i]; fin = fin && isfinite(f[i]); }
+#pragma unroll
+  for (int l = 0; l < 4; ++l) {   // a leg without force is left out: its foot is not read, the state keeps a zero
+    const bool on = f[3 * l] != 0.0 || f[3 * l + 1] != 0.0 || f[3 * l + 2] != 0.0;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+      const double v = (double)ftr[3 * l + a];
+      ft[3 * l + a] = on ? v : 0.0;
+      fin = fin && isfinite(ft[3 * l + a]);
+    }
+  }
+  s.ok = s.ok && fin;
+  const M3 R = est_rotvec_rot(th);
+  const V3 wb = est_mtv(R, om);
+  const double wv[3] = {wb.x, wb.y, wb.z};
+  double Lb[3];
+  plant_symv(Ib, wv, Lb);
+  const V3 Lw = est_mv(R, V3{Lb[0], Lb[1], Lb[2]});
+  const double L[3] = {Lw.x, Lw.y, Lw.z}, v[3] = {vc.x, vc.y, vc.z}, p[3] = {pc.x, pc.y, pc.z};
+  double Fs[3], Ms[3], cr[4][3];
+  const double pm[3] = {0.5 * (s.pp[0] + p[0]), 0.5 * (s.pp[1] + p[1]), 0.5 * (s.pp[2] + p[2])};
+#pragma unroll
+  for (int l = 0; l < 4; ++l) {
+    const bool on = s.fp[3 * l] != 0.0 || s.fp[3 * l + 1] != 0.0 || s.fp[3 * l + 2] != 0.0;
+    const double r[3] = {s.ftp[3 * l] - pm[0], s.ftp[3 * l + 1] - pm[1], s.ftp[3 * l + 2] - pm[2]};
+    const double fl[3] = {s.fp[3 * l], s.fp[3 * l + 1], s.fp[3 * l + 2]};
+    double c3[3];
+    plant_cross(r, fl, c3);
+#pragma unroll
+    for (int a = 0; a < 3; ++a) cr[l][a] = on ? c3[a] : 0.0;
+  }
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    Fs[a] = (s.fp[a] + s.fp[3 + a]) + (s.fp[6 + a] + s.fp[9 + a]);
+    Ms[a] = (cr[0][a] + cr[1][a]) + (cr[2][a] + cr[3][a]);
+    const double rf = (m * (v[a] - s.vp[a])) / par.d - Fs[a];
+    res[a] = s.live ? (a == 2 ? rf - m * par.g : rf) : 0.0;
+    res[3 + a] = s.live ? (L[a] - s.Lp[a]) / par.d - Ms[a] : 0.0;
+  }
+#pragma unroll
+  for (int i = 0; i < 6; ++i) s.dh[i] = s.live ? dist_clamp(s.dh[i] + par.kappa * (res[i] - s.dh[i]), i < 3 ? par.flim : par.tlim) : s.dh[i];
+#pragma unroll
+  for (int i = 0; i < 3; ++i) { s.Lp[i] = L[i]; s.vp[i] = v[i]; s.pp[i] = p[i]; }
+#pragma unroll
+  for (int i = 0; i < 12; ++i) { s.fp[i] = f[i]; s.ftp[i] = ft[i]; }
+  s.live = true;
+}
+
 // mpcqp_disturbance_track: lane b runs robot b over its T rows.  body / state / dist / resid may be null.
 template <typename TIO>
 __global__ void __launch_bounds__(256)
 mpcqp_disturb_track_kernel(const TIO* __restrict__ actual, const TIO* __restrict__ forces, const TIO* __restrict__ feet,
                            const TIO* __restrict__ body, const PlantModel model, const DistPar par, double* state, TIO* __restrict__ dist,
                            TIO* __restrict__ resid, const int64_t B, const int T) {
-#pragma clang fp contract(off)
   const int64_t b = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (b >= B) return;
   double* const sb = state ? state + b * DIST_STATE : nullptr;
-  double bd[7], Ii[6], dh[6], Lp[3], vp[3], pp[3], fp[12], ftp[12];
+  double bd[7], Ii[6];
   plant_body_row(body, model, b, bd);
   const double Ib[6] = {bd[1], bd[2], bd[3], bd[4], bd[5], bd[6]};
-  const double m = bd[0];
-  bool ok = plant_inertia(m, Ib, Ii);   // the robot's flag
-  bool live = false;
-#pragma unroll
-  for (int i = 0; i < 6; ++i) dh[i] = 0.0;
-#pragma unroll
-  for (int i = 0; i < 3; ++i) { Lp[i] = 0.0; vp[i] = 0.0; pp[i] = 0.0; }
-#pragma unroll
-  for (int i = 0; i < 12; ++i) { fp[i] = 0.0; ftp[i] = 0.0; }
-  if (sb) {
-#pragma unroll
-    for (int i = 0; i < DIST_STATE; ++i) ok = ok && isfinite(sb[i]);
-    live = sb[DIST_LIVE] != 0.0;
-#pragma unroll
-    for (int i = 0; i < 6; ++i) dh[i] = sb[i];
-#pragma unroll
-    for (int i = 0; i < 3; ++i) { Lp[i] = sb[DIST_PREV + i]; vp[i] = sb[DIST_PREV + 3 + i]; pp[i] = sb[DIST_PREV + 6 + i]; }
-#pragma unroll
-    for (int i = 0; i < 12; ++i) { fp[i] = sb[DIST_PREV + 9 + i]; ftp[i] = sb[DIST_PREV + 21 + i]; }
-  }
+  DistLane s;
+  dist_state_load(sb, plant_inertia(bd[0], Ib, Ii), s);   // (the robot's flag starts from its body row)
   for (int t = 0; t < T; ++t) {
     const int64_t row = b * T + t;
-    const V3 th = load3(actual + 12 * row), pc = load3(actual + 12 * row + 3), om = load3(actual + 12 * row + 6), vc = load3(actual + 12 * row + 9);
-    double f[12], ft[12];
-    bool fin = fin3(th) && fin3(pc) && fin3(om) && fin3(vc);
-#pragma unroll
-    for (int i = 0; i < 12; ++i) { f[i] = (double)forces[12 * row + i]; fin = fin && isfinite(f[i]); }
-#pragma unroll
-    for (int l = 0; l < 4; ++l) {   // a leg without force is left out: its foot is not read, the state keeps a zero
-      const bool on = f[3 * l] != 0.0 || f[3 * l + 1] != 0.0 || f[3 * l + 2] != 0.0;
-#pragma unroll
-      for (int a = 0; a < 3; ++a) {
-        const double v = (double)feet[12 * row + 3 * l + a];
-        ft[3 * l + a] = on ? v : 0.0;
-        fin = fin && isfinite(ft[3 * l + a]);
-      }
-    }
-    ok = ok && fin;
-    const M3 R = est_rotvec_rot(th);
-    const V3 wb = est_mtv(R, om);
-    const double wv[3] = {wb.x, wb.y, wb.z};
-    double Lb[3];
-    plant_symv(Ib, wv, Lb);
-    const V3 Lw = est_mv(R, V3{Lb[0], Lb[1], Lb[2]});
-    const double L[3] = {Lw.x, Lw.y, Lw.z}, v[3] = {vc.x, vc.y, vc.z}, p[3] = {pc.x, pc.y, pc.z};
-    double res[6], Fs[3], Ms[3], cr[4][3];
-    const double pm[3] = {0.5 * (pp[0] + p[0]), 0.5 * (pp[1] + p[1]), 0.5 * (pp[2] + p[2])};
-#pragma unroll
-    for (int l = 0; l < 4; ++l) {
-      const bool on = fp[3 * l] != 0.0 || fp[3 * l + 1] != 0.0 || fp[3 * l + 2] != 0.0;
-      const double r[3] = {ftp[3 * l] - pm[0], ftp[3 * l + 1] - pm[1], ftp[3 * l + 2] - pm[2]};
-      const double fl[3] = {fp[3 * l], fp[3 * l + 1], fp[3 * l + 2]};
-      double c3[3];
-      plant_cross(r, fl, c3);
-#pragma unroll
-      for (int a = 0; a < 3; ++a) cr[l][a] = on ? c3[a] : 0.0;
-    }
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-      Fs[a] = (fp[a] + fp[3 + a]) + (fp[6 + a] + fp[9 + a]);
-      Ms[a] = (cr[0][a] + cr[1][a]) + (cr[2][a] + cr[3][a]);
-      const double rf = (m * (v[a] - vp[a])) / par.d - Fs[a];
-      res[a] = live ? (a == 2 ? rf - m * par.g : rf) : 0.0;
-      res[3 + a] = live ? (L[a] - Lp[a]) / par.d - Ms[a] : 0.0;
-    }
-#pragma unroll
-    for (int i = 0; i < 6; ++i) dh[i] = live ? dist_clamp(dh[i] + par.kappa * (res[i] - dh[i]), i < 3 ? par.flim : par.tlim) : dh[i];
+    double res[6];
+    dist_observer_row(actual + 12 * row, forces + 12 * row, feet + 12 * row, bd[0], Ib, par, s, res);
 #pragma unroll
     for (int i = 0; i < 6; ++i) {
-      if (dist) dist[6 * row + i] = est_out<TIO>(ok, dh[i]);
-      if (resid) resid[6 * row + i] = est_out<TIO>(ok, res[i]);
+      if (dist) dist[6 * row + i] = est_out<TIO>(s.ok, s.dh[i]);
+      if (resid) resid[6 * row + i] = est_out<TIO>(s.ok, res[i]);
     }
-#pragma unroll
-    for (int i = 0; i < 3; ++i) { Lp[i] = L[i]; vp[i] = v[i]; pp[i] = p[i]; }
-#pragma unroll
-    for (int i = 0; i < 12; ++i) { fp[i] = f[i]; ftp[i] = ft[i]; }
-    live = true;
   }
-  if (sb) {
-    const double nan = __builtin_nan("");
-#pragma unroll
-    for (int i = 0; i < 6; ++i) sb[i] = ok ? dh[i] : nan;
-#pragma unroll
-    for (int i = 0; i < 3; ++i) { sb[DIST_PREV + i] = ok ? Lp[i] : nan; sb[DIST_PREV + 3 + i] = ok ? vp[i] : nan; sb[DIST_PREV + 6 + i] = ok ? pp[i] : nan; }
-#pragma unroll
-    for (int i = 0; i < 12; ++i) { sb[DIST_PREV + 9 + i] = ok ? fp[i] : nan; sb[DIST_PREV + 21 + i] = ok ? ftp[i] : nan; }
-    sb[DIST_LIVE] = ok ? (live ? 1.0 : 0.0) : nan;
-  }
+  if (sb) dist_state_store(sb, s);
 }
 
 }  // namespace

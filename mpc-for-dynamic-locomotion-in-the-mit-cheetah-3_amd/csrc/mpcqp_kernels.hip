@@ -4,7 +4,7 @@
 // CasADi Opti('conic') -> OSQP on the QP of src/mpc.py:58-173, filled at src/mpc.py:242-255, solved at :258.
 //
 // This translation unit is the C-ABI of include/mpcqp.h, mpcqp_plan.h, mpcqp_sim.h, mpcqp_model.h, mpcqp_joints.h, mpcqp_actuators.h, mpcqp_slip.h,
-// mpcqp_estimate.h, mpcqp_observe.h, mpcqp_gate.h, mpcqp_attitude.h and mpcqp_disturb.h,
+// mpcqp_estimate.h, mpcqp_observe.h, mpcqp_gate.h, mpcqp_attitude.h, mpcqp_disturb.h and mpcqp_compensate.h,
 // in three parts: the handle; its host helpers in one anonymous namespace, in order of use (errors, I/O-type dispatch, the solve, workspaces,
 // the device guard and the launch tail `on_device`, grids, the policy behind the configuration's defaults, the engine's tables, the roll-out
 // loops, the leg rows, the row tables); one extern "C" block of entry points, each its own checks and its own launches.  The device code is in
@@ -30,6 +30,7 @@
 //                        two kernels that call mpcqp_estimate.h's helpers around a tick
 //   mpcqp_disturb.h      per-robot disturbance wrench rows: the kernels in front of and behind a solve that shift xdes and add the shift back
 //                        to the predicted states, and the wrench observer over a roll-out's logs
+//   mpcqp_compensate.h   that observer and the table update inside the tick loop of mpcqp_rollout_observe: one kernel per tick
 // DESIGN.md has the derivations.
 
 #include "mpcqp_wrench.h"
@@ -47,6 +48,7 @@
 #include "mpcqp_estimate.h"
 #include "mpcqp_observe.h"
 #include "mpcqp_disturb.h"
+#include "mpcqp_compensate.h"
 #include "../../include/mpcqp_gate.h"
 #include "../../include/mpcqp_attitude.h"
 
@@ -355,6 +357,22 @@ bool table_reserve(const RowTable& t, int64_t B, int width) {
   if (!grow(t.mem, (size_t)B * width * sizeof(double))) return false;
   t.cap = B; t.B = 0;
   return true;
+}
+
+// Room for a disturbance table of B rows and the shifted xdes a solve reads under it (mpcqp_set_disturbance and the entry of
+// mpcqp_rollout_observe_compensated; the caller holds the device).  The buffer first: when it cannot be grown, the table set before stays.
+int reserve_disturbance(mpcqp_engine* h, int64_t B, const char* who) {
+  if (h->dist_cap >= B) return MPCQP_OK;
+  char msg[128];
+  if (!grow(h->dshift_mem, (size_t)B * (h->cfg.N + 1) * 13 * io_size(h))) {
+    snprintf(msg, sizeof(msg), "%s: buffer allocation failed", who);
+    return fail(h, MPCQP_ENOMEM, msg);
+  }
+  if (!table_reserve(disturbances(h), B, DIST_ROW)) {   // (the buffer is larger than the table's rows need: harmless)
+    snprintf(msg, sizeof(msg), "%s: table allocation failed", who);
+    return fail(h, MPCQP_ENOMEM, msg);
+  }
+  return MPCQP_OK;
 }
 
 // Workspace that depends on the batch size: the dispatch-order buffer of the queued launch forms and, for warm-started
@@ -912,16 +930,32 @@ struct RolloutObserveArgs {
   const EstGate* gate; void* trust_log;
   const EstAid* aid; double* att_state; void* bias_log;
 };
+// What mpcqp_rollout_observe_compensated adds to mpcqp_rollout_observe (include/mpcqp_compensate.h): where the observer reads, the ticks
+// between two table updates, the checked observer parameters, the body it believes or null, its state [B,40] and its two logs or null.
+struct RolloutCompensateArgs { int32_t source, hold; DistPar par; const void* obs_body; double* dist_state; void *dist_log, *resid_log; };
 
-// mpcqp_rollout_legs (dr = null), mpcqp_rollout_drive, mpcqp_rollout_slip (sl, with dr) and mpcqp_rollout_observe (ob, with both): one
-// argument check, one loop.
+// The table a compensated roll-out begins with: B rows from dist_state[:,0:6], set as mpcqp_set_disturbance sets its rows.
+int compensate_enter(mpcqp_handle h, const char* who, int64_t B, const double* dist_state, hipStream_t st) {
+  GUARD(h);
+  if (const int rc = reserve_disturbance(h, B, who)) return rc;
+  with_io(h, [&](auto tag) {
+    hipLaunchKernelGGL((mpcqp_compensate_enter_kernel<decltype(tag)>), blocks(B), dim3(256), 0, st, dist_state, h->dist_mem, B);
+  });
+  const int rc = launched(h, "compensate table kernel launch");
+  h->dist_B = rc == MPCQP_OK ? B : 0;
+  return rc;
+}
+
+// mpcqp_rollout_legs (dr = null), mpcqp_rollout_drive, mpcqp_rollout_slip (sl, with dr), mpcqp_rollout_observe (ob, with both) and
+// mpcqp_rollout_observe_compensated (cp, with all three): one argument check, one loop.
 int rollout_legs_run(mpcqp_handle h, const char* who, int64_t B, int32_t T, void* x, void* ref, void* feet, double* legs, const int32_t* gait,
                      const void* stand, const void* gain, int32_t* tick, const void* mu, const void* body, const void* push,
                      const int32_t* push_ticks, int32_t substeps, const void* step_height, const void* gains, int32_t leg_substeps,
                      const MpcQpLegGeometry* geo, const MpcQpLegInertia* inr, int32_t land, void* actual, void* desired, void* forces,
                      void* feet_log, uint8_t* contact_log, int32_t* solved, void* swing_log, void* q_log, void* qd_log, void* tau_log,
                      void* foot_log, void* err_log, uint8_t* flag_log, void* miss_log, void* stream, const RolloutDriveArgs* dr,
-                     const RolloutSlipArgs* sl = nullptr, const RolloutObserveArgs* ob = nullptr) {
+                     const RolloutSlipArgs* sl = nullptr, const RolloutObserveArgs* ob = nullptr,
+                     const RolloutCompensateArgs* cp = nullptr) {
   if (!h) return MPCQP_EINVAL;
   if (B < 0 || B > 0x7fffffff || T < 0 || B * (int64_t)T > 0x7fffffff) return bad(h, who, "size out of range");
   const int n = plant_substeps(substeps);
@@ -935,10 +969,16 @@ int rollout_legs_run(mpcqp_handle h, const char* who, int64_t B, int32_t T, void
   if (B > 0 && sl && (!dr->ground || !sl->foot_mass || !sl->slip)) return bad(h, who, "null buffer");
   if (B > 0 && ob && !ob->est_state) return bad(h, who, "null buffer");
   if (B > 0 && ob && ob->aid && !ob->att_state) return bad(h, who, "null att_state buffer");
+  if (B > 0 && cp && !cp->dist_state) return bad(h, who, "null dist_state buffer");
   LegGeoDev g;
   LegInrDev r;
   if (const int rc = leg_rows(h, who, geo, inr, true, g, r)) return rc;
   if (B == 0 || T == 0) return MPCQP_OK;
+  if (cp) {   // the call sets the disturbance table itself, once the other tables have passed: a call that is refused leaves it alone
+    if (const int rc = table_match(h, models(h), "model", B, who)) return rc;
+    if (const int rc = actuators_match(h, B, who)) return rc;
+    if (const int rc = compensate_enter(h, who, B, cp->dist_state, (hipStream_t)stream)) return rc;
+  }
   if (const int rc = solve_tables_match(h, B, who)) return rc;
   if (const int rc = actuators_match(h, B, who)) return rc;
   const int nl = swing_substeps(h->cfg.delta, leg_substeps);
@@ -954,6 +994,8 @@ int rollout_legs_run(mpcqp_handle h, const char* who, int64_t B, int32_t T, void
   // With the slip rule in the drive's place the log step waits until after the landing and moves the feet in the same launch: 7.
   // With the estimator (ob) its update runs in front of the expand and its predict between the slip rule and the legs step: 9; with
   // MPCQP_FEED_ESTIMATE the expand and the solve read the update's side buffers in place of x and feet.
+  // With the wrench observer (cp) its tick kernel runs in front of the advance, while x and feet are still the tick's: 10, the shift and
+  // add-back kernels of the table it keeps not counted (they are the solve's).
   const auto observe_in = [&](auto tag) {
     using TIO = decltype(tag);
     return ObsIn<TIO>{(const TIO*)ob->est_init, (const TIO*)ob->height, (const TIO*)ob->bias, (const TIO*)ob->noise, (const TIO*)ob->enc_noise};
@@ -1012,6 +1054,14 @@ int rollout_legs_run(mpcqp_handle h, const char* who, int64_t B, int32_t T, void
       if (dr && !sl && (tau_log || flag_log))
         hipLaunchKernelGGL((mpcqp_drive_log_kernel<TIO>), gl, nt, 0, st, gait, tick, dw.tau, dw.flag,
                            (int)(dr->drive == MPCQP_DRIVE_IDEAL && !dr->ground), B, (int)T, it, (TIO*)tau_log, flag_log);
+      if (cp) {   // the observer's row on the tick's operands and, every `hold` ticks and on the last, the robot's table row
+        const bool sensed = cp->source == MPCQP_WRENCH_SENSED, update = (it + 1) % cp->hold == 0 || it == T - 1;
+        const ObsWs<TIO> ow = observe_ws<TIO>(h->roll_mem, B, N);
+        hipLaunchKernelGGL((mpcqp_compensate_tick_kernel<TIO>), ga, nt, 0, st, sensed ? (const TIO*)ow.xhat : (const TIO*)xs,
+                           sensed ? (const TIO*)o.u : u, sensed ? (int64_t)N * 12 : (int64_t)Nu * 12, sensed ? (const TIO*)ow.feet : (const TIO*)feet,
+                           sensed ? (const double*)ob->est_state : (const double*)nullptr, (const TIO*)cp->obs_body, plant_model(h), cp->par,
+                           cp->dist_state, h->dist_mem, (TIO*)cp->dist_log, (TIO*)cp->resid_log, B, (int)T, it, update);
+      }
       hipLaunchKernelGGL((mpcqp_phase_advance_kernel<TIO>), ga, nt, 0, st, xs, rf, (TIO*)feet, ph, tick, plant_in<TIO>(h, plant), u, o.status, d, Nu, B,
                          (int)T, it, (TIO*)actual, (TIO*)desired, (TIO*)forces, (TIO*)feet_log, contact_log, solved);
       hipLaunchKernelGGL((mpcqp_legs_land_kernel<TIO>), gl, nt, 0, st, xs, (TIO*)feet, gait, tick, legs, g, (int)land, B, (int)T, it,
@@ -1128,11 +1178,13 @@ struct RolloutSlipCall {
 };
 
 // mpcqp_rollout_observe (gated = false), mpcqp_rollout_observe_gated and mpcqp_rollout_observe_aided (ad: whether the gate runs is its
-// flags'): the checks of what they add to mpcqp_rollout_slip, then its loop.
+// flags'): the checks of what they add to mpcqp_rollout_slip, then its loop.  cp: the checked arguments of
+// mpcqp_rollout_observe_compensated, which runs one of the three with the wrench observer in the loop.
 int rollout_observe_run(mpcqp_handle h, const char* who, const RolloutSlipCall& c, int32_t feed, double* est_state, const void* est_init,
                         const void* height, const void* bias, const void* noise, const void* enc_noise, const MpcQpEstimator* par,
                         void* imu_log, void* q_enc_log, void* qd_enc_log, void* est_log, void* feet_est_log, void* sigma_log, void* nis_log,
-                        bool gated, const MpcQpTrustGate* gate, void* trust_log, void* stream, const EstimateAidedArgs* ad = nullptr) {
+                        bool gated, const MpcQpTrustGate* gate, void* trust_log, void* stream, const EstimateAidedArgs* ad = nullptr,
+                        const RolloutCompensateArgs* cp = nullptr) {
   if (!h) return MPCQP_EINVAL;
   if (feed != MPCQP_FEED_TRUTH && feed != MPCQP_FEED_ESTIMATE) return bad(h, who, "feed is neither MPCQP_FEED_TRUTH nor MPCQP_FEED_ESTIMATE");
   RolloutObserveArgs ob = {feed, est_state, est_init, height, bias, noise, enc_noise, {}, imu_log, q_enc_log, qd_enc_log, est_log, feet_est_log,
@@ -1154,7 +1206,7 @@ int rollout_observe_run(mpcqp_handle h, const char* who, const RolloutSlipCall& 
   return rollout_legs_run(h, who, c.B, c.T, c.x, c.ref, c.feet, c.legs, c.gait, c.stand, c.gain, c.tick, c.mu, c.body, c.push, c.push_ticks,
                           c.substeps, c.step_height, c.gains, c.leg_substeps, c.geo, c.inr, c.land, c.actual, c.desired, c.forces, c.feet_log,
                           c.contact_log, c.solved, c.swing_log, c.q_log, c.qd_log, c.tau_log, c.foot_log, c.err_log, c.flag_log, c.miss_log,
-                          stream, &dr, &sl, &ob);
+                          stream, &dr, &sl, &ob, cp);
 }
 
 }  // namespace
@@ -1411,13 +1463,7 @@ int mpcqp_set_disturbance(mpcqp_handle h, int64_t B, const double* rows, void* s
   if (B <= 0 || B > 0x7fffffff) return fail(h, MPCQP_EINVAL, "mpcqp_set_disturbance: batch size out of range");
   if (!rows) return fail(h, MPCQP_EINVAL, "mpcqp_set_disturbance: null disturbance table");
   GUARD(h);
-  if (h->dist_cap < B) {   // the shifted-xdes buffer first: when it cannot be grown, the table set before stays
-    if (!grow(h->dshift_mem, (size_t)B * (h->cfg.N + 1) * 13 * io_size(h)))
-      return fail(h, MPCQP_ENOMEM, "mpcqp_set_disturbance: buffer allocation failed");
-    if (!table_reserve(disturbances(h), B, DIST_ROW)) {   // (the buffer is larger than the table's rows need: harmless)
-      return fail(h, MPCQP_ENOMEM, "mpcqp_set_disturbance: table allocation failed");
-    }
-  }
+  if (const int rc = reserve_disturbance(h, B, "mpcqp_set_disturbance")) return rc;
   hipLaunchKernelGGL(mpcqp_disturb_rows_kernel, blocks(B), dim3(256), 0, (hipStream_t)stream, rows, h->dist_mem, B);
   const int rc = launched(h, "disturbance table kernel launch");
   h->dist_B = rc == MPCQP_OK ? B : 0;
@@ -1908,6 +1954,52 @@ int mpcqp_rollout_observe_aided(mpcqp_handle h, int64_t B, int32_t T, void* x, v
   const EstimateAidedArgs ad = {flags, att, att_state, bias_log};
   return rollout_observe_run(h, "mpcqp_rollout_observe_aided", c, feed, est_state, est_init, height, bias, noise, enc_noise, par, imu_log,
                              q_enc_log, qd_enc_log, est_log, feet_est_log, sigma_log, nis_log, false, gate, trust_log, stream, &ad);
+}
+
+int mpcqp_default_compensate(MpcQpCompensate* comp) {
+  if (!comp) return MPCQP_EINVAL;
+  memset(comp, 0, sizeof(*comp));
+  comp->size = (uint32_t)sizeof(*comp);
+  comp->source = MPCQP_WRENCH_TRUTH;
+  comp->hold = 1;
+  return mpcqp_default_wrench_observer(&comp->observer);
+}
+
+int mpcqp_rollout_observe_compensated(mpcqp_handle h, int64_t B, int32_t T, void* x, void* ref, void* feet, double* legs, const int32_t* gait,
+                                      const void* stand, const void* gain, int32_t* tick, const void* mu, const void* body, const void* push,
+                                      const int32_t* push_ticks, int32_t substeps, const void* step_height, const void* gains,
+                                      int32_t leg_substeps, const MpcQpLegGeometry* geo, const MpcQpLegInertia* inr, int32_t land, int32_t drive,
+                                      const void* ground, const void* foot_mass, double* slip, void* actual, void* desired, void* forces,
+                                      void* feet_log, uint8_t* contact_log, int32_t* solved, void* swing_log, void* q_log, void* qd_log,
+                                      void* tau_log, void* foot_log, void* err_log, uint8_t* flag_log, void* miss_log, void* cmd_log,
+                                      double* slip_log, void* disp_log, int32_t feed, double* est_state, const void* est_init, const void* height,
+                                      const void* bias, const void* noise, const void* enc_noise, const MpcQpEstimator* par, void* imu_log,
+                                      void* q_enc_log, void* qd_enc_log, void* est_log, void* feet_est_log, void* sigma_log, void* nis_log,
+                                      const MpcQpTrustGate* gate, void* trust_log, int32_t flags, const MpcQpAttitude* att, double* att_state,
+                                      void* bias_log, const MpcQpCompensate* comp, const void* obs_body, double* dist_state, void* dist_log,
+                                      void* resid_log, void* stream) {
+  const char* who = "mpcqp_rollout_observe_compensated";
+  if (!h) return MPCQP_EINVAL;
+  MpcQpCompensate dflt;
+  if (!comp) { (void)mpcqp_default_compensate(&dflt); comp = &dflt; }
+  if (comp->size != sizeof(MpcQpCompensate)) return bad(h, who, "compensate struct size mismatch");
+  if (comp->flags & ~(uint32_t)(MPCQP_COMP_GATED | MPCQP_COMP_AIDED)) return bad(h, who, "compensate: flags has a bit other than MPCQP_COMP_GATED and MPCQP_COMP_AIDED");
+  if (comp->source != MPCQP_WRENCH_TRUTH && comp->source != MPCQP_WRENCH_SENSED)
+    return bad(h, who, "compensate: source is neither MPCQP_WRENCH_TRUTH nor MPCQP_WRENCH_SENSED");
+  if (comp->hold < 1) return bad(h, who, "compensate: hold must be at least 1");
+  RolloutCompensateArgs cp = {comp->source, comp->hold, {}, obs_body, dist_state, dist_log, resid_log};
+  if (const int rc = observer_row(h, who, &comp->observer, cp.par)) return rc;
+  const RolloutSlipCall c = {B, T, x, ref, feet, legs, gait, stand, gain, tick, mu, body, push, push_ticks, substeps, step_height, gains,
+                             leg_substeps, geo, inr, land, drive, ground, foot_mass, slip, actual, desired, forces, feet_log, contact_log,
+                             solved, swing_log, q_log, qd_log, tau_log, foot_log, err_log, flag_log, miss_log, cmd_log, slip_log, disp_log};
+  const bool gated = (comp->flags & MPCQP_COMP_GATED) != 0;
+  if (comp->flags & MPCQP_COMP_AIDED) {
+    const EstimateAidedArgs ad = {gated ? (flags | MPCQP_AIDED_GATE) : flags, att, att_state, bias_log};
+    return rollout_observe_run(h, who, c, feed, est_state, est_init, height, bias, noise, enc_noise, par, imu_log, q_enc_log, qd_enc_log, est_log,
+                               feet_est_log, sigma_log, nis_log, true, gate, trust_log, stream, &ad, &cp);
+  }
+  return rollout_observe_run(h, who, c, feed, est_state, est_init, height, bias, noise, enc_noise, par, imu_log, q_enc_log, qd_enc_log, est_log,
+                             feet_est_log, sigma_log, nis_log, gated, gate, gated ? trust_log : nullptr, stream, nullptr, &cp);
 }
 
 int mpcqp_rollout_observe_gated(mpcqp_handle h, int64_t B, int32_t T, void* x, void* ref, void* feet, double* legs, const int32_t* gait,

@@ -6,7 +6,8 @@ s[k+1] = Ad s[k] + Cd the disturbed QP is the undisturbed one with xdes - s in t
 plus s.  ``shift_host`` forms s by that recursion with explicit 13 x 13 matrices -- the device writes the closed form --,
 ``DisturbedEngine`` wraps a checker handle so that every host roll-out of ``gaits`` and ``plant`` runs with a table unchanged,
 ``disturbance_track_host`` is the observer in the device's operation order, and ``compensated_rollout`` closes the loop between the
-two piece by piece, on either side.
+two piece by piece, on either side.  ``rollout_compensated_host`` is that loop over ``gaits.rollout_observe_host``: the host counterpart of
+mpcqp_rollout_observe_compensated (include/mpcqp_compensate.h), where the device runs the observer inside the roll-out's tick.
 """
 from __future__ import annotations
 
@@ -58,6 +59,42 @@ def observer_struct(observer):
     for k, v in row.items():
         setattr(par, k, v)
     return par
+
+
+SOURCES = {"truth": _capi.WRENCH_TRUTH, "sensed": _capi.WRENCH_SENSED}
+COMPENSATE_DEFAULTS = {"source": "truth", "hold": 1, "body": None}     # what a `compensate` dict has besides the observer's fields
+
+
+def compensate_row(**kw):
+    """A `compensate` dict in full: `observer_row`'s fields (checked there), "source" ("truth" or "sensed"; an int goes to the library as
+    it is), "hold" (>= 1) and "body" ([B,7], the body the observer believes, or None: the handle's model)."""
+    unknown = set(kw) - set(OBSERVER_DEFAULTS) - set(COMPENSATE_DEFAULTS)
+    if unknown:
+        raise ValueError(f"compensate has no field {sorted(unknown)}; the fields are {tuple(OBSERVER_DEFAULTS) + tuple(COMPENSATE_DEFAULTS)}")
+    row = {**COMPENSATE_DEFAULTS, **{k: kw[k] for k in COMPENSATE_DEFAULTS if k in kw}}
+    if not isinstance(row["source"], int) and row["source"] not in SOURCES:
+        raise ValueError(f"source must be 'truth' or 'sensed', got {row['source']!r}")
+    if int(row["hold"]) != row["hold"] or row["hold"] < 1:
+        raise ValueError(f"hold must be a whole number >= 1, got {row['hold']!r}")
+    row["hold"] = int(row["hold"])
+    return {**observer_row(**{k: v for k, v in kw.items() if k in OBSERVER_DEFAULTS}), **row}
+
+
+def compensate_struct(compensate, gated=False, aided=False):
+    """A `compensate` dict ({} = the defaults) or an MpcQpCompensate -> (the structure the binding passes, with the flags of the
+    estimator variant that runs, and the observer's body or None).  A structure is passed as it is: the library checks it."""
+    if isinstance(compensate, _capi.MpcQpCompensate):
+        return compensate, None
+    row = compensate_row(**compensate)
+    par = _capi.MpcQpCompensate()
+    par.size = _capi.ctypes.sizeof(_capi.MpcQpCompensate)
+    par.flags = (_capi.COMP_GATED if gated else 0) | (_capi.COMP_AIDED if aided else 0)
+    par.source = row["source"] if isinstance(row["source"], int) else SOURCES[row["source"]]
+    par.hold = row["hold"]
+    par.observer.size = _capi.ctypes.sizeof(_capi.MpcQpWrenchObserver)
+    for k in OBSERVER_DEFAULTS:
+        setattr(par.observer, k, row[k])
+    return par, row["body"]
 
 
 def offsets_host(x0, rows, cfg, models=None):
@@ -246,3 +283,57 @@ def _join(pieces):
         else:
             out[k] = vals[-1]
     return out
+
+
+SENSED_LOGS = {"actual": "est", "forces": "cmd", "feet_log": "feet_est"}      # what the observer reads of `rollout_observe`'s logs
+
+
+def sensed_logs(logs):
+    """The logs of a `rollout_observe` under the names the observer reads: what a robot has in the place of the plant's truth."""
+    return {k: logs[src] for k, src in SENSED_LOGS.items()}
+
+
+def rollout_compensated_host(oracle_engine, x, ref, feet, legs, gait, stand, gain, tick, mu, T, step_height, ground, foot_mass, compensate=None,
+                             dist_state=None, slip=None, est_state=None, att_state=None, noise=None, enc_noise=None, models=None, **kw):
+    """mpcqp_rollout_observe_compensated (include/mpcqp_compensate.h, which has the rule) on the CPU checker, composed from what
+    exists and nothing else: `compensated_rollout` at piece = hold over `gaits.rollout_observe_host` on a `DisturbedEngine` whose rows
+    start from dist_state[:, :6], with `disturbance_track_host` on the truth logs (source "truth") or on "est", "cmd" and "feet_est"
+    (source "sensed").  `compensate`: None or a dict as `compensate_row` takes it; dist_state [B,40] or None (a fresh observer);
+    slip, est_state, att_state, noise [B,T,6], enc_noise [B,T,4,6] and every keyword of `rollout_observe_host` as there (the noise
+    rows are cut to each piece); `models` as `DisturbedEngine` takes it.  Nothing is modified in place.  Returns
+    `rollout_observe_host`'s dict for the T ticks plus "dist", "resid" [B,T,6] and "dist_state" [B,40]."""
+    from . import gaits
+    row = compensate_row(**(compensate or {}))
+    if isinstance(row["source"], int) and row["source"] not in SOURCES.values():
+        raise ValueError(f"source must be 'truth' or 'sensed', got {row['source']!r}")
+    sensed = row["source"] in ("sensed", _capi.WRENCH_SENSED)
+    B, T = np.asarray(x).shape[0], int(T)
+    state = np.zeros((B, STATE)) if dist_state is None else _f64(dist_state).reshape(B, STATE).copy()
+    eng = DisturbedEngine(oracle_engine, state[:, :ROW], models)
+    st = {"x": _f64(x), "ref": _f64(ref), "feet": _f64(feet), "legs": _f64(legs), "tick": np.asarray(tick, np.int32), "slip": slip,
+          "est_state": est_state, "att_state": att_state}
+    done, pieces = [0], []
+
+    def step(n):
+        cut = lambda a: None if a is None else _f64(a)[:, done[0]:done[0] + n]
+        carried = {k: st[k] for k in ("slip", "est_state")}
+        if kw.get("attitude") is not None:
+            carried["att_state"] = st["att_state"]
+        o = gaits.rollout_observe_host(eng, st["x"], st["ref"], st["feet"], st["legs"], gait, stand, gain, st["tick"], mu, n, step_height, ground,
+                                       foot_mass, noise=cut(noise), enc_noise=cut(enc_noise), **carried, **kw)
+        st.update({k: o[k] for k in st if k in o})
+        done[0] += n
+        pieces.append(o)
+        return o
+
+    obs = {k: row[k] for k in OBSERVER_DEFAULTS}
+    track = lambda logs, s: disturbance_track_host(sensed_logs(logs) if sensed else logs, eng.cfg, body=row["body"], observer=obs, state=s)
+    out = compensated_rollout(step, T, row["hold"], track, eng.set_rows, state)
+    if not pieces:
+        step(0)
+    # (`compensated_rollout` joins the logs it knows by name; a leg roll-out's dict has more: every key but the carried state is a log)
+    carried = ("x", "ref", "tick", "feet", "legs", "slip", "est_state", "att_state")
+    logs = {k: pieces[-1][k] if k in carried else (sum(p[k] for p in pieces) if k == "solved" else np.concatenate([p[k] for p in pieces], axis=1))
+            for k in pieces[-1]}
+    return {**logs, "dist": np.zeros((B, 0, ROW)) if out["dist"] is None else out["dist"],
+            "resid": np.zeros((B, 0, ROW)) if out["resid"] is None else out["resid"], "dist_state": out["state"]}

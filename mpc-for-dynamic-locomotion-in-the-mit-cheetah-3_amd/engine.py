@@ -709,7 +709,7 @@ class MPCBatch:
     def rollout_observe(self, x, ref, feet, legs, gait, stand, gain, tick, mu, T, step_height, ground, foot_mass, slip, est_state,
                         feed="estimate", est_init=None, height=None, bias=None, noise=None, enc_noise=None, estimator=None, land="rule",
                         drive="limited", body=None, push=None, push_ticks=None, substeps=10, gains=None, leg_substeps=0, inertia=None,
-                        geometry=None, log=True, stream=None, gate=None, attitude=None, att_state=None):
+                        geometry=None, log=True, stream=None, gate=None, attitude=None, att_state=None, compensate=None, dist_state=None):
         """`rollout_slip` with sensors and the state estimator inside the tick loop (include/mpcqp_observe.h, mpcqp_rollout_observe,
         which has the rule; the host counterpart is gaits.rollout_observe_host): per tick the encoders and the IMU are read off the
         live state, one row of `estimate_track` runs on est_state float64 [B,131] (state next to `x`, ..., `slip`, advanced IN PLACE;
@@ -724,11 +724,21 @@ class MPCBatch:
         dict of estimator.attitude_row's fields ({} = the defaults) or an MpcQpAttitude for mpcqp_rollout_observe_aided
         (include/mpcqp_attitude.h): the velocity update's correction steers the orientation and a gyro-bias state; att_state float64
         [B,8] is state like est_state, advanced IN PLACE (None: a fresh zero one), and the dict gains "gyro_bias" [B,T,3] and
-        "att_state".  Asynchronous on `stream`."""
+        "att_state".  compensate: None (today's call through today's entry points), or a dict for
+        mpcqp_rollout_observe_compensated (include/mpcqp_compensate.h, which has the rule; the host counterpart is
+        disturbance.rollout_compensated_host): the wrench observer of `disturbance_track` runs inside the tick and every `hold` ticks its
+        estimate becomes the engine's disturbance table.  The dict has disturbance.observer_row's fields plus "source" ("truth": the
+        observer reads x, the applied forces and the feet; "sensed": the estimate, the commanded forces and the estimated feet), "hold"
+        (1) and "body" ([B,7], the body the observer believes, or None: the engine's model); {} = the defaults.  dist_state float64
+        [B,40] is the observer's state, advanced IN PLACE (None: a fresh zero one); the dict gains "dist", "resid" [B,T,6] and
+        "dist_state".  The call sets the engine's disturbance table from dist_state[:, :6] and leaves it set (`clear_disturbance`).
+        Asynchronous on `stream`."""
         from . import estimator as _est
         B, T, f64 = int(x.shape[0]), int(T), _torch().float64
         if attitude is None and att_state is not None:
             raise ValueError("att_state needs attitude")
+        if compensate is None and dist_state is not None:
+            raise ValueError("dist_state needs compensate")
         feeds = {"truth": _capi.FEED_TRUTH, "estimate": _capi.FEED_ESTIMATE}
         if not isinstance(feed, int) and feed not in feeds:
             raise ValueError(f"feed must be 'truth' or 'estimate', got {feed!r}")
@@ -741,12 +751,23 @@ class MPCBatch:
                 _ptr(enc_noise), _est.estimator_struct(estimator))
         leg3 = ((4, 3), self.tdtype)
         call, more = self.engine.rollout_observe_ptr, ()
-        if attitude is not None:
-            if att_state is None:
-                att_state, = self._alloc(stream, ((B, _capi.ATT_STATE), f64, True))
+        if attitude is not None and att_state is None:
+            att_state, = self._alloc(stream, ((B, _capi.ATT_STATE), f64, True))
+        aided = (None if gate is None else _est.gate_struct(gate), 0 if gate is None else _capi.AIDED_GATE,
+                 None if attitude is None else _est.attitude_struct(attitude), _ptr(att_state))
+        if compensate is not None:
+            from . import disturbance as _dist
+            comp, obs_body = _dist.compensate_struct(compensate, gated=gate is not None, aided=attitude is not None)
+            check_operands(self.device, (("compensate body", obs_body, (B, 7), self.tdtype), ("dist_state", dist_state, (B, _capi.DIST_STATE), f64)),
+                           optional=("compensate body", "dist_state"))
+            if dist_state is None:
+                dist_state, = self._alloc(stream, ((B, _capi.DIST_STATE), f64, True))
+            call = self.engine.rollout_observe_compensated_ptr
+            more = (("trust", (4,), self.tdtype), ("gyro_bias", (3,), self.tdtype), ("dist", (6,), self.tdtype), ("resid", (6,), self.tdtype))
+            tail += aided + (comp, _ptr(obs_body), dist_state.data_ptr())
+        elif attitude is not None:
             call, more = self.engine.rollout_observe_aided_ptr, (("trust", (4,), self.tdtype), ("gyro_bias", (3,), self.tdtype))
-            tail += (None if gate is None else _est.gate_struct(gate), 0 if gate is None else _capi.AIDED_GATE,
-                     _est.attitude_struct(attitude), att_state.data_ptr())
+            tail += aided
         elif gate is not None:
             call, more, tail = self.engine.rollout_observe_gated_ptr, (("trust", (4,), self.tdtype),), tail + (_est.gate_struct(gate),)
         out = self._rollout_legs(call, x, ref, feet, legs, gait, stand, gain, tick, mu, T, step_height, land, body, push, push_ticks, substeps,
@@ -758,8 +779,12 @@ class MPCBatch:
                                         ("feet_est", *leg3), ("sigma", (6,), self.tdtype), ("nis", (), self.tdtype)) + more, tail=tail)
         if attitude is not None:
             out["att_state"] = att_state
-            if gate is None:
-                del out["trust"]
+        if compensate is not None:
+            out["dist_state"] = dist_state
+        if "trust" in out and gate is None:
+            del out["trust"]
+        if "gyro_bias" in out and attitude is None:
+            del out["gyro_bias"]
         return out
 
     def score(self, logs, score=None, rule=None, stream=None):
